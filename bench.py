@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: render + loss + backward iterations per second.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 N = 1 (default): BASELINE.json configs[2] -- 500k Gaussians, 1920x1080, one tracking iteration per
 step: render(viewpoint, gaussians, pipe, bg) -> get_loss_tracking -> backward, with gradients to
@@ -22,6 +22,12 @@ Rank 0 prints ONE JSON line.  `value` is whole-job iterations/s with all inputs 
 `roofline` prices the dominant kernel (by HIP-event time measured here) against the 8 TB/s HBM
 peak with the algorithmic byte count of SURVEY.md section 8(d); `cpu_baseline` times the CPU oracle
 (a scalar C port, 1 core) on one iteration of the same scene.
+
+`--dump-outputs DIR`: rank 0 writes what the LAST timed step computed -- the arrays a caller of the timed path receives --
+as DIR/<name>.npy (float32; integers and float64 tensors as float64), at most 64 MB in all: where the whole arrays do not fit,
+per-Gaussian arrays and images are cut to fixed seeded samples of rows / pixels sized to the budget (their indices:
+DIR/gaussian_rows.npy, DIR/pixel_index.npy).  The inputs are seeded, so two builds run with the same arguments can be compared
+output for output.  bench_outputs/ is git-ignored for the purpose (`--dump-outputs bench_outputs/<name>`).
 """
 import argparse
 import gc
@@ -69,6 +75,107 @@ def algorithmic_bytes(kernel, N, V, D, P, T):
         "preprocess_bwd": 56 * N + 92 * V + 56 * N + 12 * N + 24,
     }
     return table.get(kernel)
+
+
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: all files together, headers included (64 MB)
+DUMP_IMAGE_SHARE = 0.75        # images: whole while they fit in this share of the budget (or in what the Gaussians leave), else sampled
+DUMP_HEADER_BYTES = 256        # what one .npy header may take (numpy pads it to 128 bytes; long shapes to 192)
+
+
+def _dump_itemsize(t):
+    return 4 if t.dtype in (torch.float32, torch.float16, torch.bfloat16) else 8
+
+
+def snapshot_outputs(entries, N, H, W, dev, limit=None):
+    """Copies, on the device, of the last timed step's outputs.  ``entries``: (name, tensor, kind) with kind "gaussian" (leading
+    dimension N), "image" (trailing dimensions H, W) or "small" (written whole).  Where everything does not fit in ``limit`` bytes
+    (default DUMP_LIMIT_BYTES), images keep up to DUMP_IMAGE_SHARE of what the small arrays leave and the per-Gaussian arrays the rest:
+    each kind is cut to a fixed seeded sample of rows / pixels sized to its share, and the sample's indices are written beside it
+    (gaussian_rows, pixel_index; counted in the share).  Taken right after the timed region, before anything else runs the step
+    again; written by write_outputs."""
+    import numpy as np
+    limit = DUMP_LIMIT_BYTES if limit is None else limit
+    entries = [(n, t.detach(), k) for n, t, k in entries if t is not None and t.numel() > 0]
+    small = sum(t.numel() * _dump_itemsize(t) for _, t, k in entries if k == "small")
+    per_row = sum(t.numel() // N * _dump_itemsize(t) for _, t, k in entries if k == "gaussian")
+    per_pix = sum(t.numel() // (H * W) * _dump_itemsize(t) for _, t, k in entries if k == "image")
+    budget = limit - small - DUMP_HEADER_BYTES * (len(entries) + 2)
+    if budget <= 0:
+        raise ValueError(f"--dump-outputs: the whole arrays alone take {small} bytes of the {limit}")
+    rows = pix = None
+    if N * per_row + H * W * per_pix > budget:
+        img_budget = min(H * W * per_pix, max(int(DUMP_IMAGE_SHARE * budget), budget - N * per_row))
+        if img_budget < H * W * per_pix:   # sampled: 8 bytes of index per pixel
+            pix = min(H * W, img_budget // (per_pix + 8))
+            img_budget = pix * (per_pix + 8)
+        if N * per_row > budget - img_budget:
+            rows = min(N, (budget - img_budget) // (per_row + 8))
+    snap = {}
+    if rows is not None:
+        rows = np.sort(np.random.default_rng(0).choice(N, rows, replace=False))
+        snap["gaussian_rows"] = torch.from_numpy(rows).to(torch.float64)
+        rows = torch.from_numpy(rows).to(dev)
+    if pix is not None:
+        pix = np.sort(np.random.default_rng(1).choice(H * W, pix, replace=False))
+        snap["pixel_index"] = torch.from_numpy(pix).to(torch.float64)
+        pix = torch.from_numpy(pix).to(dev)
+    for name, t, kind in entries:
+        if kind == "gaussian" and rows is not None:
+            t = t.index_select(0, rows)
+        elif kind == "image" and pix is not None:
+            t = t.reshape(-1, H * W).index_select(1, pix)
+        snap[name] = t.clone()
+    return snap
+
+
+def dump_entries(cam, session=None, last=None, params=None, pose_params=None, backend=None, window=None):
+    """(name, tensor, kind) of what the timed step hands its caller, for snapshot_outputs: the TrackingSession's render, loss,
+    gradients and stepped pose (``session``); the autograd step's render package, loss and the parameters' .grad (``last``, with
+    ``params`` / ``pose_params``); else the mapping iteration's updated Gaussians and window keyframes (``backend``, ``window``)."""
+    if session is not None:
+        s = session
+        return [("color", s.color, "image"), ("depth", s.depth, "image"), ("opacity", s.opacity, "image"),
+                ("radii", s.radii, "gaussian"), ("n_touched", s.n_touched, "gaussian"), ("loss", s.loss, "small"),
+                ("grad_means3D", s.d_m3, "gaussian"), ("grad_means2D", s.d_m2, "gaussian"), ("grad_opacities", s.d_op, "gaussian"),
+                ("grad_scales", s.d_sc, "gaussian"), ("grad_rotations", s.d_rot, "gaussian"), ("grad_shs", s.d_sh, "gaussian"),
+                ("grad_tau", s.d_tau, "small"), ("grad_exposure_a", s.d_a, "small"), ("grad_exposure_b", s.d_b, "small"),
+                ("R", s.R, "small"), ("T", s.T, "small"), ("viewmatrix", s.view, "small"), ("projmatrix", s.proj, "small"),
+                ("campos", s.campos, "small"), ("cam_rot_delta", cam.cam_rot_delta, "small"),
+                ("cam_trans_delta", cam.cam_trans_delta, "small"), ("exposure_a", cam.exposure_a, "small"),
+                ("exposure_b", cam.exposure_b, "small")]
+    if last is not None:
+        pkg = last["pkg"]
+        out = [("color", pkg["render"], "image"), ("depth", pkg["depth"], "image"), ("opacity", pkg["opacity"], "image"),
+               ("radii", pkg["radii"], "gaussian"), ("loss", last["loss"], "small")]
+        names = ("xyz", "features_dc", "features_rest", "scaling", "rotation", "opacity")
+        out += [("grad_" + n, p.grad, "gaussian") for n, p in zip(names, params)]
+        out += [("grad_" + n, p.grad, "small") for n, p in zip(("cam_rot_delta", "cam_trans_delta", "exposure_a", "exposure_b"), pose_params)]
+        return out
+    m = backend.gaussians
+    out = [("xyz", m._xyz, "gaussian"), ("features_dc", m._features_dc, "gaussian"), ("features_rest", m._features_rest, "gaussian"),
+           ("scaling", m._scaling, "gaussian"), ("rotation", m._rotation, "gaussian"), ("opacity", m._opacity, "gaussian"),
+           ("max_radii2D", m.max_radii2D, "gaussian"), ("xyz_gradient_accum", m.xyz_gradient_accum, "gaussian"),
+           ("denom", m.denom, "gaussian")]
+    for kf in window:
+        vp = backend.viewpoints[kf]
+        out += [(f"kf{kf}_{n}", getattr(vp, n), "small") for n in ("R", "T", "exposure_a", "exposure_b")]
+    return out
+
+
+def write_outputs(directory, snap):
+    """DIR/<name>.npy for every snapshot entry: float32, or float64 for integer and float64 tensors."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {}
+    for name, t in snap.items():
+        dt = np.float32 if t.dtype in (torch.float32, torch.float16, torch.bfloat16) else np.float64
+        arrays[name] = t.cpu().to(torch.float64 if dt is np.float64 else torch.float32).numpy().astype(dt, copy=False)
+    total = 0
+    for name, a in arrays.items():
+        path = os.path.join(directory, name + ".npy")
+        np.save(path, a)
+        total += os.path.getsize(path)
+    return {"dir": directory, "files": len(arrays), "bytes": int(total)}
 
 
 def build_scene(workload, rank, dev):
@@ -175,6 +282,9 @@ def main():
                          "the product's tracking loop (fast_tracking.TrackingSession: render, tracking loss, backward, pose "
                          "optimiser step -- three C-ABI calls, no autograd); tracking-autograd: render() -> "
                          "get_loss_tracking -> backward through the public autograd API, without the optimiser step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, <= 64 MB in all; rank 0); "
+                         "bench_outputs/<name> is git-ignored")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -275,11 +385,16 @@ def main():
         # its rate is printed beside the headline: config.pose_only_iters_per_s.)
         session = TrackingSession(cam, model, CONFIG, pipe, bg, gaussian_gradients=not args.pose_only)
 
+    last = {}   # the autograd step's render package and loss (what --dump-outputs writes)
+
     def autograd_step():
         for p in params + pose_params:
             p.grad = None
         pkg = render(cam, model, pipe, bg)
-        slam_utils.get_loss_tracking(CONFIG, pkg["render"], pkg["depth"], pkg["opacity"], cam).backward()
+        loss = slam_utils.get_loss_tracking(CONFIG, pkg["render"], pkg["depth"], pkg["opacity"], cam)
+        loss.backward()
+        if args.dump_outputs:
+            last["pkg"], last["loss"] = pkg, loss
         return pkg["radii"]
 
     def step():
@@ -317,6 +432,12 @@ def main():
         radii = step()
     sync()
     elapsed = time.perf_counter() - t0
+    dump_snap = None
+    if args.dump_outputs and rank == 0:
+        ent = (dump_entries(cam, session=session) if session is not None else
+               dump_entries(cam, last=last, params=params, pose_params=pose_params) if tracking else
+               dump_entries(cam, backend=backend, window=window))
+        dump_snap = snapshot_outputs(ent, N, H, W, dev)
     if session is not None:
         stats["D"] = int(session.num_rendered)
     elif backend is not None and getattr(backend, "_lvdgs_view_pass", None) is not None:
@@ -582,6 +703,8 @@ def main():
             "roofline": roofline, "cpu_baseline": cpu_baseline, "steady_state": steady,
             "kernels_us_per_step": {k: round(v["us_per_step"], 2) for k, v in kernels.items()},
         }
+        if dump_snap is not None:
+            out["dump_outputs"] = write_outputs(args.dump_outputs, dump_snap)
         # the loops as a system, once more at the END of the line in short (a record that keeps only the line's tail still shows it):
         # config.side.sequence_kitti07_geom has the full entry
         sq = (side or {}).get("sequence_kitti07_geom")

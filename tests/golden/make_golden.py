@@ -17,6 +17,10 @@ Fixtures:
   loss_mapping.npz   utils/slam_utils.py:82-121  get_loss_mapping (+ grads)
   median_depth.npz   utils/slam_utils.py:124-134 get_median_depth
   config_07.json     utils/config_utils.py:4-50  merged KITTI-07 config
+  dropin_reference.json  utils/camera_utils.py / utils/slam_backend.py loaded through lvd_gs-slam_amd/dropin:
+                     the Camera's matrices, the objects the back end's imports resolve to, BackEnd.set_hyperparams / reset
+
+`python -B tests/golden/make_golden.py dropin` writes dropin_reference.json alone.
 """
 import json
 import os
@@ -185,6 +189,61 @@ def gen_config():
         json.dump(cfg, f, indent=1, sort_keys=True)
 
 
+DROPIN_CAMERA = dict(fx=700.0, fy=710.0, cx=600.0, cy=180.0, W=1226, H=370, FoVx=1.4, FoVy=0.5,
+                     tau=[0.1, -0.2, 0.3, 0.05, 0.02, -0.04])
+
+
+def gen_dropin():
+    """The reference's own Camera and BackEnd, imported with the drop-in shim on the path (their gaussian_splatting imports
+    resolve to lvdgs): what tests/test_dropin.py checks the build's Camera / shim / GaussianModel against."""
+    import types
+    root = os.path.dirname(os.path.dirname(HERE))
+    sys.path.insert(0, root)
+    import lvdgs  # noqa: F401
+    sys.path.insert(0, os.path.join(root, "lvd_gs-slam_amd", "dropin"))
+    from lvdgs.graphics_utils import getProjectionMatrix2
+    from lvdgs.pose_utils import SE3_exp
+    ref_cam = __import__("utils.camera_utils", fromlist=["Camera"])
+    c = DROPIN_CAMERA
+    proj = getProjectionMatrix2(znear=0.01, zfar=100.0, fx=c["fx"], fy=c["fy"], cx=c["cx"], cy=c["cy"], W=c["W"], H=c["H"]).transpose(0, 1)
+    cam = ref_cam.Camera(0, torch.rand(3, 8, 8), None, None, torch.eye(4), proj, c["fx"], c["fy"], c["cx"], c["cy"], c["FoVx"], c["FoVy"],
+                         c["H"], c["W"], device="cpu")
+    T = SE3_exp(torch.tensor(c["tau"]))
+    cam.update_RT(T[:3, :3], T[:3, 3])
+    out = {"camera": {"inputs": c, **{n: getattr(cam, n).tolist() for n in ("world_view_transform", "full_proj_transform", "camera_center")},
+                      "parameter_names": sorted(n for n, _ in cam.named_parameters())}}
+    stub = types.ModuleType("utils.init_pose")   # (MASt3R + cv2: not importable here)
+    stub.save_depth_comparison = lambda *a, **k: None
+    sys.modules["utils.init_pose"] = stub
+    backend = __import__("utils.slam_backend", fromlist=["BackEnd"])
+    name = lambda o: o.__module__ + "." + o.__qualname__
+    out["backend_imports"] = {n: name(getattr(backend, n)) for n in ("render", "l1_loss", "ssim", "getProjectionMatrix2", "getWorld2View2")}
+    cfg = json.load(open(os.path.join(HERE, "config_07.json")))
+    cfg["Training"]["monocular"] = cfg["Dataset"]["sensor_type"] == "monocular"
+    be = backend.BackEnd(cfg)
+    be.cameras_extent = 6.0
+    be.set_hyperparams()
+    out["backend_hyperparams"] = {"cameras_extent": 6.0, **{n: getattr(be, n) for n in (
+        "window_size", "gaussian_extent", "init_gaussian_extent", "init_itr_num", "mapping_itr_num", "gaussian_update_every",
+        "gaussian_update_offset", "gaussian_th", "gaussian_reset", "size_threshold")}}
+    from gaussian_splatting.scene.gaussian_model import GaussianModel
+    g = GaussianModel.from_activated(torch.rand(9, 3), torch.rand(9, 3) + 0.1, torch.nn.functional.normalize(torch.randn(9, 4)),
+                                     torch.rand(9, 1), colors=torch.rand(9, 3), device="cpu")
+    g.init_lr(6.0)
+    g.training_setup(cfg["opt_params"])
+    be.gaussians = g
+    be.backend_queue = types.SimpleNamespace(empty=lambda: True)
+    be.reset()
+    out["backend_reset"] = {"gaussians_before": 9, "gaussians_after": int(g.get_xyz.shape[0]), "iteration_count": be.iteration_count,
+                            "current_window": be.current_window, "initialized": be.initialized}
+    with open(os.path.join(HERE, "dropin_reference.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+
+
 if __name__ == "__main__":
-    gen_se3(); gen_update_pose(); gen_losses(); gen_median(); gen_config()
+    if sys.argv[1:] == ["dropin"]:
+        gen_dropin()
+        print("golden fixture written to", os.path.join(HERE, "dropin_reference.json"))
+        sys.exit(0)
+    gen_se3(); gen_update_pose(); gen_losses(); gen_median(); gen_config(); gen_dropin()
     print("golden fixtures written to", HERE)

@@ -1,9 +1,9 @@
-"""The import names the reference's files use resolve to the lvdgs implementation, and the reference's
-own utils/camera_utils.py (which needs gaussian_splatting.utils.graphics_utils) becomes importable."""
+"""The import names the reference's files use resolve to the lvdgs implementation, and what the reference's own
+utils/camera_utils.py and utils/slam_backend.py did when loaded through the shim (tests/golden/dropin_reference.json,
+written by tests/golden/make_golden.py) is what the build's Camera, shim and GaussianModel give."""
+import json
 import os
-import sys
 
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DROPIN = os.path.join(ROOT, "lvd_gs-slam_amd", "dropin")
@@ -26,76 +26,73 @@ def test_shim_names_resolve(monkeypatch):
     assert getWorld2View2.__module__ == "lvdgs.graphics_utils"
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/utils"), reason="reference checkout not present on this box")
+def _reference():
+    """What the reference's own Camera and BackEnd did when loaded through the shim (tests/golden/make_golden.py gen_dropin)."""
+    return json.load(open(os.path.join(ROOT, "tests", "golden", "dropin_reference.json")))
+
+
 def test_reference_camera_imports_through_the_shim(monkeypatch):
-    """utils/camera_utils.py:4 imports gaussian_splatting.utils.graphics_utils; with the shim on the path the
-    reference's own Camera class loads and produces the same matrices as the mirror."""
+    """utils/camera_utils.py:4 imports gaussian_splatting.utils.graphics_utils; with the shim on the path that import resolves, and
+    the reference's own Camera class, loaded through it, produced the matrices and parameters the mirror produces."""
     import importlib
     import torch
     monkeypatch.syspath_prepend(DROPIN)
-    monkeypatch.syspath_prepend("/root/reference")
-    monkeypatch.setattr(sys, "dont_write_bytecode", True)
-    for m in [k for k in sys.modules if k == "utils" or k.startswith("utils.")]:
-        monkeypatch.delitem(sys.modules, m)
-    ref_cam = importlib.import_module("utils.camera_utils")
+    gu = importlib.import_module("gaussian_splatting.utils.graphics_utils")
+    assert callable(gu.getProjectionMatrix2) and callable(gu.getWorld2View2)
     from lvdgs.camera_utils import Camera
-    from lvdgs.graphics_utils import getProjectionMatrix2
     from lvdgs.pose_utils import SE3_exp
-    proj = getProjectionMatrix2(znear=0.01, zfar=100.0, fx=700.0, fy=710.0, cx=600.0, cy=180.0, W=1226, H=370).transpose(0, 1)
-    args = (0, torch.rand(3, 8, 8), None, None, torch.eye(4), proj, 700.0, 710.0, 600.0, 180.0, 1.4, 0.5, 370, 1226)
-    a, b = ref_cam.Camera(*args, device="cpu"), Camera(*args, device="cpu")
-    T = SE3_exp(torch.tensor([0.1, -0.2, 0.3, 0.05, 0.02, -0.04]))
-    a.update_RT(T[:3, :3], T[:3, 3])
+    ref = _reference()["camera"]
+    c = ref["inputs"]
+    proj = gu.getProjectionMatrix2(znear=0.01, zfar=100.0, fx=c["fx"], fy=c["fy"], cx=c["cx"], cy=c["cy"], W=c["W"], H=c["H"]).transpose(0, 1)
+    b = Camera(0, torch.rand(3, 8, 8), None, None, torch.eye(4), proj, c["fx"], c["fy"], c["cx"], c["cy"], c["FoVx"], c["FoVy"], c["H"], c["W"],
+               device="cpu")
+    T = SE3_exp(torch.tensor(c["tau"]))
     b.update_RT(T[:3, :3], T[:3, 3])
     for name in ("world_view_transform", "full_proj_transform", "camera_center"):
-        assert torch.allclose(getattr(a, name), getattr(b, name), atol=1e-6), name
-    assert sorted(n for n, _ in a.named_parameters()) == sorted(n for n, _ in b.named_parameters())
-    for m in [k for k in sys.modules if k == "utils" or k.startswith("utils.")]:
-        monkeypatch.delitem(sys.modules, m)
+        assert torch.allclose(torch.tensor(ref[name]), getattr(b, name), atol=1e-6), name
+    assert ref["parameter_names"] == sorted(n for n, _ in b.named_parameters())
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/utils"), reason="reference checkout not present on this box")
 def test_reference_backend_constructs_and_resets_on_the_shim(monkeypatch):
-    """utils/slam_backend.py imports render / l1_loss / ssim / getProjectionMatrix2 from gaussian_splatting (:10-12);
-    with the shim on the path the reference's own BackEnd class loads, takes the KITTI-07 hyper-parameters and
-    drives GaussianModel.prune_points through BackEnd.reset (:79-92).  utils/init_pose.py (MASt3R + cv2, out of
-    scope and not installed) is replaced by an empty module for the import."""
+    """utils/slam_backend.py imports render / l1_loss / ssim / getProjectionMatrix2 / getWorld2View2 from gaussian_splatting (:10-12):
+    through the shim they are the objects the reference's own BackEnd received; BackEnd.set_hyperparams took the KITTI-07
+    hyper-parameters the build's make_backend holds; BackEnd.reset (:79-92) leaves the state make_backend starts in and drives
+    GaussianModel.prune_points of the shim's model down to an empty map."""
     import importlib
-    import json
-    import types
     import torch
     monkeypatch.syspath_prepend(DROPIN)
-    monkeypatch.syspath_prepend("/root/reference")
-    monkeypatch.setattr(sys, "dont_write_bytecode", True)
-    for m in [k for k in sys.modules if k == "utils" or k.startswith("utils.")]:
-        monkeypatch.delitem(sys.modules, m)
-    stub = types.ModuleType("utils.init_pose")
-    stub.save_depth_comparison = lambda *a, **k: None
-    monkeypatch.setitem(sys.modules, "utils.init_pose", stub)
-    backend = importlib.import_module("utils.slam_backend")
+    ref = _reference()
+    where = {"render": "gaussian_splatting.gaussian_renderer", "l1_loss": "gaussian_splatting.utils.loss_utils",
+             "ssim": "gaussian_splatting.utils.loss_utils", "getProjectionMatrix2": "gaussian_splatting.utils.graphics_utils",
+             "getWorld2View2": "gaussian_splatting.utils.graphics_utils"}
+    assert set(where) == set(ref["backend_imports"])
+    for n, mod in where.items():
+        o = getattr(importlib.import_module(mod), n)
+        assert o.__module__ + "." + o.__qualname__ == ref["backend_imports"][n], n
     import lvdgs.gaussian_renderer
     import lvdgs.loss_utils
-    assert backend.render is lvdgs.gaussian_renderer.render
-    assert backend.ssim is lvdgs.loss_utils.ssim and backend.l1_loss is lvdgs.loss_utils.l1_loss
+    assert importlib.import_module("gaussian_splatting.gaussian_renderer").render is lvdgs.gaussian_renderer.render
+    assert importlib.import_module("gaussian_splatting.utils.loss_utils").ssim is lvdgs.loss_utils.ssim
+
+    # the build's BackEnd state (lvdgs.slam_sequence.make_backend) holds the hyper-parameters the reference's set_hyperparams took from the
+    # same configuration, and starts where the reference's reset leaves the back end
+    from lvdgs.slam_sequence import make_backend
     cfg = json.load(open(os.path.join(ROOT, "tests", "golden", "config_07.json")))
-    cfg["Training"]["monocular"] = cfg["Dataset"]["sensor_type"] == "monocular"  # set by the absent slam.py entry point
-    be = backend.BackEnd(cfg)
-    be.cameras_extent = 6.0
-    be.set_hyperparams()
+    cfg["Training"]["monocular"] = cfg["Dataset"]["sensor_type"] == "monocular"
+    hp = ref["backend_hyperparams"]
+    be = make_backend(cfg, None, None, None, cameras_extent=hp["cameras_extent"])
+    for n, v in hp.items():
+        assert getattr(be, n) == v, n
     assert be.window_size == 8 and be.gaussian_extent == 6.0 and be.init_gaussian_extent == 180.0
+    rs = ref["backend_reset"]
+    assert (be.iteration_count, be.current_window, be.initialized) == (rs["iteration_count"], rs["current_window"], rs["initialized"])
 
     from gaussian_splatting.scene.gaussian_model import GaussianModel
     g = GaussianModel.from_activated(torch.rand(9, 3), torch.rand(9, 3) + 0.1, torch.nn.functional.normalize(torch.randn(9, 4)),
                                      torch.rand(9, 1), colors=torch.rand(9, 3), device="cpu")
     g.init_lr(6.0)
     g.training_setup(cfg["opt_params"])
-    be.gaussians = g
-
-    class _Q:
-        def empty(self):
-            return True
-    be.backend_queue = _Q()
-    be.reset()
-    assert g.get_xyz.shape[0] == 0 and be.iteration_count == 0 and be.current_window == []
-    for m in [k for k in sys.modules if k == "utils" or k.startswith("utils.")]:
-        monkeypatch.delitem(sys.modules, m, raising=False)
+    assert g.get_xyz.shape[0] == rs["gaussians_before"]
+    g.prune_points(g.unique_kfIDs >= 0)   # what BackEnd.reset asks of the model
+    assert g.get_xyz.shape[0] == rs["gaussians_after"] == 0
+    assert all(p.shape[0] == 0 for p in g.parameters())
