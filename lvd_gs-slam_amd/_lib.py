@@ -6,6 +6,8 @@ from here raises -- there is no CPU or PyTorch fallback.
 import ctypes as C
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LVDGS_LIB: another build of the library (same-box A/B of compile-time variants: `make OUT=../lib_b EXTRA=-D...`)
 LIB_PATH = os.environ.get("LVDGS_LIB") or os.path.join(_HERE, "lib", "liblvdgs.so")
@@ -221,10 +223,32 @@ def lib():
     return _lib
 
 
+def ptr(t):
+    """A tensor's data as a pointer field of an argument block (None: NULL)."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def is_f32(t, device=None):
+    """Is ``t`` a contiguous float32 tensor on ``device`` (None: on any GPU)?"""
+    return (torch.is_tensor(t) and (t.is_cuda if device is None else t.device == device) and t.dtype is torch.float32
+            and t.is_contiguous())
+
+
+def f32(t, device):
+    """``t`` detached, as a contiguous float32 tensor on ``device`` (itself when it is one: no conversion kernel, no dispatcher
+    round trip through ``.to()``)."""
+    t = t.detach()
+    return t if is_f32(t, device) else t.to(device=device, dtype=torch.float32).contiguous()
+
+
+def device_bytes(n, device):
+    """A byte buffer of at least ``n`` bytes (and at least 256) on ``device``."""
+    return torch.empty(max(int(n), 256), dtype=torch.uint8, device=device)
+
+
 def raw_stream(device):
     """hipStream_t of PyTorch's current stream ON `device` (the tensor's device, which need not be the current one),
     as a c_void_p.  A direct C call: torch.cuda.current_stream() costs tens of microseconds of Python per call."""
-    import torch
     idx = device.index if (device is not None and device.index is not None) else torch.cuda.current_device()
     return C.c_void_p(torch._C._cuda_getCurrentRawStream(idx))
 
@@ -238,7 +262,6 @@ class on_device:
         self.idx = device.index
 
     def __enter__(self):
-        import torch
         self.prev = None
         if self.idx is not None:
             cur = torch.cuda.current_device()
@@ -248,7 +271,6 @@ class on_device:
 
     def __exit__(self, *exc):
         if self.prev is not None:
-            import torch
             torch.cuda.set_device(self.prev)
         return False
 

@@ -39,6 +39,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
+from ._lib import ptr as _P
 
 from .fast_mapping import MapViewPass, MapWindowBatch, _PARAM_FIELDS
 from .gaussian_renderer import render
@@ -485,7 +486,8 @@ class ShardedAdam:
         if len(skip) == len(params):
             return
         dev = params[0].device
-        use_kernel = dev.type == "cuda" and all(_on_gpu_f32(p.detach(), optimizer.state[p]["exp_avg"], optimizer.state[p]["exp_avg_sq"]) for p in params if p.numel())
+        use_kernel = dev.type == "cuda" and all(_lib.is_f32(t) for p in params if p.numel()
+                                                for t in (p.detach(), optimizer.state[p]["exp_avg"], optimizer.state[p]["exp_avg_sq"]))
         if use_kernel and pieces:
             arr = (_lib.AdamTensor * 8)()
             b1, b2 = items[pieces[0][0]][0]["betas"]
@@ -534,13 +536,6 @@ class ShardedAdam:
             tensors = [optimizer.state[p][key] for p in params]
             self._gather_into(tensors, key)
         self.stale = False
-
-
-_P = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _on_gpu_f32(*tensors):
-    return all(t is not None and t.is_cuda and t.dtype is torch.float32 and t.is_contiguous() for t in tensors)
 
 
 class KeyframeStepper:
@@ -627,7 +622,7 @@ class KeyframeStepper:
         for gp in optimizer.param_groups:
             if gp.get("weight_decay", 0) or gp.get("amsgrad", False) or gp.get("maximize", False):
                 return False
-            if not _on_gpu_f32(*gp["params"]):
+            if not all(_lib.is_f32(t) for t in gp["params"]):
                 return False
         owned = {id(getattr(vp, n, None)) for vp in viewpoints for n in _POSE_FIELDS}
         return all(id(p) in owned for gp in optimizer.param_groups for p in gp["params"]) and all(hasattr(vp, "update_RT") for vp in viewpoints)
@@ -659,7 +654,7 @@ class KeyframeStepper:
             g = lambda n: getattr(vp, n).grad if has[n] else None
             gr, gt, ga, gb = g("cam_rot_delta"), g("cam_trans_delta"), g("exposure_a"), g("exposure_b")
             for t in (gr, gt, ga, gb):
-                if t is not None and not _on_gpu_f32(t):
+                if t is not None and not _lib.is_f32(t):
                     raise ValueError("KeyframeStepper: gradients must be contiguous float32 GPU tensors")
             a.grad_rot, a.grad_trans, a.grad_exposure_a, a.grad_exposure_b = _P(gr), _P(gt), _P(ga), _P(gb)
             if pose and (vp.R is not keep[1] or vp.T is not keep[2]):
@@ -725,7 +720,7 @@ class _ViewStats:
         plane = self.split_xy[2 * N * k:2 * N * (k + 1)] if k >= 0 else None
         counts = row0 == 0
         fast = (self.dev.type == "cuda" and radii.dtype is torch.int32 and nt.dtype is torch.int32 and radii.is_contiguous()
-                and nt.is_contiguous() and (vg is None or _on_gpu_f32(vg)))
+                and nt.is_contiguous() and (vg is None or _lib.is_f32(vg)))
         if fast:
             row = self.flags[view] if view < n_window else None
             with _lib.on_device(self.dev):
@@ -748,8 +743,8 @@ class _ViewStats:
     def apply(self, G, radii_max, norm_sum, vis_count, split_xy):
         """``max_radii2D`` / ``xyz_gradient_accum`` / ``denom`` from the (reduced) statistics (reference :350-357)."""
         N, n_split = self.N, len(self.split)
-        fast = (self.dev.type == "cuda" and _on_gpu_f32(G.max_radii2D, G.xyz_gradient_accum, G.denom, norm_sum, vis_count)
-                and radii_max.dtype is torch.int32 and radii_max.is_contiguous() and (n_split == 0 or _on_gpu_f32(split_xy))
+        fast = (self.dev.type == "cuda" and all(_lib.is_f32(t) for t in (G.max_radii2D, G.xyz_gradient_accum, G.denom, norm_sum, vis_count))
+                and radii_max.dtype is torch.int32 and radii_max.is_contiguous() and (n_split == 0 or _lib.is_f32(split_xy))
                 and G.max_radii2D.numel() == N and G.xyz_gradient_accum.numel() == N and G.denom.numel() == N)
         if fast:
             with _lib.on_device(self.dev):
@@ -774,12 +769,12 @@ def _isotropic_fused(G, weight=10.0):
     """The same term through ``lvdgs_isotropic_reg``: value returned, gradient ADDED to ``G._scaling.grad`` (two
     launches instead of a dozen).  None when the model is not the standard one on the GPU."""
     raw = getattr(G, "_scaling", None)
-    if not (getattr(G, "standard_activations", False) and torch.is_tensor(raw) and _on_gpu_f32(raw) and raw.dim() == 2 and raw.shape[1] == 3):
+    if not (getattr(G, "standard_activations", False) and torch.is_tensor(raw) and _lib.is_f32(raw) and raw.dim() == 2 and raw.shape[1] == 3):
         return None
     N, dev = raw.shape[0], raw.device
     if raw.grad is None:
         raw.grad = torch.zeros_like(raw)
-    elif not _on_gpu_f32(raw.grad):
+    elif not _lib.is_f32(raw.grad):
         return None
     L = _lib.lib()
     scratch = torch.empty(int(L.lvdgs_isotropic_scratch_bytes(N)), dtype=torch.uint8, device=dev)

@@ -40,17 +40,9 @@ import torch
 
 from . import _lib
 from . import rasterizer as _rz
+from ._lib import ptr as _P
 from .gaussian_renderer import _raw_parameters
 from .slam_utils import _gt_image, _mono_depth, get_median_depth
-
-_P = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _f32c(t, dev):
-    t = t.detach()
-    if t.dtype is not torch.float32 or t.device != dev or not t.is_contiguous():
-        t = t.to(device=dev, dtype=torch.float32).contiguous()
-    return t
 
 
 class TrackingSession:
@@ -58,7 +50,6 @@ class TrackingSession:
     into the viewpoint (``R``, ``T`` via ``update_RT``; exposure and the zeroed deltas were updated in place)."""
 
     def __init__(self, viewpoint, gaussians, config, pipeline_params, background, converged_threshold=1e-4, gaussian_gradients=False):
-        import math
         dev = gaussians.get_xyz.device
         if dev.type != "cuda":
             raise _lib.LvdgsError("TrackingSession needs the map on the GPU (there is no CPU path)")
@@ -75,24 +66,22 @@ class TrackingSession:
         keep = self._keep = []
 
         # ---- camera state on the device: the session's own copies, advanced by lvdgs_pose_step ----
-        self.R = _f32c(viewpoint.R, dev).clone()
-        self.T = _f32c(viewpoint.T, dev).clone()
-        self.proj_raw = _f32c(viewpoint.projection_matrix, dev)
-        self.view = _f32c(viewpoint.world_view_transform, dev).clone()
-        self.proj = _f32c(viewpoint.full_proj_transform, dev).clone()
-        self.campos = _f32c(viewpoint.camera_center, dev).clone()
+        self.R = _lib.f32(viewpoint.R, dev).clone()
+        self.T = _lib.f32(viewpoint.T, dev).clone()
+        self.proj_raw = _lib.f32(viewpoint.projection_matrix, dev)
+        self.view = _lib.f32(viewpoint.world_view_transform, dev).clone()
+        self.proj = _lib.f32(viewpoint.full_proj_transform, dev).clone()
+        self.campos = _lib.f32(viewpoint.camera_center, dev).clone()
         for name in ("cam_rot_delta", "cam_trans_delta", "exposure_a", "exposure_b"):
             p = getattr(viewpoint, name)
             if p.device != dev or p.dtype is not torch.float32 or not p.is_contiguous():
                 raise ValueError(f"TrackingSession: viewpoint.{name} must be a contiguous float32 tensor on {dev}")
-        self.bg = _f32c(background, dev)
+        self.bg = _lib.f32(background, dev)
 
         # ---- forward / backward argument block (include/lvdgs.h: lvdgs_args) ----
         a = self.a = _lib.Args()
         a.image_height, a.image_width = H, W
-        a.tanfovx, a.tanfovy = math.tan(viewpoint.FoVx * 0.5), math.tan(viewpoint.FoVy * 0.5)
-        a.scale_modifier, a.sh_degree, a.prefiltered, a.debug = 1.0, int(gaussians.active_sh_degree), 0, 0
-        a.bg, a.viewmatrix, a.projmatrix, a.projmatrix_raw, a.campos = _P(self.bg), _P(self.view), _P(self.proj), _P(self.proj_raw), _P(self.campos)
+        _rz.fill_camera(a, viewpoint, gaussians.active_sh_degree, self.bg, self.view, self.proj, self.proj_raw, self.campos)
         raw = _raw_parameters(gaussians)
         if raw is not None:
             scales, rotations, opacity = raw
@@ -104,7 +93,7 @@ class TrackingSession:
         self.pose_only = not gaussian_gradients and int(gaussians.active_sh_degree) == 0
         if self.pose_only:
             a.flags |= _lib.FLAG_POSE_ONLY
-        m3, sc, rot, op, shs = (_f32c(t, dev) for t in (gaussians.get_xyz, scales, rotations, opacity, gaussians.get_features))
+        m3, sc, rot, op, shs = (_lib.f32(t, dev) for t in (gaussians.get_xyz, scales, rotations, opacity, gaussians.get_features))
         keep += [m3, sc, rot, op, shs]
         a.num_gaussians, a.sh_coeffs = N, int(shs.shape[1])
         a.means3D, a.opacities, a.scales, a.rotations, a.shs = _P(m3), _P(op), _P(sc), _P(rot), _P(shs)
@@ -113,12 +102,11 @@ class TrackingSession:
         a.radii, a.n_touched = _P(self.radii), _P(self.n_touched)
         a.out_color, a.out_depth, a.out_opacity = _P(self.color), _P(self.depth), _P(self.opacity)
         L = self.L
-        bytes_ = lambda n: torch.empty(max(int(n), 256), dtype=torch.uint8, device=dev)
-        self.geom, self.image = bytes_(L.lvdgs_geom_bytes(N)), bytes_(L.lvdgs_image_bytes(W, H))
+        self.geom, self.image = _lib.device_bytes(L.lvdgs_geom_bytes(N), dev), _lib.device_bytes(L.lvdgs_image_bytes(W, H), dev)
         a.geom_state, a.geom_bytes = _P(self.geom), self.geom.numel()
         a.image_state, a.image_bytes = _P(self.image), self.image.numel()
         key = dev.index if dev.index is not None else torch.cuda.current_device()
-        self.cap = max(_rz._PAIR_CAPACITY.get(key, 0), _rz._MIN_PAIR_CAPACITY, _rz._PAIRS_PER_GAUSSIAN_GUESS * N, 1)
+        self.cap = _rz.first_pair_capacity(N, _rz._PAIR_CAPACITY.get(key, 0))
         self._size_for_pairs(self.cap)
         # gradient outputs of lvdgs_backward (only dL/dtau is consumed; the Gaussians' go to scratch when they are asked for)
         self.d_tau = e(6)
@@ -133,7 +121,7 @@ class TrackingSession:
         # ---- tracking loss (reference utils/slam_utils.py:42-79; include/lvdgs.h: lvdgs_loss_args) ----
         la = self.la = _lib.LossArgs()
         la.width, la.height = W, H
-        gt = _f32c(_gt_image(viewpoint, self.color), dev)
+        gt = _lib.f32(_gt_image(viewpoint, self.color), dev)
         gm = viewpoint.grad_mask
         gm = None if gm is None else gm.reshape(-1).to(dev)
         if gm is not None:
@@ -146,11 +134,11 @@ class TrackingSession:
             la.weight_rgb, la.weight_depth, la.depth_needs_opaque = 1.0, 0.0, 0
         else:
             alpha = T.get("alpha", 0.95)
-            md = _f32c(_mono_depth(viewpoint, self.color), dev)
+            md = _lib.f32(_mono_depth(viewpoint, self.color), dev)
             keep.append(md)
             la.depth, la.gt_depth = _P(self.depth), _P(md)
             la.weight_rgb, la.weight_depth, la.depth_needs_opaque = float(alpha), float(1 - alpha), 1
-        self.loss_scratch = bytes_(L.lvdgs_loss_scratch_bytes(W, H))
+        self.loss_scratch = _lib.device_bytes(L.lvdgs_loss_scratch_bytes(W, H), dev)
         self.loss, self.one = e(()), torch.ones((), dtype=torch.float32, device=dev)
         self.d_a, self.d_b = e(1), e(1)
         la.scratch, la.scratch_bytes, la.loss, la.grad_loss = _P(self.loss_scratch), self.loss_scratch.numel(), _P(self.loss), _P(self.one)
@@ -187,37 +175,20 @@ class TrackingSession:
         self.num_rendered = 0
 
     def _size_for_pairs(self, pairs):
-        L, a, dev = self.L, self.a, self.dev
-        bytes_ = lambda n: torch.empty(max(int(n), 256), dtype=torch.uint8, device=dev)
-        self.binning = bytes_(L.lvdgs_binning_bytes(pairs))
-        self.scratch = bytes_(max(L.lvdgs_prepare_scratch_bytes(self.N), L.lvdgs_render_scratch_bytes(self.N, pairs, self.W, self.H),
-                                  L.lvdgs_backward_scratch_bytes(self.N, pairs)))
-        a.pair_capacity = pairs
-        a.binning_state, a.binning_bytes = _P(self.binning), self.binning.numel()
-        a.scratch, a.scratch_bytes = _P(self.scratch), self.scratch.numel()
+        self.binning, self.scratch = _rz.pair_buffers(self.a, pairs, self.dev)
 
     def step(self, record_loss=None):
         """Enqueue one tracking iteration.  ``record_loss``: a 0-dim device tensor to receive a copy of the loss."""
         L, a = self.L, self.a
         with _lib.on_device(self.dev):
             stream = _lib.raw_stream(self.dev)
-            num = C.c_int64(0)
             # forward and backward as one call: the backward evaluates the loss's image gradients as it reads its pixels (the
             # objective is the loss: d/d loss = 1), and on small grids the two blend passes of a tile share a launch
             # (lvdgs_forward_backward_fused_loss); the loss's final reduction, the pose gradient's and the pose step share the
             # iteration's last launch
             # (the two-level grouping hint follows the previous iteration's pair count: rasterizer.super_tiles_flag)
             a.flags = (a.flags & ~_lib.FLAG_SUPER_TILES) | _rz.super_tiles_flag(self.N, self.num_rendered)
-            status = L.lvdgs_forward_backward_fused_loss(C.byref(a), C.byref(self.la), int(_rz.PROPAGATE_OPACITY_GRAD), C.byref(num), stream)
-            D = int(num.value)
-            if status == _lib.E_CAPACITY:   # more pairs than the buffers hold: grow them and redo binning + blend, then the backward
-                self._size_for_pairs(D + D // 2)
-                a.num_rendered = D
-                _lib.check(L.lvdgs_forward_render(C.byref(a), stream), "lvdgs_forward_render")
-                _lib.check(L.lvdgs_backward_fused_loss(C.byref(a), C.byref(self.la), int(_rz.PROPAGATE_OPACITY_GRAD), stream), "lvdgs_backward_fused_loss")
-            else:
-                _lib.check(status, "lvdgs_forward_backward_fused_loss")
-            self.num_rendered = a.num_rendered = D
+            self.num_rendered = _rz.run_forward(a, stream, self._size_for_pairs, self.la, int(_rz.PROPAGATE_OPACITY_GRAD))
             _lib.check(L.lvdgs_tracking_tail(C.byref(self.la), C.byref(a), C.byref(self.pa), _P(self.d_tau), 1, stream), "lvdgs_tracking_tail")
             if record_loss is not None:
                 record_loss.copy_(self.loss)

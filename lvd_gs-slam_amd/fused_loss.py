@@ -9,10 +9,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
+from ._lib import ptr as _p, raw_stream as _raw_stream
 
 
 def _aligned(t):
@@ -25,11 +22,6 @@ def _c32(t):
     if t.dtype is torch.float32 and t.is_contiguous():
         return _aligned(t.detach())
     return _aligned(t.detach().to(torch.float32).contiguous())
-
-
-def _raw_stream(dev):
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    return C.c_void_p(torch._C._cuda_getCurrentRawStream(idx))
 
 
 class _Photometric(torch.autograd.Function):

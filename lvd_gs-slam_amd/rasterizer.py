@@ -19,14 +19,15 @@ All compute happens in ``lib/liblvdgs.so`` (HIP, gfx950) through the C ABI in
 ``include/lvdgs.h``; this file only allocates tensors and passes pointers.
 """
 import ctypes as C
-from typing import NamedTuple
-
+import math
 import os
+from typing import NamedTuple
 
 import torch
 from torch import nn
 
 from . import _lib
+from ._lib import ptr as _P
 
 # d(loss)/d(opacity image) is NOT propagated by default: the backward binding this module mirrors
 # (INTEGRATION.md, `rasterize_gaussians_backward(..., dL_dout_color, dL_dout_depth, ...)`) takes the gradients of
@@ -71,19 +72,7 @@ def _f32(t, device):
         return None
     if not torch.is_tensor(t):
         t = torch.as_tensor(t)
-    if t.numel() == 0:
-        return None
-    if t.dtype is torch.float32 and t.device == device and t.is_contiguous():
-        return t.detach()  # the common case: no conversion kernel, no dispatcher round trip through .to()
-    return t.detach().to(device=device, dtype=torch.float32).contiguous()
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _bytes(n, device):
-    return torch.empty(max(int(n), 256), dtype=torch.uint8, device=device)
+    return None if t.numel() == 0 else _lib.f32(t, device)
 
 
 def _fill_settings(a, rs, device, keep):
@@ -94,14 +83,73 @@ def _fill_settings(a, rs, device, keep):
     for name in ("bg", "viewmatrix", "projmatrix", "projmatrix_raw", "campos"):
         t = _f32(getattr(rs, name), device)
         keep.append(t)
-        setattr(a, name, _ptr(t))
+        setattr(a, name, _P(t))
 
 
-def _stream(device=None):
-    """Raw hipStream_t of PyTorch's current stream on `device` (a direct C call: torch.cuda.current_stream()
-    goes through lazy-init and device-count checks that cost tens of microseconds per call)."""
-    idx = device.index if (device is not None and device.index is not None) else torch.cuda.current_device()
-    return C.c_void_p(torch._C._cuda_getCurrentRawStream(idx))
+def fill_camera(a, viewpoint, sh_degree, bg, view, proj, proj_raw, campos):
+    """The camera fields of ``a`` for ``viewpoint`` (a ``Camera``: field of view) with the background and camera matrices given as
+    contiguous float32 tensors on the device, which the caller keeps alive -- what ``render()`` puts into the settings."""
+    a.tanfovx, a.tanfovy = math.tan(viewpoint.FoVx * 0.5), math.tan(viewpoint.FoVy * 0.5)
+    a.scale_modifier, a.sh_degree, a.prefiltered, a.debug = 1.0, int(sh_degree), 0, 0
+    a.bg, a.viewmatrix, a.projmatrix, a.projmatrix_raw, a.campos = _P(bg), _P(view), _P(proj), _P(proj_raw), _P(campos)
+
+
+# ---- the pair capacity: every caller sizes its binning state for a number of (Gaussian, tile) pairs before the forward knows the
+# frame's count; a frame with more makes the forward return LVDGS_E_CAPACITY, and the caller grows its buffers and re-runs the
+# binning + blend stage (lvdgs_forward_render).  The knobs above are read at every call (tests shrink them to force that path).
+
+def first_pair_capacity(num_gaussians, remembered=0):
+    """Pairs to size the buffers of a frame of ``num_gaussians`` for: what the caller remembers, or a guess from the map's size."""
+    return max(int(remembered), _MIN_PAIR_CAPACITY, _PAIRS_PER_GAUSSIAN_GUESS * num_gaussians, 1)
+
+
+def pair_state_bytes(N, pairs, W, H, backward=True):
+    """-> (binning state, scratch) bytes for ``pairs`` pairs of a frame of N Gaussians, W x H: the scratch serves the prepare and
+    render stages and, with ``backward``, the backward's."""
+    L = _lib.lib()
+    scratch = max(L.lvdgs_prepare_scratch_bytes(N), L.lvdgs_render_scratch_bytes(N, pairs, W, H),
+                  L.lvdgs_backward_scratch_bytes(N, pairs) if backward else 0)
+    return L.lvdgs_binning_bytes(pairs), scratch
+
+
+def pair_buffers(a, pairs, device, backward=True):
+    """Binning state and scratch for ``pairs`` pairs of the frame ``a`` describes (its N, W, H), pointed at by ``a``; -> the two
+    buffers (the caller keeps them alive)."""
+    binning_bytes, scratch_bytes = pair_state_bytes(a.num_gaussians, pairs, a.image_width, a.image_height, backward)
+    binning, scratch = _lib.device_bytes(binning_bytes, device), _lib.device_bytes(scratch_bytes, device)
+    a.pair_capacity = pairs
+    a.binning_state, a.binning_bytes = _P(binning), binning.numel()
+    a.scratch, a.scratch_bytes = _P(scratch), scratch.numel()
+    return binning, scratch
+
+
+def run_forward(a, stream, resize, la=None, opacity_grad=0, exact=False):
+    """``lvdgs_forward`` on ``a`` -- with the loss block ``la``: ``lvdgs_forward_backward_fused_loss``, the backward evaluating the
+    loss per pixel -- and the overflow path behind it (``rerender``).  Sets and returns ``a.num_rendered``."""
+    L, num = _lib.lib(), C.c_int64(0)
+    if la is None:
+        status, what = L.lvdgs_forward(C.byref(a), C.byref(num), stream), "lvdgs_forward"
+    else:
+        status = L.lvdgs_forward_backward_fused_loss(C.byref(a), C.byref(la), opacity_grad, C.byref(num), stream)
+        what = "lvdgs_forward_backward_fused_loss"
+    D = int(num.value)
+    if status == _lib.E_CAPACITY:
+        rerender(a, D, stream, resize, la, opacity_grad, exact)
+    else:
+        _lib.check(status, what)
+    a.num_rendered = D
+    return D
+
+
+def rerender(a, D, stream, resize, la=None, opacity_grad=0, exact=False):
+    """A frame of ``D`` pairs, more than its buffers hold: ``resize(pairs)`` grows them -- to D (``exact``) or D + D/2 -- and the
+    binning + blend stage runs again, then (with ``la``) the fused backward."""
+    L = _lib.lib()
+    resize(D if exact else D + D // 2)
+    a.num_rendered = D
+    _lib.check(L.lvdgs_forward_render(C.byref(a), stream), "lvdgs_forward_render")
+    if la is not None:
+        _lib.check(L.lvdgs_backward_fused_loss(C.byref(a), C.byref(la), opacity_grad, stream), "lvdgs_backward_fused_loss")
 
 
 # Two-level grouping (include/lvdgs.h: LVDGS_FLAG_SUPER_TILES): worth it when a Gaussian is listed on many tiles -- the opaque surfaces of
@@ -152,51 +200,39 @@ class _RasterizeGaussians(torch.autograd.Function):
         a.num_gaussians = N
         a.activations = int(activations)
         a.flags = _lib.FLAG_LIST_ALL_TILES if LIST_ALL_TILES else 0
-        _key = dev.index if dev.index is not None else torch.cuda.current_device()
-        _last = _LAST_PAIRS.get(_key)
+        key = dev.index if dev.index is not None else torch.cuda.current_device()
+        _last = _LAST_PAIRS.get(key)
         a.flags |= super_tiles_flag(N, _last[1] if (_last is not None and _last[0] == N) else None)
         a.sh_coeffs = int(shs.shape[1]) if shs is not None else 0
-        a.means3D, a.opacities, a.scales, a.rotations = _ptr(m3), _ptr(op), _ptr(sc), _ptr(rot)
-        a.cov3D_precomp, a.shs, a.colors_precomp = _ptr(cov), _ptr(shs), _ptr(col)
+        a.means3D, a.opacities, a.scales, a.rotations = _P(m3), _P(op), _P(sc), _P(rot)
+        a.cov3D_precomp, a.shs, a.colors_precomp = _P(cov), _P(shs), _P(col)
 
         radii = torch.empty(N, dtype=torch.int32, device=dev)
         n_touched = torch.empty(N, dtype=torch.int32, device=dev)
         color = torch.empty(3, H, W, dtype=torch.float32, device=dev)
         depth = torch.empty(1, H, W, dtype=torch.float32, device=dev)
         opac = torch.empty(1, H, W, dtype=torch.float32, device=dev)
-        geom = _bytes(L.lvdgs_geom_bytes(N), dev)
-        image = _bytes(L.lvdgs_image_bytes(W, H), dev)
-        a.radii, a.n_touched = _ptr(radii), _ptr(n_touched)
-        a.out_color, a.out_depth, a.out_opacity = _ptr(color), _ptr(depth), _ptr(opac)
-        a.geom_state, a.geom_bytes = _ptr(geom), geom.numel()
-        a.image_state, a.image_bytes = _ptr(image), image.numel()
+        geom = _lib.device_bytes(L.lvdgs_geom_bytes(N), dev)
+        image = _lib.device_bytes(L.lvdgs_image_bytes(W, H), dev)
+        a.radii, a.n_touched = _P(radii), _P(n_touched)
+        a.out_color, a.out_depth, a.out_opacity = _P(color), _P(depth), _P(opac)
+        a.geom_state, a.geom_bytes = _P(geom), geom.numel()
+        a.image_state, a.image_bytes = _P(image), image.numel()
 
         # Single-call forward: buffers are sized for a pair capacity remembered per device (grown when a
         # frame gets within 25 % of it), every kernel is enqueued before the host waits for the pair
         # count, and an overflow (rare) re-runs only the binning + blend stage with exact sizes.
-        stream = _stream(dev)
-        key = dev.index if dev.index is not None else torch.cuda.current_device()
-        cap = max(_PAIR_CAPACITY.get(key, 0), _MIN_PAIR_CAPACITY, _PAIRS_PER_GAUSSIAN_GUESS * N, 1) if N > 0 else 0
-        binning = _bytes(L.lvdgs_binning_bytes(cap), dev)
-        scratch = _bytes(max(L.lvdgs_prepare_scratch_bytes(N), L.lvdgs_render_scratch_bytes(N, cap, W, H)), dev)
-        a.pair_capacity = cap
-        a.binning_state, a.binning_bytes = _ptr(binning), binning.numel()
-        a.scratch, a.scratch_bytes = _ptr(scratch), scratch.numel()
-        num = C.c_int64(0)
-        status = L.lvdgs_forward(C.byref(a), C.byref(num), stream)
-        D = int(num.value)
-        binning_pairs = cap
-        if status == _lib.E_CAPACITY:
-            binning_pairs = D
-            binning = _bytes(L.lvdgs_binning_bytes(D), dev)
-            scratch = _bytes(L.lvdgs_render_scratch_bytes(N, D, W, H), dev)
-            a.num_rendered = D
-            a.binning_state, a.binning_bytes = _ptr(binning), binning.numel()
-            a.scratch, a.scratch_bytes = _ptr(scratch), scratch.numel()
-            _lib.check(L.lvdgs_forward_render(C.byref(a), stream), "lvdgs_forward_render")
-        else:
-            _lib.check(status, "lvdgs_forward")
-        _LAST_PAIRS[_key] = (N, D)
+        cap = first_pair_capacity(N, _PAIR_CAPACITY.get(key, 0)) if N > 0 else 0
+        bufs = pair_buffers(a, cap, dev, backward=False)
+
+        def resize(pairs):
+            nonlocal bufs
+            bufs = pair_buffers(a, pairs, dev, backward=False)
+
+        D = run_forward(a, _lib.raw_stream(dev), resize, exact=True)
+        binning = bufs[0]
+        binning_pairs = int(a.pair_capacity)
+        _LAST_PAIRS[key] = (N, D)
         if N > 0 and 4 * D > 3 * cap:
             _PAIR_CAPACITY[key] = max(cap, D + D // 2)
         else:
@@ -205,7 +241,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         if KEEP_DEBUG_STATE:
             _DEBUG_LAST.clear()
             _DEBUG_LAST.update(geom=geom, binning=binning, image=image, num_rendered=D, N=N, W=W, H=H,
-                               binning_pairs=binning_pairs, overflowed=status == _lib.E_CAPACITY)
+                               binning_pairs=binning_pairs, overflowed=binning_pairs != cap)
         ctx.raster_settings = rs
         ctx.num_rendered = D
         ctx.activations = int(activations)
@@ -229,22 +265,22 @@ class _RasterizeGaussians(torch.autograd.Function):
         _fill_settings(a, rs, dev, keep)
         a.num_gaussians = N
         a.sh_coeffs = int(shs.shape[1]) if shs is not None else 0
-        a.means3D, a.opacities, a.scales, a.rotations = _ptr(m3), _ptr(op), _ptr(sc), _ptr(rot)
-        a.cov3D_precomp, a.shs, a.colors_precomp = _ptr(cov), _ptr(shs), _ptr(col)
-        a.radii = _ptr(radii)
+        a.means3D, a.opacities, a.scales, a.rotations = _P(m3), _P(op), _P(sc), _P(rot)
+        a.cov3D_precomp, a.shs, a.colors_precomp = _P(cov), _P(shs), _P(col)
+        a.radii = _P(radii)
         a.activations = ctx.activations
         a.flags = ctx.flags
         a.num_rendered = D
-        a.geom_state, a.geom_bytes = _ptr(geom), geom.numel()
-        a.binning_state, a.binning_bytes = _ptr(binning), binning.numel()
-        a.image_state, a.image_bytes = _ptr(image), image.numel()
-        scratch = _bytes(L.lvdgs_backward_scratch_bytes(N, D), dev)
-        a.scratch, a.scratch_bytes = _ptr(scratch), scratch.numel()
+        a.geom_state, a.geom_bytes = _P(geom), geom.numel()
+        a.binning_state, a.binning_bytes = _P(binning), binning.numel()
+        a.image_state, a.image_bytes = _P(image), image.numel()
+        scratch = _lib.device_bytes(L.lvdgs_backward_scratch_bytes(N, D), dev)
+        a.scratch, a.scratch_bytes = _P(scratch), scratch.numel()
 
         g_color = _f32(grad_color, dev) if grad_color is not None else torch.zeros(3, H, W, device=dev)
         g_depth = _f32(grad_depth, dev) if grad_depth is not None else None
         g_opac = _f32(grad_opacity, dev) if (grad_opacity is not None and PROPAGATE_OPACITY_GRAD) else None
-        a.dL_dout_color, a.dL_dout_depth, a.dL_dout_opacity = _ptr(g_color), _ptr(g_depth), _ptr(g_opac)
+        a.dL_dout_color, a.dL_dout_depth, a.dL_dout_opacity = _P(g_color), _P(g_depth), _P(g_opac)
 
         e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         d_m3, d_m2, d_op = e(N, 3), e(N, 3), e(*op.shape) if op is not None else e(N, 1)
@@ -254,10 +290,10 @@ class _RasterizeGaussians(torch.autograd.Function):
         d_sh = e(*shs.shape) if shs is not None else None
         d_col = e(N, 3) if col is not None else None
         d_tau = e(6)
-        a.dL_dmeans3D, a.dL_dmeans2D, a.dL_dopacities = _ptr(d_m3), _ptr(d_m2), _ptr(d_op)
-        a.dL_dscales, a.dL_drotations, a.dL_dcov3D = _ptr(d_sc), _ptr(d_rot), _ptr(d_cov)
-        a.dL_dshs, a.dL_dcolors, a.dL_dtau = _ptr(d_sh), _ptr(d_col), _ptr(d_tau)
-        _lib.check(L.lvdgs_backward(C.byref(a), _stream(dev)), "lvdgs_backward")
+        a.dL_dmeans3D, a.dL_dmeans2D, a.dL_dopacities = _P(d_m3), _P(d_m2), _P(d_op)
+        a.dL_dscales, a.dL_drotations, a.dL_dcov3D = _P(d_sc), _P(d_rot), _P(d_cov)
+        a.dL_dshs, a.dL_dcolors, a.dL_dtau = _P(d_sh), _P(d_col), _P(d_tau)
+        _lib.check(L.lvdgs_backward(C.byref(a), _lib.raw_stream(dev)), "lvdgs_backward")
         # (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, theta, rho, settings)
         d_theta = d_tau[3:] if ctx.pose[0] else None
         d_rho = d_tau[:3] if ctx.pose[1] else None
@@ -287,7 +323,7 @@ class GaussianRasterizer(nn.Module):
             N = int(positions.shape[0])
             out = torch.empty(N, dtype=torch.uint8, device=positions.device)
             view, proj = _f32(rs.viewmatrix, positions.device), _f32(rs.projmatrix, positions.device)
-            _lib.check(_lib.lib().lvdgs_mark_visible(N, _ptr(pos), _ptr(view), _ptr(proj), _ptr(out), _stream(positions.device)),
+            _lib.check(_lib.lib().lvdgs_mark_visible(N, _P(pos), _P(view), _P(proj), _P(out), _lib.raw_stream(positions.device)),
                        "lvdgs_mark_visible")
             return out.bool()
 

@@ -77,7 +77,8 @@ def test_window_batch_with_more_views_than_one_launch_takes():
 def test_gaussian_backward_batch_adds_to_gradients_that_are_there():
     """lvdgs_gaussian_backward_batch with LVDGS_FLAG_ACCUMULATE_PARAM_GRADS on its FIRST view (the model's parameters already carry
     gradients when the window's passes begin: nothing cleared them since the last backward): the launch starts from what the buffers
-    hold and adds the views in order -- the bits of the view-after-view launches (LVDGS_MAP_PBWD_BATCH=0), which add in memory."""
+    hold and adds the views in order -- the bits of MapViewPass.run view after view in the window's order, which adds in memory.
+    Every gradient: the model's parameters' and the viewpoints' pose and exposure gradients."""
     import bench
     from lvdgs import synthetic
     from lvdgs.fast_mapping import MapViewPass, MapWindowBatch
@@ -85,7 +86,7 @@ def test_gaussian_backward_batch_adds_to_gradients_that_are_there():
     synthetic.CONFIGS.setdefault(workload, dict(N=30000, W=400, H=240))
     dev = torch.device("cuda", 0)
     out = {}
-    for one_pass in ("1", "0"):
+    for batch in (True, False):
         torch.manual_seed(0)
         model, cam, g, _ = bench.build_scene(workload, 0, dev)
         backend, window = bench.build_window(workload, 6, dev, model, n_window=4)
@@ -94,19 +95,20 @@ def test_gaussian_backward_batch_adds_to_gradients_that_are_there():
         for p_ in G.parameters():
             p_.grad = torch.randn(p_.shape, device=dev, generator=gen) * 1e-3 if p_.numel() else None
         views = [backend.viewpoints[k] for k in window]
-        before = os.environ.get("LVDGS_MAP_PBWD_BATCH")
-        os.environ["LVDGS_MAP_PBWD_BATCH"] = one_pass
-        try:
+        if batch:
             MapWindowBatch(MapViewPass(dev)).run(backend, views)
-        finally:
-            if before is None:
-                os.environ.pop("LVDGS_MAP_PBWD_BATCH", None)
-            else:
-                os.environ["LVDGS_MAP_PBWD_BATCH"] = before
+        else:
+            vpass = MapViewPass(dev)
+            for vp in views:
+                vpass.run(backend, vp)
         torch.cuda.synchronize()
-        out[one_pass] = [p_.grad.clone() for p_ in G.parameters() if p_.grad is not None]
-    assert len(out["1"]) >= 5 and all(float(t.abs().sum()) > 0 for t in out["1"])
-    for a, b in zip(out["1"], out["0"]):
+        out[batch] = ([p_.grad.clone() for p_ in G.parameters() if p_.grad is not None],
+                      [p_.grad.clone() for vp in views for p_ in (vp.cam_rot_delta, vp.cam_trans_delta, vp.exposure_a, vp.exposure_b)])
+    params_b, views_b = out[True]
+    params_s, views_s = out[False]
+    assert len(params_b) >= 5 and all(float(t.abs().sum()) > 0 for t in params_b)
+    assert len(params_b) == len(params_s) and len(views_b) == len(views_s) == 16
+    for a, b in zip(params_b + views_b, params_s + views_s):
         assert torch.equal(a, b)
 
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The one-GPU 8 + 2 mapping window of a workload, masked and unmasked: ms per iteration (as bench.py's config.side measures it).
-usage: python tools/window_bench.py [workload ...]   (LVDGS_MAX_BATCH_TILES / LVDGS_MAP_BATCH / LVDGS_MAP_FWD_BATCH: A/B knobs)"""
+usage: python tools/window_bench.py [workload ...]   (LVDGS_MAX_BATCH_TILES / LVDGS_MAP_BATCH: A/B knobs)"""
 import os
 import sys
 import time
