@@ -536,6 +536,50 @@ int lvdgs_blend_backward_window_batch(const lvdgs_args *const *views, const lvdg
  * Replaces: the reference's per-view loss.backward() accumulation into .grad (utils/slam_backend.py:262-306). */
 int lvdgs_gaussian_backward_batch(const lvdgs_args *const *views, int32_t count, void *stream);
 
+/* ---- patch-based scale alignment of a keyframe's mono depth (LVD-GS Algorithm 1: reference utils/depth_utils.py process_depth,
+ * called for every keyframe after the first, utils/slam_frontend.py:1380-1405) ----
+ * r = render_depth, m = mono_depth (H x W).  Patches tile the image from (0, 0) in steps of patch_size, edge patches clipped.
+ * Iteration k = 0 .. max_iter-1 with the current scale s (1 at the start), ms = float32(m * s):
+ *   top:  stop if |s - s_prev| < epsilon (float32) and s != 1; s_prev = s;
+ *   a patch PASSES when |mean r - mean ms| < mean_threshold * mean ms and |std r - std ms| < std_threshold * std ms (population
+ *   statistics, float64); in a passing patch a pixel is ACCURATE when
+ *   |(r - mean r) / (std r + 1e-6) - (ms - mean ms) / (std ms + 1e-6)| < error_threshold (NaN: never);
+ *   count < min (= int(min_accurate_pixels_ratio * H * W)) and k == 2 or k == 3: num_accurate = count, the caller's SCALE REMEDY
+ *   gives the next s (k == 2: continue with k = 3; k == 3: stop);
+ *   else num_accurate = 0, and if count > 0 and (k < 2 or count >= min): s = mean r[acc] / mean m[acc] (UNSCALED m), num_accurate = count.
+ * Fill (float32, as NumPy): ms = m * s; error = |r - ms| / (ms + 1e-8) > final_error_threshold or r == 0; final = error ? ms : r.
+ * lvdgs_depth_align enqueues max_iter iteration launches and the fill (an iteration whose state is not RUNNING stands down); no host
+ * wait.  The last launch to change the state copies it to host_state (LVDGS_DEPTH_ALIGN_STATE_WORDS int32 words of page-locked,
+ * mapped host memory: [0] s (float bits), [1] s_prev (float bits), [2] status, [3] k of the last iteration run, [4] num_accurate,
+ * [5] passing patches of the last iteration run, [6] accurate pixels of the last iteration run, [7] 1 once the fill has run).  The
+ * caller synchronises the stream once and reads it.  status LVDGS_DEPTH_ALIGN_REMEDY (final_depth / error_mask not written): the
+ * caller evaluates the remedy and calls lvdgs_depth_align_resume with its scale, which enqueues iteration 3 and the fill (remedy at
+ * k == 2) or the fill alone (k == 3), and synchronises again.  scratch: lvdgs_depth_align_scratch_bytes(W, H, patch_size) bytes,
+ * ZERO-FILLED before its first use (every call leaves it so).  Bit-deterministic: the sums are taken in a fixed order.
+ * LVDGS_E_INVALID: bad sizes, patch_size outside 1..LVDGS_DEPTH_ALIGN_MAX_PATCH, max_iter < 0, a NULL pointer, scratch too small;
+ * LVDGS_E_HIP: host_state is not mapped pinned memory. */
+#define LVDGS_DEPTH_ALIGN_MAX_PATCH 64
+#define LVDGS_DEPTH_ALIGN_STATE_WORDS 8
+enum {
+    LVDGS_DEPTH_ALIGN_RUNNING = 0,
+    LVDGS_DEPTH_ALIGN_CONVERGED = 1,  /* the top-of-iteration test stopped the loop */
+    LVDGS_DEPTH_ALIGN_EXHAUSTED = 2,  /* max_iter iterations ran (or the remedy at k == 3 ended them) */
+    LVDGS_DEPTH_ALIGN_REMEDY = 3      /* too few accurate pixels at k == 2 or 3: the caller's remedy is due */
+};
+typedef struct lvdgs_depth_align_args {
+    int32_t width, height, patch_size, max_iter;
+    double mean_threshold, std_threshold, error_threshold, final_error_threshold, epsilon, min_accurate_pixels_ratio;
+    const float *render_depth;   /* H*W                                             */
+    const float *mono_depth;     /* H*W                                             */
+    float *final_depth;          /* out H*W                                         */
+    uint8_t *error_mask;         /* out H*W bytes (0 / 1)                           */
+    int32_t *host_state;         /* LVDGS_DEPTH_ALIGN_STATE_WORDS, pinned host (the host address) */
+    void *scratch; size_t scratch_bytes;
+} lvdgs_depth_align_args;
+size_t lvdgs_depth_align_scratch_bytes(int32_t width, int32_t height, int32_t patch_size);
+int lvdgs_depth_align(const lvdgs_depth_align_args *a, void *stream);
+int lvdgs_depth_align_resume(const lvdgs_depth_align_args *a, float scale, void *stream);
+
 /* ---- diagnostics ---- */
 const char *lvdgs_last_error(void);
 const char *lvdgs_version(void);

@@ -115,6 +115,21 @@ class MaskedLossArgs(C.Structure):
     ]
 
 
+class DepthAlignArgs(C.Structure):
+    """struct lvdgs_depth_align_args (include/lvdgs.h)."""
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32), ("patch_size", C.c_int32), ("max_iter", C.c_int32),
+        ("mean_threshold", C.c_double), ("std_threshold", C.c_double), ("error_threshold", C.c_double),
+        ("final_error_threshold", C.c_double), ("epsilon", C.c_double), ("min_accurate_pixels_ratio", C.c_double),
+        ("render_depth", _fp), ("mono_depth", _fp), ("final_depth", _fp), ("error_mask", _fp), ("host_state", _fp),
+        ("scratch", _fp), ("scratch_bytes", C.c_size_t),
+    ]
+
+
+DEPTH_ALIGN_MAX_PATCH, DEPTH_ALIGN_STATE_WORDS = 64, 8
+DEPTH_ALIGN_RUNNING, DEPTH_ALIGN_CONVERGED, DEPTH_ALIGN_EXHAUSTED, DEPTH_ALIGN_REMEDY = 0, 1, 2, 3
+
+
 class StateLayout(C.Structure):
     _fields_ = [(n, C.c_size_t) for n in (
         "geom_rec", "geom_tiles_touched", "geom_slot_base", "bin_point_list", "bin_tile_keys",
@@ -134,7 +149,8 @@ EXPORTS = (
     "lvdgs_dist2_knn3", "lvdgs_rope2d", "lvdgs_rope2d_strided", "lvdgs_loss_scratch_bytes", "lvdgs_photometric_loss_forward",
     "lvdgs_photometric_loss_backward", "lvdgs_photometric_loss_value_and_grad", "lvdgs_photometric_loss_partials", "lvdgs_tracking_tail", "lvdgs_backward_fused_loss", "lvdgs_blend_forward_batch", "lvdgs_blend_backward_fused_loss_batch", "lvdgs_masked_depth_scratch_bytes", "lvdgs_masked_depth_l1_forward",
     "lvdgs_masked_depth_l1_backward", "lvdgs_pose_step", "lvdgs_host_device_pointer", "lvdgs_pose_step_batch", "lvdgs_adam_step", "lvdgs_isotropic_scratch_bytes", "lvdgs_isotropic_reg", "lvdgs_view_stats", "lvdgs_map_stats_apply", "lvdgs_map_view_tail", "lvdgs_ssim_scratch_bytes", "lvdgs_ssim_l1",
-    "lvdgs_masked_loss_scratch_bytes", "lvdgs_masked_loss_batch", "lvdgs_backward_masked_loss", "lvdgs_blend_backward_window_batch", "lvdgs_forward_batch", "lvdgs_forward_backward_fused_loss", "lvdgs_map_view_tail_batch", "lvdgs_gaussian_backward_batch", "lvdgs_last_error", "lvdgs_version", "lvdgs_profile_enable",
+    "lvdgs_masked_loss_scratch_bytes", "lvdgs_masked_loss_batch", "lvdgs_backward_masked_loss", "lvdgs_blend_backward_window_batch", "lvdgs_forward_batch", "lvdgs_forward_backward_fused_loss", "lvdgs_map_view_tail_batch", "lvdgs_gaussian_backward_batch",
+    "lvdgs_depth_align_scratch_bytes", "lvdgs_depth_align", "lvdgs_depth_align_resume", "lvdgs_last_error", "lvdgs_version", "lvdgs_profile_enable",
     "lvdgs_profile_reset", "lvdgs_profile_read",
 )
 
@@ -217,6 +233,10 @@ def lib():
         L.lvdgs_gaussian_backward_batch.argtypes = [C.POINTER(C.POINTER(Args)), C.c_int32, C.c_void_p]
         L.lvdgs_blend_backward_window_batch.argtypes = [C.POINTER(C.POINTER(Args)), C.POINTER(C.POINTER(LossArgs)), C.POINTER(C.POINTER(MaskedLossArgs)),
                                                         C.c_int32, C.c_int32, C.c_void_p]
+        L.lvdgs_depth_align_scratch_bytes.restype = C.c_size_t
+        L.lvdgs_depth_align_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+        L.lvdgs_depth_align.argtypes = [C.POINTER(DepthAlignArgs), C.c_void_p]
+        L.lvdgs_depth_align_resume.argtypes = [C.POINTER(DepthAlignArgs), C.c_float, C.c_void_p]
         L.lvdgs_profile_enable.argtypes = [C.c_int]
         L.lvdgs_profile_read.argtypes = [C.POINTER(KernelTime), C.c_int]
         _lib = L

@@ -25,8 +25,10 @@ iterations per tracked frame (``idle_map_iters``; in the reference that number i
 Stand-ins for what is out of scope, all injectable:
   * the pose initialisation: the previous frame's pose -- the reference's own branch for "MASt3R returned the identity";
   * ``keyframe_depth``: the depth map a new keyframe seeds Gaussians from.  Default: the keyframe's mono depth under the valid-pixel
-    mask, i.e. ``add_new_keyframe``'s own statements for the first keyframe (:1364-1382) applied to every keyframe -- for later
-    keyframes the reference blends rendered and MASt3R depth patch by patch (``process_depth``, utils/depth_utils.py, needs MASt3R);
+    mask, i.e. ``add_new_keyframe``'s own statements for the first keyframe (:1364-1382) applied to every keyframe.  For later
+    keyframes the reference blends rendered and mono depth patch by patch and rescales the mono depth (``process_depth``,
+    utils/depth_utils.py, :1383-1405): ``keyframe_depth="patch_align"`` does that (``depth_utils.process_depth``, HIP); only the
+    algorithm's scale remedy ``find_scale`` needs MASt3R -- injectable as ``scale_remedy``, by default the current scale is kept;
   * ``dataset.static_mask(idx)`` for the GroundingDINO + SAM masks (``dynamic_masker.get_static_mask_for_gaussian_init``).
 
 ``render_fn`` / ``view_loss_fn`` / ``refine_loss_fn`` / ``knn_fn`` default to the HIP paths; the CPU tests pass the dense float64
@@ -104,14 +106,28 @@ class SlamSequence:
 
     def __init__(self, config, dataset, gaussians, pipeline_params, background, *, fused="auto", render_fn=render, view_loss_fn=None,
                  refine_loss_fn=None, keyframe_depth=None, idle_map_iters=0, camera_cls=None, cameras_extent=6.0, on_event=None,
-                 group=None, aux_group=None, bands_ok=None):
+                 group=None, aux_group=None, bands_ok=None, depth_align_fn=None, scale_remedy=None, depth_align_params=None):
         from .backend_map import map_window
         if camera_cls is None:
             from .camera_utils import Camera as camera_cls
         self.config, self.dataset, self.gaussians = config, dataset, gaussians
         self.pipeline_params, self.background = pipeline_params, background
         self.fused, self.render_fn, self.view_loss_fn, self.refine_loss_fn = fused, render_fn, view_loss_fn, refine_loss_fn
-        self.keyframe_depth = keyframe_depth if keyframe_depth is not None else self.default_keyframe_depth
+        # keyframe_depth: None / "mono" (the default), "patch_align" (Algorithm 1 for every keyframe after the first), or a callable.
+        # depth_align_fn: process_depth's signature (default depth_utils.process_depth); depth_align_params: its keyword parameters
+        # (patch_size, thresholds, ...: the reference's config["depth"]); scale_remedy: find_scale's arguments -> a scale, or None to keep it
+        self.patch_align = keyframe_depth == "patch_align"
+        if keyframe_depth is None or keyframe_depth == "mono":
+            self.keyframe_depth = self.default_keyframe_depth
+        elif self.patch_align:
+            self.keyframe_depth = self.patch_align_keyframe_depth
+        elif callable(keyframe_depth):
+            self.keyframe_depth = keyframe_depth
+        else:
+            raise ValueError(f"keyframe_depth: None, 'mono', 'patch_align' or a callable, not {keyframe_depth!r}")
+        self.depth_align_fn, self.scale_remedy = depth_align_fn, scale_remedy
+        self.depth_align_params = dict(depth_align_params or {})
+        self.depth_align_log = []      # per aligned keyframe: frame, scale_factor, num_accurate_pixels, error_pixel_share, remedy_fired
         self.idle_map_iters, self.camera_cls, self.on_event = int(idle_map_iters), camera_cls, on_event
         self._map_window = map_window
         # several ranks (torch.distributed initialised): every rank runs the whole sequence -- tracking, map initialisation and colour
@@ -137,6 +153,8 @@ class SlamSequence:
                            refinement_iterations=0)
         self.gaussian_counts = []      # (event, N) whenever the map's size may have changed
         self.seconds = dict(tracking=0.0, mapping=0.0, init=0.0, seeding=0.0, refinement=0.0, other=0.0)
+        if self.patch_align:
+            self.seconds["depth_align"] = 0.0
         self.window_log = []           # the window after every keyframe
         self.frame_log = []            # per tracked frame: tracking iterations, the keyframe test's inputs and its outcome
         self.batched_sizes = []        # the map's size at every mapping call that went through the batched window (MapWindowBatch)
@@ -210,6 +228,38 @@ class SlamSequence:
         d = torch.from_numpy(np.asarray(viewpoint.mono_depth)).clone().unsqueeze(0)
         d[~valid_rgb.cpu()] = 0
         return d[0].numpy()
+
+    def patch_align_keyframe_depth(self, viewpoint, render_pkg, valid_rgb, init):
+        """``add_new_keyframe``'s statements for every keyframe after the first (:1383-1405): ``process_depth`` on the tracking render's
+        depth and the keyframe's mono depth (the previous keyframe's mono depth and image go to the scale remedy), the mono depth
+        rescaled by the scale found, the result zero where invalid.  The first keyframe keeps the mono path (``init``)."""
+        if init or render_pkg is None or len(self.kf_indices) < 2:
+            return self.default_keyframe_depth(viewpoint, render_pkg, valid_rgb, init)
+        from . import depth_utils
+        fn = self.depth_align_fn or depth_utils.process_depth
+        prev = self.cameras[self.kf_indices[-2]]
+        fired = []
+
+        def remedy(im1, im2, last_depth, mono_depth, model):
+            fired.append(True)
+            return None if self.scale_remedy is None else self.scale_remedy(im1, im2, last_depth, mono_depth, model)
+
+        with self._timed("depth_align"):
+            final, scale, error_mask, num_accurate = fn(render_pkg["depth"].detach(), viewpoint.mono_depth, last_depth=prev.mono_depth,
+                                                        im1=prev.original_image, im2=viewpoint.original_image, model=None,
+                                                        scale_remedy=remedy, **self.depth_align_params)
+            viewpoint.mono_depth = (np.asarray(viewpoint.mono_depth, dtype=np.float32) * np.float32(scale)).astype(np.float32)
+            if torch.is_tensor(final):
+                final = final.clone()
+                final[~valid_rgb[0].to(final.device)] = 0
+                share = float(error_mask.float().mean())
+            else:
+                final = np.array(final, dtype=np.float32)
+                final[~valid_rgb[0].cpu().numpy()] = 0
+                share = float(np.mean(error_mask))
+        self.depth_align_log.append(dict(frame=int(self.kf_indices[-1]), scale_factor=float(scale), num_accurate_pixels=int(num_accurate),
+                                         error_pixel_share=share, remedy_fired=bool(fired)))
+        return final
 
     def add_new_keyframe(self, cur_frame_idx, render_pkg=None, init=False):
         """utils/slam_frontend.py:1268-1414 without the detector and MASt3R: rotation to the last keyframe, the valid-pixel mask
@@ -420,4 +470,5 @@ class SlamSequence:
                     frames_per_s=None if not s.get("wall") else round(c["frames"] / s["wall"], 3),
                     tracking_plus_mapping_iterations_per_s=None if not loops else round(its / loops, 2),
                     tracking_iterations_per_s=None if not s.get("tracking") else round(c["tracking_iterations"] / s["tracking"], 2),
-                    mapping_iterations_per_s=None if not s.get("mapping") else round(c["mapping_iterations"] / s["mapping"], 2))
+                    mapping_iterations_per_s=None if not s.get("mapping") else round(c["mapping_iterations"] / s["mapping"], 2),
+                    **({"depth_align": list(self.depth_align_log)} if self.patch_align else {}))

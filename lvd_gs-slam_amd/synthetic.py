@@ -202,13 +202,16 @@ class SequenceDataset:
 
 
 def make_sequence(truth, render_fn, pipe, W, H, n_frames, device, fx=None, fy=None, cx=None, cy=None, seed=0, depth_noise=0.02,
-                  image_noise=0.0, dynamic_objects=False, step=0.02, sway=0.15, yaw=0.03, period=40.0, camera_cls=None):
+                  image_noise=0.0, dynamic_objects=False, step=0.02, sway=0.15, yaw=0.03, period=40.0, camera_cls=None, mono_scale_drift=0.0):
     """``n_frames`` frames of ``vehicle_trajectory`` through the map ``truth`` (a GaussianModel), rendered ONCE by ``render_fn``
     (the product's ``render`` on the GPU, the dense float64 renderer in the CPU tests): image = clamped render (+ seeded pixel
     noise), mono depth = expected depth of the opaque pixels x (1 + ``depth_noise`` N(0,1)) -- a metric depth predictor's output,
     what ``get_depth`` (MASt3R, out of scope) hands the reference's front end.  ``dynamic_objects``: every frame also carries two
     to four flat-coloured rectangles ("vehicles", ``dynamic_object_mask``, redrawn per frame: they move) painted over the image
-    and marked dynamic in ``static_mask(idx)``."""
+    and marked dynamic in ``static_mask(idx)``.  ``mono_scale_drift``: frame i's mono depth is further multiplied by
+    ``mono_scale_factor(i, mono_scale_drift)`` -- a monocular predictor's per-frame scale inconsistency, what the keyframe depth
+    alignment (LVD-GS Algorithm 1) exists for; deterministic, no random draws (at 0 the dataset is bit-identical to one made without
+    it).  The factors are kept as ``dataset.mono_scales``."""
     if camera_cls is None:
         from .camera_utils import Camera as camera_cls
     fx = float(W) if fx is None else fx
@@ -233,6 +236,8 @@ def make_sequence(truth, render_fn, pipe, W, H, n_frames, device, fx=None, fy=No
         opac = pkg["opacity"][0].detach().float()
         depth = torch.where(opac > 0.5, pkg["depth"][0].detach().float() / opac.clamp(min=1e-3), torch.zeros_like(opac))
         depth = depth * (1.0 + depth_noise * torch.randn(H, W, generator=gen).to(depth.device))
+        if mono_scale_drift:
+            depth = depth * mono_scale_factor(i, mono_scale_drift)
         if dynamic_objects:
             m = dynamic_object_mask(H, W, 100 * seed + i)
             colour = torch.rand(3, generator=gen)
@@ -240,4 +245,12 @@ def make_sequence(truth, render_fn, pipe, W, H, n_frames, device, fx=None, fy=No
             masks.append(m.to(device))
         images.append(img.contiguous().to(device))
         monos.append(depth.cpu().numpy().astype("float32"))
-    return SequenceDataset(images, monos, poses, W, H, fx, fy, cx, cy, device, static_masks=masks if dynamic_objects else None)
+    ds = SequenceDataset(images, monos, poses, W, H, fx, fy, cx, cy, device, static_masks=masks if dynamic_objects else None)
+    ds.mono_scales = [mono_scale_factor(i, mono_scale_drift) if mono_scale_drift else 1.0 for i in range(len(poses))]
+    return ds
+
+
+def mono_scale_factor(i, drift):
+    """Frame i's mono depth scale under ``make_sequence(..., mono_scale_drift=drift)``: 1 + drift * sin(2 pi i / 11) -- a
+    wander between 1 - drift and 1 + drift that never repeats within a short drive."""
+    return 1.0 + drift * math.sin(2.0 * math.pi * i / 11.0)

@@ -72,7 +72,7 @@ GEOMETRY = {"kitti07": dict(W=1226, H=370, fx=707.0912, cx=601.8873, cy=183.1104
 
 
 def kitti_sequence(dev, frames=60, scale=1.0, cadence="reference", masks=True, n_true=None, seed=0, training=None, window_size=None, geometry="kitti07",
-                   pcd_downsample=None):
+                   pcd_downsample=None, mono_scale_drift=0.0):
     """(config, dataset, true map): a frame geometry of ``GEOMETRY`` (x ``scale``), the merged KITTI-07 config with the chosen cadence."""
     geo = GEOMETRY[geometry]
     W, H = int(round(geo["W"] * scale)), int(round(geo["H"] * scale))
@@ -95,16 +95,17 @@ def kitti_sequence(dev, frames=60, scale=1.0, cadence="reference", masks=True, n
     # of view is wider than the generator's (fx < W) and the camera moves
     truth = truth_model(W, H, n_true, 1.5 * scale, 16.0 * scale, 0.9, dev, seed=11 + seed)
     ds = synthetic.make_sequence(truth, render, PIPE, W, H, frames, dev, fx=fx, fy=fy, cx=cx, cy=cy, seed=seed, depth_noise=0.02,
-                                 image_noise=0.01, dynamic_objects=masks, step=0.02, sway=0.15, yaw=0.03, period=40.0)
+                                 image_noise=0.01, dynamic_objects=masks, step=0.02, sway=0.15, yaw=0.03, period=40.0,
+                                 mono_scale_drift=mono_scale_drift)
     return cfg, ds, truth
 
 
 def run_sequence(dev, frames=60, scale=1.0, cadence="reference", fused="auto", idle=10, refine=500, masks=True, seed=0, training=None,
-                 window_size=None, on_event=None, geometry="kitti07", pcd_downsample=None, **sequence_kwargs):
+                 window_size=None, on_event=None, geometry="kitti07", pcd_downsample=None, mono_scale_drift=0.0, **sequence_kwargs):
     torch.manual_seed(seed)
     random.seed(seed)
     cfg, ds, truth = kitti_sequence(dev, frames, scale, cadence, masks, seed=seed, training=training, window_size=window_size, geometry=geometry,
-                                    pcd_downsample=pcd_downsample)
+                                    pcd_downsample=pcd_downsample, mono_scale_drift=mono_scale_drift)
     del truth
     m = empty_map(cfg, dev)
     seq = SlamSequence(cfg, ds, m, PIPE, torch.zeros(3, device=dev), fused=fused, idle_map_iters=idle, on_event=on_event, **sequence_kwargs)
@@ -127,6 +128,8 @@ def run_sequence(dev, frames=60, scale=1.0, cadence="reference", fused="auto", i
     out["window_log"] = seq.window_log
     out["batched_window_runs"] = int(getattr(getattr(seq.backend, "_lvdgs_window_batch", None), "runs", 0))
     out.update(geometry=geometry, width=ds.width, height=ds.height, cadence=cadence, fused=fused, idle_map_iters=idle, keyframes_carry_static_mask=masks)
+    if mono_scale_drift or sequence_kwargs.get("keyframe_depth") is not None:
+        out.update(mono_scale_drift=mono_scale_drift, keyframe_depth=sequence_kwargs.get("keyframe_depth") or "mono")
     return out, seq
 
 
@@ -144,13 +147,17 @@ def main():
     ap.add_argument("--pcd-downsample", type=int, nargs=2, default=None, metavar=("INIT", "KEYFRAME"),
                     help="seed one Gaussian per INIT valid pixels of frame 0 and per KEYFRAME of every later keyframe (the config's 32 / 64): smaller = a larger map")
     ap.add_argument("--seed", type=int, default=0, help="scene, trajectory noise, dynamic objects and the loops' random draws")
+    ap.add_argument("--keyframe-depth", choices=["mono", "patch_align"], default="mono",
+                    help="seed later keyframes from the mono depth (default) or from LVD-GS Algorithm 1's alignment to the rendered depth")
+    ap.add_argument("--mono-scale-drift", type=float, default=0.0, help="per-frame scale wander of the synthetic mono depth (synthetic.mono_scale_factor)")
     ap.add_argument("--verbose", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     t0 = time.perf_counter()
     ev = (lambda e, s: print(f"  frame {s.counts['frames']:3d} {e:16s} N = {s._n()}", file=sys.stderr)) if a.verbose else None
     out, _ = run_sequence(dev, a.frames, a.scale, a.cadence, False if a.no_fused else "auto", a.idle, a.refine, not a.no_masks, seed=a.seed,
-                          window_size=a.window_size, on_event=ev, geometry=a.geometry, pcd_downsample=a.pcd_downsample)
+                          window_size=a.window_size, on_event=ev, geometry=a.geometry, pcd_downsample=a.pcd_downsample,
+                          mono_scale_drift=a.mono_scale_drift, **({"keyframe_depth": "patch_align"} if a.keyframe_depth == "patch_align" else {}))
     out["seed"] = a.seed
     out["tool_seconds"] = round(time.perf_counter() - t0, 2)
     print(json.dumps(out))
