@@ -153,7 +153,11 @@ enum {
                                       the keys to scatter and sort there -- and every tile's list is read off its super-tile's sorted list.  point_list,
                                       ranges and every output are the same bits with and without it; worth setting when num_rendered exceeds ~16 pairs per
                                       Gaussian (lvdgs.rasterizer decides from the previous frame's count).  Ignored with LVDGS_FLAG_LIST_ALL_TILES, with a
-                                      band of tile rows and on frames of fewer than 64 tiles; the views of lvdgs_forward_batch must agree on it.
+                                      band of tile rows, on frames of fewer than 64 tiles and by lvdgs_forward_render; the views of lvdgs_forward_batch must agree on it.
+                                      The super-tile lists share pair_capacity and may hold more pairs than the tile lists (a Gaussian whose rectangle spans more
+                                      than 64 super-tiles is listed on all of them); when they outgrow the capacity and the tile lists do not, lvdgs_forward,
+                                      lvdgs_forward_batch (per view) and lvdgs_forward_backward_fused_loss redo the view without the hint inside the call and
+                                      return LVDGS_OK with the tile pair count -- num_rendered and LVDGS_E_CAPACITY concern the tile lists alone.
                                       B: the per-Gaussian pass of lvdgs_backward*, lvdgs_forward_backward_fused_loss and lvdgs_gaussian_backward_batch runs with helper waves (workgroups of eight waves: the second half of a
                                       large-footprint wave's pair records is summed beside the first) -- the same sums in the same order, sooner. */
     LVDGS_FLAG_POSE_ONLY = 4,      /* B: only the camera-pose gradient (dL_dtau, or its partial sums for lvdgs_tracking_tail) and --

@@ -315,7 +315,8 @@ namespace {
 struct PairProbe {
     int device = -1;
     uint32_t *pinned = nullptr;   // [0] pair count, [1] longest queued tile segment of the frame, [2] length of that queue, [3] sequence number of the call that wrote them;
-                                  // [16 + 4 k ...]: the same four words of view k of lvdgs_forward_batch
+                                  // [8 ...]: the first three of them for the super-tile lists of the two-level grouping (LVDGS_FLAG_SUPER_TILES);
+                                  // [16 + 4 k ...]: the same four words of view k of lvdgs_forward_batch, [PROBE_SUPER + 4 k ...] its super-tile lists' three
     uint32_t *pinned_dev = nullptr;   // the same words as the device addresses them
     uint32_t seq = 0;             // of the last single-call forward on this thread and device
     hipEvent_t ready = nullptr;
@@ -323,7 +324,8 @@ struct PairProbe {
     int longest = 0, queued = 0;  // of the previous frame on this device: which kernels for long segments the next frame
     int keep = 0;                 // launches behind its tile sort (a hint, never a result); kept for a few frames
 };
-constexpr int PROBE_WORDS = 16 + 4 * FWD_BATCH_VIEWS + 8;
+constexpr int PROBE_SUPER = 16 + 4 * FWD_BATCH_VIEWS;
+constexpr int PROBE_WORDS = PROBE_SUPER + 4 * FWD_BATCH_VIEWS + 8;
 thread_local PairProbe g_probe[16];
 
 int get_probe(PairProbe **out) {
@@ -475,6 +477,18 @@ int check_render_buffers(const lvdgs_args *a, int64_t cap) {
     }
     return LVDGS_OK;
 }
+
+// Two-level grouping whose super lists outgrew the pair capacity while the tile lists fit (Ds > cap >= D: a Gaussian whose rectangle spans
+// more than 64 super-tiles is listed on all of them, however few of its tiles are kept): the tile lists read off the super lists were cut
+// short.  The view is redone one-level behind what is enqueued -- the projection's counts, geom_state and slot_base stand -- with no
+// further host wait; the flag's contract makes the bits those the hint would have given.
+int enqueue_render_one_level(const lvdgs_args *a, int64_t cap, hipStream_t s) {
+    lvdgs_args one = *a;
+    one.flags &= ~LVDGS_FLAG_SUPER_TILES;
+    // (the blend of the cut lists counted into n_touched; the counting path's projection cleared it)
+    if (int e = check_hip(hipMemsetAsync(a->n_touched, 0, sizeof(int32_t) * (size_t)a->num_gaussians, s), "memset n_touched")) return e;
+    return enqueue_render(&one, cap, true, s, true, nullptr);
+}
 }  // namespace
 
 int lvdgs_forward_prepare(const lvdgs_args *a, int64_t *num_rendered, void *stream) {
@@ -506,7 +520,11 @@ int lvdgs_forward_render(const lvdgs_args *a, void *stream) {
     const int64_t D = a->num_gaussians == 0 ? 0 : a->num_rendered;
     if (D < 0) { set_error("negative num_rendered"); return LVDGS_E_INVALID; }
     if (int e = check_render_buffers(a, D)) return e;
-    return enqueue_render(a, D, false, s);
+    // (two-level grouping is left out: the super lists' count is not known here, and this call is the rare re-render behind a count
+    // that outgrew the capacity -- the contract makes the bits the same)
+    lvdgs_args one = *a;
+    one.flags &= ~LVDGS_FLAG_SUPER_TILES;
+    return enqueue_render(&one, D, false, s);
 }
 
 int lvdgs_forward(const lvdgs_args *a, int64_t *num_rendered, void *stream) {
@@ -551,13 +569,13 @@ int lvdgs_forward(const lvdgs_args *a, int64_t *num_rendered, void *stream) {
         if (int e = wait_for_sequence(probe)) return e;
     } else if (int e = check_hip(hipEventSynchronize(probe->ready), "wait for pair count")) return e;
     const uint32_t total = probe->pinned[0];
+    uint32_t total_super = 0u;   // (two-level grouping: the super lists' pair count -- the sequence number waited for covers it)
     if (counted) {   // what the next frames expect: this frame's long segments, or a recent frame's for a while (views alternate)
         const int longest = (int)probe->pinned[1], queued = (int)probe->pinned[2];
         if (longest >= probe->longest || probe->keep == 0) { probe->longest = longest; probe->queued = queued; probe->keep = longest ? 32 : 0; }
         else probe->keep--;
         if (super_tiles_in_use(*a)) {
-            // (the super scan runs behind the tile scan whose sequence number was waited for: these two words may still be the previous
-            // frame's -- they are hints for the next frame's sort launch either way)
+            total_super = probe->pinned[8];
             probe->longest_super = (int)probe->pinned[8 + 1]; probe->queued_super = (int)probe->pinned[8 + 2];
         }
     }
@@ -567,6 +585,7 @@ int lvdgs_forward(const lvdgs_args *a, int64_t *num_rendered, void *stream) {
         set_error("%u pairs exceed pair_capacity %lld: grow binning_state / scratch and call lvdgs_forward_render", total, (long long)cap);
         return LVDGS_E_CAPACITY;
     }
+    if ((int64_t)total_super > cap) return enqueue_render_one_level(a, cap, s);
     return LVDGS_OK;
 }
 
@@ -678,7 +697,7 @@ int lvdgs_forward_batch(const lvdgs_args *const *views, int32_t count, int64_t *
         const lvdgs_args *const *av = views + first;
         uint32_t *words = probe->pinned + 16, *words_dev = probe->pinned_dev + 16;
         if (int e = launch_preprocess_count_batch(av, &g[first], &im[first], &w[first], m, s)) return e;
-        if (int e = launch_group_scan_batch(av, &g[first], &im[first], &w[first], &caps[first], m, words_dev, probe->seq, s)) return e;
+        if (int e = launch_group_scan_batch(av, &g[first], &im[first], &w[first], &caps[first], m, words_dev, probe->seq, probe->pinned_dev + PROBE_SUPER, s)) return e;
         if (int e = launch_group_scatter_batch(av, &g[first], &im[first], &w[first], &b[first], &caps[first], m, s)) return e;
         const bool super = super_tiles_in_use(*a0);   // two-level grouping: the launches above worked on the super-tile grid; the tiles' lists are read off the sorted super lists
         if (int e = launch_tile_depth_sort_batch(av, &g[first], &im[first], &w[first], &b[first], m, super ? probe->longest_super : probe->longest,
@@ -689,12 +708,19 @@ int lvdgs_forward_batch(const lvdgs_args *const *views, int32_t count, int64_t *
             if (int e = launch_blend_fwd_batch(av, &g[first], &b[first], &im[first], m, probe->longest > 0, s)) return e;
         // everything is enqueued: now the counts (the GPU is busy with the scatter, the sorts and the blend meanwhile)
         int longest = 0, queued = 0;
+        const uint32_t *words_super = probe->pinned + PROBE_SUPER;   // (two-level grouping: view k's super lists' count and hints; the wait covers them)
         for (int k = 0; k < m; k++) {
             if (int e = wait_for_sequence(probe, words + 4 * k)) return e;
             num_rendered[first + k] = (int64_t)words[4 * k];
             longest = std::max(longest, (int)words[4 * k + 1]); queued = std::max(queued, (int)words[4 * k + 2]);
         }
-        if (super) { probe->longest_super = (int)probe->pinned[8 + 1]; probe->queued_super = (int)probe->pinned[8 + 2]; }   // (hints; possibly still the previous call's)
+        if (super) {
+            probe->longest_super = (int)words_super[1]; probe->queued_super = (int)words_super[2];   // (the first view's)
+            // a view whose super lists outgrew its capacity while its tile lists fit: redone one-level (enqueue_render_one_level)
+            for (int k = 0; k < m; k++)
+                if (num_rendered[first + k] <= caps[first + k] && (int64_t)words_super[4 * k] > caps[first + k])
+                    if (int e = enqueue_render_one_level(av[k], caps[first + k], s)) return e;
+        }
         if (m < count) { probe->seq++; if (probe->seq == 0u) probe->seq = 1u; }   // (the next group of views re-uses the words)
         if (longest >= probe->longest || probe->keep == 0) { probe->longest = longest; probe->queued = queued; probe->keep = longest ? 32 : 0; }
         else probe->keep--;
@@ -760,25 +786,30 @@ int lvdgs_forward_backward_fused_loss(const lvdgs_args *a, const lvdgs_loss_args
     fw.flags |= LVDGS_FLAG_NO_BLEND;   // (grouping and tile sort; the blend follows below, together with the backward's)
     if (int e = enqueue_render(&fw, cap, true, s, true, probe)) return e;
     // (both halves of the backward look at the frame's pair count on the device and stand down when it exceeds the capacity)
-    if (int e = launch_blend_fwd_bwd_fused_loss(*a, v.g, v.b, v.im, v.w, lp, propagate_opacity_grad != 0, probe->longest > 0, g.total, (uint32_t)cap, s)) return e;
-    if (int e = launch_preprocess_bwd(*a, v.g, v.w, v.b.pair_valid, s, g.total, (uint32_t)cap)) return e;
+    // (two-level grouping: and when the super lists' count does -- the tile lists read off them were cut short)
+    const bool super = super_tiles_in_use(*a);
+    const uint32_t *total_super_dev = super ? g.total + SUPER_TOTAL_WORD : nullptr;
+    if (int e = launch_blend_fwd_bwd_fused_loss(*a, v.g, v.b, v.im, v.w, lp, propagate_opacity_grad != 0, probe->longest > 0, g.total, (uint32_t)cap, total_super_dev, s)) return e;
+    if (int e = launch_preprocess_bwd(*a, v.g, v.w, v.b.pair_valid, s, g.total, (uint32_t)cap, total_super_dev)) return e;
     if (int e = wait_for_sequence(probe)) return e;
-    const uint32_t total = probe->pinned[0];
+    const uint32_t total = probe->pinned[0], total_super = super ? probe->pinned[8] : 0u;
     {
         const int longest = (int)probe->pinned[1], queued = (int)probe->pinned[2];
         if (longest >= probe->longest || probe->keep == 0) { probe->longest = longest; probe->queued = queued; probe->keep = longest ? 32 : 0; }
         else probe->keep--;
-        if (super_tiles_in_use(*a)) {
-            // (the super scan runs behind the tile scan whose sequence number was waited for: these two words may still be the previous
-            // frame's -- they are hints for the next frame's sort launch either way)
-            probe->longest_super = (int)probe->pinned[8 + 1]; probe->queued_super = (int)probe->pinned[8 + 2];
-        }
+        if (super) { probe->longest_super = (int)probe->pinned[8 + 1]; probe->queued_super = (int)probe->pinned[8 + 2]; }
     }
     if (total > 0x7FFFFFFFu) { set_error("%u (Gaussian, tile) pairs exceed the 2^31 limit", total); return LVDGS_E_RANGE; }
     *num_rendered = (int64_t)total;
     if ((int64_t)total > cap) {
         set_error("%u pairs exceed pair_capacity %lld: grow binning_state / scratch, then lvdgs_forward_render and lvdgs_backward_fused_loss", total, (long long)cap);
         return LVDGS_E_CAPACITY;
+    }
+    if ((int64_t)total_super > cap) {
+        // both passes stood down: the view one-level (enqueue_render_one_level), then the two blend passes and the per-Gaussian pass again
+        if (int e = enqueue_render_one_level(&fw, cap, s)) return e;
+        if (int e = launch_blend_fwd_bwd_fused_loss(*a, v.g, v.b, v.im, v.w, lp, propagate_opacity_grad != 0, probe->longest > 0, nullptr, 0u, nullptr, s)) return e;
+        if (int e = launch_preprocess_bwd(*a, v.g, v.w, v.b.pair_valid, s)) return e;
     }
     return LVDGS_OK;
 }

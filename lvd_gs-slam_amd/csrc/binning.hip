@@ -153,12 +153,15 @@ __global__ void __launch_bounds__(1024) group_colscan_batch_kernel(int T, int nc
 // that the sort needs no pass of its own to find them;
 // tile_order (optional, tiles [t_lo, t_hi)): those tiles by descending list length (in steps of 8 entries; ties in
 // arrival order -- it only decides which workgroup of a blend kernel takes which tile, never a result).
+// arrive (two-level grouping: the tile grid's and the super-tile grid's scans of one view, each with pinned words of its own): a
+// device word both workgroups count on (zero before the launch); the LATER of the two writes host_seq to seq_out, behind both
+// workgroups' words, so that the host's one wait covers both pair counts.  Null: the sequence number goes to host_out[3].
 template <int THREADS>
 __device__ __forceinline__ void group_tilescan_body(int T, const uint32_t *__restrict__ totals, uint32_t capacity,
                                                     uint2 *__restrict__ ranges, uint32_t *__restrict__ total_out,
                                                     uint32_t long_limit, uint32_t *__restrict__ queue_count, uint32_t *__restrict__ queue,
                                                     uint32_t *__restrict__ tile_order, int t_lo, int t_hi, uint32_t *__restrict__ order_valid,
-                                                    uint32_t *host_out, uint32_t host_seq) {
+                                                    uint32_t *host_out, uint32_t host_seq, uint32_t *arrive = nullptr, uint32_t *seq_out = nullptr) {
     static_assert(THREADS == 1024 || THREADS == 512, "the grouping kernels' workgroup sizes (the scan rides in the scatter's launch)");
     __shared__ uint32_t s_scan[1024];
     __shared__ uint32_t s_q, s_longest, s_total;
@@ -236,7 +239,11 @@ __device__ __forceinline__ void group_tilescan_body(int T, const uint32_t *__res
         if (host_out) {
             host_out[0] = s_total; host_out[1] = s_longest; host_out[2] = s_q;
             __threadfence_system();
-            __hip_atomic_store(host_out + 3, host_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (!arrive) __hip_atomic_store(host_out + 3, host_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            else if (__hip_atomic_fetch_add(arrive, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_SYSTEM) == 1u) {   // the second to arrive
+                __threadfence_system();
+                __hip_atomic_store(seq_out, host_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
         }
     }
     if (!tile_order) return;
@@ -296,7 +303,7 @@ __global__ void __launch_bounds__(1024) group_tilescan_kernel(int T, const uint3
     group_tilescan_body<1024>(T, totals, capacity, ranges, total_out, long_limit, queue_count, queue, tile_order, t_lo, t_hi, order_valid, host_out, host_seq);
 }
 // lvdgs_forward_batch: one workgroup per view (blockIdx.x); view k's pair count and hints go to host_out + 4 k
-struct TilescanView { const uint32_t *totals; uint32_t capacity; uint2 *ranges; uint32_t *total_out, *queue_count, *queue, *tile_order, *order_valid; };
+struct TilescanView { const uint32_t *totals; uint32_t capacity; uint2 *ranges; uint32_t *total_out, *queue_count, *queue, *tile_order, *order_valid; uint32_t *arrive = nullptr; };
 struct TilescanBatch { TilescanView v[FWD_BATCH_VIEWS]; };
 __global__ void __launch_bounds__(1024) group_tilescan_batch_kernel(int T, TilescanBatch b, uint32_t long_limit, int t_lo, int t_hi, uint32_t *host_out,
                                                                     uint32_t host_seq) {
@@ -315,10 +322,11 @@ __global__ void __launch_bounds__(1024) group_colscan_pair_kernel(int T0, int T1
     group_colscan_body<R>(T, nchunks, blockIdx.y ? hist1 : hist0, blockIdx.y ? totals1 : totals0, blockIdx.y != 0);   // (grid 0: the tiles' -- totals only)
 }
 struct TilescanPairView { int T; const uint32_t *totals; uint2 *ranges; uint32_t *total_out, *queue_count, *queue, *tile_order; int t_lo, t_hi; uint32_t *order_valid, *host_out; uint32_t host_seq; };
-__global__ void __launch_bounds__(1024) group_tilescan_pair_kernel(TilescanPairView a, TilescanPairView b, uint32_t capacity, uint32_t long_limit) {
+// (arrive, seq_out: see group_tilescan_body -- with host words, the later workgroup of the two writes a's sequence word)
+__global__ void __launch_bounds__(1024) group_tilescan_pair_kernel(TilescanPairView a, TilescanPairView b, uint32_t capacity, uint32_t long_limit, uint32_t *arrive) {
     const TilescanPairView &v = blockIdx.x ? b : a;
     group_tilescan_body<1024>(v.T, v.totals, capacity, v.ranges, v.total_out, long_limit, v.queue_count, v.queue, v.tile_order, v.t_lo, v.t_hi, v.order_valid,
-                              v.host_out, v.host_seq);
+                              v.host_out, a.host_seq, a.host_out ? arrive : nullptr, a.host_out ? a.host_out + 3 : nullptr);
 }
 
 // lvdgs_forward_batch with two-level grouping: both grids of every view (blockIdx.y = 2 * view + grid; blockIdx.x likewise for the range scan)
@@ -335,10 +343,12 @@ __global__ void __launch_bounds__(1024) group_tilescan_pair_batch_kernel(int T0,
                                                                          uint32_t *host_out, uint32_t host_seq, uint32_t *host_super) {
     const TilescanView &v = b.v[blockIdx.x];
     const int grid = blockIdx.x & 1, view = blockIdx.x >> 1;
-    // (the tile grid's workgroup writes the view's four pinned words -- count, hints, the sequence number the host waits for; of the
-    // super grids the first view's leaves its hints -- longest queued list, queue length -- for the next call's sort launch)
+    // (the tile grid's workgroup writes the view's pair count and hints to host_out + 4 view, the super grid's its super pair count and hints
+    // to host_super + 4 view -- the first view's hints are the next call's sort launch's -- and the later of the two the sequence number the
+    // host waits for, behind host_out + 4 view)
     group_tilescan_body<1024>(grid ? T1 : T0, v.totals, v.capacity, v.ranges, v.total_out, long_limit, v.queue_count, v.queue, v.tile_order,
-                              grid ? 0 : t_lo, grid ? T1 : t_hi, v.order_valid, grid ? (view == 0 ? host_super : nullptr) : host_out + 4 * view, grid ? 0u : host_seq);
+                              grid ? 0 : t_lo, grid ? T1 : t_hi, v.order_valid, host_out ? (grid ? host_super : host_out) + 4 * view : nullptr, host_seq,
+                              host_out ? v.arrive : nullptr, host_out ? host_out + 4 * view + 3 : nullptr);
 }
 
 // SLOT_SCAN (lvdgs_forward): also makes slot_base[i] = exclusive scan of tiles_touched in id order (the backward's
@@ -634,6 +644,9 @@ __device__ __forceinline__ void expand_super_body(int gx, int gy, int gxs, const
         }
         __syncthreads();
     }
+    // A super list cut short at the pair capacity (the super count beyond it, the tile count within) leaves the tail of the tile's segment
+    // unwritten: id 0 there -- a record of the map -- for the passes enqueued before the host's verdict, which redoes the view one-level.
+    for (uint32_t q = out + (uint32_t)lane; q < mine.y; q += 64u) point_list[q] = 0u;
 }
 __global__ void __launch_bounds__(64 * SUPER * SUPER) expand_super_kernel(int gx, int gy, int gxs, const uint2 *__restrict__ ranges_s,
                                                                         const uint32_t *__restrict__ super_list, const uint4 *__restrict__ rect,
@@ -711,13 +724,14 @@ int launch_group_scan(const lvdgs_args &a, const ImageView &im, const RenderScra
         else if (nchunks <= 16 * 16) hipLaunchKernelGGL(group_colscan_pair_kernel<16>, grid, dim3(1024), 0, s, T, Ts, nchunks, w.group_hist, w.group_totals, sv.hist, sv.totals);
         else if (nchunks <= 32 * 16) hipLaunchKernelGGL(group_colscan_pair_kernel<32>, grid, dim3(1024), 0, s, T, Ts, nchunks, w.group_hist, w.group_totals, sv.hist, sv.totals);
         else hipLaunchKernelGGL(group_colscan_pair_kernel<0>, grid, dim3(1024), 0, s, T, Ts, nchunks, w.group_hist, w.group_totals, sv.hist, sv.totals);
-        // (the super grid's hints -- longest queued list, queue length -- go to the pinned words behind the call's own four: for the NEXT
-        // frame's sort launch, read whenever; only the tile grid's workgroup writes the sequence number the host waits for)
+        // (the super grid's pair count and hints -- longest queued list, queue length -- go to the pinned words behind the call's own four;
+        // the later of the two workgroups writes the sequence number the host waits for: the host's verdict takes both pair counts)
         const TilescanPairView tv{T, w.group_totals, im.ranges, total_out, im.long_count, im.long_tiles, tile_order_in_use(T) ? im.long_tiles + T : nullptr,
                                   row0 * gx, row1 * gx, im.long_count + 1, host_out, host_seq};
-        const TilescanPairView sv2{Ts, sv.totals, sv.ranges, sv.total, sv.long_count, sv.long_tiles, tile_order_in_use(Ts) ? sv.long_tiles + Ts : nullptr,
+        const TilescanPairView sv2{Ts, sv.totals, sv.ranges, total_out ? total_out + SUPER_TOTAL_WORD : sv.total, sv.long_count, sv.long_tiles, tile_order_in_use(Ts) ? sv.long_tiles + Ts : nullptr,
                                    0, Ts, sv.long_count + 1, host_out ? host_out + 8 : nullptr, 0u};
-        hipLaunchKernelGGL(group_tilescan_pair_kernel, dim3(2), dim3(1024), 0, s, tv, sv2, (uint32_t)capacity, (uint32_t)tile_sort_wave_limit());
+        hipLaunchKernelGGL(group_tilescan_pair_kernel, dim3(2), dim3(1024), 0, s, tv, sv2, (uint32_t)capacity, (uint32_t)tile_sort_wave_limit(),
+                           sv.long_count + SUPER_ARRIVE_WORD);
         LVDGS_LAUNCH_CHECK("group_scan (two-level)", a.debug, s);
         return LVDGS_OK;
     }
@@ -836,7 +850,7 @@ int launch_super_expand(const lvdgs_args &a, const GeomView &g, const SuperView 
 
 // ---- lvdgs_forward_batch: the same stages for n views of one map and one image size, one launch each ----
 int launch_group_scan_batch(const lvdgs_args *const *a, const GeomView *g, const ImageView *im, const RenderScratch *w, const int64_t *caps, int n,
-                            uint32_t *host_words, uint32_t host_seq, hipStream_t s) {
+                            uint32_t *host_words, uint32_t host_seq, uint32_t *host_super, hipStream_t s) {
     const int N = a[0]->num_gaussians;
     const int gx = (a[0]->image_width + TILE - 1) / TILE, gy = (a[0]->image_height + TILE - 1) / TILE, T = gx * gy;
     if (N == 0 || T == 0 || n == 0) return LVDGS_OK;
@@ -861,9 +875,9 @@ int launch_group_scan_batch(const lvdgs_args *const *a, const GeomView *g, const
             cpb.hist[2 * k] = w[k].group_hist; cpb.totals[2 * k] = w[k].group_totals;
             cpb.hist[2 * k + 1] = sv.hist; cpb.totals[2 * k + 1] = sv.totals;
             tpb.v[2 * k] = TilescanView{w[k].group_totals, (uint32_t)caps[k], im[k].ranges, g[k].total, im[k].long_count, im[k].long_tiles,
-                                        tile_order_in_use(T) ? im[k].long_tiles + T : nullptr, im[k].long_count + 1};
-            tpb.v[2 * k + 1] = TilescanView{sv.totals, (uint32_t)caps[k], sv.ranges, sv.total, sv.long_count, sv.long_tiles,
-                                            tile_order_in_use(Ts) ? sv.long_tiles + Ts : nullptr, sv.long_count + 1};
+                                        tile_order_in_use(T) ? im[k].long_tiles + T : nullptr, im[k].long_count + 1, sv.long_count + SUPER_ARRIVE_WORD};
+            tpb.v[2 * k + 1] = TilescanView{sv.totals, (uint32_t)caps[k], sv.ranges, g[k].total + SUPER_TOTAL_WORD, sv.long_count, sv.long_tiles,
+                                            tile_order_in_use(Ts) ? sv.long_tiles + Ts : nullptr, sv.long_count + 1, sv.long_count + SUPER_ARRIVE_WORD};
         }
         const dim3 grid2(cdiv(T, COLSCAN_TILES), 2 * n);
         if (nchunks <= 8 * 16) hipLaunchKernelGGL(group_colscan_pair_batch_kernel<8>, grid2, dim3(1024), 0, s, T, Ts, nchunks, cpb);
@@ -871,7 +885,7 @@ int launch_group_scan_batch(const lvdgs_args *const *a, const GeomView *g, const
         else if (nchunks <= 32 * 16) hipLaunchKernelGGL(group_colscan_pair_batch_kernel<32>, grid2, dim3(1024), 0, s, T, Ts, nchunks, cpb);
         else hipLaunchKernelGGL(group_colscan_pair_batch_kernel<0>, grid2, dim3(1024), 0, s, T, Ts, nchunks, cpb);
         hipLaunchKernelGGL(group_tilescan_pair_batch_kernel, dim3(2 * n), dim3(1024), 0, s, T, Ts, tpb, (uint32_t)tile_sort_wave_limit(), row0 * gx, row1 * gx, host_words,
-                           host_seq, host_words ? host_words - 8 : nullptr);   // (the call's pinned words: [8..11] the super grid's hints, [16 + 4 k..] view k's)
+                           host_seq, host_super);
         LVDGS_LAUNCH_CHECK("group_scan (batch, two-level)", a[0]->debug, s);
         return LVDGS_OK;
     }

@@ -68,8 +68,9 @@ struct BlendParams {
     int loss_mode;               // LOSS_FUSED or LOSS_MASKED: which of the two this VIEW takes in a launch compiled for LOSS_PER_VIEW
     // blend_fwd_bwd_kernel (forward and backward in one launch, enqueued before the host knows the pair count): the frame's count as the
     // tile scan left it and the capacity the record buffer was sized for -- beyond it the backward half is left out (its slots
-    // would lie outside the buffer; the caller re-runs both passes with room)
-    const uint32_t *pair_total;
+    // would lie outside the buffer; the caller re-runs both passes with room).  pair_total_super (two-level grouping): the super lists' count,
+    // the same verdict -- the tile lists read off them were cut short when it exceeds the capacity
+    const uint32_t *pair_total, *pair_total_super;
     uint32_t pair_capacity;
 };
 #ifndef LVDGS_HEAVY_PRIO
@@ -798,7 +799,8 @@ __global__ void __launch_bounds__(256, POSE_ONLY ? (DEPTH_GRAD ? 6 : LVDGS_BWD_W
     }
 #endif
     blend_fwd2_body<DEEP_LISTS>(p, u.f);
-    if (p.pair_total && *p.pair_total > p.pair_capacity) return;   // (uniform: the forward's outputs are invalid too, the caller knows)
+    if ((p.pair_total && *p.pair_total > p.pair_capacity) || (p.pair_total_super && *p.pair_total_super > p.pair_capacity))
+        return;   // (uniform: the forward's outputs are invalid too, the caller knows)
     __threadfence_block();
     __syncthreads();   // (every wave is through with the forward pass's LDS)
     blend_bwd3_body<LOSS_FUSED, DEPTH_GRAD, POSE_ONLY>(p, u.b);
@@ -912,10 +914,10 @@ int launch_blend_bwd_masked_loss(const lvdgs_args &a, const GeomView &g, const B
 // One launch for both blend passes of a view (api.hip: lvdgs_forward_backward_fused_loss decides when).
 int launch_blend_fwd_bwd_fused_loss(const lvdgs_args &a, const GeomView &g, const BinView &b, const ImageView &im, const BwdScratch &w,
                                     const LossParams &loss, int propagate_opacity, bool deep_lists, const uint32_t *pair_total, uint32_t pair_capacity,
-                                    hipStream_t s) {
+                                    const uint32_t *pair_total_super, hipStream_t s) {
     BlendParams p = make_params(a, g, b, im);
     p.pair_grads = w.pair_grads; p.pair_valid = b.pair_valid;
-    p.pair_total = pair_total; p.pair_capacity = pair_capacity;
+    p.pair_total = pair_total; p.pair_total_super = pair_total_super; p.pair_capacity = pair_capacity;
     p.loss = loss; p.loss_mode = LOSS_FUSED;
     p.loss_propagate_opacity = propagate_opacity;
     if (p.num_tiles == 0) return LVDGS_OK;

@@ -192,21 +192,24 @@ struct GeomView {
     uint32_t *depth_bits;    // N: view depth as ordered bits (positive floats compare like unsigned integers)
     uint4 *rect;             // N: tile rectangle x0 | x1 << 16, y0 | y1 << 16 (empty for culled Gaussians) and the kept-tile mask
     uint32_t *slot_base;     // N: exclusive scan of tiles_touched in id order: first pair / gradient slot of a Gaussian
-    uint32_t *total;         // 1: pair count D of this frame (device copy)
+    uint32_t *total;         // 64: [0] pair count D of this frame (device copy), [1] [2] its hints; [SUPER_TOTAL_WORD ..]: the same for the super lists
 };
 struct PrepScratch {
     uint32_t *blocksums; // scan block sums
 };
 // Two-level grouping (LVDGS_FLAG_SUPER_TILES, binning.hip): the grid of SUPER x SUPER-tile super-tiles and its own counting state
 constexpr int SUPER = 4;
+constexpr int SUPER_ARRIVE_WORD = 8;   // of SuperView::long_count (cleared with the queue by the super count's first workgroup)
+constexpr int SUPER_TOTAL_WORD = 4;    // of GeomView::total: where a call that counts on the device has the super lists' pair count (and hints) left,
+                                       // behind the tile lists' -- outside the scratch, which the backward's pair records share
 struct SuperView {
     uint4 *rect;           // N: a Gaussian's rectangle in super-tile units + which of them hold a listed tile
     uint32_t *hist;        // [Gaussian chunk][super-tile]
     uint32_t *totals;      // Ts (+4)
     uint2 *ranges;         // Ts
-    uint32_t *long_count;  // 64: queue length, order-valid flag (as ImageView::long_count)
+    uint32_t *long_count;  // 64: queue length, order-valid flag (as ImageView::long_count); [SUPER_ARRIVE_WORD]: the range scans' arrival count
     uint32_t *long_tiles;  // 2 Ts: queue of super-tiles with lists beyond one wave's sort, the super-tiles by list length
-    uint32_t *total;       // 4: super pair count, longest queued list, queue length
+    uint32_t *total;       // 4: super pair count, longest queued list, queue length (a call that counts on the device: GeomView::total + SUPER_TOTAL_WORD)
 };
 struct RenderScratch {
     uint32_t *blocksums; // same place as PrepScratch::blocksums: the counting path's first kernel still reads them
@@ -252,7 +255,7 @@ int launch_preprocess_fwd(const lvdgs_args &a, const GeomView &g, uint32_t *bloc
 // pair_total / pair_capacity (lvdgs_forward_backward_fused_loss): the pass does nothing when *pair_total exceeds the capacity
 int launch_preprocess_bwd_views(const lvdgs_args *const *a, const GeomView *g, const BwdScratch *w, const BinView *b, int n, hipStream_t s);
 int launch_preprocess_bwd(const lvdgs_args &a, const GeomView &g, const BwdScratch &b, const uint8_t *pair_valid, hipStream_t s,
-                          const uint32_t *pair_total = nullptr, uint32_t pair_capacity = 0);
+                          const uint32_t *pair_total = nullptr, uint32_t pair_capacity = 0, const uint32_t *pair_total_super = nullptr);
 int launch_mark_visible(int N, const float *means3D, const float *view, uint8_t *present, hipStream_t s);
 
 // stable LSD radix sort of (key, val) pairs on key bits [0, total_bits); result lands in
@@ -294,7 +297,7 @@ int launch_preprocess_count(const lvdgs_args &a, const GeomView &g, const ImageV
 constexpr int FWD_BATCH_VIEWS = 10;
 int launch_preprocess_count_batch(const lvdgs_args *const *a, const GeomView *g, const ImageView *im, const RenderScratch *w, int n, hipStream_t s);
 int launch_group_scan_batch(const lvdgs_args *const *a, const GeomView *g, const ImageView *im, const RenderScratch *w, const int64_t *caps, int n,
-                            uint32_t *host_words, uint32_t host_seq, hipStream_t s);
+                            uint32_t *host_words, uint32_t host_seq, uint32_t *host_super, hipStream_t s);
 int launch_group_scatter_batch(const lvdgs_args *const *a, const GeomView *g, const ImageView *im, const RenderScratch *w, const BinView *b,
                                const int64_t *caps, int n, hipStream_t s);
 int launch_tile_depth_sort_batch(const lvdgs_args *const *a, const GeomView *g, const ImageView *im, const RenderScratch *w, const BinView *b, int n,
@@ -336,7 +339,7 @@ struct LossParams;
 int launch_blend_fwd_batch(const lvdgs_args *const *a, const GeomView *g, const BinView *b, const ImageView *im, int n, bool deep_lists, hipStream_t s);
 int launch_blend_fwd_bwd_fused_loss(const lvdgs_args &a, const GeomView &g, const BinView &b, const ImageView &im, const BwdScratch &w,
                                     const LossParams &loss, int propagate_opacity, bool deep_lists, const uint32_t *pair_total, uint32_t pair_capacity,
-                                    hipStream_t s);
+                                    const uint32_t *pair_total_super, hipStream_t s);
 // The static-mask mapping loss of one view as the backward blend pass reads it (lvdgs_masked_loss_args, checked by api.hip).
 struct MaskedLossView {
     const float *d_image;        // 3*P: d loss / d colour, written by lvdgs_masked_loss_batch

@@ -455,8 +455,9 @@ struct BwdParams {
     int accumulate;   // LVDGS_FLAG_ACCUMULATE_PARAM_GRADS: the parameter gradients are added to what their buffers hold
     // lvdgs_forward_backward_fused_loss enqueues this pass before the host knows the frame's pair count: when the count (left on the
     // device by the tile scan) exceeds the capacity the buffers were sized for, the pass does NOTHING -- its slots would lie beyond
-    // the record buffer -- and the caller runs the backward again behind a forward with room.  Null: no such check.
-    const uint32_t *pair_total;
+    // the record buffer -- and the caller runs the backward again behind a forward with room.  Null: no such check.  pair_total_super
+    // (two-level grouping): the super lists' count, the same verdict (the tile lists read off them were cut short beyond the capacity).
+    const uint32_t *pair_total, *pair_total_super;
     uint32_t pair_capacity;
 };
 
@@ -760,7 +761,7 @@ __device__ __forceinline__ void preprocess_bwd_body(const BwdParams &p, GradAcc 
     const bool helper = HELPERS && threadIdx.x >= 256;
     constexpr int PF = POSE_ONLY ? PAIR_FLOATS_POSE : PAIR_FLOATS;   // floats per pair record
     __shared__ float s_tau[4][6];
-    if (p.pair_total && *p.pair_total > p.pair_capacity) return;   // (uniform over the launch)
+    if ((p.pair_total && *p.pair_total > p.pair_capacity) || (p.pair_total_super && *p.pair_total_super > p.pair_capacity)) return;   // (uniform over the launch)
     const int i = blockIdx.x * 256 + (threadIdx.x & 255);   // (a helper thread: its owner's Gaussian)
     const Cam &c = p.cam;
     // The camera's matrices, read once into scalar registers (the compiler reads them with vector loads where they are
@@ -1380,7 +1381,7 @@ int launch_preprocess_count_batch(const lvdgs_args *const *a, const GeomView *g,
 }
 
 int launch_preprocess_bwd(const lvdgs_args &a, const GeomView &g, const BwdScratch &b, const uint8_t *pair_valid, hipStream_t s,
-                          const uint32_t *pair_total, uint32_t pair_capacity) {
+                          const uint32_t *pair_total, uint32_t pair_capacity, const uint32_t *pair_total_super) {
     const int N = a.num_gaussians;
     const int nblk = cdiv(N, 256);
     if (N > 0) {
@@ -1392,7 +1393,7 @@ int launch_preprocess_bwd(const lvdgs_args &a, const GeomView &g, const BwdScrat
         p.dmeans3D = a.dL_dmeans3D; p.dmeans2D = a.dL_dmeans2D; p.dopac = a.dL_dopacities; p.dscales = a.dL_dscales;
         p.drot = a.dL_drotations; p.dcov3D = a.cov3D_precomp ? a.dL_dcov3D : nullptr; p.dshs = a.dL_dshs;
         p.dcolors = a.dL_dcolors; p.tau_part = b.tau_part; p.accumulate = (a.flags & LVDGS_FLAG_ACCUMULATE_PARAM_GRADS) ? 1 : 0;
-        p.pair_total = pair_total; p.pair_capacity = pair_capacity;
+        p.pair_total = pair_total; p.pair_total_super = pair_total_super; p.pair_capacity = pair_capacity;
         ProfScope ps("preprocess_bwd", s);
         // helper waves where the caller expects large footprints (the two-level grouping's hint): the same sums, bit for bit, sooner
         const bool helpers = (a.flags & LVDGS_FLAG_SUPER_TILES) != 0;
@@ -1430,7 +1431,7 @@ int launch_preprocess_bwd_views(const lvdgs_args *const *a, const GeomView *g, c
         p.dcolors = nullptr;
         // (a later group of the same call adds to what the first group wrote)
         p.accumulate = (first > 0 || (a0.flags & LVDGS_FLAG_ACCUMULATE_PARAM_GRADS)) ? 1 : 0;
-        p.pair_total = nullptr; p.pair_capacity = 0;
+        p.pair_total = p.pair_total_super = nullptr; p.pair_capacity = 0;
         bv.n = m;
         for (int k = 0; k < m; k++) {
             const int v = first + k;

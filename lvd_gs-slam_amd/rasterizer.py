@@ -241,7 +241,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         if KEEP_DEBUG_STATE:
             _DEBUG_LAST.clear()
             _DEBUG_LAST.update(geom=geom, binning=binning, image=image, num_rendered=D, N=N, W=W, H=H,
-                               binning_pairs=binning_pairs, overflowed=binning_pairs != cap)
+                               binning_pairs=binning_pairs, overflowed=binning_pairs != cap, capacity=cap, flags=int(a.flags))
         ctx.raster_settings = rs
         ctx.num_rendered = D
         ctx.activations = int(activations)

@@ -24,19 +24,32 @@ def _view(buf, off, count, dtype):
 
 
 def run_hip(g, cam, W, H, bg, use_sh=False, sh_degree=0, cov_precomp=None, grads=None, pose=True, dev="cuda",
-            propagate_opacity=True, tile_cull=True):
+            propagate_opacity=True, tile_cull=True, super_tiles=None):
     """g: dict of float32 CPU tensors (synthetic.make_gaussians).  grads: optional (dL_dcolor, dL_ddepth,
     dL_dopacity) CPU tensors.  Returns (forward dict, backward dict or None).
 
     tile_cull=False (rasterizer.LIST_ALL_TILES for the call: LVDGS_FLAG_LIST_ALL_TILES in lvdgs_args.flags) lists every tile of
     a Gaussian's rectangle, which makes the pair list, the ranges and n_contrib the reference's bit for bit; the default
-    drops the tiles the Gaussian cannot reach."""
-    before = rasterizer.LIST_ALL_TILES
+    drops the tiles the Gaussian cannot reach.
+
+    super_tiles=True / False forces the two-level grouping hint (LVDGS_FLAG_SUPER_TILES) on / off for the call, as
+    LVDGS_SUPER_TILES=1 / 0 would; None leaves the automatic choice.  The forward dict's "flags" are those the frame was rendered with."""
+    before = rasterizer.LIST_ALL_TILES, rasterizer._SUPER_TILES_ENV
     rasterizer.LIST_ALL_TILES = not tile_cull
+    if super_tiles is not None:
+        rasterizer._SUPER_TILES_ENV = "1" if super_tiles else "0"
     try:
         return _run_hip(g, cam, W, H, bg, use_sh, sh_degree, cov_precomp, grads, pose, dev, propagate_opacity, tile_cull)
     finally:
-        rasterizer.LIST_ALL_TILES = before
+        rasterizer.LIST_ALL_TILES, rasterizer._SUPER_TILES_ENV = before
+
+
+def geom_super_count(geom, lay, N):
+    """The super-tile pair count Ds that a single-call forward with LVDGS_FLAG_SUPER_TILES left in geom_state (uint8 tensor): word
+    SUPER_TOTAL_WORD = 4 of the 64 pair-count words behind slot_base (csrc/api.hip geom_layout: every array 256-byte aligned; csrc/common.hpp).
+    Written before clamping to the capacity, by the scan whose sequence number the host waited for."""
+    off = int(lay.geom_slot_base) + ((4 * N + 255) // 256) * 256 + 4 * 4
+    return int(_view(geom, off, 1, np.uint32)[0])
 
 
 def _run_hip(g, cam, W, H, bg, use_sh, sh_degree, cov_precomp, grads, pose, dev, propagate_opacity, tile_cull):
@@ -73,6 +86,7 @@ def _run_hip(g, cam, W, H, bg, use_sh, sh_degree, cov_precomp, grads, pose, dev,
     fwd = dict(
         color=color.detach().cpu().numpy(), depth=depth.detach().cpu().numpy(), opacity=opacity.detach().cpu().numpy(),
         radii=radii.cpu().numpy(), n_touched=n_touched.cpu().numpy(), num_rendered=D, rec=rec, overflowed=st["overflowed"],
+        flags=st["flags"], capacity=st["capacity"], binning_pairs=st["binning_pairs"],
         tiles_touched=_view(st["geom"], lay.geom_tiles_touched, N, np.uint32) if N else np.zeros(0, np.uint32),
         slot_base=_view(st["geom"], lay.geom_slot_base, N, np.uint32) if N else np.zeros(0, np.uint32),
         point_list=_view(st["binning"], lay.bin_point_list, D, np.uint32) if D else np.zeros(0, np.uint32),
@@ -80,6 +94,9 @@ def _run_hip(g, cam, W, H, bg, use_sh, sh_degree, cov_precomp, grads, pose, dev,
         final_T=_view(st["image"], lay.img_final_T, W * H, np.float32).reshape(H, W),
         n_contrib=_view(st["image"], lay.img_n_contrib, W * H, np.uint32).reshape(H, W), tile_cull=bool(tile_cull),
     )
+    if N and st["flags"] & _lib.FLAG_SUPER_TILES:
+        # the library's super-tile pair count of the frame's single-call forward (left in geom_state, see geom_super_count)
+        fwd["num_rendered_super"] = geom_super_count(st["geom"], lay, N)
     # tile id of every entry of point_list, from the ranges (the counting path never materialises tile keys)
     r = fwd["ranges"].astype(np.int64)
     fwd["tile_keys"] = np.repeat(np.arange(NT, dtype=np.uint32), np.maximum(r[:, 1] - r[:, 0], 0))

@@ -69,6 +69,22 @@ def test_full_size_forward_and_backward_match_oracle(name, pose_seed):
 
 
 @pytest.mark.parametrize("name", ["surface_12k_640x480", "surface_100k_1920x1080"])
+def test_opaque_surfaces_of_large_gaussians_match_oracle_with_super_tiles(name):
+    """The same scenes with the two-level grouping hint forced on (LVDGS_FLAG_SUPER_TILES: the pair lists read off per-super-tile
+    sorted lists, the per-Gaussian backward with helper waves), forward and backward against the oracle under the same rules."""
+    from lvdgs import _lib
+    orc, hr, syn = tp._mods()
+    g, cam, N, W, H = _workload(name, 2)
+    bg = torch.tensor([0.1, 0.3, 0.2])
+    grads = syn.make_image_grads(W, H, 0)
+    f_hip, b_hip = hr.run_hip(g, cam, W, H, bg, grads=grads, super_tiles=True)
+    assert f_hip["flags"] & _lib.FLAG_SUPER_TILES
+    f_ora, b_ora = hr.run_oracle(orc, g, cam, W, H, bg, grads=grads)
+    tp._check_forward(f_hip, f_ora, W, H)
+    tp._check_backward(b_hip, b_ora, GRADS, f_ora, W, H, rerun=tp.masked_rerun(hr, orc, g, cam, W, H, bg, grads, super_tiles=True))
+
+
+@pytest.mark.parametrize("name", ["surface_12k_640x480", "surface_100k_1920x1080"])
 def test_opaque_surfaces_of_large_gaussians_match_oracle(name):
     """The regime real maps live in (synthetic.make_surface_gaussians): large flat Gaussians on opaque surfaces -- tile
     lists of ~900-1300 entries (beyond one wave's register sort at the long end: the tile sort's queue and its in-launch

@@ -37,6 +37,26 @@ def test_random_scene_matches_oracle(case_seed):
     _check_case(_case(np.random.default_rng(1000 + case_seed)))
 
 
+def _super_tile_seeds(n=24):
+    """The first n case seeds of the sweep whose frame has at least 64 tiles (the two-level grouping hint is ignored below that)."""
+    out, k = [], 0
+    while len(out) < n:
+        c = _case(np.random.default_rng(1000 + k))
+        if -(-c["W"] // 16) * -(-c["H"] // 16) >= 64:
+            out.append(k)
+        k += 1
+    return out
+
+
+@pytest.mark.parametrize("case_seed", _super_tile_seeds())
+def test_random_scene_with_super_tiles_matches_oracle(case_seed):
+    """The same cases with the two-level grouping hint forced on (LVDGS_FLAG_SUPER_TILES: per-super-tile scatter and sort, tile lists
+    expanded from the super lists; the per-Gaussian backward with helper waves), under the same rules."""
+    c = _case(np.random.default_rng(1000 + case_seed))
+    c["super_tiles"] = True
+    _check_case(c)
+
+
 @pytest.mark.parametrize("opacity_scale", [0.02, 1.0])
 def test_wide_faint_gaussians_keep_every_quadrant_busy(opacity_scale):
     """Footprints of 25-70 px on a 112 x 90 image: every tile's list is long and nearly every entry reaches every 8 x 8
@@ -56,7 +76,10 @@ def _check_case(c):
     cam = syn.make_camera(c["W"], c["H"], pose_seed=c["pose"])
     bg = torch.tensor([0.3, 0.1, 0.6])
     grads = syn.make_image_grads(c["W"], c["H"], c["seed"])
-    f_hip, b_hip = hr.run_hip(g, cam, c["W"], c["H"], bg, grads=grads)
+    f_hip, b_hip = hr.run_hip(g, cam, c["W"], c["H"], bg, grads=grads, super_tiles=c.get("super_tiles"))
+    if c.get("super_tiles"):
+        from lvdgs import _lib
+        assert f_hip["flags"] & _lib.FLAG_SUPER_TILES, c
     f_ora, b_ora = hr.run_oracle(orc, g, cam, c["W"], c["H"], bg, grads=grads)
     # (same checks as the fixed cases, without the 98 % solid-pixel expectation: tiny images can be mostly fragile)
     np.testing.assert_array_equal(f_hip["radii"], f_ora["radii"], err_msg=str(c))
@@ -95,7 +118,7 @@ def _second_look(c, g, cam, bg, grads, b_hip, b_ora, solid, names, strict):
     orc, hr, syn = tp._mods()
     if not solid.all():
         masked = tuple(torch.where(torch.from_numpy(np.broadcast_to(solid, t.shape[1:]).copy())[None], t, torch.zeros_like(t)) for t in grads)
-        _, bh = hr.run_hip(g, cam, c["W"], c["H"], bg, grads=masked)
+        _, bh = hr.run_hip(g, cam, c["W"], c["H"], bg, grads=masked, super_tiles=c.get("super_tiles"))
         _, bo = hr.run_oracle(orc, g, cam, c["W"], c["H"], bg, grads=masked)
         try:
             tp._check_backward(bh, bo, names + ["tau"])

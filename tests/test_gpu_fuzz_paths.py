@@ -45,6 +45,14 @@ def _register(c):
     return name
 
 
+def _hint(on):
+    """rasterizer.super_tiles_flag forced on (True), off (False) or automatic (None); -> the previous setting."""
+    from lvdgs import rasterizer as _rz
+    before = _rz._SUPER_TILES_ENV
+    _rz._SUPER_TILES_ENV = "auto" if on is None else ("1" if on else "0")
+    return before
+
+
 def _tracking(c, workload):
     import bench
     from lvdgs import _lib, rasterizer as _rz
@@ -62,6 +70,8 @@ def _tracking(c, workload):
                 s.step()
             else:
                 L, a = s.L, s.a
+                if c.get("super_tiles"):   # (as step() sets it)
+                    a.flags = (a.flags & ~_lib.FLAG_SUPER_TILES) | _rz.super_tiles_flag(s.N, s.num_rendered)
                 stream = _lib.raw_stream(dev)
                 num = C.c_int64(0)
                 status = L.lvdgs_forward(C.byref(a), C.byref(num), stream)
@@ -86,6 +96,8 @@ def _tracking(c, workload):
             if full:
                 snap.update(d_m3=s.d_m3.clone(), d_m2=s.d_m2.clone(), d_op=s.d_op.clone(), d_sc=s.d_sc.clone(), d_rot=s.d_rot.clone(), d_sh=s.d_sh.clone())
             snaps.append(snap)
+            if c.get("super_tiles"):
+                assert s.a.flags & _lib.FLAG_SUPER_TILES, (c, "tracking", one_call)
         s.finish()
         out.append(snaps)
     for it, (a, b) in enumerate(zip(*out)):
@@ -114,6 +126,9 @@ def _window(c, workload, batch):
     torch.cuda.synchronize()
     G = backend.gaussians
     used = getattr(backend, "_lvdgs_window_batch", None) is not None
+    if used and c.get("super_tiles"):
+        from lvdgs import _lib
+        assert all(p.a.flags & _lib.FLAG_SUPER_TILES for p in backend._lvdgs_window_batch.passes[:c["n_window"]]), (c, "window")
     params = [p.detach().clone() for p in G.parameters()]
     poses = [torch.cat([vp.cam_rot_delta.detach().flatten(), vp.cam_trans_delta.detach().flatten(), vp.exposure_a.detach().flatten(),
                         vp.exposure_b.detach().flatten(), vp.R.detach().flatten().to(dev), vp.T.detach().flatten().to(dev)]).clone()
@@ -125,7 +140,35 @@ def _window(c, workload, batch):
 
 @pytest.mark.parametrize("seed", list(range(int(os.environ.get("LVDGS_FUZZ_PATH_CASES", "8")))))
 def test_round5_launch_forms_equal_the_forms_they_replace(seed):
+    _launch_forms(_case(seed))
+
+
+def _super_tile_seeds(n=8):
+    """The first n case seeds whose frame has at least 64 tiles (the two-level grouping hint is ignored below that)."""
+    out, k = [], 0
+    while len(out) < n:
+        c = _case(k)
+        if -(-c["W"] // 16) * -(-c["H"] // 16) >= 64:
+            out.append(k)
+        k += 1
+    return out
+
+
+@pytest.mark.parametrize("seed", _super_tile_seeds())
+def test_launch_forms_with_super_tiles_equal_the_forms_they_replace(seed):
+    """The same comparisons with the two-level grouping hint forced on: the batched forward (lvdgs_forward_batch) and the fused tracking
+    call on the super-tile grid against the single-view / two-call forms, which take the same hint."""
     c = _case(seed)
+    c["super_tiles"] = True
+    before = _hint(True)
+    try:
+        _launch_forms(c)
+    finally:
+        from lvdgs import rasterizer as _rz
+        _rz._SUPER_TILES_ENV = before
+
+
+def _launch_forms(c):
     workload = _register(c)
     try:
         _tracking(c, workload)
