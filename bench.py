@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: render + loss + backward iterations per second.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 N = 1 (default): BASELINE.json configs[2] -- 500k Gaussians, 1920x1080, one tracking iteration per
 step: render(viewpoint, gaussians, pipe, bg) -> get_loss_tracking -> backward, with gradients to
@@ -19,9 +19,12 @@ the SAME window on one GPU measured inside the job, config.phases_us_per_step th
 `--window weak` is the round-2 line instead: a window of N keyframes, one whole keyframe per GPU, no random views.
 
 Rank 0 prints ONE JSON line.  `value` is whole-job iterations/s with all inputs resident in HBM.
-`roofline` prices the dominant kernel (by HIP-event time measured here) against the 8 TB/s HBM
-peak with the algorithmic byte count of SURVEY.md section 8(d); `cpu_baseline` times the CPU oracle
-(a scalar C port, 1 core) on one iteration of the same scene.
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line; everything
+else it measures runs only with `--full` (and is null in the line without it): `steady_state` and the
+per-kernel times, `roofline`, which prices the dominant kernel (by HIP-event time measured there) against
+the 8 TB/s HBM peak with the algorithmic byte count of SURVEY.md section 8(d), `cpu_baseline`, which times
+the CPU oracle on one iteration of the same scene, the autograd-API and pose-only rates, `config.side`,
+and on N > 1 the same step on one GPU, the window with the masks the other way round and the phases.
 
 `--dump-outputs DIR`: rank 0 writes what the LAST timed step computed -- the arrays a caller of the timed path receives --
 as DIR/<name>.npy (float32; integers and float64 tensors as float64), at most 64 MB in all: where the whole arrays do not fit,
@@ -266,8 +269,11 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default=os.environ.get("LVDGS_BENCH_WORKLOAD", "cfg3_500k_1920x1080"))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-side", action="store_true", help="skip config.side (the other workloads, bounded to ~10 s) and the steady-state block")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: steady state, per-kernel times and roofline, CPU baseline, "
+                         "config.side, the autograd-API and pose-only rates; N > 1: the same step on one GPU, the other masks, the phases")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-side", action="store_true", help="with --full: skip config.side (the other workloads, bounded to ~10 s) and the steady-state block")
     ap.add_argument("--pose-only", action="store_true", help="tracking step: the backward the product's tracking loop runs (pose + exposure gradients only)")
     ap.add_argument("--window", choices=["real", "weak"], default="real",
                     help="mapping step: 'real' = the reference's window, 8 keyframes + 2 random older ones per iteration, its ten "
@@ -450,87 +456,88 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # ---- steady state, same process: >= 50 ms of load (the clocks are up, tools/short_region.py), then 200 steps untimed by
+    # ---- --full: steady state, same process: >= 50 ms of load (the clocks are up, tools/short_region.py), then 200 steps untimed by
     # events, then -- without a pause -- the same steps with HIP events around every launch (per-kernel durations).  The
     # roofline below is priced from THIS block's kernel time; the headline `value` stays the short region above.
     roofline = None
     kernels = {}
     steady = None
-    ss_steps = max(args.steps, 200) if not args.no_side else args.steps
-    n_warm = max(args.warmup, 1)
-    if not args.no_side:
-        n_warm = max(n_warm, int(0.050 / max(elapsed / args.steps, 1e-6)) + 1)
-    for _ in range(n_warm):   # (the read-backs above let the GPU idle: back to the clocks first)
-        step()
-    sync()
-    t1 = time.perf_counter()
-    for _ in range(ss_steps):
-        step()
-    sync()
-    ss_elapsed = time.perf_counter() - t1
-    if rank == 0:
-        _lib.profile_reset()
-        _lib.profile_enable(True)
-    t1 = time.perf_counter()
-    for _ in range(ss_steps):
-        step()
-    sync()
-    prof_elapsed = time.perf_counter() - t1
-    if world > 1:
-        t = torch.tensor([ss_elapsed, prof_elapsed], device=dev, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        ss_elapsed, prof_elapsed = (float(x) for x in t.tolist())
-    if rank == 0:
-        _lib.profile_enable(False)
-        times = _lib.profile_read()
-        P, T = W * H, ((W + 15) // 16) * ((H + 15) // 16)
-        for name, (n, ms) in sorted(times.items(), key=lambda kv: -kv[1][1]):
-            kernels[name] = {"launches_per_step": n / ss_steps, "avg_us": 1e3 * ms / max(n, 1),
-                             "us_per_step": 1e3 * ms / ss_steps}
-        steady = {"warmup_steps": n_warm, "steps": ss_steps, "ms_per_step": round(1e3 * ss_elapsed / ss_steps, 4),
-                  "value": round((1 if tracking else (10 if real_window else world)) * ss_steps / ss_elapsed, 3),
-                  "ms_per_step_with_events": round(1e3 * prof_elapsed / ss_steps, 4),
-                  "kernels_us_per_step": {k: round(v["us_per_step"], 2) for k, v in kernels.items()},
-                  "kernels_sum_us": round(sum(v["us_per_step"] for v in kernels.values()), 2),
-                  "note": "kernels_us_per_step: HIP events recorded around every launch on its stream, in the loop whose wall time is "
-                          "ms_per_step_with_events (an event pair costs ~2 us of stream time per launch: the sum is below that figure and "
-                          "may exceed the event-free ms_per_step)"}
-        dom = max(times, key=lambda k: times[k][1])
-        n, ms = times[dom]
-        avg_s = ms / 1e3 / max(n, 1)
-        nbytes = algorithmic_bytes(dom, N, stats["V"], stats["D"], P, T)
-        traffic = valu_insts = source = None
-        tpath = os.path.join(ROOT, "profiles", "traffic.json")
-        # (the PMC passes were taken on the tracking iteration with the full backward; the mapping iteration's scene moves under
-        # Adam, its pair count differs: no traffic / instruction figures are attached to it)
-        if os.path.exists(tpath) and session is not None and not args.pose_only:
-            tj = json.load(open(tpath))
-            ent = tj.get(args.workload, {}).get(dom)
-            if ent:
-                traffic = ent.get("hbm_bytes_per_launch")
-                valu_insts = ent.get("valu_wave_instructions_per_launch")
-                source = tj.get(args.workload, {}).get("_source")
-        if nbytes:
-            achieved = nbytes / avg_s / 1e9
-            roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
-                        "traffic_source": ("separate rocprofv3 --pmc passes of this workload, NOT measured in this run: profiles/traffic.json"
-                                           + (f" <- {source}" if source else "")) if traffic else None,
-                        "algorithmic_bytes_per_launch": int(nbytes), "avg_launch_us": round(avg_s * 1e6, 2),
-                        "measured_in": "steady_state block of this run (HIP events around the launch on its stream)"}
-            if valu_insts:
-                # The resource that actually binds the blend kernels: vector-instruction issue.
-                # peak: one wave64 instruction per 2 cycles per SIMD, 1024 SIMDs, 2.4 GHz (MI355X_MICROARCH.md);
-                # ceiling: what a stream of independent v_fma_f32 reaches on this chip at the clock it then runs at
-                # (tools/valu_clock.hip: 2.88 cycles at the nominal clock, 8 waves/SIMD).
-                g_per_s = valu_insts / avg_s / 1e9
-                roofline["valu"] = {"wave_instructions_per_launch": int(valu_insts), "achieved": round(g_per_s, 1), "unit": "G wave-instructions/s",
-                                    "peak": VALU_PEAK_G, "frac": round(g_per_s / VALU_PEAK_G, 4), "measured_issue_ceiling": VALU_MEASURED_G,
-                                    "frac_of_measured_ceiling": round(g_per_s / VALU_MEASURED_G, 4),
-                                    "source": "SQ_INSTS_VALU of a separate rocprofv3 --pmc pass (profiles/traffic.json), not measured in this run"}
+    if args.full:
+        ss_steps = max(args.steps, 200) if not args.no_side else args.steps
+        n_warm = max(args.warmup, 1)
+        if not args.no_side:
+            n_warm = max(n_warm, int(0.050 / max(elapsed / args.steps, 1e-6)) + 1)
+        for _ in range(n_warm):   # (the read-backs above let the GPU idle: back to the clocks first)
+            step()
+        sync()
+        t1 = time.perf_counter()
+        for _ in range(ss_steps):
+            step()
+        sync()
+        ss_elapsed = time.perf_counter() - t1
+        if rank == 0:
+            _lib.profile_reset()
+            _lib.profile_enable(True)
+        t1 = time.perf_counter()
+        for _ in range(ss_steps):
+            step()
+        sync()
+        prof_elapsed = time.perf_counter() - t1
+        if world > 1:
+            t = torch.tensor([ss_elapsed, prof_elapsed], device=dev, dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            ss_elapsed, prof_elapsed = (float(x) for x in t.tolist())
+        if rank == 0:
+            _lib.profile_enable(False)
+            times = _lib.profile_read()
+            P, T = W * H, ((W + 15) // 16) * ((H + 15) // 16)
+            for name, (n, ms) in sorted(times.items(), key=lambda kv: -kv[1][1]):
+                kernels[name] = {"launches_per_step": n / ss_steps, "avg_us": 1e3 * ms / max(n, 1),
+                                 "us_per_step": 1e3 * ms / ss_steps}
+            steady = {"warmup_steps": n_warm, "steps": ss_steps, "ms_per_step": round(1e3 * ss_elapsed / ss_steps, 4),
+                      "value": round((1 if tracking else (10 if real_window else world)) * ss_steps / ss_elapsed, 3),
+                      "ms_per_step_with_events": round(1e3 * prof_elapsed / ss_steps, 4),
+                      "kernels_us_per_step": {k: round(v["us_per_step"], 2) for k, v in kernels.items()},
+                      "kernels_sum_us": round(sum(v["us_per_step"] for v in kernels.values()), 2),
+                      "note": "kernels_us_per_step: HIP events recorded around every launch on its stream, in the loop whose wall time is "
+                              "ms_per_step_with_events (an event pair costs ~2 us of stream time per launch: the sum is below that figure and "
+                              "may exceed the event-free ms_per_step)"}
+            dom = max(times, key=lambda k: times[k][1])
+            n, ms = times[dom]
+            avg_s = ms / 1e3 / max(n, 1)
+            nbytes = algorithmic_bytes(dom, N, stats["V"], stats["D"], P, T)
+            traffic = valu_insts = source = None
+            tpath = os.path.join(ROOT, "profiles", "traffic.json")
+            # (the PMC passes were taken on the tracking iteration with the full backward; the mapping iteration's scene moves under
+            # Adam, its pair count differs: no traffic / instruction figures are attached to it)
+            if os.path.exists(tpath) and session is not None and not args.pose_only:
+                tj = json.load(open(tpath))
+                ent = tj.get(args.workload, {}).get(dom)
+                if ent:
+                    traffic = ent.get("hbm_bytes_per_launch")
+                    valu_insts = ent.get("valu_wave_instructions_per_launch")
+                    source = tj.get(args.workload, {}).get("_source")
+            if nbytes:
+                achieved = nbytes / avg_s / 1e9
+                roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                            "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
+                            "traffic_source": ("separate rocprofv3 --pmc passes of this workload, NOT measured in this run: profiles/traffic.json"
+                                               + (f" <- {source}" if source else "")) if traffic else None,
+                            "algorithmic_bytes_per_launch": int(nbytes), "avg_launch_us": round(avg_s * 1e6, 2),
+                            "measured_in": "steady_state block of this run (HIP events around the launch on its stream)"}
+                if valu_insts:
+                    # The resource that actually binds the blend kernels: vector-instruction issue.
+                    # peak: one wave64 instruction per 2 cycles per SIMD, 1024 SIMDs, 2.4 GHz (the MI355X's published figures);
+                    # ceiling: what a stream of independent v_fma_f32 reaches on this chip at the clock it then runs at
+                    # (tools/valu_clock.hip: 2.88 cycles at the nominal clock, 8 waves/SIMD).
+                    g_per_s = valu_insts / avg_s / 1e9
+                    roofline["valu"] = {"wave_instructions_per_launch": int(valu_insts), "achieved": round(g_per_s, 1), "unit": "G wave-instructions/s",
+                                        "peak": VALU_PEAK_G, "frac": round(g_per_s / VALU_PEAK_G, 4), "measured_issue_ceiling": VALU_MEASURED_G,
+                                        "frac_of_measured_ceiling": round(g_per_s / VALU_MEASURED_G, 4),
+                                        "source": "SQ_INSTS_VALU of a separate rocprofv3 --pmc pass (profiles/traffic.json), not measured in this run"}
 
     autograd_rate = None
-    if rank == 0 and session is not None:
+    if args.full and rank == 0 and session is not None:
         # the same iteration through the public autograd API (render() / get_loss_tracking / backward), for comparison
         for _ in range(10):
             autograd_step()
@@ -545,7 +552,7 @@ def main():
 
     pose_only_rate = None
     side = None
-    if rank == 0 and session is not None and world == 1 and not args.pose_only and not args.no_side:
+    if args.full and rank == 0 and session is not None and world == 1 and not args.pose_only and not args.no_side:
         from lvdgs.fast_tracking import TrackingSession
         po = TrackingSession(cam, model, CONFIG, pipe, bg)   # the product's default: pose + exposure gradients only
         pose_only_rate = time_session(po, 60, 200)
@@ -567,7 +574,7 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MIN)
         return bool(t.item() > 0.5)
 
-    if world > 1 and not tracking:
+    if args.full and world > 1 and not tracking:
         # The same step on ONE GPU, measured inside this job (every rank alone in a group of its own: no collective),
         # so that the N-GPU number can be read against the right single-GPU number: bench.py's N = 1 default is the
         # tracking iteration of BASELINE configs[2], a different (lighter) step than the mapping iteration timed here.
@@ -605,7 +612,7 @@ def main():
                 notes.append("the one-GPU run of the same step failed on another rank: not reported")
 
     other_masks_value = None
-    if world > 1 and not tracking and real_window:
+    if args.full and world > 1 and not tracking and real_window:
         # The same window with the keyframes' masks the OTHER way round (default run: without masks -- every view scored by
         # get_loss_mapping, the step of rounds 2-4 under this metric name; --no-masks run: with them), so that lines of different
         # rounds can be compared like for like.  Built on every rank alike; its collectives are map_window's own.
@@ -633,7 +640,7 @@ def main():
             other_masks_value = round(10 * args.steps / float(t.item()), 3)
             del other_backend, other_model
 
-    if not tracking:
+    if args.full and not tracking:
         # the iteration by phase (events on the stream at the phase boundaries, one wait at the end of each iteration).  map_window's
         # own collectives are the benchmark's: a rank-local failure inside them is fatal for the job as it was in the timed region.
         st = {}
@@ -648,7 +655,7 @@ def main():
         comm_us = phases.get("collectives")
 
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_baseline = run_cpu_baseline(g_cpu, args.workload, N, W, H)
 
     if rank == 0:
@@ -656,7 +663,7 @@ def main():
         value = views_per_step * args.steps / elapsed
         out = {
             "metric": "render+backward iters/sec @500k Gaussians 1080p; 1/2/4/8-GPU scaling",
-            "value": round(value, 3), "unit": "iters/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "value": round(value, 3), "unit": "iters/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True,
             # N > 1 shards the reference's ten-view mapping window over the GPUs (total work fixed: strong), `--window weak` one
             # keyframe per GPU; the N = 1 line is the single-GPU tracking iteration BASELINE configs[2] names, and carries the one-GPU
@@ -701,7 +708,7 @@ def main():
                                "same per-step time as 200 after 20)"}
                if (max(args.warmup, 1) + args.steps) * elapsed / args.steps < 0.040 else {}),
             "roofline": roofline, "cpu_baseline": cpu_baseline, "steady_state": steady,
-            "kernels_us_per_step": {k: round(v["us_per_step"], 2) for k, v in kernels.items()},
+            "kernels_us_per_step": {k: round(v["us_per_step"], 2) for k, v in kernels.items()} if args.full else None,
         }
         if dump_snap is not None:
             out["dump_outputs"] = write_outputs(args.dump_outputs, dump_snap)

@@ -8,7 +8,7 @@ while [ $# -gt 0 ] && [ "$1" != "--" ]; do vals+=("$1"); shift; done
 [ "$1" = "--" ] && shift
 for round in 1 2; do
   for v in "${vals[@]}"; do
-    env "$var=$v" python bench.py --steps 200 --warmup 20 --no-cpu-baseline "$@" 2>/dev/null | python -c "
+    env "$var=$v" python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline())
 print('$var=$v', d['value'], 'it/s', d['ms_per_step'], 'ms', 'pairs', d['config'].get('pairs'), json.dumps(d.get('kernels_us_per_step')))"

@@ -6,7 +6,7 @@ TAG=${1:-r0x_final}
 ROOT=$(cd "$(dirname "$0")/.." && pwd); OUT=$ROOT/gpurun_out/$TAG; mkdir -p "$OUT"
 bash "$ROOT/tools/profile_round.sh" "$TAG" > "$OUT/profile_round.log" 2>&1
 ( cd "$ROOT" && python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_driver_flags.json" 2> "$OUT/bench_driver_flags.err" )
-( cd /tmp && export TMPDIR=/tmp && LVDGS_BENCH_WORKLOAD=kitti07_geom rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kitti_stats" -o run -- python3 "$ROOT/bench.py" --pose-only --steps 100 --warmup 60 --no-cpu-baseline --no-side > "$OUT/kitti_stats.log" 2>&1 )
+( cd /tmp && export TMPDIR=/tmp && LVDGS_BENCH_WORKLOAD=kitti07_geom rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kitti_stats" -o run -- python3 "$ROOT/bench.py" --full --pose-only --steps 100 --warmup 60 --no-cpu-baseline --no-side > "$OUT/kitti_stats.log" 2>&1 )
 bash "$ROOT/tools/map_trace.sh" "${TAG}_unmasked" > "$OUT/map_trace_unmasked.log" 2>&1
 MAP_BENCH_MASKED=1 bash "$ROOT/tools/map_trace.sh" "${TAG}_masked" > "$OUT/map_trace_masked.log" 2>&1
 ( cd "$ROOT" && python3 tools/soak.py > "$OUT/soak.txt" 2>&1 )

@@ -9,7 +9,7 @@ i=0
 for SET in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_MFMA" "SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS" \
            "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_ANY" "SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_VALU_MFMA_COEXEC_CYCLES SQ_INSTS_VALU_TRANS_F32"; do
   i=$((i+1))
-  rocprofv3 --pmc $SET --output-format csv -d "$OUT/s$i" -o run -- python3 "$ROOT/bench.py" --steps 3 --warmup 2 --no-cpu-baseline > "$OUT/s$i.log" 2>&1
+  rocprofv3 --pmc $SET --output-format csv -d "$OUT/s$i" -o run -- python3 "$ROOT/bench.py" --full --steps 3 --warmup 2 --no-cpu-baseline > "$OUT/s$i.log" 2>&1
 done
 python3 - "$OUT" <<'PY'
 import csv, glob, sys, collections

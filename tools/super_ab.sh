@@ -9,7 +9,7 @@ for W in surface_100k_1920x1080 kitti07_geom cfg3_500k_1920x1080; do
 done > $OUT/track_ab.txt
 cat $OUT/track_ab.txt
 for M in 0 1; do
-  LVDGS_SUPER_TILES=$M LVDGS_BENCH_WORKLOAD=surface_100k_1920x1080 python3 bench.py --steps 100 --warmup 60 --no-cpu-baseline --no-side 2>/dev/null | python3 -c "
+  LVDGS_SUPER_TILES=$M LVDGS_BENCH_WORKLOAD=surface_100k_1920x1080 python3 bench.py --full --steps 100 --warmup 60 --no-cpu-baseline --no-side 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('super=$M', d['value'], 'it/s', d['steady_state']['ms_per_step'], 'ms; kernels us/step:', d['kernels_us_per_step'])" 
