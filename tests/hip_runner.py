@@ -24,9 +24,10 @@ def _view(buf, off, count, dtype):
 
 
 def run_hip(g, cam, W, H, bg, use_sh=False, sh_degree=0, cov_precomp=None, grads=None, pose=True, dev="cuda",
-            propagate_opacity=True, tile_cull=True, super_tiles=None):
+            propagate_opacity=True, tile_cull=True, super_tiles=None, scale_modifier=1.0):
     """g: dict of float32 CPU tensors (synthetic.make_gaussians).  grads: optional (dL_dcolor, dL_ddepth,
-    dL_dopacity) CPU tensors.  Returns (forward dict, backward dict or None).
+    dL_dopacity) CPU tensors.  scale_modifier: the raster settings' (every scale times it).  Returns (forward dict, backward
+    dict or None).
 
     tile_cull=False (rasterizer.LIST_ALL_TILES for the call: LVDGS_FLAG_LIST_ALL_TILES in lvdgs_args.flags) lists every tile of
     a Gaussian's rectangle, which makes the pair list, the ranges and n_contrib the reference's bit for bit; the default
@@ -39,7 +40,8 @@ def run_hip(g, cam, W, H, bg, use_sh=False, sh_degree=0, cov_precomp=None, grads
     if super_tiles is not None:
         rasterizer._SUPER_TILES_ENV = "1" if super_tiles else "0"
     try:
-        return _run_hip(g, cam, W, H, bg, use_sh, sh_degree, cov_precomp, grads, pose, dev, propagate_opacity, tile_cull)
+        return _run_hip(g, cam, W, H, bg, use_sh, sh_degree, cov_precomp, grads, pose, dev, propagate_opacity, tile_cull,
+                        scale_modifier)
     finally:
         rasterizer.LIST_ALL_TILES, rasterizer._SUPER_TILES_ENV = before
 
@@ -52,12 +54,12 @@ def geom_super_count(geom, lay, N):
     return int(_view(geom, off, 1, np.uint32)[0])
 
 
-def _run_hip(g, cam, W, H, bg, use_sh, sh_degree, cov_precomp, grads, pose, dev, propagate_opacity, tile_cull):
+def _run_hip(g, cam, W, H, bg, use_sh, sh_degree, cov_precomp, grads, pose, dev, propagate_opacity, tile_cull, scale_modifier):
     rasterizer.KEEP_DEBUG_STATE = True
     # the parity tests feed a gradient of the opacity image too: switch that (non-default) path on for the run
     propagate_before = rasterizer.PROPAGATE_OPACITY_GRAD
     rasterizer.PROPAGATE_OPACITY_GRAD = bool(propagate_opacity)
-    rs = settings_from_cam(cam, W, H, bg, sh_degree=sh_degree, dev=dev)
+    rs = settings_from_cam(cam, W, H, bg, sh_degree=sh_degree, scale_modifier=scale_modifier, dev=dev)
     leaf = lambda t: t.to(dev).clone().requires_grad_(True)
     means3D, opac = leaf(g["means3D"]), leaf(g["opacities"])
     N = means3D.shape[0]
@@ -128,7 +130,7 @@ def _run_hip(g, cam, W, H, bg, use_sh, sh_degree, cov_precomp, grads, pose, dev,
     return fwd, bwd
 
 
-def run_oracle(orc, g, cam, W, H, bg, use_sh=False, sh_degree=0, cov_precomp=None, grads=None, prec="f32"):
+def run_oracle(orc, g, cam, W, H, bg, use_sh=False, sh_degree=0, cov_precomp=None, grads=None, prec="f32", scale_modifier=1.0):
     o = orc.Oracle(prec)
     kw = dict(scales=g["scales"].numpy(), rotations=g["rotations"].numpy())
     if cov_precomp is not None:
@@ -137,7 +139,7 @@ def run_oracle(orc, g, cam, W, H, bg, use_sh=False, sh_degree=0, cov_precomp=Non
                     tanfovy=cam.tanfovy, viewmatrix=cam.world_view_transform.numpy(),
                     projmatrix=cam.full_proj_transform.numpy(), projmatrix_raw=cam.projection_matrix.numpy(),
                     campos=cam.camera_center.numpy(), bg=bg.numpy(), shs=g["shs"].numpy() if use_sh else None,
-                    colors_precomp=None if use_sh else g["colors"].numpy(), sh_degree=sh_degree, **kw)
+                    colors_precomp=None if use_sh else g["colors"].numpy(), sh_degree=sh_degree, scale_modifier=scale_modifier, **kw)
     bwd = None
     if grads is not None:
         gc, gd, go = grads

@@ -124,8 +124,8 @@ def masked_rerun(hr, orc, g, cam, W, H, bg, grads, **run_kw):
         keep = torch.from_numpy(np.ascontiguousarray(solid.reshape(H, W)))[None]
         masked = tuple(None if t is None else torch.where(keep, t, torch.zeros_like(t)) for t in grads)
         _, bh = hr.run_hip(g, cam, W, H, bg, grads=masked, **run_kw)
-        _, bo = hr.run_oracle(orc, g, cam, W, H, bg, grads=masked, **{k: v for k, v in run_kw.items() if k in ("use_sh", "sh_degree", "cov_precomp")})
-        ora_kw = {k: v for k, v in run_kw.items() if k in ("use_sh", "sh_degree", "cov_precomp")}
+        ora_kw = {k: v for k, v in run_kw.items() if k in ("use_sh", "sh_degree", "cov_precomp", "scale_modifier")}
+        _, bo = hr.run_oracle(orc, g, cam, W, H, bg, grads=masked, **ora_kw)
         return bh, bo, lambda: hr.run_oracle(orc, g, cam, W, H, bg, grads=masked, prec="f64", **ora_kw)[1]
     return rerun
 
