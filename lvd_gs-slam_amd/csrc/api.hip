@@ -1,17 +1,15 @@
 // C ABI entry points (include/lvdgs.h): argument checks, state-buffer layouts, launch sequencing.
 #include <stdarg.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
+#include <chrono>
 #include <mutex>
 #include <string>
-#include <vector>
-
-#include <cstdlib>
-
-#include <chrono>
 #include <thread>
+#include <vector>
 
 #include "common.hpp"
 #include "photometric.hpp"
@@ -132,48 +130,47 @@ bool tile_order_in_use(int num_tiles) {
 }
 
 // ---------------------------------------------------------------- layouts
-template <typename T>
-static void carve(T *&ptr, size_t count, char *base, size_t &off) {
-    ptr = base ? reinterpret_cast<T *>(base + off) : nullptr;
-    off += align256(count * sizeof(T));
-}
+// Carves the arrays of a state view out of a buffer, every one aligned to 256 bytes (no view: into one of its own; no buffer: sizes only).
+template <typename V>
+struct Carver {
+    V own, &v;
+    char *base;
+    size_t off = 0;
+    Carver(V *view, void *buffer) : v(view ? *view : own), base((char *)buffer) {}
+    template <typename T>
+    void operator()(T *&ptr, size_t count) {
+        ptr = base ? reinterpret_cast<T *>(base + off) : nullptr;
+        off += align256(count * sizeof(T));
+    }
+};
 
 size_t geom_layout(int N, GeomView *v, void *base) {
-    GeomView tmp;
-    if (!v) v = &tmp;
-    size_t off = 0;
-    char *b = (char *)base;
+    Carver<GeomView> c(v, base);
     const size_t n = (size_t)(N > 0 ? N : 1);
-    carve(v->rec, n * REC_FLOATS, b, off);
-    carve(v->tiles_touched, n, b, off);
-    carve(v->depth_bits, n, b, off);
-    carve(v->rect, n, b, off);
-    carve(v->slot_base, n, b, off);
-    carve(v->total, 64, b, off);
-    return off;
+    c(c.v.rec, n * REC_FLOATS);
+    c(c.v.tiles_touched, n);
+    c(c.v.depth_bits, n);
+    c(c.v.rect, n);
+    c(c.v.slot_base, n);
+    c(c.v.total, 64);
+    return c.off;
 }
 
 static size_t scan_blocks(int N) { return (size_t)cdiv(N > 0 ? N : 1, 256) + 1; }  // one sum per preprocess_fwd workgroup
 
 size_t prep_scratch_layout(int N, PrepScratch *v, void *base) {
-    PrepScratch tmp;
-    if (!v) v = &tmp;
-    size_t off = 0;
-    char *b = (char *)base;
-    carve(v->blocksums, scan_blocks(N), b, off);
-    return off;
+    Carver<PrepScratch> c(v, base);
+    c(c.v.blocksums, scan_blocks(N));
+    return c.off;
 }
 
 size_t bin_layout(int64_t D, BinView *v, void *base) {
-    BinView tmp;
-    if (!v) v = &tmp;
-    size_t off = 0;
-    char *b = (char *)base;
+    Carver<BinView> c(v, base);
     const size_t d = (size_t)(D > 0 ? D : 1);
-    carve(v->point_list, d, b, off);
-    carve(v->tile_keys, d, b, off);
-    carve(v->pair_valid, d + 16, b, off);
-    return off;
+    c(c.v.point_list, d);
+    c(c.v.tile_keys, d);
+    c(c.v.pair_valid, d + 16);
+    return c.off;
 }
 
 // Where the arrays lie is a function of the BUFFER's size, not of the pair count of the call: the forward pass lays the
@@ -190,65 +187,57 @@ int64_t bin_view(const lvdgs_args *a, BinView *v) {
 }
 
 size_t image_layout(int W, int H, ImageView *v, void *base) {
-    ImageView tmp;
-    if (!v) v = &tmp;
-    size_t off = 0;
-    char *b = (char *)base;
+    Carver<ImageView> c(v, base);
     const size_t P = (size_t)W * H, T = (size_t)cdiv(W, TILE) * cdiv(H, TILE);
-    carve(v->ranges, T ? T : 1, b, off);
-    carve(v->long_count, 64, b, off);  // directly behind ranges: one memset clears both
-    carve(v->long_tiles, 2 * (T ? T : 1), b, off);  // queue of up to T tile ids (the second half is unused)
-    carve(v->final_T, P ? P : 1, b, off);
-    carve(v->n_contrib, P ? P : 1, b, off);
-    return off;
+    c(c.v.ranges, T ? T : 1);
+    c(c.v.long_count, 64);  // directly behind ranges: one memset clears both
+    c(c.v.long_tiles, 2 * (T ? T : 1));  // queue of up to T tile ids (the second half is unused)
+    c(c.v.final_T, P ? P : 1);
+    c(c.v.n_contrib, P ? P : 1);
+    return c.off;
 }
 
 size_t render_scratch_layout(int N, int64_t D, int W, int H, RenderScratch *v, void *base) {
-    RenderScratch tmp;
-    if (!v) v = &tmp;
-    size_t off = 0;
-    char *b = (char *)base;
+    Carver<RenderScratch> c(v, base);
+    RenderScratch &r = c.v;
     const size_t d = (size_t)(D > 0 ? D : 1);
-    const int T = cdiv(W, TILE) * cdiv(H, TILE);
-    carve(v->blocksums, scan_blocks(N), b, off);  // as in prep_scratch_layout: left by preprocess_fwd, read by count_pairs
-    carve(v->keys, d, b, off);
-    carve(v->vals, d, b, off);
-    v->hist = v->totals = v->group_hist = v->group_totals = v->chunk_sums = nullptr;
-    v->super = SuperView{};
-    if (use_counting_path(T)) {
-        carve(v->group_hist, group_hist_entries(N, T), b, off);
-        carve(v->group_totals, (size_t)(T > 0 ? T : 1) + 4, b, off);   // (+4: the tile-range scan reads them 16 bytes at a time)
-        carve(v->chunk_sums, group_chunks(N), b, off);
+    const TileGrid t(W, H);
+    c(r.blocksums, scan_blocks(N));  // as in prep_scratch_layout: left by preprocess_fwd, read by count_pairs
+    c(r.keys, d);
+    c(r.vals, d);
+    r.hist = r.totals = r.group_hist = r.group_totals = r.chunk_sums = nullptr;
+    r.super = SuperView{};
+    if (use_counting_path(t.T)) {
+        c(r.group_hist, group_hist_entries(N, t.T));
+        c(r.group_totals, (size_t)(t.T > 0 ? t.T : 1) + 4);   // (+4: the tile-range scan reads them 16 bytes at a time)
+        c(r.chunk_sums, group_chunks(N));
         // two-level grouping (LVDGS_FLAG_SUPER_TILES): the super-tile grid's own counting state
-        const size_t Ts = (size_t)super_tiles_of(W, H);
-        carve(v->super.rect, (size_t)(N > 0 ? N : 1), b, off);
-        carve(v->super.hist, group_chunks(N) * (Ts ? Ts : 1), b, off);
-        carve(v->super.totals, (Ts ? Ts : 1) + 4, b, off);
-        carve(v->super.ranges, Ts ? Ts : 1, b, off);
-        carve(v->super.long_count, 64, b, off);
-        carve(v->super.long_tiles, 2 * (Ts ? Ts : 1), b, off);
-        carve(v->super.total, 64, b, off);
+        const size_t Ts = (size_t)(t.Ts ? t.Ts : 1);
+        c(r.super.rect, (size_t)(N > 0 ? N : 1));
+        c(r.super.hist, group_chunks(N) * Ts);
+        c(r.super.totals, Ts + 4);
+        c(r.super.ranges, Ts);
+        c(r.super.long_count, 64);
+        c(r.super.long_tiles, 2 * Ts);
+        c(r.super.total, 64);
     } else {
-        carve(v->hist, radix_hist_entries(D), b, off);
-        carve(v->totals, (size_t)1 << SORT_MAX_BITS, b, off);
+        c(r.hist, radix_hist_entries(D));
+        c(r.totals, (size_t)1 << SORT_MAX_BITS);
     }
-    return off;
+    return c.off;
 }
 
 size_t bwd_scratch_layout(int N, int64_t D, BwdScratch *v, void *base) {
-    BwdScratch tmp;
-    if (!v) v = &tmp;
-    size_t off = 0;
-    char *b = (char *)base;
+    Carver<BwdScratch> c(v, base);
     // (the pose-gradient partials first: their place must not depend on the pair count -- lvdgs_forward_backward_fused_loss
     // enqueues the backward before the host knows it, and lvdgs_tracking_tail looks for them with the count the caller then has)
-    carve(v->tau_part, (size_t)(cdiv(N > 0 ? N : 1, 256)) * 6, b, off);
-    carve(v->pair_grads, (size_t)(D > 0 ? D : 1) * PAIR_FLOATS + 8, b, off);   // (+8: the staging loads of preprocess_bwd are 16 bytes wide)
-    return off;
+    c(c.v.tau_part, (size_t)(cdiv(N > 0 ? N : 1, 256)) * 6);
+    c(c.v.pair_grads, (size_t)(D > 0 ? D : 1) * PAIR_FLOATS + 8);   // (+8: the staging loads of preprocess_bwd are 16 bytes wide)
+    return c.off;
 }
 
 int tile_sort_bits(int W, int H) {
-    const int T = cdiv(W, TILE) * cdiv(H, TILE);
+    const int T = TileGrid(W, H).T;
     int bits = 0;
     while ((1 << bits) < T) bits++;
     return bits < 1 ? 1 : bits;
@@ -262,6 +251,7 @@ static int check_common(const lvdgs_args *a) {
     if (!(a->tanfovx > 0.f) || !(a->tanfovy > 0.f)) { set_error("tanfov must be positive"); return LVDGS_E_INVALID; }
     if (a->sh_degree < 0 || a->sh_degree > 3) { set_error("sh_degree %d outside 0..3", a->sh_degree); return LVDGS_E_INVALID; }
     if (!a->bg || !a->viewmatrix || !a->projmatrix) { set_error("bg / viewmatrix / projmatrix is NULL"); return LVDGS_E_INVALID; }
+    // (in 64 bits: this is the check that makes a TileGrid's products fit an int)
     if ((int64_t)cdiv(a->image_width, TILE) * cdiv(a->image_height, TILE) > (1 << 22)) { set_error("image too large"); return LVDGS_E_RANGE; }
     return LVDGS_OK;
 }
@@ -309,23 +299,61 @@ int lvdgs_state_layout_query(int32_t N, int64_t D, int32_t W, int32_t H, lvdgs_s
     return LVDGS_OK;
 }
 
-// Per-thread, per-device host resources of the single-call forward: 4 pinned bytes that receive the
-// pair count and the event that says they have arrived.  Nothing else in the library is stateful.
 namespace {
+static inline void cpu_relax() {
+#if defined(__x86_64__) || defined(__i386__)
+    __builtin_ia32_pause();
+#elif defined(__aarch64__)
+    asm volatile("yield");
+#endif
+}
+
+// Per-thread, per-device host resources of the forward calls that wait for their pair counts: the pinned words the tile scans report in
+// (common.hpp: PROBE_*) with their protocol -- sequence numbers, the wait, what becomes of the hints.  Nothing else in the library is stateful.
 struct PairProbe {
     int device = -1;
-    uint32_t *pinned = nullptr;   // [0] pair count, [1] longest queued tile segment of the frame, [2] length of that queue, [3] sequence number of the call that wrote them;
-                                  // [8 ...]: the first three of them for the super-tile lists of the two-level grouping (LVDGS_FLAG_SUPER_TILES);
-                                  // [16 + 4 k ...]: the same four words of view k of lvdgs_forward_batch, [PROBE_SUPER + 4 k ...] its super-tile lists' three
+    uint32_t *pinned = nullptr;       // PROBE_WORDS words
     uint32_t *pinned_dev = nullptr;   // the same words as the device addresses them
-    uint32_t seq = 0;             // of the last single-call forward on this thread and device
+    uint32_t seq = 0;                 // of the last call on this thread and device whose tile scans reported
     hipEvent_t ready = nullptr;
     int longest_super = -1, queued_super = 0;   // the same hints for the super-tile lists of the two-level grouping (LVDGS_FLAG_SUPER_TILES)
     int longest = 0, queued = 0;  // of the previous frame on this device: which kernels for long segments the next frame
     int keep = 0;                 // launches behind its tile sort (a hint, never a result); kept for a few frames
+    // (a call whose scans report, or the next group of a batch's views: under a number no block holds -- 0 is what the words are allocated with)
+    void next_sequence() { if (++seq == 0u) seq = 1u; }
+    PairReport report() const { return PairReport{pinned_dev, seq}; }
+    uint32_t count(int block) const { return pinned[block + PROBE_COUNT]; }
+    // The tile scan of this call has written a block when its sequence word holds the call's number.  (Two-level grouping: the later of
+    // the view's two scans writes it, so the wait for the tile lists' block covers the super lists'.)
+    int wait(int block) const {
+        const uint32_t *flag = pinned + block + PROBE_SEQ;
+        const auto t0 = std::chrono::steady_clock::now();
+        // The count arrives some tens of microseconds after the call got here (the projection and the two scans); the wait is a
+        // spin on a pinned word, polite to the core's sibling thread (pause) and, past ~20 us, to the scheduler (yield) -- the
+        // reference's front end and back end are two processes that each sit in this wait once per render.
+        for (uint64_t spins = 0;; spins++) {
+            if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return LVDGS_OK;
+            if (spins < 2000) cpu_relax();
+            else std::this_thread::yield();
+            if ((spins & 0xffffu) == 0xffffu) {
+                if (int e = check_hip(hipGetLastError(), "while waiting for the pair count")) return e;
+                if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(60)) {
+                    set_error("timed out waiting for the pair count (the kernels before it never finished)");
+                    return LVDGS_E_HIP;
+                }
+            }
+        }
+    }
+    // What the next frames expect: this call's long segments -- the longest over its `views` tile-list blocks from `block` on -- or a recent call's
+    // for a while (views alternate).  super_block (< 0: none): the super lists' block of its first view, whose hints are taken as they are.
+    void fold_hints(int block, int views, int super_block) {
+        int l = 0, q = 0;
+        for (const uint32_t *w = pinned + block; views-- > 0; w += PROBE_BLOCK) { l = std::max(l, (int)w[PROBE_LONGEST]); q = std::max(q, (int)w[PROBE_QUEUED]); }
+        if (l >= longest || keep == 0) { longest = l; queued = q; keep = l ? 32 : 0; }
+        else keep--;
+        if (super_block >= 0) { longest_super = (int)pinned[super_block + PROBE_LONGEST]; queued_super = (int)pinned[super_block + PROBE_QUEUED]; }
+    }
 };
-constexpr int PROBE_SUPER = 16 + 4 * FWD_BATCH_VIEWS;
-constexpr int PROBE_WORDS = PROBE_SUPER + 4 * FWD_BATCH_VIEWS + 8;
 thread_local PairProbe g_probe[16];
 
 int get_probe(PairProbe **out) {
@@ -343,6 +371,22 @@ int get_probe(PairProbe **out) {
     return LVDGS_OK;
 }
 
+// The host's verdict on a view's pair counts (total_super: its super lists', 0 without two-level grouping): *num_rendered and the status, in whose
+// message `view` (< 0: none) names the view of a batch and `remedy` is the entry point's advice; *redo: see enqueue_render_one_level.
+int pair_verdict(uint32_t total, uint32_t total_super, int64_t cap, int view, const char *remedy, int64_t *num_rendered, bool *redo) {
+    *redo = false;
+    if (total > 0x7FFFFFFFu) { set_error("%u (Gaussian, tile) pairs exceed the 2^31 limit", total); return LVDGS_E_RANGE; }
+    *num_rendered = (int64_t)total;
+    if ((int64_t)total > cap) {
+        char who[24] = "";
+        if (view >= 0) snprintf(who, sizeof(who), "view %d: ", view);
+        set_error("%s%u pairs exceed pair_capacity %lld: grow binning_state / scratch%s", who, total, (long long)cap, remedy);
+        return LVDGS_E_CAPACITY;
+    }
+    *redo = (int64_t)total_super > cap;
+    return LVDGS_OK;
+}
+
 // preprocess -> prefix sum of tiles touched; the pair count ends up in g.total (device)
 int enqueue_prepare(const lvdgs_args *a, const GeomView &g, hipStream_t s) {
     const int N = a->num_gaussians;
@@ -352,69 +396,36 @@ int enqueue_prepare(const lvdgs_args *a, const GeomView &g, hipStream_t s) {
     return launch_slot_scan(g.tiles_touched, g.slot_base, w.blocksums, g.total, N, a->debug, s);
 }
 
-static inline void cpu_relax() {
-#if defined(__x86_64__) || defined(__i386__)
-    __builtin_ia32_pause();
-#elif defined(__aarch64__)
-    asm volatile("yield");
-#endif
-}
-
-// The tile scan of this call has written the pinned words when their fourth holds the call's sequence number.
-// (words: the four words of the call -- or of one view of lvdgs_forward_batch)
-int wait_for_sequence(PairProbe *probe, const uint32_t *words = nullptr) {
-    volatile const uint32_t *flag = (words ? words : probe->pinned) + 3;
-    const uint32_t want = probe->seq;
-    const auto t0 = std::chrono::steady_clock::now();
-    // The count arrives some tens of microseconds after the call got here (the projection and the two scans); the wait is a
-    // spin on a pinned word, polite to the core's sibling thread (pause) and, past ~20 us, to the scheduler (yield) -- the
-    // reference's front end and back end are two processes that each sit in this wait once per render.
-    for (uint64_t spins = 0;; spins++) {
-        if (__atomic_load_n(const_cast<uint32_t *>(flag), __ATOMIC_ACQUIRE) == want) return LVDGS_OK;
-        if (spins < 2000) cpu_relax();
-        else std::this_thread::yield();
-        if ((spins & 0xffffu) == 0xffffu) {
-            if (int e = check_hip(hipGetLastError(), "while waiting for the pair count")) return e;
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(60)) {
-                set_error("timed out waiting for the pair count (the kernels before it never finished)");
-                return LVDGS_E_HIP;
-            }
-        }
-    }
-}
-
-// (radix path: the slot scan leaves the pair count alone -- ONE word is copied; the words behind it are the counting path's
-// hints and the sequence number lvdgs_forward's wait spins on, which a copy of uninitialised device words must not touch)
-int enqueue_count_probe(PairProbe *probe, const uint32_t *total, hipStream_t s) {
-    if (int e = check_hip(hipMemcpyAsync(probe->pinned, total, sizeof(uint32_t), hipMemcpyDeviceToHost, s), "read pair count")) return e;
-    return check_hip(hipEventRecord(probe->ready, s), "record pair count event");
-}
-
-// (pair emission ->) grouping by tile -> ranges -> depth order inside each tile -> blend.  `cap` sizes grids and buffers; when `count_on_device`
-// the kernels take the actual pair count from g.total (clamped to cap), otherwise cap IS the count.
-// counted (lvdgs_forward on the counting path): the projection kernel has left the per-chunk tile counts already; the
-// tile-range scan then makes the pair count, which is copied to the host (probe) as soon as it exists, and the scatter
-// makes slot_base.
-int enqueue_render(const lvdgs_args *a, int64_t cap, bool count_on_device, hipStream_t s, bool counted = false, PairProbe *probe = nullptr) {
+// Where the pair count of a render comes from
+enum class PairCount {
+    known,     // the caller has it: `cap` IS the count (lvdgs_forward_render; an empty map)
+    scanned,   // the slot scan behind the projection has left it in g.total (enqueue_prepare: lvdgs_forward on the radix path); clamped to cap
+    counted,   // the projection kernel has left the per-chunk tile counts (enqueue_counted_forward): the tile-range scan makes the count in g.total,
+               // reports it to the call's probe -- if it has one -- as soon as it exists, and the scatter makes slot_base
+};
+// (pair emission ->) grouping by tile -> ranges -> depth order inside each tile -> blend.  `cap` sizes grids and buffers.
+// probe (may be null): the hints of the recent frames on this device, and where a counted render reports.
+int enqueue_render(const lvdgs_args *a, int64_t cap, PairCount from, const PairProbe *probe, hipStream_t s) {
     const int N = a->num_gaussians, W = a->image_width, H = a->image_height;
     GeomView g{}; BinView b{}; ImageView im; RenderScratch w{};
     image_layout(W, H, &im, a->image_state);
-    const int gx = cdiv(W, TILE), num_tiles = gx * cdiv(H, TILE);
+    const TileGrid t(W, H);
+    const bool counted = from == PairCount::counted;
     int row0, row1;
     tile_row_band(*a, &row0, &row1);
     const uint32_t *count = nullptr;
     if (N > 0) {
         geom_layout(N, &g, a->geom_state);
         // blend_fwd accumulates into n_touched: the counting path clears it in its first kernel, the radix path here
-        if (!(cap > 0 && use_counting_path(num_tiles)))
+        if (!(cap > 0 && use_counting_path(t.T)))
             if (int e = check_hip(hipMemsetAsync(a->n_touched, 0, sizeof(int32_t) * (size_t)N, s), "memset n_touched")) return e;
-        if (count_on_device) count = g.total;
+        if (from != PairCount::known) count = g.total;
     }
     bool grouped = false, super = false;
     if (cap > 0) {
         if (bin_view(a, &b) < cap) { set_error("internal: binning_state smaller than the pair capacity"); return LVDGS_E_INVALID; }
         render_scratch_layout(N, cap, W, H, &w, a->scratch);
-        if (use_counting_path(num_tiles)) {
+        if (use_counting_path(t.T)) {
             // counting path: no pair list is materialised, the tile ranges fall out of the counts
             if (!counted)
                 if (int e = launch_group_count(*a, g, im, w, s)) return e;
@@ -422,20 +433,19 @@ int enqueue_render(const lvdgs_args *a, int64_t cap, bool count_on_device, hipSt
             if (super && !counted)   // two-level grouping: the super-tile grid's counts first (single-call forward: the projection kernel has made them), the scan below then takes both grids in its two launches
                 if (int e = launch_super_count(*a, g, w.super, s)) return e;
             // (single-call forward: the tile scan writes the pair count and the hints into the caller thread's pinned words itself)
-            if (int e = launch_group_scan(*a, im, w, cap, counted ? g.total : nullptr, s, counted && probe ? probe->pinned_dev : nullptr,
-                                          counted && probe ? probe->seq : 0u)) return e;
+            uint32_t *total_out = counted ? g.total : nullptr;
+            const PairReport report = counted && probe ? probe->report() : PairReport{};
+            if (int e = launch_group_scan(*a, im, w, cap, total_out, report, s)) return e;
+            if (int e = launch_group_scatter(*a, g, im, w, (unsigned long long *)w.keys, cap, counted, b.pair_valid, total_out, report, s)) return e;
             if (super) {
                 // two-level grouping: keys scattered and sorted per 64 x 64-pixel super-tile, the tiles' lists read off the sorted super lists
                 // (binning.hip); b.tile_keys -- the radix path's -- takes the sorted super lists
-                if (int e = launch_super_scatter(*a, g, w.super, w, (unsigned long long *)w.keys, cap, counted, b.pair_valid, s)) return e;
                 ImageView ims{};
                 ims.ranges = w.super.ranges; ims.long_count = w.super.long_count; ims.long_tiles = w.super.long_tiles;
-                const int Ts = super_tiles_of(W, H);
-                if (int e = launch_tile_depth_sort(ims, Ts, 0, Ts, g.rec, b.tile_keys, w.keys, true, probe ? probe->longest_super : -1,
+                if (int e = launch_tile_depth_sort(ims, t.Ts, 0, t.Ts, g.rec, b.tile_keys, w.keys, true, probe ? probe->longest_super : -1,
                                                    probe ? probe->queued_super : 0, a->debug, s)) return e;
                 if (int e = launch_super_expand(*a, g, w.super, im, b.tile_keys, b.point_list, s)) return e;
-            } else if (int e = launch_group_scatter(*a, g, im, w, (unsigned long long *)w.keys, cap, counted, b.pair_valid, s, counted ? g.total : nullptr,
-                                                    counted && probe ? probe->pinned_dev : nullptr, counted && probe ? probe->seq : 0u)) return e;
+            }
             grouped = true;
         } else {
             if (!w.hist) { set_error("internal: scratch was not laid out for the radix grouping"); return LVDGS_E_INVALID; }
@@ -452,11 +462,11 @@ int enqueue_render(const lvdgs_args *a, int64_t cap, bool count_on_device, hipSt
         }
     }
     if (!grouped)
-        if (int e = launch_tile_ranges(b.tile_keys, cap, count, im, num_tiles, a->debug, s)) return e;
+        if (int e = launch_tile_ranges(b.tile_keys, cap, count, im, t.T, a->debug, s)) return e;
     // w.keys + w.vals: the (depth, id) keys the counting path scattered, or scratch for over-long segments after the radix path
     if (cap > 0 && !super) {
         // long segments: expected as the recent frames on this device had them (single-call forward), unknown otherwise
-        if (int e = launch_tile_depth_sort(im, num_tiles, row0 * gx, row1 * gx, g.rec, b.point_list, w.keys, grouped, probe ? probe->longest : -1,
+        if (int e = launch_tile_depth_sort(im, t.T, row0 * t.gx, row1 * t.gx, g.rec, b.point_list, w.keys, grouped, probe ? probe->longest : -1,
                                            probe ? probe->queued : 0, a->debug, s)) return e;
     }
     // (tile lists beyond what one wave sorts on recent frames: the blend kernel built for deep lists)
@@ -478,6 +488,36 @@ int check_render_buffers(const lvdgs_args *a, int64_t cap) {
     return LVDGS_OK;
 }
 
+// What the projection of a map (N > 0) writes: the geometry half of a forward call's buffers
+int check_projection_buffers(const lvdgs_args *a) {
+    if (!a->radii || !a->geom_state || !a->scratch) { set_error("radii / geom_state / scratch is NULL"); return LVDGS_E_INVALID; }
+    if (a->geom_bytes < lvdgs_geom_bytes(a->num_gaussians) || a->scratch_bytes < lvdgs_prepare_scratch_bytes(a->num_gaussians)) {
+        set_error("geom_state or scratch too small"); return LVDGS_E_INVALID;
+    }
+    return LVDGS_OK;
+}
+
+// A forward of a map (N > 0) with a pair capacity: the capacity and every buffer it sizes
+int check_forward(const lvdgs_args *a) {
+    const int64_t cap = a->pair_capacity;
+    if (cap <= 0 || cap > 0x7FFFFFFFll) { set_error("pair_capacity must be in 1..2^31-1"); return LVDGS_E_INVALID; }
+    if (int e = check_projection_buffers(a)) return e;
+    return check_render_buffers(a, cap);
+}
+
+// Are a and a0 views of one frame: the image size, the band, and those of `flags` that must agree
+bool one_frame(const lvdgs_args *a, const lvdgs_args *a0, int flags) {
+    return a->image_width == a0->image_width && a->image_height == a0->image_height && a->tile_row_begin == a0->tile_row_begin &&
+           a->tile_row_end == a0->tile_row_end && !((a->flags ^ a0->flags) & flags);
+}
+
+// lvdgs_loss_args as the backward blend pass of this rasterizer call reads it
+int fused_loss_params(const lvdgs_args *a, const lvdgs_loss_args *loss, LossParams *out) {
+    if (int e = loss_fused_params(loss, out)) return e;
+    if (loss->width != a->image_width || loss->height != a->image_height) { set_error("fused loss: image size differs from the rasterizer's"); return LVDGS_E_INVALID; }
+    return LVDGS_OK;
+}
+
 // Two-level grouping whose super lists outgrew the pair capacity while the tile lists fit (Ds > cap >= D: a Gaussian whose rectangle spans
 // more than 64 super-tiles is listed on all of them, however few of its tiles are kept): the tile lists read off the super lists were cut
 // short.  The view is redone one-level behind what is enqueued -- the projection's counts, geom_state and slot_base stand -- with no
@@ -487,7 +527,27 @@ int enqueue_render_one_level(const lvdgs_args *a, int64_t cap, hipStream_t s) {
     one.flags &= ~LVDGS_FLAG_SUPER_TILES;
     // (the blend of the cut lists counted into n_touched; the counting path's projection cleared it)
     if (int e = check_hip(hipMemsetAsync(a->n_touched, 0, sizeof(int32_t) * (size_t)a->num_gaussians, s), "memset n_touched")) return e;
-    return enqueue_render(&one, cap, true, s, true, nullptr);
+    return enqueue_render(&one, cap, PairCount::counted, nullptr, s);
+}
+
+// A forward on the counting path: the projection kernel counts the pairs per (chunk, tile) as it goes, the tile-range scan makes the pair count
+// and the scatter the slot prefix sum: three launches fewer than project / scan / count in turn.  (render: a, or its copy with LVDGS_FLAG_NO_BLEND)
+int enqueue_counted_forward(const lvdgs_args *a, const lvdgs_args *render, PairProbe *probe, GeomView *g, hipStream_t s) {
+    const int N = a->num_gaussians, W = a->image_width, H = a->image_height;
+    ImageView im; RenderScratch w{};
+    geom_layout(N, g, a->geom_state);
+    image_layout(W, H, &im, a->image_state);
+    render_scratch_layout(N, a->pair_capacity, W, H, &w, a->scratch);
+    if (int e = launch_preprocess_count(*a, *g, im, w, s)) return e;
+    probe->next_sequence();
+    return enqueue_render(render, a->pair_capacity, PairCount::counted, probe, s);
+}
+// ... and the host's half behind everything the call enqueues: the wait for the counts, the hints for the next frames, the verdict
+int finish_counted_forward(const lvdgs_args *a, PairProbe *probe, const char *remedy, int64_t *num_rendered, bool *redo) {
+    if (int e = probe->wait(PROBE_CALL)) return e;
+    const bool super = super_tiles_in_use(*a);
+    probe->fold_hints(PROBE_CALL, 1, super ? PROBE_CALL_SUPER : -1);
+    return pair_verdict(probe->count(PROBE_CALL), super ? probe->count(PROBE_CALL_SUPER) : 0u, a->pair_capacity, -1, remedy, num_rendered, redo);
 }
 }  // namespace
 
@@ -499,10 +559,7 @@ int lvdgs_forward_prepare(const lvdgs_args *a, int64_t *num_rendered, void *stre
     const int N = a->num_gaussians;
     *num_rendered = 0;
     if (N == 0) return LVDGS_OK;
-    if (!a->radii || !a->geom_state || !a->scratch) { set_error("radii / geom_state / scratch is NULL"); return LVDGS_E_INVALID; }
-    if (a->geom_bytes < lvdgs_geom_bytes(N) || a->scratch_bytes < lvdgs_prepare_scratch_bytes(N)) {
-        set_error("geom_state or scratch too small"); return LVDGS_E_INVALID;
-    }
+    if (int e = check_projection_buffers(a)) return e;
     GeomView g;
     geom_layout(N, &g, a->geom_state);
     if (int e = enqueue_prepare(a, g, s)) return e;
@@ -524,7 +581,7 @@ int lvdgs_forward_render(const lvdgs_args *a, void *stream) {
     // that outgrew the capacity -- the contract makes the bits the same)
     lvdgs_args one = *a;
     one.flags &= ~LVDGS_FLAG_SUPER_TILES;
-    return enqueue_render(&one, D, false, s);
+    return enqueue_render(&one, D, PairCount::known, nullptr, s);
 }
 
 int lvdgs_forward(const lvdgs_args *a, int64_t *num_rendered, void *stream) {
@@ -536,121 +593,107 @@ int lvdgs_forward(const lvdgs_args *a, int64_t *num_rendered, void *stream) {
     *num_rendered = 0;
     if (N == 0) {
         if (int e = check_render_buffers(a, 0)) return e;
-        return enqueue_render(a, 0, false, s);
+        return enqueue_render(a, 0, PairCount::known, nullptr, s);
     }
+    if (int e = check_forward(a)) return e;
     const int64_t cap = a->pair_capacity;
-    if (cap <= 0 || cap > 0x7FFFFFFFll) { set_error("pair_capacity must be in 1..2^31-1"); return LVDGS_E_INVALID; }
-    if (!a->radii || !a->geom_state || !a->scratch) { set_error("radii / geom_state / scratch is NULL"); return LVDGS_E_INVALID; }
-    if (a->geom_bytes < lvdgs_geom_bytes(N) || a->scratch_bytes < lvdgs_prepare_scratch_bytes(N)) {
-        set_error("geom_state or scratch too small"); return LVDGS_E_INVALID;
-    }
-    if (int e = check_render_buffers(a, cap)) return e;
     PairProbe *probe = nullptr;
     if (int e = get_probe(&probe)) return e;
     GeomView g;
-    geom_layout(N, &g, a->geom_state);
-    // On the counting path the projection kernel counts the pairs per (chunk, tile) as it goes, the tile-range scan makes
-    // the pair count and the scatter the slot prefix sum: three launches fewer than project / scan / count in turn.
-    const bool counted = use_counting_path(cdiv(a->image_width, TILE) * cdiv(a->image_height, TILE));
-    if (counted) {
-        ImageView im; RenderScratch w{};
-        image_layout(a->image_width, a->image_height, &im, a->image_state);
-        render_scratch_layout(N, cap, a->image_width, a->image_height, &w, a->scratch);
-        if (int e = launch_preprocess_count(*a, g, im, w, s)) return e;
-    } else {
-        if (int e = enqueue_prepare(a, g, s)) return e;
-        if (int e = enqueue_count_probe(probe, g.total, s)) return e;
-    }
+    const char *remedy = " and call lvdgs_forward_render";
+    bool redo;
     // Everything after the count is enqueued BEFORE the host waits for it: the GPU keeps working on
     // the tile sort and the blend while the host learns whether the capacity was enough.
-    if (counted) { probe->seq++; if (probe->seq == 0u) probe->seq = 1u; }
-    if (int e = enqueue_render(a, cap, true, s, counted, probe)) return e;
-    if (counted) {
-        if (int e = wait_for_sequence(probe)) return e;
-    } else if (int e = check_hip(hipEventSynchronize(probe->ready), "wait for pair count")) return e;
-    const uint32_t total = probe->pinned[0];
-    uint32_t total_super = 0u;   // (two-level grouping: the super lists' pair count -- the sequence number waited for covers it)
-    if (counted) {   // what the next frames expect: this frame's long segments, or a recent frame's for a while (views alternate)
-        const int longest = (int)probe->pinned[1], queued = (int)probe->pinned[2];
-        if (longest >= probe->longest || probe->keep == 0) { probe->longest = longest; probe->queued = queued; probe->keep = longest ? 32 : 0; }
-        else probe->keep--;
-        if (super_tiles_in_use(*a)) {
-            total_super = probe->pinned[8];
-            probe->longest_super = (int)probe->pinned[8 + 1]; probe->queued_super = (int)probe->pinned[8 + 2];
-        }
+    if (use_counting_path(TileGrid(*a).T)) {
+        if (int e = enqueue_counted_forward(a, a, probe, &g, s)) return e;
+        if (int e = finish_counted_forward(a, probe, remedy, num_rendered, &redo)) return e;
+    } else {
+        geom_layout(N, &g, a->geom_state);
+        if (int e = enqueue_prepare(a, g, s)) return e;
+        // (the slot scan leaves the pair count alone -- ONE word is copied; the words behind it are the counting path's hints and
+        // the sequence number its wait spins on, which a copy of uninitialised device words must not touch)
+        if (int e = check_hip(hipMemcpyAsync(probe->pinned + PROBE_CALL + PROBE_COUNT, g.total, sizeof(uint32_t), hipMemcpyDeviceToHost, s), "read pair count")) return e;
+        if (int e = check_hip(hipEventRecord(probe->ready, s), "record pair count event")) return e;
+        if (int e = enqueue_render(a, cap, PairCount::scanned, probe, s)) return e;
+        if (int e = check_hip(hipEventSynchronize(probe->ready), "wait for pair count")) return e;
+        if (int e = pair_verdict(probe->count(PROBE_CALL), 0u, cap, -1, remedy, num_rendered, &redo)) return e;
     }
-    if (total > 0x7FFFFFFFu) { set_error("%u (Gaussian, tile) pairs exceed the 2^31 limit", total); return LVDGS_E_RANGE; }
-    *num_rendered = (int64_t)total;
-    if ((int64_t)total > cap) {
-        set_error("%u pairs exceed pair_capacity %lld: grow binning_state / scratch and call lvdgs_forward_render", total, (long long)cap);
-        return LVDGS_E_CAPACITY;
-    }
-    if ((int64_t)total_super > cap) return enqueue_render_one_level(a, cap, s);
-    return LVDGS_OK;
+    return redo ? enqueue_render_one_level(a, cap, s) : LVDGS_OK;
 }
 
-// views_out (lvdgs_blend_backward_fused_loss_batch): the call checks its arguments, lays its buffers out and stops there
-struct BackwardViews { GeomView g; BinView b; ImageView im; BwdScratch w; };
-static int backward_impl(const lvdgs_args *a, const LossParams *fused, int propagate_opacity, hipStream_t s, BackwardViews *views_out = nullptr,
-                         const MaskedLossView *masked = nullptr) {
+// What a backward call is given for the pixels' gradients: which pointers it needs, which flags it may carry
+enum class BackwardKind {
+    pixel_gradients,   // dL_dout_*: the call's own blend pass reads them (lvdgs_backward)
+    fused_loss,        // a lvdgs_loss_args: the blend pass evaluates the photometric loss itself
+    masked_loss,       // a lvdgs_masked_loss_args: ... the static-mask mapping loss
+    blended,           // nothing: the blend pass has run (lvdgs_gaussian_backward_batch behind a batched one)
+};
+struct BackwardViews { int64_t D; GeomView g; BinView b; ImageView im; BwdScratch w; };
+
+// The arguments of a backward call of a kind, and its buffers laid out (D: its pair count)
+static int check_backward(const lvdgs_args *a, BackwardKind kind, BackwardViews *v) {
     if (int e = check_common(a)) return e;
     if (int e = check_gaussians(a)) return e;
     const int N = a->num_gaussians, W = a->image_width, H = a->image_height;
     const int64_t D = N == 0 ? 0 : a->num_rendered;
     if (D < 0) { set_error("negative num_rendered"); return LVDGS_E_INVALID; }
     if (!a->image_state || a->image_bytes < lvdgs_image_bytes(W, H)) { set_error("image_state is NULL or too small"); return LVDGS_E_INVALID; }
-    GeomView g{}; BinView b{}; ImageView im; BwdScratch w{};
-    image_layout(W, H, &im, a->image_state);
+    *v = BackwardViews{};
+    v->D = D;
+    image_layout(W, H, &v->im, a->image_state);
     const bool pose_only = (a->flags & LVDGS_FLAG_POSE_ONLY) != 0;
-    if (N > 0) {
-        if ((!fused && !masked && !a->dL_dout_color) || !a->projmatrix_raw || !a->radii) { set_error("a required backward pointer is NULL"); return LVDGS_E_INVALID; }
-        if (masked && pose_only) { set_error("LVDGS_FLAG_POSE_ONLY: the static-mask mapping loss is a mapping loss, its backward makes every gradient"); return LVDGS_E_INVALID; }
-        if (pose_only) {
-            // a view-dependent colour moves with the camera centre: its gradient feeds dL/dtau (preprocess.hip), and the
-            // pose-only passes do not make it
-            if (a->shs && a->sh_degree > 0) { set_error("LVDGS_FLAG_POSE_ONLY needs sh_degree 0 or colors_precomp"); return LVDGS_E_INVALID; }
-            if (a->flags & LVDGS_FLAG_ACCUMULATE_PARAM_GRADS) { set_error("LVDGS_FLAG_POSE_ONLY writes no parameter gradients: nothing to accumulate"); return LVDGS_E_INVALID; }
-        } else {
-            if (!a->dL_dmeans3D || !a->dL_dmeans2D || !a->dL_dopacities) { set_error("a required backward pointer is NULL"); return LVDGS_E_INVALID; }
-            if (a->cov3D_precomp ? !a->dL_dcov3D : (!a->dL_dscales || !a->dL_drotations)) { set_error("covariance gradient output is NULL"); return LVDGS_E_INVALID; }
-            if (a->shs ? !a->dL_dshs : !a->dL_dcolors) { set_error("colour gradient output is NULL"); return LVDGS_E_INVALID; }
-        }
-        if (!a->geom_state || !a->scratch || (D > 0 && !a->binning_state)) { set_error("a state / scratch buffer is NULL"); return LVDGS_E_INVALID; }
-        if (a->geom_bytes < lvdgs_geom_bytes(N) || (D > 0 && a->binning_bytes < lvdgs_binning_bytes(D)) ||
-            a->scratch_bytes < lvdgs_backward_scratch_bytes(N, D)) {
-            set_error("a state / scratch buffer is too small"); return LVDGS_E_INVALID;
-        }
-        geom_layout(N, &g, a->geom_state);
-        bwd_scratch_layout(N, D, &w, a->scratch);
-        if (D > 0) bin_view(a, &b);
+    if (N == 0) return LVDGS_OK;
+    if ((kind == BackwardKind::pixel_gradients && !a->dL_dout_color) || !a->projmatrix_raw || !a->radii) { set_error("a required backward pointer is NULL"); return LVDGS_E_INVALID; }
+    if (kind == BackwardKind::masked_loss && pose_only) { set_error("LVDGS_FLAG_POSE_ONLY: the static-mask mapping loss is a mapping loss, its backward makes every gradient"); return LVDGS_E_INVALID; }
+    if (pose_only) {
+        // a view-dependent colour moves with the camera centre: its gradient feeds dL/dtau (preprocess.hip), and the
+        // pose-only passes do not make it
+        if (a->shs && a->sh_degree > 0) { set_error("LVDGS_FLAG_POSE_ONLY needs sh_degree 0 or colors_precomp"); return LVDGS_E_INVALID; }
+        if (a->flags & LVDGS_FLAG_ACCUMULATE_PARAM_GRADS) { set_error("LVDGS_FLAG_POSE_ONLY writes no parameter gradients: nothing to accumulate"); return LVDGS_E_INVALID; }
+    } else {
+        if (!a->dL_dmeans3D || !a->dL_dmeans2D || !a->dL_dopacities) { set_error("a required backward pointer is NULL"); return LVDGS_E_INVALID; }
+        if (a->cov3D_precomp ? !a->dL_dcov3D : (!a->dL_dscales || !a->dL_drotations)) { set_error("covariance gradient output is NULL"); return LVDGS_E_INVALID; }
+        if (a->shs ? !a->dL_dshs : !a->dL_dcolors) { set_error("colour gradient output is NULL"); return LVDGS_E_INVALID; }
     }
-    // With the loss inside, the blend pass runs even over empty lists (a view that sees nothing, an empty map): it is what
-    // evaluates the loss of the background image -- value and exposure gradients -- and no pair record is written.
-    if (views_out) { *views_out = BackwardViews{g, b, im, w}; return LVDGS_OK; }
-    if (fused) {
-        if (!(a->flags & LVDGS_FLAG_NO_BLEND))
-            if (int e = launch_blend_bwd_fused_loss(*a, g, b, im, w, *fused, propagate_opacity, s)) return e;
-    } else if (masked) {
-        if (D > 0 && !(a->flags & LVDGS_FLAG_NO_BLEND))
-            if (int e = launch_blend_bwd_masked_loss(*a, g, b, im, w, *masked, s)) return e;
-    } else if (D > 0) {
-        if (int e = launch_blend_bwd(*a, g, b, im, w, s)) return e;
+    if (!a->geom_state || !a->scratch || (D > 0 && !a->binning_state)) { set_error("a state / scratch buffer is NULL"); return LVDGS_E_INVALID; }
+    if (a->geom_bytes < lvdgs_geom_bytes(N) || (D > 0 && a->binning_bytes < lvdgs_binning_bytes(D)) ||
+        a->scratch_bytes < lvdgs_backward_scratch_bytes(N, D)) {
+        set_error("a state / scratch buffer is too small"); return LVDGS_E_INVALID;
     }
-    if (N == 0) return a->dL_dtau ? check_hip(hipMemsetAsync(a->dL_dtau, 0, 6 * sizeof(float), s), "memset tau") : LVDGS_OK;
-    return launch_preprocess_bwd(*a, g, w, b.pair_valid, s);
+    geom_layout(N, &v->g, a->geom_state);
+    bwd_scratch_layout(N, D, &v->w, a->scratch);
+    if (D > 0) bin_view(a, &v->b);
+    return LVDGS_OK;
+}
+
+// The per-Gaussian pass behind a view's backward blend pass (an empty map: the pose gradient is zero)
+static int enqueue_gaussian_backward(const lvdgs_args *a, const BackwardViews &v, hipStream_t s) {
+    if (a->num_gaussians == 0) return a->dL_dtau ? check_hip(hipMemsetAsync(a->dL_dtau, 0, 6 * sizeof(float), s), "memset tau") : LVDGS_OK;
+    return launch_preprocess_bwd(*a, v.g, v.w, v.b.pair_valid, s);
 }
 
 int lvdgs_backward(const lvdgs_args *a, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (a && (a->flags & LVDGS_FLAG_NO_BLEND)) { set_error("LVDGS_FLAG_NO_BLEND: lvdgs_backward runs its own blend pass; the calls that leave it to a batched one (lvdgs_blend_backward_fused_loss_batch / lvdgs_blend_backward_window_batch) are lvdgs_backward_fused_loss, lvdgs_backward_masked_loss and lvdgs_gaussian_backward_batch"); return LVDGS_E_INVALID; }
-    return backward_impl(a, nullptr, 0, (hipStream_t)stream);
+    BackwardViews v;
+    if (int e = check_backward(a, BackwardKind::pixel_gradients, &v)) return e;
+    if (v.D > 0)
+        if (int e = launch_blend_bwd(*a, v.g, v.b, v.im, v.w, s)) return e;
+    return enqueue_gaussian_backward(a, v, s);
 }
 
 int lvdgs_backward_fused_loss(const lvdgs_args *a, const lvdgs_loss_args *loss, int32_t propagate_opacity_grad, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (!a) { set_error("backward: args is NULL"); return LVDGS_E_INVALID; }
     LossParams lp;
-    if (int e = loss_fused_params(loss, &lp)) return e;
-    if (loss->width != a->image_width || loss->height != a->image_height) { set_error("fused loss: image size differs from the rasterizer's"); return LVDGS_E_INVALID; }
-    return backward_impl(a, &lp, propagate_opacity_grad != 0, (hipStream_t)stream);
+    if (int e = fused_loss_params(a, loss, &lp)) return e;
+    BackwardViews v;
+    if (int e = check_backward(a, BackwardKind::fused_loss, &v)) return e;
+    // With the loss inside, the blend pass runs even over empty lists (a view that sees nothing, an empty map): it is what
+    // evaluates the loss of the background image -- value and exposure gradients -- and no pair record is written.
+    if (!(a->flags & LVDGS_FLAG_NO_BLEND))
+        if (int e = launch_blend_bwd_fused_loss(*a, v.g, v.b, v.im, v.w, lp, propagate_opacity_grad != 0, s)) return e;
+    return enqueue_gaussian_backward(a, v, s);
 }
 
 // The forward passes of `count` views of one map and one image size, every stage ONE launch (include/lvdgs.h).
@@ -663,8 +706,7 @@ int lvdgs_forward_batch(const lvdgs_args *const *views, int32_t count, int64_t *
     if (!a0) { set_error("forward batch: view 0 is NULL"); return LVDGS_E_INVALID; }
     const int N = a0->num_gaussians, W = a0->image_width, H = a0->image_height;
     if (int e = check_common(a0)) return e;
-    const int num_tiles = cdiv(W, TILE) * cdiv(H, TILE);
-    if (N <= 0 || !use_counting_path(num_tiles)) { set_error("forward batch: needs a map (N > 0) and an image of at most %d tiles (the views go through lvdgs_forward one by one otherwise)", group_max_tiles()); return LVDGS_E_INVALID; }
+    if (N <= 0 || !use_counting_path(TileGrid(W, H).T)) { set_error("forward batch: needs a map (N > 0) and an image of at most %d tiles (the views go through lvdgs_forward one by one otherwise)", group_max_tiles()); return LVDGS_E_INVALID; }
     std::vector<GeomView> g(count); std::vector<BinView> b(count); std::vector<ImageView> im(count); std::vector<RenderScratch> w(count);
     std::vector<int64_t> caps(count);
     for (int k = 0; k < count; k++) {
@@ -672,34 +714,30 @@ int lvdgs_forward_batch(const lvdgs_args *const *views, int32_t count, int64_t *
         if (!a) { set_error("forward batch: view %d is NULL", k); return LVDGS_E_INVALID; }
         if (int e = check_common(a)) return e;
         if (int e = check_gaussians(a)) return e;
-        if (a->num_gaussians != N || a->image_width != W || a->image_height != H || a->tile_row_begin != a0->tile_row_begin || a->tile_row_end != a0->tile_row_end ||
+        if (a->num_gaussians != N || !one_frame(a, a0, LVDGS_FLAG_LIST_ALL_TILES | LVDGS_FLAG_NO_BLEND | LVDGS_FLAG_SUPER_TILES) ||
             a->means3D != a0->means3D || a->opacities != a0->opacities || a->scales != a0->scales || a->rotations != a0->rotations ||
             a->cov3D_precomp != a0->cov3D_precomp || a->shs != a0->shs || a->colors_precomp != a0->colors_precomp || a->sh_coeffs != a0->sh_coeffs ||
-            a->activations != a0->activations || ((a->flags ^ a0->flags) & (LVDGS_FLAG_LIST_ALL_TILES | LVDGS_FLAG_NO_BLEND | LVDGS_FLAG_SUPER_TILES))) {
+            a->activations != a0->activations) {
             set_error("forward batch: the views differ in map (means3D / opacities / scales / rotations / cov3D_precomp / shs / colors_precomp / activations), image size, band or flags"); return LVDGS_E_INVALID;
         }
-        const int64_t cap = a->pair_capacity;
-        if (cap <= 0 || cap > 0x7FFFFFFFll) { set_error("pair_capacity must be in 1..2^31-1"); return LVDGS_E_INVALID; }
-        if (!a->radii || !a->geom_state || !a->scratch) { set_error("radii / geom_state / scratch is NULL"); return LVDGS_E_INVALID; }
-        if (a->geom_bytes < lvdgs_geom_bytes(N) || a->scratch_bytes < lvdgs_prepare_scratch_bytes(N)) { set_error("geom_state or scratch too small"); return LVDGS_E_INVALID; }
-        if (int e = check_render_buffers(a, cap)) return e;
-        caps[k] = cap;
+        if (int e = check_forward(a)) return e;
+        caps[k] = a->pair_capacity;
         geom_layout(N, &g[k], a->geom_state);
         image_layout(W, H, &im[k], a->image_state);
-        render_scratch_layout(N, cap, W, H, &w[k], a->scratch);
-        if (bin_view(a, &b[k]) < cap) { set_error("internal: binning_state smaller than the pair capacity"); return LVDGS_E_INVALID; }
+        render_scratch_layout(N, caps[k], W, H, &w[k], a->scratch);
+        if (bin_view(a, &b[k]) < caps[k]) { set_error("internal: binning_state smaller than the pair capacity"); return LVDGS_E_INVALID; }
     }
     PairProbe *probe = nullptr;
     if (int e = get_probe(&probe)) return e;
-    probe->seq++; if (probe->seq == 0u) probe->seq = 1u;
+    const bool super = super_tiles_in_use(*a0);   // two-level grouping: the scan and the scatter work on the super-tile grid; the tiles' lists are read off the sorted super lists
+    int status = LVDGS_OK;
     for (int first = 0; first < count; first += FWD_BATCH_VIEWS) {
         const int m = count - first < FWD_BATCH_VIEWS ? count - first : FWD_BATCH_VIEWS;
         const lvdgs_args *const *av = views + first;
-        uint32_t *words = probe->pinned + 16, *words_dev = probe->pinned_dev + 16;
+        probe->next_sequence();
         if (int e = launch_preprocess_count_batch(av, &g[first], &im[first], &w[first], m, s)) return e;
-        if (int e = launch_group_scan_batch(av, &g[first], &im[first], &w[first], &caps[first], m, words_dev, probe->seq, probe->pinned_dev + PROBE_SUPER, s)) return e;
+        if (int e = launch_group_scan_batch(av, &g[first], &im[first], &w[first], &caps[first], m, probe->report(), s)) return e;
         if (int e = launch_group_scatter_batch(av, &g[first], &im[first], &w[first], &b[first], &caps[first], m, s)) return e;
-        const bool super = super_tiles_in_use(*a0);   // two-level grouping: the launches above worked on the super-tile grid; the tiles' lists are read off the sorted super lists
         if (int e = launch_tile_depth_sort_batch(av, &g[first], &im[first], &w[first], &b[first], m, super ? probe->longest_super : probe->longest,
                                                  super ? probe->queued_super : probe->queued, s)) return e;
         if (super)
@@ -707,31 +745,18 @@ int lvdgs_forward_batch(const lvdgs_args *const *views, int32_t count, int64_t *
         if (!(a0->flags & LVDGS_FLAG_NO_BLEND))
             if (int e = launch_blend_fwd_batch(av, &g[first], &b[first], &im[first], m, probe->longest > 0, s)) return e;
         // everything is enqueued: now the counts (the GPU is busy with the scatter, the sorts and the blend meanwhile)
-        int longest = 0, queued = 0;
-        const uint32_t *words_super = probe->pinned + PROBE_SUPER;   // (two-level grouping: view k's super lists' count and hints; the wait covers them)
         for (int k = 0; k < m; k++) {
-            if (int e = wait_for_sequence(probe, words + 4 * k)) return e;
-            num_rendered[first + k] = (int64_t)words[4 * k];
-            longest = std::max(longest, (int)words[4 * k + 1]); queued = std::max(queued, (int)words[4 * k + 2]);
+            const int block = PROBE_BATCH + PROBE_BLOCK * k, block_super = PROBE_BATCH_SUPER + PROBE_BLOCK * k;
+            if (int e = probe->wait(block)) return e;
+            bool redo;
+            const int e = pair_verdict(probe->count(block), super ? probe->count(block_super) : 0u, caps[first + k], first + k, " and call lvdgs_forward_render for it",
+                                       &num_rendered[first + k], &redo);
+            if (e == LVDGS_E_RANGE) return e;
+            if (e) status = e;
+            if (redo)
+                if (int e2 = enqueue_render_one_level(av[k], caps[first + k], s)) return e2;
         }
-        if (super) {
-            probe->longest_super = (int)words_super[1]; probe->queued_super = (int)words_super[2];   // (the first view's)
-            // a view whose super lists outgrew its capacity while its tile lists fit: redone one-level (enqueue_render_one_level)
-            for (int k = 0; k < m; k++)
-                if (num_rendered[first + k] <= caps[first + k] && (int64_t)words_super[4 * k] > caps[first + k])
-                    if (int e = enqueue_render_one_level(av[k], caps[first + k], s)) return e;
-        }
-        if (m < count) { probe->seq++; if (probe->seq == 0u) probe->seq = 1u; }   // (the next group of views re-uses the words)
-        if (longest >= probe->longest || probe->keep == 0) { probe->longest = longest; probe->queued = queued; probe->keep = longest ? 32 : 0; }
-        else probe->keep--;
-    }
-    int status = LVDGS_OK;
-    for (int k = 0; k < count; k++) {
-        if (num_rendered[k] > 0x7FFFFFFFll) { set_error("%lld (Gaussian, tile) pairs exceed the 2^31 limit", (long long)num_rendered[k]); return LVDGS_E_RANGE; }
-        if (num_rendered[k] > caps[k]) {
-            set_error("view %d: %lld pairs exceed pair_capacity %lld: grow binning_state / scratch and call lvdgs_forward_render for it", k, (long long)num_rendered[k], (long long)caps[k]);
-            status = LVDGS_E_CAPACITY;
-        }
+        probe->fold_hints(PROBE_BATCH, m, super ? PROBE_BATCH_SUPER : -1);
     }
     return status;
 }
@@ -746,8 +771,7 @@ int lvdgs_forward_backward_fused_loss(const lvdgs_args *a, const lvdgs_loss_args
     hipStream_t s = (hipStream_t)stream;
     if (!a || !num_rendered) { set_error("forward + backward: args / num_rendered is NULL"); return LVDGS_E_INVALID; }
     if (int e = check_common(a)) return e;
-    const int N = a->num_gaussians, W = a->image_width, H = a->image_height;
-    const int num_tiles = cdiv(W, TILE) * cdiv(H, TILE);
+    const int N = a->num_gaussians, num_tiles = TileGrid(*a).T;
     const int64_t cap = a->pair_capacity;
     static const bool off = getenv("LVDGS_NO_FUSED_BLEND") != nullptr;   // (test / A-B hook: the two calls in turn whatever the grid)
     const bool fuse = !off && N > 0 && use_counting_path(num_tiles) && num_tiles <= LVDGS_FUSED_BLEND_MAX_TILES && !(a->flags & LVDGS_FLAG_NO_BLEND) &&
@@ -761,51 +785,28 @@ int lvdgs_forward_backward_fused_loss(const lvdgs_args *a, const lvdgs_loss_args
     *num_rendered = 0;
     if (int e = check_gaussians(a)) return e;
     LossParams lp;
-    if (int e = loss_fused_params(loss, &lp)) return e;
-    if (loss->width != W || loss->height != H) { set_error("fused loss: image size differs from the rasterizer's"); return LVDGS_E_INVALID; }
-    if (!a->radii || !a->geom_state || !a->scratch) { set_error("radii / geom_state / scratch is NULL"); return LVDGS_E_INVALID; }
-    if (a->geom_bytes < lvdgs_geom_bytes(N) || a->scratch_bytes < lvdgs_prepare_scratch_bytes(N)) { set_error("geom_state or scratch too small"); return LVDGS_E_INVALID; }
-    if (int e = check_render_buffers(a, cap)) return e;
+    if (int e = fused_loss_params(a, loss, &lp)) return e;
+    if (int e = check_forward(a)) return e;
     // the backward's arguments, checked with the pair CAPACITY standing in for the count (the scratch must hold that many records)
     lvdgs_args bw = *a;
     bw.num_rendered = cap;
     BackwardViews v;
-    if (int e = backward_impl(&bw, &lp, propagate_opacity_grad != 0, s, &v)) return e;
+    if (int e = check_backward(&bw, BackwardKind::fused_loss, &v)) return e;
     PairProbe *probe = nullptr;
     if (int e = get_probe(&probe)) return e;
     GeomView g;
-    geom_layout(N, &g, a->geom_state);
-    {
-        ImageView im; RenderScratch w{};
-        image_layout(W, H, &im, a->image_state);
-        render_scratch_layout(N, cap, W, H, &w, a->scratch);
-        if (int e = launch_preprocess_count(*a, g, im, w, s)) return e;
-    }
-    probe->seq++; if (probe->seq == 0u) probe->seq = 1u;
     lvdgs_args fw = *a;
     fw.flags |= LVDGS_FLAG_NO_BLEND;   // (grouping and tile sort; the blend follows below, together with the backward's)
-    if (int e = enqueue_render(&fw, cap, true, s, true, probe)) return e;
+    if (int e = enqueue_counted_forward(a, &fw, probe, &g, s)) return e;
     // (both halves of the backward look at the frame's pair count on the device and stand down when it exceeds the capacity)
     // (two-level grouping: and when the super lists' count does -- the tile lists read off them were cut short)
     const bool super = super_tiles_in_use(*a);
     const uint32_t *total_super_dev = super ? g.total + SUPER_TOTAL_WORD : nullptr;
     if (int e = launch_blend_fwd_bwd_fused_loss(*a, v.g, v.b, v.im, v.w, lp, propagate_opacity_grad != 0, probe->longest > 0, g.total, (uint32_t)cap, total_super_dev, s)) return e;
     if (int e = launch_preprocess_bwd(*a, v.g, v.w, v.b.pair_valid, s, g.total, (uint32_t)cap, total_super_dev)) return e;
-    if (int e = wait_for_sequence(probe)) return e;
-    const uint32_t total = probe->pinned[0], total_super = super ? probe->pinned[8] : 0u;
-    {
-        const int longest = (int)probe->pinned[1], queued = (int)probe->pinned[2];
-        if (longest >= probe->longest || probe->keep == 0) { probe->longest = longest; probe->queued = queued; probe->keep = longest ? 32 : 0; }
-        else probe->keep--;
-        if (super) { probe->longest_super = (int)probe->pinned[8 + 1]; probe->queued_super = (int)probe->pinned[8 + 2]; }
-    }
-    if (total > 0x7FFFFFFFu) { set_error("%u (Gaussian, tile) pairs exceed the 2^31 limit", total); return LVDGS_E_RANGE; }
-    *num_rendered = (int64_t)total;
-    if ((int64_t)total > cap) {
-        set_error("%u pairs exceed pair_capacity %lld: grow binning_state / scratch, then lvdgs_forward_render and lvdgs_backward_fused_loss", total, (long long)cap);
-        return LVDGS_E_CAPACITY;
-    }
-    if ((int64_t)total_super > cap) {
+    bool redo;
+    if (int e = finish_counted_forward(a, probe, ", then lvdgs_forward_render and lvdgs_backward_fused_loss", num_rendered, &redo)) return e;
+    if (redo) {
         // both passes stood down: the view one-level (enqueue_render_one_level), then the two blend passes and the per-Gaussian pass again
         if (int e = enqueue_render_one_level(&fw, cap, s)) return e;
         if (int e = launch_blend_fwd_bwd_fused_loss(*a, v.g, v.b, v.im, v.w, lp, propagate_opacity_grad != 0, probe->longest > 0, nullptr, 0u, nullptr, s)) return e;
@@ -826,8 +827,7 @@ int lvdgs_blend_forward_batch(const lvdgs_args *const *views, int32_t count, voi
         const int64_t D = a->num_gaussians == 0 ? 0 : a->num_rendered;
         if (D < 0) { set_error("negative num_rendered"); return LVDGS_E_INVALID; }
         if (int e = check_render_buffers(a, D)) return e;
-        if (a->image_width != views[0]->image_width || a->image_height != views[0]->image_height || a->tile_row_begin != views[0]->tile_row_begin ||
-            a->tile_row_end != views[0]->tile_row_end) { set_error("blend batch: the views differ in image size or band"); return LVDGS_E_INVALID; }
+        if (!one_frame(a, views[0], 0)) { set_error("blend batch: the views differ in image size or band"); return LVDGS_E_INVALID; }
         g[k] = GeomView{}; b[k] = BinView{};
         if (a->num_gaussians > 0) geom_layout(a->num_gaussians, &g[k], a->geom_state);
         bin_view(a, &b[k]);
@@ -849,10 +849,15 @@ static int masked_loss_view(const lvdgs_args *a, const lvdgs_masked_loss_args *m
 }
 
 int lvdgs_backward_masked_loss(const lvdgs_args *a, const lvdgs_masked_loss_args *loss, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
     if (!a) { set_error("backward: args is NULL"); return LVDGS_E_INVALID; }
     MaskedLossView mv;
     if (int e = masked_loss_view(a, loss, &mv)) return e;
-    return backward_impl(a, nullptr, 0, (hipStream_t)stream, nullptr, &mv);
+    BackwardViews v;
+    if (int e = check_backward(a, BackwardKind::masked_loss, &v)) return e;
+    if (v.D > 0 && !(a->flags & LVDGS_FLAG_NO_BLEND))
+        if (int e = launch_blend_bwd_masked_loss(*a, v.g, v.b, v.im, v.w, mv, s)) return e;
+    return enqueue_gaussian_backward(a, v, s);
 }
 
 int lvdgs_blend_backward_window_batch(const lvdgs_args *const *views, const lvdgs_loss_args *const *losses,
@@ -867,20 +872,13 @@ int lvdgs_blend_backward_window_batch(const lvdgs_args *const *views, const lvdg
         const lvdgs_args *a = views[k];
         const lvdgs_masked_loss_args *m = masked ? masked[k] : nullptr;
         if (!a || (!m && !(losses && losses[k]))) { set_error("blend batch: view %d is NULL or has no loss", k); return LVDGS_E_INVALID; }
-        if (a->image_width != views[0]->image_width || a->image_height != views[0]->image_height || a->tile_row_begin != views[0]->tile_row_begin ||
-            a->tile_row_end != views[0]->tile_row_end || ((a->flags ^ views[0]->flags) & LVDGS_FLAG_POSE_ONLY)) {
-            set_error("blend batch: the views differ in image size, band or LVDGS_FLAG_POSE_ONLY"); return LVDGS_E_INVALID;
-        }
-        BackwardViews v;
+        if (!one_frame(a, views[0], LVDGS_FLAG_POSE_ONLY)) { set_error("blend batch: the views differ in image size, band or LVDGS_FLAG_POSE_ONLY"); return LVDGS_E_INVALID; }
         if (m) {
             if (int e = masked_loss_view(a, m, &mv[k])) return e;
             mp[k] = &mv[k];
-            if (int e = backward_impl(a, nullptr, 0, s, &v, &mv[k])) return e;
-        } else {
-            if (int e = loss_fused_params(losses[k], &lp[k])) return e;
-            if (losses[k]->width != a->image_width || losses[k]->height != a->image_height) { set_error("fused loss: image size differs from the rasterizer's"); return LVDGS_E_INVALID; }
-            if (int e = backward_impl(a, &lp[k], propagate_opacity_grad != 0, s, &v)) return e;
-        }
+        } else if (int e = fused_loss_params(a, losses[k], &lp[k])) return e;
+        BackwardViews v;
+        if (int e = check_backward(a, m ? BackwardKind::masked_loss : BackwardKind::fused_loss, &v)) return e;
         g[k] = v.g; b[k] = v.b; im[k] = v.im; w[k] = v.w;
     }
     return launch_blend_bwd_fused_loss_batch(views, g.data(), b.data(), im.data(), w.data(), lp.data(), masked ? mp.data() : nullptr, count,
@@ -917,10 +915,8 @@ int lvdgs_gaussian_backward_batch(const lvdgs_args *const *views, int32_t count,
         if (k > 0 && !(a->flags & LVDGS_FLAG_ACCUMULATE_PARAM_GRADS)) { set_error("gaussian backward batch: view %d does not carry LVDGS_FLAG_ACCUMULATE_PARAM_GRADS (the views' gradients are summed)", k); return LVDGS_E_INVALID; }
     }
     for (int k = 0; k < count; k++) {
-        const lvdgs_args *a = views[k];
         BackwardViews v;
-        LossParams unused{};   // (the checks of a backward call whose pixel gradients came from a loss: the blend pass has run)
-        if (int e = backward_impl(a, &unused, 0, s, &v)) return e;
+        if (int e = check_backward(views[k], BackwardKind::blended, &v)) return e;
         g[k] = v.g; b[k] = v.b; w[k] = v.w;
     }
     return launch_preprocess_bwd_views(views, g.data(), w.data(), b.data(), count, s);

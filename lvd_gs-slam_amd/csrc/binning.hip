@@ -155,7 +155,7 @@ __global__ void __launch_bounds__(1024) group_colscan_batch_kernel(int T, int nc
 // arrival order -- it only decides which workgroup of a blend kernel takes which tile, never a result).
 // arrive (two-level grouping: the tile grid's and the super-tile grid's scans of one view, each with pinned words of its own): a
 // device word both workgroups count on (zero before the launch); the LATER of the two writes host_seq to seq_out, behind both
-// workgroups' words, so that the host's one wait covers both pair counts.  Null: the sequence number goes to host_out[3].
+// workgroups' words, so that the host's one wait covers both pair counts.  Null: the sequence number goes to host_out[PROBE_SEQ].
 template <int THREADS>
 __device__ __forceinline__ void group_tilescan_body(int T, const uint32_t *__restrict__ totals, uint32_t capacity,
                                                     uint2 *__restrict__ ranges, uint32_t *__restrict__ total_out,
@@ -237,9 +237,9 @@ __device__ __forceinline__ void group_tilescan_body(int T, const uint32_t *__res
         // behind a system-scope fence -- the sequence number of the call, which is what the host spins on.  (A device-to-host
         // copy enqueued behind this kernel is a blit kernel of its own: 3.6 us on every frame's critical path.)
         if (host_out) {
-            host_out[0] = s_total; host_out[1] = s_longest; host_out[2] = s_q;
+            host_out[PROBE_COUNT] = s_total; host_out[PROBE_LONGEST] = s_longest; host_out[PROBE_QUEUED] = s_q;
             __threadfence_system();
-            if (!arrive) __hip_atomic_store(host_out + 3, host_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (!arrive) __hip_atomic_store(host_out + PROBE_SEQ, host_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
             else if (__hip_atomic_fetch_add(arrive, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_SYSTEM) == 1u) {   // the second to arrive
                 __threadfence_system();
                 __hip_atomic_store(seq_out, host_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -302,14 +302,14 @@ __global__ void __launch_bounds__(1024) group_tilescan_kernel(int T, const uint3
                                                               uint32_t *host_out, uint32_t host_seq) {
     group_tilescan_body<1024>(T, totals, capacity, ranges, total_out, long_limit, queue_count, queue, tile_order, t_lo, t_hi, order_valid, host_out, host_seq);
 }
-// lvdgs_forward_batch: one workgroup per view (blockIdx.x); view k's pair count and hints go to host_out + 4 k
+// lvdgs_forward_batch: one workgroup per view (blockIdx.x); view k's pair count and hints go to host_out + PROBE_BLOCK * k
 struct TilescanView { const uint32_t *totals; uint32_t capacity; uint2 *ranges; uint32_t *total_out, *queue_count, *queue, *tile_order, *order_valid; uint32_t *arrive = nullptr; };
 struct TilescanBatch { TilescanView v[FWD_BATCH_VIEWS]; };
 __global__ void __launch_bounds__(1024) group_tilescan_batch_kernel(int T, TilescanBatch b, uint32_t long_limit, int t_lo, int t_hi, uint32_t *host_out,
                                                                     uint32_t host_seq) {
     const TilescanView &v = b.v[blockIdx.x];
     group_tilescan_body<1024>(T, v.totals, v.capacity, v.ranges, v.total_out, long_limit, v.queue_count, v.queue, v.tile_order, t_lo, t_hi, v.order_valid,
-                              host_out + 4 * blockIdx.x, host_seq);
+                              host_out + PROBE_BLOCK * blockIdx.x, host_seq);
 }
 
 // Two-level grouping: the tile grid's and the super-tile grid's scans side by side -- blockIdx.y picks the grid (column scan), blockIdx.x
@@ -326,7 +326,7 @@ struct TilescanPairView { int T; const uint32_t *totals; uint2 *ranges; uint32_t
 __global__ void __launch_bounds__(1024) group_tilescan_pair_kernel(TilescanPairView a, TilescanPairView b, uint32_t capacity, uint32_t long_limit, uint32_t *arrive) {
     const TilescanPairView &v = blockIdx.x ? b : a;
     group_tilescan_body<1024>(v.T, v.totals, capacity, v.ranges, v.total_out, long_limit, v.queue_count, v.queue, v.tile_order, v.t_lo, v.t_hi, v.order_valid,
-                              v.host_out, a.host_seq, a.host_out ? arrive : nullptr, a.host_out ? a.host_out + 3 : nullptr);
+                              v.host_out, a.host_seq, a.host_out ? arrive : nullptr, a.host_out ? a.host_out + PROBE_SEQ : nullptr);
 }
 
 // lvdgs_forward_batch with two-level grouping: both grids of every view (blockIdx.y = 2 * view + grid; blockIdx.x likewise for the range scan)
@@ -343,12 +343,12 @@ __global__ void __launch_bounds__(1024) group_tilescan_pair_batch_kernel(int T0,
                                                                          uint32_t *host_out, uint32_t host_seq, uint32_t *host_super) {
     const TilescanView &v = b.v[blockIdx.x];
     const int grid = blockIdx.x & 1, view = blockIdx.x >> 1;
-    // (the tile grid's workgroup writes the view's pair count and hints to host_out + 4 view, the super grid's its super pair count and hints
-    // to host_super + 4 view -- the first view's hints are the next call's sort launch's -- and the later of the two the sequence number the
-    // host waits for, behind host_out + 4 view)
+    // (the tile grid's workgroup writes the view's pair count and hints to the view's block of host_out, the super grid's its super pair count and
+    // hints to the view's block of host_super -- the first view's hints are the next call's sort launch's -- and the later of the two the sequence
+    // number the host waits for, into the view's block of host_out)
     group_tilescan_body<1024>(grid ? T1 : T0, v.totals, v.capacity, v.ranges, v.total_out, long_limit, v.queue_count, v.queue, v.tile_order,
-                              grid ? 0 : t_lo, grid ? T1 : t_hi, v.order_valid, host_out ? (grid ? host_super : host_out) + 4 * view : nullptr, host_seq,
-                              host_out ? v.arrive : nullptr, host_out ? host_out + 4 * view + 3 : nullptr);
+                              grid ? 0 : t_lo, grid ? T1 : t_hi, v.order_valid, host_out ? (grid ? host_super : host_out) + PROBE_BLOCK * view : nullptr, host_seq,
+                              host_out ? v.arrive : nullptr, host_out ? host_out + PROBE_BLOCK * view + PROBE_SEQ : nullptr);
 }
 
 // SLOT_SCAN (lvdgs_forward): also makes slot_base[i] = exclusive scan of tiles_touched in id order (the backward's
@@ -678,16 +678,16 @@ size_t group_hist_entries(int N, int num_tiles) { return group_chunks(N) * (size
 
 int launch_group_count(const lvdgs_args &a, const GeomView &g, const ImageView &im, const RenderScratch &w, hipStream_t s) {
     const int N = a.num_gaussians;
-    const int gx = (a.image_width + TILE - 1) / TILE, gy = (a.image_height + TILE - 1) / TILE, T = gx * gy;
-    if (N == 0 || T == 0) return LVDGS_OK;
+    const TileGrid t(a);
+    if (N == 0 || t.T == 0) return LVDGS_OK;
     const int nchunks = (int)group_chunks(N);
-    const size_t lds = (size_t)T * sizeof(uint32_t);
+    const size_t lds = (size_t)t.T * sizeof(uint32_t);
     static unsigned char done[GROUP_SHAPES][16];
     ProfScope ps("group_count", s);
     if (int e = group_dispatch(group_shape_for(N), [&](auto threads_, auto owners_, auto per_, int d) {
             constexpr int THREADS = decltype(threads_)::value, OWNERS = decltype(owners_)::value, PER = decltype(per_)::value;
             if (int e = allow_dynamic_lds(reinterpret_cast<const void *>(&count_pairs_kernel<THREADS, OWNERS, PER>), GROUP_MAX_TILES * 4, done[d])) return e;
-            hipLaunchKernelGGL((count_pairs_kernel<THREADS, OWNERS, PER>), dim3(nchunks), dim3(THREADS), lds, s, N, gx, T, (const uint4 *)g.rect, w.group_hist,
+            hipLaunchKernelGGL((count_pairs_kernel<THREADS, OWNERS, PER>), dim3(nchunks), dim3(THREADS), lds, s, N, t.gx, t.T, (const uint4 *)g.rect, w.group_hist,
                                a.n_touched, im.long_count);
             return (int)LVDGS_OK;
         })) return e;
@@ -704,69 +704,82 @@ static bool scan_rides_in_scatter(const lvdgs_args &a, int N, int T) {
     return LVDGS_SCAN_IN_SCATTER != 0 && (threads == 512 || threads == 1024) && cdiv(T, threads) <= SCAN_IN_SCATTER_RUN;
 }
 
-int launch_group_scan(const lvdgs_args &a, const ImageView &im, const RenderScratch &w, int64_t capacity, uint32_t *total_out, hipStream_t s,
-                      uint32_t *host_out, uint32_t host_seq) {
-    const int N = a.num_gaussians;
-    const int gx = (a.image_width + TILE - 1) / TILE, gy = (a.image_height + TILE - 1) / TILE, T = gx * gy;
-    if (N == 0 || T == 0) return LVDGS_OK;
-    const int nchunks = (int)group_chunks(N);
+// launch(R): the column scan's build for nchunks matrix rows -- as many waves per workgroup as leave every wave at most 16 (then 32) rows to hold in registers
+template <typename F>
+static void colscan_dispatch(int nchunks, F &&launch) {
+    if (nchunks <= 8 * 16) launch(template_int<8>{});
+    else if (nchunks <= 16 * 16) launch(template_int<16>{});
+    else if (nchunks <= 32 * 16) launch(template_int<32>{});
+    else launch(template_int<0>{});
+}
+
+// The tile scan's arguments for a call's tile grid (the rows of its band) and for its super-tile grid
+static TileScanArgs tile_grid_scan(const lvdgs_args &a, const TileGrid &t, const ImageView &im, uint32_t *total_out, uint32_t *host_out, uint32_t host_seq) {
     int row0, row1;
     tile_row_band(a, &row0, &row1);
+    return TileScanArgs{im.ranges, total_out, (uint32_t)tile_sort_wave_limit(), im.long_count, im.long_tiles, tile_order_in_use(t.T) ? im.long_tiles + t.T : nullptr,
+                        row0 * t.gx, row1 * t.gx, im.long_count + 1, host_out, host_seq};
+}
+static TileScanArgs super_grid_scan(const TileGrid &t, const SuperView &sv, uint32_t *total_out, uint32_t *host_out) {
+    return TileScanArgs{sv.ranges, total_out, (uint32_t)tile_sort_wave_limit(), sv.long_count, sv.long_tiles, tile_order_in_use(t.Ts) ? sv.long_tiles + t.Ts : nullptr,
+                        0, t.Ts, sv.long_count + 1, host_out, 0u};
+}
+static TilescanPairView pair_view(int T, const uint32_t *totals, const TileScanArgs &ts) {
+    return TilescanPairView{T, totals, ts.ranges, ts.total_out, ts.queue_count, ts.queue, ts.tile_order, ts.t_lo, ts.t_hi, ts.order_valid, ts.host_out, ts.host_seq};
+}
+
+int launch_group_scan(const lvdgs_args &a, const ImageView &im, const RenderScratch &w, int64_t capacity, uint32_t *total_out, PairReport report, hipStream_t s) {
+    const int N = a.num_gaussians;
+    const TileGrid t(a);
+    if (N == 0 || t.T == 0) return LVDGS_OK;
+    const int nchunks = (int)group_chunks(N);
     ProfScope ps("group_scan", s);
-    // waves per workgroup: as many as leave every wave at most 16 (then 32) matrix rows to hold in registers
-    const int wg_tiles = cdiv(T, COLSCAN_TILES);
+    const int wg_tiles = cdiv(t.T, COLSCAN_TILES);
+    const TileScanArgs ts = tile_grid_scan(a, t, im, total_out, report.words ? report.words + PROBE_CALL : nullptr, report.seq);
     if (super_tiles_in_use(a)) {
         // two-level grouping: the super-tile grid's count matrix (launch_super_count has run) is scanned in the same two launches
         const SuperView &sv = w.super;
-        const int Ts = super_tiles_of(a.image_width, a.image_height);
-        const dim3 grid(wg_tiles, 2);
-        if (nchunks <= 8 * 16) hipLaunchKernelGGL(group_colscan_pair_kernel<8>, grid, dim3(1024), 0, s, T, Ts, nchunks, w.group_hist, w.group_totals, sv.hist, sv.totals);
-        else if (nchunks <= 16 * 16) hipLaunchKernelGGL(group_colscan_pair_kernel<16>, grid, dim3(1024), 0, s, T, Ts, nchunks, w.group_hist, w.group_totals, sv.hist, sv.totals);
-        else if (nchunks <= 32 * 16) hipLaunchKernelGGL(group_colscan_pair_kernel<32>, grid, dim3(1024), 0, s, T, Ts, nchunks, w.group_hist, w.group_totals, sv.hist, sv.totals);
-        else hipLaunchKernelGGL(group_colscan_pair_kernel<0>, grid, dim3(1024), 0, s, T, Ts, nchunks, w.group_hist, w.group_totals, sv.hist, sv.totals);
-        // (the super grid's pair count and hints -- longest queued list, queue length -- go to the pinned words behind the call's own four;
+        colscan_dispatch(nchunks, [&](auto R) {
+            hipLaunchKernelGGL(group_colscan_pair_kernel<decltype(R)::value>, dim3(wg_tiles, 2), dim3(1024), 0, s, t.T, t.Ts, nchunks, w.group_hist, w.group_totals, sv.hist, sv.totals);
+        });
+        // (the super grid's pair count and hints -- longest queued list, queue length -- go to the pinned block of the call's super lists;
         // the later of the two workgroups writes the sequence number the host waits for: the host's verdict takes both pair counts)
-        const TilescanPairView tv{T, w.group_totals, im.ranges, total_out, im.long_count, im.long_tiles, tile_order_in_use(T) ? im.long_tiles + T : nullptr,
-                                  row0 * gx, row1 * gx, im.long_count + 1, host_out, host_seq};
-        const TilescanPairView sv2{Ts, sv.totals, sv.ranges, total_out ? total_out + SUPER_TOTAL_WORD : sv.total, sv.long_count, sv.long_tiles, tile_order_in_use(Ts) ? sv.long_tiles + Ts : nullptr,
-                                   0, Ts, sv.long_count + 1, host_out ? host_out + 8 : nullptr, 0u};
-        hipLaunchKernelGGL(group_tilescan_pair_kernel, dim3(2), dim3(1024), 0, s, tv, sv2, (uint32_t)capacity, (uint32_t)tile_sort_wave_limit(),
-                           sv.long_count + SUPER_ARRIVE_WORD);
+        const TileScanArgs ss = super_grid_scan(t, sv, total_out ? total_out + SUPER_TOTAL_WORD : sv.total, report.words ? report.words + PROBE_CALL_SUPER : nullptr);
+        hipLaunchKernelGGL(group_tilescan_pair_kernel, dim3(2), dim3(1024), 0, s, pair_view(t.T, w.group_totals, ts), pair_view(t.Ts, sv.totals, ss), (uint32_t)capacity,
+                           ts.long_limit, sv.long_count + SUPER_ARRIVE_WORD);
         LVDGS_LAUNCH_CHECK("group_scan (two-level)", a.debug, s);
         return LVDGS_OK;
     }
-    if (nchunks <= 8 * 16) hipLaunchKernelGGL(group_colscan_kernel<8>, dim3(wg_tiles), dim3(1024), 0, s, T, nchunks, w.group_hist, w.group_totals);
-    else if (nchunks <= 16 * 16) hipLaunchKernelGGL(group_colscan_kernel<16>, dim3(wg_tiles), dim3(1024), 0, s, T, nchunks, w.group_hist, w.group_totals);
-    else if (nchunks <= 32 * 16) hipLaunchKernelGGL(group_colscan_kernel<32>, dim3(wg_tiles), dim3(1024), 0, s, T, nchunks, w.group_hist, w.group_totals);
-    else hipLaunchKernelGGL(group_colscan_kernel<0>, dim3(wg_tiles), dim3(1024), 0, s, T, nchunks, w.group_hist, w.group_totals);
-    if (!scan_rides_in_scatter(a, N, T))   // (else: launch_group_scatter's last workgroup)
-        hipLaunchKernelGGL(group_tilescan_kernel, dim3(1), dim3(1024), 0, s, T, (const uint32_t *)w.group_totals, (uint32_t)capacity, im.ranges,
-                           total_out, (uint32_t)tile_sort_wave_limit(), im.long_count, im.long_tiles,
-                           tile_order_in_use(T) ? im.long_tiles + T : nullptr, row0 * gx, row1 * gx, im.long_count + 1, host_out, host_seq);
+    colscan_dispatch(nchunks, [&](auto R) {
+        hipLaunchKernelGGL(group_colscan_kernel<decltype(R)::value>, dim3(wg_tiles), dim3(1024), 0, s, t.T, nchunks, w.group_hist, w.group_totals);
+    });
+    if (!scan_rides_in_scatter(a, N, t.T))   // (else: launch_group_scatter's last workgroup)
+        hipLaunchKernelGGL(group_tilescan_kernel, dim3(1), dim3(1024), 0, s, t.T, (const uint32_t *)w.group_totals, (uint32_t)capacity, ts.ranges, ts.total_out, ts.long_limit,
+                           ts.queue_count, ts.queue, ts.tile_order, ts.t_lo, ts.t_hi, ts.order_valid, ts.host_out, ts.host_seq);
     LVDGS_LAUNCH_CHECK("group_scan", a.debug, s);
     return LVDGS_OK;
 }
 
 int launch_group_scatter(const lvdgs_args &a, const GeomView &g, const ImageView &im, const RenderScratch &w, unsigned long long *keys64,
-                         int64_t capacity, bool slot_scan, uint8_t *pair_valid, hipStream_t s, uint32_t *total_out, uint32_t *host_out, uint32_t host_seq) {
+                         int64_t capacity, bool slot_scan, uint8_t *pair_valid, uint32_t *total_out, PairReport report, hipStream_t s) {
     const int N = a.num_gaussians;
-    const int gx = (a.image_width + TILE - 1) / TILE, gy = (a.image_height + TILE - 1) / TILE, T = gx * gy;
-    if (N == 0 || T == 0) return LVDGS_OK;
+    const TileGrid t(a);
+    if (N == 0 || t.T == 0) return LVDGS_OK;
     const int nchunks = (int)group_chunks(N);
+    const bool super = super_tiles_in_use(a);   // two-level grouping: the same kernel on the super-tile grid (its rectangles, counts and ranges)
+    const SuperView &sv = w.super;
+    const int gx = super ? t.gxs : t.gx, T = super ? t.Ts : t.T;
     const size_t lds = (size_t)T * sizeof(uint32_t);
     static unsigned char done[4 * GROUP_SHAPES][16];
-    ProfScope ps("group_scatter", s);
+    ProfScope ps(super ? "super_scatter" : "group_scatter", s);
     TileScanArgs ts{};
-    if (scan_rides_in_scatter(a, N, T)) {   // the tile scan as this launch's last workgroup (launch_group_scan has made the tile totals)
-        int row0, row1;
-        tile_row_band(a, &row0, &row1);
-        ts = TileScanArgs{im.ranges, total_out, (uint32_t)tile_sort_wave_limit(), im.long_count, im.long_tiles, tile_order_in_use(T) ? im.long_tiles + T : nullptr,
-                          row0 * gx, row1 * gx, im.long_count + 1, host_out, host_seq};
-    }
+    if (scan_rides_in_scatter(a, N, t.T))   // the tile scan as this launch's last workgroup (launch_group_scan has made the tile totals)
+        ts = tile_grid_scan(a, t, im, total_out, report.words ? report.words + PROBE_CALL : nullptr, report.seq);
     auto launch = [&](auto kernel, int d, int threads) {
         if (int e = allow_dynamic_lds(reinterpret_cast<const void *>(kernel), GROUP_MAX_TILES * 4, done[d])) return e;
-        hipLaunchKernelGGL(kernel, dim3(nchunks + (ts.ranges ? 1 : 0)), dim3(threads), lds, s, N, gx, T, (const uint4 *)g.rect, (const uint32_t *)w.group_hist,
-                           (const uint2 *)im.ranges, ts.ranges ? (const uint32_t *)w.group_totals : nullptr, (uint32_t)capacity, (const uint32_t *)g.depth_bits, keys64,
+        hipLaunchKernelGGL(kernel, dim3(nchunks + (ts.ranges ? 1 : 0)), dim3(threads), lds, s, N, gx, T, (const uint4 *)(super ? sv.rect : g.rect),
+                           (const uint32_t *)(super ? sv.hist : w.group_hist), (const uint2 *)(super ? sv.ranges : im.ranges),
+                           ts.ranges ? (const uint32_t *)w.group_totals : nullptr, (uint32_t)capacity, (const uint32_t *)g.depth_bits, keys64,
                            (const uint32_t *)g.tiles_touched, (const uint32_t *)w.chunk_sums, g.slot_base, pair_valid, ts);
         return (int)LVDGS_OK;
     };
@@ -776,32 +789,31 @@ int launch_group_scatter(const lvdgs_args &a, const GeomView &g, const ImageView
                 return slot_scan ? launch(&scatter_pairs_kernel<THREADS, OWNERS, PER, true, true>, 4 * d, THREADS) : launch(&scatter_pairs_kernel<THREADS, OWNERS, PER, false, true>, 4 * d + 1, THREADS);
             return slot_scan ? launch(&scatter_pairs_kernel<THREADS, OWNERS, PER, true, false>, 4 * d + 2, THREADS) : launch(&scatter_pairs_kernel<THREADS, OWNERS, PER, false, false>, 4 * d + 3, THREADS);
         })) return e;
-    LVDGS_LAUNCH_CHECK("group_scatter", a.debug, s);
+    LVDGS_LAUNCH_CHECK(super ? "super_scatter" : "group_scatter", a.debug, s);
     return LVDGS_OK;
 }
 
-// ---- two-level grouping: count_super -> scans -> scatter on the super grid (the tile sort and the expansion: api.hip calls them) ----
+// ---- two-level grouping: count_super -> launch_group_scan and _scatter, which take the super grid (the tile sort and the expansion: api.hip calls them) ----
 bool super_tiles_in_use(const lvdgs_args &a) {
     if (!(a.flags & LVDGS_FLAG_SUPER_TILES) || (a.flags & LVDGS_FLAG_LIST_ALL_TILES)) return false;
     if (a.tile_row_begin != 0 || a.tile_row_end != 0) return false;   // (bands: a super-tile would straddle the band's edge)
-    const int gx = (a.image_width + TILE - 1) / TILE, gy = (a.image_height + TILE - 1) / TILE;
-    return a.num_gaussians > 0 && gx * gy <= GROUP_MAX_TILES && gx * gy >= 4 * SUPER * SUPER;
+    const TileGrid t(a);
+    return a.num_gaussians > 0 && t.T <= GROUP_MAX_TILES && t.T >= 4 * SUPER * SUPER;
 }
-int super_tiles_of(int W, int H) { return cdiv(cdiv(W, TILE), SUPER) * cdiv(cdiv(H, TILE), SUPER); }
+int super_tiles_of(int W, int H) { return TileGrid(W, H).Ts; }
 
 int launch_super_count(const lvdgs_args &a, const GeomView &g, const SuperView &sv, hipStream_t s) {
     const int N = a.num_gaussians;
-    const int gx = (a.image_width + TILE - 1) / TILE, gy = (a.image_height + TILE - 1) / TILE;
-    const int gxs = cdiv(gx, SUPER), Ts = gxs * cdiv(gy, SUPER);
-    if (N == 0 || Ts == 0) return LVDGS_OK;
+    const TileGrid t(a);
+    if (N == 0 || t.Ts == 0) return LVDGS_OK;
     const int nchunks = (int)group_chunks(N);
-    const size_t lds = (size_t)Ts * sizeof(uint32_t);
+    const size_t lds = (size_t)t.Ts * sizeof(uint32_t);
     static unsigned char done[GROUP_SHAPES][16];
     ProfScope ps("super_count", s);
     if (int e = group_dispatch(group_shape_for(N), [&](auto threads_, auto owners_, auto per_, int d) {
             constexpr int THREADS = decltype(threads_)::value, OWNERS = decltype(owners_)::value, PER = decltype(per_)::value;
             if (int e = allow_dynamic_lds(reinterpret_cast<const void *>(&count_super_kernel<THREADS, OWNERS, PER>), GROUP_MAX_TILES * 4, done[d])) return e;
-            hipLaunchKernelGGL((count_super_kernel<THREADS, OWNERS, PER>), dim3(nchunks), dim3(THREADS), lds, s, N, gxs, Ts, (const uint4 *)g.rect, sv.rect, sv.hist,
+            hipLaunchKernelGGL((count_super_kernel<THREADS, OWNERS, PER>), dim3(nchunks), dim3(THREADS), lds, s, N, t.gxs, t.Ts, (const uint4 *)g.rect, sv.rect, sv.hist,
                                sv.long_count);
             return (int)LVDGS_OK;
         })) return e;
@@ -809,92 +821,68 @@ int launch_super_count(const lvdgs_args &a, const GeomView &g, const SuperView &
     return LVDGS_OK;
 }
 
-int launch_super_scatter(const lvdgs_args &a, const GeomView &g, const SuperView &sv, const RenderScratch &w, unsigned long long *keys64, int64_t capacity,
-                         bool slot_scan, uint8_t *pair_valid, hipStream_t s) {
-    const int N = a.num_gaussians;
-    const int gx = (a.image_width + TILE - 1) / TILE, gy = (a.image_height + TILE - 1) / TILE;
-    const int gxs = cdiv(gx, SUPER), Ts = gxs * cdiv(gy, SUPER);
-    if (N == 0 || Ts == 0) return LVDGS_OK;
-    const int nchunks = (int)group_chunks(N);
-    const size_t lds = (size_t)Ts * sizeof(uint32_t);
-    static unsigned char done[2 * GROUP_SHAPES][16];
-    ProfScope ps("super_scatter", s);
-    TileScanArgs ts{};
-    auto launch = [&](auto kernel, int d, int threads) {
-        if (int e = allow_dynamic_lds(reinterpret_cast<const void *>(kernel), GROUP_MAX_TILES * 4, done[d])) return e;
-        hipLaunchKernelGGL(kernel, dim3(nchunks), dim3(threads), lds, s, N, gxs, Ts, (const uint4 *)sv.rect, (const uint32_t *)sv.hist, (const uint2 *)sv.ranges,
-                           (const uint32_t *)nullptr, (uint32_t)capacity, (const uint32_t *)g.depth_bits, keys64, (const uint32_t *)g.tiles_touched,
-                           (const uint32_t *)w.chunk_sums, g.slot_base, pair_valid, ts);
-        return (int)LVDGS_OK;
-    };
-    if (int e = group_dispatch(group_shape_for(N), [&](auto threads_, auto owners_, auto per_, int d) {
-            constexpr int THREADS = decltype(threads_)::value, OWNERS = decltype(owners_)::value, PER = decltype(per_)::value;
-            return slot_scan ? launch(&scatter_pairs_kernel<THREADS, OWNERS, PER, true, false>, 2 * d, THREADS)
-                             : launch(&scatter_pairs_kernel<THREADS, OWNERS, PER, false, false>, 2 * d + 1, THREADS);
-        })) return e;
-    LVDGS_LAUNCH_CHECK("super_scatter", a.debug, s);
-    return LVDGS_OK;
-}
-
 int launch_super_expand(const lvdgs_args &a, const GeomView &g, const SuperView &sv, const ImageView &im, const uint32_t *super_list, uint32_t *point_list,
                         hipStream_t s) {
-    const int gx = (a.image_width + TILE - 1) / TILE, gy = (a.image_height + TILE - 1) / TILE;
-    const int gxs = cdiv(gx, SUPER), Ts = gxs * cdiv(gy, SUPER);
-    if (a.num_gaussians == 0 || Ts == 0) return LVDGS_OK;
+    const TileGrid t(a);
+    if (a.num_gaussians == 0 || t.Ts == 0) return LVDGS_OK;
     ProfScope ps("super_expand", s);
-    hipLaunchKernelGGL(expand_super_kernel, dim3(Ts), dim3(64 * SUPER * SUPER), 0, s, gx, gy, gxs, (const uint2 *)sv.ranges, super_list, (const uint4 *)g.rect,
+    hipLaunchKernelGGL(expand_super_kernel, dim3(t.Ts), dim3(64 * SUPER * SUPER), 0, s, t.gx, t.gy, t.gxs, (const uint2 *)sv.ranges, super_list, (const uint4 *)g.rect,
                        (const uint2 *)im.ranges, point_list);
     LVDGS_LAUNCH_CHECK("super_expand", a.debug, s);
     return LVDGS_OK;
 }
 
 // ---- lvdgs_forward_batch: the same stages for n views of one map and one image size, one launch each ----
+// a view's tile scans as the batched kernels take them (arrive: two-level grouping -- the word the view's two scans count on)
+static TilescanView tile_grid_scan_view(const TileGrid &t, const GeomView &g, const ImageView &im, const RenderScratch &w, int64_t cap, uint32_t *arrive) {
+    return TilescanView{w.group_totals, (uint32_t)cap, im.ranges, g.total, im.long_count, im.long_tiles, tile_order_in_use(t.T) ? im.long_tiles + t.T : nullptr,
+                        im.long_count + 1, arrive};
+}
+static TilescanView super_grid_scan_view(const TileGrid &t, const GeomView &g, const SuperView &sv, int64_t cap) {
+    return TilescanView{sv.totals, (uint32_t)cap, sv.ranges, g.total + SUPER_TOTAL_WORD, sv.long_count, sv.long_tiles, tile_order_in_use(t.Ts) ? sv.long_tiles + t.Ts : nullptr,
+                        sv.long_count + 1, sv.long_count + SUPER_ARRIVE_WORD};
+}
+
 int launch_group_scan_batch(const lvdgs_args *const *a, const GeomView *g, const ImageView *im, const RenderScratch *w, const int64_t *caps, int n,
-                            uint32_t *host_words, uint32_t host_seq, uint32_t *host_super, hipStream_t s) {
+                            PairReport report, hipStream_t s) {
     const int N = a[0]->num_gaussians;
-    const int gx = (a[0]->image_width + TILE - 1) / TILE, gy = (a[0]->image_height + TILE - 1) / TILE, T = gx * gy;
-    if (N == 0 || T == 0 || n == 0) return LVDGS_OK;
+    const TileGrid t(*a[0]);
+    if (N == 0 || t.T == 0 || n == 0) return LVDGS_OK;
     const int nchunks = (int)group_chunks(N);
     int row0, row1;
     tile_row_band(*a[0], &row0, &row1);
-    ColscanBatch cb{};
-    TilescanBatch tb{};
-    for (int k = 0; k < n; k++) {
-        cb.hist[k] = w[k].group_hist; cb.totals[k] = w[k].group_totals;
-        tb.v[k] = TilescanView{w[k].group_totals, (uint32_t)caps[k], im[k].ranges, g[k].total, im[k].long_count, im[k].long_tiles,
-                               tile_order_in_use(T) ? im[k].long_tiles + T : nullptr, im[k].long_count + 1};
-    }
+    const uint32_t long_limit = (uint32_t)tile_sort_wave_limit();
+    uint32_t *host_words = report.words ? report.words + PROBE_BATCH : nullptr;
     ProfScope ps("group_scan", s);
     if (super_tiles_in_use(*a[0])) {
         // two-level grouping: the tile grid's and the super-tile grid's count matrices of every view in the same two launches
-        const int Ts = super_tiles_of(a[0]->image_width, a[0]->image_height);
         ColscanPairBatch cpb{};
         TilescanPairBatch tpb{};
         for (int k = 0; k < n; k++) {
             const SuperView &sv = w[k].super;
             cpb.hist[2 * k] = w[k].group_hist; cpb.totals[2 * k] = w[k].group_totals;
             cpb.hist[2 * k + 1] = sv.hist; cpb.totals[2 * k + 1] = sv.totals;
-            tpb.v[2 * k] = TilescanView{w[k].group_totals, (uint32_t)caps[k], im[k].ranges, g[k].total, im[k].long_count, im[k].long_tiles,
-                                        tile_order_in_use(T) ? im[k].long_tiles + T : nullptr, im[k].long_count + 1, sv.long_count + SUPER_ARRIVE_WORD};
-            tpb.v[2 * k + 1] = TilescanView{sv.totals, (uint32_t)caps[k], sv.ranges, g[k].total + SUPER_TOTAL_WORD, sv.long_count, sv.long_tiles,
-                                            tile_order_in_use(Ts) ? sv.long_tiles + Ts : nullptr, sv.long_count + 1, sv.long_count + SUPER_ARRIVE_WORD};
+            tpb.v[2 * k] = tile_grid_scan_view(t, g[k], im[k], w[k], caps[k], sv.long_count + SUPER_ARRIVE_WORD);
+            tpb.v[2 * k + 1] = super_grid_scan_view(t, g[k], sv, caps[k]);
         }
-        const dim3 grid2(cdiv(T, COLSCAN_TILES), 2 * n);
-        if (nchunks <= 8 * 16) hipLaunchKernelGGL(group_colscan_pair_batch_kernel<8>, grid2, dim3(1024), 0, s, T, Ts, nchunks, cpb);
-        else if (nchunks <= 16 * 16) hipLaunchKernelGGL(group_colscan_pair_batch_kernel<16>, grid2, dim3(1024), 0, s, T, Ts, nchunks, cpb);
-        else if (nchunks <= 32 * 16) hipLaunchKernelGGL(group_colscan_pair_batch_kernel<32>, grid2, dim3(1024), 0, s, T, Ts, nchunks, cpb);
-        else hipLaunchKernelGGL(group_colscan_pair_batch_kernel<0>, grid2, dim3(1024), 0, s, T, Ts, nchunks, cpb);
-        hipLaunchKernelGGL(group_tilescan_pair_batch_kernel, dim3(2 * n), dim3(1024), 0, s, T, Ts, tpb, (uint32_t)tile_sort_wave_limit(), row0 * gx, row1 * gx, host_words,
-                           host_seq, host_super);
+        colscan_dispatch(nchunks, [&](auto R) {
+            hipLaunchKernelGGL(group_colscan_pair_batch_kernel<decltype(R)::value>, dim3(cdiv(t.T, COLSCAN_TILES), 2 * n), dim3(1024), 0, s, t.T, t.Ts, nchunks, cpb);
+        });
+        hipLaunchKernelGGL(group_tilescan_pair_batch_kernel, dim3(2 * n), dim3(1024), 0, s, t.T, t.Ts, tpb, long_limit, row0 * t.gx, row1 * t.gx, host_words, report.seq,
+                           report.words ? report.words + PROBE_BATCH_SUPER : nullptr);
         LVDGS_LAUNCH_CHECK("group_scan (batch, two-level)", a[0]->debug, s);
         return LVDGS_OK;
     }
-    const dim3 grid(cdiv(T, COLSCAN_TILES), n);
-    if (nchunks <= 8 * 16) hipLaunchKernelGGL(group_colscan_batch_kernel<8>, grid, dim3(1024), 0, s, T, nchunks, cb);
-    else if (nchunks <= 16 * 16) hipLaunchKernelGGL(group_colscan_batch_kernel<16>, grid, dim3(1024), 0, s, T, nchunks, cb);
-    else if (nchunks <= 32 * 16) hipLaunchKernelGGL(group_colscan_batch_kernel<32>, grid, dim3(1024), 0, s, T, nchunks, cb);
-    else hipLaunchKernelGGL(group_colscan_batch_kernel<0>, grid, dim3(1024), 0, s, T, nchunks, cb);
-    hipLaunchKernelGGL(group_tilescan_batch_kernel, dim3(n), dim3(1024), 0, s, T, tb, (uint32_t)tile_sort_wave_limit(), row0 * gx, row1 * gx, host_words, host_seq);
+    ColscanBatch cb{};
+    TilescanBatch tb{};
+    for (int k = 0; k < n; k++) {
+        cb.hist[k] = w[k].group_hist; cb.totals[k] = w[k].group_totals;
+        tb.v[k] = tile_grid_scan_view(t, g[k], im[k], w[k], caps[k], nullptr);
+    }
+    colscan_dispatch(nchunks, [&](auto R) {
+        hipLaunchKernelGGL(group_colscan_batch_kernel<decltype(R)::value>, dim3(cdiv(t.T, COLSCAN_TILES), n), dim3(1024), 0, s, t.T, nchunks, cb);
+    });
+    hipLaunchKernelGGL(group_tilescan_batch_kernel, dim3(n), dim3(1024), 0, s, t.T, tb, long_limit, row0 * t.gx, row1 * t.gx, host_words, report.seq);
     LVDGS_LAUNCH_CHECK("group_scan (batch)", a[0]->debug, s);
     return LVDGS_OK;
 }
@@ -902,25 +890,24 @@ int launch_group_scan_batch(const lvdgs_args *const *a, const GeomView *g, const
 int launch_group_scatter_batch(const lvdgs_args *const *a, const GeomView *g, const ImageView *im, const RenderScratch *w, const BinView *b,
                                const int64_t *caps, int n, hipStream_t s) {
     const int N = a[0]->num_gaussians;
-    const int gx = (a[0]->image_width + TILE - 1) / TILE, gy = (a[0]->image_height + TILE - 1) / TILE, T = gx * gy;
-    if (N == 0 || T == 0 || n == 0) return LVDGS_OK;
+    const TileGrid t(*a[0]);
+    if (N == 0 || t.T == 0 || n == 0) return LVDGS_OK;
     const int nchunks = (int)group_chunks(N);
     const bool super = super_tiles_in_use(*a[0]);   // two-level grouping: the same kernel on the super-tile grid (its rectangles, counts and ranges)
-    const int gxs = cdiv(gx, SUPER), Ts = gxs * cdiv(gy, SUPER);
-    const size_t lds = (size_t)(super ? Ts : T) * sizeof(uint32_t);
+    const int gx = super ? t.gxs : t.gx, T = super ? t.Ts : t.T;
+    const size_t lds = (size_t)T * sizeof(uint32_t);
     ScatterBatch sb{};
-    for (int k = 0; k < n; k++)
-        sb.v[k] = super ? ScatterView{(const uint4 *)w[k].super.rect, w[k].super.hist, w[k].super.ranges, (uint32_t)caps[k], g[k].depth_bits, (unsigned long long *)w[k].keys,
-                                      g[k].tiles_touched, w[k].chunk_sums, g[k].slot_base, b[k].pair_valid}
-                        : ScatterView{(const uint4 *)g[k].rect, w[k].group_hist, im[k].ranges, (uint32_t)caps[k], g[k].depth_bits, (unsigned long long *)w[k].keys,
-                                      g[k].tiles_touched, w[k].chunk_sums, g[k].slot_base, b[k].pair_valid};
+    for (int k = 0; k < n; k++) {
+        const SuperView &sv = w[k].super;
+        sb.v[k] = ScatterView{(const uint4 *)(super ? sv.rect : g[k].rect), super ? sv.hist : w[k].group_hist, super ? sv.ranges : im[k].ranges, (uint32_t)caps[k],
+                              g[k].depth_bits, (unsigned long long *)w[k].keys, g[k].tiles_touched, w[k].chunk_sums, g[k].slot_base, b[k].pair_valid};
+    }
     static unsigned char done[GROUP_SHAPES][16];
     ProfScope ps(super ? "super_scatter" : "group_scatter", s);
     if (int e = group_dispatch(group_shape_for(N), [&](auto threads_, auto owners_, auto per_, int d) {
             constexpr int THREADS = decltype(threads_)::value, OWNERS = decltype(owners_)::value, PER = decltype(per_)::value;
             if (int e = allow_dynamic_lds(reinterpret_cast<const void *>(&scatter_pairs_batch_kernel<THREADS, OWNERS, PER>), GROUP_MAX_TILES * 4, done[d])) return e;
-            hipLaunchKernelGGL((scatter_pairs_batch_kernel<THREADS, OWNERS, PER>), dim3((nchunks + 7) & ~7, n), dim3(THREADS), lds, s, N, super ? gxs : gx, super ? Ts : T,
-                               nchunks, sb);
+            hipLaunchKernelGGL((scatter_pairs_batch_kernel<THREADS, OWNERS, PER>), dim3((nchunks + 7) & ~7, n), dim3(THREADS), lds, s, N, gx, T, nchunks, sb);
             return (int)LVDGS_OK;
         })) return e;
     LVDGS_LAUNCH_CHECK("group_scatter (batch)", a[0]->debug, s);
@@ -928,13 +915,12 @@ int launch_group_scatter_batch(const lvdgs_args *const *a, const GeomView *g, co
 }
 
 int launch_super_expand_batch(const lvdgs_args *const *a, const GeomView *g, const ImageView *im, const RenderScratch *w, const BinView *b, int n, hipStream_t s) {
-    const int gx = (a[0]->image_width + TILE - 1) / TILE, gy = (a[0]->image_height + TILE - 1) / TILE;
-    const int gxs = cdiv(gx, SUPER), Ts = gxs * cdiv(gy, SUPER);
-    if (a[0]->num_gaussians == 0 || Ts == 0 || n == 0) return LVDGS_OK;
+    const TileGrid t(*a[0]);
+    if (a[0]->num_gaussians == 0 || t.Ts == 0 || n == 0) return LVDGS_OK;
     ExpandBatch eb{};
     for (int k = 0; k < n; k++) eb.v[k] = ExpandView{(const uint2 *)w[k].super.ranges, b[k].tile_keys, (const uint4 *)g[k].rect, (const uint2 *)im[k].ranges, b[k].point_list};
     ProfScope ps("super_expand", s);
-    hipLaunchKernelGGL(expand_super_batch_kernel, dim3(Ts, n), dim3(64 * SUPER * SUPER), 0, s, gx, gy, gxs, eb);
+    hipLaunchKernelGGL(expand_super_batch_kernel, dim3(t.Ts, n), dim3(64 * SUPER * SUPER), 0, s, t.gx, t.gy, t.gxs, eb);
     LVDGS_LAUNCH_CHECK("super_expand (batch)", a[0]->debug, s);
     return LVDGS_OK;
 }
@@ -942,9 +928,8 @@ int launch_super_expand_batch(const lvdgs_args *const *a, const GeomView *g, con
 int launch_emit_pairs(const lvdgs_args &a, const GeomView &g, uint32_t *tile_keys, uint32_t *ids, int64_t capacity, hipStream_t s) {
     const int N = a.num_gaussians;
     if (N == 0) return LVDGS_OK;
-    const int gx = (a.image_width + TILE - 1) / TILE;
     ProfScope ps("emit_pairs", s);
-    hipLaunchKernelGGL(emit_pairs_kernel, dim3(cdiv(N, 256)), dim3(256), 0, s, N, gx, g.slot_base, g.tiles_touched,
+    hipLaunchKernelGGL(emit_pairs_kernel, dim3(cdiv(N, 256)), dim3(256), 0, s, N, TileGrid(a).gx, g.slot_base, g.tiles_touched,
                        (const uint4 *)g.rect, tile_keys, ids, (uint32_t)capacity);
     LVDGS_LAUNCH_CHECK("emit_pairs", a.debug, s);
     return LVDGS_OK;

@@ -202,6 +202,12 @@ constexpr int SUPER = 4;
 constexpr int SUPER_ARRIVE_WORD = 8;   // of SuperView::long_count (cleared with the queue by the super count's first workgroup)
 constexpr int SUPER_TOTAL_WORD = 4;    // of GeomView::total: where a call that counts on the device has the super lists' pair count (and hints) left,
                                        // behind the tile lists' -- outside the scratch, which the backward's pair records share
+// the tile grid of a frame and its grid of super-tiles
+struct TileGrid {
+    int gx, gy, T, gxs, Ts;
+    TileGrid(int W, int H) : gx(cdiv(W, TILE)), gy(cdiv(H, TILE)), T(gx * gy), gxs(cdiv(gx, SUPER)), Ts(gxs * cdiv(gy, SUPER)) {}
+    explicit TileGrid(const lvdgs_args &a) : TileGrid(a.image_width, a.image_height) {}
+};
 struct SuperView {
     uint4 *rect;           // N: a Gaussian's rectangle in super-tile units + which of them hold a listed tile
     uint32_t *hist;        // [Gaussian chunk][super-tile]
@@ -266,7 +272,6 @@ int radix_sort_pairs(uint32_t *keys_a, uint32_t *vals_a, uint32_t *keys_b, uint3
 int radix_num_passes(int total_bits);
 size_t radix_hist_entries(int64_t n);
 
-// slot_base[i] = exclusive scan over i of tiles_touched[i]; *total_dev = the sum (pair count D)
 bool tile_order_in_use(int num_tiles);   // api.hip: the blend kernels take their tiles from ImageView::long_tiles + T
 
 // Pieces lvdgs_tracking_tail (pose.hip) puts into one launch.
@@ -279,6 +284,7 @@ int loss_fused_params(const lvdgs_loss_args *a, LossParams *out);   // for the b
 int launch_blend_bwd_fused_loss(const lvdgs_args &a, const GeomView &g, const BinView &b, const ImageView &im, const BwdScratch &w,
                                 const LossParams &loss, int propagate_opacity, hipStream_t s);
 
+// slot_base[i] = exclusive scan over i of tiles_touched[i]; *total_dev = the sum (pair count D)
 int launch_slot_scan(const uint32_t *tiles_touched, uint32_t *slot_base, uint32_t *blocksums, uint32_t *total_dev, int N, int dbg,
                      hipStream_t s);
 
@@ -291,34 +297,42 @@ size_t group_chunks(int N);
 // lvdgs_forward: projection + per-chunk tile counts in one kernel (preprocess.hip); the two-call API projects in
 // lvdgs_forward_prepare and counts with launch_group_count.
 int launch_preprocess_count(const lvdgs_args &a, const GeomView &g, const ImageView &im, const RenderScratch &w, hipStream_t s);
+
+// ---- the pinned words in which the tile scans of a forward call report to the host (api.hip: PairProbe owns them) ----
+// One block of PROBE_BLOCK words per pair list: its pair count, its longest queued segment (0: none), the length of that queue and -- tile
+// lists only -- the sequence number of the call that wrote them, which is what the host waits for.  (Two-level grouping,
+// LVDGS_FLAG_SUPER_TILES: the super lists' block has no sequence word of its own; the later of a view's two scans writes the tile lists'.)
+constexpr int FWD_BATCH_VIEWS = 10;   // views per launch of lvdgs_forward_batch
+enum : int { PROBE_COUNT = 0, PROBE_LONGEST = 1, PROBE_QUEUED = 2, PROBE_SEQ = 3, PROBE_BLOCK = 4 };
+constexpr int PROBE_CALL = 0;          // the block of a single call's tile lists
+constexpr int PROBE_CALL_SUPER = 8;    // ... of its super lists
+constexpr int PROBE_BATCH = 16;        // ... of the tile lists of view k of lvdgs_forward_batch: PROBE_BATCH + PROBE_BLOCK * k
+constexpr int PROBE_BATCH_SUPER = PROBE_BATCH + PROBE_BLOCK * FWD_BATCH_VIEWS;   // ... of its super lists: likewise
+constexpr int PROBE_WORDS = PROBE_BATCH_SUPER + PROBE_BLOCK * FWD_BATCH_VIEWS + 8;
+struct PairReport { uint32_t *words = nullptr; uint32_t seq = 0; };   // where a call's tile scans report: the words as the device addresses them (null: nowhere), its sequence number
 // lvdgs_forward_batch: the stages of up to FWD_BATCH_VIEWS views of one map and one image size in one launch each (the view is
-// blockIdx.y; every view its own state and scratch buffers).  caps[k]: view k's pair capacity; host_words: 4 pinned words per view
-// as the device addresses them (pair count, longest queued segment, queue length, the call's sequence number).
-constexpr int FWD_BATCH_VIEWS = 10;
+// blockIdx.y; every view its own state and scratch buffers).  caps[k]: view k's pair capacity.
 int launch_preprocess_count_batch(const lvdgs_args *const *a, const GeomView *g, const ImageView *im, const RenderScratch *w, int n, hipStream_t s);
 int launch_group_scan_batch(const lvdgs_args *const *a, const GeomView *g, const ImageView *im, const RenderScratch *w, const int64_t *caps, int n,
-                            uint32_t *host_words, uint32_t host_seq, uint32_t *host_super, hipStream_t s);
+                            PairReport report, hipStream_t s);
 int launch_group_scatter_batch(const lvdgs_args *const *a, const GeomView *g, const ImageView *im, const RenderScratch *w, const BinView *b,
                                const int64_t *caps, int n, hipStream_t s);
 int launch_tile_depth_sort_batch(const lvdgs_args *const *a, const GeomView *g, const ImageView *im, const RenderScratch *w, const BinView *b, int n,
                                  int longest_expected, int queue_expected, hipStream_t s);
 int launch_group_count(const lvdgs_args &a, const GeomView &g, const ImageView &im, const RenderScratch &w, hipStream_t s);
 // prefixes over the chunks, tile ranges, the pair count (*total_out, may be null), the queue of over-long segments
-int launch_group_scan(const lvdgs_args &a, const ImageView &im, const RenderScratch &w, int64_t capacity, uint32_t *total_out, hipStream_t s,
-                      uint32_t *host_out = nullptr, uint32_t host_seq = 0);   // host_out: pinned words the tile scan writes the pair count + hints + host_seq to
-// slot_scan: also makes slot_base from tiles_touched and w.chunk_sums (launch_preprocess_count's leftovers)
-// total_out / host_out / host_seq: launch_group_scan's, for the tile scan that rides in this launch (binning.hip: LVDGS_SCAN_IN_SCATTER)
+int launch_group_scan(const lvdgs_args &a, const ImageView &im, const RenderScratch &w, int64_t capacity, uint32_t *total_out, PairReport report, hipStream_t s);
+// the pairs into their tiles' segments (two-level grouping: their super-tiles').  slot_scan: also makes slot_base from tiles_touched and w.chunk_sums
+// (launch_preprocess_count's leftovers)
+// total_out / report: launch_group_scan's, for the tile scan that rides in this launch (binning.hip: LVDGS_SCAN_IN_SCATTER)
 int launch_group_scatter(const lvdgs_args &a, const GeomView &g, const ImageView &im, const RenderScratch &w, unsigned long long *keys64,
-                         int64_t capacity, bool slot_scan, uint8_t *pair_valid, hipStream_t s, uint32_t *total_out = nullptr, uint32_t *host_out = nullptr,
-                         uint32_t host_seq = 0);
+                         int64_t capacity, bool slot_scan, uint8_t *pair_valid, uint32_t *total_out, PairReport report, hipStream_t s);
 int launch_emit_pairs(const lvdgs_args &a, const GeomView &g, uint32_t *tile_keys, uint32_t *ids, int64_t capacity, hipStream_t s);
-// two-level grouping (binning.hip): is it in use for this call; super_count + scans + scatter of the super grid; the expansion of the
+// two-level grouping (binning.hip): is it in use for this call (launch_group_scan and _scatter then work on the super grid); its super_count; the expansion of the
 // sorted super lists into the tiles' segments of point_list
 bool super_tiles_in_use(const lvdgs_args &a);
 int super_tiles_of(int W, int H);
 int launch_super_count(const lvdgs_args &a, const GeomView &g, const SuperView &sv, hipStream_t s);   // before launch_group_scan, which then scans both grids
-int launch_super_scatter(const lvdgs_args &a, const GeomView &g, const SuperView &sv, const RenderScratch &w, unsigned long long *keys64, int64_t capacity,
-                         bool slot_scan, uint8_t *pair_valid, hipStream_t s);
 int launch_super_expand_batch(const lvdgs_args *const *a, const GeomView *g, const ImageView *im, const RenderScratch *w, const BinView *b, int n, hipStream_t s);
 int launch_super_expand(const lvdgs_args &a, const GeomView &g, const SuperView &sv, const ImageView &im, const uint32_t *super_list, uint32_t *point_list,
                         hipStream_t s);
@@ -335,7 +349,6 @@ int launch_tile_ranges(const uint32_t *tile_keys, int64_t D, const uint32_t *D_d
                        hipStream_t s);
 
 int launch_blend_fwd(const lvdgs_args &a, const GeomView &g, const BinView &b, const ImageView &im, bool deep_lists, hipStream_t s);   // deep_lists: a hint (which build of the kernel), never a result
-struct LossParams;
 int launch_blend_fwd_batch(const lvdgs_args *const *a, const GeomView *g, const BinView *b, const ImageView *im, int n, bool deep_lists, hipStream_t s);
 int launch_blend_fwd_bwd_fused_loss(const lvdgs_args &a, const GeomView &g, const BinView &b, const ImageView &im, const BwdScratch &w,
                                     const LossParams &loss, int propagate_opacity, bool deep_lists, const uint32_t *pair_total, uint32_t pair_capacity,
