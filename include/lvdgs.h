@@ -584,6 +584,67 @@ size_t lvdgs_depth_align_scratch_bytes(int32_t width, int32_t height, int32_t pa
 int lvdgs_depth_align(const lvdgs_depth_align_args *a, void *stream);
 int lvdgs_depth_align_resume(const lvdgs_depth_align_args *a, float scale, void *stream);
 
+/* ---- pose initialisation by PnP-RANSAC on the rendered depth (reference utils/init_pose.py get_pose :160-175: cv2.undistortPoints +
+ * depth_to_3d + cv2.solvePnPRansac, called for every tracked frame, utils/slam_frontend.py:1448) ----
+ * The unknown is the keyframe -> frame motion T = [R | t] (world = the keyframe's camera frame).  All arithmetic and every comparison
+ * below is float64 from the float32 / int32 loads.
+ * Gather.  Match i = (keyframe pixel (x, y) int32, frame pixel (u, v) float32) is VALID when 0 <= x < width, 0 <= y < height and
+ *   Z = depth[y * width + x] is finite and > 0 (deviation: the reference back-projects zero depth to the origin and leaves it to RANSAC).
+ *   Both pixels go to normalised coordinates by TEN fixed-point steps of the Brown model (cv2.undistortPoints' scheme, twice its
+ *   default count): x0 = (u - cx) / fx, y0 = (v - cy) / fy, (x, y) = (x0, y0), then ten times r2 = x^2 + y^2,
+ *   icd = 1 / (1 + ((k3 r2 + k2) r2 + k1) r2), dx = 2 p1 x y + p2 (r2 + 2 x^2), dy = p1 (r2 + 2 y^2) + 2 p2 x y,
+ *   (x, y) = ((x0 - dx) icd, (y0 - dy) icd).  Object point P = (x_n Z, y_n Z, Z); frame point q = (u_n, v_n).
+ * Residual of a match under T: with (X, Y, Zc) = R P + t, r = (fx (X / Zc - u_n), fy (Y / Zc - v_n)) -- pixels of the undistorted image.
+ *   It is an INLIER when it is valid, Zc > 0 and |r|^2 < reproj_error^2.
+ * Gauss-Newton step on a set of matches: A = sum J^T J, g = sum J^T r with J = dr/dtau under the left perturbation T <- Exp(tau) T,
+ *   tau = [rho; theta] (pose_utils.SE3_exp, series below 1e-5 rad); the diagonal of A is multiplied by 1 + 1e-3 (the damping);
+ *   A tau = -g by Cholesky.  The step FAILS when a pivot is not > 0 or tau is not finite.
+ * Hypotheses.  mix32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 (uint32).  Draw d of hypothesis h:
+ *   mix32(mix32(mix32(seed ^ 0x9e3779b9) + h) + d) % num_matches.  Slot s = 0, 1, 2 takes the first of its draws d = 32 s .. 32 s + 31
+ *   that is a valid match not taken by an earlier slot; a slot that finds none voids the hypothesis.  Eight steps on the three
+ *   matches from the identity; void when a step fails or a sample point ends with Zc <= 0.  Score: the number of inliers.
+ *   Winner: the highest score, ties to the lowest h.
+ * Refinement.  Three rounds of: select the inliers under the current pose, five steps on them.  The inlier mask and count are taken
+ *   under the final pose.  Sums over matches are taken in a fixed order: two calls give the same bits.
+ * FAILED (the pose is the exact identity, the mask zero) with reason FEW_VALID (fewer than 6 valid matches), ALL_VOID, FEW_INLIERS
+ *   (the winner's score < min_inliers) or SINGULAR (a refinement step fails).
+ * Two launches, enqueued at once; no host wait.  host_state: LVDGS_PNP_HOST_BYTES bytes of page-locked, mapped host memory (the host
+ * address): LVDGS_PNP_STATE_WORDS int32 words -- [0] status, [1] valid matches, [2] inliers under the final pose, [3] the winning
+ * hypothesis (-1: none), [4] its score, [5] reason, [6] [7] zero -- then the pose as 12 doubles, row-major [R | t].  The caller
+ * synchronises the stream once and reads it.  scratch: lvdgs_pnp_scratch_bytes(num_matches, hypotheses) bytes, no initialisation needed.
+ * LVDGS_E_INVALID: args NULL, a NULL pointer, bad raster size, num_matches < 0, hypotheses outside 1..LVDGS_PNP_MAX_HYPOTHESES,
+ * reproj_error / fx / fy not > 0, scratch too small; LVDGS_E_HIP: host_state is not mapped pinned memory. */
+#define LVDGS_PNP_MAX_HYPOTHESES 4096
+#define LVDGS_PNP_STATE_WORDS 8
+#define LVDGS_PNP_HOST_BYTES 128
+enum {
+    LVDGS_PNP_OK = 1,
+    LVDGS_PNP_FAILED = 2
+};
+enum {
+    LVDGS_PNP_FAIL_NONE = 0,
+    LVDGS_PNP_FAIL_FEW_VALID = 1,
+    LVDGS_PNP_FAIL_ALL_VOID = 2,
+    LVDGS_PNP_FAIL_FEW_INLIERS = 3,
+    LVDGS_PNP_FAIL_SINGULAR = 4
+};
+typedef struct lvdgs_pnp_args {
+    int32_t width, height;        /* the raster of depth (W1, H1)                   */
+    int32_t num_matches, hypotheses, min_inliers;
+    uint32_t seed;
+    double fx, fy, cx, cy;        /* intrinsics at that raster                      */
+    double dist[5];               /* k1 k2 p1 p2 k3 (all zero: no distortion)       */
+    double reproj_error;          /* pixels                                         */
+    const float *depth;           /* H1*W1                                          */
+    const int32_t *matches_im1;   /* M*2 (x, y) in the keyframe's raster            */
+    const float *matches_im2;     /* M*2 (u, v) in the frame                        */
+    uint8_t *inlier_mask;         /* out M bytes (0 / 1)                            */
+    int32_t *host_state;          /* LVDGS_PNP_HOST_BYTES, pinned host (the host address) */
+    void *scratch; size_t scratch_bytes;
+} lvdgs_pnp_args;
+size_t lvdgs_pnp_scratch_bytes(int32_t num_matches, int32_t hypotheses);
+int lvdgs_pnp_ransac(const lvdgs_pnp_args *a, void *stream);
+
 /* ---- diagnostics ---- */
 const char *lvdgs_last_error(void);
 const char *lvdgs_version(void);

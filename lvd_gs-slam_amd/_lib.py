@@ -130,6 +130,23 @@ DEPTH_ALIGN_MAX_PATCH, DEPTH_ALIGN_STATE_WORDS = 64, 8
 DEPTH_ALIGN_RUNNING, DEPTH_ALIGN_CONVERGED, DEPTH_ALIGN_EXHAUSTED, DEPTH_ALIGN_REMEDY = 0, 1, 2, 3
 
 
+class PnpArgs(C.Structure):
+    """struct lvdgs_pnp_args (include/lvdgs.h)."""
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32), ("num_matches", C.c_int32), ("hypotheses", C.c_int32), ("min_inliers", C.c_int32),
+        ("seed", C.c_uint32),
+        ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("dist", C.c_double * 5),
+        ("reproj_error", C.c_double),
+        ("depth", _fp), ("matches_im1", _fp), ("matches_im2", _fp), ("inlier_mask", _fp), ("host_state", _fp),
+        ("scratch", _fp), ("scratch_bytes", C.c_size_t),
+    ]
+
+
+PNP_MAX_HYPOTHESES, PNP_STATE_WORDS, PNP_HOST_BYTES = 4096, 8, 128
+PNP_OK, PNP_FAILED = 1, 2
+PNP_FAIL_NONE, PNP_FAIL_FEW_VALID, PNP_FAIL_ALL_VOID, PNP_FAIL_FEW_INLIERS, PNP_FAIL_SINGULAR = 0, 1, 2, 3, 4
+
+
 class StateLayout(C.Structure):
     _fields_ = [(n, C.c_size_t) for n in (
         "geom_rec", "geom_tiles_touched", "geom_slot_base", "bin_point_list", "bin_tile_keys",
@@ -150,7 +167,7 @@ EXPORTS = (
     "lvdgs_photometric_loss_backward", "lvdgs_photometric_loss_value_and_grad", "lvdgs_photometric_loss_partials", "lvdgs_tracking_tail", "lvdgs_backward_fused_loss", "lvdgs_blend_forward_batch", "lvdgs_blend_backward_fused_loss_batch", "lvdgs_masked_depth_scratch_bytes", "lvdgs_masked_depth_l1_forward",
     "lvdgs_masked_depth_l1_backward", "lvdgs_pose_step", "lvdgs_host_device_pointer", "lvdgs_pose_step_batch", "lvdgs_adam_step", "lvdgs_isotropic_scratch_bytes", "lvdgs_isotropic_reg", "lvdgs_view_stats", "lvdgs_map_stats_apply", "lvdgs_map_view_tail", "lvdgs_ssim_scratch_bytes", "lvdgs_ssim_l1",
     "lvdgs_masked_loss_scratch_bytes", "lvdgs_masked_loss_batch", "lvdgs_backward_masked_loss", "lvdgs_blend_backward_window_batch", "lvdgs_forward_batch", "lvdgs_forward_backward_fused_loss", "lvdgs_map_view_tail_batch", "lvdgs_gaussian_backward_batch",
-    "lvdgs_depth_align_scratch_bytes", "lvdgs_depth_align", "lvdgs_depth_align_resume", "lvdgs_last_error", "lvdgs_version", "lvdgs_profile_enable",
+    "lvdgs_depth_align_scratch_bytes", "lvdgs_depth_align", "lvdgs_depth_align_resume", "lvdgs_pnp_scratch_bytes", "lvdgs_pnp_ransac", "lvdgs_last_error", "lvdgs_version", "lvdgs_profile_enable",
     "lvdgs_profile_reset", "lvdgs_profile_read",
 )
 
@@ -237,6 +254,9 @@ def lib():
         L.lvdgs_depth_align_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
         L.lvdgs_depth_align.argtypes = [C.POINTER(DepthAlignArgs), C.c_void_p]
         L.lvdgs_depth_align_resume.argtypes = [C.POINTER(DepthAlignArgs), C.c_float, C.c_void_p]
+        L.lvdgs_pnp_scratch_bytes.restype = C.c_size_t
+        L.lvdgs_pnp_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
+        L.lvdgs_pnp_ransac.argtypes = [C.POINTER(PnpArgs), C.c_void_p]
         L.lvdgs_profile_enable.argtypes = [C.c_int]
         L.lvdgs_profile_read.argtypes = [C.POINTER(KernelTime), C.c_int]
         _lib = L

@@ -158,8 +158,8 @@ def track_frame(viewpoint, gaussians, config, pipeline_params, background, track
                 on_iteration=None, fused="auto"):
     """Pose + exposure optimisation of one frame against the map (reference utils/slam_frontend.py:1467-1536): up to
     ``tracking_itr_num`` iterations of render -> get_loss_tracking -> backward -> Adam step -> ``update_pose``, stopping
-    when the pose update falls under 1e-4 (utils/pose_utils.py:82).  The frame's initial ``R, T`` (MASt3R / PnP, out of
-    scope here) must already be set.  Returns (last render package, median depth :1535, iterations run).
+    when the pose update falls under 1e-4 (utils/pose_utils.py:82).  The frame's initial ``R, T`` (the previous pose, or
+    ``init_pose.get_pose``'s PnP estimate) must already be set.  Returns (last render package, median depth :1535, iterations run).
 
     ``fused`` ("auto" / True / False): with the HIP renderer and everything on the GPU the loop runs on
     ``fast_tracking.TrackingSession`` -- the same arithmetic as three C-ABI calls per iteration on buffers that live for

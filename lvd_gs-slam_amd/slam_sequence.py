@@ -23,7 +23,10 @@ visibility vectors the size of the map it renders while the back end densifies a
 iterations per tracked frame (``idle_map_iters``; in the reference that number is whatever the wall clock allows).
 
 Stand-ins for what is out of scope, all injectable:
-  * the pose initialisation: the previous frame's pose -- the reference's own branch for "MASt3R returned the identity";
+  * the pose initialisation: by default the previous frame's pose -- the reference's own branch for "MASt3R returned the identity".
+    ``pose_init="pnp"`` follows ``FrontEnd.tracking`` (:1442-1465): ``init_pose.get_pose`` (PnP-RANSAC on the last keyframe's rendered
+    depth, HIP) gives the keyframe -> frame motion, ``pose_init = rel_pose @ pose_last_kf``, the previous pose when that is the identity;
+    only the matcher needs MASt3R -- injectable as ``matcher`` (``synthetic.GroundTruthMatcher`` is the stand-in);
   * ``keyframe_depth``: the depth map a new keyframe seeds Gaussians from.  Default: the keyframe's mono depth under the valid-pixel
     mask, i.e. ``add_new_keyframe``'s own statements for the first keyframe (:1364-1382) applied to every keyframe.  For later
     keyframes the reference blends rendered and mono depth patch by patch and rescales the mono depth (``process_depth``,
@@ -106,7 +109,8 @@ class SlamSequence:
 
     def __init__(self, config, dataset, gaussians, pipeline_params, background, *, fused="auto", render_fn=render, view_loss_fn=None,
                  refine_loss_fn=None, keyframe_depth=None, idle_map_iters=0, camera_cls=None, cameras_extent=6.0, on_event=None,
-                 group=None, aux_group=None, bands_ok=None, depth_align_fn=None, scale_remedy=None, depth_align_params=None):
+                 group=None, aux_group=None, bands_ok=None, depth_align_fn=None, scale_remedy=None, depth_align_params=None,
+                 pose_init=None, matcher=None, pose_init_params=None):
         from .backend_map import map_window
         if camera_cls is None:
             from .camera_utils import Camera as camera_cls
@@ -128,6 +132,21 @@ class SlamSequence:
         self.depth_align_fn, self.scale_remedy = depth_align_fn, scale_remedy
         self.depth_align_params = dict(depth_align_params or {})
         self.depth_align_log = []      # per aligned keyframe: frame, scale_factor, num_accurate_pixels, error_pixel_share, remedy_fired
+        # pose_init: None (the default: the previous frame's pose, nothing logged), "previous" (the same poses, with the per-frame log),
+        # "pnp" (init_pose.get_pose with `matcher`), or a callable (last_kf, viewpoint, kf_idx, frame_idx) -> (4, 4) keyframe -> frame motion
+        # (the identity: no estimate).  pose_init_params: get_pose's keyword parameters (hypotheses, reproj_error, seed, min_inliers).
+        if pose_init == "pnp":
+            if matcher is None:
+                raise TypeError("SlamSequence(pose_init='pnp') needs the `matcher` argument (init_pose.get_pose's matcher)")
+            self.pose_init_fn = self.pnp_pose_init
+        elif pose_init is None or pose_init == "previous":
+            self.pose_init_fn = None
+        elif callable(pose_init):
+            self.pose_init_fn = pose_init
+        else:
+            raise ValueError(f"pose_init: None, 'previous', 'pnp' or a callable, not {pose_init!r}")
+        self.pose_init, self.matcher, self.pose_init_params = pose_init, matcher, dict(pose_init_params or {})
+        self.pose_init_log = []        # per tracked frame (pose_init not None): see `tracking`
         self.idle_map_iters, self.camera_cls, self.on_event = int(idle_map_iters), camera_cls, on_event
         self._map_window = map_window
         # several ranks (torch.distributed initialised): every rank runs the whole sequence -- tracking, map initialisation and colour
@@ -155,6 +174,8 @@ class SlamSequence:
         self.seconds = dict(tracking=0.0, mapping=0.0, init=0.0, seeding=0.0, refinement=0.0, other=0.0)
         if self.patch_align:
             self.seconds["depth_align"] = 0.0
+        if self.pose_init_fn is not None:
+            self.seconds["pose_init"] = 0.0
         self.window_log = []           # the window after every keyframe
         self.frame_log = []            # per tracked frame: tracking iterations, the keyframe test's inputs and its outcome
         self.batched_sizes = []        # the map's size at every mapping call that went through the batched window (MapWindowBatch)
@@ -317,18 +338,63 @@ class SlamSequence:
         self.frontend_gaussians = clone_map(self.gaussians)
         self.occ_aware_visibility = dict(self.backend.occ_aware_visibility)
 
+    def pnp_pose_init(self, last_kf, viewpoint, kf_idx, cur_frame_idx):
+        """``get_pose`` as ``FrontEnd.tracking`` calls it (:1445-1453): the last keyframe rendered from the front end's copy of the map."""
+        from . import init_pose
+        if hasattr(self.matcher, "set_frames"):      # a stand-in that works from the dataset, not from the images
+            self.matcher.set_frames(kf_idx, cur_frame_idx)
+        rel_pose, _ = init_pose.get_pose(last_kf.original_image, viewpoint.original_image, None, getattr(self.dataset, "dist_coeffs", None),
+                                         last_kf, self.frontend_gaussians, self.pipeline_params, self.background, matcher=self.matcher,
+                                         **self.pose_init_params)
+        return rel_pose
+
+    @staticmethod
+    def _pose_error(R, T, viewpoint):
+        """(distance of the camera centres, rotation angle in degrees) of the pose (R, T) against the viewpoint's ground truth."""
+        R, T = R.detach().double().cpu(), T.detach().double().cpu()
+        Rg, Tg = viewpoint.R_gt.detach().double().cpu(), viewpoint.T_gt.detach().double().cpu()
+        cos = ((torch.trace(R @ Rg.T) - 1.0) / 2.0).clamp(-1.0, 1.0)
+        return float((R.T @ T - Rg.T @ Tg).norm()), float(torch.rad2deg(torch.acos(cos)))
+
     def tracking(self, cur_frame_idx, viewpoint):
-        """FrontEnd.tracking (:1416-1536) with the previous frame's pose as the initial estimate."""
+        """FrontEnd.tracking (:1416-1536).  The initial estimate: the previous frame's pose, or (``pose_init``) :1442-1465."""
         if self.enable_dynamic_filtering:
             self._attach_masks(viewpoint, cur_frame_idx, False)
         prev = self.cameras[cur_frame_idx - 1]
-        viewpoint.update_RT(prev.R, prev.T)
+        record = None
+        if self.pose_init_fn is None:
+            viewpoint.update_RT(prev.R, prev.T)
+        else:
+            kf_idx = self.current_window[0]
+            last_kf = self.cameras[kf_idx]
+            with self._timed("pose_init"):
+                rel_pose = np.asarray(self.pose_init_fn(last_kf, viewpoint, kf_idx, cur_frame_idx), dtype=np.float64)
+            estimated = not np.allclose(rel_pose, np.eye(4), atol=1e-6)
+            if estimated:
+                pose_last_kf = torch.eye(4, dtype=torch.float64)
+                pose_last_kf[:3, :3], pose_last_kf[:3, 3] = last_kf.R.detach().double().cpu(), last_kf.T.detach().double().cpu()
+                init = torch.from_numpy(rel_pose) @ pose_last_kf
+                viewpoint.update_RT(init[:3, :3].to(prev.R.dtype), init[:3, 3].to(prev.T.dtype))
+            else:
+                viewpoint.update_RT(prev.R, prev.T)
+            record = dict(frame=cur_frame_idx, keyframe=int(kf_idx), estimated=bool(estimated))
+            if self.pose_init == "pnp":
+                from . import init_pose
+                lc = init_pose.last_call
+                record.update(matches=lc.matches, valid_matches=lc.valid_matches, inliers=lc.inliers)
+        if self.pose_init is not None:
+            record = record or dict(frame=cur_frame_idx, keyframe=int(self.current_window[0]), estimated=False)
+            record["init_translation_error"], record["init_rotation_error_deg"] = self._pose_error(viewpoint.R, viewpoint.T, viewpoint)
+            record["previous_translation_error"], record["previous_rotation_error_deg"] = self._pose_error(prev.R, prev.T, viewpoint)
         with self._timed("tracking"):
             render_pkg, median_depth, its = track_frame(viewpoint, self.frontend_gaussians, self.config, self.pipeline_params, self.background,
                                                         tracking_itr_num=self.tracking_itr_num, render_fn=self.render_fn, fused=self.fused)
         self.median_depth = median_depth
         self.counts["tracking_iterations"] += int(its)
         self._last_tracking_iterations = int(its)
+        if record is not None:
+            record["tracking_iterations"] = int(its)
+            self.pose_init_log.append(record)
         return render_pkg
 
     def handle_keyframe(self, cur_frame_idx, viewpoint, depth_map):
@@ -471,4 +537,5 @@ class SlamSequence:
                     tracking_plus_mapping_iterations_per_s=None if not loops else round(its / loops, 2),
                     tracking_iterations_per_s=None if not s.get("tracking") else round(c["tracking_iterations"] / s["tracking"], 2),
                     mapping_iterations_per_s=None if not s.get("mapping") else round(c["mapping_iterations"] / s["mapping"], 2),
-                    **({"depth_align": list(self.depth_align_log)} if self.patch_align else {}))
+                    **({"depth_align": list(self.depth_align_log)} if self.patch_align else {}),
+                    **({"pose_init": list(self.pose_init_log)} if self.pose_init is not None else {}))

@@ -254,3 +254,57 @@ def mono_scale_factor(i, drift):
     """Frame i's mono depth scale under ``make_sequence(..., mono_scale_drift=drift)``: 1 + drift * sin(2 pi i / 11) -- a
     wander between 1 - drift and 1 + drift that never repeats within a short drive."""
     return 1.0 + drift * math.sin(2.0 * math.pi * i / 11.0)
+
+
+class GroundTruthMatcher:
+    """The stand-in for the MASt3R matcher of ``init_pose.get_pose`` (descriptors + ``fast_reciprocal_NNs(subsample_or_initxy1=8)``, out
+    of scope): 2D-2D matches between a keyframe and a frame of a ``SequenceDataset`` made from the ground truth.
+
+    The stride-``stride`` grid of the keyframe at the matcher's raster; every grid point is carried into the new frame with the two
+    ground-truth poses and the keyframe's mono depth at that pixel (points without depth are dropped), perturbed by Gaussian noise of
+    ``noise_px`` raster pixels, and dropped when it leaves the frame.  A seeded share ``outlier_ratio`` of the matches -- and every match
+    that lies on a dynamic rectangle in either frame: those objects move -- is replaced by a uniformly random pixel of the new frame.
+    ``set_frames(keyframe_idx, frame_idx)`` says which pair the next call is about (``SlamSequence`` calls it); the call itself has the
+    matcher's signature ``(img1, img2, model, (W1, H1)) -> (matches_im1 (M, 2) int32, matches_im2 (M, 2) float32)``, NumPy arrays."""
+
+    def __init__(self, dataset, stride=8, noise_px=0.7, outlier_ratio=0.3, seed=0):
+        self.dataset, self.stride, self.noise_px, self.outlier_ratio, self.seed = dataset, int(stride), float(noise_px), float(outlier_ratio), int(seed)
+        self.pair = None
+
+    def set_frames(self, keyframe_idx, frame_idx):
+        self.pair = (int(keyframe_idx), int(frame_idx))
+
+    def __call__(self, img1, img2, model, raster):
+        import numpy as np
+        if self.pair is None:
+            raise RuntimeError("GroundTruthMatcher: set_frames(keyframe_idx, frame_idx) first")
+        kf, cur = self.pair
+        ds = self.dataset
+        W1, H1 = raster
+        sw, sh = W1 / ds.width, H1 / ds.height
+        rng = np.random.default_rng([self.seed, kf, cur])
+        gy, gx = np.meshgrid(np.arange(self.stride // 2, H1, self.stride), np.arange(self.stride // 2, W1, self.stride), indexing="ij")
+        gx, gy = gx.ravel(), gy.ravel()
+        # the full-size pixel under each grid point
+        fx_, fy_ = np.minimum((gx / sw).round().astype(np.int64), ds.width - 1), np.minimum((gy / sh).round().astype(np.int64), ds.height - 1)
+        Z = np.asarray(ds.mono_depths[kf], dtype=np.float64)[fy_, fx_]
+        P = np.stack([(gx / sw - ds.cx) / ds.fx * Z, (gy / sh - ds.cy) / ds.fy * Z, Z], 1)
+        T1, T2 = ds.poses[kf].double().cpu().numpy(), ds.poses[cur].double().cpu().numpy()
+        rel = T2 @ np.linalg.inv(T1)
+        X = P @ rel[:3, :3].T + rel[:3, 3]
+        with np.errstate(all="ignore"):
+            u = (ds.fx * X[:, 0] / X[:, 2] + ds.cx) * sw + self.noise_px * rng.normal(size=len(Z))
+            v = (ds.fy * X[:, 1] / X[:, 2] + ds.cy) * sh + self.noise_px * rng.normal(size=len(Z))
+            keep = (Z > 0) & np.isfinite(Z) & (X[:, 2] > 0) & (u >= 0) & (u <= W1 - 1) & (v >= 0) & (v <= H1 - 1)
+        gx, gy, fx_, fy_, u, v = gx[keep], gy[keep], fx_[keep], fy_[keep], u[keep], v[keep]
+        M = len(gx)
+        bad = rng.random(M) < self.outlier_ratio
+        m1s, m2s = ds.static_mask(kf), ds.static_mask(cur)
+        if m1s is not None:
+            bad |= ~m1s.cpu().numpy()[fy_, fx_]
+        if m2s is not None:
+            ux, vy = np.clip((u / sw).round().astype(np.int64), 0, ds.width - 1), np.clip((v / sh).round().astype(np.int64), 0, ds.height - 1)
+            bad |= ~m2s.cpu().numpy()[vy, ux]
+        u = np.where(bad, rng.uniform(0, W1 - 1, M), u)
+        v = np.where(bad, rng.uniform(0, H1 - 1, M), v)
+        return np.stack([gx, gy], 1).astype(np.int32), np.stack([u, v], 1).astype(np.float32)

@@ -5,7 +5,7 @@ pruning / opacity resets at the reference's cadence -> pruning pass, the back en
 the end ATE (Umeyama), PSNR before / after a colour refinement (lvdgs.slam_sequence.SlamSequence; reference utils/slam_frontend.py:1740-1899,
 utils/slam_backend.py:485-609, utils/eval_utils_0806.py:33-306).
 
-    python tools/sequence.py [--frames 60] [--scale 1.0] [--cadence reference|short] [--no-fused] [--idle 10] [--refine 500] [--no-masks]
+    python tools/sequence.py [--frames 60] [--scale 1.0] [--cadence reference|short] [--no-fused] [--idle 10] [--refine 500] [--no-masks] [--pose-init previous|pnp]
 
 Prints one JSON object (bench.py's config.side.sequence_kitti07_geom is the same record).  `--cadence reference`: the iteration
 counts and densification schedule of configs/mono/KITTI/base_config.yaml as they are; `short`: every burst a fifth of it (the GPU
@@ -72,8 +72,9 @@ GEOMETRY = {"kitti07": dict(W=1226, H=370, fx=707.0912, cx=601.8873, cy=183.1104
 
 
 def kitti_sequence(dev, frames=60, scale=1.0, cadence="reference", masks=True, n_true=None, seed=0, training=None, window_size=None, geometry="kitti07",
-                   pcd_downsample=None, mono_scale_drift=0.0):
-    """(config, dataset, true map): a frame geometry of ``GEOMETRY`` (x ``scale``), the merged KITTI-07 config with the chosen cadence."""
+                   pcd_downsample=None, mono_scale_drift=0.0, trajectory=None):
+    """(config, dataset, true map): a frame geometry of ``GEOMETRY`` (x ``scale``), the merged KITTI-07 config with the chosen cadence.
+    ``trajectory``: ``synthetic.vehicle_trajectory``'s parameters (step, sway, yaw, period) laid over the default drive's."""
     geo = GEOMETRY[geometry]
     W, H = int(round(geo["W"] * scale)), int(round(geo["H"] * scale))
     fx = fy = geo["fx"] * scale
@@ -95,19 +96,21 @@ def kitti_sequence(dev, frames=60, scale=1.0, cadence="reference", masks=True, n
     # of view is wider than the generator's (fx < W) and the camera moves
     truth = truth_model(W, H, n_true, 1.5 * scale, 16.0 * scale, 0.9, dev, seed=11 + seed)
     ds = synthetic.make_sequence(truth, render, PIPE, W, H, frames, dev, fx=fx, fy=fy, cx=cx, cy=cy, seed=seed, depth_noise=0.02,
-                                 image_noise=0.01, dynamic_objects=masks, step=0.02, sway=0.15, yaw=0.03, period=40.0,
-                                 mono_scale_drift=mono_scale_drift)
+                                 image_noise=0.01, dynamic_objects=masks, mono_scale_drift=mono_scale_drift,
+                                 **{**dict(step=0.02, sway=0.15, yaw=0.03, period=40.0), **(trajectory or {})})
     return cfg, ds, truth
 
 
 def run_sequence(dev, frames=60, scale=1.0, cadence="reference", fused="auto", idle=10, refine=500, masks=True, seed=0, training=None,
-                 window_size=None, on_event=None, geometry="kitti07", pcd_downsample=None, mono_scale_drift=0.0, **sequence_kwargs):
+                 window_size=None, on_event=None, geometry="kitti07", pcd_downsample=None, mono_scale_drift=0.0, trajectory=None, **sequence_kwargs):
     torch.manual_seed(seed)
     random.seed(seed)
     cfg, ds, truth = kitti_sequence(dev, frames, scale, cadence, masks, seed=seed, training=training, window_size=window_size, geometry=geometry,
-                                    pcd_downsample=pcd_downsample, mono_scale_drift=mono_scale_drift)
+                                    pcd_downsample=pcd_downsample, mono_scale_drift=mono_scale_drift, trajectory=trajectory)
     del truth
     m = empty_map(cfg, dev)
+    if sequence_kwargs.get("pose_init") == "pnp" and sequence_kwargs.get("matcher") is None:
+        sequence_kwargs["matcher"] = synthetic.GroundTruthMatcher(ds, stride=8, noise_px=0.7, outlier_ratio=0.3, seed=seed)
     seq = SlamSequence(cfg, ds, m, PIPE, torch.zeros(3, device=dev), fused=fused, idle_map_iters=idle, on_event=on_event, **sequence_kwargs)
     seq.run()
     out = seq.summary()
@@ -150,6 +153,8 @@ def main():
     ap.add_argument("--keyframe-depth", choices=["mono", "patch_align"], default="mono",
                     help="seed later keyframes from the mono depth (default) or from LVD-GS Algorithm 1's alignment to the rendered depth")
     ap.add_argument("--mono-scale-drift", type=float, default=0.0, help="per-frame scale wander of the synthetic mono depth (synthetic.mono_scale_factor)")
+    ap.add_argument("--pose-init", choices=["previous", "pnp"], default=None,
+                    help="log every tracked frame's initial pose (summary key pose_init); pnp: start it from init_pose.get_pose with synthetic.GroundTruthMatcher")
     ap.add_argument("--verbose", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -157,7 +162,12 @@ def main():
     ev = (lambda e, s: print(f"  frame {s.counts['frames']:3d} {e:16s} N = {s._n()}", file=sys.stderr)) if a.verbose else None
     out, _ = run_sequence(dev, a.frames, a.scale, a.cadence, False if a.no_fused else "auto", a.idle, a.refine, not a.no_masks, seed=a.seed,
                           window_size=a.window_size, on_event=ev, geometry=a.geometry, pcd_downsample=a.pcd_downsample,
-                          mono_scale_drift=a.mono_scale_drift, **({"keyframe_depth": "patch_align"} if a.keyframe_depth == "patch_align" else {}))
+                          mono_scale_drift=a.mono_scale_drift, **({"keyframe_depth": "patch_align"} if a.keyframe_depth == "patch_align" else {}),
+                          **({"pose_init": a.pose_init} if a.pose_init else {}))
+    for rec in out.get("pose_init", []):
+        print("  frame {frame:3d} kf {keyframe:3d} inliers {inl:>5} init error {e:.4f} ({r:.3f} deg; previous pose {p:.4f}) tracking iterations {it}".format(
+            frame=rec["frame"], keyframe=rec["keyframe"], inl=rec.get("inliers", "-"), e=rec["init_translation_error"], r=rec["init_rotation_error_deg"],
+            p=rec["previous_translation_error"], it=rec["tracking_iterations"]), file=sys.stderr)
     out["seed"] = a.seed
     out["tool_seconds"] = round(time.perf_counter() - t0, 2)
     print(json.dumps(out))
