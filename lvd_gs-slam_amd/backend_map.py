@@ -33,6 +33,8 @@ replicas only.
 """
 import ctypes as C
 import os
+from collections import namedtuple
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Sequence
 
 import torch
@@ -41,7 +43,7 @@ import torch.distributed as dist
 from . import _lib
 from ._lib import ptr as _P
 
-from .fast_mapping import MapViewPass, MapWindowBatch, _PARAM_FIELDS
+from .fast_mapping import MapViewPass, MapWindowBatch, _PARAM_FIELDS, _remember
 from .gaussian_renderer import render
 from .loss_utils import masked_mapping_loss
 from .pose_utils import update_pose
@@ -260,6 +262,25 @@ class FlatReducer:
         if world > 1:
             work = dist.all_reduce(flat, op=dist.ReduceOp.MAX, group=group, async_op=async_op)
         return (list(flat.split(sizes)), work) if async_op else list(flat.split(sizes))
+
+
+class FloatLayout:
+    """The float SUM bucket of one sharded mapping iteration; the order of its pieces is written here and nowhere else:
+        [ Gaussian parameter gradients | pad | keyframe gradients | norm_sum (N) | vis_count (N) | split_xy (2 N per split view) | loss (1) ]
+    (``pad`` brings the first ``scatter_len`` floats, which ``ShardedAdam`` reduce-scatters, to a multiple of the world size.)"""
+
+    def __init__(self, params, pad, kf_params, N, n_split):
+        self.n_params, self.n_kf = len(params), len(kf_params)
+        self.sizes = [p.numel() for p in params] + [pad] + [p.numel() for p in kf_params] + [N, N, 2 * N * n_split, 1]
+        self.scatter_len = sum(self.sizes[:self.n_params + 1])
+
+    def tensors(self, grads, kf_grads, norm_sum, vis_count, split_xy, loss):
+        return list(grads) + [None] + list(kf_grads) + [norm_sum, vis_count, split_xy, loss]
+
+    def pieces(self, views):
+        k, m = self.n_params, self.n_params + 1 + self.n_kf
+        norm_sum, vis_count, split_xy, loss = views[m:]
+        return SimpleNamespace(params=views[:k], kf_params=views[k + 1:m], norm_sum=norm_sum, vis_count=vis_count, split_xy=split_xy, loss=loss)
 
 
 FLAGS_AS_INT32 = False   # set by ``collective_preflight`` when the communicator cannot MAX-reduce uint8
@@ -826,280 +847,70 @@ def map_window(backend, current_window, prune=False, iters=1, up_pose=True, grou
 
 def _map_window(backend, current_window, prune, iters, up_pose, group, reducer, render_fn, view_loss_fn, stats, fused, aux_group, bands_ok,
                 sharded_adam):
+    """What stands for the whole call (``c``), then per iteration the steps the phase marks name: ``_deal``, ``_plan_bucket`` and
+    ``_render_and_score`` ("views"), ``vs.add`` ("statistics"), ``_reduce`` ("collectives"), the visibility rows and either
+    ``_pruning_pass`` (which ends the call) or ``_bookkeeping`` ("bookkeeping"), ``_optimizer_steps``."""
     if bands_ok is None:
         bands_ok = view_loss_fn is None or view_loss_fn is view_loss
     if sharded_adam is None:
         sharded_adam = bool(getattr(backend, "shard_optimizer", False))
     view_loss_fn = view_loss if view_loss_fn is None else view_loss_fn
     rank, world = _world(group)
-    reducer = reducer if reducer is not None else getattr(backend, "_lvdgs_reducer", None) or FlatReducer()
-    try:
-        backend._lvdgs_reducer = reducer
-    except Exception:
-        pass
+    reducer = _remember(backend, "_lvdgs_reducer", reducer if reducer is not None else getattr(backend, "_lvdgs_reducer", None) or FlatReducer())
     cfg = backend.config
     G = backend.gaussians
     sharder = getattr(backend, "_lvdgs_sharder", None)
     if sharded_adam and world > 1 and (sharder is None or sharder.group is not group):
-        sharder = ShardedAdam(group)
-        try:
-            backend._lvdgs_sharder = sharder
-        except Exception:
-            pass
+        sharder = _remember(backend, "_lvdgs_sharder", ShardedAdam(group))
     if sharder is not None and not (sharded_adam and world > 1):
         sharder.sync_moments(G.optimizer, G.parameters())   # back to the replicated step: every rank needs every moment
         sharder = None
-    viewpoint_stack = [backend.viewpoints[kf_idx] for kf_idx in current_window]
-    frames_to_optimize = cfg["Training"]["pose_window"]
     window_set = set(current_window)
-    random_viewpoint_stack = [vp for cam_idx, vp in backend.viewpoints.items() if cam_idx not in window_set]
-    n_window = len(current_window)
     # pose / exposure parameters the keyframe optimiser holds: their gradients ride in the float bucket
     kf_params = []
     if backend.keyframe_optimizers is not None:
         for gp in backend.keyframe_optimizers.param_groups:
             kf_params.extend(gp["params"])
+    c = SimpleNamespace(
+        backend=backend, G=G, cfg=cfg, rank=rank, world=world, group=group, reducer=reducer, sharder=sharder, stats=stats,
+        small_group=aux_group if aux_group is not None else (getattr(backend, "shard_aux_group", None) or group),   # (of the two MAX collectives)
+        window=current_window, n_window=len(current_window), kf_params=kf_params, pose_window=cfg["Training"]["pose_window"],
+        window_views=[backend.viewpoints[kf_idx] for kf_idx in current_window],
+        older_views=[vp for cam_idx, vp in backend.viewpoints.items() if cam_idx not in window_set],
+        render_fn=render_fn, view_loss_fn=view_loss_fn, bands_ok=bands_ok, fused=fused, up_pose=up_pose,
+        vpass=_view_pass(backend) if (fused and render_fn is render and view_loss_fn is view_loss) else None,
+        masked_spec=(float(backend.opt_params.lambda_dssim), float(cfg["Training"].get("depth_lambda", 0.1))))   # of MapViewPass's masked_loss
     gaussian_split = False
 
     for _ in range(iters):
         backend.iteration_count += 1
         backend.last_sent += 1
-        picks = random_view_indices(len(random_viewpoint_stack), 2, backend.iteration_count, world,
-                                    seed=getattr(backend, "shard_seed", 0))
-        views = viewpoint_stack + [random_viewpoint_stack[i] for i in picks]
         marks = _PhaseMarks(G.get_xyz.device) if stats is not None else None
-        vpass = _view_pass(backend) if (fused and render_fn is render and view_loss_fn is view_loss) else None
-        # a view renders in bands when its loss is a sum over pixels: get_loss_mapping, i.e. no static mask (L1 + SSIM and a
-        # count-normalised depth term are not); window views without MapViewPass take the _BandView route through autograd
-        # (the random views always score with get_loss_mapping; a caller's own window loss splits only if the caller says so)
-        splittable = [(bands_ok and getattr(v, "static_mask", None) is None) or i >= n_window for i, v in enumerate(views)]
-        pieces = plan_pieces([_tile_rows(v) for v in views], world, backend.iteration_count, splittable)
-        split = sorted({v for v, r0, r1, _ in pieces if (r0, r1) != (0, _tile_rows(views[v]))})
-        mine = [(v, r0, r1) for v, r0, r1, o in pieces if o == rank]
-
-        loss_mapping = 0      # pieces that go through autograd (a graph)
-        loss_direct = None    # pieces rendered, scored and differentiated by MapViewPass (values only)
-        direct_losses = []    # (summed once: an addition per view is a launch per view)
-        pkgs = []
-        # sharded: the first piece's backward writes the parameter gradients straight into their slices of the float
-        # bucket the all-reduce works on (no packing copy); the statistics' float pieces live there too
-        plan = first = None
-        N0 = G.get_xyz.shape[0]
-        pad = 0   # (sharded Adam: the parameter-gradient part of the bucket is a multiple of the world size)
-        if world > 1:
-            live = G.parameters()
-            if sharder is not None:
-                _, total_p, padded_p, _ = sharder.plan(live)
-                pad = padded_p - total_p
-            plan = reducer.plan_floats([p.numel() for p in live] + [pad] + [p.numel() for p in kf_params] + [N0, N0, 2 * N0 * len(split), 1],
-                                       live[0].device)
-            if vpass is not None:
-                first = {n: plan[k].view_as(p) for k, (n, p) in enumerate(zip(_PARAM_FIELDS, live))}
+        views, mine, split = _deal(c)
+        params = G.parameters()
+        layout, first, vs = _plan_bucket(c, params, split)
+        pkgs, loss = _render_and_score(c, mine, first, vs)
         with torch.no_grad():
-            vs = _ViewStats(N0, n_window, G.get_xyz.device, split, (plan[-4], plan[-3], plan[-2]) if plan is not None else None)
-        # A window keyframe with a static mask -- under the reference's default configuration every one of them
-        # (utils/slam_frontend.py:1218,1429-1433) -- is scored by L1 + SSIM on the static pixels and the masked depth term (:196-261):
-        # (lambda_dssim, depth_lambda) for MapViewPass / MapWindowBatch; every other view by get_loss_mapping (None)
-        masked_spec = (float(backend.opt_params.lambda_dssim), float(cfg["Training"].get("depth_lambda", 0.1)))
-        masked_of = [masked_spec if (i < n_window and getattr(v, "static_mask", None) is not None and vpass is not None
-                                     and MapViewPass.masked_loss_usable(v)) else None for i, v in enumerate(views)]
-        # The WHOLE views of this rank (one GPU: the whole window; two GPUs: five views each; four: two each + bands; eight: one +
-        # a band) with every stage in one launch for all of them: forward chains, blend passes, static-mask losses
-        # (fast_mapping.MapWindowBatch -- a KITTI-size frame alone leaves the chip half empty; LVDGS_MAP_BATCH=0: view by view).
-        # The rank's bands, and whole views the batch cannot take, follow view by view and add to the batch's gradients.
-        together = []
-        if vpass is not None and os.environ.get("LVDGS_MAP_BATCH", "1") != "0":
-            together = [(v, r0, r1) for v, r0, r1 in mine if (r0, r1) == (0, _tile_rows(views[v]))
-                        and (masked_of[v] is not None or getattr(views[v], "static_mask", None) is None or v >= n_window)]
-            if not MapWindowBatch.usable(backend, [views[v] for v, _, _ in together], [masked_of[v] for v, _, _ in together]):
-                together = []
-        if together:
-            batch = getattr(backend, "_lvdgs_window_batch", None)
-            if batch is None or batch.passes[0] is not vpass:
-                batch = backend._lvdgs_window_batch = MapWindowBatch(vpass)
-            for (v, r0, _), (pkg, l) in zip(together, batch.run(backend, [views[v] for v, _, _ in together], first=first,
-                                                                 stats=[vs.targets(v, r0) for v, r0, _ in together],
-                                                                 masked=[masked_of[v] for v, _, _ in together])):
-                pkgs.append((v, r0, pkg))
-                direct_losses.append(l)
-        for v, r0, r1 in [pc for pc in mine if pc not in together]:
-            whole = (r0, r1) == (0, _tile_rows(views[v]))
-            masked = v < n_window and getattr(views[v], "static_mask", None) is not None
-            if vpass is not None and MapViewPass.usable(backend, views[v], allow_static_mask=True) and (not masked or masked_of[v] is not None):
-                # a window keyframe with a static mask: the static-mask loss (its colour-gradient image from the fused L1 + SSIM
-                # launch, the depth term's gradient inside the backward blend pass); every other view: get_loss_mapping inside
-                # the backward blend pass
-                pkg, l = vpass.run(backend, views[v], first=first, band=None if whole else (r0, r1), masked_loss=masked_of[v],
-                                   stats=vs.targets(v, r0))
-                pkgs.append((v, r0, pkg))
-                direct_losses.append(l)
-                continue
-            pkg = render_fn(views[v], G, backend.pipeline_params, backend.background)
-            pkgs.append((v, r0, pkg))
-            if not whole and not cfg["Training"]["rgb_boundary_threshold"] >= 0:
-                raise ValueError("a view in bands needs rgb_boundary_threshold >= 0: pixels outside the band are masked out by their zeroed target")
-            target = views[v] if whole else _BandView(views[v], 16 * r0, min(16 * r1, int(views[v].image_height)))
-            if v < n_window:
-                loss_mapping = loss_mapping + view_loss_fn(backend, target, pkg)
-            else:
-                loss_mapping = loss_mapping + get_loss_mapping(cfg, pkg["render"], target, depth=pkg["depth"], monodepth=True)
-        # isotropic regulariser (:303-305), rank 0 only: fused kernel after the backward where it applies, else in the graph
-        fuse_iso = rank == 0 and fused and G.get_xyz.is_cuda and getattr(G, "standard_activations", False)
-        if rank == 0 and not fuse_iso:
-            loss_mapping = loss_mapping + _isotropic_term(G)
-        if torch.is_tensor(loss_mapping):
-            loss_mapping.backward()
-            loss_mapping = loss_mapping.detach()
-        if direct_losses:
-            loss_direct = direct_losses[0] if len(direct_losses) == 1 else torch.stack(direct_losses).sum()
-        if loss_direct is not None:
-            loss_mapping = loss_mapping + loss_direct
-        if fuse_iso:
-            iso = _isotropic_fused(G)
-            if iso is None:          # not the standard model after all: the autograd statement
-                iso = _isotropic_term(G)
-                iso.backward()
-            loss_mapping = loss_mapping + iso.detach()
-
-        with torch.no_grad():
-            N = G.get_xyz.shape[0]
-            dev = G.get_xyz.device
             if marks: marks.mark("views")
-            # ---- what this rank's pieces say, in order (pieces that went through MapViewPass have said it already) ----
-            for v, r0, pkg in pkgs:
-                vs.add(v, r0, pkg)
-            radii_max, norm_sum, vis_count, split_xy, flags = vs.radii_max, vs.norm_sum, vs.vis_count, vs.split_xy, vs.flags
-            # ---- the collectives (a pruning pass reduces the flags only, see below) ----
-            params = G.parameters()
+            # what this rank's pieces say, in order (pieces that went through MapViewPass have said it already)
+            for p, pkg in pkgs:
+                vs.add(p.view, p.row0, pkg)
             if marks: marks.mark("statistics")
-            # the two small MAX collectives first (on the auxiliary communicator when there is one): they are in flight while
-            # the float bucket is reduced
-            small_works = []
-            if world > 1:
-                small_group = aux_group if aux_group is not None else (getattr(backend, "shard_aux_group", None) or group)
-                (radii_red,), w_radii = reducer.max_ints([radii_max], dev, small_group, async_op=True)
-                small_works = [w for w in (w_radii, _max_bytes(flags, small_group, async_op=True)) if w is not None]
-            grad_share = None
-            if not prune and world > 1:
-                tensors = [p.grad for p in params] + [None] + [p.grad for p in kf_params] + [norm_sum, vis_count, split_xy,
-                           loss_mapping.detach().reshape(1).float() if torch.is_tensor(loss_mapping) else None]
-                sizes = [p.numel() for p in params] + [pad] + [p.numel() for p in kf_params] + [N, N, 2 * N * len(split), 1]
-                n_par = sum(p.numel() for p in params)
-                red = reducer.sum_floats(tensors, sizes, dev, group, scatter=sharder, scatter_len=(n_par + pad) if sharder is not None else 0)
-                grad_share = reducer.share
-                for p, g in zip(params, red):
-                    p.grad = None if sharder is not None else g.view_as(p)   # (sharded: no rank holds the whole reduced gradient)
-                for p, g in zip(kf_params, red[len(params) + 1:]):
-                    p.grad = g.view_as(p)
-                norm_sum, vis_count, split_xy = red[-4], red[-3], red[-2]
-                if stats is not None:
-                    stats.setdefault("losses", []).append(red[-1].clone())
-            elif stats is not None and torch.is_tensor(loss_mapping):
-                stats.setdefault("losses", []).append(loss_mapping.detach().reshape(1).float())
-            if world > 1:
-                for w in small_works:
-                    w.wait()
-                radii_max = radii_red
+            radii_max, norm_sum, vis_count, split_xy, grad_share = _reduce(c, params, layout, vs, loss, local=prune)
             if marks: marks.mark("collectives")
             if stats is not None:
-                stats.setdefault("iterations", []).append(dict(views=[v for v, _, _ in mine], pieces=list(mine), phases=marks))
-
-            # ---- bookkeeping of reference :309-389 on the reduced values ----
-            backend.occ_aware_visibility = {}
-            touched = flags[:n_window].long()   # one conversion for the window; the dict holds its rows
-            for idx in range(n_window):
-                backend.occ_aware_visibility[current_window[idx]] = touched[idx]
-
-            # Only prune on the last iteration and when we have full window (:318-348).  The reference returns from here
-            # without an optimizer step and without clearing the gradients, so (unless pruning replaces the parameters)
-            # they are still there when the next call's backward accumulates.  To keep that sum right across ranks
-            # the gradients of this pass stay LOCAL (unreduced): the next pass reduces old + new together.
+                stats.setdefault("iterations", []).append(dict(views=[p.view for p in mine], pieces=[(p.view, p.row0, p.row1) for p in mine], phases=marks))
+            # ---- the bookkeeping of reference :309-389 on the reduced values: first the occlusion-aware visibility ----
+            touched = vs.flags[:c.n_window].long()   # one conversion for the window; the dict holds its rows
+            backend.occ_aware_visibility = {kf: touched[idx] for idx, kf in enumerate(current_window)}
             if prune:
-                if sharder is not None:
-                    sharder.sync_moments(G.optimizer, G.parameters())   # pruning edits the moments per Gaussian
-                if n_window == cfg["Training"]["window_size"]:
-                    prune_mode = cfg["Training"]["prune_mode"]
-                    prune_coviz = cfg["Training"]["prune_num"]
-                    # (`n_obs += visibility.cpu()` per window keyframe: the same integer sums, made on the device and fetched once --
-                    # eight blocking copies fewer in a pass the free-running back end makes every ten iterations)
-                    rows = list(backend.occ_aware_visibility.values())
-                    summed = torch.stack(rows).sum(0) if all(r.is_cuda for r in rows) else sum(r.cpu() for r in rows)
-                    G.n_obs.copy_(summed.cpu().to(G.n_obs.dtype))
-                    to_prune = None
-                    if prune_mode == "odometry":
-                        to_prune = G.n_obs < 3
-                    if prune_mode == "slam":
-                        sorted_window = sorted(current_window, reverse=True)
-                        mask = G.unique_kfIDs >= sorted_window[2]
-                        if not backend.initialized:
-                            mask = G.unique_kfIDs >= 0
-                        to_prune = torch.logical_and(G.n_obs <= prune_coviz, mask)
-                    if to_prune is not None and backend.monocular:
-                        G.prune_points(to_prune.to(dev))
-                        # (the rows that stay, as indices found once: a boolean mask per keyframe is a device count the host waits for each time)
-                        keep_idx = torch.nonzero(~to_prune.to(dev)).squeeze(1)
-                        for idx in range(n_window):
-                            k = current_window[idx]
-                            backend.occ_aware_visibility[k] = backend.occ_aware_visibility[k].index_select(0, keep_idx.to(backend.occ_aware_visibility[k].device))
-                    if not backend.initialized:
-                        backend.initialized = True
+                _pruning_pass(c)
                 return False
-
-            vs.apply(G, radii_max, norm_sum, vis_count, split_xy)
-
-            update_gaussian = backend.iteration_count % backend.gaussian_update_every == backend.gaussian_update_offset
-            gaussian_split = False
-            resetting = (backend.iteration_count % backend.gaussian_reset) == 0 and (not update_gaussian)
-            if sharder is not None and (update_gaussian or resetting):
-                sharder.sync_moments(G.optimizer, G.parameters())   # densification / the reset edit the moments per Gaussian
-            if update_gaussian:
-                G.densify_and_prune(backend.opt_params.densify_grad_threshold, backend.gaussian_th, backend.gaussian_extent,
-                                    backend.size_threshold)
-                gaussian_split = True
-            if (backend.iteration_count % backend.gaussian_reset) == 0 and (not update_gaussian):
-                # seen by any view of the iteration: every view is counted by exactly one rank, a sum that reduces correctly
-                G.reset_opacity_nonvisible([vis_count > 0])
-                gaussian_split = True
-
+            gaussian_split = _bookkeeping(c, vs, radii_max, norm_sum, vis_count, split_xy)
             if stats is not None and callable(stats.get("before_steps")):
                 stats["before_steps"](backend)   # tests look at the (reduced) gradients here
             if marks: marks.mark("bookkeeping")
-            if sharder is not None and grad_share is not None:
-                # A parameter tensor the bookkeeping has just replaced carries no gradient, and torch's Adam passes over it
-                # (all of them after a densification -- the reference's iteration then steps nothing --, the opacities after the
-                # reset of the non-visible): the same here.
-                now = G.parameters()
-                replaced = {k for k, (a, b) in enumerate(zip(params, now)) if a is not b}
-                if len(now) == len(params) and all(a.numel() == b.numel() for a, b in zip(params, now)):
-                    sharder.step(G.optimizer, now, grad_share, skip=replaced)
-            else:
-                G.optimizer.step()
-            G.optimizer.zero_grad(set_to_none=True)
-            G.update_learning_rate(backend.iteration_count)
-            stepper = None
-            if backend.keyframe_optimizers is not None:
-                stepper = _keyframe_stepper(backend, viewpoint_stack, frames_to_optimize) if (fused and up_pose) else None
-                if stepper is not None:
-                    stepper.step()       # Adam + update_pose of every window keyframe, one launch each
-                else:
-                    stale = getattr(backend.keyframe_optimizers, "_lvdgs_stepper", None)
-                    if stale is not None:   # earlier iterations went through the stepper: hand its moments to torch's optimiser
-                        stale.export_to_optimizer()
-                        backend.keyframe_optimizers._lvdgs_stepper = None
-                    backend.keyframe_optimizers.step()
-                backend.keyframe_optimizers.zero_grad(set_to_none=True)
-            for v in views:   # exposure gradients of the random views are never stepped; do not let them pile up
-                for name in _POSE_FIELDS:
-                    p = getattr(v, name, None)
-                    if p is not None and p.grad is not None and not any(p is q for q in kf_params):
-                        p.grad = None
-            # Pose update (:383-389): every rank holds the same reduced gradients, so every rank moves every keyframe
-            if up_pose and stepper is None:
-                for cam_idx in range(min(frames_to_optimize, n_window)):
-                    viewpoint = viewpoint_stack[cam_idx]
-                    if viewpoint.uid == 0:
-                        continue
-                    update_pose(viewpoint)
+            _optimizer_steps(c, views, params, grad_share)
             if marks: marks.mark("optimizer_steps")
     # The moments leave this function whole on every rank: between calls the reference extends the map (extend_from_pcd_seq on
     # every keyframe, utils/slam_backend.py:75-78 -- the share boundaries move) and steps the optimiser outside this loop
@@ -1109,6 +920,247 @@ def _map_window(backend, current_window, prune, iters, up_pose, group, reducer, 
     return gaussian_split
 
 
+# Tile rows [row0, row1) of view ``view`` (viewpoint ``vp``) as dealt to this rank.  window: a window keyframe, not a random older view;
+# masked: a window keyframe with a static mask; masked_loss: ``masked_spec`` where the fused passes can compute that loss, else None
+_Piece = namedtuple("_Piece", "view vp row0 row1 whole window masked masked_loss")
+
+
+def _fused_can_score(p):
+    """The fused passes' admission rule (``MapWindowBatch`` and ``MapViewPass`` alike): a masked window keyframe needs its ``masked_loss``."""
+    return not p.masked or p.masked_loss is not None
+
+
+def _deal(c):
+    """Step 1.  The iteration's views -- the window's keyframes + two random older ones (:275) -- cut into pieces and dealt to the ranks.
+    -> (views, this rank's pieces, the views cut into bands).  Whole / window / masked / masked_loss are decided here, once."""
+    backend, n_window = c.backend, c.n_window
+    picks = random_view_indices(len(c.older_views), 2, backend.iteration_count, c.world, seed=getattr(backend, "shard_seed", 0))
+    views = c.window_views + [c.older_views[i] for i in picks]
+    # A window keyframe with a static mask -- under the reference's default configuration every one of them
+    # (utils/slam_frontend.py:1218,1429-1433) -- is scored by L1 + SSIM on the static pixels and the masked depth term (:196-261);
+    # every other view by get_loss_mapping (the random views always, whatever they carry)
+    masked = [i < n_window and getattr(v, "static_mask", None) is not None for i, v in enumerate(views)]
+    # a view renders in bands when its loss is a sum over pixels: get_loss_mapping, i.e. no static mask (L1 + SSIM and a
+    # count-normalised depth term are not); window views without MapViewPass take the _BandView route through autograd
+    # (a caller's own window loss splits only if the caller says so)
+    splittable = [i >= n_window or (c.bands_ok and not m) for i, m in enumerate(masked)]
+    rows = [_tile_rows(v) for v in views]
+    pieces = [(v, r0, r1, o, (r0, r1) == (0, rows[v])) for v, r0, r1, o in plan_pieces(rows, c.world, backend.iteration_count, splittable)]
+    split = sorted({v for v, _, _, _, whole in pieces if not whole})
+    fused_masked = lambda v: c.vpass is not None and MapViewPass.masked_loss_usable(views[v])
+    mine = [_Piece(v, views[v], r0, r1, whole, v < n_window, masked[v], c.masked_spec if masked[v] and fused_masked(v) else None)
+            for v, r0, r1, o, whole in pieces if o == c.rank]
+    return views, mine, split
+
+
+def _plan_bucket(c, params, split):
+    """-> (the float bucket's layout, ``first`` for the fused passes, the statistics' accumulators).  Several ranks: the first piece's
+    backward writes the parameter gradients straight into their slices of the float bucket the all-reduce works on (no packing
+    copy), and the statistics' float pieces live there too; one rank: no layout, no ``first``."""
+    G = c.G
+    N = G.get_xyz.shape[0]
+    layout = first = in_bucket = None
+    if c.world > 1:
+        pad = 0   # (sharded Adam: the parameter-gradient part of the bucket is a multiple of the world size)
+        if c.sharder is not None:
+            _, total_p, padded_p, _ = c.sharder.plan(params)
+            pad = padded_p - total_p
+        layout = FloatLayout(params, pad, c.kf_params, N, len(split))
+        planned = layout.pieces(c.reducer.plan_floats(layout.sizes, params[0].device))
+        in_bucket = (planned.norm_sum, planned.vis_count, planned.split_xy)
+        if c.vpass is not None:
+            first = {n: g.view_as(p) for n, p, g in zip(_PARAM_FIELDS, params, planned.params)}
+    with torch.no_grad():
+        vs = _ViewStats(N, c.n_window, G.get_xyz.device, split, in_bucket)
+    return layout, first, vs
+
+
+def _render_and_score(c, mine, first, vs):
+    """Step 2.  Render, score and differentiate this rank's pieces: -> ([(piece, render package)], loss), the gradients left where
+    autograd would have put them (or in ``first``, their slices of the float bucket)."""
+    backend, vpass = c.backend, c.vpass
+    pkgs = []
+    direct_losses = []   # of the pieces the fused passes took (values only; summed once: an addition per view is a launch per view)
+    # The WHOLE views of this rank (one GPU: the whole window; two GPUs: five views each; four: two each + bands; eight: one +
+    # a band) with every stage in one launch for all of them: forward chains, blend passes, static-mask losses
+    # (fast_mapping.MapWindowBatch -- a KITTI-size frame alone leaves the chip half empty; LVDGS_MAP_BATCH=0: view by view).
+    # The rank's bands, and whole views the batch cannot take, follow view by view and add to the batch's gradients.
+    together = []
+    if vpass is not None and os.environ.get("LVDGS_MAP_BATCH", "1") != "0":
+        together = [p for p in mine if p.whole and _fused_can_score(p)]
+        if not MapWindowBatch.usable(backend, [p.vp for p in together], [p.masked_loss for p in together]):
+            together = []
+    if together:
+        batch = getattr(backend, "_lvdgs_window_batch", None)
+        if batch is None or batch.passes[0] is not vpass:
+            batch = backend._lvdgs_window_batch = MapWindowBatch(vpass)
+        for p, (pkg, l) in zip(together, batch.run(backend, [p.vp for p in together], first=first,
+                                                    stats=[vs.targets(p.view, p.row0) for p in together],
+                                                    masked=[p.masked_loss for p in together])):
+            pkgs.append((p, pkg))
+            direct_losses.append(l)
+    loss = 0   # of the pieces that go through autograd (a graph)
+    for p in [p for p in mine if p not in together]:
+        if vpass is not None and _fused_can_score(p) and MapViewPass.usable(backend, p.vp, allow_static_mask=True):
+            # a window keyframe with a static mask: the static-mask loss (its colour-gradient image from the fused L1 + SSIM
+            # launch, the depth term's gradient inside the backward blend pass); every other view: get_loss_mapping inside
+            # the backward blend pass
+            pkg, l = vpass.run(backend, p.vp, first=first, band=None if p.whole else (p.row0, p.row1), masked_loss=p.masked_loss,
+                               stats=vs.targets(p.view, p.row0))
+            direct_losses.append(l)
+        else:
+            pkg = c.render_fn(p.vp, c.G, backend.pipeline_params, backend.background)
+            if not p.whole and not c.cfg["Training"]["rgb_boundary_threshold"] >= 0:
+                raise ValueError("a view in bands needs rgb_boundary_threshold >= 0: pixels outside the band are masked out by their zeroed target")
+            target = p.vp if p.whole else _BandView(p.vp, 16 * p.row0, min(16 * p.row1, int(p.vp.image_height)))
+            loss = loss + (c.view_loss_fn(backend, target, pkg) if p.window else
+                           get_loss_mapping(c.cfg, pkg["render"], target, depth=pkg["depth"], monodepth=True))
+        pkgs.append((p, pkg))
+    # the isotropic regulariser (:303-305), rank 0 only -- fused kernel after the backward where it applies, else in the graph --, the
+    # ONE backward of the graph part, and the rank's loss: graph part + the fused passes' values + the regulariser
+    G = c.G
+    fuse_iso = c.rank == 0 and c.fused and G.get_xyz.is_cuda and getattr(G, "standard_activations", False)
+    if c.rank == 0 and not fuse_iso:
+        loss = loss + _isotropic_term(G)
+    if torch.is_tensor(loss):
+        loss.backward()
+        loss = loss.detach()
+    if direct_losses:
+        loss = loss + (direct_losses[0] if len(direct_losses) == 1 else torch.stack(direct_losses).sum())
+    if fuse_iso:
+        iso = _isotropic_fused(G)
+        if iso is None:          # not the standard model after all: the autograd statement
+            iso = _isotropic_term(G)
+            iso.backward()
+        loss = loss + iso.detach()
+    return pkgs, loss
+
+
+def _reduce(c, params, layout, vs, loss, local):
+    """Step 3, the collectives: -> the reduced (radii_max, norm_sum, vis_count, split_xy, grad_share), the reduced gradients handed back
+    as the parameters' ``.grad``.  ``local`` (a pruning pass): the two MAX collectives only, see ``_pruning_pass``."""
+    stats, reducer, sharder, dev = c.stats, c.reducer, c.sharder, vs.dev
+    radii_max, norm_sum, vis_count, split_xy, grad_share = vs.radii_max, vs.norm_sum, vs.vis_count, vs.split_xy, None
+    # the two small MAX collectives first (on the auxiliary communicator when there is one): they are in flight while
+    # the float bucket is reduced
+    small_works = []
+    if c.world > 1:
+        (radii_max,), w_radii = reducer.max_ints([radii_max], dev, c.small_group, async_op=True)
+        small_works = [w for w in (w_radii, _max_bytes(vs.flags, c.small_group, async_op=True)) if w is not None]
+    if c.world > 1 and not local:
+        tensors = layout.tensors([p.grad for p in params], [p.grad for p in c.kf_params], norm_sum, vis_count, split_xy,
+                                 loss.detach().reshape(1).float() if torch.is_tensor(loss) else None)
+        red = layout.pieces(reducer.sum_floats(tensors, layout.sizes, dev, c.group, scatter=sharder, scatter_len=layout.scatter_len))
+        grad_share = reducer.share
+        for p, g in zip(params, red.params):
+            p.grad = None if sharder is not None else g.view_as(p)   # (sharded: no rank holds the whole reduced gradient)
+        for p, g in zip(c.kf_params, red.kf_params):
+            p.grad = g.view_as(p)
+        norm_sum, vis_count, split_xy = red.norm_sum, red.vis_count, red.split_xy
+        if stats is not None:
+            stats.setdefault("losses", []).append(red.loss.clone())
+    elif stats is not None and torch.is_tensor(loss):
+        stats.setdefault("losses", []).append(loss.detach().reshape(1).float())
+    for w in small_works:
+        w.wait()
+    return radii_max, norm_sum, vis_count, split_xy, grad_share
+
+
+def _pruning_pass(c):
+    """Only prune on the last iteration and when we have full window (:318-348).  The reference returns from here
+    without an optimizer step and without clearing the gradients, so (unless pruning replaces the parameters)
+    they are still there when the next call's backward accumulates.  To keep that sum right across ranks
+    the gradients of this pass stay LOCAL (unreduced): the next pass reduces old + new together."""
+    backend, G, cfg = c.backend, c.G, c.cfg
+    if c.sharder is not None:
+        c.sharder.sync_moments(G.optimizer, G.parameters())   # pruning edits the moments per Gaussian
+    if c.n_window != cfg["Training"]["window_size"]:
+        return
+    prune_mode = cfg["Training"]["prune_mode"]
+    prune_coviz = cfg["Training"]["prune_num"]
+    # (`n_obs += visibility.cpu()` per window keyframe: the same integer sums, made on the device and fetched once --
+    # eight blocking copies fewer in a pass the free-running back end makes every ten iterations)
+    rows = list(backend.occ_aware_visibility.values())
+    summed = torch.stack(rows).sum(0) if all(r.is_cuda for r in rows) else sum(r.cpu() for r in rows)
+    G.n_obs.copy_(summed.cpu().to(G.n_obs.dtype))
+    to_prune = None
+    if prune_mode == "odometry":
+        to_prune = G.n_obs < 3
+    if prune_mode == "slam":
+        sorted_window = sorted(c.window, reverse=True)
+        mask = G.unique_kfIDs >= sorted_window[2]
+        if not backend.initialized:
+            mask = G.unique_kfIDs >= 0
+        to_prune = torch.logical_and(G.n_obs <= prune_coviz, mask)
+    if to_prune is not None and backend.monocular:
+        dev = G.get_xyz.device
+        G.prune_points(to_prune.to(dev))
+        # (the rows that stay, as indices found once: a boolean mask per keyframe is a device count the host waits for each time)
+        keep_idx = torch.nonzero(~to_prune.to(dev)).squeeze(1)
+        for k in c.window:
+            backend.occ_aware_visibility[k] = backend.occ_aware_visibility[k].index_select(0, keep_idx.to(backend.occ_aware_visibility[k].device))
+    if not backend.initialized:
+        backend.initialized = True
+
+
+def _bookkeeping(c, vs, radii_max, norm_sum, vis_count, split_xy):
+    """Step 4 on the reduced values (:350-370): the densification statistics, densify / prune on its cadence, the opacity reset on
+    its own.  -> ``gaussian_split``."""
+    backend, G, sharder = c.backend, c.G, c.sharder
+    vs.apply(G, radii_max, norm_sum, vis_count, split_xy)
+    update_gaussian = backend.iteration_count % backend.gaussian_update_every == backend.gaussian_update_offset
+    resetting = (backend.iteration_count % backend.gaussian_reset) == 0 and (not update_gaussian)
+    if sharder is not None and (update_gaussian or resetting):
+        sharder.sync_moments(G.optimizer, G.parameters())   # densification / the reset edit the moments per Gaussian
+    if update_gaussian:
+        G.densify_and_prune(backend.opt_params.densify_grad_threshold, backend.gaussian_th, backend.gaussian_extent,
+                            backend.size_threshold)
+    if resetting:
+        # seen by any view of the iteration: every view is counted by exactly one rank, a sum that reduces correctly
+        G.reset_opacity_nonvisible([vis_count > 0])
+    return update_gaussian or resetting
+
+
+def _optimizer_steps(c, views, params, grad_share):
+    """Step 5 (:372-389): the Gaussian Adam (``params``: the parameter tensors the gradients were taken for), the learning rates, the
+    keyframes' Adam and ``update_pose``."""
+    backend, G, sharder = c.backend, c.G, c.sharder
+    if sharder is not None and grad_share is not None:
+        # A parameter tensor the bookkeeping has just replaced carries no gradient, and torch's Adam passes over it
+        # (all of them after a densification -- the reference's iteration then steps nothing --, the opacities after the
+        # reset of the non-visible): the same here.
+        now = G.parameters()
+        replaced = {k for k, (a, b) in enumerate(zip(params, now)) if a is not b}
+        if len(now) == len(params) and all(a.numel() == b.numel() for a, b in zip(params, now)):
+            sharder.step(G.optimizer, now, grad_share, skip=replaced)
+    else:
+        G.optimizer.step()
+    G.optimizer.zero_grad(set_to_none=True)
+    G.update_learning_rate(backend.iteration_count)
+    stepper = None
+    if backend.keyframe_optimizers is not None:
+        stepper = _keyframe_stepper(backend, c.window_views, c.pose_window) if (c.fused and c.up_pose) else None
+        if stepper is not None:
+            stepper.step()       # Adam + update_pose of every window keyframe, one launch each
+        else:
+            stale = getattr(backend.keyframe_optimizers, "_lvdgs_stepper", None)
+            if stale is not None:   # earlier iterations went through the stepper: hand its moments to torch's optimiser
+                stale.export_to_optimizer()
+                backend.keyframe_optimizers._lvdgs_stepper = None
+            backend.keyframe_optimizers.step()
+        backend.keyframe_optimizers.zero_grad(set_to_none=True)
+    for v in views:   # exposure gradients of the random views are never stepped; do not let them pile up
+        for name in _POSE_FIELDS:
+            p = getattr(v, name, None)
+            if p is not None and p.grad is not None and not any(p is q for q in c.kf_params):
+                p.grad = None
+    # Pose update (:383-389): every rank holds the same reduced gradients, so every rank moves every keyframe
+    if c.up_pose and stepper is None:
+        for viewpoint in c.window_views[:c.pose_window]:
+            if viewpoint.uid != 0:
+                update_pose(viewpoint)
+
+
 def _view_pass(backend):
     """The back end's MapViewPass (its buffers live as long as the back end); None off the GPU."""
     dev = backend.gaussians.get_xyz.device
@@ -1116,11 +1168,7 @@ def _view_pass(backend):
         return None
     vp = getattr(backend, "_lvdgs_view_pass", None)
     if vp is None or vp.dev != dev:
-        vp = MapViewPass(dev)
-        try:
-            backend._lvdgs_view_pass = vp
-        except Exception:
-            pass
+        vp = _remember(backend, "_lvdgs_view_pass", MapViewPass(dev))
     return vp
 
 

@@ -47,6 +47,16 @@ _PARAM_FIELDS = ("_xyz", "_features_dc", "_features_rest", "_scaling", "_rotatio
 _VIEW_FIELDS = ("cam_rot_delta", "cam_trans_delta", "exposure_a", "exposure_b")
 
 
+def _remember(backend, name, value):
+    """Keep ``value`` on the back end for the next call if it lets us (a caller's class may refuse new attributes: then it is made
+    again next time); returns ``value``."""
+    try:
+        setattr(backend, name, value)
+    except Exception:   # noqa: BLE001
+        pass
+    return value
+
+
 class MapViewPass:
     """Buffers and argument blocks for render + ``get_loss_mapping`` + backward of one view; re-pointed at every call
     (the model's tensors are replaced by densification, the viewpoint changes from call to call).
@@ -409,7 +419,7 @@ class MapWindowBatch:
         dev = G.get_xyz.device
         (h, w), = size
         batch = getattr(backend, "_lvdgs_window_batch", None)
-        cap = max((int(getattr(p, "cap", 0) or 0) for p in batch.passes), default=0) if batch is not None else 0
+        cap = batch.pair_capacity if batch is not None else 0
         key = (int(G._xyz.shape[0]), w, h, len(viewpoints), tuple(m is not None for m in masked), cap, dev)
         kept = getattr(backend, "_lvdgs_batch_fits", None)
         if kept is not None and kept[0] == key:
@@ -419,11 +429,13 @@ class MapWindowBatch:
         cached = torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)   # (what the caching allocator can hand out again)
         held = getattr(batch, "bytes_held", 0) if batch is not None else 0
         fits = need - held <= MEMORY_FRACTION * (free + cached)
-        try:
-            backend._lvdgs_batch_fits = (key, fits)
-        except Exception:
-            pass
+        _remember(backend, "_lvdgs_batch_fits", (key, fits))
         return fits
+
+    @property
+    def pair_capacity(self):
+        """The pair capacity the passes have grown to (the largest of them)."""
+        return max((int(getattr(p, "cap", 0) or 0) for p in self.passes), default=0)
 
     @staticmethod
     def bytes_per_view(N, W, H, cap=None):
@@ -443,7 +455,7 @@ class MapWindowBatch:
         G = backend.gaussians
         self.runs = getattr(self, "runs", 0) + 1
         self.bytes_held = self.bytes_per_view(int(G._xyz.shape[0]), int(viewpoints[0].image_width), int(viewpoints[0].image_height),
-                                              max((int(getattr(p, "cap", 0) or 0) for p in self.passes), default=0)) * len(self.passes)
+                                              self.pair_capacity) * len(self.passes)
         n = len(viewpoints)
         masked = masked or [None] * n
         with _lib.on_device(dev):

@@ -123,3 +123,30 @@ def build_scene(device="cpu", camera_cls=None, n_cameras=N_CAMERAS, window=None)
     return dict(gaussians=model, cameras=cameras, track_camera=track_camera, track_mono_depth=cams[N_CAMERAS][1],
                 background=bg.to(device), pipe=pipe, window=list(WINDOW if window is None else window), map_iters=MAP_ITERS,
                 make_keyframe_optimizer=make_keyframe_optimizer, opt=dict(OPT))
+
+
+def backend_namespace(sc, cfg):
+    """A BackEnd-shaped namespace: the attributes reference utils/slam_backend.py:21-72 sets."""
+    T = cfg["Training"]
+    be = SimpleNamespace(
+        config=cfg, gaussians=sc["gaussians"], pipeline_params=sc["pipe"], background=sc["background"],
+        opt_params=SimpleNamespace(**cfg["opt_params"]), monocular=T["monocular"], iteration_count=0, last_sent=0,
+        occ_aware_visibility={}, viewpoints={}, current_window=[], initialized=not T["monocular"], keyframe_optimizers=None,
+        cameras_extent=6.0, init_itr_num=T["init_itr_num"], init_gaussian_update=T["init_gaussian_update"],
+        init_gaussian_reset=T["init_gaussian_reset"], init_gaussian_th=T["init_gaussian_th"],
+        init_gaussian_extent=6.0 * T["init_gaussian_extent"], gaussian_update_every=T["gaussian_update_every"],
+        gaussian_update_offset=T["gaussian_update_offset"], gaussian_th=T["gaussian_th"], gaussian_extent=6.0 * T["gaussian_extent"],
+        gaussian_reset=T["gaussian_reset"], size_threshold=T["size_threshold"], window_size=T["window_size"])
+    return be
+
+
+def cpu_view_loss(backend, viewpoint, pkg):
+    """The window keyframe's loss with the float64 statements of oracle/loss_oracle.py where the product uses its fused
+    HIP kernels (which have no CPU path): reference utils/slam_backend.py:196-266."""
+    import loss_oracle as lo
+    from lvdgs.slam_utils import get_loss_mapping
+    if getattr(viewpoint, "static_mask", None) is not None:
+        return lo.masked_mapping_loss(pkg["render"], pkg["depth"], viewpoint.original_image, torch.from_numpy(viewpoint.mono_depth),
+                                      viewpoint.static_mask, backend.background, backend.opt_params.lambda_dssim,
+                                      backend.config["Training"].get("depth_lambda", 0.1)).to(pkg["render"].dtype)
+    return get_loss_mapping(backend.config, pkg["render"], viewpoint, depth=pkg["depth"], monodepth=True)
