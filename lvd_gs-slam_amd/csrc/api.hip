@@ -646,7 +646,7 @@ static int check_backward(const lvdgs_args *a, BackwardKind kind, BackwardViews 
     if ((kind == BackwardKind::pixel_gradients && !a->dL_dout_color) || !a->projmatrix_raw || !a->radii) { set_error("a required backward pointer is NULL"); return LVDGS_E_INVALID; }
     if (kind == BackwardKind::masked_loss && pose_only) { set_error("LVDGS_FLAG_POSE_ONLY: the static-mask mapping loss is a mapping loss, its backward makes every gradient"); return LVDGS_E_INVALID; }
     if (pose_only) {
-        // a view-dependent colour moves with the camera centre: its gradient feeds dL/dtau (preprocess.hip), and the
+        // a view-dependent colour moves with the camera centre: its gradient feeds dL/dtau (preprocess_bwd.hip: chain_colour), and the
         // pose-only passes do not make it
         if (a->shs && a->sh_degree > 0) { set_error("LVDGS_FLAG_POSE_ONLY needs sh_degree 0 or colors_precomp"); return LVDGS_E_INVALID; }
         if (a->flags & LVDGS_FLAG_ACCUMULATE_PARAM_GRADS) { set_error("LVDGS_FLAG_POSE_ONLY writes no parameter gradients: nothing to accumulate"); return LVDGS_E_INVALID; }

@@ -4,7 +4,7 @@ gradient must be the SAME BITS with and without it -- on opaque surfaces (where 
 whose size is no multiple of the super-tile, on rectangles of more than 64 tiles and of more than 64 super-tiles, when the pair
 capacity overflows, through the autograd API, the tracking session and the mapping window.
 
-In the backward the same flag selects preprocess_bwd's helper-wave kernels (csrc/preprocess.hip: the second half of a large-footprint wave's
+In the backward the same flag selects preprocess_bwd's helper-wave kernels (csrc/preprocess_bwd.hip: the second half of a large-footprint wave's
 pair records summed by a wave of its own): the gradient comparisons below are also "helper waves == one wave, part after part"."""
 import os
 import sys
