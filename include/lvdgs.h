@@ -645,6 +645,51 @@ typedef struct lvdgs_pnp_args {
 size_t lvdgs_pnp_scratch_bytes(int32_t num_matches, int32_t hypotheses);
 int lvdgs_pnp_ransac(const lvdgs_pnp_args *a, void *stream);
 
+/* ---- matching two descriptor maps by reciprocal nearest neighbours (what the reference's get_pose calls first:
+ * fast_reciprocal_NNs(desc1, desc2, subsample_or_initxy1=8, dist='dot') over MASt3R descriptors; the network itself is out of scope) ----
+ * desc1: (height1, width1, dim), desc2: (height2, width2, dim), float32, contiguous.  The score of a pair is the float32 dot product,
+ * summed in ascending component order by one fmaf chain from zero -- the same arithmetic for every row of a map, so bit-identical rows
+ * score bit-identically.  Flat index of a pixel: x + width * y.  arg-max ties go to the LOWEST flat index.
+ * Seeds.  The grid y = S/2, S/2 + S, ... < height1, x = S/2, S/2 + S, ... < width1 (S = subsample, integer division), row-major: seed
+ *   k starts at xy1 = its flat index, xy2 = -1, old1 = xy1, old2 = -1, active.
+ * One round, active seeds only: (1) xy2 <- argmax_j <desc1[xy1], desc2[j]>; (2) xy2 == old2: the seed becomes inactive;
+ *   (3) still active: xy1 <- argmax_i <desc2[xy2], desc1[i]>; (4) xy1 == old1: inactive; (5) old2 <- xy2, old1 <- xy1.
+ * Rounds run until no seed is active, at most max_iter of them.  A seed still active then is UNCONVERGED and dropped.  A seed's
+ * trajectory depends on no other seed.
+ * Output.  The distinct pairs (xy1, xy2) of the inactive seeds, ascending by xy1, then xy2, as pixels: matches_im1 (M, 2) int32 (x, y)
+ *   in map 1, matches_im2 (M, 2) float32 (x, y) in map 2 -- what lvdgs_pnp_ransac takes.  Both need room for `capacity` >= seeds pairs.
+ *   seed_state (optional, may be NULL): 3 int32 per seed -- its final xy1, xy2 and 1 (inactive: it contributed its pair) / 0 (unconverged).
+ * Every index written lies inside its map whatever the descriptors hold; with non-finite descriptors the result is otherwise unspecified.
+ * Two calls on the same inputs give the same bytes.
+ * 2 + 4 max_iter launches, enqueued at once; no host wait (the active set lives on the device; a search launch without active seeds
+ * does nothing).  host_state: LVDGS_RNN_STATE_WORDS int32 words of page-locked, mapped host memory (the host address): [0] status
+ * (LVDGS_RNN_OK once the call has run), [1] seeds, [2] matches M, [3] unconverged seeds, [4] rounds that had an active seed, [5..7] zero.
+ * scratch: lvdgs_recip_nn_scratch_bytes(...) bytes, no initialisation needed.
+ * LVDGS_E_INVALID: args NULL, a NULL pointer, a size not > 0, a map of more than 2^31 - 1 floats, dim outside 1..LVDGS_RNN_MAX_DIM,
+ * subsample < 1, max_iter < 1, more than LVDGS_RNN_MAX_SEEDS seeds, capacity below the seed count, scratch too small;
+ * LVDGS_E_HIP: host_state is not mapped pinned memory. */
+#define LVDGS_RNN_MAX_DIM 64
+#define LVDGS_RNN_MAX_SEEDS 8192
+#define LVDGS_RNN_STATE_WORDS 8
+enum {
+    LVDGS_RNN_OK = 1
+};
+typedef struct lvdgs_recip_nn_args {
+    int32_t width1, height1, width2, height2;
+    int32_t dim, subsample, max_iter;
+    int32_t capacity;             /* pairs matches_im1 / matches_im2 have room for (>= seeds) */
+    const float *desc1;           /* height1*width1*dim                             */
+    const float *desc2;           /* height2*width2*dim                             */
+    int32_t *matches_im1;         /* out capacity*2 (x, y) in map 1                 */
+    float *matches_im2;           /* out capacity*2 (x, y) in map 2                 */
+    int32_t *seed_state;          /* out seeds*3 (xy1, xy2, converged), or NULL     */
+    int32_t *host_state;          /* LVDGS_RNN_STATE_WORDS, pinned host (the host address) */
+    void *scratch; size_t scratch_bytes;
+} lvdgs_recip_nn_args;
+/* the scratch a call with this seed grid needs (0 when an argument is not > 0) */
+size_t lvdgs_recip_nn_scratch_bytes(int32_t width1, int32_t height1, int32_t subsample);
+int lvdgs_reciprocal_nn(const lvdgs_recip_nn_args *a, void *stream);
+
 /* ---- diagnostics ---- */
 const char *lvdgs_last_error(void);
 const char *lvdgs_version(void);

@@ -147,6 +147,20 @@ PNP_OK, PNP_FAILED = 1, 2
 PNP_FAIL_NONE, PNP_FAIL_FEW_VALID, PNP_FAIL_ALL_VOID, PNP_FAIL_FEW_INLIERS, PNP_FAIL_SINGULAR = 0, 1, 2, 3, 4
 
 
+class RecipNnArgs(C.Structure):
+    """struct lvdgs_recip_nn_args (include/lvdgs.h)."""
+    _fields_ = [
+        ("width1", C.c_int32), ("height1", C.c_int32), ("width2", C.c_int32), ("height2", C.c_int32),
+        ("dim", C.c_int32), ("subsample", C.c_int32), ("max_iter", C.c_int32), ("capacity", C.c_int32),
+        ("desc1", _fp), ("desc2", _fp), ("matches_im1", _fp), ("matches_im2", _fp), ("seed_state", _fp), ("host_state", _fp),
+        ("scratch", _fp), ("scratch_bytes", C.c_size_t),
+    ]
+
+
+RNN_MAX_DIM, RNN_MAX_SEEDS, RNN_STATE_WORDS = 64, 8192, 8
+RNN_OK = 1
+
+
 class StateLayout(C.Structure):
     _fields_ = [(n, C.c_size_t) for n in (
         "geom_rec", "geom_tiles_touched", "geom_slot_base", "bin_point_list", "bin_tile_keys",
@@ -167,7 +181,8 @@ EXPORTS = (
     "lvdgs_photometric_loss_backward", "lvdgs_photometric_loss_value_and_grad", "lvdgs_photometric_loss_partials", "lvdgs_tracking_tail", "lvdgs_backward_fused_loss", "lvdgs_blend_forward_batch", "lvdgs_blend_backward_fused_loss_batch", "lvdgs_masked_depth_scratch_bytes", "lvdgs_masked_depth_l1_forward",
     "lvdgs_masked_depth_l1_backward", "lvdgs_pose_step", "lvdgs_host_device_pointer", "lvdgs_pose_step_batch", "lvdgs_adam_step", "lvdgs_isotropic_scratch_bytes", "lvdgs_isotropic_reg", "lvdgs_view_stats", "lvdgs_map_stats_apply", "lvdgs_map_view_tail", "lvdgs_ssim_scratch_bytes", "lvdgs_ssim_l1",
     "lvdgs_masked_loss_scratch_bytes", "lvdgs_masked_loss_batch", "lvdgs_backward_masked_loss", "lvdgs_blend_backward_window_batch", "lvdgs_forward_batch", "lvdgs_forward_backward_fused_loss", "lvdgs_map_view_tail_batch", "lvdgs_gaussian_backward_batch",
-    "lvdgs_depth_align_scratch_bytes", "lvdgs_depth_align", "lvdgs_depth_align_resume", "lvdgs_pnp_scratch_bytes", "lvdgs_pnp_ransac", "lvdgs_last_error", "lvdgs_version", "lvdgs_profile_enable",
+    "lvdgs_depth_align_scratch_bytes", "lvdgs_depth_align", "lvdgs_depth_align_resume", "lvdgs_pnp_scratch_bytes", "lvdgs_pnp_ransac", "lvdgs_recip_nn_scratch_bytes", "lvdgs_reciprocal_nn",
+    "lvdgs_last_error", "lvdgs_version", "lvdgs_profile_enable",
     "lvdgs_profile_reset", "lvdgs_profile_read",
 )
 
@@ -257,6 +272,9 @@ def lib():
         L.lvdgs_pnp_scratch_bytes.restype = C.c_size_t
         L.lvdgs_pnp_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
         L.lvdgs_pnp_ransac.argtypes = [C.POINTER(PnpArgs), C.c_void_p]
+        L.lvdgs_recip_nn_scratch_bytes.restype = C.c_size_t
+        L.lvdgs_recip_nn_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+        L.lvdgs_reciprocal_nn.argtypes = [C.POINTER(RecipNnArgs), C.c_void_p]
         L.lvdgs_profile_enable.argtypes = [C.c_int]
         L.lvdgs_profile_read.argtypes = [C.POINTER(KernelTime), C.c_int]
         _lib = L

@@ -1,0 +1,387 @@
+// Matching two descriptor maps by reciprocal nearest neighbours (the reference's get_pose starts with fast_reciprocal_NNs(desc1, desc2,
+// subsample_or_initxy1=8, dist='dot'): blocks of A @ B.T + max on the device and a device-to-host copy after every half round).
+// Semantics: include/lvdgs.h, DESIGN.md section 4d.
+//
+// 2 + 4 max_iter launches per call, all enqueued at once:
+//   rnn_init_kernel   : the seed grid, every seed active, the merge keys cleared.
+//   rnn_search_kernel : one half round's arg-max as a tall-skinny GEMM with an arg-max epilogue.  A workgroup holds 128 active queries
+//                       (4 tiles of 32) in LDS and streams a chunk of the database map past them: each of its four waves takes
+//                       RNN_WAVE_TILES tiles of 32 database rows, and a 32 x 32 tile of scores is dim / 2 v_mfma_f32_32x32x2_f32 -- exact
+//                       f32, bitwise one fmaf chain over the components in ascending order, the same for every row whatever its place in
+//                       a tile.  The database rows are the A operand, so a lane keeps ONE query (its column) and sixteen database rows
+//                       (its registers): the running arg-max is per lane, in registers, strict > in ascending row order.  Lanes, waves
+//                       and workgroups are then merged by a 64-bit max over (order-preserving score bits, complemented index): the order
+//                       of the merge cannot matter, the lowest index wins a tie.  Workgroups beyond the active count return at once.
+//   rnn_update_kernel : one workgroup.  Decodes the winners, retires the seeds that repeat themselves, compacts the active list (stable:
+//                       ascending seed order) and leaves its length for the next search.
+//   rnn_final_kernel  : one workgroup.  Bitonic sort of the retired seeds' (xy1, xy2) keys in LDS, distinct, pixel coordinates, the state
+//                       words through pinned memory.
+// No workgroup waits on another; every loop is bounded.
+#include <math.h>
+
+#include "common.hpp"
+
+namespace lvdgs {
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned long long u64;
+
+constexpr int RNN_THREADS = 256;
+constexpr int RNN_WAVES = RNN_THREADS / WAVE;
+constexpr int RNN_TILE = 32;                         // the MFMA's tile edge
+constexpr int RNN_QT = 4;                            // query tiles per workgroup
+constexpr int RNN_QGROUP = RNN_QT * RNN_TILE;        // queries per workgroup
+constexpr int RNN_QSTRIDE = RNN_QGROUP + 32;         // floats between two components in LDS: the two lane halves hit different banks
+constexpr int RNN_WAVE_TILES = 4;                    // database tiles per wave
+constexpr int RNN_KS_MAX = LVDGS_RNN_MAX_DIM / 2;
+constexpr int RNN_ONE = 1024;                        // threads of the single-workgroup kernels
+constexpr int RNN_ONE_WAVES = RNN_ONE / WAVE;
+constexpr u64 RNN_DROPPED = ~0ull;                   // sort key of an unconverged seed (a map index is below 2^31)
+
+struct RnnHeader {
+    uint32_t nact[2];     // length of the active list a half round reads: [half & 1]
+    uint32_t rounds;      // rounds that began with an active seed
+    uint32_t pad[61];
+};
+
+struct RnnParams {
+    int W1, H1, W2, H2, D, S, seeds, seeds_x, capacity;
+    const float *desc1, *desc2;
+    int32_t *m1;
+    float *m2;
+    int32_t *seed_state;
+    RnnHeader *hdr;
+    int32_t *xy1, *xy2, *old1, *old2, *retired;   // per seed
+    uint32_t *act[2];                             // the active seeds, ascending; a half round reads [half & 1] and writes the other
+    u64 *keys;                                    // per seed: the merge key of the search in flight (0 between searches)
+    int32_t *host_state;                          // device address of the caller's pinned block
+};
+
+__device__ __forceinline__ uint32_t ordered_bits(float f) {   // a < b  <=>  ordered_bits(a) < ordered_bits(b), for all non-NaN floats
+    const uint32_t b = __float_as_uint(f);
+    return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
+}
+
+__global__ void __launch_bounds__(RNN_THREADS) rnn_init_kernel(RnnParams P) {
+    const int k = blockIdx.x * RNN_THREADS + threadIdx.x;
+    if (k == 0) { P.hdr->nact[0] = (uint32_t)P.seeds; P.hdr->nact[1] = 0; P.hdr->rounds = 0; }
+    if (k >= P.seeds) return;
+    const int gy = k / P.seeds_x, gx = k - gy * P.seeds_x;
+    const int xy = (P.S / 2 + gx * P.S) + P.W1 * (P.S / 2 + gy * P.S);
+    P.xy1[k] = xy; P.old1[k] = xy; P.xy2[k] = -1; P.old2[k] = -1; P.retired[k] = 0;
+    P.act[0][k] = (uint32_t)k;
+    P.keys[k] = 0;
+}
+
+// the running arg-max of one lane over the sixteen rows of a score tile it holds: row_base + (r & 3) + 8 (r >> 2), ascending in r
+template <bool TAIL>
+__device__ __forceinline__ void tile_argmax(const f32x16 &acc, int row_base, int N, float &best, int &bidx) {
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int row = row_base + (r & 3) + 8 * (r >> 2);
+        const float v = acc[r];
+        bool gt = v > best;
+        if (TAIL) gt = gt && row < N;
+        best = gt ? v : best;
+        bidx = gt ? row : bidx;
+    }
+}
+
+// KS_T: dim / 2 rounded up when the launcher has a build for it (the database fragment of a tile is then loaded at once), 0: any dim
+template <int KS_T>
+__global__ void __launch_bounds__(RNN_THREADS) rnn_search_kernel(RnnParams P, int half) {
+    __shared__ float s_q[2 * RNN_KS_MAX * RNN_QSTRIDE];   // [component][query]
+    __shared__ int s_row[RNN_QGROUP];
+    __shared__ u64 s_keys[RNN_WAVES][RNN_QGROUP];
+    const int dir = half & 1;
+    const int nact = (int)P.hdr->nact[dir];
+    const int q0 = blockIdx.y * RNN_QGROUP;
+    if (q0 >= nact) return;                                // (uniform: before any barrier)
+    const int nq = min(RNN_QGROUP, nact - q0), nqt = (nq + RNN_TILE - 1) / RNN_TILE;
+    const uint32_t *act = P.act[dir];
+    const float *qmap = dir ? P.desc2 : P.desc1, *db = dir ? P.desc1 : P.desc2;
+    const int32_t *qrow = dir ? P.xy2 : P.xy1;
+    const int N = dir ? P.W1 * P.H1 : P.W2 * P.H2, Nq = dir ? P.W2 * P.H2 : P.W1 * P.H1;
+    const int D = P.D, KS = KS_T > 0 ? KS_T : (D + 1) / 2, Dpad = 2 * KS;
+    const int tid = threadIdx.x, lane = tid % WAVE, wave = tid / WAVE, j = lane % RNN_TILE, h = lane / RNN_TILE;
+
+    if (tid < RNN_QGROUP) s_row[tid] = tid < nq ? min(max(qrow[act[q0 + tid]], 0), Nq - 1) : -1;
+    __syncthreads();
+    for (int e = tid; e < RNN_QGROUP * Dpad; e += RNN_THREADS) {
+        const int q = e / Dpad, k = e - q * Dpad, row = s_row[q];
+        s_q[k * RNN_QSTRIDE + q] = (row >= 0 && k < D) ? qmap[(size_t)row * D + k] : 0.f;
+    }
+    __syncthreads();
+
+    const int ntiles = (N + RNN_TILE - 1) / RNN_TILE;
+    const int t0 = (blockIdx.x * RNN_WAVES + wave) * RNN_WAVE_TILES, t1 = min(t0 + RNN_WAVE_TILES, ntiles);
+    float best[RNN_QT];
+    int bidx[RNN_QT];
+#pragma unroll
+    for (int qt = 0; qt < RNN_QT; qt++) { best[qt] = -INFINITY; bidx[qt] = min(t0 * RNN_TILE, N - 1); }
+    const float *sq = s_q + j;
+    for (int t = t0; t < t1; t++) {
+        const int r0 = t * RNN_TILE;
+        const float *p = db + (size_t)min(r0 + j, N - 1) * D;    // a row past the map reads the last one; its scores are masked below
+        f32x16 acc[RNN_QT];
+#pragma unroll
+        for (int qt = 0; qt < RNN_QT; qt++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[qt][r] = 0.f;
+        if (KS_T > 0) {
+            float a[KS_T > 0 ? KS_T : 1];
+#pragma unroll
+            for (int s = 0; s < KS_T; s++) {
+                const int k = 2 * s + h;
+                a[s] = p[min(k, D - 1)];
+                a[s] = k < D ? a[s] : 0.f;
+            }
+#pragma unroll
+            for (int s = 0; s < KS_T; s++) {
+                const float *b = sq + (2 * s + h) * RNN_QSTRIDE;
+#pragma unroll
+                for (int qt = 0; qt < RNN_QT; qt++)
+                    if (qt < nqt) acc[qt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], b[qt * RNN_TILE], acc[qt], 0, 0, 0);
+            }
+        } else {
+            float a = p[min(h, D - 1)];
+            a = h < D ? a : 0.f;
+            for (int s = 0; s < KS; s++) {
+                const int kn = 2 * (s + 1) + h;
+                float an = p[min(kn, D - 1)];                    // the next step's component, in flight under this step's products
+                an = kn < D ? an : 0.f;
+                const float *b = sq + (2 * s + h) * RNN_QSTRIDE;
+#pragma unroll
+                for (int qt = 0; qt < RNN_QT; qt++)
+                    if (qt < nqt) acc[qt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b[qt * RNN_TILE], acc[qt], 0, 0, 0);
+                a = an;
+            }
+        }
+        if (r0 + RNN_TILE > N) {
+#pragma unroll
+            for (int qt = 0; qt < RNN_QT; qt++)
+                if (qt < nqt) tile_argmax<true>(acc[qt], r0 + 4 * h, N, best[qt], bidx[qt]);
+        } else {
+#pragma unroll
+            for (int qt = 0; qt < RNN_QT; qt++)
+                if (qt < nqt) tile_argmax<false>(acc[qt], r0 + 4 * h, N, best[qt], bidx[qt]);
+        }
+    }
+    // ---- the merge: lane halves, waves, workgroups ----
+#pragma unroll
+    for (int qt = 0; qt < RNN_QT; qt++) {
+        u64 key = t0 < t1 ? ((u64)ordered_bits(best[qt]) << 32) | (u64)(~(uint32_t)bidx[qt]) : 0ull;
+        const u64 other = ((u64)(uint32_t)__shfl_xor((int)(key >> 32), RNN_TILE, WAVE) << 32) | (u64)(uint32_t)__shfl_xor((int)(uint32_t)key, RNN_TILE, WAVE);
+        key = other > key ? other : key;
+        if (h == 0) s_keys[wave][qt * RNN_TILE + j] = key;
+    }
+    __syncthreads();
+    if (tid < nq) {
+        u64 key = s_keys[0][tid];
+#pragma unroll
+        for (int w = 1; w < RNN_WAVES; w++) key = s_keys[w][tid] > key ? s_keys[w][tid] : key;
+        u64 *dst = P.keys + act[q0 + tid];
+        // (the plain look first spares most of the atomics: a key that cannot raise the maximum changes nothing)
+        if (key > __hip_atomic_load(dst, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+            __hip_atomic_fetch_max(dst, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// exclusive prefix of v over the RNN_ONE threads of the workgroup; *total: the sum, the same in every thread (two barriers)
+__device__ __forceinline__ int block_exclusive_scan(int v, int *sh, int *total) {
+    const int lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE;
+    int inc = v;
+#pragma unroll
+    for (int o = 1; o < WAVE; o <<= 1) {
+        const int n = __shfl_up(inc, o, WAVE);
+        if (lane >= o) inc += n;
+    }
+    __syncthreads();
+    if (lane == WAVE - 1) sh[wave] = inc;
+    __syncthreads();
+    int before = 0, sum = 0;
+    for (int w = 0; w < RNN_ONE_WAVES; w++) {
+        const int s = sh[w];
+        before += w < wave ? s : 0;
+        sum += s;
+    }
+    *total = sum;
+    return before + inc - v;
+}
+
+__global__ void __launch_bounds__(RNN_ONE) rnn_update_kernel(RnnParams P, int half) {
+    __shared__ int s_scan[RNN_ONE_WAVES];
+    const int dir = half & 1, tid = threadIdx.x;
+    const int nact = (int)P.hdr->nact[dir];
+    const uint32_t *src = P.act[dir];
+    uint32_t *dst = P.act[dir ^ 1];
+    const int N = dir ? P.W1 * P.H1 : P.W2 * P.H2;
+    const int per = (nact + RNN_ONE - 1) / RNN_ONE, lo = min(tid * per, nact), hi = min(lo + per, nact);
+    int cnt = 0;
+    for (int a = lo; a < hi; a++) {
+        const uint32_t seed = src[a];
+        const u64 key = P.keys[seed];
+        P.keys[seed] = 0;
+        const int idx = (int)min(~(uint32_t)key, (uint32_t)(N - 1));
+        bool still;
+        if (dir == 0) {
+            P.xy2[seed] = idx;
+            still = idx != P.old2[seed];
+        } else {
+            P.xy1[seed] = idx;
+            still = idx != P.old1[seed];
+            P.old1[seed] = idx; P.old2[seed] = P.xy2[seed];
+        }
+        if (!still) P.retired[seed] = 1;
+        cnt += still ? 1 : 0;
+    }
+    int total;
+    int out = block_exclusive_scan(cnt, s_scan, &total);
+    for (int a = lo; a < hi; a++) {
+        const uint32_t seed = src[a];
+        if (!P.retired[seed]) dst[out++] = seed;   // (this thread's own writes)
+    }
+    if (tid == 0) {
+        P.hdr->nact[dir ^ 1] = (uint32_t)total;
+        if (dir == 0 && nact > 0) P.hdr->rounds = (uint32_t)(half / 2 + 1);
+    }
+}
+
+__global__ void __launch_bounds__(RNN_ONE) rnn_final_kernel(RnnParams P, int n2) {
+    extern __shared__ u64 s_key[];   // n2: a power of two >= 2 RNN_ONE and >= seeds
+    __shared__ int s_scan[RNN_ONE_WAVES];
+    const int tid = threadIdx.x;
+    int kept = 0;
+    for (int i = tid; i < n2; i += RNN_ONE) {
+        u64 key = RNN_DROPPED;
+        if (i < P.seeds) {
+            const int a = P.xy1[i], b = P.xy2[i], r = P.retired[i];
+            if (r) key = ((u64)(uint32_t)a << 32) | (u64)(uint32_t)b;
+            kept += r ? 1 : 0;
+            if (P.seed_state) { P.seed_state[3 * i] = a; P.seed_state[3 * i + 1] = b; P.seed_state[3 * i + 2] = r ? 1 : 0; }
+        }
+        s_key[i] = key;
+    }
+    int retired;
+    block_exclusive_scan(kept, s_scan, &retired);   // (its barriers also publish s_key)
+    for (int k = 2; k <= n2; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < n2; i += RNN_ONE) {
+                const int o = i ^ j;
+                if (o > i) {
+                    const u64 x = s_key[i], y = s_key[o];
+                    if ((x > y) == ((i & k) == 0)) { s_key[i] = y; s_key[o] = x; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    const int per = n2 / RNN_ONE, lo = tid * per;
+    int cnt = 0;
+    for (int i = lo; i < lo + per; i++) cnt += (s_key[i] != RNN_DROPPED && (i == 0 || s_key[i] != s_key[i - 1])) ? 1 : 0;
+    int M;
+    int out = block_exclusive_scan(cnt, s_scan, &M);
+    for (int i = lo; i < lo + per; i++) {
+        const u64 key = s_key[i];
+        if (key != RNN_DROPPED && (i == 0 || key != s_key[i - 1]) && out < P.capacity) {
+            const int a = (int)(key >> 32), b = (int)(uint32_t)key;
+            P.m1[2 * out] = a % P.W1; P.m1[2 * out + 1] = a / P.W1;
+            P.m2[2 * out] = (float)(b % P.W2); P.m2[2 * out + 1] = (float)(b / P.W2);
+            out++;
+        }
+    }
+    if (tid == 0) {
+        int32_t *w = P.host_state;
+        w[1] = P.seeds; w[2] = M; w[3] = P.seeds - retired; w[4] = (int32_t)P.hdr->rounds; w[5] = 0; w[6] = 0; w[7] = 0;
+        w[0] = LVDGS_RNN_OK;
+        __threadfence_system();
+    }
+}
+
+int seeds_along(int n, int S) { return n > S / 2 ? (n - S / 2 + S - 1) / S : 0; }
+
+}  // namespace
+}  // namespace lvdgs
+
+using namespace lvdgs;
+
+extern "C" {
+
+size_t lvdgs_recip_nn_scratch_bytes(int32_t width1, int32_t height1, int32_t subsample) {
+    if (width1 <= 0 || height1 <= 0 || subsample <= 0) return 0;
+    const size_t n = (size_t)seeds_along(width1, subsample) * (size_t)seeds_along(height1, subsample);
+    return align256(sizeof(RnnHeader)) + 7 * align256(n * sizeof(int32_t)) + align256(n * sizeof(u64));
+}
+
+int lvdgs_reciprocal_nn(const lvdgs_recip_nn_args *a, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    static unsigned char lds_done[16];
+    if (!a) { set_error("recip_nn: args is NULL"); return LVDGS_E_INVALID; }
+    if (a->width1 <= 0 || a->height1 <= 0 || a->width2 <= 0 || a->height2 <= 0) {
+        set_error("recip_nn: bad map size %dx%d / %dx%d", a->width1, a->height1, a->width2, a->height2); return LVDGS_E_INVALID;
+    }
+    if (a->dim < 1 || a->dim > LVDGS_RNN_MAX_DIM) { set_error("recip_nn: dim %d outside 1..%d", a->dim, LVDGS_RNN_MAX_DIM); return LVDGS_E_INVALID; }
+    if ((int64_t)a->width1 * a->height1 * a->dim > INT32_MAX || (int64_t)a->width2 * a->height2 * a->dim > INT32_MAX) {
+        set_error("recip_nn: a map of more than 2^31 - 1 floats"); return LVDGS_E_INVALID;
+    }
+    if (a->subsample < 1) { set_error("recip_nn: subsample %d < 1", a->subsample); return LVDGS_E_INVALID; }
+    if (a->max_iter < 1) { set_error("recip_nn: max_iter %d < 1", a->max_iter); return LVDGS_E_INVALID; }
+    const int sx = seeds_along(a->width1, a->subsample), sy = seeds_along(a->height1, a->subsample);
+    const int64_t seeds = (int64_t)sx * sy;
+    if (seeds < 1) { set_error("recip_nn: subsample %d leaves a %dx%d map no seed", a->subsample, a->width1, a->height1); return LVDGS_E_INVALID; }
+    if (seeds > LVDGS_RNN_MAX_SEEDS) { set_error("recip_nn: %lld seeds, more than %d", (long long)seeds, LVDGS_RNN_MAX_SEEDS); return LVDGS_E_INVALID; }
+    if (a->capacity < seeds) { set_error("recip_nn: capacity %d below the seed count %lld", a->capacity, (long long)seeds); return LVDGS_E_INVALID; }
+    if (!a->desc1 || !a->desc2 || !a->matches_im1 || !a->matches_im2 || !a->host_state || !a->scratch) {
+        set_error("recip_nn: desc1 / desc2 / matches_im1 / matches_im2 / host_state / scratch is NULL"); return LVDGS_E_INVALID;
+    }
+    if (a->scratch_bytes < lvdgs_recip_nn_scratch_bytes(a->width1, a->height1, a->subsample)) { set_error("recip_nn: scratch too small"); return LVDGS_E_INVALID; }
+    RnnParams P{};
+    P.W1 = a->width1; P.H1 = a->height1; P.W2 = a->width2; P.H2 = a->height2; P.D = a->dim; P.S = a->subsample;
+    P.seeds = (int)seeds; P.seeds_x = sx; P.capacity = a->capacity;
+    P.desc1 = a->desc1; P.desc2 = a->desc2; P.m1 = a->matches_im1; P.m2 = a->matches_im2; P.seed_state = a->seed_state;
+    char *base = reinterpret_cast<char *>(a->scratch);
+    P.hdr = reinterpret_cast<RnnHeader *>(base);
+    base += align256(sizeof(RnnHeader));
+    const size_t col = align256((size_t)seeds * sizeof(int32_t));
+    P.xy1 = reinterpret_cast<int32_t *>(base); P.xy2 = reinterpret_cast<int32_t *>(base + col); P.old1 = reinterpret_cast<int32_t *>(base + 2 * col);
+    P.old2 = reinterpret_cast<int32_t *>(base + 3 * col); P.retired = reinterpret_cast<int32_t *>(base + 4 * col);
+    P.act[0] = reinterpret_cast<uint32_t *>(base + 5 * col); P.act[1] = reinterpret_cast<uint32_t *>(base + 6 * col);
+    P.keys = reinterpret_cast<u64 *>(base + 7 * col);
+    void *dev = nullptr;
+    if (int e = check_hip(hipHostGetDevicePointer(&dev, a->host_state, 0), "recip_nn: host_state is not mapped pinned memory")) return e;
+    P.host_state = reinterpret_cast<int32_t *>(dev);
+    int n2 = 2 * RNN_ONE;
+    while (n2 < P.seeds) n2 *= 2;
+    if (int e = allow_dynamic_lds(reinterpret_cast<const void *>(&rnn_final_kernel), LVDGS_RNN_MAX_SEEDS * (int)sizeof(u64), lds_done)) return e;
+    {
+        ProfScope ps("rnn_init", s);
+        hipLaunchKernelGGL(rnn_init_kernel, dim3(cdiv(P.seeds, RNN_THREADS)), dim3(RNN_THREADS), 0, s, P);
+        LVDGS_LAUNCH_CHECK("rnn_init", 0, s);
+    }
+    const int groups = cdiv(P.seeds, RNN_QGROUP);
+    const int ks = (P.D + 1) / 2;
+    for (int half = 0; half < 2 * a->max_iter; half++) {
+        const int N = (half & 1) ? P.W1 * P.H1 : P.W2 * P.H2;
+        const dim3 grid(cdiv(cdiv(N, RNN_TILE), RNN_WAVES * RNN_WAVE_TILES), groups);
+        {
+            ProfScope ps("rnn_search", s);
+            if (ks == 12) hipLaunchKernelGGL(rnn_search_kernel<12>, grid, dim3(RNN_THREADS), 0, s, P, half);
+            else hipLaunchKernelGGL(rnn_search_kernel<0>, grid, dim3(RNN_THREADS), 0, s, P, half);
+            LVDGS_LAUNCH_CHECK("rnn_search", 0, s);
+        }
+        {
+            ProfScope ps("rnn_update", s);
+            hipLaunchKernelGGL(rnn_update_kernel, dim3(1), dim3(RNN_ONE), 0, s, P, half);
+            LVDGS_LAUNCH_CHECK("rnn_update", 0, s);
+        }
+    }
+    {
+        ProfScope ps("rnn_final", s);
+        hipLaunchKernelGGL(rnn_final_kernel, dim3(1), dim3(RNN_ONE), (size_t)n2 * sizeof(u64), s, P, n2);
+        LVDGS_LAUNCH_CHECK("rnn_final", 0, s);
+    }
+    return LVDGS_OK;
+}
+
+}  // extern "C"

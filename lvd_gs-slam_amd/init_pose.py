@@ -6,9 +6,12 @@ pixel (``depth_to_3d`` with ``cv2.undistortPoints``), and solves ``cv2.solvePnPR
 Here the depth stays on its device and the gather, the hypotheses, the consensus and the refinement are one ``lvdgs_pnp_ransac``
 call (include/lvdgs.h states the semantics): two launches, one host wait.
 
-The matcher that produces the matches (MASt3R descriptors + ``fast_reciprocal_NNs``) is out of scope: it is injectable as
-``matcher(img1, img2, model, (W1, H1)) -> (matches_im1, matches_im2)`` -- (M, 2) pixel coordinates (x, y) at the raster ``(W1, H1)``,
-integers in the keyframe and floats in the new frame, NumPy arrays or tensors.
+The matches come from ``matcher(img1, img2, model, (W1, H1)) -> (matches_im1, matches_im2)`` -- (M, 2) pixel coordinates (x, y) at
+the raster ``(W1, H1)``, integers in the keyframe and floats in the new frame, NumPy arrays or tensors.  The reference's matcher is
+MASt3R descriptors + ``fast_reciprocal_NNs(desc1, desc2, subsample_or_initxy1=8, dist='dot')``.  Only the network that makes the
+descriptors is out of scope; the matching is ``reciprocal_matches`` (one ``lvdgs_reciprocal_nn`` call: include/lvdgs.h, DESIGN.md
+section 4d), and ``DescriptorMatcher(describe)`` is the matcher built on it -- ``describe`` is the network's seat.  With it everything
+between two descriptor maps and the initial pose runs on the device, and the matches never visit the host.
 """
 import ctypes as C
 from types import SimpleNamespace
@@ -23,7 +26,13 @@ from .gaussian_renderer import render_with_custom_resolution
 # pose), hypothesis (the winner, -1: none), winner_count (its score), matches (M), inlier_mask (bool tensor (M,) on the device).
 last_call = SimpleNamespace(status=None, reason=None, valid_matches=0, inliers=0, hypothesis=-1, winner_count=0, matches=0, inlier_mask=None)
 
+# The record of the most recent ``reciprocal_matches`` call: seeds, matches (M), unconverged (seeds still active after max_iter rounds,
+# dropped), rounds (those that began with an active seed), seed_state ((seeds, 3) int32 device tensor of every seed's final flat xy1, xy2
+# and converged flag when the call asked for it, else None).
+last_match = SimpleNamespace(seeds=0, matches=0, unconverged=0, rounds=0, seed_state=None)
+
 _resources = {}   # device index -> (pinned host block, its words as int32, its pose as float64, scratch tensor)
+_match_resources = {}   # device index -> (pinned state words, scratch tensor)
 
 
 def matcher_raster(W, H, size=512):
@@ -94,6 +103,74 @@ def pnp_ransac(depth, matches_im1, matches_im2, K, dist_coeffs=None, hypotheses=
     return pose, last_call.inlier_mask
 
 
+def reciprocal_matches(desc1, desc2, subsample=8, max_iter=10, seed_state=False):
+    """Reciprocal nearest neighbours of two descriptor maps under the dot product (``fast_reciprocal_NNs(desc1, desc2,
+    subsample_or_initxy1=subsample, dist='dot')`` as include/lvdgs.h restates it), one ``lvdgs_reciprocal_nn`` call.  ``desc1``: (H1, W1, D),
+    ``desc2``: (H2, W2, D) tensors on a GPU.  -> ``(matches_im1 (M, 2) int32, matches_im2 (M, 2) float32)``, pixel coordinates (x, y), on
+    that device, sorted by map-1 pixel (row-major), distinct -- what ``pnp_ransac`` takes.  One host wait, to learn M; the counts go to
+    ``last_match``."""
+    if not torch.is_tensor(desc1) or not torch.is_tensor(desc2):
+        raise _lib.LvdgsError("reciprocal_matches: the descriptor maps must be tensors on a GPU (there is no CPU path)")
+    if desc1.ndim != 3 or desc2.ndim != 3:
+        raise ValueError(f"reciprocal_matches: the maps must be (H, W, D), got {tuple(desc1.shape)} and {tuple(desc2.shape)}")
+    if desc1.shape[2] != desc2.shape[2]:
+        raise ValueError(f"reciprocal_matches: the maps differ in descriptor size ({desc1.shape[2]} and {desc2.shape[2]})")
+    if min(desc1.shape) < 1 or min(desc2.shape) < 1:
+        raise ValueError(f"reciprocal_matches: an empty map ({tuple(desc1.shape)} and {tuple(desc2.shape)})")
+    if not desc1.is_cuda or not desc2.is_cuda:
+        raise _lib.LvdgsError("reciprocal_matches: the descriptor maps must be tensors on a GPU (there is no CPU path)")
+    device = desc1.device
+    if desc2.device != device:
+        raise ValueError(f"reciprocal_matches: the maps are on different devices ({device} and {desc2.device})")
+    d1, d2 = _lib.f32(desc1, device), _lib.f32(desc2, device)
+    (H1, W1, D), (H2, W2, _) = d1.shape, d2.shape
+    S = int(subsample)
+    seeds = len(range(S // 2, H1, S)) * len(range(S // 2, W1, S)) if S >= 1 else 0
+    L = _lib.lib()
+    need = L.lvdgs_recip_nn_scratch_bytes(W1, H1, S) if S >= 1 else 0
+    block, scratch = _match_resources.get(device.index, (None, None))
+    if block is None:
+        block = torch.zeros(_lib.RNN_STATE_WORDS, dtype=torch.int32).pin_memory()
+    if scratch is None or scratch.numel() < need:
+        scratch = torch.empty(max(int(need), 256), dtype=torch.uint8, device=device)
+    _match_resources[device.index] = (block, scratch)
+    cap = max(seeds, 1)
+    m1 = torch.empty((cap, 2), dtype=torch.int32, device=device)
+    m2 = torch.empty((cap, 2), dtype=torch.float32, device=device)
+    state = torch.empty((cap, 3), dtype=torch.int32, device=device) if seed_state else None
+    block.zero_()
+    a = _lib.RecipNnArgs(width1=W1, height1=H1, width2=W2, height2=H2, dim=D, subsample=S, max_iter=int(max_iter), capacity=cap,
+                         desc1=d1.data_ptr(), desc2=d2.data_ptr(), matches_im1=m1.data_ptr(), matches_im2=m2.data_ptr(),
+                         seed_state=None if state is None else state.data_ptr(), host_state=block.data_ptr(), scratch=scratch.data_ptr(),
+                         scratch_bytes=scratch.numel())
+    with _lib.on_device(device):
+        _lib.check(L.lvdgs_reciprocal_nn(C.byref(a), _lib.raw_stream(device)), "lvdgs_reciprocal_nn")
+        torch.cuda.current_stream(device).synchronize()      # the one wait of the call
+    w = block.numpy().copy()
+    if int(w[0]) != _lib.RNN_OK:
+        raise _lib.LvdgsError(f"lvdgs_reciprocal_nn left no state (status word {int(w[0])})")
+    last_match.seeds, last_match.matches, last_match.unconverged, last_match.rounds = int(w[1]), int(w[2]), int(w[3]), int(w[4])
+    last_match.seed_state = None if state is None else state[:last_match.seeds]
+    return m1[:last_match.matches], m2[:last_match.matches]
+
+
+class DescriptorMatcher:
+    """The matcher of ``get_pose`` on descriptor maps: ``describe(img1, img2, model, (W1, H1)) -> (desc1, desc2)`` -- the network's seat
+    (MASt3R in the reference, out of scope; ``synthetic.WorldDescriptors`` is the stand-in), (H1, W1, D) tensors on a GPU at the
+    matcher's raster -- followed by ``reciprocal_matches``.  ``set_frames`` goes on to a ``describe`` that has it."""
+
+    def __init__(self, describe, subsample=8, max_iter=10):
+        self.describe, self.subsample, self.max_iter = describe, int(subsample), int(max_iter)
+
+    def set_frames(self, keyframe_idx, frame_idx):
+        if hasattr(self.describe, "set_frames"):
+            self.describe.set_frames(keyframe_idx, frame_idx)
+
+    def __call__(self, img1, img2, model, raster):
+        desc1, desc2 = self.describe(img1, img2, model, raster)
+        return reciprocal_matches(desc1, desc2, subsample=self.subsample, max_iter=self.max_iter)
+
+
 def get_pose(img1, img2, model, dist_coeffs, viewpoint, gaussians, pipeline_params, background, *, matcher=None, hypotheses=128,
              reproj_error=5.0, seed=0, min_inliers=6, size=512):
     """The reference's ``get_pose`` (same positional signature) -> ``(pose_w2c, render_depth)``: the keyframe -> frame motion as a
@@ -101,10 +178,11 @@ def get_pose(img1, img2, model, dist_coeffs, viewpoint, gaussians, pipeline_para
     ``allclose(rel_pose, identity)`` test looks for -- and the keyframe's depth rendered at the matcher's raster.
 
     Deviation: ``render_depth`` is the detached (1, H1, W1) tensor on its device; the map does not go to the host.
-    ``viewpoint`` is the last keyframe (its pose, intrinsics and size); ``matcher(img1, img2, model, (W1, H1))`` supplies the matches."""
+    ``viewpoint`` is the last keyframe (its pose, intrinsics and size); ``matcher(img1, img2, model, (W1, H1))`` supplies the matches:
+    ``DescriptorMatcher(describe)`` is the supplied one (descriptor maps -> ``reciprocal_matches``, on the device)."""
     if matcher is None:
-        raise TypeError("get_pose: the `matcher` argument is required (the MASt3R matcher is out of scope: pass a callable "
-                        "matcher(img1, img2, model, (W1, H1)) -> (matches_im1, matches_im2))")
+        raise TypeError("get_pose: the `matcher` argument is required (only the descriptor network is out of scope: pass "
+                        "DescriptorMatcher(describe), or any callable matcher(img1, img2, model, (W1, H1)) -> (matches_im1, matches_im2))")
     W, H = viewpoint.image_width, viewpoint.image_height
     W1, H1 = matcher_raster(W, H, size)
     matches_im1, matches_im2 = matcher(img1, img2, model, (W1, H1))

@@ -26,7 +26,9 @@ Stand-ins for what is out of scope, all injectable:
   * the pose initialisation: by default the previous frame's pose -- the reference's own branch for "MASt3R returned the identity".
     ``pose_init="pnp"`` follows ``FrontEnd.tracking`` (:1442-1465): ``init_pose.get_pose`` (PnP-RANSAC on the last keyframe's rendered
     depth, HIP) gives the keyframe -> frame motion, ``pose_init = rel_pose @ pose_last_kf``, the previous pose when that is the identity;
-    only the matcher needs MASt3R -- injectable as ``matcher`` (``synthetic.GroundTruthMatcher`` is the stand-in);
+    only the matcher's descriptor network needs MASt3R -- ``matcher`` is injectable: ``init_pose.DescriptorMatcher(describe)`` matches
+    descriptor maps on the device (``synthetic.WorldDescriptors`` stands in for the network), ``synthetic.GroundTruthMatcher`` makes
+    matches from the ground truth without matching anything;
   * ``keyframe_depth``: the depth map a new keyframe seeds Gaussians from.  Default: the keyframe's mono depth under the valid-pixel
     mask, i.e. ``add_new_keyframe``'s own statements for the first keyframe (:1364-1382) applied to every keyframe.  For later
     keyframes the reference blends rendered and mono depth patch by patch and rescales the mono depth (``process_depth``,

@@ -257,8 +257,9 @@ def mono_scale_factor(i, drift):
 
 
 class GroundTruthMatcher:
-    """The stand-in for the MASt3R matcher of ``init_pose.get_pose`` (descriptors + ``fast_reciprocal_NNs(subsample_or_initxy1=8)``, out
-    of scope): 2D-2D matches between a keyframe and a frame of a ``SequenceDataset`` made from the ground truth.
+    """A stand-in for the whole matcher of ``init_pose.get_pose`` (MASt3R descriptors + ``fast_reciprocal_NNs(subsample_or_initxy1=8)``)
+    that matches nothing: 2D-2D matches between a keyframe and a frame of a ``SequenceDataset`` made from the ground truth.  (Only the
+    descriptor network is out of scope: ``WorldDescriptors`` below stands in for it alone, under ``init_pose.DescriptorMatcher``.)
 
     The stride-``stride`` grid of the keyframe at the matcher's raster; every grid point is carried into the new frame with the two
     ground-truth poses and the keyframe's mono depth at that pixel (points without depth are dropped), perturbed by Gaussian noise of
@@ -308,3 +309,61 @@ class GroundTruthMatcher:
         u = np.where(bad, rng.uniform(0, W1 - 1, M), u)
         v = np.where(bad, rng.uniform(0, H1 - 1, M), v)
         return np.stack([gx, gy], 1).astype(np.int32), np.stack([u, v], 1).astype(np.float32)
+
+
+class WorldDescriptors:
+    """The stand-in for the descriptor network of the reference's matcher (MASt3R, out of scope): dense descriptor maps of a keyframe
+    and a frame of a ``SequenceDataset`` at the matcher's raster, for ``init_pose.DescriptorMatcher`` to match.
+
+    A raster pixel is back-projected with the frame's mono depth (the full-size pixel under it; ``smooth`` > 1: the mean of the valid
+    depths in the ``smooth`` x ``smooth`` full-size pixels around it -- a network's descriptor sees a neighbourhood, not one pixel's
+    depth noise) and the frame's true pose; the world point p goes through seeded random Fourier features cos(p . f_k + b_k), k < ``dim``
+    (f_k ~ N(0, ``freq``^2) rad per world unit, b_k uniform), seeded N(0, ``noise``^2) is added per component (per frame: two frames see
+    different noise) and the vector is unit-normalised.  Pixels without depth, and pixels on a dynamic rectangle of the frame's static
+    mask -- those objects move -- get seeded random unit vectors: they match nothing consistently.  Everything is float32 tensor
+    arithmetic on the dataset's device.  ``set_frames(keyframe_idx, frame_idx)`` says which pair the next call is about (``SlamSequence``
+    calls it through the matcher); the call has the network's seat in ``DescriptorMatcher``: ``(img1, img2, model, (W1, H1)) -> (desc1,
+    desc2)``, (H1, W1, dim) float32 tensors."""
+
+    def __init__(self, dataset, dim=24, seed=0, noise=0.02, freq=8.0, smooth=5):
+        self.dataset, self.dim, self.seed, self.noise, self.freq, self.smooth = dataset, int(dim), int(seed), float(noise), float(freq), int(smooth)
+        g = torch.Generator().manual_seed(31000 + self.seed)
+        self.f = (self.freq * torch.randn(3, self.dim, generator=g)).to(dataset.device)
+        self.b = (2.0 * math.pi * torch.rand(self.dim, generator=g)).to(dataset.device)
+        self.pair = None
+
+    def set_frames(self, keyframe_idx, frame_idx):
+        self.pair = (int(keyframe_idx), int(frame_idx))
+
+    def describe(self, idx, raster):
+        """The descriptor map of frame ``idx`` at ``raster`` = (W1, H1)."""
+        ds, dev = self.dataset, self.dataset.device
+        W1, H1 = raster
+        sw, sh = W1 / ds.width, H1 / ds.height
+        gx, gy = torch.arange(W1, device=dev, dtype=torch.float32), torch.arange(H1, device=dev, dtype=torch.float32)
+        px = (gx / sw).round().clamp(max=ds.width - 1).long()
+        py = (gy / sh).round().clamp(max=ds.height - 1).long()
+        mono = torch.as_tensor(ds.mono_depths[idx], dtype=torch.float32, device=dev)
+        valid = torch.isfinite(mono) & (mono > 0)
+        mono = torch.where(valid, mono, torch.zeros_like(mono))
+        if self.smooth > 1:
+            box = lambda t: torch.nn.functional.avg_pool2d(t[None, None], self.smooth, stride=1, padding=self.smooth // 2, count_include_pad=True)[0, 0]
+            mono = box(mono) / box(valid.float()).clamp(min=1e-6)
+        Z = mono[py][:, px]
+        ok = valid[py][:, px]
+        m = ds.static_mask(idx)
+        if m is not None:
+            ok = ok & m.to(dev)[py][:, px]
+        X = (gx[None, :] / sw - ds.cx) / ds.fx * Z
+        Y = (gy[:, None] / sh - ds.cy) / ds.fy * Z
+        T = ds.poses[idx].to(device=dev, dtype=torch.float32)
+        P = (torch.stack([X, Y, Z], -1) - T[:3, 3]) @ T[:3, :3]      # world = R^T (camera - t)
+        g = torch.Generator().manual_seed(32000 + 1000 * self.seed + int(idx))
+        d = torch.cos(P @ self.f + self.b) + self.noise * torch.randn(H1, W1, self.dim, generator=g).to(dev)
+        d = torch.where(ok[..., None], d, torch.randn(H1, W1, self.dim, generator=g).to(dev))
+        return (d / d.norm(dim=-1, keepdim=True).clamp(min=1e-12)).contiguous()
+
+    def __call__(self, img1, img2, model, raster):
+        if self.pair is None:
+            raise RuntimeError("WorldDescriptors: set_frames(keyframe_idx, frame_idx) first")
+        return self.describe(self.pair[0], raster), self.describe(self.pair[1], raster)

@@ -109,6 +109,9 @@ def run_sequence(dev, frames=60, scale=1.0, cadence="reference", fused="auto", i
                                     pcd_downsample=pcd_downsample, mono_scale_drift=mono_scale_drift, trajectory=trajectory)
     del truth
     m = empty_map(cfg, dev)
+    if sequence_kwargs.get("matcher") == "descriptors":      # descriptor maps matched on the device (the network's stand-in: synthetic.WorldDescriptors)
+        from lvdgs import init_pose
+        sequence_kwargs["matcher"] = init_pose.DescriptorMatcher(synthetic.WorldDescriptors(ds, seed=seed))
     if sequence_kwargs.get("pose_init") == "pnp" and sequence_kwargs.get("matcher") is None:
         sequence_kwargs["matcher"] = synthetic.GroundTruthMatcher(ds, stride=8, noise_px=0.7, outlier_ratio=0.3, seed=seed)
     seq = SlamSequence(cfg, ds, m, PIPE, torch.zeros(3, device=dev), fused=fused, idle_map_iters=idle, on_event=on_event, **sequence_kwargs)
@@ -155,6 +158,8 @@ def main():
     ap.add_argument("--mono-scale-drift", type=float, default=0.0, help="per-frame scale wander of the synthetic mono depth (synthetic.mono_scale_factor)")
     ap.add_argument("--pose-init", choices=["previous", "pnp"], default=None,
                     help="log every tracked frame's initial pose (summary key pose_init); pnp: start it from init_pose.get_pose with synthetic.GroundTruthMatcher")
+    ap.add_argument("--matcher", choices=["ground_truth", "descriptors"], default="ground_truth",
+                    help="with --pose-init pnp: matches made from the ground truth (default), or synthetic.WorldDescriptors' maps matched by init_pose.reciprocal_matches")
     ap.add_argument("--verbose", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -163,7 +168,7 @@ def main():
     out, _ = run_sequence(dev, a.frames, a.scale, a.cadence, False if a.no_fused else "auto", a.idle, a.refine, not a.no_masks, seed=a.seed,
                           window_size=a.window_size, on_event=ev, geometry=a.geometry, pcd_downsample=a.pcd_downsample,
                           mono_scale_drift=a.mono_scale_drift, **({"keyframe_depth": "patch_align"} if a.keyframe_depth == "patch_align" else {}),
-                          **({"pose_init": a.pose_init} if a.pose_init else {}))
+                          **({"pose_init": a.pose_init} if a.pose_init else {}), **({"matcher": "descriptors"} if a.matcher == "descriptors" else {}))
     for rec in out.get("pose_init", []):
         print("  frame {frame:3d} kf {keyframe:3d} inliers {inl:>5} init error {e:.4f} ({r:.3f} deg; previous pose {p:.4f}) tracking iterations {it}".format(
             frame=rec["frame"], keyframe=rec["keyframe"], inl=rec.get("inliers", "-"), e=rec["init_translation_error"], r=rec["init_rotation_error_deg"],
