@@ -690,6 +690,98 @@ typedef struct lvdgs_recip_nn_args {
 size_t lvdgs_recip_nn_scratch_bytes(int32_t width1, int32_t height1, int32_t subsample);
 int lvdgs_reciprocal_nn(const lvdgs_recip_nn_args *a, void *stream);
 
+/* ---- the matcher's image formatting (reference utils/init_pose.py torch_images_to_dust3r_format :35-75, the first statement of
+ * get_pose, get_depth and find_scale: a device-to-host copy, PIL's resize and crop, torchvision's normalisation, an upload) ----
+ * image: (3, height, width) float32, contiguous.  out: (3, H1, W1) float32 with (W1, H1) the matcher's raster of size `size`.
+ * Quantise.  q = uint8(trunc(float32(x) * 255.0f)); a product outside [0, 255] clamps and NaN gives 0 (deviation: NumPy wraps).
+ * Resize to (w, h) = (round(W size / S), round(H size / S)), S = max(W, H), halves to even, by PIL's 8-bit resampling with the
+ *   LANCZOS filter (sinc(x) sinc(x / 3) on [-3, 3), support 3) when S > size, else BICUBIC (Keys, a = -0.5, support 2): a horizontal
+ *   pass to uint8, then a vertical pass to uint8; a pass whose edge does not change is skipped.  Output sample xx of a pass from `in`
+ *   to `out` samples, float64: scale = in / out, fs = max(scale, 1), support = filter support * fs, center = (xx + 0.5) scale,
+ *   xmin = max(int(center - support + 0.5), 0), n = min(int(center + support + 0.5), in) - xmin,
+ *   w[x] = filter((x + xmin - center + 0.5) * (1 / fs)), divided by their sum ww when ww != 0,
+ *   k[x] = int(w[x] 2^22 + 0.5) for w[x] >= 0, int(w[x] 2^22 - 0.5) below; sample = clamp((2^21 + sum k[x] pixel[xmin + x]) >> 22, 0, 255)
+ *   in int32.
+ * Crop.  cx = w / 2, cy = h / 2 (integer division), halfw = ((2 cx) / 16) 8, halfh likewise, halfh = 3 halfw / 4 when w == h; the
+ *   columns cx - halfw .. cx + halfw - 1 and the rows cy - halfh .. cy + halfh - 1: (W1, H1) = (2 halfw, 2 halfh).  Only these are
+ *   computed, and the horizontal pass runs over the image rows the vertical pass reads.
+ * Normalise.  (float32(q) / 255.0f - 0.5f) / 0.5f, IEEE float32.  quantised (optional, may be NULL): the cropped uint8 image,
+ *   (H1, W1, 3), before the normalisation.
+ * lvdgs_format_plan_query gives the sizes of a call; lvdgs_format_table makes the entries first .. first + count - 1 of a pass' table on
+ * the HOST (no GPU involved): per entry 2 + taps int32 words -- xmin, n, then the n coefficients, zero-filled to `taps`
+ * (plan.taps_x / taps_y; a skipped pass has one tap: xmin = xx, n = 1, k = 2^22).  The caller keeps the tables of an image size on the
+ * device: table_x = entries crop_x .. crop_x + W1 - 1 of the pass width -> w, table_y = entries crop_y .. crop_y + H1 - 1 of the pass
+ * height -> h.  A kernel reads no image or scratch element outside its buffers whatever a table holds.
+ * lvdgs_format_image: two launches, enqueued at once; no host wait, no copy.  scratch: lvdgs_format_scratch_bytes(W, H, size) bytes
+ * (0: the sizes are refused), no initialisation needed.  Two calls give the same bytes.
+ * LVDGS_E_INVALID: args / plan / table NULL, a NULL pointer, an edge not in 1..LVDGS_FORMAT_MAX_EDGE, size 224 (the reference's other
+ * crop rule, which it never uses) or outside 16..LVDGS_FORMAT_MAX_SIZE, an empty raster, an unknown filter, table entries outside the
+ * pass, scratch too small. */
+#define LVDGS_FORMAT_MAX_EDGE 16384
+#define LVDGS_FORMAT_MAX_SIZE 4096
+enum {
+    LVDGS_FORMAT_BICUBIC = 0,
+    LVDGS_FORMAT_LANCZOS = 1
+};
+typedef struct lvdgs_format_plan {
+    int32_t resized_width, resized_height;   /* (w, h)                                */
+    int32_t filter;                          /* LVDGS_FORMAT_LANCZOS / _BICUBIC       */
+    int32_t crop_x, crop_y;                  /* the crop's first column and row in the resized image */
+    int32_t out_width, out_height;           /* (W1, H1)                              */
+    int32_t taps_x, taps_y;                  /* coefficient slots per table entry     */
+    int32_t row_first, row_count;            /* the image rows the vertical pass reads */
+} lvdgs_format_plan;
+typedef struct lvdgs_format_image_args {
+    int32_t width, height, size;
+    const float *image;           /* 3*H*W                                          */
+    const int32_t *table_x;       /* W1*(2 + taps_x), device                        */
+    const int32_t *table_y;       /* H1*(2 + taps_y), device                        */
+    float *out;                   /* out 3*H1*W1                                    */
+    uint8_t *quantised;           /* out H1*W1*3, or NULL                           */
+    void *scratch; size_t scratch_bytes;
+} lvdgs_format_image_args;
+int lvdgs_format_plan_query(int32_t width, int32_t height, int32_t size, lvdgs_format_plan *plan);
+int lvdgs_format_table(int32_t in, int32_t out, int32_t filter, int32_t first, int32_t count, int32_t *table);
+size_t lvdgs_format_scratch_bytes(int32_t width, int32_t height, int32_t size);
+int lvdgs_format_image(const lvdgs_format_image_args *a, void *stream);
+
+/* ---- the scale between two depth maps at matched pixels (reference utils/depth_utils.py find_scale :31-55: cv2.resize of both maps
+ * to the matcher's raster on the host, a gather at the matches, a ratio of means -- the scale remedy of LVD-GS Algorithm 1) ----
+ * Match i = (map-1 pixel (x, y) int32, map-2 pixel (u, v) float32, truncated toward zero) at the raster (raster_width, raster_height),
+ * as lvdgs_reciprocal_nn writes them.  depth1: (height1, width1), depth2: (height2, width2), float32; the sizes may differ from each
+ * other and from the raster.
+ * Sampling.  A match takes depth1 at its map-1 pixel and depth2 at its map-2 pixel as if each map had been resized bilinearly to the
+ *   raster.  Per axis, pixel i of n_dst from n_src samples: f = (i + 0.5) (n_src / n_dst) - 0.5, s = floor(f), t = f - s;
+ *   s < 0: (s, t) = (0, 0); s >= n_src - 1: (s, t) = (n_src - 1, 0); the neighbour s + 1 is clamped to n_src - 1.  With a, b the
+ *   samples of row sy at sx and its neighbour and c, d those of the next row:
+ *   value = (1 - ty) ((1 - tx) a + tx b) + ty ((1 - tx) c + tx d).  All arithmetic is float64 from the float32 loads, as written.
+ *   UNPINNED against cv2.resize(INTER_LINEAR), which interpolates in float32.
+ * A match is VALID when 0 <= x < raster_width, 0 <= y < raster_height, -1 < u < raster_width, -1 < v < raster_height (NaN: not) and both
+ *   values are finite and > 0 (deviations: the reference lets +inf through, and its out-of-raster indices wrap or raise).
+ * scale = float32((sum1 / n) / (sum2 / n)) over the n valid matches, the sums in float64 in a fixed order: two calls give the same bits.
+ * One launch; no host wait.  host_state: LVDGS_MATCH_SCALE_HOST_BYTES bytes of page-locked, mapped host memory (the host address):
+ * LVDGS_MATCH_SCALE_STATE_WORDS int32 words -- [0] status, [1] num_matches, [2] n, [3] the scale's float bits (0 when n == 0),
+ * [4..7] zero -- then sum1 and sum2 as two doubles.  The caller synchronises the stream once and reads it.
+ * LVDGS_E_INVALID: args NULL, a NULL pointer (the matches may be NULL when num_matches == 0), num_matches < 0, a size not > 0;
+ * LVDGS_E_HIP: host_state is not mapped pinned memory. */
+#define LVDGS_MATCH_SCALE_STATE_WORDS 8
+#define LVDGS_MATCH_SCALE_HOST_BYTES 64
+enum {
+    LVDGS_MATCH_SCALE_OK = 1,
+    LVDGS_MATCH_SCALE_NO_VALID = 2   /* no valid match: there is no scale */
+};
+typedef struct lvdgs_match_scale_args {
+    int32_t num_matches;
+    int32_t raster_width, raster_height;   /* (W1, H1) of the matches                */
+    int32_t width1, height1, width2, height2;
+    const int32_t *matches_im1;   /* M*2 (x, y) in map 1's raster                   */
+    const float *matches_im2;     /* M*2 (u, v) in map 2's raster                   */
+    const float *depth1;          /* height1*width1                                 */
+    const float *depth2;          /* height2*width2                                 */
+    int32_t *host_state;          /* LVDGS_MATCH_SCALE_HOST_BYTES, pinned host (the host address) */
+} lvdgs_match_scale_args;
+int lvdgs_match_depth_scale(const lvdgs_match_scale_args *a, void *stream);
+
 /* ---- diagnostics ---- */
 const char *lvdgs_last_error(void);
 const char *lvdgs_version(void);

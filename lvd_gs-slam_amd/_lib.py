@@ -161,6 +161,38 @@ RNN_MAX_DIM, RNN_MAX_SEEDS, RNN_STATE_WORDS = 64, 8192, 8
 RNN_OK = 1
 
 
+class FormatPlan(C.Structure):
+    """struct lvdgs_format_plan (include/lvdgs.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("resized_width", "resized_height", "filter", "crop_x", "crop_y", "out_width", "out_height",
+                                         "taps_x", "taps_y", "row_first", "row_count")]
+
+
+class FormatImageArgs(C.Structure):
+    """struct lvdgs_format_image_args (include/lvdgs.h)."""
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32), ("size", C.c_int32),
+        ("image", _fp), ("table_x", _fp), ("table_y", _fp), ("out", _fp), ("quantised", _fp),
+        ("scratch", _fp), ("scratch_bytes", C.c_size_t),
+    ]
+
+
+FORMAT_MAX_EDGE, FORMAT_MAX_SIZE = 16384, 4096
+FORMAT_BICUBIC, FORMAT_LANCZOS = 0, 1
+
+
+class MatchScaleArgs(C.Structure):
+    """struct lvdgs_match_scale_args (include/lvdgs.h)."""
+    _fields_ = [
+        ("num_matches", C.c_int32), ("raster_width", C.c_int32), ("raster_height", C.c_int32),
+        ("width1", C.c_int32), ("height1", C.c_int32), ("width2", C.c_int32), ("height2", C.c_int32),
+        ("matches_im1", _fp), ("matches_im2", _fp), ("depth1", _fp), ("depth2", _fp), ("host_state", _fp),
+    ]
+
+
+MATCH_SCALE_STATE_WORDS, MATCH_SCALE_HOST_BYTES = 8, 64
+MATCH_SCALE_OK, MATCH_SCALE_NO_VALID = 1, 2
+
+
 class StateLayout(C.Structure):
     _fields_ = [(n, C.c_size_t) for n in (
         "geom_rec", "geom_tiles_touched", "geom_slot_base", "bin_point_list", "bin_tile_keys",
@@ -182,6 +214,7 @@ EXPORTS = (
     "lvdgs_masked_depth_l1_backward", "lvdgs_pose_step", "lvdgs_host_device_pointer", "lvdgs_pose_step_batch", "lvdgs_adam_step", "lvdgs_isotropic_scratch_bytes", "lvdgs_isotropic_reg", "lvdgs_view_stats", "lvdgs_map_stats_apply", "lvdgs_map_view_tail", "lvdgs_ssim_scratch_bytes", "lvdgs_ssim_l1",
     "lvdgs_masked_loss_scratch_bytes", "lvdgs_masked_loss_batch", "lvdgs_backward_masked_loss", "lvdgs_blend_backward_window_batch", "lvdgs_forward_batch", "lvdgs_forward_backward_fused_loss", "lvdgs_map_view_tail_batch", "lvdgs_gaussian_backward_batch",
     "lvdgs_depth_align_scratch_bytes", "lvdgs_depth_align", "lvdgs_depth_align_resume", "lvdgs_pnp_scratch_bytes", "lvdgs_pnp_ransac", "lvdgs_recip_nn_scratch_bytes", "lvdgs_reciprocal_nn",
+    "lvdgs_format_plan_query", "lvdgs_format_table", "lvdgs_format_scratch_bytes", "lvdgs_format_image", "lvdgs_match_depth_scale",
     "lvdgs_last_error", "lvdgs_version", "lvdgs_profile_enable",
     "lvdgs_profile_reset", "lvdgs_profile_read",
 )
@@ -275,6 +308,12 @@ def lib():
         L.lvdgs_recip_nn_scratch_bytes.restype = C.c_size_t
         L.lvdgs_recip_nn_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
         L.lvdgs_reciprocal_nn.argtypes = [C.POINTER(RecipNnArgs), C.c_void_p]
+        L.lvdgs_format_plan_query.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(FormatPlan)]
+        L.lvdgs_format_table.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+        L.lvdgs_format_scratch_bytes.restype = C.c_size_t
+        L.lvdgs_format_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+        L.lvdgs_format_image.argtypes = [C.POINTER(FormatImageArgs), C.c_void_p]
+        L.lvdgs_match_depth_scale.argtypes = [C.POINTER(MatchScaleArgs), C.c_void_p]
         L.lvdgs_profile_enable.argtypes = [C.c_int]
         L.lvdgs_profile_read.argtypes = [C.POINTER(KernelTime), C.c_int]
         _lib = L

@@ -12,6 +12,11 @@ MASt3R descriptors + ``fast_reciprocal_NNs(desc1, desc2, subsample_or_initxy1=8,
 descriptors is out of scope; the matching is ``reciprocal_matches`` (one ``lvdgs_reciprocal_nn`` call: include/lvdgs.h, DESIGN.md
 section 4d), and ``DescriptorMatcher(describe)`` is the matcher built on it -- ``describe`` is the network's seat.  With it everything
 between two descriptor maps and the initial pose runs on the device, and the matches never visit the host.
+
+What the reference does around the network is here too: ``torch_images_to_dust3r_format`` / ``format_image``
+(one ``lvdgs_format_image`` call per frame: PIL's 8-bit resize, crop and normalisation bit for bit, without the frame's trip to the
+host), ``get_depth`` (the pointmap's z resized by nearest neighbour, on the device), and ``NetworkDescribe(infer)``, the ``describe``
+whose seat is exactly the reference's ``inference(model)``: formatted views in, ``desc`` / ``pts3d`` out.
 """
 import ctypes as C
 from types import SimpleNamespace
@@ -33,6 +38,8 @@ last_match = SimpleNamespace(seeds=0, matches=0, unconverged=0, rounds=0, seed_s
 
 _resources = {}   # device index -> (pinned host block, its words as int32, its pose as float64, scratch tensor)
 _match_resources = {}   # device index -> (pinned state words, scratch tensor)
+_format_tables = {}     # (device index, W, H, size) -> (plan, table_x, table_y device tensors): made once per image size and device
+_format_scratch = {}    # device index -> scratch tensor
 
 
 def matcher_raster(W, H, size=512):
@@ -154,10 +161,113 @@ def reciprocal_matches(desc1, desc2, subsample=8, max_iter=10, seed_state=False)
     return m1[:last_match.matches], m2[:last_match.matches]
 
 
+def _format_plan(device, W, H, size):
+    key = (device.index, W, H, size)
+    hit = _format_tables.get(key)
+    if hit is None:
+        L = _lib.lib()
+        p = _lib.FormatPlan()
+        _lib.check(L.lvdgs_format_plan_query(W, H, size, C.byref(p)), "lvdgs_format_plan_query")
+        tables = []
+        for n_in, n_out, first, count, taps in ((W, p.resized_width, p.crop_x, p.out_width, p.taps_x),
+                                                (H, p.resized_height, p.crop_y, p.out_height, p.taps_y)):
+            t = np.zeros((count, 2 + taps), dtype=np.int32)
+            _lib.check(L.lvdgs_format_table(n_in, n_out, p.filter, first, count, t.ctypes.data), "lvdgs_format_table")
+            tables.append(torch.from_numpy(t).to(device))
+        hit = _format_tables[key] = (p, tables[0], tables[1])
+    return hit
+
+
+def format_image(img, size=512, *, quantised=False):
+    """The matcher's formatting of one frame (``torch_images_to_dust3r_format``'s loop body, utils/init_pose.py:49-72), one
+    ``lvdgs_format_image`` call: ``img`` (3, H, W) float tensor on a GPU -> (1, 3, H1, W1) float32, contiguous, on that device, with
+    (W1, H1) = ``matcher_raster(W, H, size)`` -- the bits PIL and torchvision give.  ``quantised=True``: the cropped uint8 image
+    (H1, W1, 3) before the normalisation instead.  No host wait and no device-to-host copy (the coefficient tables of an image size are
+    made on the host and uploaded once per device)."""
+    if not torch.is_tensor(img) or not img.is_cuda:
+        raise _lib.LvdgsError("format_image: the image must be a tensor on a GPU (there is no CPU path)")
+    if img.ndim != 3 or img.shape[0] != 3:
+        raise ValueError(f"format_image: the image must be (3, H, W), got {tuple(img.shape)}")
+    device = img.device
+    x = _lib.f32(img, device)
+    H, W = int(x.shape[1]), int(x.shape[2])
+    p, table_x, table_y = _format_plan(device, W, H, int(size))
+    L = _lib.lib()
+    need = L.lvdgs_format_scratch_bytes(W, H, int(size))
+    scratch = _format_scratch.get(device.index)
+    if scratch is None or scratch.numel() < need:
+        scratch = _format_scratch[device.index] = torch.empty(max(int(need), 256), dtype=torch.uint8, device=device)
+    out = torch.empty((1, 3, p.out_height, p.out_width), dtype=torch.float32, device=device)
+    q = torch.empty((p.out_height, p.out_width, 3), dtype=torch.uint8, device=device) if quantised else None
+    a = _lib.FormatImageArgs(width=W, height=H, size=int(size), image=x.data_ptr(), table_x=table_x.data_ptr(), table_y=table_y.data_ptr(),
+                             out=out.data_ptr(), quantised=None if q is None else q.data_ptr(), scratch=scratch.data_ptr(),
+                             scratch_bytes=scratch.numel())
+    with _lib.on_device(device):
+        _lib.check(L.lvdgs_format_image(C.byref(a), _lib.raw_stream(device)), "lvdgs_format_image")
+    return q if quantised else out
+
+
+def torch_images_to_dust3r_format(tensor_images, size, square_ok=False, verbose=False):
+    """The reference's function (same signature; utils/init_pose.py:35-75) -> its list of dicts ``img`` (1, 3, H1, W1), ``true_shape`` =
+    ``np.int32([[H1, W1]])``, ``idx``, ``instance``.  Deviation: ``img`` is a tensor on the images' device -- the frames never visit the
+    host.  ``square_ok=True`` (a square image kept square) is not supported: the reference never passes it."""
+    if square_ok:
+        raise ValueError("torch_images_to_dust3r_format: square_ok=True is not supported")
+    imgs = []
+    for idx, image in enumerate(tensor_images):
+        img = format_image(image, size)
+        imgs.append(dict(img=img, true_shape=np.int32([[img.shape[2], img.shape[3]]]), idx=idx, instance=str(idx)))
+    assert imgs, "no images found"
+    return imgs
+
+
+class NetworkDescribe:
+    """A ``describe`` for ``DescriptorMatcher`` whose seat is the network alone: both images are formatted on the device
+    (``torch_images_to_dust3r_format``), ``infer(view1, view2, model) -> (pred1, pred2)`` is the reference's ``inference`` -- dicts with
+    ``desc`` (1, H1, W1, D) (and ``pts3d`` (1, H1, W1, 3)) -- and the two (H1, W1, D) descriptor maps come back, checked against the
+    raster the matcher was given."""
+
+    def __init__(self, infer, size=512):
+        self.infer, self.size = infer, int(size)
+
+    def set_frames(self, keyframe_idx, frame_idx):
+        if hasattr(self.infer, "set_frames"):
+            self.infer.set_frames(keyframe_idx, frame_idx)
+
+    def __call__(self, img1, img2, model, raster):
+        view1, view2 = torch_images_to_dust3r_format([img1, img2], size=self.size)
+        pred1, pred2 = self.infer(view1, view2, model)
+        W1, H1 = raster
+        maps = []
+        for pred in (pred1, pred2):
+            desc = pred["desc"]
+            if desc.ndim != 4 or desc.shape[0] != 1 or tuple(desc.shape[1:3]) != (H1, W1):
+                raise ValueError(f"NetworkDescribe: the network's descriptors are {tuple(desc.shape)}, not (1, {H1}, {W1}, D)")
+            maps.append(desc[0].detach())
+        return maps[0], maps[1]
+
+
+def get_depth(img1, img2, model, *, infer=None, size=512):
+    """The reference's ``get_depth`` (same positional signature; utils/init_pose.py:189-208): the z of the network's pointmap of ``img1``,
+    resized to the frame's (H, W) by ``cv2.INTER_NEAREST``'s rule -- source index ``min(floor(d * n_src / n_dst), n_src - 1)`` -- as plain
+    device indexing.  ``infer`` as in ``NetworkDescribe``.  Deviation: the result is a float32 tensor on the images' device, not NumPy."""
+    if infer is None:
+        raise TypeError("get_depth: the `infer` argument is required (the network is out of scope: infer(view1, view2, model) -> (pred1, pred2))")
+    H, W = int(img1.shape[1]), int(img1.shape[2])
+    view1, view2 = torch_images_to_dust3r_format([img1, img2], size=size)
+    pred1, _ = infer(view1, view2, model)
+    z = pred1["pts3d"][0][..., 2].detach()
+    Hs, Ws = int(z.shape[0]), int(z.shape[1])
+    # (integer arithmetic: floor(d * n_src / n_dst) of the float64 rule, exactly)
+    sx = torch.clamp(torch.arange(W, device=z.device, dtype=torch.int64) * Ws // W, max=Ws - 1)
+    sy = torch.clamp(torch.arange(H, device=z.device, dtype=torch.int64) * Hs // H, max=Hs - 1)
+    return z.index_select(0, sy).index_select(1, sx).to(torch.float32).contiguous()
+
+
 class DescriptorMatcher:
     """The matcher of ``get_pose`` on descriptor maps: ``describe(img1, img2, model, (W1, H1)) -> (desc1, desc2)`` -- the network's seat
-    (MASt3R in the reference, out of scope; ``synthetic.WorldDescriptors`` is the stand-in), (H1, W1, D) tensors on a GPU at the
-    matcher's raster -- followed by ``reciprocal_matches``.  ``set_frames`` goes on to a ``describe`` that has it."""
+    (``NetworkDescribe(infer)`` narrows it to the network alone -- MASt3R in the reference, out of scope; ``synthetic.WorldDescriptors``
+    is the stand-in), (H1, W1, D) tensors on a GPU at the matcher's raster -- followed by ``reciprocal_matches``.  ``set_frames`` goes on to a ``describe`` that has it."""
 
     def __init__(self, describe, subsample=8, max_iter=10):
         self.describe, self.subsample, self.max_iter = describe, int(subsample), int(max_iter)

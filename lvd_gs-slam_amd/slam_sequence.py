@@ -33,7 +33,9 @@ Stand-ins for what is out of scope, all injectable:
     mask, i.e. ``add_new_keyframe``'s own statements for the first keyframe (:1364-1382) applied to every keyframe.  For later
     keyframes the reference blends rendered and mono depth patch by patch and rescales the mono depth (``process_depth``,
     utils/depth_utils.py, :1383-1405): ``keyframe_depth="patch_align"`` does that (``depth_utils.process_depth``, HIP); only the
-    algorithm's scale remedy ``find_scale`` needs MASt3R -- injectable as ``scale_remedy``, by default the current scale is kept;
+    algorithm's scale remedy is injectable as ``scale_remedy``, by default the current scale is kept; ``scale_remedy="matches"`` is
+    the reference's ``find_scale`` on ``matcher``'s matches (``depth_utils.MatchScaleRemedy``: only the descriptor network behind the
+    matcher needs MASt3R);
   * ``dataset.static_mask(idx)`` for the GroundingDINO + SAM masks (``dynamic_masker.get_static_mask_for_gaussian_init``).
 
 ``render_fn`` / ``view_loss_fn`` / ``refine_loss_fn`` / ``knn_fn`` default to the HIP paths; the CPU tests pass the dense float64
@@ -131,6 +133,14 @@ class SlamSequence:
             self.keyframe_depth = keyframe_depth
         else:
             raise ValueError(f"keyframe_depth: None, 'mono', 'patch_align' or a callable, not {keyframe_depth!r}")
+        # scale_remedy="matches": the reference's find_scale on `matcher`'s matches (depth_utils.MatchScaleRemedy)
+        if isinstance(scale_remedy, str):
+            if scale_remedy != "matches":
+                raise ValueError(f"scale_remedy: None, 'matches' or a callable, not {scale_remedy!r}")
+            if matcher is None:
+                raise TypeError("SlamSequence(scale_remedy='matches') needs the `matcher` argument (depth_utils.find_scale's matcher)")
+            from .depth_utils import MatchScaleRemedy
+            scale_remedy = MatchScaleRemedy(matcher)
         self.depth_align_fn, self.scale_remedy = depth_align_fn, scale_remedy
         self.depth_align_params = dict(depth_align_params or {})
         self.depth_align_log = []      # per aligned keyframe: frame, scale_factor, num_accurate_pixels, error_pixel_share, remedy_fired
@@ -265,7 +275,11 @@ class SlamSequence:
 
         def remedy(im1, im2, last_depth, mono_depth, model):
             fired.append(True)
-            return None if self.scale_remedy is None else self.scale_remedy(im1, im2, last_depth, mono_depth, model)
+            if self.scale_remedy is None:
+                return None
+            if hasattr(self.scale_remedy, "set_frames"):      # a matcher that works from the dataset, not from the images
+                self.scale_remedy.set_frames(self.kf_indices[-2], self.kf_indices[-1])
+            return self.scale_remedy(im1, im2, last_depth, mono_depth, model)
 
         with self._timed("depth_align"):
             final, scale, error_mask, num_accurate = fn(render_pkg["depth"].detach(), viewpoint.mono_depth, last_depth=prev.mono_depth,

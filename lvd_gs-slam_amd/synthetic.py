@@ -206,7 +206,7 @@ def make_sequence(truth, render_fn, pipe, W, H, n_frames, device, fx=None, fy=No
     """``n_frames`` frames of ``vehicle_trajectory`` through the map ``truth`` (a GaussianModel), rendered ONCE by ``render_fn``
     (the product's ``render`` on the GPU, the dense float64 renderer in the CPU tests): image = clamped render (+ seeded pixel
     noise), mono depth = expected depth of the opaque pixels x (1 + ``depth_noise`` N(0,1)) -- a metric depth predictor's output,
-    what ``get_depth`` (MASt3R, out of scope) hands the reference's front end.  ``dynamic_objects``: every frame also carries two
+    what ``get_depth`` (the pointmap of MASt3R, which is out of scope) hands the reference's front end.  ``dynamic_objects``: every frame also carries two
     to four flat-coloured rectangles ("vehicles", ``dynamic_object_mask``, redrawn per frame: they move) painted over the image
     and marked dynamic in ``static_mask(idx)``.  ``mono_scale_drift``: frame i's mono depth is further multiplied by
     ``mono_scale_factor(i, mono_scale_drift)`` -- a monocular predictor's per-frame scale inconsistency, what the keyframe depth

@@ -5,7 +5,7 @@ pruning / opacity resets at the reference's cadence -> pruning pass, the back en
 the end ATE (Umeyama), PSNR before / after a colour refinement (lvdgs.slam_sequence.SlamSequence; reference utils/slam_frontend.py:1740-1899,
 utils/slam_backend.py:485-609, utils/eval_utils_0806.py:33-306).
 
-    python tools/sequence.py [--frames 60] [--scale 1.0] [--cadence reference|short] [--no-fused] [--idle 10] [--refine 500] [--no-masks] [--pose-init previous|pnp]
+    python tools/sequence.py [--frames 60] [--scale 1.0] [--cadence reference|short] [--no-fused] [--idle 10] [--refine 500] [--no-masks] [--pose-init previous|pnp] [--scale-remedy keep|matches]
 
 Prints one JSON object (bench.py's config.side.sequence_kitti07_geom is the same record).  `--cadence reference`: the iteration
 counts and densification schedule of configs/mono/KITTI/base_config.yaml as they are; `short`: every burst a fifth of it (the GPU
@@ -112,7 +112,7 @@ def run_sequence(dev, frames=60, scale=1.0, cadence="reference", fused="auto", i
     if sequence_kwargs.get("matcher") == "descriptors":      # descriptor maps matched on the device (the network's stand-in: synthetic.WorldDescriptors)
         from lvdgs import init_pose
         sequence_kwargs["matcher"] = init_pose.DescriptorMatcher(synthetic.WorldDescriptors(ds, seed=seed))
-    if sequence_kwargs.get("pose_init") == "pnp" and sequence_kwargs.get("matcher") is None:
+    if (sequence_kwargs.get("pose_init") == "pnp" or sequence_kwargs.get("scale_remedy") == "matches") and sequence_kwargs.get("matcher") is None:
         sequence_kwargs["matcher"] = synthetic.GroundTruthMatcher(ds, stride=8, noise_px=0.7, outlier_ratio=0.3, seed=seed)
     seq = SlamSequence(cfg, ds, m, PIPE, torch.zeros(3, device=dev), fused=fused, idle_map_iters=idle, on_event=on_event, **sequence_kwargs)
     seq.run()
@@ -160,6 +160,9 @@ def main():
                     help="log every tracked frame's initial pose (summary key pose_init); pnp: start it from init_pose.get_pose with synthetic.GroundTruthMatcher")
     ap.add_argument("--matcher", choices=["ground_truth", "descriptors"], default="ground_truth",
                     help="with --pose-init pnp: matches made from the ground truth (default), or synthetic.WorldDescriptors' maps matched by init_pose.reciprocal_matches")
+    ap.add_argument("--scale-remedy", choices=["keep", "matches"], default="keep",
+                    help="with --keyframe-depth patch_align: keep the current scale when Algorithm 1's remedy branch fires (default), or take "
+                         "depth_utils.find_scale's on the matches of --matcher (ground_truth: synthetic.GroundTruthMatcher)")
     ap.add_argument("--verbose", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -168,7 +171,8 @@ def main():
     out, _ = run_sequence(dev, a.frames, a.scale, a.cadence, False if a.no_fused else "auto", a.idle, a.refine, not a.no_masks, seed=a.seed,
                           window_size=a.window_size, on_event=ev, geometry=a.geometry, pcd_downsample=a.pcd_downsample,
                           mono_scale_drift=a.mono_scale_drift, **({"keyframe_depth": "patch_align"} if a.keyframe_depth == "patch_align" else {}),
-                          **({"pose_init": a.pose_init} if a.pose_init else {}), **({"matcher": "descriptors"} if a.matcher == "descriptors" else {}))
+                          **({"pose_init": a.pose_init} if a.pose_init else {}), **({"matcher": "descriptors"} if a.matcher == "descriptors" else {}),
+                          **({"scale_remedy": "matches"} if a.scale_remedy == "matches" else {}))
     for rec in out.get("pose_init", []):
         print("  frame {frame:3d} kf {keyframe:3d} inliers {inl:>5} init error {e:.4f} ({r:.3f} deg; previous pose {p:.4f}) tracking iterations {it}".format(
             frame=rec["frame"], keyframe=rec["keyframe"], inl=rec.get("inliers", "-"), e=rec["init_translation_error"], r=rec["init_rotation_error_deg"],
