@@ -211,7 +211,7 @@ __device__ __forceinline__ int composite_one(const float4 A, const float2 B, con
 // the kernel that runs the forward and the backward pass of a tile in one launch overlays it with the backward pass's.)
 struct FwdShared {
     float4 a[256], b[256], c[256];
-    float d[256];
+    float4 q[256];    // the quadrant test's own: raw conic c and quad_prepare()'s three values, made once by the staging thread
     int touch[256];   // pixels of this tile each staged Gaussian "touched" (T after it > 0.5)
 };
 template <bool DEEP_LISTS>
@@ -219,7 +219,7 @@ __device__ __forceinline__ void blend_fwd2_body(const BlendParams &p, FwdShared 
     float4 *const s_a = s_recs.a;  // x, y, -a/2*log2e, -b*log2e
     float4 *const s_b = s_recs.b;  // -c/2*log2e, opacity | raw conic a, b (for the quadrant test; survivors read the first half only)
     float4 *const s_c = s_recs.c;  // r, g, b, depth
-    float *const s_d = s_recs.d;   // raw conic c
+    float4 *const s_q = s_recs.q;  // raw conic c, 1/a, 1/c, ln(255 opacity) resp. -inf / +inf (common.hpp: quad_prepare)
     int *const s_touch = s_recs.touch;
 
 #ifdef LVDGS_DIAG_REPEAT   // diagnostic build: the grid repeated $LVDGS_DIAG_REPEAT times (what a launch over several views of this size would cost)
@@ -261,7 +261,8 @@ __device__ __forceinline__ void blend_fwd2_body(const BlendParams &p, FwdShared 
             s_a[tid] = make_float4(r0.x, r0.y, -0.5f * LOG2E * r0.z, -LOG2E * r0.w);
             s_b[tid] = make_float4(-0.5f * LOG2E * r1.x, r1.y, r0.z, r0.w);
             s_c[tid] = make_float4(r1.z, r1.w, r2.x, r2.y);
-            s_d[tid] = r1.x;
+            const QuadBound qb = quad_prepare(r0.z, r0.w, r1.x, r1.y);
+            s_q[tid] = make_float4(r1.x, qb.inv_a, qb.inv_c, qb.bound);
         }
         s_touch[tid] = 0;
         __syncthreads();
@@ -275,9 +276,10 @@ __device__ __forceinline__ void blend_fwd2_body(const BlendParams &p, FwdShared 
                 const int jl = c0 + lane;
                 bool keep = false;
                 if (jl < cnt) {
-                    const float4 A = s_a[jl];
-                    const float4 B = s_b[jl];
-                    keep = reaches_rect(A.x, A.y, B.z, B.w, s_d[jl], B.y, rx0, ry0, rx1, ry1);
+                    const float2 M = *reinterpret_cast<const float2 *>(&s_a[jl]);
+                    const float2 K = *reinterpret_cast<const float2 *>(&s_b[jl].z);
+                    const float4 Q = s_q[jl];
+                    keep = reaches_rect_prepared(M.x, M.y, K.x, K.y, Q.x, Q.y, Q.z, Q.w, rx0, ry0, rx1, ry1);
                 }
                 uint64_t live = __ballot(keep);
                 // ---- lane -> pixel: composite the survivors in list order ----
@@ -407,6 +409,9 @@ struct Bwd3Shared {
     float4 b[BR];                        // -c/2*log2e, opacity, depth, -a/2*log2e
     float4 c[BR];                        // r, g, b, -b*log2e
     float craw[BR];                      // c
+    float2 reach[BR];                    // 1/c, ln(255 opacity) resp. -inf / +inf (common.hpp: quad_prepare), made once by the staging thread.  (Two floats:
+                                         // a third, 1/a, would take the pose-only form with a depth gradient past the LDS of six workgroups per CU;
+                                         // the test takes that one reciprocal itself.)
     uint32_t slot[BR];
     float acc[4][BR * ACC];              // per wave: Sx Sy Sxx Sxy Syy Su C0 C1 C2 CD of every entry it accumulated
     unsigned long long mask[4];
@@ -422,7 +427,7 @@ struct Bwd3Shared {
 #define LVDGS_BWD_WGS 5   // workgroups per CU the backward blend is compiled for (A/B builds)
 #endif
 #ifndef LVDGS_BWD_WGS_POSE
-#define LVDGS_BWD_WGS_POSE 7   // ... and its pose-only form (18.2 KB of LDS, 74 VGPRs; 26.4 KB with a depth gradient: six). Same box, config 3 / KITTI geometry: 5: 240.9 / 92.0 us, 6: 240.4 / 92.1, 7: 233.7 / 92.6, 8: 233.6 / 95.8
+#define LVDGS_BWD_WGS_POSE 7   // ... and its pose-only form (18.7 KB of LDS, 72 VGPRs; 26 880 B with a depth gradient -- all that six leave each). Same box, config 3 / KITTI geometry: 5: 240.9 / 92.0 us, 6: 240.4 / 92.1, 7: 233.7 / 92.6, 8: 233.6 / 95.8
 #endif
 template <int LOSS, bool DEPTH_GRAD, bool POSE_ONLY>
 __device__ __forceinline__ void blend_bwd3_body(const BlendParams &p, Bwd3Shared<POSE_ONLY, DEPTH_GRAD> &sh) {
@@ -555,6 +560,8 @@ __device__ __forceinline__ void blend_bwd3_body(const BlendParams &p, Bwd3Shared
             sh.b[tid] = make_float4(-0.5f * LOG2E * r1.x, r1.y, r2.y, -0.5f * LOG2E * r0.z);
             sh.c[tid] = make_float4(r1.z, r1.w, r2.x, -LOG2E * r0.w);
             sh.craw[tid] = r1.x;
+            const QuadBound qb = quad_prepare(r0.z, r0.w, r1.x, r1.y);
+            sh.reach[tid] = make_float2(qb.inv_c, qb.bound);
             sh.slot[tid] = pair_slot(p, id, tx, ty);
         }
         __syncthreads();
@@ -567,7 +574,8 @@ __device__ __forceinline__ void blend_bwd3_body(const BlendParams &p, Bwd3Shared
             bool keep = false;
             if (lane < cnt && base + lane < wave_last) {
                 const float4 A = sh.a[lane];
-                keep = reaches_rect(A.x, A.y, A.z, A.w, sh.craw[lane], sh.b[lane].y, rx0, ry0, rx1, ry1);
+                const float2 Q = sh.reach[lane];
+                keep = reaches_rect_prepared(A.x, A.y, A.z, A.w, sh.craw[lane], __builtin_amdgcn_rcpf(A.z), Q.x, Q.y, rx0, ry0, rx1, ry1);
             }
             uint64_t live = __ballot(keep);
             const uint32_t rel_last = my_last > (uint32_t)base ? my_last - (uint32_t)base : 0u;  // entries below this position composited

@@ -97,6 +97,51 @@ __device__ __forceinline__ bool reaches_rect(float mx, float my, float a, float 
     return qmin <= __logf(op * 255.f) + margin;
 }
 
+// reaches_rect() in two steps, for callers that test one Gaussian against several rectangles (the blend kernels: the
+// four 8x8 quadrants of a tile).  THE SAME BOOLEAN as reaches_rect() for every finite input -- which survivors a
+// quadrant walks decides the order its pixels' gradients are summed in, so "conservative as well" is not enough
+// (tools/quadrant_reach_check.hip compares the two forms case by case).
+//  * quad_prepare(), once per Gaussian: the two reciprocals and ln(255 op) by reaches_rect()'s own operations, and its two
+//    early exits folded into the bound -- -inf: opacity below 1/255, never; +inf: not an ellipse, always.
+//  * reaches_rect_prepared(), once per rectangle: q on the edges that face the mean only (FACING_EDGES; the sign tests
+//    are reaches_rect()'s, the expressions on a chosen edge too).  A convex q with its minimum at the mean decreases along
+//    the segment from any point of the rectangle to the mean, and that segment leaves through a facing edge, so the minimum
+//    over the facing edges is the minimum over all four; an edge that does not face the mean counts as +inf.  A mean inside
+//    the rectangle counts as q = 0, which passes every bound but -inf.  The clamps keep q finite whatever the reciprocals
+//    are (fmaxf / fminf drop a NaN), so a finite conic meets +-inf with a finite q.
+struct QuadBound { float inv_a, inv_c, bound; };
+__device__ __forceinline__ QuadBound quad_prepare(float a, float b, float c, float op) {
+    const bool never = !(op >= ALPHA_MIN), always = !(a > 0.f && c > 0.f && a * c - b * b > 0.f);
+    const float inf = __builtin_inff();
+    return {__builtin_amdgcn_rcpf(a), __builtin_amdgcn_rcpf(c), never ? -inf : (always ? inf : __logf(op * 255.f))};
+}
+template <bool FACING_EDGES = true>
+__device__ __forceinline__ bool reaches_rect_prepared(float mx, float my, float a, float b, float c, float inv_a, float inv_c, float bound,
+                                                      float x0, float y0, float x1, float y1) {
+    const float dx_lo = mx - x1, dx_hi = mx - x0, dy_lo = my - y1, dy_hi = my - y0;  // d = mean - pixel
+    auto along_y = [&](float dx) {
+        const float dy = fminf(fmaxf(-b * dx * inv_c, dy_lo), dy_hi);
+        return 0.5f * (a * dx * dx + c * dy * dy) + b * dx * dy;
+    };
+    auto along_x = [&](float dy) {
+        const float dx = fminf(fmaxf(-b * dy * inv_a, dx_lo), dx_hi);
+        return 0.5f * (a * dx * dx + c * dy * dy) + b * dx * dy;
+    };
+    const float inf = __builtin_inff();
+    float qmin;
+    if constexpr (FACING_EDGES) {
+        const bool right = dx_lo > 0.f, left = dx_hi < 0.f, below = dy_lo > 0.f, above = dy_hi < 0.f;
+        const float qx = along_y(right ? dx_lo : dx_hi), qy = along_x(below ? dy_lo : dy_hi);
+        qmin = (right || left || below || above) ? fminf((right || left) ? qx : inf, (below || above) ? qy : inf) : 0.f;
+    } else {
+        const bool in = dx_lo <= 0.f && dx_hi >= 0.f && dy_lo <= 0.f && dy_hi >= 0.f;
+        qmin = in ? 0.f : fminf(fminf(along_y(dx_lo), along_y(dx_hi)), fminf(along_x(dy_lo), along_x(dy_hi)));
+    }
+    const float dxm = fmaxf(fabsf(dx_lo), fabsf(dx_hi)), dym = fmaxf(fabsf(dy_lo), fabsf(dy_hi));
+    const float margin = 0.02f + 2e-5f * (a * dxm * dxm + c * dym * dym);
+    return qmin <= bound + margin;
+}
+
 // reaches_rect() for the tiles of one Gaussian's rectangle, with the per-Gaussian part hoisted: the same bound (exact
 // minimum of q over the tile against ln(255 op) plus the rounding margin, here the margin of the whole rectangle), the
 // minimum taken over the two edges that face the mean -- a convex q with its minimum at the mean cannot have its

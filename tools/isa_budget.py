@@ -3,13 +3,16 @@
 gfx950 assembly, cuts the kernel into the regions of its inner loop by what the code between two labels contains, and counts
 instructions by kind.  Writes a markdown table (stdout).  Needs no GPU.
 
-    python3 tools/isa_budget.py > profiles/r04_blend_bwd_isa_budget.md
+    python3 tools/isa_budget.py > profiles/quadrant_test/blend_bwd_isa_budget.md
+    (profiles/r04_blend_bwd_isa_budget.md: the table of round 4, when the quadrant test was reaches_rect() whole)
 
 Regions:  pixel pass, straight-line  = the code between two labels that holds eight v_exp_f32 (a full batch of eight survivors);
           pixel pass, rolled         = the loop body with one v_exp_f32 and one M store (the last, partial batch of a round);
           splat pass                 = the code with the DPP subtracts / multiply-adds (one per batch, full or not);
-          quadrant test              = the code with v_log_f32 (reaches_rect: 64 staged entries per execution and wave);
-          everything else            = prologue (fused loss), staging, flush, loop control."""
+          quadrant test              = the code with a v_rcp_f32 and the clamps' v_min_f32 / v_max_f32 but neither v_exp_f32 nor v_log_f32 (reaches_rect_prepared: 64 staged
+                                       entries per execution and wave; its one reciprocal is 1/a);
+          staging                    = the code with v_log_f32 (quad_prepare: once per round of 64 entries, the first wave alone);
+          everything else            = prologue (fused loss), flush, loop control."""
 import os, re, subprocess, sys, collections
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "lvd_gs-slam_amd", "csrc", "blend.hip")
@@ -48,7 +51,8 @@ def budget(name_re, title):
         cur.append(("valu_dpp" if (k == "valu" and dpp) else k, op))
     segs.append(cur)
     regions = collections.OrderedDict((r, collections.Counter()) for r in ("pixel pass, straight-line batch of 8", "pixel pass, rolled (per entry)",
-                                                                          "splat pass (per batch)", "quadrant test (per 64 staged entries and wave)", "everything else"))
+                                                                          "splat pass (per batch)", "quadrant test (per 64 staged entries and wave)",
+                                                                          "staging with quad_prepare (per round of 64 entries)", "everything else"))
     for s in segs:
         ops = [o for _, o in s]
         n_exp = sum(o.startswith("v_exp_f32") for o in ops)
@@ -56,7 +60,9 @@ def budget(name_re, title):
         if n_exp >= 8: r = "pixel pass, straight-line batch of 8"
         elif n_exp == 1 and any(o.startswith("ds_write") for o in ops) and any(o.startswith("v_rcp") for o in ops): r = "pixel pass, rolled (per entry)"
         elif has_dppmac: r = "splat pass (per batch)"
-        elif any(o.startswith("v_log_f32") for o in ops): r = "quadrant test (per 64 staged entries and wave)"
+        elif any(o.startswith("v_log_f32") for o in ops): r = "staging with quad_prepare (per round of 64 entries)"
+        elif n_exp == 0 and any(o.startswith("v_rcp_f32") for o in ops) and sum(o.startswith(("v_min_f32", "v_max_f32")) for o in ops) >= 4:
+            r = "quadrant test (per 64 staged entries and wave)"
         else: r = "everything else"
         for k, _ in s: regions[r][k] += 1
     print(f"### {title}\n\n`{name}`\n")
@@ -75,9 +81,9 @@ FILL = 0.9045   # tools/fill_diag.py on the GPU, config 3: survivors / (8 x batc
 print("# blend_bwd3: instructions per surviving (quadrant, Gaussian), from the gfx950 disassembly\n")
 print("Static counts of the code regions (one execution each); `tools/isa_budget.py` regenerates this file.  Issue cost relative to a plain "
       "vector instruction (tools/valu_clock.hip, 8 waves/SIMD): transcendental 3.25, DPP 1.5, v_permlane*_swap 2.7.\n")
-full = budget(r"17blend_bwd3_kernelILb1ELb0ELb0EEE", "Full backward, fused loss, no depth gradient (the bench's headline step)")
+full = budget(r"17blend_bwd3_kernelILi1ELb0ELb0EEE", "Full backward, fused loss, no depth gradient (the bench's headline step)")
 print()
-pose = budget(r"17blend_bwd3_kernelILb1ELb0ELb1EEE", "Pose-only backward (LVDGS_FLAG_POSE_ONLY), fused loss, no depth gradient (the tracking loop's step)")
+pose = budget(r"17blend_bwd3_kernelILi1ELb0ELb1EEE", "Pose-only backward (LVDGS_FLAG_POSE_ONLY), fused loss, no depth gradient (the tracking loop's step)")
 
 # ---- reconciliation with the counters (profiles/traffic.json: SQ_INSTS_VALU of separate rocprofv3 --pmc passes) ----
 import json
