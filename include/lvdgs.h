@@ -782,6 +782,92 @@ typedef struct lvdgs_match_scale_args {
 } lvdgs_match_scale_args;
 int lvdgs_match_depth_scale(const lvdgs_match_scale_args *a, void *stream);
 
+/* ---- the edge mask of the tracking loss (reference utils/camera_utils.py compute_grad_mask :126-155: a channel mean, two reflect
+ * pads, the Scharr gradients and the validity mask as convolutions, a magnitude, and a full sort of the image for its median) ----
+ * image: (3, height, width) float32, contiguous, channels r, g, b.  All arithmetic is IEEE float32 in exactly this order, no
+ * contraction, division and square root correctly rounded:
+ *   gray = ((r + g) + b) / 3;  p = gray with ONE reflected pixel on each side (NumPy's pad mode "reflect": p[-1] = gray[1],
+ *   p[n] = gray[n - 2]), so width and height must be at least 2.  With p[row][col] the 3 x 3 window around a pixel:
+ *   gv = (((((p00*3 + p01*10) + p02*3) + p20*(-3)) + p21*(-10)) + p22*(-3)) * (1/32)
+ *   gh = (((((p00*3 + p02*(-3)) + p10*10) + p12*(-10)) + p20*3) + p22*(-3)) * (1/32)
+ *   full = |p| > 0.01f at all nine taps;  gv, gh are multiplied by full as 0 / 1;  mag = sqrtf(gv*gv + gh*gh).
+ * The MEDIAN of n values is the (n - 1) / 2-th smallest (integer division; torch.median's lower median), found by radix selection on
+ * the bit patterns: the bits a sort would give.  A NaN magnitude (a non-finite image) is outside the contract.
+ * mode LVDGS_EDGE_MASK_MEDIAN: cut = median(mag) * (float)edge_threshold; mask: height*width bytes, 1 where mag > cut, else 0 -- a
+ *   torch.bool tensor's storage, and the bytes the photometric loss takes as grad_mask.
+ * mode LVDGS_EDGE_MASK_BLOCKS (the reference's rule for the "replica" dataset type): bh = height / 32, bw = width / 32 (integer
+ *   division; width and height must be at least 32); block (i, j), 0 <= i, j < 32, is rows i bh .. i bh + bh - 1, columns j bw ..
+ *   j bw + bw - 1, and has its own cut = median(its bh bw magnitudes) * (float)edge_threshold.  mask: height*width FLOAT32; inside
+ *   the grid v = mag > cut ? 1 : mag, then v <= cut ? 0 : v (the reference's two assignments in their order: a cut of 1 or more
+ *   clears the ones again); the rows and columns outside the grid keep their magnitude.
+ * loss_mask (optional, may be NULL): height*width bytes, result != 0 -- the photometric loss' grad_mask in either mode (mode MEDIAN:
+ *   the same bytes as mask).  magnitude (optional): mag, height*width float32.  stats (optional): (median, cut) as two float32, in
+ *   mode BLOCKS per block: 2 * 1024 float32, block i * 32 + j at [2 (32 i + j)].  Both are for tests.
+ * Mode MEDIAN: a clear of the selection state and six launches; mode BLOCKS: two launches.  All enqueued at once; no host wait, no copy.
+ * scratch: the bytes lvdgs_edge_mask_scratch_bytes gives for (width, height) (0: the size is refused), no initialisation needed.
+ * Two calls give the same bytes.
+ * LVDGS_E_INVALID: args NULL, an unknown mode, image / mask / scratch NULL, scratch too small; LVDGS_E_RANGE: width or height below 2
+ * (mode BLOCKS: below 32), or more than 2^31 - 1 pixels. */
+enum {
+    LVDGS_EDGE_MASK_MEDIAN = 0,
+    LVDGS_EDGE_MASK_BLOCKS = 1
+};
+typedef struct lvdgs_edge_mask_args {
+    int32_t width, height, mode;
+    double edge_threshold;        /* config Training.edge_threshold; rounded to float32  */
+    const float *image;           /* 3*H*W                                          */
+    void *mask;                   /* out: H*W bytes (MEDIAN) / H*W float32 (BLOCKS)  */
+    uint8_t *loss_mask;           /* out H*W bytes, or NULL                         */
+    float *magnitude;             /* out H*W, or NULL                               */
+    float *stats;                 /* out 2 (MEDIAN) / 2*1024 (BLOCKS) float32, or NULL */
+    void *scratch; size_t scratch_bytes;
+} lvdgs_edge_mask_args;
+size_t lvdgs_edge_mask_scratch_bytes(int32_t width, int32_t height);
+int lvdgs_edge_mask(const lvdgs_edge_mask_args *a, void *stream);
+
+/* ---- what the front end reads after a frame's last tracking iteration (reference utils/slam_utils.py get_median_depth :124-134: a
+ * boolean gather and a sort; utils/slam_frontend.py is_keyframe / add_to_window :1579-1674: two counts read per keyframe) ----
+ * Median depth.  Pixel i of num_pixels is SELECTED when depth[i] > 0, opacity[i] > opacity_bar (opacity NULL: no such test) and
+ *   mask[i] != 0 (mask NULL: no such test); NaN fails every test.  The result is the (n - 1) / 2-th smallest of the n selected depths
+ *   (integer division), by radix selection on the bit patterns: the bits torch.median gives.  n == 0: the quiet NaN 0x7fc00000.
+ * Covisibility.  cur[g] = n_touched[g] > 0 for Gaussian g of num_gaussians.  For row r of num_rows (rows[r]: num_gaussians bytes,
+ *   nonzero = visible from that keyframe): intersection = #(cur & row), union = #(cur | row), own = #row.  visible = #cur.
+ * mask_count = the nonzero bytes of count_mask (num_pixels bytes; NULL: 0).
+ * A clear of the state and six launches, enqueued at once; no host wait.  host_state: LVDGS_FRAME_SUMMARY_HOST_BYTES bytes of
+ * page-locked, mapped host memory (the host address), as int32 words: [LVDGS_FRAME_SUMMARY_SEQ] the call's `seq`, WRITTEN LAST -- a
+ * caller that passes a fresh seq and, after synchronising the stream once, finds it there has the whole block --,
+ * [_MEDIAN] the median's float bits, [_SELECTED] n, [_VISIBLE], [_MASK_COUNT], zeros up to LVDGS_FRAME_SUMMARY_ROWS, then three
+ * words per row, LVDGS_FRAME_SUMMARY_MAX_ROWS of them: intersection, union, own (zero for the rows not passed).
+ * scratch: the bytes lvdgs_frame_summary_scratch_bytes gives, no initialisation needed.  Integer sums only: two calls give the same bytes.
+ * LVDGS_E_RANGE: num_rows outside 0..LVDGS_FRAME_SUMMARY_MAX_ROWS, num_gaussians < 0, num_pixels < 0; LVDGS_E_INVALID: args NULL,
+ * host_state / scratch NULL, depth NULL with num_pixels > 0, n_touched or one of the rows NULL with num_gaussians > 0, scratch too
+ * small -- all before any launch; LVDGS_E_HIP: host_state is not mapped pinned memory. */
+#define LVDGS_FRAME_SUMMARY_MAX_ROWS 16
+#define LVDGS_FRAME_SUMMARY_HOST_BYTES 256
+enum {
+    LVDGS_FRAME_SUMMARY_SEQ = 0,
+    LVDGS_FRAME_SUMMARY_MEDIAN = 1,
+    LVDGS_FRAME_SUMMARY_SELECTED = 2,
+    LVDGS_FRAME_SUMMARY_VISIBLE = 3,
+    LVDGS_FRAME_SUMMARY_MASK_COUNT = 4,
+    LVDGS_FRAME_SUMMARY_ROWS = 8
+};
+typedef struct lvdgs_frame_summary_args {
+    int32_t num_pixels, num_gaussians, num_rows;
+    uint32_t seq;
+    float opacity_bar;            /* get_median_depth's 0.95                        */
+    const float *depth;           /* num_pixels                                     */
+    const float *opacity;         /* num_pixels, or NULL                            */
+    const uint8_t *mask;          /* num_pixels bytes, or NULL                      */
+    const int32_t *n_touched;     /* num_gaussians                                  */
+    const uint8_t *rows[LVDGS_FRAME_SUMMARY_MAX_ROWS];   /* num_rows of num_gaussians bytes */
+    const uint8_t *count_mask;    /* num_pixels bytes, or NULL                      */
+    int32_t *host_state;          /* LVDGS_FRAME_SUMMARY_HOST_BYTES, pinned host (the host address) */
+    void *scratch; size_t scratch_bytes;
+} lvdgs_frame_summary_args;
+size_t lvdgs_frame_summary_scratch_bytes(void);
+int lvdgs_frame_summary(const lvdgs_frame_summary_args *a, void *stream);
+
 /* ---- diagnostics ---- */
 const char *lvdgs_last_error(void);
 const char *lvdgs_version(void);

@@ -193,6 +193,29 @@ MATCH_SCALE_STATE_WORDS, MATCH_SCALE_HOST_BYTES = 8, 64
 MATCH_SCALE_OK, MATCH_SCALE_NO_VALID = 1, 2
 
 
+class EdgeMaskArgs(C.Structure):
+    """struct lvdgs_edge_mask_args (include/lvdgs.h)."""
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32), ("mode", C.c_int32), ("edge_threshold", C.c_double),
+        ("image", _fp), ("mask", _fp), ("loss_mask", _fp), ("magnitude", _fp), ("stats", _fp),
+        ("scratch", _fp), ("scratch_bytes", C.c_size_t),
+    ]
+
+
+EDGE_MASK_MEDIAN, EDGE_MASK_BLOCKS = 0, 1
+FRAME_SUMMARY_MAX_ROWS, FRAME_SUMMARY_HOST_BYTES = 16, 256
+FRAME_SUMMARY_SEQ, FRAME_SUMMARY_MEDIAN, FRAME_SUMMARY_SELECTED, FRAME_SUMMARY_VISIBLE, FRAME_SUMMARY_MASK_COUNT, FRAME_SUMMARY_ROWS = 0, 1, 2, 3, 4, 8
+
+
+class FrameSummaryArgs(C.Structure):
+    """struct lvdgs_frame_summary_args (include/lvdgs.h)."""
+    _fields_ = [
+        ("num_pixels", C.c_int32), ("num_gaussians", C.c_int32), ("num_rows", C.c_int32), ("seq", C.c_uint32), ("opacity_bar", C.c_float),
+        ("depth", _fp), ("opacity", _fp), ("mask", _fp), ("n_touched", _fp), ("rows", _fp * FRAME_SUMMARY_MAX_ROWS), ("count_mask", _fp),
+        ("host_state", _fp), ("scratch", _fp), ("scratch_bytes", C.c_size_t),
+    ]
+
+
 class StateLayout(C.Structure):
     _fields_ = [(n, C.c_size_t) for n in (
         "geom_rec", "geom_tiles_touched", "geom_slot_base", "bin_point_list", "bin_tile_keys",
@@ -215,6 +238,7 @@ EXPORTS = (
     "lvdgs_masked_loss_scratch_bytes", "lvdgs_masked_loss_batch", "lvdgs_backward_masked_loss", "lvdgs_blend_backward_window_batch", "lvdgs_forward_batch", "lvdgs_forward_backward_fused_loss", "lvdgs_map_view_tail_batch", "lvdgs_gaussian_backward_batch",
     "lvdgs_depth_align_scratch_bytes", "lvdgs_depth_align", "lvdgs_depth_align_resume", "lvdgs_pnp_scratch_bytes", "lvdgs_pnp_ransac", "lvdgs_recip_nn_scratch_bytes", "lvdgs_reciprocal_nn",
     "lvdgs_format_plan_query", "lvdgs_format_table", "lvdgs_format_scratch_bytes", "lvdgs_format_image", "lvdgs_match_depth_scale",
+    "lvdgs_edge_mask_scratch_bytes", "lvdgs_edge_mask", "lvdgs_frame_summary_scratch_bytes", "lvdgs_frame_summary",
     "lvdgs_last_error", "lvdgs_version", "lvdgs_profile_enable",
     "lvdgs_profile_reset", "lvdgs_profile_read",
 )
@@ -314,6 +338,12 @@ def lib():
         L.lvdgs_format_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
         L.lvdgs_format_image.argtypes = [C.POINTER(FormatImageArgs), C.c_void_p]
         L.lvdgs_match_depth_scale.argtypes = [C.POINTER(MatchScaleArgs), C.c_void_p]
+        L.lvdgs_edge_mask_scratch_bytes.restype = C.c_size_t
+        L.lvdgs_edge_mask_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
+        L.lvdgs_edge_mask.argtypes = [C.POINTER(EdgeMaskArgs), C.c_void_p]
+        L.lvdgs_frame_summary_scratch_bytes.restype = C.c_size_t
+        L.lvdgs_frame_summary_scratch_bytes.argtypes = []
+        L.lvdgs_frame_summary.argtypes = [C.POINTER(FrameSummaryArgs), C.c_void_p]
         L.lvdgs_profile_enable.argtypes = [C.c_int]
         L.lvdgs_profile_read.argtypes = [C.POINTER(KernelTime), C.c_int]
         _lib = L

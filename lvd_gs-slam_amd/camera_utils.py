@@ -11,6 +11,7 @@ versions and compares by identity), which takes about ten launches off every tra
 import torch
 from torch import nn
 
+from ._lib import f32 as _f32
 from .graphics_utils import getProjectionMatrix2, getWorld2View2
 from .slam_utils import image_gradient, image_gradient_mask
 
@@ -86,8 +87,15 @@ class Camera(nn.Module):
         self.T = t.to(device=self.device)
 
     # ---- edge mask of the tracking loss (utils/camera_utils.py:126-155) ---------------------------
-    def compute_grad_mask(self, config):
+    def compute_grad_mask(self, config, fused=False):
+        """``fused``: one ``frame_stats.edge_mask`` call (HIP; the image must be on a GPU) in place of the statements below.  Its
+        grey image is a sum divided by three where ``mean`` multiplies by a rounded third, so a pixel whose magnitude sits
+        on the cut may fall on its other side: the default stays this PyTorch path."""
         thr = config["Training"]["edge_threshold"]
+        if fused:
+            from .frame_stats import edge_mask
+            self.grad_mask = edge_mask(_f32(self.original_image, self.original_image.device), thr, config["Dataset"]["type"])
+            return
         gray = self.original_image.mean(dim=0, keepdim=True)
         gv, gh = image_gradient(gray)
         mv, mh = image_gradient_mask(gray)

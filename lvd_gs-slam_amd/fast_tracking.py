@@ -259,9 +259,9 @@ class TrackingSession:
 
 
 def track_frame_fused(viewpoint, gaussians, config, pipeline_params, background, tracking_itr_num=None, on_iteration=None,
-                      poll_lag=2):
+                      poll_lag=2, median_depth=True):
     """``slam_loops.track_frame`` on a ``TrackingSession``: same arguments, same results (render package of the last
-    iteration, median depth, iterations run), no autograd, no host synchronisation inside the loop."""
+    iteration, median depth -- None with ``median_depth=False`` --, iterations run), no autograd, no host synchronisation inside the loop."""
     n_iter = config["Training"]["tracking_itr_num"] if tracking_itr_num is None else tracking_itr_num
     sess = TrackingSession(viewpoint, gaussians, config, pipeline_params, background)
     losses = torch.zeros(max(n_iter, 1), dtype=torch.float32, device=sess.dev) if on_iteration is not None else None
@@ -282,4 +282,4 @@ def track_frame_fused(viewpoint, gaussians, config, pipeline_params, background,
         for it, v in enumerate(losses[:applied].cpu()):
             on_iteration(it, v, None)
     pkg = sess.render_package()
-    return pkg, get_median_depth(pkg["depth"], pkg["opacity"]), applied
+    return pkg, (get_median_depth(pkg["depth"], pkg["opacity"]) if median_depth else None), applied

@@ -29,34 +29,45 @@ def covisibility(cur_visibility: torch.Tensor, kf_visibility: torch.Tensor) -> T
 
 
 def is_keyframe(config, cameras: Dict, cur_frame_idx, last_keyframe_idx, cur_frame_visibility_filter, occ_aware_visibility,
-                median_depth) -> bool:
+                median_depth, covis=None, mask_share=None) -> bool:
     """Does the tracked frame become a keyframe?  (reference :1579-1619)
 
     Yes when it has moved more than ``kf_translation`` median depths from the last keyframe, or more than
     ``kf_min_translation`` median depths while sharing less than ``kf_overlap`` (intersection over union) of the visible
-    Gaussians with it.  A frame whose expanded static mask covers under 30 % of the image lowers the overlap bar to 70 %."""
+    Gaussians with it.  A frame whose expanded static mask covers under 30 % of the image lowers the overlap bar to 70 %.
+
+    ``covis`` ({keyframe: ``covisibility``'s tuple}, ``frame_stats.frame_summary(...).covis``) and ``mask_share`` (the mean of the
+    frame's ``expanded_static_mask``) stand for the counts this function otherwise reads from the device one at a time; with both
+    given (and a float ``median_depth``) the two visibility arguments are not looked at and the only device values read are the
+    two poses."""
     T = config["Training"]
     cur, last = cameras[cur_frame_idx], cameras[last_keyframe_idx]
     dist = float(_relative_translation(cur, last))
     far = dist > T["kf_translation"] * float(median_depth)
     moved = dist > T["kf_min_translation"] * float(median_depth)
-    inter, union, _, _ = covisibility(cur_frame_visibility_filter, occ_aware_visibility[last_keyframe_idx])
+    if covis is not None:
+        inter, union, _, _ = covis[last_keyframe_idx]
+    else:
+        inter, union, _, _ = covisibility(cur_frame_visibility_filter, occ_aware_visibility[last_keyframe_idx])
     overlap_bar = T["kf_overlap"]
     mask = getattr(cur, "expanded_static_mask", None)
-    if mask is not None and float(mask.float().mean()) < 0.3:
+    if mask is not None and (float(mask.float().mean()) if mask_share is None else mask_share) < 0.3:
         overlap_bar = overlap_bar * 0.7
     ratio = inter / union if union else float("nan")
     return bool((ratio < overlap_bar and moved) or far)
 
 
 def add_to_window(config, cameras: Dict, cur_frame_idx, cur_frame_visibility_filter, occ_aware_visibility, window: Sequence,
-                  initialized: bool = True) -> Tuple[List, Optional[int]]:
+                  initialized: bool = True, covis=None) -> Tuple[List, Optional[int]]:
     """The window with the new keyframe in front, and the keyframe that left it, if any (reference :1621-1674).
 
     The two newest keyframes always stay.  Of the others, the LAST one (oldest) whose covisibility with the new keyframe
     -- intersection over the smaller of the two visible sets -- is at most ``kf_cutoff`` leaves when the window is over
     ``window_size``; if the window is still too large, the keyframe with the largest
-    sqrt(distance to the new keyframe) x sum of inverse distances to the other old keyframes leaves."""
+    sqrt(distance to the new keyframe) x sum of inverse distances to the other old keyframes leaves.
+
+    ``covis``: as in ``is_keyframe``, with an entry for every keyframe of the window behind the two newest; the visibility
+    arguments are then not looked at (the distance rule still reads poses)."""
     T = config["Training"]
     keep_newest = 2
     window = [cur_frame_idx] + list(window)
@@ -64,7 +75,8 @@ def add_to_window(config, cameras: Dict, cur_frame_idx, cur_frame_visibility_fil
     cut_off = T.get("kf_cutoff", 0.4) if initialized else 0.4
     candidates = []
     for kf_idx in window[keep_newest:]:
-        inter, _, n_cur, n_kf = covisibility(cur_frame_visibility_filter, occ_aware_visibility[kf_idx])
+        inter, _, n_cur, n_kf = (covis[kf_idx] if covis is not None else
+                                 covisibility(cur_frame_visibility_filter, occ_aware_visibility[kf_idx]))
         denom = min(n_cur, n_kf)
         ratio = inter / denom if denom else float("nan")
         if ratio <= cut_off and len(window) > T["window_size"]:

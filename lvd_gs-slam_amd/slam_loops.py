@@ -155,7 +155,7 @@ def _can_fuse(viewpoint, gaussians, pipeline_params):
 
 
 def track_frame(viewpoint, gaussians, config, pipeline_params, background, tracking_itr_num=None, render_fn=render,
-                on_iteration=None, fused="auto"):
+                on_iteration=None, fused="auto", median_depth=True):
     """Pose + exposure optimisation of one frame against the map (reference utils/slam_frontend.py:1467-1536): up to
     ``tracking_itr_num`` iterations of render -> get_loss_tracking -> backward -> Adam step -> ``update_pose``, stopping
     when the pose update falls under 1e-4 (utils/pose_utils.py:82).  The frame's initial ``R, T`` (the previous pose, or
@@ -166,10 +166,12 @@ def track_frame(viewpoint, gaussians, config, pipeline_params, background, track
     the frame, the Adam step / retraction / camera matrices in one device kernel, no autograd engine and no host
     synchronisation inside the loop.  ``on_iteration`` then gets (iteration, loss as a 0-dim CPU tensor, None) after
     the loop.  ``fused=False`` (or another ``render_fn``) is the PyTorch loop below, statement for statement the
-    reference's."""
+    reference's.  ``median_depth=False``: None is returned in the median's place (the caller takes it from
+    ``frame_stats.frame_summary`` with everything else it reads after the loop)."""
     if fused is True or (fused == "auto" and render_fn is render and _can_fuse(viewpoint, gaussians, pipeline_params)):
         from .fast_tracking import track_frame_fused
-        return track_frame_fused(viewpoint, gaussians, config, pipeline_params, background, tracking_itr_num, on_iteration)
+        return track_frame_fused(viewpoint, gaussians, config, pipeline_params, background, tracking_itr_num, on_iteration,
+                                 median_depth=median_depth)
     n_iter = config["Training"]["tracking_itr_num"] if tracking_itr_num is None else tracking_itr_num
     pose_optimizer = make_pose_optimizer(viewpoint, config)
     render_pkg, it = None, 0
@@ -187,5 +189,5 @@ def track_frame(viewpoint, gaussians, config, pipeline_params, background, track
         it = tracking_itr + 1
         if converged:
             break
-    median_depth = get_median_depth(render_pkg["depth"], render_pkg["opacity"])
+    median_depth = get_median_depth(render_pkg["depth"], render_pkg["opacity"]) if median_depth else None
     return render_pkg, median_depth, it

@@ -114,7 +114,7 @@ class SlamSequence:
     def __init__(self, config, dataset, gaussians, pipeline_params, background, *, fused="auto", render_fn=render, view_loss_fn=None,
                  refine_loss_fn=None, keyframe_depth=None, idle_map_iters=0, camera_cls=None, cameras_extent=6.0, on_event=None,
                  group=None, aux_group=None, bands_ok=None, depth_align_fn=None, scale_remedy=None, depth_align_params=None,
-                 pose_init=None, matcher=None, pose_init_params=None):
+                 pose_init=None, matcher=None, pose_init_params=None, frame_stats="torch", edge_mask="torch"):
         from .backend_map import map_window
         if camera_cls is None:
             from .camera_utils import Camera as camera_cls
@@ -159,6 +159,15 @@ class SlamSequence:
             raise ValueError(f"pose_init: None, 'previous', 'pnp' or a callable, not {pose_init!r}")
         self.pose_init, self.matcher, self.pose_init_params = pose_init, matcher, dict(pose_init_params or {})
         self.pose_init_log = []        # per tracked frame (pose_init not None): see `tracking`
+        # frame_stats: "torch" (the default: get_median_depth and covisibility, a host wait per count) or "fused" (frame_stats.frame_summary:
+        # the median depth and every count the keyframe test, add_to_window and the frame log read, in one call and one wait per tracked
+        # frame -- the same bits and counts).  edge_mask: "torch" (Camera.compute_grad_mask's PyTorch statements) or "fused"
+        # (frame_stats.edge_mask).  Both fused paths need the frames on a GPU; frames elsewhere keep the PyTorch path.
+        for name, value in (("frame_stats", frame_stats), ("edge_mask", edge_mask)):
+            if value not in ("torch", "fused"):
+                raise ValueError(f"{name}: 'torch' or 'fused', not {value!r}")
+        self.frame_stats, self.edge_mask = frame_stats, edge_mask
+        self._summary = None           # the tracked frame's FrameSummary (frame_stats="fused"), else None
         self.idle_map_iters, self.camera_cls, self.on_event = int(idle_map_iters), camera_cls, on_event
         self._map_window = map_window
         # several ranks (torch.distributed initialised): every rank runs the whole sequence -- tracking, map initialisation and colour
@@ -243,7 +252,10 @@ class SlamSequence:
     def new_viewpoint(self, idx):
         """``Camera.init_from_dataset`` + ``compute_grad_mask`` (utils/slam_frontend.py:1794-1798)."""
         vp = self.camera_cls.init_from_dataset(self.dataset, idx, self.projection_matrix)
-        vp.compute_grad_mask(self.config)
+        if self.edge_mask == "fused" and torch.is_tensor(vp.original_image) and vp.original_image.is_cuda:
+            vp.compute_grad_mask(self.config, fused=True)
+        else:
+            vp.compute_grad_mask(self.config)
         return vp
 
     def _attach_masks(self, viewpoint, idx, first):
@@ -402,9 +414,23 @@ class SlamSequence:
             record = record or dict(frame=cur_frame_idx, keyframe=int(self.current_window[0]), estimated=False)
             record["init_translation_error"], record["init_rotation_error_deg"] = self._pose_error(viewpoint.R, viewpoint.T, viewpoint)
             record["previous_translation_error"], record["previous_rotation_error_deg"] = self._pose_error(prev.R, prev.T, viewpoint)
+        fused_stats = self.frame_stats == "fused" and self.frontend_gaussians.get_xyz.is_cuda
+        self._summary = None
         with self._timed("tracking"):
             render_pkg, median_depth, its = track_frame(viewpoint, self.frontend_gaussians, self.config, self.pipeline_params, self.background,
-                                                        tracking_itr_num=self.tracking_itr_num, render_fn=self.render_fn, fused=self.fused)
+                                                        tracking_itr_num=self.tracking_itr_num, render_fn=self.render_fn, fused=self.fused,
+                                                        **({"median_depth": False} if fused_stats else {}))
+            if fused_stats:
+                from .frame_stats import frame_summary
+                depth, opacity = render_pkg["depth"], render_pkg["opacity"]
+                if _lib.is_f32(depth) and _lib.is_f32(opacity, depth.device) and render_pkg["n_touched"].dtype is torch.int32:
+                    self._summary = frame_summary(dict(depth=depth.detach(), opacity=opacity.detach(), n_touched=render_pkg["n_touched"]),
+                                                  {k: self.occ_aware_visibility[k] for k in self.current_window},
+                                                  count_mask=getattr(viewpoint, "expanded_static_mask", None))
+                    median_depth = self._summary.median_depth
+                else:   # (a renderer that leaves something else than the HIP path's buffers)
+                    from .slam_utils import get_median_depth
+                    median_depth = get_median_depth(depth, opacity)
         self.median_depth = median_depth
         self.counts["tracking_iterations"] += int(its)
         self._last_tracking_iterations = int(its)
@@ -461,20 +487,22 @@ class SlamSequence:
         last_keyframe_idx = self.current_window[0]
         check_time = (cur_frame_idx - last_keyframe_idx) >= self.kf_interval
         curr_visibility = (render_pkg["n_touched"] > 0).long()
+        fs = self._summary
+        covis = None if fs is None else fs.covis
         create_kf = is_keyframe(self.config, self.cameras, cur_frame_idx, last_keyframe_idx, curr_visibility, self.occ_aware_visibility,
-                                self.median_depth)
-        inter, union, _, _ = covisibility(curr_visibility, self.occ_aware_visibility[last_keyframe_idx])
+                                self.median_depth, covis=covis, mask_share=None if fs is None else fs.mask_share)
+        inter, union, _, _ = covis[last_keyframe_idx] if fs is not None else covisibility(curr_visibility, self.occ_aware_visibility[last_keyframe_idx])
         point_ratio = inter / union if union else float("nan")
         if len(self.current_window) < self.window_size:
             create_kf = check_time and point_ratio < self.config["Training"]["kf_overlap"]
         if self.single_thread:
             create_kf = check_time and create_kf
         self.frame_log.append(dict(frame=cur_frame_idx, tracking_iterations=self._last_tracking_iterations, median_depth=float(self.median_depth),
-                                   covisibility=point_ratio, visible=int(curr_visibility.count_nonzero()), keyframe=bool(create_kf),
+                                   covisibility=point_ratio, visible=fs.visible if fs is not None else int(curr_visibility.count_nonzero()), keyframe=bool(create_kf),
                                    gaussians_tracked_against=int(self.frontend_gaussians.get_xyz.shape[0])))
         if create_kf:
             self.current_window, removed = add_to_window(self.config, self.cameras, cur_frame_idx, curr_visibility,
-                                                         self.occ_aware_visibility, self.current_window, initialized=self.initialized)
+                                                         self.occ_aware_visibility, self.current_window, initialized=self.initialized, covis=covis)
             depth_map = self.add_new_keyframe(cur_frame_idx, render_pkg=render_pkg, init=False)
             self.handle_keyframe(cur_frame_idx, viewpoint, depth_map)
             self.counts["keyframes"] += 1

@@ -163,6 +163,11 @@ def main():
     ap.add_argument("--scale-remedy", choices=["keep", "matches"], default="keep",
                     help="with --keyframe-depth patch_align: keep the current scale when Algorithm 1's remedy branch fires (default), or take "
                          "depth_utils.find_scale's on the matches of --matcher (ground_truth: synthetic.GroundTruthMatcher)")
+    ap.add_argument("--frame-stats", choices=["torch", "fused"], default="torch",
+                    help="what a tracked frame reads after its loop (median depth, covisibility counts): PyTorch statements with a host wait "
+                         "per count (default), or one frame_stats.frame_summary call and one wait")
+    ap.add_argument("--edge-mask", choices=["torch", "fused"], default="torch",
+                    help="Camera.compute_grad_mask's PyTorch statements (default) or one frame_stats.edge_mask call")
     ap.add_argument("--verbose", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -172,7 +177,9 @@ def main():
                           window_size=a.window_size, on_event=ev, geometry=a.geometry, pcd_downsample=a.pcd_downsample,
                           mono_scale_drift=a.mono_scale_drift, **({"keyframe_depth": "patch_align"} if a.keyframe_depth == "patch_align" else {}),
                           **({"pose_init": a.pose_init} if a.pose_init else {}), **({"matcher": "descriptors"} if a.matcher == "descriptors" else {}),
-                          **({"scale_remedy": "matches"} if a.scale_remedy == "matches" else {}))
+                          **({"scale_remedy": "matches"} if a.scale_remedy == "matches" else {}),
+                          **({"frame_stats": "fused"} if a.frame_stats == "fused" else {}), **({"edge_mask": "fused"} if a.edge_mask == "fused" else {}))
+    out.update(frame_stats=a.frame_stats, edge_mask=a.edge_mask)
     for rec in out.get("pose_init", []):
         print("  frame {frame:3d} kf {keyframe:3d} inliers {inl:>5} init error {e:.4f} ({r:.3f} deg; previous pose {p:.4f}) tracking iterations {it}".format(
             frame=rec["frame"], keyframe=rec["keyframe"], inl=rec.get("inliers", "-"), e=rec["init_translation_error"], r=rec["init_rotation_error_deg"],
