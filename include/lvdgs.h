@@ -249,6 +249,32 @@ int lvdgs_rope2d(float *tokens, const int64_t *positions, int32_t B, int32_t N, 
 enum { LVDGS_F32 = 0, LVDGS_F16 = 1, LVDGS_BF16 = 2 };
 int lvdgs_rope2d_strided(void *tokens, int32_t dtype, const int64_t *positions, int32_t B, int32_t N, int32_t H, int32_t D,
                          int64_t stride_b, int64_t stride_n, int64_t stride_h, float base, float fwd, void *stream);
+/* Multi-scale deformable attention (Deformable-DETR; GroundingDINO's groundingdino._C.ms_deform_attn_forward / _backward,
+ * reference GroundingDINO-main/groundingdino/models/GroundingDINO/ms_deform_attn.py:53, :80), float32.  For level l of
+ * size (h, w): x = loc_x * w - 0.5, y = loc_y * h - 0.5; a sample takes part only if y > -1 && x > -1 && y < h && x < w, each
+ * of its four corners only if it lies inside the level, and
+ *     out[b, q, h, :] = sum_{l, p} weight * sum_corners bilinear * value[b, start_l + yy * w + xx, h, :].
+ * spatial_shapes and level_start are DEVICE memory and are read on the device; no call waits for the host.  A corner is read
+ * (or, in the backward, added to) only if its flattened index is below S, and NaN, infinite or huge locations take no part:
+ * shapes that do not add up to S give wrong numbers, never an access outside the tensors.  B * Q == 0 or S == 0: LVDGS_OK,
+ * nothing launched (S == 0: the outputs are zero-filled).  The forward and the location / weight gradients are bitwise
+ * reproducible; grad_value is summed by float atomics and may differ in its last bits from run to run. */
+int lvdgs_ms_deform_attn_forward(const float *value,            /* (B, S, H, D) */
+                                 const int64_t *spatial_shapes, /* (L, 2) = (h, w), device */
+                                 const int64_t *level_start,    /* (L), device */
+                                 const float *sampling_loc,     /* (B, Q, H, L, P, 2) = (x, y) in [0, 1] */
+                                 const float *attn_weight,      /* (B, Q, H, L, P) */
+                                 int32_t B, int32_t S, int32_t H, int32_t D, int32_t Q, int32_t L, int32_t P,
+                                 float *out,                    /* (B, Q, H * D) */
+                                 void *stream);
+int lvdgs_ms_deform_attn_backward(const float *value, const int64_t *spatial_shapes, const int64_t *level_start,
+                                  const float *sampling_loc, const float *attn_weight,
+                                  int32_t B, int32_t S, int32_t H, int32_t D, int32_t Q, int32_t L, int32_t P,
+                                  const float *grad_out,        /* (B, Q, H * D) */
+                                  float *grad_value,            /* (B, S, H, D), zeroed by the call */
+                                  float *grad_sampling_loc,     /* (B, Q, H, L, P, 2) */
+                                  float *grad_attn_weight,      /* (B, Q, H, L, P) */
+                                  void *stream);
 
 /* ---- fused photometric losses (reference utils/slam_utils.py:42-121) ---- */
 /*   loss = weight_rgb   * mean_{c,p} [ omega_p * |(e^a I_cp + b) m_p - G_cp m_p| ]

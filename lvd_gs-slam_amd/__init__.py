@@ -14,6 +14,7 @@ Import as ``lvdgs`` (see ``/lvdgs.py``).  Submodules:
   slam_loops         map initialisation and per-frame pose tracking loops
   loss_utils         fused L1 + SSIM and masked depth losses; fused_loss: photometric losses
   gaussian_model     the Gaussian map (parameters, Adam groups, seeding, densify / prune)
+  ms_deform_attn     multi-scale deformable attention (GroundingDINO's ``groundingdino._C``); install() puts it in place
 
 Nothing here falls back to a CPU implementation: the HIP library
 (``lib/liblvdgs.so``) must be present for any render call.

@@ -239,6 +239,7 @@ EXPORTS = (
     "lvdgs_depth_align_scratch_bytes", "lvdgs_depth_align", "lvdgs_depth_align_resume", "lvdgs_pnp_scratch_bytes", "lvdgs_pnp_ransac", "lvdgs_recip_nn_scratch_bytes", "lvdgs_reciprocal_nn",
     "lvdgs_format_plan_query", "lvdgs_format_table", "lvdgs_format_scratch_bytes", "lvdgs_format_image", "lvdgs_match_depth_scale",
     "lvdgs_edge_mask_scratch_bytes", "lvdgs_edge_mask", "lvdgs_frame_summary_scratch_bytes", "lvdgs_frame_summary",
+    "lvdgs_ms_deform_attn_forward", "lvdgs_ms_deform_attn_backward",
     "lvdgs_last_error", "lvdgs_version", "lvdgs_profile_enable",
     "lvdgs_profile_reset", "lvdgs_profile_read",
 )
@@ -344,6 +345,8 @@ def lib():
         L.lvdgs_frame_summary_scratch_bytes.restype = C.c_size_t
         L.lvdgs_frame_summary_scratch_bytes.argtypes = []
         L.lvdgs_frame_summary.argtypes = [C.POINTER(FrameSummaryArgs), C.c_void_p]
+        L.lvdgs_ms_deform_attn_forward.argtypes = [_fp] * 5 + [C.c_int32] * 7 + [_fp, C.c_void_p]
+        L.lvdgs_ms_deform_attn_backward.argtypes = [_fp] * 5 + [C.c_int32] * 7 + [_fp] * 4 + [C.c_void_p]
         L.lvdgs_profile_enable.argtypes = [C.c_int]
         L.lvdgs_profile_read.argtypes = [C.POINTER(KernelTime), C.c_int]
         _lib = L
