@@ -894,6 +894,92 @@ typedef struct lvdgs_frame_summary_args {
 size_t lvdgs_frame_summary_scratch_bytes(void);
 int lvdgs_frame_summary(const lvdgs_frame_summary_args *a, void *stream);
 
+/* ---- dynamic-object masks from the detector's boxes and the segmenter's masks (reference utils/slam_frontend.py
+ * EnhancedDynamicObjectMasker.detect_and_segment :906-1056 after its two networks, _temporal_consistency :1168-1182,
+ * FrontEnd._expand_dynamic_mask :1260-1266, add_new_keyframe :1290-1323 and :1367-1369: NumPy rectangle fills, np.median over a
+ * history, two cv2.dilate, two uploads and two waited-for means) ----
+ * (h, w) = (height, width).  first_frame: detect_and_segment's own flag, frame_idx == 0 or not first_frame_processed (host state).
+ * 1. Boxes.  num_boxes rows of four float32.  LVDGS_DYNAMIC_MASK_BOXES_XYXY: (x1, y1, x2, y2) in pixels, as
+ *    GroundingDINODetector.detect returns them.  LVDGS_DYNAMIC_MASK_BOXES_CXCYWH: the model's normalised (cx, cy, bw, bh), taken
+ *    through detect's float32 statements first (:364-382), in this order with no contraction: cx*w, cy*h, bw*w, bh*h; the two halves
+ *    bw/2, bh/2; x1 = cx - bw/2, y1 = cy - bh/2, x2 = cx + bw/2, y2 = cy + bh/2; x clipped to [0, w], y to [0, h].
+ *    Then the four values are truncated toward zero (astype(int)); x1, x2 are clamped to [0, w-1], y1, y2 to [0, h-1]; the box is
+ *    DROPPED when x2 <= x1 or y2 <= y1.  vehicle[b] != 0 (a host-computed byte: the label contains one of the eight vehicle keywords,
+ *    :926; vehicle NULL: none does) widens a surviving box: ew = (int)((double)(x2-x1) * r), eh = (int)((double)(y2-y1) * r), r = 0.15
+ *    on a first frame, else 0.1 (one float64 product, truncated); x1 = max(0, x1-ew), y1 = max(0, y1-eh), x2 = min(w, x2+ew),
+ *    y2 = min(h, y2+eh).  Rows y1..y2-1, columns x1..x2-1 of the box mask are set.  vehicle_detected: some surviving box is a vehicle's.
+ *    Non-finite coordinates are outside the contract (every store stays inside the frame).
+ * 2. The segmenter.  sam_masks: num_sam_masks masks of h*w bytes each, contiguous, nonzero = object; `union` is their OR.
+ *    use_sam_result = (union has a set pixel) -- data on the device.  final = use_sam_result ? union : box mask (replaced, not merged).
+ * 3. The reference's motion refinement is an identity (logical_and with ~ of a uint8 array, :1134) and is not computed.
+ * 4. Temporal consistency, only when the frame is not first and use_sam_result is 0: final (before any dilation) is appended to the
+ *    history in `state`, the oldest entry dropped when it then holds more than history_length entries; with n >= 3 entries a pixel
+ *    stays set exactly when more than n / 2 of the n entries have it set (np.median(...).astype(uint8); a tie gives 0); with fewer,
+ *    final is unchanged.  The history keeps the unfiltered inputs.
+ * 5. When vehicle_detected, final is dilated by a k x k square of ones, k = vehicle_kernel_first on a first frame, else
+ *    vehicle_kernel (7 and 5 in the reference).  DILATION: a pixel is set when any pixel of its centred k x k window that lies inside
+ *    the image is set.  dynamic = final, static = 1 - dynamic.
+ * 6. expand_kernel != 0 (keyframes: 9 for frame 0, else 7): expanded_dynamic = dynamic dilated by expand_kernel, expanded_static its
+ *    complement, valid_rgb = ((r + g) + b > (float)rgb_boundary_threshold) & expanded_static with image (3, h, w) float32 and the
+ *    float32 sum in that order; depth_out (optional) = depth_in where valid_rgb, else 0.
+ * With num_boxes == 0 the steps run as stated on an empty box mask; the reference's fallback branch (:887-904) is the caller's.
+ * Outputs: h*w bytes of 0 / 1 each -- a torch.bool tensor's storage, the bytes the masked loss reads --, each may be NULL.
+ * info: LVDGS_DYNAMIC_MASK_INFO_WORDS int32 on the device (required; nobody has to read them): [_BOXES] surviving boxes, [_VEHICLE]
+ *   vehicle_detected, [_USE_SAM], [_FILTERED] step 4 ran, [_HISTORY] entries in the history after the call, then the set pixels of
+ *   [_BOX_PIXELS] the box mask, [_SAM_PIXELS] the union, [_DYNAMIC_PIXELS], [_STATIC_PIXELS], [_EXPANDED_PIXELS] expanded_dynamic,
+ *   [_VALID_PIXELS] valid_rgb, [_DEPTH_PIXELS] the pixels of the masked depth above 0 (depth_in given); the rest 0.
+ * state: the persistent history, caller-owned, lvdgs_dynamic_mask_state_bytes bytes: a header (frame size, ring length, entries,
+ *   head) and history_length bit planes.  A zeroed block -- and a block left by another frame size or ring length -- is an empty history.
+ * scratch: lvdgs_dynamic_mask_scratch_bytes bytes, no initialisation needed.  Either size query gives 0 for sizes the call refuses.
+ * A clear of info and four launches (three when expand_kernel == 0), enqueued at once: their number does not depend on the boxes, on
+ * use_sam_result or on the history.  No host wait, no copy.  Integer work only: equal inputs and equal state give equal bytes.
+ * LVDGS_E_INVALID: args NULL; state / scratch / info NULL; boxes or sam_masks NULL with a count above 0; image NULL with
+ * expand_kernel != 0; depth_out without depth_in; an unknown box_format; a vehicle kernel that is even or outside 1..15, an
+ * expand_kernel that is neither 0 nor odd in 1..15; state or scratch too small.  LVDGS_E_RANGE: width or height below 1, more than
+ * 2^31 - 1 pixels, a negative count, history_length outside 1..8.  All before any launch. */
+enum {
+    LVDGS_DYNAMIC_MASK_BOXES_XYXY = 0,
+    LVDGS_DYNAMIC_MASK_BOXES_CXCYWH = 1
+};
+#define LVDGS_DYNAMIC_MASK_INFO_WORDS 16
+enum {
+    LVDGS_DYNAMIC_MASK_INFO_BOXES = 0,
+    LVDGS_DYNAMIC_MASK_INFO_VEHICLE = 1,
+    LVDGS_DYNAMIC_MASK_INFO_USE_SAM = 2,
+    LVDGS_DYNAMIC_MASK_INFO_FILTERED = 3,
+    LVDGS_DYNAMIC_MASK_INFO_HISTORY = 4,
+    LVDGS_DYNAMIC_MASK_INFO_BOX_PIXELS = 5,
+    LVDGS_DYNAMIC_MASK_INFO_SAM_PIXELS = 6,
+    LVDGS_DYNAMIC_MASK_INFO_DYNAMIC_PIXELS = 7,
+    LVDGS_DYNAMIC_MASK_INFO_STATIC_PIXELS = 8,
+    LVDGS_DYNAMIC_MASK_INFO_EXPANDED_PIXELS = 9,
+    LVDGS_DYNAMIC_MASK_INFO_VALID_PIXELS = 10,
+    LVDGS_DYNAMIC_MASK_INFO_DEPTH_PIXELS = 11
+};
+typedef struct lvdgs_dynamic_mask_args {
+    int32_t width, height;
+    int32_t first_frame;          /* detect_and_segment's is_first_frame                */
+    int32_t box_format, num_boxes;
+    const float *boxes;           /* num_boxes * 4                                  */
+    const uint8_t *vehicle;       /* num_boxes bytes, or NULL                       */
+    int32_t num_sam_masks;
+    const uint8_t *sam_masks;     /* num_sam_masks * H*W bytes                      */
+    int32_t history_length;       /* 1..8; the reference's 5                        */
+    int32_t vehicle_kernel_first, vehicle_kernel;   /* 7, 5                         */
+    int32_t expand_kernel;        /* 0: no step 6                                   */
+    const float *image;           /* 3*H*W; may be NULL when expand_kernel == 0     */
+    double rgb_boundary_threshold;  /* config Training.rgb_boundary_threshold; rounded to float32 */
+    const float *depth_in;        /* H*W, or NULL                                   */
+    float *depth_out;             /* out H*W, or NULL                               */
+    uint8_t *static_mask, *dynamic_mask, *expanded_dynamic, *expanded_static, *valid_rgb;   /* out H*W bytes each, or NULL */
+    int32_t *info;                /* out LVDGS_DYNAMIC_MASK_INFO_WORDS              */
+    void *state; size_t state_bytes;
+    void *scratch; size_t scratch_bytes;
+} lvdgs_dynamic_mask_args;
+size_t lvdgs_dynamic_mask_state_bytes(int32_t width, int32_t height, int32_t history_length);
+size_t lvdgs_dynamic_mask_scratch_bytes(int32_t width, int32_t height);
+int lvdgs_dynamic_mask(const lvdgs_dynamic_mask_args *a, void *stream);
+
 /* ---- diagnostics ---- */
 const char *lvdgs_last_error(void);
 const char *lvdgs_version(void);

@@ -216,6 +216,24 @@ class FrameSummaryArgs(C.Structure):
     ]
 
 
+class DynamicMaskArgs(C.Structure):
+    """struct lvdgs_dynamic_mask_args (include/lvdgs.h)."""
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32), ("first_frame", C.c_int32), ("box_format", C.c_int32), ("num_boxes", C.c_int32),
+        ("boxes", _fp), ("vehicle", _fp), ("num_sam_masks", C.c_int32), ("sam_masks", _fp), ("history_length", C.c_int32),
+        ("vehicle_kernel_first", C.c_int32), ("vehicle_kernel", C.c_int32), ("expand_kernel", C.c_int32),
+        ("image", _fp), ("rgb_boundary_threshold", C.c_double), ("depth_in", _fp), ("depth_out", _fp),
+        ("static_mask", _fp), ("dynamic_mask", _fp), ("expanded_dynamic", _fp), ("expanded_static", _fp), ("valid_rgb", _fp),
+        ("info", _fp), ("state", _fp), ("state_bytes", C.c_size_t), ("scratch", _fp), ("scratch_bytes", C.c_size_t),
+    ]
+
+
+DYNAMIC_MASK_BOXES_XYXY, DYNAMIC_MASK_BOXES_CXCYWH = 0, 1
+DYNAMIC_MASK_INFO_WORDS = 16
+DYNAMIC_MASK_INFO = ("boxes", "vehicle_detected", "use_sam_result", "filtered", "history", "box_pixels", "sam_pixels", "dynamic_pixels",
+                     "static_pixels", "expanded_pixels", "valid_pixels", "depth_pixels")   # the words' names, in LVDGS_DYNAMIC_MASK_INFO_* order
+
+
 class StateLayout(C.Structure):
     _fields_ = [(n, C.c_size_t) for n in (
         "geom_rec", "geom_tiles_touched", "geom_slot_base", "bin_point_list", "bin_tile_keys",
@@ -240,6 +258,7 @@ EXPORTS = (
     "lvdgs_format_plan_query", "lvdgs_format_table", "lvdgs_format_scratch_bytes", "lvdgs_format_image", "lvdgs_match_depth_scale",
     "lvdgs_edge_mask_scratch_bytes", "lvdgs_edge_mask", "lvdgs_frame_summary_scratch_bytes", "lvdgs_frame_summary",
     "lvdgs_ms_deform_attn_forward", "lvdgs_ms_deform_attn_backward",
+    "lvdgs_dynamic_mask_state_bytes", "lvdgs_dynamic_mask_scratch_bytes", "lvdgs_dynamic_mask",
     "lvdgs_last_error", "lvdgs_version", "lvdgs_profile_enable",
     "lvdgs_profile_reset", "lvdgs_profile_read",
 )
@@ -347,6 +366,11 @@ def lib():
         L.lvdgs_frame_summary.argtypes = [C.POINTER(FrameSummaryArgs), C.c_void_p]
         L.lvdgs_ms_deform_attn_forward.argtypes = [_fp] * 5 + [C.c_int32] * 7 + [_fp, C.c_void_p]
         L.lvdgs_ms_deform_attn_backward.argtypes = [_fp] * 5 + [C.c_int32] * 7 + [_fp] * 4 + [C.c_void_p]
+        L.lvdgs_dynamic_mask_state_bytes.restype = C.c_size_t
+        L.lvdgs_dynamic_mask_state_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+        L.lvdgs_dynamic_mask_scratch_bytes.restype = C.c_size_t
+        L.lvdgs_dynamic_mask_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
+        L.lvdgs_dynamic_mask.argtypes = [C.POINTER(DynamicMaskArgs), C.c_void_p]
         L.lvdgs_profile_enable.argtypes = [C.c_int]
         L.lvdgs_profile_read.argtypes = [C.POINTER(KernelTime), C.c_int]
         _lib = L

@@ -37,6 +37,9 @@ Stand-ins for what is out of scope, all injectable:
     the reference's ``find_scale`` on ``matcher``'s matches (``depth_utils.MatchScaleRemedy``: only the descriptor network behind the
     matcher needs MASt3R);
   * ``dataset.static_mask(idx)`` for the GroundingDINO + SAM masks (``dynamic_masker.get_static_mask_for_gaussian_init``).
+    ``dynamic_masks="detections"`` runs that call instead: ``masker`` (a ``dynamic_mask.DynamicMasker``; only the two networks behind
+    its seats are out of scope) assembles the masks from boxes, labels and SAM masks on every tracked frame and again on every
+    keyframe, as the reference does (``lvdgs_dynamic_mask``, HIP, or the masker's PyTorch chain).
 
 ``render_fn`` / ``view_loss_fn`` / ``refine_loss_fn`` / ``knn_fn`` default to the HIP paths; the CPU tests pass the dense float64
 renderer and the loss oracle so that the same harness runs at toy size without a GPU.
@@ -114,7 +117,8 @@ class SlamSequence:
     def __init__(self, config, dataset, gaussians, pipeline_params, background, *, fused="auto", render_fn=render, view_loss_fn=None,
                  refine_loss_fn=None, keyframe_depth=None, idle_map_iters=0, camera_cls=None, cameras_extent=6.0, on_event=None,
                  group=None, aux_group=None, bands_ok=None, depth_align_fn=None, scale_remedy=None, depth_align_params=None,
-                 pose_init=None, matcher=None, pose_init_params=None, frame_stats="torch", edge_mask="torch"):
+                 pose_init=None, matcher=None, pose_init_params=None, frame_stats="torch", edge_mask="torch", dynamic_masks="dataset",
+                 masker=None):
         from .backend_map import map_window
         if camera_cls is None:
             from .camera_utils import Camera as camera_cls
@@ -167,6 +171,13 @@ class SlamSequence:
             if value not in ("torch", "fused"):
                 raise ValueError(f"{name}: 'torch' or 'fused', not {value!r}")
         self.frame_stats, self.edge_mask = frame_stats, edge_mask
+        # dynamic_masks: "dataset" (the default: dataset.static_mask's finished masks) or "detections" (`masker`, a
+        # dynamic_mask.DynamicMasker: the masks, add_new_keyframe's dilation and valid_rgb come from its calls)
+        if dynamic_masks not in ("dataset", "detections"):
+            raise ValueError(f"dynamic_masks: 'dataset' or 'detections', not {dynamic_masks!r}")
+        if dynamic_masks == "detections" and masker is None:
+            raise TypeError("SlamSequence(dynamic_masks='detections') needs the `masker` argument (a dynamic_mask.DynamicMasker)")
+        self.dynamic_masks, self.masker = dynamic_masks, masker if dynamic_masks == "detections" else None
         self._summary = None           # the tracked frame's FrameSummary (frame_stats="fused"), else None
         self.idle_map_iters, self.camera_cls, self.on_event = int(idle_map_iters), camera_cls, on_event
         self._map_window = map_window
@@ -179,7 +190,7 @@ class SlamSequence:
         self.tracking_itr_num, self.kf_interval, self.window_size = T["tracking_itr_num"], T["kf_interval"], T["window_size"]
         self.single_thread = T.get("single_thread", False)
         df = config.get("dynamic_filtering", {})
-        self.enable_dynamic_filtering = df.get("enabled", True) and hasattr(dataset, "static_mask")
+        self.enable_dynamic_filtering = df.get("enabled", True) and (self.masker is not None or hasattr(dataset, "static_mask"))
         self.filter_initialization = df.get("filter_initialization", True)
         # front-end state (FrontEnd.__init__, utils/slam_frontend.py:1184-1213)
         self.initialized = False
@@ -260,6 +271,10 @@ class SlamSequence:
 
     def _attach_masks(self, viewpoint, idx, first):
         """What ``add_new_keyframe`` / ``tracking`` store on the viewpoint from the detector's mask (:1306-1329, :1419-1436)."""
+        if self.masker is not None:
+            static = self.masker.get_static_mask_for_gaussian_init(viewpoint.original_image, idx)
+            viewpoint.static_mask, viewpoint.dynamic_mask = static, self.masker.last.dynamic_mask
+            return static
         static = self.dataset.static_mask(idx)
         if static is None:
             return None
@@ -322,7 +337,9 @@ class SlamSequence:
         self.kf_indices.append(cur_frame_idx)
         gt_img = viewpoint.original_image
         valid_rgb = (gt_img.sum(dim=0) > thr)[None]
-        if self.enable_dynamic_filtering and (not init or self.filter_initialization):
+        if self.masker is not None and self.enable_dynamic_filtering and (not init or self.filter_initialization):
+            valid_rgb = self.masker.keyframe_masks(viewpoint, cur_frame_idx, thr).valid_rgb[None]
+        elif self.enable_dynamic_filtering and (not init or self.filter_initialization):
             static = self._attach_masks(viewpoint, cur_frame_idx, cur_frame_idx == 0)
             if static is not None:
                 expanded_dynamic = expand_dynamic_mask(viewpoint.dynamic_mask, 9 if cur_frame_idx == 0 else 7)

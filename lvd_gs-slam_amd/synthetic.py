@@ -149,13 +149,21 @@ def dynamic_object_mask(H, W, seed):
     """A frame's ``static_mask`` (bool (H,W), True = static) as LVD-GS's front end makes it from GroundingDINO + SAM detections
     (utils/slam_frontend.py:1309-1329; the models are out of scope): two to four "vehicles" -- rectangles of 8-25 % of the image's
     width and 10-35 % of its height in the lower two thirds of the frame -- marked dynamic, seeded per frame."""
-    g = torch.Generator().manual_seed(7000 + seed)
     m = torch.ones(H, W, dtype=torch.bool)
+    for x0, y0, w, h in dynamic_object_rectangles(H, W, seed):
+        m[y0:y0 + h, x0:x0 + w] = False
+    return m
+
+
+def dynamic_object_rectangles(H, W, seed):
+    """The rectangles ``dynamic_object_mask`` marks, as (x0, y0, w, h) in its drawing order."""
+    g = torch.Generator().manual_seed(7000 + seed)
+    out = []
     for _ in range(2 + int(torch.randint(0, 3, (1,), generator=g))):
         w = int(W * (0.08 + 0.17 * float(torch.rand(1, generator=g)))); h = int(H * (0.10 + 0.25 * float(torch.rand(1, generator=g))))
         x0 = int(torch.randint(0, max(W - w, 1), (1,), generator=g)); y0 = H // 3 + int(torch.randint(0, max(H - H // 3 - h, 1), (1,), generator=g))
-        m[y0:y0 + h, x0:x0 + w] = False
-    return m
+        out.append((x0, y0, w, h))
+    return out
 
 
 def vehicle_trajectory(n_frames, step=0.02, sway=0.15, yaw=0.03, period=40.0):
@@ -196,9 +204,12 @@ class SequenceDataset:
 
     def to(self, device):
         """The same frames held on another device."""
-        return SequenceDataset([t.to(device) for t in self.images], self.mono_depths, self.poses, self.width, self.height, self.fx, self.fy,
-                               self.cx, self.cy, device, depths=self.depths,
-                               static_masks=None if self.static_masks is None else [m.to(device) for m in self.static_masks])
+        ds = SequenceDataset([t.to(device) for t in self.images], self.mono_depths, self.poses, self.width, self.height, self.fx, self.fy,
+                             self.cx, self.cy, device, depths=self.depths,
+                             static_masks=None if self.static_masks is None else [m.to(device) for m in self.static_masks])
+        if hasattr(self, "dynamic_seeds"):
+            ds.dynamic_seeds = self.dynamic_seeds
+        return ds
 
 
 def make_sequence(truth, render_fn, pipe, W, H, n_frames, device, fx=None, fy=None, cx=None, cy=None, seed=0, depth_noise=0.02,
@@ -247,6 +258,8 @@ def make_sequence(truth, render_fn, pipe, W, H, n_frames, device, fx=None, fy=No
         monos.append(depth.cpu().numpy().astype("float32"))
     ds = SequenceDataset(images, monos, poses, W, H, fx, fy, cx, cy, device, static_masks=masks if dynamic_objects else None)
     ds.mono_scales = [mono_scale_factor(i, mono_scale_drift) if mono_scale_drift else 1.0 for i in range(len(poses))]
+    if dynamic_objects:
+        ds.dynamic_seeds = [100 * seed + i for i in range(len(poses))]      # dynamic_object_rectangles' seeds (RectangleDetector)
     return ds
 
 
@@ -254,6 +267,34 @@ def mono_scale_factor(i, drift):
     """Frame i's mono depth scale under ``make_sequence(..., mono_scale_drift=drift)``: 1 + drift * sin(2 pi i / 11) -- a
     wander between 1 - drift and 1 + drift that never repeats within a short drive."""
     return 1.0 + drift * math.sin(2.0 * math.pi * i / 11.0)
+
+
+class RectangleDetector:
+    """A stand-in for BOTH networks behind ``dynamic_mask.DynamicMasker`` (GroundingDINO and SAM, out of scope) on a
+    ``SequenceDataset`` made with ``dynamic_objects=True``: the rectangles ``dynamic_object_mask`` drew on a frame come back as pixel
+    boxes (x0, y0, x0 + w, y0 + h) labelled "car" -- ``detect(image, frame_idx) -> (boxes (K, 4) float32 on the image's device,
+    labels)``, the GroundingDINO seat -- and as one exact mask per rectangle -- ``segment(image, boxes) -> (K, H, W)`` bool, the SAM
+    seat, for the frame ``detect`` was last asked about."""
+
+    def __init__(self, dataset):
+        if not hasattr(dataset, "dynamic_seeds"):
+            raise ValueError("RectangleDetector needs a dataset made by make_sequence(dynamic_objects=True)")
+        self.dataset, self.frame = dataset, None
+
+    def rectangles(self, idx):
+        return dynamic_object_rectangles(self.dataset.height, self.dataset.width, self.dataset.dynamic_seeds[idx])
+
+    def detect(self, image, frame_idx):
+        self.frame = int(frame_idx)
+        rows = [[x0, y0, x0 + w, y0 + h] for x0, y0, w, h in self.rectangles(self.frame)]
+        return torch.tensor(rows, dtype=torch.float32).reshape(-1, 4).to(image.device), ["car"] * len(rows)
+
+    def segment(self, image, boxes):
+        rects = self.rectangles(self.frame)
+        masks = torch.zeros(len(rects), self.dataset.height, self.dataset.width, dtype=torch.bool)
+        for m, (x0, y0, w, h) in zip(masks, rects):
+            m[y0:y0 + h, x0:x0 + w] = True
+        return masks.to(image.device)
 
 
 class GroundTruthMatcher:

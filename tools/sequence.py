@@ -114,6 +114,11 @@ def run_sequence(dev, frames=60, scale=1.0, cadence="reference", fused="auto", i
         sequence_kwargs["matcher"] = init_pose.DescriptorMatcher(synthetic.WorldDescriptors(ds, seed=seed))
     if (sequence_kwargs.get("pose_init") == "pnp" or sequence_kwargs.get("scale_remedy") == "matches") and sequence_kwargs.get("matcher") is None:
         sequence_kwargs["matcher"] = synthetic.GroundTruthMatcher(ds, stride=8, noise_px=0.7, outlier_ratio=0.3, seed=seed)
+    if sequence_kwargs.get("dynamic_masks") == "detections" and sequence_kwargs.get("masker") is None:
+        # the masks assembled from detections (dynamic_mask.DynamicMasker) of the stand-in for the two networks: the dataset's rectangles
+        from lvdgs.dynamic_mask import DynamicMasker
+        det = synthetic.RectangleDetector(ds)
+        sequence_kwargs["masker"] = DynamicMasker(det.detect, det.segment, fused=sequence_kwargs.pop("fused_masks", True))
     seq = SlamSequence(cfg, ds, m, PIPE, torch.zeros(3, device=dev), fused=fused, idle_map_iters=idle, on_event=on_event, **sequence_kwargs)
     seq.run()
     out = seq.summary()
@@ -168,6 +173,9 @@ def main():
                          "per count (default), or one frame_stats.frame_summary call and one wait")
     ap.add_argument("--edge-mask", choices=["torch", "fused"], default="torch",
                     help="Camera.compute_grad_mask's PyTorch statements (default) or one frame_stats.edge_mask call")
+    ap.add_argument("--dynamic-masks", choices=["dataset", "detections"], default="dataset",
+                    help="the frames' static masks: the dataset's finished ones (default), or assembled on the device from the boxes and masks of "
+                         "synthetic.RectangleDetector by dynamic_mask.DynamicMasker (lvdgs_dynamic_mask)")
     ap.add_argument("--verbose", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -178,8 +186,9 @@ def main():
                           mono_scale_drift=a.mono_scale_drift, **({"keyframe_depth": "patch_align"} if a.keyframe_depth == "patch_align" else {}),
                           **({"pose_init": a.pose_init} if a.pose_init else {}), **({"matcher": "descriptors"} if a.matcher == "descriptors" else {}),
                           **({"scale_remedy": "matches"} if a.scale_remedy == "matches" else {}),
-                          **({"frame_stats": "fused"} if a.frame_stats == "fused" else {}), **({"edge_mask": "fused"} if a.edge_mask == "fused" else {}))
-    out.update(frame_stats=a.frame_stats, edge_mask=a.edge_mask)
+                          **({"frame_stats": "fused"} if a.frame_stats == "fused" else {}), **({"edge_mask": "fused"} if a.edge_mask == "fused" else {}),
+                          **({"dynamic_masks": "detections"} if a.dynamic_masks == "detections" else {}))
+    out.update(frame_stats=a.frame_stats, edge_mask=a.edge_mask, dynamic_masks=a.dynamic_masks)
     for rec in out.get("pose_init", []):
         print("  frame {frame:3d} kf {keyframe:3d} inliers {inl:>5} init error {e:.4f} ({r:.3f} deg; previous pose {p:.4f}) tracking iterations {it}".format(
             frame=rec["frame"], keyframe=rec["keyframe"], inl=rec.get("inliers", "-"), e=rec["init_translation_error"], r=rec["init_rotation_error_deg"],
