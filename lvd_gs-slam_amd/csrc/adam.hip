@@ -13,6 +13,7 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "device_utils.hpp"
 #include "map_stats.hpp"
 
 namespace lvdgs {
@@ -117,7 +118,7 @@ __global__ void __launch_bounds__(256) isotropic_kernel(int N, const float *__re
         }
     }
     // block sum in a fixed order
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) partial[blockIdx.x] = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];

@@ -188,8 +188,7 @@ __global__ void __launch_bounds__(KNN_BOX) knn_search_kernel(int P, int nbox, co
     };
     auto workgroup_bound = [&]() {  // max over the workgroup's points of their current third-best distance
         float m = ok ? b2 : 0.f;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        m = wave_max(m);
         if (KNN_BOX == 64) return m;
         __syncthreads();
         if (lane == 0) s_red[wave] = m;

@@ -164,9 +164,8 @@ __device__ __forceinline__ void group_tilescan_body(int T, const uint32_t *__res
                                                     uint32_t *host_out, uint32_t host_seq, uint32_t *arrive = nullptr, uint32_t *seq_out = nullptr) {
     static_assert(THREADS == 1024 || THREADS == 512, "the grouping kernels' workgroup sizes (the scan rides in the scatter's launch)");
     __shared__ uint32_t s_scan[1024];
-    __shared__ uint32_t s_q, s_longest, s_total;
+    __shared__ uint32_t s_q, s_longest;
     constexpr int PER = GROUP_MAX_TILES / THREADS;   // 16 or 32 tiles per thread: 16-byte loads, 16-byte stores
-    constexpr int WAVES = THREADS / 64;
     uint32_t v[PER], sum = 0;
     if (threadIdx.x == 0) { s_q = 0u; s_longest = 0u; }
     {
@@ -186,33 +185,10 @@ __device__ __forceinline__ void group_tilescan_body(int T, const uint32_t *__res
 #pragma unroll
         for (int k = 0; k < PER; k++) sum += v[k];
     }
-    // inclusive scan of the thread sums: inside every wave by lane shifts, then the up to 16 wave totals by wave 0
+    // exclusive scan of the thread sums in words 0-31 of s_scan, which nothing else has in use yet
     // (two barriers; the log-step scan over all 1024 threads it replaces needed twenty)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t x = (uint32_t)__shfl_up((int)inc, off, 64);
-        if (lane >= off) inc += x;
-    }
-    if (lane == 63) s_scan[wave] = inc;
-    __syncthreads();
-    if (wave == 0) {
-        uint32_t w = lane < WAVES ? s_scan[lane] : 0u;
-#pragma unroll
-        for (int off = 1; off < 16; off <<= 1) {
-            const uint32_t x = (uint32_t)__shfl_up((int)w, off, 64);
-            if (lane >= off) w += x;
-        }
-        if (lane < 16) s_scan[16 + lane] = w;   // inclusive over the waves
-    }
-    __syncthreads();
-    inc += wave ? s_scan[16 + wave - 1] : 0u;
-    if (threadIdx.x == THREADS - 1) {
-        s_total = inc;
-        if (total_out) total_out[0] = inc;   // the frame's pair count (before clamping)
-    }
-    uint32_t run = inc - sum;
+    uint32_t total;
+    uint32_t run = scan_workgroup<THREADS>(sum, s_scan, &total);   // total: the frame's pair count, before clamping
     uint32_t longest = 0;
 #pragma unroll
     for (int k = 0; k < PER; k += 2) {
@@ -232,12 +208,12 @@ __device__ __forceinline__ void group_tilescan_body(int T, const uint32_t *__res
     __syncthreads();
     if (threadIdx.x == 0) {
         *queue_count = s_q;
-        if (total_out) { total_out[1] = s_longest; total_out[2] = s_q; }   // longest queued segment (0: none) and the queue's length, read back with the pair count
+        if (total_out) { total_out[0] = total; total_out[1] = s_longest; total_out[2] = s_q; }   // the pair count, the longest queued segment (0: none) and the queue's length: read back together
         // The host's copy, written straight into its (pinned, device-visible) memory: the pair count and the two hints, then --
         // behind a system-scope fence -- the sequence number of the call, which is what the host spins on.  (A device-to-host
         // copy enqueued behind this kernel is a blit kernel of its own: 3.6 us on every frame's critical path.)
         if (host_out) {
-            host_out[PROBE_COUNT] = s_total; host_out[PROBE_LONGEST] = s_longest; host_out[PROBE_QUEUED] = s_q;
+            host_out[PROBE_COUNT] = total; host_out[PROBE_LONGEST] = s_longest; host_out[PROBE_QUEUED] = s_q;
             __threadfence_system();
             if (!arrive) __hip_atomic_store(host_out + PROBE_SEQ, host_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
             else if (__hip_atomic_fetch_add(arrive, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_SYSTEM) == 1u) {   // the second to arrive
@@ -263,27 +239,11 @@ __device__ __forceinline__ void group_tilescan_body(int T, const uint32_t *__res
     uint32_t cnt[BPT], mine = 0u;
 #pragma unroll
     for (int q = 0; q < BPT; q++) { cnt[q] = s_scan[BPT * threadIdx.x + q]; mine += cnt[q]; }
-    uint32_t incl = mine;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t x = (uint32_t)__shfl_up((int)incl, off, 64);
-        if (lane >= off) incl += x;
-    }
-    __shared__ uint32_t s_wave[32];
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    if (wave == 0) {
-        uint32_t w = lane < WAVES ? s_wave[lane] : 0u;
-#pragma unroll
-        for (int off = 1; off < 16; off <<= 1) {
-            const uint32_t x = (uint32_t)__shfl_up((int)w, off, 64);
-            if (lane >= off) w += x;
-        }
-        if (lane < 16) s_wave[16 + lane] = w;
-    }
-    __syncthreads();
+    // the scan's words are an array of their own: s_scan still holds counters that their threads may not have read yet
+    __shared__ uint32_t s_wave[SCAN_WORDS];
     {
-        uint32_t first = incl - mine + (wave ? s_wave[16 + wave - 1] : 0u);   // first position of this thread's first bucket
+        uint32_t all;
+        uint32_t first = scan_workgroup<THREADS>(mine, s_wave, &all);   // first position of this thread's first bucket
 #pragma unroll
         for (int q = 0; q < BPT; q++) { s_scan[BPT * threadIdx.x + q] = first; first += cnt[q]; }
     }
@@ -382,7 +342,7 @@ __device__ __forceinline__ void scatter_pairs_body(int chunk, int N, int gx, int
     constexpr bool HELPERS = GROUP_THREADS > OWNERS;   // waves without a Gaussian of their own: they help with the large rectangles
     static_assert(!HELPERS || PER == 1, "helper waves: one Gaussian per owner thread");
     extern __shared__ uint32_t s_tile[];
-    __shared__ uint32_t s_scan[33];
+    __shared__ uint32_t s_scan[SCAN_WORDS];   // up to three workgroup scans in a row, no barrier between them (device_utils.hpp)
     __shared__ uint32_t s_slots[2];
     __shared__ BigRectQueue s_big;
     const bool owner = (int)threadIdx.x < OWNERS;
@@ -410,8 +370,7 @@ __device__ __forceinline__ void scatter_pairs_body(int chunk, int N, int gx, int
         for (int t = t0; t < t1; t++) sum += totals[t];
         uint32_t all;
         uint32_t run = scan_workgroup<GROUP_THREADS>(sum, s_scan, &all);
-        for (int t = t0; t < t1; t++) { s_tile[t] = run + row[t]; run += totals[t]; }
-        __syncthreads();   // (s_scan is used again below)
+        for (int t = t0; t < t1; t++) { s_tile[t] = run + row[t]; run += totals[t]; }   // (published by the barrier in front of the walk)
     } else {
         for (int t = threadIdx.x; t < T; t += GROUP_THREADS) s_tile[t] = ranges[t].x + row[t];  // (empty tiles are never visited)
     }
@@ -425,7 +384,6 @@ __device__ __forceinline__ void scatter_pairs_body(int chunk, int N, int gx, int
         for (int k = 0; k < PER; k++) { v[k] = (owner && base + k < N) ? tt[base + k] : 0u; mine += v[k]; }
         uint32_t prefix;
         scan_workgroup<GROUP_THREADS>(before, s_scan, &prefix);  // only the total is of interest
-        __syncthreads();                     // s_scan is used again
         uint32_t total;
         uint32_t run = scan_workgroup<GROUP_THREADS>(mine, s_scan, &total) + prefix;
 #pragma unroll

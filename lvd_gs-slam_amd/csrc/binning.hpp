@@ -183,33 +183,4 @@ __device__ __forceinline__ int xcd_contiguous_chunk(int b, int n) {
     return x * q + min(x, r) + k;
 }
 
-// Exclusive scan of one value per thread over a workgroup of THREADS threads (wave shifts, then the up to 16 wave totals by
-// wave 0: two barriers); *total = sum over the workgroup.  s_scan: 33 words.
-template <int THREADS>
-__device__ __forceinline__ uint32_t scan_workgroup(uint32_t v, uint32_t *s_scan, uint32_t *total) {
-    constexpr int WAVES = THREADS / 64;
-    static_assert(WAVES >= 1 && WAVES <= 16 && THREADS % 64 == 0, "up to 16 whole waves");
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t x = (uint32_t)__shfl_up((int)inc, off, 64);
-        if (lane >= off) inc += x;
-    }
-    if (lane == 63) s_scan[wave] = inc;
-    __syncthreads();
-    if (wave == 0) {
-        uint32_t w = lane < WAVES ? s_scan[lane] : 0u;
-#pragma unroll
-        for (int off = 1; off < 16; off <<= 1) {
-            const uint32_t x = (uint32_t)__shfl_up((int)w, off, 64);
-            if (lane >= off) w += x;
-        }
-        if (lane < 16) s_scan[16 + lane] = w;   // inclusive over the waves
-    }
-    __syncthreads();
-    *total = s_scan[16 + WAVES - 1];
-    return inc - v + (wave ? s_scan[16 + wave - 1] : 0u);
-}
-
 }  // namespace lvdgs

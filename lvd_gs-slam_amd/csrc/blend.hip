@@ -508,9 +508,7 @@ __device__ __forceinline__ void blend_bwd3_body(const BlendParams &p, Bwd3Shared
     if constexpr (!DEPTH_GRAD) gD = 0.f;
     const float tail = T_final * (p.bg[0] * gC0 + p.bg[1] * gC1 + p.bg[2] * gC2 - gO);
 
-    uint32_t m = my_last;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, off, 64));
+    uint32_t m = wave_max(my_last);
     // A quadrant whose 64 pixels all receive a zero gradient (masked out of the loss: the tracking loss's edge and
     // brightness masks, a static mask) adds exactly zero to every sum: its wave sits the lists out.
     const uint32_t m_all = m;

@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include "common.hpp"
+#include "device_utils.hpp"
 
 namespace lvdgs {
 namespace {
@@ -69,17 +70,6 @@ __host__ __device__ inline bool top_stop(float s, float s_prev, float eps) {
     return d < eps && s != 1.0f;
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, WAVE);
-    return v;
-}
-__device__ __forceinline__ int wave_sum_i32(int v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, WAVE);
-    return v;
-}
-
 __device__ __forceinline__ void mirror_state(const AlignParams &P, const DepthAlignState &st) {
     P.hdr->st = st;
     if (P.host_state) {
@@ -118,7 +108,7 @@ __global__ void __launch_bounds__(DA_THREADS) depth_align_iter_kernel(AlignParam
             sr += (double)r[o];
             sm += (double)(m[o] * s);
         }
-        const double mr = wave_sum_f64(sr) / n, mm = wave_sum_f64(sm) / n;
+        const double mr = wave_sum(sr) / n, mm = wave_sum(sm) / n;
         // pass 2: population standard deviations
         double vr = 0.0, vm = 0.0;
         for (int i = lane; i < n; i += WAVE) {
@@ -128,7 +118,7 @@ __global__ void __launch_bounds__(DA_THREADS) depth_align_iter_kernel(AlignParam
             vr += dr * dr;
             vm += dm * dm;
         }
-        const double sdr = sqrt(wave_sum_f64(vr) / n), sdm = sqrt(wave_sum_f64(vm) / n);
+        const double sdr = sqrt(wave_sum(vr) / n), sdm = sqrt(wave_sum(vm) / n);
         // (NaN anywhere makes both comparisons false)
         if (fabs(mr - mm) < P.mean_thr * mm && fabs(sdr - sdm) < P.std_thr * sdm) {
             passed = 1;
@@ -143,9 +133,9 @@ __global__ void __launch_bounds__(DA_THREADS) depth_align_iter_kernel(AlignParam
                     acc_m += (double)mv;   // the scale update reads the UNSCALED mono depth
                 }
             }
-            acc_n = wave_sum_i32(acc_n);
-            acc_r = wave_sum_f64(acc_r);
-            acc_m = wave_sum_f64(acc_m);
+            acc_n = wave_sum(acc_n);
+            acc_r = wave_sum(acc_r);
+            acc_m = wave_sum(acc_m);
         }
     }
     if (lane == 0) {

@@ -31,6 +31,114 @@ __device__ __forceinline__ float wave_sum_to_lane63(float v) {
     return v;
 }
 
+// The integer twin: inclusive prefix over the wave in every lane (lane 63: the total).  row_shr:1,2,4,8 inside the 16-lane rows,
+// row_bcast:15 / :31 chain the rows (six DPP adds instead of the six ds_bpermute round trips of wave_inclusive_scan).
+__device__ __forceinline__ uint32_t wave_inclusive_scan_dpp(uint32_t inc) {
+    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x111, 0xf, 0xf, false);
+    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x112, 0xf, 0xf, false);
+    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x114, 0xf, 0xf, false);
+    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x118, 0xf, 0xf, false);
+    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x142, 0xa, 0xf, false);
+    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x143, 0xc, 0xf, false);
+    return inc;
+}
+
+// Sum over the 64 lanes, valid in every lane: xor butterfly with offsets 32, 16, ... 1 (for float and double that order is part
+// of the result's bits).  T: int, uint32_t, unsigned long long, float, double.  No LDS, no barrier.
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// Maximum over the 64 lanes, valid in every lane (same butterfly): max for integers, fmaxf for float.
+template <typename T>
+__device__ __forceinline__ T wave_max(T v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
+    return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
+// Inclusive prefix sum over the wave's lanes, in every lane (lane 63: the wave's total); lane shifts by 1, 2, ... 32.
+// T: uint32_t, int.  Reached by all 64 lanes.  No LDS, no barrier.
+template <typename T>
+__device__ __forceinline__ T wave_inclusive_scan(T v) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const T x = __shfl_up(v, off, 64);
+        if (lane >= off) v += x;
+    }
+    return v;
+}
+
+// Exclusive prefix sum of one value per thread over a workgroup of THREADS threads (up to 16 whole waves, all of which reach it);
+// *total = the workgroup's sum, in every thread.  T: uint32_t, int.  s_scan: SCAN_WORDS words of LDS; two barriers (wave scans,
+// then the wave totals by wave 0), both passed by every thread, so they also publish what the caller wrote to LDS before the call.
+// Words 0-15 are written before the first barrier and read between the two, words 16-31 written between them and read behind the
+// second: a second call on the same s_scan needs NO barrier in front (its first barrier orders its writes of 16-31 behind this
+// call's reads), and the first call needs none either when nothing else has s_scan in use.
+constexpr int SCAN_WORDS = 32;
+template <int THREADS, typename T>
+__device__ __forceinline__ T scan_workgroup(T v, T *s_scan, T *total) {
+    constexpr int WAVES = THREADS / 64;
+    static_assert(WAVES >= 1 && WAVES <= 16 && THREADS % 64 == 0, "up to 16 whole waves");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const T inc = wave_inclusive_scan(v);
+    if (lane == 63) s_scan[wave] = inc;
+    __syncthreads();
+    if (wave == 0) {
+        T w = lane < WAVES ? s_scan[lane] : (T)0;
+#pragma unroll
+        for (int off = 1; off < 16; off <<= 1) {   // (wave_inclusive_scan, stopped at the 16 lanes that hold a total)
+            const T x = __shfl_up(w, off, 64);
+            if (lane >= off) w += x;
+        }
+        if (lane < 16) s_scan[16 + lane] = w;   // inclusive over the waves
+    }
+    __syncthreads();
+    *total = s_scan[16 + WAVES - 1];
+    return inc - v + (wave ? s_scan[16 + wave - 1] : (T)0);
+}
+
+// Sum of one value per thread over a workgroup of WAVES waves, in every thread.  s: WAVES words of LDS.  Two barriers, the first in
+// FRONT of the write of s: calls may follow each other on one s with nothing in between.
+// float: wave_sum_to_lane63, then the wave totals in a FIXED order that is part of the results' bits -- one per specialisation.
+__device__ __forceinline__ void block_sum_publish(float v, float *s) {
+    v = wave_sum_to_lane63(v);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 63) s[wave] = v;
+    __syncthreads();
+}
+template <int WAVES> __device__ __forceinline__ float block_sum(float v, float *s);
+// four waves: left to right, ((s0 + s1) + s2) + s3
+template <> __device__ __forceinline__ float block_sum<4>(float v, float *s) {
+    block_sum_publish(v, s);
+    return ((s[0] + s[1]) + s[2]) + s[3];
+}
+// eight waves: the pairwise tree ((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7))
+template <> __device__ __forceinline__ float block_sum<8>(float v, float *s) {
+    block_sum_publish(v, s);
+    return (((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7])));
+}
+// int: wave_sum, then the wave totals from wave 0 up (any order gives the same integer)
+template <int WAVES> __device__ __forceinline__ int block_sum(int v, int *s) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int t = 0;
+    for (int w = 0; w < WAVES; w++) t += s[w];
+    return t;
+}
+
 // Pairwise folds for multi-value wave reductions (gfx950 v_permlane32_swap / v_permlane16_swap).
 // fold32(a, b): lanes 0-31 hold a[l] + a[l+32], lanes 32-63 hold b[l-32] + b[l].
 __device__ __forceinline__ float fold32(float a, float b) {

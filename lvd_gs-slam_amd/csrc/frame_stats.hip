@@ -108,7 +108,7 @@ struct BlockSource {   // block (by, bx) of the 32 x 32 grid, row-major inside t
 
 __global__ void __launch_bounds__(SEL_THREADS) edge_blocks_kernel(EdgeParams P) {
     __shared__ uint32_t hist[SEL_THREADS];
-    __shared__ uint32_t sh[SEL_THREADS / WAVE + 2];
+    __shared__ uint32_t sh[SCAN_WORDS + 2];
     const int bh = P.H / EDGE_GRID, bw = P.W / EDGE_GRID;
     const int by = blockIdx.x / EDGE_GRID, bx = blockIdx.x - by * EDGE_GRID;
     const BlockSource src{P.mag, P.W, bw, (int64_t)by * bh * P.W + (int64_t)bx * bw};

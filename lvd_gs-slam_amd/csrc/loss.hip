@@ -20,15 +20,6 @@ namespace {
 constexpr int LOSS_THREADS = 256;
 constexpr int LOSS_PIX_PER_THREAD = 4;
 
-__device__ __forceinline__ float block_sum(float v, float *s /* [4] */) {
-    v = wave_sum_to_lane63(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 63) s[wave] = v;
-    __syncthreads();
-    return ((s[0] + s[1]) + s[2]) + s[3];
-}
-
 // 4 consecutive pixels per lane: 16-byte loads / stores on every plane when P % 4 == 0 (VEC), scalar otherwise.
 // MODE 0: the loss value; 1: every gradient; 2: both in ONE pass over the images (the tracking session's case: the
 // objective IS the loss, d objective / d loss is known -- 1, or a device scalar -- before the pixels are read).
@@ -97,13 +88,13 @@ __global__ void __launch_bounds__(LOSS_THREADS) photometric_kernel(LossParams p)
     }
     // partial sums of a block: [0], [1] value (rgb, depth), [2], [3] gradients (d_a, d_b)
     if (VALUE) {
-        const float s0 = block_sum(acc0, s_red);
-        const float s1 = block_sum(acc1, s_red);
+        const float s0 = block_sum<4>(acc0, s_red);
+        const float s1 = block_sum<4>(acc1, s_red);
         if (threadIdx.x == 0) { p.partial[4 * blockIdx.x] = s0; p.partial[4 * blockIdx.x + 1] = s1; }
     }
     if (BACKWARD) {
-        const float s2 = block_sum(acc2, s_red);
-        const float s3 = block_sum(acc3, s_red);
+        const float s2 = block_sum<4>(acc2, s_red);
+        const float s3 = block_sum<4>(acc3, s_red);
         if (threadIdx.x == 0) { p.partial[4 * blockIdx.x + 2] = s2; p.partial[4 * blockIdx.x + 3] = s3; }
     }
 }
@@ -194,11 +185,9 @@ __global__ void __launch_bounds__(LOSS_THREADS) masked_depth_kernel(MaskedDepthP
         }
     }
     if (!BACKWARD) {
-        const float s0 = block_sum(acc, s_red);
+        const float s0 = block_sum<4>(acc, s_red);
         // exact integer count: wave popcount-free sum through the same lane-63 reduction on floats would round above 2^24
-        uint32_t c = cnt;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) c += (uint32_t)__shfl_xor((int)c, off, 64);
+        const uint32_t c = wave_sum(cnt);
         if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = c;
         __syncthreads();
         if (threadIdx.x == 0) { p.partial_sum[blockIdx.x] = s0; p.partial_cnt[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3]; }

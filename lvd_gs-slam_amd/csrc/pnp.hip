@@ -15,6 +15,7 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "device_utils.hpp"
 
 namespace lvdgs {
 namespace {
@@ -212,17 +213,6 @@ __device__ __forceinline__ bool is_inlier(const Pose &T, double fx, double fy, d
     return ex * ex + ey * ey < thr2;   // (NaN: never)
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, WAVE);
-    return v;
-}
-__device__ __forceinline__ int wave_sum_i32(int v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, WAVE);
-    return v;
-}
-
 __device__ __forceinline__ void write_state(const PnpParams &P, int status, int valid, int inliers, int hyp, int winner_count, int reason, const Pose &T) {
     int32_t *w = P.host_state;
     double *pose = reinterpret_cast<double *>(w + LVDGS_PNP_STATE_WORDS);
@@ -233,17 +223,6 @@ __device__ __forceinline__ void write_state(const PnpParams &P, int status, int 
     w[1] = valid; w[2] = inliers; w[3] = hyp; w[4] = winner_count; w[5] = reason; w[6] = 0; w[7] = 0;
     w[0] = status;
     __threadfence_system();
-}
-
-// the block's sum of an int, the same in every thread (two barriers)
-__device__ __forceinline__ int block_sum_i32(int v, int *sh) {
-    v = wave_sum_i32(v);
-    __syncthreads();
-    if (threadIdx.x % WAVE == 0) sh[threadIdx.x / WAVE] = v;
-    __syncthreads();
-    int s = 0;
-    for (int w = 0; w < PNP_WAVES; w++) s += sh[w];
-    return s;
 }
 
 __global__ void __launch_bounds__(PNP_THREADS) pnp_hypotheses_kernel(PnpParams P) {
@@ -292,7 +271,7 @@ __global__ void __launch_bounds__(PNP_THREADS) pnp_hypotheses_kernel(PnpParams P
         if (live) {
             for (int i = lane; i < M; i += WAVE)
                 count += is_inlier(T, P.fx, P.fy, P.thr2, P.px[i], P.py[i], P.pz[i], P.qu[i], P.qv[i]) ? 1 : 0;
-            count = wave_sum_i32(count);
+            count = wave_sum(count);
         }
         if (lane == 0) {
             HypRec &r = P.recs[h];
@@ -323,7 +302,7 @@ __global__ void __launch_bounds__(PNP_THREADS) pnp_hypotheses_kernel(PnpParams P
     const int tid = threadIdx.x;
     int nv = 0;
     for (int i = tid; i < M; i += PNP_THREADS) nv += P.pz[i] > 0.0 ? 1 : 0;
-    const int valid = block_sum_i32(nv, s_int);
+    const int valid = block_sum<PNP_WAVES>(nv, s_int);
     int bc = -1, bh = -1;
     for (int k = tid; k < P.hyp; k += PNP_THREADS) {
         const int c = P.recs[k].count;
@@ -367,7 +346,7 @@ __global__ void __launch_bounds__(PNP_THREADS) pnp_hypotheses_kernel(PnpParams P
             for (int i = tid; i < M; i += PNP_THREADS)
                 if (P.mask[i]) accumulate(T, P.fx, P.fy, P.px[i], P.py[i], P.pz[i], P.qu[i], P.qv[i], S);
 #pragma unroll
-            for (int i = 0; i < NS; i++) S[i] = wave_sum_f64(S[i]);
+            for (int i = 0; i < NS; i++) S[i] = wave_sum(S[i]);
             __syncthreads();
             if (lane == 0) {
 #pragma unroll
@@ -395,7 +374,7 @@ __global__ void __launch_bounds__(PNP_THREADS) pnp_hypotheses_kernel(PnpParams P
         P.mask[i] = in ? 1 : 0;
         ni += in ? 1 : 0;
     }
-    const int inliers = block_sum_i32(ni, s_int);
+    const int inliers = block_sum<PNP_WAVES>(ni, s_int);
     if (tid == 0) write_state(P, LVDGS_PNP_OK, valid, inliers, win, win_count, LVDGS_PNP_FAIL_NONE, T);
 }
 

@@ -60,8 +60,7 @@ __global__ void __launch_bounds__(256) preprocess_fwd_kernel(FwdParams p) {
     uint4 rect;
     if (i < p.N) preprocess_one(p, i, load_raw(p, i), tiles, rect);
     // the workgroup's pair count: the slot scan starts from these sums instead of re-reading tiles_touched in a launch of its own
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) tiles += (uint32_t)__shfl_xor((int)tiles, off, 64);
+    tiles = wave_sum(tiles);
     if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = tiles;
     __syncthreads();
     if (threadIdx.x == 0) p.blocksums[blockIdx.x] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
@@ -126,8 +125,7 @@ __device__ __forceinline__ void preprocess_count_body(const FwdParams &p, int T,
             }
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mine += (uint32_t)__shfl_xor((int)mine, off, 64);
+    mine = wave_sum(mine);
     if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = mine;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -173,15 +173,7 @@ __device__ LVDGS_BIG_PATH_ATTR void sum_region_compacted(const float *__restrict
             mine &= keep_hi & keep_lo;
         }
         const uint32_t cnt = (uint32_t)__popc(mine);
-        // inclusive prefix over the wave: row_shr:1,2,4,8 inside the 16-lane rows, row_bcast:15 / :31 chain the rows (six DPP adds
-        // instead of six ds_bpermute round trips)
-        uint32_t inc = cnt;
-        inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x111, 0xf, 0xf, false);
-        inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x112, 0xf, 0xf, false);
-        inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x114, 0xf, 0xf, false);
-        inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x118, 0xf, 0xf, false);
-        inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x142, 0xa, 0xf, false);
-        inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x143, 0xc, 0xf, false);
+        const uint32_t inc = wave_inclusive_scan_dpp(cnt);
         const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
         {
             uint32_t at = inc - cnt;
@@ -262,7 +254,7 @@ __device__ LVDGS_BIG_PATH_ATTR void sum_region_compacted(const float *__restrict
 #ifdef LVDGS_DIAG_PBWD
             {
                 int trips = (!wide && b > a) ? (int)((b - a + LVDGS_PBWD_TAKE - 1) / LVDGS_PBWD_TAKE) : 0;
-                for (int off = 32; off; off >>= 1) trips = max(trips, __shfl_xor(trips, off, 64));
+                trips = wave_max(trips);
                 PBWD_ADD(8, trips);
                 PBWD_ADD(9, __popcll(__ballot(wide)));
             }

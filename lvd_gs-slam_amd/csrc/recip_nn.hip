@@ -20,6 +20,7 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "device_utils.hpp"
 
 namespace lvdgs {
 namespace {
@@ -36,7 +37,6 @@ constexpr int RNN_QSTRIDE = RNN_QGROUP + 32;         // floats between two compo
 constexpr int RNN_WAVE_TILES = 4;                    // database tiles per wave
 constexpr int RNN_KS_MAX = LVDGS_RNN_MAX_DIM / 2;
 constexpr int RNN_ONE = 1024;                        // threads of the single-workgroup kernels
-constexpr int RNN_ONE_WAVES = RNN_ONE / WAVE;
 constexpr u64 RNN_DROPPED = ~0ull;                   // sort key of an unconverged seed (a map index is below 2^31)
 
 struct RnnHeader {
@@ -188,30 +188,8 @@ __global__ void __launch_bounds__(RNN_THREADS) rnn_search_kernel(RnnParams P, in
     }
 }
 
-// exclusive prefix of v over the RNN_ONE threads of the workgroup; *total: the sum, the same in every thread (two barriers)
-__device__ __forceinline__ int block_exclusive_scan(int v, int *sh, int *total) {
-    const int lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < WAVE; o <<= 1) {
-        const int n = __shfl_up(inc, o, WAVE);
-        if (lane >= o) inc += n;
-    }
-    __syncthreads();
-    if (lane == WAVE - 1) sh[wave] = inc;
-    __syncthreads();
-    int before = 0, sum = 0;
-    for (int w = 0; w < RNN_ONE_WAVES; w++) {
-        const int s = sh[w];
-        before += w < wave ? s : 0;
-        sum += s;
-    }
-    *total = sum;
-    return before + inc - v;
-}
-
 __global__ void __launch_bounds__(RNN_ONE) rnn_update_kernel(RnnParams P, int half) {
-    __shared__ int s_scan[RNN_ONE_WAVES];
+    __shared__ int s_scan[SCAN_WORDS];
     const int dir = half & 1, tid = threadIdx.x;
     const int nact = (int)P.hdr->nact[dir];
     const uint32_t *src = P.act[dir];
@@ -237,7 +215,7 @@ __global__ void __launch_bounds__(RNN_ONE) rnn_update_kernel(RnnParams P, int ha
         cnt += still ? 1 : 0;
     }
     int total;
-    int out = block_exclusive_scan(cnt, s_scan, &total);
+    int out = scan_workgroup<RNN_ONE>(cnt, s_scan, &total);
     for (int a = lo; a < hi; a++) {
         const uint32_t seed = src[a];
         if (!P.retired[seed]) dst[out++] = seed;   // (this thread's own writes)
@@ -250,7 +228,7 @@ __global__ void __launch_bounds__(RNN_ONE) rnn_update_kernel(RnnParams P, int ha
 
 __global__ void __launch_bounds__(RNN_ONE) rnn_final_kernel(RnnParams P, int n2) {
     extern __shared__ u64 s_key[];   // n2: a power of two >= 2 RNN_ONE and >= seeds
-    __shared__ int s_scan[RNN_ONE_WAVES];
+    __shared__ int s_scan[SCAN_WORDS];
     const int tid = threadIdx.x;
     int kept = 0;
     for (int i = tid; i < n2; i += RNN_ONE) {
@@ -264,7 +242,7 @@ __global__ void __launch_bounds__(RNN_ONE) rnn_final_kernel(RnnParams P, int n2)
         s_key[i] = key;
     }
     int retired;
-    block_exclusive_scan(kept, s_scan, &retired);   // (its barriers also publish s_key)
+    scan_workgroup<RNN_ONE>(kept, s_scan, &retired);   // (its two barriers, passed by every thread, also publish s_key to the sort below)
     for (int k = 2; k <= n2; k <<= 1) {
         for (int j = k >> 1; j > 0; j >>= 1) {
             for (int i = tid; i < n2; i += RNN_ONE) {
@@ -281,7 +259,7 @@ __global__ void __launch_bounds__(RNN_ONE) rnn_final_kernel(RnnParams P, int n2)
     int cnt = 0;
     for (int i = lo; i < lo + per; i++) cnt += (s_key[i] != RNN_DROPPED && (i == 0 || s_key[i] != s_key[i - 1])) ? 1 : 0;
     int M;
-    int out = block_exclusive_scan(cnt, s_scan, &M);
+    int out = scan_workgroup<RNN_ONE>(cnt, s_scan, &M);   // (s_scan again: the sort's barriers lie between the two scans)
     for (int i = lo; i < lo + per; i++) {
         const u64 key = s_key[i];
         if (key != RNN_DROPPED && (i == 0 || key != s_key[i - 1]) && out < P.capacity) {

@@ -19,6 +19,7 @@
 // A source is a struct with `__device__ bool get(int64_t i, float &v) const`: element i's value, and whether it takes part.
 #pragma once
 #include "common.hpp"
+#include "device_utils.hpp"
 
 namespace lvdgs {
 
@@ -65,28 +66,10 @@ __device__ __forceinline__ void hist_add(uint32_t *hist, bool ok, uint32_t digit
 
 // The bucket that holds rank k among 256 counts, one count per thread.  median: k is the lower-median rank of the counts' total (pass 0).
 // -> true in the one thread whose bucket it is (none when the total is zero); k_in_bucket: the rank inside it; total: in every thread.
-// sh: SEL_THREADS / WAVE words of LDS.  Two barriers; the caller puts one more in front of the next use of sh.
+// sh: SCAN_WORDS words of LDS for the one workgroup scan (two barriers, none needed in front of the next call: device_utils.hpp).
 __device__ __forceinline__ bool pick_bucket(uint32_t count, bool median, uint32_t k, uint32_t *sh, uint32_t *k_in_bucket, uint32_t *total) {
-    const int lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE;
-    uint32_t incl = count;
-#pragma unroll
-    for (int o = 1; o < WAVE; o <<= 1) {
-        const uint32_t up = (uint32_t)__shfl_up((int)incl, o, WAVE);
-        if (lane >= o) incl += up;
-    }
-    __syncthreads();
-    if (lane == WAVE - 1) sh[wave] = incl;
-    __syncthreads();
-    uint32_t base = 0, sum = 0;
-#pragma unroll
-    for (int w = 0; w < SEL_THREADS / WAVE; w++) {
-        const uint32_t t = sh[w];
-        if (w < wave) base += t;
-        sum += t;
-    }
-    *total = sum;
-    if (median) k = lower_median_rank(sum);
-    const uint32_t excl = base + incl - count;
+    const uint32_t excl = scan_workgroup<SEL_THREADS>(count, sh, total);
+    if (median) k = lower_median_rank(*total);
     *k_in_bucket = k - excl;
     return count > 0 && excl <= k && k - excl < count;
 }
@@ -96,7 +79,7 @@ __device__ __forceinline__ bool pick_bucket(uint32_t count, bool median, uint32_
 template <class Src>
 __global__ void __launch_bounds__(SEL_THREADS) select_pass_kernel(Src src, int64_t n, SelectState *st, int pass, int64_t k_fixed) {
     __shared__ uint32_t hist[SEL_THREADS];
-    __shared__ uint32_t sh[SEL_THREADS / WAVE];
+    __shared__ uint32_t sh[SCAN_WORDS];
     __shared__ int s_last;
     if (pass > 0 && st->n == 0) return;   // uniform over the launch: nothing took part, the result is NaN
     hist[threadIdx.x] = 0;
@@ -159,7 +142,7 @@ int launch_select(const Src &src, int64_t n, SelectState *st, int64_t k_fixed, c
 }
 
 // One workgroup, one segment of n elements: the bits of the lower median of those that take part (quiet NaN: none), in every thread.
-// hist: SEL_THREADS words of LDS, sh: SEL_THREADS / WAVE + 2 words.  Called by all SEL_THREADS threads.
+// hist: SEL_THREADS words of LDS, sh: SCAN_WORDS + 2 words.  Called by all SEL_THREADS threads.
 template <class Src>
 __device__ __forceinline__ uint32_t select_segment(const Src &src, int n, uint32_t *hist, uint32_t *sh) {
     uint32_t prefix = 0, k = 0, taking_part = 0;
@@ -181,12 +164,12 @@ __device__ __forceinline__ uint32_t select_segment(const Src &src, int n, uint32
         if (pass == 0) taking_part = total;
         if (taking_part == 0) return SEL_QUIET_NAN;   // uniform
         if (owner) {
-            sh[SEL_THREADS / WAVE] = prefix | ((uint32_t)threadIdx.x << shift);
-            sh[SEL_THREADS / WAVE + 1] = k_in;
+            sh[SCAN_WORDS] = prefix | ((uint32_t)threadIdx.x << shift);
+            sh[SCAN_WORDS + 1] = k_in;
         }
         __syncthreads();
-        prefix = sh[SEL_THREADS / WAVE];
-        k = sh[SEL_THREADS / WAVE + 1];
+        prefix = sh[SCAN_WORDS];
+        k = sh[SCAN_WORDS + 1];
         __syncthreads();
     }
     return select_unkey(prefix);

@@ -50,12 +50,7 @@ __global__ void __launch_bounds__(256) radix_rowscan_kernel(uint32_t *__restrict
     for (int b0 = 0; b0 < nblk; b0 += 64) {
         const int b = b0 + lane;
         const uint32_t v = b < nblk ? row[b] : 0u;
-        uint32_t inc = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t t = __shfl_up(inc, off, 64);
-            if (lane >= off) inc += t;
-        }
+        const uint32_t inc = wave_inclusive_scan(v);
         if (b < nblk) row[b] = carry + inc - v;
         carry += __shfl(inc, 63, 64);
     }
@@ -180,22 +175,6 @@ constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_IPT = 8;
 constexpr int SCAN_CHUNK = SCAN_THREADS * SCAN_IPT;
 
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t *s, uint32_t *total) {
-    const int tid = threadIdx.x;
-    s[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < SCAN_THREADS; off <<= 1) {
-        const uint32_t t = tid >= off ? s[tid - off] : 0u;
-        __syncthreads();
-        s[tid] += t;
-        __syncthreads();
-    }
-    const uint32_t incl = s[tid];
-    *total = s[SCAN_THREADS - 1];
-    __syncthreads();
-    return incl - v;
-}
-
 // slot_base[i] = exclusive scan over i of tiles_touched[i]: where Gaussian i's pairs (and, in the backward pass, its
 // per-pair partial gradients) start in the unsorted pair list.
 // One launch: preprocess_fwd left the pair count of every 256 Gaussians in `blocksums`; every workgroup here first
@@ -204,11 +183,11 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t *s
 __global__ void __launch_bounds__(SCAN_THREADS) scan_apply_kernel(const uint32_t *__restrict__ tt, int N,
                                                                   const uint32_t *__restrict__ blocksums,
                                                                   uint32_t *__restrict__ slot_base, uint32_t *__restrict__ total_out) {
-    __shared__ uint32_t s[SCAN_THREADS];
+    __shared__ uint32_t s[SCAN_WORDS];   // both scans' words: the second call needs no barrier in front (device_utils.hpp)
     uint32_t before = 0;
     for (int b = threadIdx.x; b < (int)blockIdx.x * (SCAN_CHUNK / 256); b += SCAN_THREADS) before += blocksums[b];
     uint32_t prefix;
-    block_exclusive_scan(before, s, &prefix);  // only the total is of interest
+    scan_workgroup<SCAN_THREADS>(before, s, &prefix);  // only the total is of interest
     uint32_t v[SCAN_IPT];
     uint32_t sum = 0;
     const int base = blockIdx.x * SCAN_CHUNK + threadIdx.x * SCAN_IPT;
@@ -218,7 +197,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) scan_apply_kernel(const uint32_t
         sum += v[k];
     }
     uint32_t total;
-    uint32_t run = block_exclusive_scan(sum, s, &total) + prefix;
+    uint32_t run = scan_workgroup<SCAN_THREADS>(sum, s, &total) + prefix;
 #pragma unroll
     for (int k = 0; k < SCAN_IPT; k++) {
         if (base + k < N) slot_base[base + k] = run;

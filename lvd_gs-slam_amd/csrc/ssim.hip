@@ -56,24 +56,6 @@ struct SsimParams {
     SsimView v[SSIM_BATCH];
 };
 
-__device__ __forceinline__ float block_sum8(float v, float *s) {
-    v = wave_sum_to_lane63(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 63) s[wave] = v;
-    __syncthreads();
-    return (((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7])));
-}
-
-__device__ __forceinline__ float block_sum4(float v, float *s) {
-    v = wave_sum_to_lane63(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 63) s[wave] = v;
-    __syncthreads();
-    return ((s[0] + s[1]) + s[2]) + s[3];
-}
-
 template <bool GRAD>
 __global__ void __launch_bounds__(SSIM_THREADS) ssim_l1_kernel(SsimParams p) {
     // sxy: the two input windows; later the three derivative maps (3 * S2 * P2 <= 2 * S1 * P1)
@@ -248,8 +230,8 @@ __global__ void __launch_bounds__(SSIM_THREADS) ssim_l1_kernel(SsimParams p) {
 
     // ---- the two sums of this workgroup ----
     {
-        const float t1 = block_sum8(l1, s_red);
-        const float t2 = block_sum8(msum, s_red);
+        const float t1 = block_sum<8>(l1, s_red);
+        const float t2 = block_sum<8>(msum, s_red);
         if (tid == 0) {
             const size_t wg = ((size_t)plane * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
             v.partial[2 * wg] = t1;
@@ -265,10 +247,9 @@ __global__ void __launch_bounds__(SSIM_THREADS) ssim_l1_kernel(SsimParams p) {
             acc += in ? fabsf(dD[k] - dZ[k]) : 0.f;
             cnt += in ? 1u : 0u;
         }
-        const float t3 = block_sum8(acc, s_red);
+        const float t3 = block_sum<8>(acc, s_red);
         // an exact integer count (a float sum would round above 2^24 pixels)
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) cnt += (uint32_t)__shfl_xor((int)cnt, off, 64);
+        cnt = wave_sum(cnt);
         __syncthreads();
         if ((tid & 63) == 0) s_red[tid >> 6] = __uint_as_float(cnt);
         __syncthreads();
@@ -378,8 +359,8 @@ __global__ void __launch_bounds__(512) ssim_finish_kernel(const float2 *__restri
 #pragma unroll
         for (int k = 0; k < 4; k++) { a += v[k].x; b += v[k].y; }
     }
-    const float ta = block_sum8(a, s_red);
-    const float tb = block_sum8(b, s_red);
+    const float ta = block_sum<8>(a, s_red);
+    const float tb = block_sum<8>(b, s_red);
     if (threadIdx.x == 0) {
         out[0] = ta * inv_count;
         out[1] = tb * inv_count;
@@ -403,15 +384,14 @@ __global__ void __launch_bounds__(512) masked_loss_finish_kernel(MaskedFinishPar
 #pragma unroll
         for (int k = 0; k < 4; k++) { a += q[k].x; b += q[k].y; }
     }
-    const float ta = block_sum8(a, s_red);
-    const float tb = block_sum8(b, s_red);
+    const float ta = block_sum<8>(a, s_red);
+    const float tb = block_sum<8>(b, s_red);
     float d = 0.f;
     unsigned long long n = 0ull;
     if (v.dpart)
         for (int i = threadIdx.x; i < p.ntiles; i += 512) { const float2 q = v.dpart[i]; d += q.x; n += (unsigned long long)__float_as_uint(q.y); }
-    const float td = block_sum8(d, s_red);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) n += (unsigned long long)__shfl_xor((long long)n, off, 64);
+    const float td = block_sum<8>(d, s_red);
+    n = wave_sum(n);
     if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = n;
     __syncthreads();
     if (threadIdx.x == 0) {

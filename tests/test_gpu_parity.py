@@ -320,6 +320,47 @@ def test_edge_cases_empty_culled_single_and_huge():
     _check_backward(b_hip, b_ora, ["means3D", "opacities", "scales", "rotations", "colors", "tau"], f_ora, W, H)
 
 
+@pytest.mark.parametrize("N", [1, 2048, 2049, 4099])
+def test_slot_bases_are_the_exclusive_scan_of_tiles_touched(N):
+    """scan_apply_kernel against numpy.  The kernel runs behind the projection of lvdgs_forward_prepare (the single-call forward of an
+    image this small groups by counting and makes its slot bases in the scatter instead), so the test makes that call and reads
+    tiles_touched, the slot bases and the pair count it returns.  A workgroup scans a chunk of 2048 Gaussians (256 threads x 8): 4099 is
+    two full chunks and a ragged third of three elements -- the prefix from the earlier workgroups' block sums, the carry across waves
+    and the tail guard all take part; 2048 and 2049 sit on either side of the chunk boundary."""
+    import ctypes as C
+    _, hr, syn = _mods()
+    from lvdgs import _lib
+    L = _lib.lib()
+    W = H = 64
+    g, cam = _scene(syn, N, W, H, seed=11)
+    dev = torch.device("cuda")
+    p = lambda t: C.c_void_p(t.data_ptr())
+    t = {k: v.to(dev).contiguous() for k, v in g.items()}
+    mats = [getattr(cam, k).to(dev).contiguous() for k in ("world_view_transform", "full_proj_transform", "projection_matrix", "camera_center")]
+    buf = lambda n: torch.zeros(max(int(n), 256), dtype=torch.uint8, device=dev)
+    bg, radii, n_touched = torch.zeros(3, device=dev), torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev)
+    color, depth, opacity = (torch.empty(c, H, W, device=dev) for c in (3, 1, 1))
+    geom, image, scratch = buf(L.lvdgs_geom_bytes(N)), buf(L.lvdgs_image_bytes(W, H)), buf(L.lvdgs_prepare_scratch_bytes(N))
+    a = _lib.Args()
+    a.image_height, a.image_width, a.tanfovx, a.tanfovy, a.scale_modifier, a.sh_degree = H, W, cam.tanfovx, cam.tanfovy, 1.0, 0
+    a.bg, a.viewmatrix, a.projmatrix, a.projmatrix_raw, a.campos = p(bg), p(mats[0]), p(mats[1]), p(mats[2]), p(mats[3])
+    a.num_gaussians, a.sh_coeffs = N, 0
+    a.means3D, a.opacities, a.scales, a.rotations, a.colors_precomp = p(t["means3D"]), p(t["opacities"]), p(t["scales"]), p(t["rotations"]), p(t["colors"])
+    a.radii, a.n_touched, a.out_color, a.out_depth, a.out_opacity = p(radii), p(n_touched), p(color), p(depth), p(opacity)
+    a.geom_state, a.geom_bytes, a.image_state, a.image_bytes = p(geom), geom.numel(), p(image), image.numel()
+    a.scratch, a.scratch_bytes = p(scratch), scratch.numel()
+    D = C.c_int64()
+    _lib.check(L.lvdgs_forward_prepare(C.byref(a), C.byref(D), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "prepare")
+    torch.cuda.synchronize()
+    lay = _lib.StateLayout()
+    _lib.check(L.lvdgs_state_layout_query(N, max(D.value, 1), W, H, C.byref(lay)), "layout")
+    tt = hr._view(geom, lay.geom_tiles_touched, N, np.uint32).astype(np.uint64)
+    slot_base = hr._view(geom, lay.geom_slot_base, N, np.uint32).astype(np.uint64)
+    assert N == 1 or (tt[: N // 2].any() and tt[N // 2:].any()), "the scene lists nothing: the scan would be checked on zeros"
+    np.testing.assert_array_equal(slot_base, np.concatenate([[0], np.cumsum(tt)[:-1]]))
+    assert D.value == int(tt.sum())
+
+
 def test_many_gaussians_per_tile_and_early_termination():
     """> 256 entries per tile (several staging rounds) and opaque stacks that hit the T < 1e-4 stop."""
     orc, hr, syn = _mods()
