@@ -980,6 +980,62 @@ size_t lvdgs_dynamic_mask_state_bytes(int32_t width, int32_t height, int32_t his
 size_t lvdgs_dynamic_mask_scratch_bytes(int32_t width, int32_t height);
 int lvdgs_dynamic_mask(const lvdgs_dynamic_mask_args *a, void *stream);
 
+/* ---- seeding a keyframe's Gaussians (GaussianModel.create_pcd_from_image_and_depth: a full sort for the median, nonzero, a host
+ * draw, an upload and about fifteen gathers, with two host waits) ----
+ * Pixel i = v*width + u is VALID when depth[i] > 0 && depth[i] <= depth_trunc (NaN fails).  n_valid = the number of valid pixels;
+ * n_keep = (int64)((double)n_valid * inv_downsample), on the device, in double (Python's int(n_valid * (1.0 / downsample))).
+ * Every pixel has a 32-bit key, all arithmetic uint32 with wrap-around:
+ *   fmix32(h): h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16
+ *   key(i)   = fmix32( fmix32((uint32)i + seed_lo) ^ seed_hi )              seed = seed_hi:seed_lo
+ * fmix32, the addition and the xor are bijections of uint32, so for one seed all keys of an image are distinct: no ties.
+ * SELECTED are the n_keep valid pixels with the smallest keys, {i valid : key(i) <= t} with t the key of rank n_keep - 1 among the
+ * valid keys; n_keep == 0 selects nothing.  Output rows are in ascending pixel index.  For selected pixel i with z = depth[i], in
+ * float32, evaluated as written with no contraction:
+ *   cam = ( ((float)u - cx) * z / fx, ((float)v - cy) * z / fy, z )
+ *   xyz[j] = (cam[0]-T[0])*R[0][j] + (cam[1]-T[1])*R[1][j] + (cam[2]-T[2])*R[2][j], summed in that order (p_cam = R p_world + T)
+ *   per channel c = min(max(gain * image[ch][i] + offset, 0), 1), q = (uint8)(c * 255) by truncation, rgb = (float)q * (1.0f / 255.0f)
+ *   -- the bits of `uint8.float() / 255.0` in PyTorch on a GPU, which multiplies by the float32 reciprocal of a scalar divisor; a true
+ *   division differs in the last bit for 126 of the 256 values --, f_dc = (rgb - 0.5f) / 0.28209479177387814f.  A NaN colour is
+ *   outside the contract.
+ * gain, offset: one float each ON THE DEVICE (NULL: 1 and 0); the caller's exp(exposure_a) and exposure_b.
+ * want_median: the (P - 1) / 2-th smallest of all P = width*height depth values, the bits of torch.median (a NaN depth is outside
+ * that contract, as for lvdgs_frame_summary).
+ * A clear of the state and eight launches (twelve with the median), enqueued at once; no host wait.  host_state:
+ * LVDGS_SEED_HOST_BYTES bytes of page-locked, mapped host memory (the host address), as int32 words: [LVDGS_SEED_SEQ] the call's
+ * `seq`, WRITTEN LAST; [_N_VALID]; [_N_KEEP], the rows written; [_MEDIAN] the float bits, or the quiet NaN 0x7fc00000 when not asked
+ * for; [_THRESHOLD] the key t, for diagnosis; zeros after it.  scratch: the bytes lvdgs_seed_scratch_bytes gives (0: the size is
+ * refused), no initialisation needed.  No atomic decides an output position: two calls give the same bytes.
+ * Before any launch -- LVDGS_E_RANGE: width or height below 1, more than 2^31 - 1 pixels, inv_downsample NaN or outside (0, 1],
+ * capacity < (int64)((double)(width*height) * inv_downsample) (the host-side bound of n_keep); LVDGS_E_INVALID: args, depth, R, T, xyz,
+ * host_state or scratch NULL, rgb or f_dc NULL with an image, scratch too small; LVDGS_E_HIP: host_state is not mapped pinned memory. */
+#define LVDGS_SEED_HOST_BYTES 64
+enum {
+    LVDGS_SEED_SEQ = 0,
+    LVDGS_SEED_N_VALID = 1,
+    LVDGS_SEED_N_KEEP = 2,
+    LVDGS_SEED_MEDIAN = 3,
+    LVDGS_SEED_THRESHOLD = 4
+};
+typedef struct lvdgs_seed_args {
+    int32_t width, height;
+    float fx, fy, cx, cy, depth_trunc;
+    int32_t want_median;
+    double inv_downsample;        /* in (0, 1]                                      */
+    uint64_t seed;
+    uint32_t seq;
+    int32_t capacity;             /* rows the outputs hold                          */
+    const float *image;           /* 3*H*W planar, or NULL: no colours              */
+    const float *gain, *offset;   /* one float each on the device, or NULL: 1 and 0 */
+    const float *depth;           /* H*W                                            */
+    const float *R, *T;           /* 9 row-major and 3, on the device               */
+    float *xyz, *rgb, *f_dc;      /* out capacity*3 each (rgb, f_dc may be NULL without an image) */
+    int32_t *pixel;               /* out capacity: the rows' pixel indices, or NULL */
+    int32_t *host_state;          /* LVDGS_SEED_HOST_BYTES, pinned host (the host address) */
+    void *scratch; size_t scratch_bytes;
+} lvdgs_seed_args;
+size_t lvdgs_seed_scratch_bytes(int32_t width, int32_t height);
+int lvdgs_seed_points(const lvdgs_seed_args *a, void *stream);
+
 /* ---- diagnostics ---- */
 const char *lvdgs_last_error(void);
 const char *lvdgs_version(void);

@@ -234,6 +234,22 @@ DYNAMIC_MASK_INFO = ("boxes", "vehicle_detected", "use_sam_result", "filtered", 
                      "static_pixels", "expanded_pixels", "valid_pixels", "depth_pixels")   # the words' names, in LVDGS_DYNAMIC_MASK_INFO_* order
 
 
+class SeedArgs(C.Structure):
+    """struct lvdgs_seed_args (include/lvdgs.h)."""
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32),
+        ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("depth_trunc", C.c_float),
+        ("want_median", C.c_int32), ("inv_downsample", C.c_double), ("seed", C.c_uint64), ("seq", C.c_uint32), ("capacity", C.c_int32),
+        ("image", _fp), ("gain", _fp), ("offset", _fp), ("depth", _fp), ("R", _fp), ("T", _fp),
+        ("xyz", _fp), ("rgb", _fp), ("f_dc", _fp), ("pixel", _fp), ("host_state", _fp),
+        ("scratch", _fp), ("scratch_bytes", C.c_size_t),
+    ]
+
+
+SEED_HOST_BYTES = 64
+SEED_SEQ, SEED_N_VALID, SEED_N_KEEP, SEED_MEDIAN, SEED_THRESHOLD = 0, 1, 2, 3, 4
+
+
 class StateLayout(C.Structure):
     _fields_ = [(n, C.c_size_t) for n in (
         "geom_rec", "geom_tiles_touched", "geom_slot_base", "bin_point_list", "bin_tile_keys",
@@ -259,6 +275,7 @@ EXPORTS = (
     "lvdgs_edge_mask_scratch_bytes", "lvdgs_edge_mask", "lvdgs_frame_summary_scratch_bytes", "lvdgs_frame_summary",
     "lvdgs_ms_deform_attn_forward", "lvdgs_ms_deform_attn_backward",
     "lvdgs_dynamic_mask_state_bytes", "lvdgs_dynamic_mask_scratch_bytes", "lvdgs_dynamic_mask",
+    "lvdgs_seed_scratch_bytes", "lvdgs_seed_points",
     "lvdgs_last_error", "lvdgs_version", "lvdgs_profile_enable",
     "lvdgs_profile_reset", "lvdgs_profile_read",
 )
@@ -371,6 +388,9 @@ def lib():
         L.lvdgs_dynamic_mask_scratch_bytes.restype = C.c_size_t
         L.lvdgs_dynamic_mask_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
         L.lvdgs_dynamic_mask.argtypes = [C.POINTER(DynamicMaskArgs), C.c_void_p]
+        L.lvdgs_seed_scratch_bytes.restype = C.c_size_t
+        L.lvdgs_seed_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
+        L.lvdgs_seed_points.argtypes = [C.POINTER(SeedArgs), C.c_void_p]
         L.lvdgs_profile_enable.argtypes = [C.c_int]
         L.lvdgs_profile_read.argtypes = [C.POINTER(KernelTime), C.c_int]
         _lib = L

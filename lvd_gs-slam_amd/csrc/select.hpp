@@ -16,8 +16,14 @@
 //                             counters to the pass' 256 global counters (integer atomics: order-free), and the LAST workgroup to arrive
 //                             (an agent-scope ticket, as in depth_align.hip / pnp.hip) picks the bucket.  No workgroup waits on another.
 //   select_segment<Src>       one workgroup, one short segment, the four passes in a loop (the replica rule: 1024 blocks of an image).
-// A source is a struct with `__device__ bool get(int64_t i, float &v) const`: element i's value, and whether it takes part.
+// A source is a struct with `__device__ bool get(int64_t i, float &v) const`: element i's value, and whether it takes part.  A source
+// with `__device__ bool key(int64_t i, uint32_t &k) const` instead hands out the 32-bit key itself (seeding.hip: a hash of the pixel
+// index); the answer is then the key of that rank, st->prefix as it stands.
+// The rank is a SelectRank: a fixed one, or a function of the number n that pass 0 finds taking part -- the lower median, or the last
+// of the (int64)((double)n * fraction) smallest.
 #pragma once
+#include <type_traits>
+
 #include "common.hpp"
 #include "device_utils.hpp"
 
@@ -47,6 +53,34 @@ __device__ __forceinline__ uint32_t select_result_bits(uint32_t n, uint32_t pref
 // torch.median's rank among n elements: the lower median
 __host__ __device__ inline uint32_t lower_median_rank(uint32_t n) { return n ? (n - 1) / 2 : 0; }
 
+// The rank looked for among the n elements that take part; n is known when pass 0's last workgroup picks its bucket.
+struct SelectRank {
+    int64_t fixed;      // >= 0: this rank (the caller guarantees fixed < n, or accepts the NaN of n == 0)
+    double fraction;    // fixed < 0.  0: the lower median; in (0, 1]: rank keep - 1 with keep = (int64)((double)n * fraction), rank 0 when keep == 0
+    __host__ __device__ uint32_t of(uint32_t n) const {
+        if (fixed >= 0) return (uint32_t)fixed;
+        if (fraction == 0.0) return lower_median_rank(n);
+        const int64_t keep = (int64_t)((double)n * fraction);
+        return keep > 0 ? (uint32_t)(keep - 1) : 0u;
+    }
+};
+__host__ __device__ inline SelectRank select_rank(int64_t k_fixed) { return SelectRank{k_fixed, 0.0}; }   // k_fixed < 0: the lower median
+
+template <class Src, class = void> struct yields_key : std::false_type {};
+template <class Src> struct yields_key<Src, std::void_t<decltype(&Src::key)>> : std::true_type {};
+// Element i's key, and whether it takes part.
+template <class Src>
+__device__ __forceinline__ bool source_key(const Src &src, int64_t i, uint32_t &key) {
+    if constexpr (yields_key<Src>::value) {
+        return src.key(i, key);
+    } else {
+        float v = 0.f;
+        const bool in = src.get(i, v);
+        key = select_key(__float_as_uint(v));
+        return in;
+    }
+}
+
 inline int select_blocks(int64_t n) {
     const int64_t b = (n + (int64_t)SEL_THREADS * SEL_ITEMS_PER_THREAD - 1) / ((int64_t)SEL_THREADS * SEL_ITEMS_PER_THREAD);
     return (int)(b < 1 ? 1 : (b > SEL_MAX_BLOCKS ? SEL_MAX_BLOCKS : b));
@@ -64,20 +98,20 @@ __device__ __forceinline__ void hist_add(uint32_t *hist, bool ok, uint32_t digit
     if (ok && digit != d0) atomicAdd(&hist[digit], 1u);
 }
 
-// The bucket that holds rank k among 256 counts, one count per thread.  median: k is the lower-median rank of the counts' total (pass 0).
+// The bucket that holds rank k among 256 counts, one count per thread.  from_total: k is rank.of(the counts' total) (pass 0).
 // -> true in the one thread whose bucket it is (none when the total is zero); k_in_bucket: the rank inside it; total: in every thread.
 // sh: SCAN_WORDS words of LDS for the one workgroup scan (two barriers, none needed in front of the next call: device_utils.hpp).
-__device__ __forceinline__ bool pick_bucket(uint32_t count, bool median, uint32_t k, uint32_t *sh, uint32_t *k_in_bucket, uint32_t *total) {
+__device__ __forceinline__ bool pick_bucket(uint32_t count, bool from_total, const SelectRank &rank, uint32_t k, uint32_t *sh, uint32_t *k_in_bucket,
+                                            uint32_t *total) {
     const uint32_t excl = scan_workgroup<SEL_THREADS>(count, sh, total);
-    if (median) k = lower_median_rank(*total);
+    if (from_total) k = rank.of(*total);
     *k_in_bucket = k - excl;
     return count > 0 && excl <= k && k - excl < count;
 }
 
-// Pass `pass` (0: the key's top byte) of a selection over src's elements 0 .. n - 1.  k_fixed < 0: the lower median of the elements
-// that take part; otherwise that rank (the caller guarantees k_fixed < the number that take part, or accepts the NaN of n == 0).
+// Pass `pass` (0: the key's top byte) of a selection over src's elements 0 .. n - 1, for the rank `rank` gives.
 template <class Src>
-__global__ void __launch_bounds__(SEL_THREADS) select_pass_kernel(Src src, int64_t n, SelectState *st, int pass, int64_t k_fixed) {
+__global__ void __launch_bounds__(SEL_THREADS) select_pass_kernel(Src src, int64_t n, SelectState *st, int pass, SelectRank rank) {
     __shared__ uint32_t hist[SEL_THREADS];
     __shared__ uint32_t sh[SCAN_WORDS];
     __shared__ int s_last;
@@ -90,9 +124,8 @@ __global__ void __launch_bounds__(SEL_THREADS) select_pass_kernel(Src src, int64
     const int64_t stride = (int64_t)gridDim.x * SEL_THREADS;
     for (int64_t base = (int64_t)blockIdx.x * SEL_THREADS; base < n; base += stride) {   // (base is uniform: whole waves reach hist_add)
         const int64_t i = base + threadIdx.x;
-        float v = 0.f;
-        const bool in = i < n && src.get(i, v);
-        const uint32_t key = select_key(__float_as_uint(v));
+        uint32_t key = 0;
+        const bool in = i < n && source_key(src, i, key);
         hist_add(hist, in && (key & high) == prefix, (key >> shift) & 255u);
     }
     __syncthreads();
@@ -115,10 +148,9 @@ __global__ void __launch_bounds__(SEL_THREADS) select_pass_kernel(Src src, int64
     if (!s_last) return;
     // ---- the last workgroup: the bucket of rank k ----
     const uint32_t count = __hip_atomic_load(&st->hist[pass][threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool median = pass == 0 && k_fixed < 0;
-    const uint32_t k = pass == 0 ? (uint32_t)(k_fixed < 0 ? 0 : k_fixed) : st->k;
+    const uint32_t k = pass == 0 ? 0u : st->k;
     uint32_t k_in = 0, total = 0;
-    const bool owner = pick_bucket(count, median, k, sh, &k_in, &total);
+    const bool owner = pick_bucket(count, pass == 0, rank, k, sh, &k_in, &total);
     if (owner) {
         st->prefix = prefix | ((uint32_t)threadIdx.x << shift);
         st->k = k_in;
@@ -131,20 +163,25 @@ __global__ void __launch_bounds__(SEL_THREADS) select_pass_kernel(Src src, int64
 
 // The four passes over one array, enqueued at once.  The caller has zeroed *st on the stream in front of them.
 template <class Src>
-int launch_select(const Src &src, int64_t n, SelectState *st, int64_t k_fixed, const char *name, hipStream_t s) {
+int launch_select(const Src &src, int64_t n, SelectState *st, SelectRank rank, const char *name, hipStream_t s) {
     ProfScope ps(name, s);
     const int blocks = select_blocks(n);
     for (int pass = 0; pass < SEL_PASSES; pass++) {
-        hipLaunchKernelGGL(select_pass_kernel<Src>, dim3(blocks), dim3(SEL_THREADS), 0, s, src, n, st, pass, k_fixed);
+        hipLaunchKernelGGL(select_pass_kernel<Src>, dim3(blocks), dim3(SEL_THREADS), 0, s, src, n, st, pass, rank);
         LVDGS_LAUNCH_CHECK(name, 0, s);
     }
     return LVDGS_OK;
+}
+template <class Src>
+int launch_select(const Src &src, int64_t n, SelectState *st, int64_t k_fixed, const char *name, hipStream_t s) {
+    return launch_select(src, n, st, select_rank(k_fixed), name, s);
 }
 
 // One workgroup, one segment of n elements: the bits of the lower median of those that take part (quiet NaN: none), in every thread.
 // hist: SEL_THREADS words of LDS, sh: SCAN_WORDS + 2 words.  Called by all SEL_THREADS threads.
 template <class Src>
 __device__ __forceinline__ uint32_t select_segment(const Src &src, int n, uint32_t *hist, uint32_t *sh) {
+    const SelectRank median = select_rank(-1);
     uint32_t prefix = 0, k = 0, taking_part = 0;
     for (int pass = 0; pass < SEL_PASSES; pass++) {
         hist[threadIdx.x] = 0;
@@ -160,7 +197,7 @@ __device__ __forceinline__ uint32_t select_segment(const Src &src, int n, uint32
         }
         __syncthreads();
         uint32_t k_in = 0, total = 0;
-        const bool owner = pick_bucket(hist[threadIdx.x], pass == 0, k, sh, &k_in, &total);
+        const bool owner = pick_bucket(hist[threadIdx.x], pass == 0, median, k, sh, &k_in, &total);
         if (pass == 0) taking_part = total;
         if (taking_part == 0) return SEL_QUIET_NAN;   // uniform
         if (owner) {

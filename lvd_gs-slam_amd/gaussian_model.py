@@ -146,6 +146,10 @@ class GaussianModel:
         self.opacity_activation, self.inverse_opacity_activation = torch.sigmoid, inverse_sigmoid
         self.rotation_activation = torch.nn.functional.normalize
         self.rng = np.random.default_rng(0)  # pixel subsampling of new keyframes
+        # seeding: "host" (the default: the PyTorch statements and self.rng's draw) or "fused" (seeding.seed_points: one library call
+        # and one wait per keyframe; the subsample is a function of (seed, pixel) with seed = call_seed(seed_base, seed_calls), so
+        # replicas that make the same calls seed the same pixels with no generator to keep in step -- another subset than the draw's).
+        self.seeding, self.seed_base, self.seed_calls = "host", 0, 0
         # Samples of densify_and_split.  A CPU generator with a fixed seed: the draw is made on the host and copied,
         # so every replica of the map (one per GPU in the sharded mapping loop) and a CPU run of the same loop split
         # their Gaussians identically.  Set to None for torch's global generator on the model's device.
@@ -334,8 +338,11 @@ class GaussianModel:
     def create_pcd_from_image(self, cam, init=False, scale=2.0, depthmap=None):
         """Back-project one keyframe: -> (xyz, features, log-scales, quaternions, opacity logits)."""
         dev = self.device
-        image_ab = (torch.exp(cam.exposure_a.detach()) * cam.original_image.to(dev) + cam.exposure_b.detach()).clamp(0.0, 1.0)
-        rgb = (image_ab * 255).to(torch.uint8).to(torch.float32) / 255.0  # colours go through 8 bits, as with an RGBD image
+        if self._seeds_fused():
+            rgb = None      # the call quantises the selected pixels itself
+        else:
+            image_ab = (torch.exp(cam.exposure_a.detach()) * cam.original_image.to(dev) + cam.exposure_b.detach()).clamp(0.0, 1.0)
+            rgb = (image_ab * 255).to(torch.uint8).to(torch.float32) / 255.0  # colours go through 8 bits, as with an RGBD image
         H, W = int(cam.image_height), int(cam.image_width)
         if depthmap is not None:
             depth = torch.as_tensor(np.asarray(depthmap) if not torch.is_tensor(depthmap) else depthmap, dtype=torch.float32, device=dev)
@@ -346,12 +353,35 @@ class GaussianModel:
                 depth = (1.0 + (noise - 0.5) * 0.05) * scale  # a fronto-parallel slab at `scale` until depth is learnt
         return self.create_pcd_from_image_and_depth(cam, rgb, depth.reshape(H, W), init)
 
-    def create_pcd_from_image_and_depth(self, cam, rgb, depth, init=False):
-        from .simple_knn import distCUDA2
+    def _seeds_fused(self):
+        """Does seeding take the library call?  ``seeding == "fused"`` and the model on a GPU (elsewhere: the host statements)."""
+        if self.seeding not in ("host", "fused"):
+            raise ValueError(f"GaussianModel.seeding: 'host' or 'fused', not {self.seeding!r}")
+        return self.seeding == "fused" and torch.device(self.device).type == "cuda"
 
+    def _seed_fused(self, cam, depth, downsample, point_size):
+        """``create_pcd_from_image_and_depth`` from ``valid = ...`` through ``colors = ...`` and the median of ``adaptive_pointsize``
+        as one ``seeding.seed_points`` call: -> (xyz, colors, their SH DC terms, point_size)."""
+        from . import _lib
+        from .seeding import call_seed, seed_points
+        dev = torch.device(self.device)
+        dev = torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
+        seed = call_seed(self.seed_base, self.seed_calls)
+        self.seed_calls += 1
+        adaptive = bool(self._cfg("Dataset", "adaptive_pointsize", False))
+        got = seed_points(_lib.f32(cam.original_image, dev), _lib.f32(depth, dev), (cam.fx, cam.fy, cam.cx, cam.cy), cam.R, cam.T, downsample,
+                          seed, gain=torch.exp(cam.exposure_a.detach()), offset=cam.exposure_b.detach(), want_median=adaptive)
+        if adaptive:
+            point_size = min(0.05, point_size * got.median_depth)
+        return got.xyz, got.rgb, got.f_dc, point_size
+
+    def create_pcd_from_image_and_depth(self, cam, rgb, depth, init=False):
         dev = self.device
         downsample = self._cfg("Dataset", "pcd_downsample_init" if init else "pcd_downsample", 32 if init else 64)
         point_size = self._cfg("Dataset", "point_size", 0.01)
+        if self._seeds_fused():      # rgb is not read: the call takes the colours from cam.original_image
+            xyz, colors, f_dc, point_size = self._seed_fused(cam, depth, downsample, point_size)
+            return self._seeds_from_points(xyz, colors, f_dc, point_size)
         valid = (depth > 0) & (depth <= 100.0)  # depth_trunc 100
         if self._cfg("Dataset", "adaptive_pointsize", False):
             point_size = min(0.05, point_size * float(depth.median()))
@@ -365,11 +395,17 @@ class GaussianModel:
         R, T = cam.R.to(dev).float(), cam.T.to(dev).float()
         xyz = (cam_pts - T[None, :]) @ R  # p_cam = R p_world + T
         colors = rgb[:, v, u].t().contiguous()
-        self.ply_input = (xyz, colors)
+        return self._seeds_from_points(xyz, colors, RGB2SH(colors), point_size)
 
+    def _seeds_from_points(self, xyz, colors, f_dc, point_size):
+        """Seeds at ``xyz``: -> (xyz, features, log-scales from the three nearest neighbours, identity quaternions, opacity logits)."""
+        from .simple_knn import distCUDA2
+
+        dev = self.device
+        self.ply_input = (xyz, colors)
         n = xyz.shape[0]
         features = torch.zeros(n, 3, (self.max_sh_degree + 1) ** 2, device=dev)
-        features[:, :3, 0] = RGB2SH(colors)
+        features[:, :3, 0] = f_dc
         dist2 = torch.clamp_min(distCUDA2(xyz), 0.0000001) * point_size if n else torch.empty(0, device=dev)
         scales = torch.log(torch.sqrt(dist2))[:, None]
         if not self.isotropic:

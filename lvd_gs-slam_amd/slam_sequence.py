@@ -118,7 +118,7 @@ class SlamSequence:
                  refine_loss_fn=None, keyframe_depth=None, idle_map_iters=0, camera_cls=None, cameras_extent=6.0, on_event=None,
                  group=None, aux_group=None, bands_ok=None, depth_align_fn=None, scale_remedy=None, depth_align_params=None,
                  pose_init=None, matcher=None, pose_init_params=None, frame_stats="torch", edge_mask="torch", dynamic_masks="dataset",
-                 masker=None):
+                 masker=None, seeding="host"):
         from .backend_map import map_window
         if camera_cls is None:
             from .camera_utils import Camera as camera_cls
@@ -171,6 +171,11 @@ class SlamSequence:
             if value not in ("torch", "fused"):
                 raise ValueError(f"{name}: 'torch' or 'fused', not {value!r}")
         self.frame_stats, self.edge_mask = frame_stats, edge_mask
+        # seeding: "host" (the default: GaussianModel's PyTorch statements and its host draw) or "fused" (seeding.seed_points: one call and
+        # one wait per keyframe, another subsample).  Set on the map; the front end's copies (clone_map) never seed.
+        if seeding not in ("host", "fused"):
+            raise ValueError(f"seeding: 'host' or 'fused', not {seeding!r}")
+        self.seeding = seeding
         # dynamic_masks: "dataset" (the default: dataset.static_mask's finished masks) or "detections" (`masker`, a
         # dynamic_mask.DynamicMasker: the masks, add_new_keyframe's dilation and valid_rgb come from its calls)
         if dynamic_masks not in ("dataset", "detections"):
@@ -197,6 +202,7 @@ class SlamSequence:
         self.kf_indices, self.current_window, self.occ_aware_visibility, self.cameras = [], [], {}, {}
         self.median_depth, self.theta = None, 0
         self.frontend_gaussians = gaussians      # the front end's copy of the map as of the last push (``_sync_backend``)
+        gaussians.seeding = self.seeding
         self.backend = make_backend(config, gaussians, pipeline_params, background, cameras_extent)
         self.projection_matrix = getProjectionMatrix2(znear=0.01, zfar=100.0, fx=dataset.fx, fy=dataset.fy, cx=dataset.cx, cy=dataset.cy,
                                                       W=dataset.width, H=dataset.height).transpose(0, 1).to(device=dataset.device)

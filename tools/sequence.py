@@ -176,6 +176,9 @@ def main():
     ap.add_argument("--dynamic-masks", choices=["dataset", "detections"], default="dataset",
                     help="the frames' static masks: the dataset's finished ones (default), or assembled on the device from the boxes and masks of "
                          "synthetic.RectangleDetector by dynamic_mask.DynamicMasker (lvdgs_dynamic_mask)")
+    ap.add_argument("--seeding", choices=["host", "fused"], default="host",
+                    help="a keyframe's new Gaussians: GaussianModel's PyTorch statements and host draw (default), or one seeding.seed_points "
+                         "call and one wait (lvdgs_seed_points; another subsample of the same size)")
     ap.add_argument("--verbose", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -187,8 +190,9 @@ def main():
                           **({"pose_init": a.pose_init} if a.pose_init else {}), **({"matcher": "descriptors"} if a.matcher == "descriptors" else {}),
                           **({"scale_remedy": "matches"} if a.scale_remedy == "matches" else {}),
                           **({"frame_stats": "fused"} if a.frame_stats == "fused" else {}), **({"edge_mask": "fused"} if a.edge_mask == "fused" else {}),
-                          **({"dynamic_masks": "detections"} if a.dynamic_masks == "detections" else {}))
-    out.update(frame_stats=a.frame_stats, edge_mask=a.edge_mask, dynamic_masks=a.dynamic_masks)
+                          **({"dynamic_masks": "detections"} if a.dynamic_masks == "detections" else {}),
+                          **({"seeding": "fused"} if a.seeding == "fused" else {}))
+    out.update(frame_stats=a.frame_stats, edge_mask=a.edge_mask, dynamic_masks=a.dynamic_masks, seeding=a.seeding)
     for rec in out.get("pose_init", []):
         print("  frame {frame:3d} kf {keyframe:3d} inliers {inl:>5} init error {e:.4f} ({r:.3f} deg; previous pose {p:.4f}) tracking iterations {it}".format(
             frame=rec["frame"], keyframe=rec["keyframe"], inl=rec.get("inliers", "-"), e=rec["init_translation_error"], r=rec["init_rotation_error_deg"],
