@@ -1036,6 +1036,131 @@ typedef struct lvdgs_seed_args {
 size_t lvdgs_seed_scratch_bytes(int32_t width, int32_t height);
 int lvdgs_seed_points(const lvdgs_seed_args *a, void *stream);
 
+/* ---- editing the map: prune_points, densify_and_prune and the pruning pass's rule as ONE plan, then one launch that moves every
+ * per-Gaussian array (GaussianModel: three map edits in a row, each a nonzero the host waits for, an index copy to the CPU and 21
+ * index_select / cat launches) ----
+ * lvdgs_map_edit_plan decides, counts and lays out; it moves no row.  For N = num_gaussians source rows it writes, per OUTPUT row r,
+ *   src[r] (the source row), kind[r] (LVDGS_EDIT_KEEP / _CLONE / _SPLIT0 / _SPLIT1) and noise_row[r] (-1 unless a split child),
+ * and into host_state -- page-locked, mapped host memory of host_bytes >= 4 (LVDGS_EDIT_HOST_SRC + 2 N) bytes, as int32 words --
+ *   [LVDGS_EDIT_SEQ] the call's `seq`, WRITTEN LAST; [_N_OUT] output rows; [_N_KEEP] those of kind KEEP; [_N_CLONE] those of kind
+ *   CLONE; [_N_SPLIT_SEL] the split SOURCES, pruned or not (the noise tensor has 2 n_split_sel rows); [_N_PRUNED_FINAL] the rows the
+ *   final prune took (prune mode: N - n_out); zeros up to [LVDGS_EDIT_HOST_SRC]; then src[0 .. n_out), and in prune mode with rule (b)
+ *   n_obs[src[r]] for r in [0, n_out) behind it.
+ * src, kind, noise_row hold `capacity` rows: at least N in prune mode, 2 N in densify mode (every source gives at most two rows).
+ *
+ * mode LVDGS_EDIT_PRUNE: the rows of [0, N) that survive, ascending, all of kind KEEP.  Row i is REMOVED
+ *   (a) remove != NULL:  when remove[i] != 0                                   (GaussianModel.prune_points(mask));
+ *   (b) remove == NULL:  n_obs[i] = the number of k < num_vis_rows with vis_rows[k][i] != 0, written to n_obs (int32, N) -- the rows'
+ *       elements are 0 or 1, vis_stride (1, 4 or 8; 0 means 1) bytes apart, little-endian: their first byte is read --, and the row
+ *       is removed when n_obs[i] <= prune_num && kf_id[i] >= min_kf_id      (the pruning pass of the mapping loop; its `odometry`
+ *       mode, n_obs < 3, is prune_num = 2 and min_kf_id = INT32_MIN).
+ * mode LVDGS_EDIT_DENSIFY: GaussianModel.densify_and_prune's three stages -- clone, split-then-prune, final prune -- as one
+ * classification per source row, in float32, evaluated as written.  With s = the row's scale_dims (1 or 3) raw scales, o its raw opacity:
+ *   g      = grad_accum[i] / denom[i], NaN -> 0                                (0/0 is 0; x/0 stays +-inf)
+ *   big(t) = the maximum of expf(t[j]) over j, a NaN propagating               (torch.max)
+ *   clone  = |g| >= grad_threshold && big(s) <= dense_extent                   (the clone stage takes the norm of g, the split stage g itself)
+ *   split  =  g  >= grad_threshold && big(s) >  dense_extent
+ *   child(t)[j] = logf(expf(t[j]) / 1.6f), the raw scale of both split children -- the SAME device expression in plan and apply
+ *   gone(t) = 1 / (1 + expf(-o)) < min_opacity || (max_screen_size != 0 && (0 > max_screen_size || big(t) > world_extent))
+ * The list before the final prune is the host path's: originals that were not split, ascending; then the clones, ascending by source;
+ * then SPLIT0 of every split source, ascending; then SPLIT1 likewise.  The final prune drops a KEEP or CLONE row of source i when
+ * gone(s) and a split child when gone(child(s)).  The screen-size term reads NO max_radii2D: densification_postfix has set that
+ * statistic to zero before the final prune looks at it, in every call, so `max_radii2D > max_screen_size` is `0 > max_screen_size` -- what
+ * the code does, not what the name suggests; and the world-size term applies only with max_screen_size != 0, as in the code.  The
+ * field max_radii2D is accepted and never read.  noise_row of a SPLITk child = k * n_split_sel + (the rank of its source among the
+ * split sources): the row of the host path's randn((2 n_split_sel, 3)) draw, whether the child survives or not.
+ * Four launches, enqueued at once, no host wait; no atomic decides a position: two calls give the same bytes.  scratch: the bytes
+ * lvdgs_map_edit_scratch_bytes(N) gives (0: N < 0), no initialisation needed.
+ * Before any launch -- LVDGS_E_INVALID: args, src, kind, noise_row, host_state or scratch NULL; a mode's inputs NULL (prune (b):
+ * kf_id, n_obs, a vis row; densify: grad_accum, denom, scaling, opacity); scratch too small; LVDGS_E_RANGE: N < 0, an unknown mode,
+ * num_vis_rows outside [0, LVDGS_EDIT_MAX_VIS_ROWS], a vis_stride other than 0, 1, 4, 8, scale_dims not 1 or 3, capacity or host_bytes too small; LVDGS_E_HIP: host_state
+ * is not mapped pinned memory.
+ *
+ * lvdgs_map_edit_apply moves the rows of up to LVDGS_EDIT_MAX_COLUMNS columns in one launch and does not wait: for every column and
+ * every r < n_out, out row r (row_bytes bytes, any value >= 1) is
+ *   kind KEEP, or new_rows LVDGS_EDIT_COPY:   the bytes of in row src[r]          (parameters, kf ids, n_obs, visibility rows)
+ *   new_rows LVDGS_EDIT_ZERO, kind != KEEP:   zeros                                (Adam moments of new rows)
+ *   new_rows LVDGS_EDIT_XYZ,   a split child: R(q) (noise[noise_row[r]] * expf(s)) + xyz, of the source's rows of `in` (xyz, 12
+ *     bytes), `rotation` (q = (r, x, y, z), 16 bytes, as stored: normalised here) and `scaling` (s; one value serves the three axes
+ *     when scale_dims is 1).  n = sqrtf(((r r + x x) + y y) + z z); r, x, y, z /= n; R as build_rotation states it:
+ *       R0 = (1 - 2 (y y + z z), 2 (x y - r z), 2 (x z + r y));  R1 = (2 (x y + r z), 1 - 2 (x x + z z), 2 (y z - r x));
+ *       R2 = (2 (x z - r y), 2 (y z + r x), 1 - 2 (x x + y y));   v[k] = noise[..][k] * expf(s[k]);
+ *       out[j] = ((Rj[0] v[0] + Rj[1] v[1]) + Rj[2] v[2]) + xyz[j], no contraction.   (CLONE rows copy.)
+ *   new_rows LVDGS_EDIT_SCALE, a split child: child(s) of the source's row of `in` (4 scale_dims bytes).   (CLONE rows copy.)
+ * Rows at and beyond n_out of an `out` array are not written.  in and out must not overlap.  src, kind, noise_row: a plan's outputs;
+ * n_out, n_split_sel: what the plan reported.  _XYZ and _SCALE columns are for densify mode.
+ * LVDGS_E_INVALID: args, src or kind NULL, a column's in or out NULL, row_bytes < 1, an unknown new_rows, an _XYZ column without noise_row,
+ * noise, scaling and rotation or whose row_bytes is not 12, a _SCALE column whose row_bytes is not 4 scale_dims; LVDGS_E_RANGE: more
+ * than LVDGS_EDIT_MAX_COLUMNS columns or fewer than 0, n_out or N < 0, scale_dims not 1 or 3. */
+#define LVDGS_EDIT_MAX_COLUMNS 48
+#define LVDGS_EDIT_MAX_VIS_ROWS 16
+enum { LVDGS_EDIT_PRUNE = 0, LVDGS_EDIT_DENSIFY = 1 };                                               /* mode     */
+enum { LVDGS_EDIT_KEEP = 0, LVDGS_EDIT_CLONE = 1, LVDGS_EDIT_SPLIT0 = 2, LVDGS_EDIT_SPLIT1 = 3 };   /* kind     */
+enum { LVDGS_EDIT_COPY = 0, LVDGS_EDIT_ZERO = 1, LVDGS_EDIT_XYZ = 2, LVDGS_EDIT_SCALE = 3 };        /* new_rows */
+enum {
+    LVDGS_EDIT_SEQ = 0,
+    LVDGS_EDIT_N_OUT = 1,
+    LVDGS_EDIT_N_KEEP = 2,
+    LVDGS_EDIT_N_CLONE = 3,
+    LVDGS_EDIT_N_SPLIT_SEL = 4,
+    LVDGS_EDIT_N_PRUNED_FINAL = 5,
+    LVDGS_EDIT_HOST_SRC = 16
+};
+typedef struct lvdgs_map_edit_plan_args {
+    int32_t mode;                 /* LVDGS_EDIT_PRUNE / _DENSIFY                    */
+    int32_t num_gaussians;        /* N source rows                                  */
+    uint32_t seq;
+    int32_t scale_dims;           /* densify: 1 or 3 raw scales per row             */
+    const uint8_t *remove;        /* prune (a): N bytes, or NULL: rule (b)          */
+    int32_t num_vis_rows;         /* prune (b): rows of vis_rows in use             */
+    int32_t prune_num;
+    int32_t min_kf_id;
+    int32_t capacity;             /* rows src / kind / noise_row hold               */
+    const uint8_t *vis_rows[LVDGS_EDIT_MAX_VIS_ROWS];   /* prune (b): N bytes each */
+    const int32_t *kf_id;         /* prune (b): N                                   */
+    int32_t *n_obs;               /* prune (b): out N                               */
+    const float *grad_accum, *denom;      /* densify: N each                        */
+    const float *scaling;         /* densify: N*scale_dims, raw                     */
+    const float *opacity;         /* densify: N, raw                                */
+    const float *max_radii2D;     /* never read (see above); may be NULL            */
+    float grad_threshold;
+    float dense_extent;           /* percent_dense * extent                         */
+    float min_opacity;
+    float max_screen_size;        /* 0: off                                         */
+    float world_extent;           /* 0.1 * extent                                   */
+    int32_t vis_stride;           /* prune (b): bytes per element of a vis row: 1, 4 or 8 (0: 1) */
+    int32_t *src;                 /* out capacity                                   */
+    uint8_t *kind;                /* out capacity                                   */
+    int32_t *noise_row;           /* out capacity                                   */
+    int32_t *host_state;          /* pinned host (the host address)                 */
+    size_t host_bytes;
+    void *scratch; size_t scratch_bytes;
+} lvdgs_map_edit_plan_args;
+typedef struct lvdgs_map_edit_column {
+    const void *in;               /* N rows                                         */
+    void *out;                    /* at least n_out rows                            */
+    int32_t row_bytes;            /* >= 1                                           */
+    int32_t new_rows;             /* LVDGS_EDIT_COPY / _ZERO / _XYZ / _SCALE        */
+} lvdgs_map_edit_column;
+typedef struct lvdgs_map_edit_apply_args {
+    int32_t num_gaussians;        /* N source rows                                  */
+    int32_t n_out;                /* the plan's output rows                         */
+    int32_t n_split_sel;          /* the plan's split sources: noise has twice as many rows */
+    int32_t scale_dims;
+    int32_t num_columns;
+    int32_t reserved;
+    const int32_t *src;           /* the plan's outputs                             */
+    const uint8_t *kind;
+    const int32_t *noise_row;     /* may be NULL without an _XYZ column             */
+    const float *noise;           /* 2 n_split_sel * 3, or NULL                     */
+    const float *scaling;         /* N*scale_dims raw: the _XYZ column's scales, or NULL */
+    const float *rotation;        /* N*4 as stored: the _XYZ column's quaternions, or NULL */
+    lvdgs_map_edit_column columns[LVDGS_EDIT_MAX_COLUMNS];
+} lvdgs_map_edit_apply_args;
+size_t lvdgs_map_edit_scratch_bytes(int32_t num_gaussians);
+int lvdgs_map_edit_plan(const lvdgs_map_edit_plan_args *a, void *stream);
+int lvdgs_map_edit_apply(const lvdgs_map_edit_apply_args *a, void *stream);
+
 /* ---- diagnostics ---- */
 const char *lvdgs_last_error(void);
 const char *lvdgs_version(void);

@@ -250,6 +250,42 @@ SEED_HOST_BYTES = 64
 SEED_SEQ, SEED_N_VALID, SEED_N_KEEP, SEED_MEDIAN, SEED_THRESHOLD = 0, 1, 2, 3, 4
 
 
+EDIT_MAX_COLUMNS, EDIT_MAX_VIS_ROWS = 48, 16
+EDIT_PRUNE, EDIT_DENSIFY = 0, 1
+EDIT_KEEP, EDIT_CLONE, EDIT_SPLIT0, EDIT_SPLIT1 = 0, 1, 2, 3
+EDIT_COPY, EDIT_ZERO, EDIT_XYZ, EDIT_SCALE = 0, 1, 2, 3
+EDIT_SEQ, EDIT_N_OUT, EDIT_N_KEEP, EDIT_N_CLONE, EDIT_N_SPLIT_SEL, EDIT_N_PRUNED_FINAL, EDIT_HOST_SRC = 0, 1, 2, 3, 4, 5, 16
+
+
+class MapEditPlanArgs(C.Structure):
+    """struct lvdgs_map_edit_plan_args (include/lvdgs.h)."""
+    _fields_ = [
+        ("mode", C.c_int32), ("num_gaussians", C.c_int32), ("seq", C.c_uint32), ("scale_dims", C.c_int32),
+        ("remove", _fp), ("num_vis_rows", C.c_int32), ("prune_num", C.c_int32), ("min_kf_id", C.c_int32), ("capacity", C.c_int32),
+        ("vis_rows", _fp * EDIT_MAX_VIS_ROWS), ("kf_id", _fp), ("n_obs", _fp),
+        ("grad_accum", _fp), ("denom", _fp), ("scaling", _fp), ("opacity", _fp), ("max_radii2D", _fp),
+        ("grad_threshold", C.c_float), ("dense_extent", C.c_float), ("min_opacity", C.c_float), ("max_screen_size", C.c_float),
+        ("world_extent", C.c_float), ("vis_stride", C.c_int32),
+        ("src", _fp), ("kind", _fp), ("noise_row", _fp), ("host_state", _fp), ("host_bytes", C.c_size_t),
+        ("scratch", _fp), ("scratch_bytes", C.c_size_t),
+    ]
+
+
+class MapEditColumn(C.Structure):
+    """struct lvdgs_map_edit_column (include/lvdgs.h)."""
+    _fields_ = [("in_", _fp), ("out", _fp), ("row_bytes", C.c_int32), ("new_rows", C.c_int32)]
+
+
+class MapEditApplyArgs(C.Structure):
+    """struct lvdgs_map_edit_apply_args (include/lvdgs.h)."""
+    _fields_ = [
+        ("num_gaussians", C.c_int32), ("n_out", C.c_int32), ("n_split_sel", C.c_int32), ("scale_dims", C.c_int32),
+        ("num_columns", C.c_int32), ("reserved", C.c_int32),
+        ("src", _fp), ("kind", _fp), ("noise_row", _fp), ("noise", _fp), ("scaling", _fp), ("rotation", _fp),
+        ("columns", MapEditColumn * EDIT_MAX_COLUMNS),
+    ]
+
+
 class StateLayout(C.Structure):
     _fields_ = [(n, C.c_size_t) for n in (
         "geom_rec", "geom_tiles_touched", "geom_slot_base", "bin_point_list", "bin_tile_keys",
@@ -276,6 +312,7 @@ EXPORTS = (
     "lvdgs_ms_deform_attn_forward", "lvdgs_ms_deform_attn_backward",
     "lvdgs_dynamic_mask_state_bytes", "lvdgs_dynamic_mask_scratch_bytes", "lvdgs_dynamic_mask",
     "lvdgs_seed_scratch_bytes", "lvdgs_seed_points",
+    "lvdgs_map_edit_scratch_bytes", "lvdgs_map_edit_plan", "lvdgs_map_edit_apply",
     "lvdgs_last_error", "lvdgs_version", "lvdgs_profile_enable",
     "lvdgs_profile_reset", "lvdgs_profile_read",
 )
@@ -391,6 +428,10 @@ def lib():
         L.lvdgs_seed_scratch_bytes.restype = C.c_size_t
         L.lvdgs_seed_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
         L.lvdgs_seed_points.argtypes = [C.POINTER(SeedArgs), C.c_void_p]
+        L.lvdgs_map_edit_scratch_bytes.restype = C.c_size_t
+        L.lvdgs_map_edit_scratch_bytes.argtypes = [C.c_int32]
+        L.lvdgs_map_edit_plan.argtypes = [C.POINTER(MapEditPlanArgs), C.c_void_p]
+        L.lvdgs_map_edit_apply.argtypes = [C.POINTER(MapEditApplyArgs), C.c_void_p]
         L.lvdgs_profile_enable.argtypes = [C.c_int]
         L.lvdgs_profile_read.argtypes = [C.POINTER(KernelTime), C.c_int]
         _lib = L

@@ -1066,6 +1066,31 @@ def _reduce(c, params, layout, vs, loss, local):
     return radii_max, norm_sum, vis_count, split_xy, grad_share
 
 
+def _pruning_pass_fused(c, rows, prune_mode, prune_coviz):
+    """The pruning pass with a model whose map edits are fused (``GaussianModel.map_edit == "fused"``) and visibility rows on its GPU:
+    the sum over the rows and the rule on the device (``map_edit.plan_prune``), ``n_obs`` back through the plan's pinned block, and the
+    window's visibility rows edited as columns of the same launch as the map.  -> False: not taken, the host statements run."""
+    backend, G = c.backend, c.G
+    if not (hasattr(G, "_edits_fused") and G._edits_fused() and backend.monocular and prune_mode in ("odometry", "slam")):
+        return False
+    from . import map_edit
+    dev, n = G.get_xyz.device, G.get_xyz.shape[0]
+    keys = list(backend.occ_aware_visibility.keys())
+    if not rows or len(rows) > 16 or any(r.device != dev or r.dtype is not rows[0].dtype or r.dtype not in (torch.bool, torch.uint8, torch.int32, torch.int64)
+                                        or r.shape != (n,) or not r.is_contiguous() for r in rows):
+        return False
+    if prune_mode == "odometry":
+        prune_num, min_kf = 2, map_edit.INT32_MIN
+    else:
+        prune_num, min_kf = int(prune_coviz), int(sorted(c.window, reverse=True)[2]) if backend.initialized else 0
+    plan = map_edit.plan_prune(n, dev, vis_rows=rows, kf_id=G.kf_ids_on_device(), prune_num=prune_num, min_kf_id=min_kf)
+    window = [k for k in keys if k in set(c.window)]      # (the host statements re-index the window's rows, and sum every row)
+    for k, r in zip(window, G.apply_edit_plan(plan, extra=[backend.occ_aware_visibility[k] for k in window])):
+        backend.occ_aware_visibility[k] = r
+    backend.initialized = True
+    return True
+
+
 def _pruning_pass(c):
     """Only prune on the last iteration and when we have full window (:318-348).  The reference returns from here
     without an optimizer step and without clearing the gradients, so (unless pruning replaces the parameters)
@@ -1081,6 +1106,8 @@ def _pruning_pass(c):
     # (`n_obs += visibility.cpu()` per window keyframe: the same integer sums, made on the device and fetched once --
     # eight blocking copies fewer in a pass the free-running back end makes every ten iterations)
     rows = list(backend.occ_aware_visibility.values())
+    if _pruning_pass_fused(c, rows, prune_mode, prune_coviz):
+        return
     summed = torch.stack(rows).sum(0) if all(r.is_cuda for r in rows) else sum(r.cpu() for r in rows)
     G.n_obs.copy_(summed.cpu().to(G.n_obs.dtype))
     to_prune = None

@@ -150,6 +150,11 @@ class GaussianModel:
         # and one wait per keyframe; the subsample is a function of (seed, pixel) with seed = call_seed(seed_base, seed_calls), so
         # replicas that make the same calls seed the same pixels with no generator to keep in step -- another subset than the draw's).
         self.seeding, self.seed_base, self.seed_calls = "host", 0, 0
+        # map edits: "host" (the default: the PyTorch statements below) or "fused" (map_edit: prune_points and densify_and_prune as one
+        # plan with one wait and one launch that moves every per-Gaussian array; split children's xyz and scale are the library's
+        # float32 expressions, not the host statements' bits -- every other byte is the same).
+        self.map_edit = "host"
+        self._kf_mirror = None      # (the CPU unique_kfIDs tensor, its int32 copy on the device): the pruning rule's kf_id input
         # Samples of densify_and_split.  A CPU generator with a fixed seed: the draw is made on the host and copied,
         # so every replica of the map (one per GPU in the sharded mapping loop) and a CPU run of the same loop split
         # their Gaussians identically.  Set to None for torch's global generator on the model's device.
@@ -296,8 +301,72 @@ class GaussianModel:
         self._set_params(new)
 
     # ------------------------------------------------------------------ prune / append
+    def _edits_fused(self):
+        """Do map edits take the library calls?  ``map_edit == "fused"`` and the model on a GPU (elsewhere: the host statements)."""
+        if self.map_edit not in ("host", "fused"):
+            raise ValueError(f"GaussianModel.map_edit: 'host' or 'fused', not {self.map_edit!r}")
+        return self.map_edit == "fused" and self._xyz.is_cuda
+
+    def kf_ids_on_device(self):
+        """``unique_kfIDs`` as an int32 tensor on the model's GPU: uploaded when the CPU tensor has been replaced or written since the
+        last call, carried through fused edits as one more column."""
+        m = self._kf_mirror
+        if m is None or m[0] is not self.unique_kfIDs or m[1] != self.unique_kfIDs._version or m[2].shape[0] != self.unique_kfIDs.shape[0]:
+            m = self._kf_mirror = (self.unique_kfIDs, self.unique_kfIDs._version, self.unique_kfIDs.to(self._xyz.device))
+        return m[2]
+
+    def apply_edit_plan(self, plan, densify=False, noise=None, extra=()):
+        """Move every per-Gaussian array of the model by ``plan`` (map_edit.Plan) in one ``map_edit.apply``: the parameters and their Adam
+        moments (the optimiser's groups rebuilt once, as ``_rebuild_groups`` does), the three statistics (zeroed at the new size after a
+        densification, as ``densification_postfix`` leaves them), the kf-id mirror, and ``extra`` -- tensors of plan.n_in rows, whose
+        edited copies are returned in order.  The CPU ``unique_kfIDs`` / ``n_obs`` follow the plan's host copy of ``src``: no further wait."""
+        from . import map_edit
+        n_out, dev = plan.n_out, self._xyz.device
+        like = lambda t: torch.empty((n_out,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)
+        columns, new_params, new_moments = [], {}, {}
+        special = {"xyz": map_edit.XYZ, "scaling": map_edit.SCALE} if densify else {}
+        named = [(g["name"], g["params"][0]) for g in self.optimizer.param_groups] if self.optimizer is not None else list(self._params_by_name().items())
+        for name, old in named:
+            new_params[name] = like(old.data)
+            columns.append((old.data, new_params[name], special.get(name, map_edit.COPY)))
+            state = self.optimizer.state.get(old) if self.optimizer is not None else None
+            if state is not None:
+                for key in ("exp_avg", "exp_avg_sq"):
+                    new_moments[id(state[key])] = like(state[key])
+                    columns.append((state[key], new_moments[id(state[key])], map_edit.ZERO))
+        stats = None
+        if not densify:
+            stats = [like(self.xyz_gradient_accum), like(self.denom), like(self.max_radii2D)]
+            columns += [(a, b, map_edit.COPY) for a, b in zip((self.xyz_gradient_accum, self.denom, self.max_radii2D), stats)]
+        mirror = self._kf_mirror
+        kf_new = None
+        if mirror is not None and mirror[0] is self.unique_kfIDs and mirror[1] == self.unique_kfIDs._version and mirror[2].shape[0] == plan.n_in:
+            kf_new = like(mirror[2])
+            columns.append((mirror[2], kf_new, map_edit.COPY))
+        extra_new = [like(t) for t in extra]
+        columns += [(a, b, map_edit.COPY) for a, b in zip(extra, extra_new)]
+        map_edit.apply(plan, columns, noise=noise, scaling=self._scaling.data if densify else None,
+                       rotation=self._rotation.data if densify else None)
+        self._rebuild_groups(lambda name, t: new_params[name], lambda name, t: new_moments[id(t)])
+        if densify:
+            self.xyz_gradient_accum = torch.zeros(n_out, 1, device=self.device)
+            self.denom = torch.zeros(n_out, 1, device=self.device)
+            self.max_radii2D = torch.zeros(n_out, device=self.device)
+        else:
+            self.xyz_gradient_accum, self.denom, self.max_radii2D = stats
+        self.unique_kfIDs = self.unique_kfIDs.index_select(0, plan.src_cpu)
+        self.n_obs = plan.n_obs_cpu.to(self.n_obs.dtype) if plan.n_obs_cpu is not None else self.n_obs.index_select(0, plan.src_cpu)
+        self._kf_mirror = None if kf_new is None else (self.unique_kfIDs, self.unique_kfIDs._version, kf_new)
+        return extra_new
+
     def prune_points(self, mask):
         """Remove the Gaussians where ``mask`` is True (slam_backend.py:89, :339)."""
+        if self._edits_fused():
+            from . import map_edit
+            dev = self._xyz.device
+            mask = mask.to(device=dev, dtype=torch.bool).contiguous()
+            self.apply_edit_plan(map_edit.plan_prune(self._xyz.shape[0], dev, mask))
+            return
         keep = ~mask.to(device=self._xyz.device, dtype=torch.bool)
         # The surviving rows as INDICES, found once: every `t[keep]` with a boolean mask is a count on the device the host waits for before
         # it can size the result -- eighteen of them here (six parameters, twelve Adam moments) plus the three statistics, each a
@@ -474,6 +543,8 @@ class GaussianModel:
 
     def densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size):
         """slam_backend.py:132-137, :364-369."""
+        if self._edits_fused():
+            return self._densify_and_prune_fused(max_grad, min_opacity, extent, max_screen_size)
         grads = self.xyz_gradient_accum / self.denom
         grads = torch.where(grads.isnan(), torch.zeros_like(grads), grads)   # (`grads[grads.isnan()] = 0.0` without the host waiting for the count of NaNs)
         self.densify_and_clone(grads, max_grad, extent)
@@ -484,6 +555,19 @@ class GaussianModel:
             big_ws = self.get_scaling.max(dim=1).values > 0.1 * extent
             prune = prune | big_vs | big_ws
         self.prune_points(prune)
+
+    def _densify_and_prune_fused(self, max_grad, min_opacity, extent, max_screen_size):
+        """The three stages as one ``map_edit`` plan, one wait, the draw of ``densify_and_split`` (same generator, same call, same shape)
+        between plan and apply, and one launch that writes every array at its final size."""
+        from . import map_edit
+        plan = map_edit.plan_densify(self.xyz_gradient_accum, self.denom, self._scaling.data, self._opacity.data, max_grad,
+                                     self.percent_dense * extent, min_opacity, max_screen_size, 0.1 * extent)
+        dev, shape = self._xyz.device, (2 * plan.n_split_sel, 3)
+        if self.generator is not None and self.generator.device.type == "cpu":
+            noise = torch.randn(shape, generator=self.generator).to(dev)
+        else:
+            noise = torch.randn(shape, device=dev, generator=self.generator)
+        self.apply_edit_plan(plan, densify=True, noise=noise)
 
     def reset_opacity(self):
         new = inverse_sigmoid(torch.ones_like(self.get_opacity) * 0.01)

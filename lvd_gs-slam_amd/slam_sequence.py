@@ -118,7 +118,7 @@ class SlamSequence:
                  refine_loss_fn=None, keyframe_depth=None, idle_map_iters=0, camera_cls=None, cameras_extent=6.0, on_event=None,
                  group=None, aux_group=None, bands_ok=None, depth_align_fn=None, scale_remedy=None, depth_align_params=None,
                  pose_init=None, matcher=None, pose_init_params=None, frame_stats="torch", edge_mask="torch", dynamic_masks="dataset",
-                 masker=None, seeding="host"):
+                 masker=None, seeding="host", map_edit="host"):
         from .backend_map import map_window
         if camera_cls is None:
             from .camera_utils import Camera as camera_cls
@@ -176,6 +176,11 @@ class SlamSequence:
         if seeding not in ("host", "fused"):
             raise ValueError(f"seeding: 'host' or 'fused', not {seeding!r}")
         self.seeding = seeding
+        # map_edit: "host" (the default: GaussianModel's PyTorch statements) or "fused" (map_edit: prune_points, densify_and_prune and the
+        # pruning pass as one plan, one wait and one launch each).  Set on the map.
+        if map_edit not in ("host", "fused"):
+            raise ValueError(f"map_edit: 'host' or 'fused', not {map_edit!r}")
+        self.map_edit = map_edit
         # dynamic_masks: "dataset" (the default: dataset.static_mask's finished masks) or "detections" (`masker`, a
         # dynamic_mask.DynamicMasker: the masks, add_new_keyframe's dilation and valid_rgb come from its calls)
         if dynamic_masks not in ("dataset", "detections"):
@@ -203,6 +208,7 @@ class SlamSequence:
         self.median_depth, self.theta = None, 0
         self.frontend_gaussians = gaussians      # the front end's copy of the map as of the last push (``_sync_backend``)
         gaussians.seeding = self.seeding
+        gaussians.map_edit = self.map_edit
         self.backend = make_backend(config, gaussians, pipeline_params, background, cameras_extent)
         self.projection_matrix = getProjectionMatrix2(znear=0.01, zfar=100.0, fx=dataset.fx, fy=dataset.fy, cx=dataset.cx, cy=dataset.cy,
                                                       W=dataset.width, H=dataset.height).transpose(0, 1).to(device=dataset.device)

@@ -179,6 +179,9 @@ def main():
     ap.add_argument("--seeding", choices=["host", "fused"], default="host",
                     help="a keyframe's new Gaussians: GaussianModel's PyTorch statements and host draw (default), or one seeding.seed_points "
                          "call and one wait (lvdgs_seed_points; another subsample of the same size)")
+    ap.add_argument("--map-edit", choices=["host", "fused"], default="host",
+                    help="prune_points, densify_and_prune and the pruning pass: GaussianModel's PyTorch statements (default), or one map_edit plan, "
+                         "one wait and one launch each (lvdgs_map_edit_plan / lvdgs_map_edit_apply)")
     ap.add_argument("--verbose", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -191,8 +194,8 @@ def main():
                           **({"scale_remedy": "matches"} if a.scale_remedy == "matches" else {}),
                           **({"frame_stats": "fused"} if a.frame_stats == "fused" else {}), **({"edge_mask": "fused"} if a.edge_mask == "fused" else {}),
                           **({"dynamic_masks": "detections"} if a.dynamic_masks == "detections" else {}),
-                          **({"seeding": "fused"} if a.seeding == "fused" else {}))
-    out.update(frame_stats=a.frame_stats, edge_mask=a.edge_mask, dynamic_masks=a.dynamic_masks, seeding=a.seeding)
+                          **({"seeding": "fused"} if a.seeding == "fused" else {}), **({"map_edit": "fused"} if a.map_edit == "fused" else {}))
+    out.update(frame_stats=a.frame_stats, edge_mask=a.edge_mask, dynamic_masks=a.dynamic_masks, seeding=a.seeding, map_edit=a.map_edit)
     for rec in out.get("pose_init", []):
         print("  frame {frame:3d} kf {keyframe:3d} inliers {inl:>5} init error {e:.4f} ({r:.3f} deg; previous pose {p:.4f}) tracking iterations {it}".format(
             frame=rec["frame"], keyframe=rec["keyframe"], inl=rec.get("inliers", "-"), e=rec["init_translation_error"], r=rec["init_rotation_error_deg"],

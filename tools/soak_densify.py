@@ -7,7 +7,7 @@ pruning pass of the free-running back end every 10 (utils/slam_backend.py:487-49
 ordinary iterations and the ones that change the map's size (re-plan of the batched window's per-view buffers, the cached memory verdict,
 Adam state surgery) are reported separately; device memory and the map's size block by block.
 
-    python tools/soak_densify.py [iters=3300] [frames=60]"""
+    python tools/soak_densify.py [iters=3300] [frames=60] [--map-edit fused]"""
 import os
 import sys
 import time
@@ -23,10 +23,14 @@ import torch  # noqa: E402
 import lvdgs  # noqa: E402,F401
 import sequence as tool  # noqa: E402
 
-iters = int(sys.argv[1]) if len(sys.argv) > 1 else 3300
-frames = int(sys.argv[2]) if len(sys.argv) > 2 else 60
+argv = [a for a in sys.argv[1:] if not a.startswith("--")]
+map_edit = "fused" if "--map-edit" in sys.argv and sys.argv[sys.argv.index("--map-edit") + 1:][:1] == ["fused"] else "host"
+argv = [a for a in argv if a not in ("fused", "host")]
+iters = int(argv[0]) if len(argv) > 0 else 3300
+frames = int(argv[1]) if len(argv) > 1 else 60
 dev = torch.device("cuda", 0)
-rec, seq = tool.run_sequence(dev, frames=frames, refine=0)
+rec, seq = tool.run_sequence(dev, frames=frames, refine=0, **({"map_edit": "fused"} if map_edit == "fused" else {}))
+print(f"map edits: {map_edit}")
 be, window = seq.backend, list(seq.current_window)
 print(f"sequence: {rec['frames']} frames, {rec['keyframes']} keyframes, window {window}, map {seq._n()} Gaussians, iteration count {be.iteration_count}, "
       f"ATE {rec['ate_rmse']:.5f}, PSNR (static) {rec['psnr_static_before_refinement']:.2f}")
