@@ -20,7 +20,7 @@ namespace {
 constexpr int LOSS_THREADS = 256;
 constexpr int LOSS_PIX_PER_THREAD = 4;
 
-// 4 consecutive pixels per lane: 16-byte loads / stores on every plane when P % 4 == 0 (VEC), scalar otherwise.
+// 4 consecutive pixels per lane: 16-byte loads / stores on every plane when P % 4 == 0 and the planes are aligned (VEC: loss_vec_path), scalar otherwise.
 // MODE 0: the loss value; 1: every gradient; 2: both in ONE pass over the images (the tracking session's case: the
 // objective IS the loss, d objective / d loss is known -- 1, or a device scalar -- before the pixels are read).
 template <int MODE, bool VEC>
@@ -217,6 +217,22 @@ __global__ void __launch_bounds__(256) masked_depth_finish_kernel(MaskedDepthPar
 
 using namespace lvdgs;
 
+// The 16-byte path of photometric_kernel: P % 4 == 0 puts every plane a multiple of 16 bytes behind its first, but the header promises
+// no alignment for the planes themselves (a view one float into a buffer is a valid argument), so they are looked at too -- every plane
+// the kernel may touch, NULL ones being aligned; the mask is read four bytes at a time.  Both paths give a lane the same four pixels:
+// the same sums, bit for bit.
+static bool loss_vec_path(const LossParams &p) {
+    const uintptr_t planes = (uintptr_t)p.image | (uintptr_t)p.gt_image | (uintptr_t)p.depth | (uintptr_t)p.gt_depth | (uintptr_t)p.opacity |
+                             (uintptr_t)p.d_image | (uintptr_t)p.d_depth | (uintptr_t)p.d_opacity;
+    return p.P % 4 == 0 && planes % 16 == 0 && (uintptr_t)p.grad_mask % 4 == 0;
+}
+
+template <int MODE>
+static void launch_photometric(const LossParams &p, int nblk, hipStream_t s) {
+    if (loss_vec_path(p)) hipLaunchKernelGGL((photometric_kernel<MODE, true>), dim3(nblk), dim3(LOSS_THREADS), 0, s, p);
+    else hipLaunchKernelGGL((photometric_kernel<MODE, false>), dim3(nblk), dim3(LOSS_THREADS), 0, s, p);
+}
+
 extern "C" {
 
 size_t lvdgs_loss_scratch_bytes(int32_t width, int32_t height) {
@@ -250,7 +266,7 @@ int lvdgs_photometric_loss_forward(const lvdgs_loss_args *a, void *stream) {
     if (int e = loss_common(a, p, nblk)) return e;
     if (!a->loss) { set_error("loss: output is NULL"); return LVDGS_E_INVALID; }
     p.loss = a->loss;
-    { ProfScope ps("loss_fwd", s); if (p.P % 4 == 0) hipLaunchKernelGGL((photometric_kernel<0, true>), dim3(nblk), dim3(LOSS_THREADS), 0, s, p); else hipLaunchKernelGGL((photometric_kernel<0, false>), dim3(nblk), dim3(LOSS_THREADS), 0, s, p); LVDGS_LAUNCH_CHECK("loss_fwd", 0, s); }
+    { ProfScope ps("loss_fwd", s); launch_photometric<0>(p, nblk, s); LVDGS_LAUNCH_CHECK("loss_fwd", 0, s); }
     { ProfScope ps("loss_fwd_finish", s); hipLaunchKernelGGL(photometric_finish_kernel<0>, dim3(1), dim3(256), 0, s, p, nblk); LVDGS_LAUNCH_CHECK("loss_fwd_finish", 0, s); }
     return LVDGS_OK;
 }
@@ -262,7 +278,7 @@ int lvdgs_photometric_loss_backward(const lvdgs_loss_args *a, void *stream) {
     if (!a->grad_loss || !a->d_image) { set_error("loss backward: grad_loss / d_image is NULL"); return LVDGS_E_INVALID; }
     p.grad_out = a->grad_loss; p.d_image = a->d_image; p.d_depth = a->d_depth; p.d_opacity = a->d_opacity;
     p.d_a = a->d_exposure_a; p.d_b = a->d_exposure_b;
-    { ProfScope ps("loss_bwd", s); if (p.P % 4 == 0) hipLaunchKernelGGL((photometric_kernel<1, true>), dim3(nblk), dim3(LOSS_THREADS), 0, s, p); else hipLaunchKernelGGL((photometric_kernel<1, false>), dim3(nblk), dim3(LOSS_THREADS), 0, s, p); LVDGS_LAUNCH_CHECK("loss_bwd", 0, s); }
+    { ProfScope ps("loss_bwd", s); launch_photometric<1>(p, nblk, s); LVDGS_LAUNCH_CHECK("loss_bwd", 0, s); }
     { ProfScope ps("loss_bwd_finish", s); hipLaunchKernelGGL(photometric_finish_kernel<1>, dim3(1), dim3(256), 0, s, p, nblk); LVDGS_LAUNCH_CHECK("loss_bwd_finish", 0, s); }
     return LVDGS_OK;
 }
@@ -278,8 +294,7 @@ static int value_and_grad_params(const lvdgs_loss_args *a, LossParams &p, int &n
 
 static void launch_value_and_grad_pass(const LossParams &p, int nblk, hipStream_t s) {
     ProfScope ps("loss_both", s);
-    if (p.P % 4 == 0) hipLaunchKernelGGL((photometric_kernel<2, true>), dim3(nblk), dim3(LOSS_THREADS), 0, s, p);
-    else hipLaunchKernelGGL((photometric_kernel<2, false>), dim3(nblk), dim3(LOSS_THREADS), 0, s, p);
+    launch_photometric<2>(p, nblk, s);
 }
 
 int lvdgs_photometric_loss_value_and_grad(const lvdgs_loss_args *a, void *stream) {
