@@ -1161,6 +1161,49 @@ size_t lvdgs_map_edit_scratch_bytes(int32_t num_gaussians);
 int lvdgs_map_edit_plan(const lvdgs_map_edit_plan_args *a, void *stream);
 int lvdgs_map_edit_apply(const lvdgs_map_edit_apply_args *a, void *stream);
 
+/* ---- a decoded frame's way onto the device (reference utils/dataset.py MonocularDataset.__getitem__ :321-344: per frame, on the
+ * host, cv2.remap(INTER_LINEAR) over the whole frame when the calibration is distorted, image / 255.0 as a float64 array, a clamp, a
+ * permute, and an upload of float32; the map comes from cv2.initUndistortRectifyMap(K, dist, I, K, (W, H), CV_32FC1) in __init__) ----
+ * The arithmetic below is the contract of both the device entry points and the package's host mode (lvdgs.dataset, ingest="host"):
+ * the same bits.
+ * Conversion.  image[c][v][u] = (float)((double)byte / 255.0): what a float64 division followed by a cast to float32 gives.  The
+ *   reference's clamp to [0, 1] is a no-op on bytes.
+ * Undistortion map, all float64, evaluated as written (no contraction), for destination pixel (u, v), dist = (k1, k2, p1, p2, k3):
+ *   x = (u - cx) / fx;  y = (v - cy) / fy;  r2 = x*x + y*y;
+ *   kr = 1 + ((k3*r2 + k2)*r2 + k1)*r2;
+ *   xd = x*kr + 2*p1*x*y + p2*(r2 + 2*x*x);
+ *   yd = y*kr + p1*(r2 + 2*y*y) + 2*p2*x*y;
+ *   mapx = (float)(fx*xd + cx);  mapy = (float)(fy*yd + cy);
+ *   sx = rint(mapx * 32), ties to even, as int32; sy likewise.  A coordinate that is not finite or whose magnitude is >= 2^20 is
+ *   stored as INT32_MIN and means "outside".
+ * Remap.  ix = sx >> 5 (floor, negatives too), ax = sx & 31; iy, ay likewise.  The neighbours (ix, iy), (ix+1, iy), (ix, iy+1),
+ *   (ix+1, iy+1) carry the weights (32-ax)(32-ay), ax(32-ay), (32-ax)ay, ax ay; a neighbour outside the image counts as 0 on its own
+ *   (a constant border), a pixel with an "outside" coordinate is 0.  out = (sum + 512) >> 10 per channel, in integers.
+ *   Parity with the real cv2.remap is UNPINNED: OpenCV is not installed where this was written.  As recalled, it rounds these products
+ *   into 15-bit weight tables and builds the map incrementally along a row; a grey level of difference in rare pixels is possible and
+ *   has not been measured.
+ * lvdgs_undistort_map: sx, sy: height*width int32 each, device.  dist: five doubles on the HOST, read during the call (nothing the
+ *   caller must keep).  One launch, no wait.
+ * lvdgs_ingest_frame: one launch, no host wait, no copy.  src: device bytes, row v at src + v * src_row_bytes, 3 bytes per pixel
+ *   (src_row_bytes >= 3 * width; no alignment is assumed).  map_sx / map_sy: both NULL = no remap.  image_u8 (optional): the bytes
+ *   after the remap, height*width*3 without a row gap -- what a detector or the matcher's formatting would take.  A map entry
+ *   addresses no byte outside src whatever it holds.  Two calls give the same bytes.
+ * LVDGS_E_INVALID, before anything is enqueued: args NULL, width or height not > 0 (an empty frame is refused, as by
+ *   lvdgs_format_image), src / image / dist / sx / sy NULL, exactly one of map_sx / map_sy NULL, src_row_bytes < 3 * width, fx or fy
+ *   zero or a non-finite intrinsic.  LVDGS_E_RANGE: a raster beyond 2^31 workgroups. */
+typedef struct lvdgs_ingest_args {
+    int32_t width, height;
+    const uint8_t *src;           /* height rows of src_row_bytes, 3 bytes per pixel */
+    int64_t src_row_bytes;
+    const int32_t *map_sx;        /* height*width, or NULL                          */
+    const int32_t *map_sy;        /* height*width, or NULL                          */
+    float *image;                 /* out 3*height*width                             */
+    uint8_t *image_u8;            /* out height*width*3, or NULL                    */
+} lvdgs_ingest_args;
+int lvdgs_undistort_map(int32_t width, int32_t height, double fx, double fy, double cx, double cy, const double dist[5],
+                        int32_t *sx, int32_t *sy, void *stream);
+int lvdgs_ingest_frame(const lvdgs_ingest_args *a, void *stream);
+
 /* ---- diagnostics ---- */
 const char *lvdgs_last_error(void);
 const char *lvdgs_version(void);

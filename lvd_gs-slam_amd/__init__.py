@@ -14,6 +14,8 @@ Import as ``lvdgs`` (see ``/lvdgs.py``).  Submodules:
   slam_loops         map initialisation and per-frame pose tracking loops
   loss_utils         fused L1 + SSIM and masked depth losses; fused_loss: photometric losses
   gaussian_model     the Gaussian map (parameters, Adam groups, seeding, densify / prune)
+  config_utils       load_config: the YAML settings with their inherit_from chain
+  dataset            load_dataset: KITTI / waymo / dl3dv / replica / tum directories; a frame's undistortion and conversion (host or one HIP call)
   ms_deform_attn     multi-scale deformable attention (GroundingDINO's ``groundingdino._C``); install() puts it in place
 
 Nothing here falls back to a CPU implementation: the HIP library

@@ -286,6 +286,17 @@ class MapEditApplyArgs(C.Structure):
     ]
 
 
+class IngestArgs(C.Structure):
+    """struct lvdgs_ingest_args (include/lvdgs.h)."""
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32), ("src", _fp), ("src_row_bytes", C.c_int64),
+        ("map_sx", _fp), ("map_sy", _fp), ("image", _fp), ("image_u8", _fp),
+    ]
+
+
+MAP_OUTSIDE = -2 ** 31     # INT32_MIN in an undistortion map: the destination pixel's source lies outside
+
+
 class StateLayout(C.Structure):
     _fields_ = [(n, C.c_size_t) for n in (
         "geom_rec", "geom_tiles_touched", "geom_slot_base", "bin_point_list", "bin_tile_keys",
@@ -313,6 +324,7 @@ EXPORTS = (
     "lvdgs_dynamic_mask_state_bytes", "lvdgs_dynamic_mask_scratch_bytes", "lvdgs_dynamic_mask",
     "lvdgs_seed_scratch_bytes", "lvdgs_seed_points",
     "lvdgs_map_edit_scratch_bytes", "lvdgs_map_edit_plan", "lvdgs_map_edit_apply",
+    "lvdgs_undistort_map", "lvdgs_ingest_frame",
     "lvdgs_last_error", "lvdgs_version", "lvdgs_profile_enable",
     "lvdgs_profile_reset", "lvdgs_profile_read",
 )
@@ -432,6 +444,9 @@ def lib():
         L.lvdgs_map_edit_scratch_bytes.argtypes = [C.c_int32]
         L.lvdgs_map_edit_plan.argtypes = [C.POINTER(MapEditPlanArgs), C.c_void_p]
         L.lvdgs_map_edit_apply.argtypes = [C.POINTER(MapEditApplyArgs), C.c_void_p]
+        L.lvdgs_undistort_map.argtypes = [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double),
+                                          _fp, _fp, C.c_void_p]
+        L.lvdgs_ingest_frame.argtypes = [C.POINTER(IngestArgs), C.c_void_p]
         L.lvdgs_profile_enable.argtypes = [C.c_int]
         L.lvdgs_profile_read.argtypes = [C.POINTER(KernelTime), C.c_int]
         _lib = L

@@ -367,7 +367,9 @@ class SlamSequence:
         """FrontEnd.initialize (:1702-1738) + the back end's "init" message (utils/slam_backend.py:514-528)."""
         self.initialized = not self.monocular
         self.kf_indices, self.occ_aware_visibility, self.current_window = [], {}, []
-        viewpoint.update_RT(viewpoint.R_gt, viewpoint.T_gt)
+        # (a dataset read from disk hands its poses over in float64, as the reference's does; upstream's getWorld2View2 narrows them where
+        # it fills its float32 matrix, here the estimate's own dtype does: a no-op for float32 poses)
+        viewpoint.update_RT(viewpoint.R_gt.to(viewpoint.R.dtype), viewpoint.T_gt.to(viewpoint.T.dtype))
         depth_map = self.add_new_keyframe(cur_frame_idx, init=True)
         be = self.backend
         # BackEnd.reset (:80-92)

@@ -6,6 +6,7 @@ the end ATE (Umeyama), PSNR before / after a colour refinement (lvdgs.slam_seque
 utils/slam_backend.py:485-609, utils/eval_utils_0806.py:33-306).
 
     python tools/sequence.py [--frames 60] [--scale 1.0] [--cadence reference|short] [--no-fused] [--idle 10] [--refine 500] [--no-masks] [--pose-init previous|pnp] [--scale-remedy keep|matches]
+    python tools/sequence.py --config YAML [--dataset-path DIR] [--ingest host|fused]     # the frames of a directory instead (lvdgs.dataset.load_dataset)
 
 Prints one JSON object (bench.py's config.side.sequence_kitti07_geom is the same record).  `--cadence reference`: the iteration
 counts and densification schedule of configs/mono/KITTI/base_config.yaml as they are; `short`: every burst a fifth of it (the GPU
@@ -101,13 +102,42 @@ def kitti_sequence(dev, frames=60, scale=1.0, cadence="reference", masks=True, n
     return cfg, ds, truth
 
 
+def directory_sequence(dev, config_path, dataset_path=None, ingest="host", cadence="reference", training=None, window_size=None):
+    """(config, dataset): the settings of ``config_path`` (lvdgs.config_utils.load_config) and the dataset they name
+    (lvdgs.dataset.load_dataset: KITTI, waymo, dl3dv, replica or tum files on disk; ``dataset_path`` replaces the YAML's).  ``cadence``
+    "reference" leaves the Training block as the file has it, "short" lays ``SHORT`` over it; ``training`` / ``window_size`` as in
+    ``kitti_sequence``."""
+    from lvdgs.config_utils import load_config
+    from lvdgs.dataset import load_dataset
+    cfg = load_config(config_path)
+    cfg["Training"]["monocular"] = cfg["Dataset"]["sensor_type"] == "monocular"   # (set by the absent slam.py entry point)
+    tr = dict(SHORT) if cadence == "short" else {}
+    if window_size is not None:
+        tr.update(window_size=window_size, pose_window=min(3, window_size - 1))
+    tr.update(training or {})
+    lr = tr.pop("lr", None)
+    cfg["Training"].update(tr)
+    if lr:
+        cfg["Training"]["lr"].update(lr)
+    cfg.setdefault("Results", {}).update(save_results=False, use_gui=False)
+    if dataset_path is not None:
+        cfg["Dataset"]["dataset_path"] = dataset_path
+    return cfg, load_dataset(None, None, cfg, device=dev, ingest=ingest)
+
+
 def run_sequence(dev, frames=60, scale=1.0, cadence="reference", fused="auto", idle=10, refine=500, masks=True, seed=0, training=None,
-                 window_size=None, on_event=None, geometry="kitti07", pcd_downsample=None, mono_scale_drift=0.0, trajectory=None, **sequence_kwargs):
+                 window_size=None, on_event=None, geometry="kitti07", pcd_downsample=None, mono_scale_drift=0.0, trajectory=None,
+                 config_path=None, dataset_path=None, ingest="host", **sequence_kwargs):
     torch.manual_seed(seed)
     random.seed(seed)
-    cfg, ds, truth = kitti_sequence(dev, frames, scale, cadence, masks, seed=seed, training=training, window_size=window_size, geometry=geometry,
-                                    pcd_downsample=pcd_downsample, mono_scale_drift=mono_scale_drift, trajectory=trajectory)
-    del truth
+    if config_path is not None:      # frames from a directory: at most ``frames`` of them
+        cfg, ds = directory_sequence(dev, config_path, dataset_path, ingest, cadence, training, window_size)
+        masks, geometry = False, cfg["Dataset"]["type"]
+        ds.num_imgs = min(len(ds), frames)
+    else:
+        cfg, ds, truth = kitti_sequence(dev, frames, scale, cadence, masks, seed=seed, training=training, window_size=window_size, geometry=geometry,
+                                        pcd_downsample=pcd_downsample, mono_scale_drift=mono_scale_drift, trajectory=trajectory)
+        del truth
     m = empty_map(cfg, dev)
     if sequence_kwargs.get("matcher") == "descriptors":      # descriptor maps matched on the device (the network's stand-in: synthetic.WorldDescriptors)
         from lvdgs import init_pose
@@ -134,11 +164,13 @@ def run_sequence(dev, frames=60, scale=1.0, cadence="reference", fused="auto", i
         out["refinement_ms_per_iteration"] = round(1e3 * s / refine, 4)
     err = seq.pose_errors()
     out["pose_error_unaligned_mean"], out["pose_error_unaligned_max"] = sum(err.values()) / len(err), max(err.values())
-    out["trajectory_length"] = float(sum(float(torch.linalg.inv(ds.poses[i + 1])[:3, 3].sub(torch.linalg.inv(ds.poses[i])[:3, 3]).norm())
+    out["trajectory_length"] = float(sum(float(torch.linalg.inv(torch.as_tensor(ds.poses[i + 1]))[:3, 3].sub(torch.linalg.inv(torch.as_tensor(ds.poses[i]))[:3, 3]).norm())
                                          for i in range(len(ds) - 1)))
     out["window_log"] = seq.window_log
     out["batched_window_runs"] = int(getattr(getattr(seq.backend, "_lvdgs_window_batch", None), "runs", 0))
     out.update(geometry=geometry, width=ds.width, height=ds.height, cadence=cadence, fused=fused, idle_map_iters=idle, keyframes_carry_static_mask=masks)
+    if config_path is not None:
+        out.update(config=config_path, ingest=ingest)
     if mono_scale_drift or sequence_kwargs.get("keyframe_depth") is not None:
         out.update(mono_scale_drift=mono_scale_drift, keyframe_depth=sequence_kwargs.get("keyframe_depth") or "mono")
     return out, seq
@@ -182,6 +214,13 @@ def main():
     ap.add_argument("--map-edit", choices=["host", "fused"], default="host",
                     help="prune_points, densify_and_prune and the pruning pass: GaussianModel's PyTorch statements (default), or one map_edit plan, "
                          "one wait and one launch each (lvdgs_map_edit_plan / lvdgs_map_edit_apply)")
+    ap.add_argument("--config", default=None, metavar="YAML",
+                    help="run on the dataset this settings file names (lvdgs.config_utils.load_config + lvdgs.dataset.load_dataset) instead of the "
+                         "synthetic drive; --frames caps the frames read, --cadence short lays the short schedule over the file's Training block")
+    ap.add_argument("--dataset-path", default=None, metavar="DIR", help="with --config: the directory of the frames, instead of the file's dataset_path")
+    ap.add_argument("--ingest", choices=["host", "fused"], default="host",
+                    help="with --config: undistort and convert a decoded frame in NumPy and upload float32 (default), or upload its bytes and make "
+                         "one lvdgs_ingest_frame call (the same bits)")
     ap.add_argument("--verbose", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -194,7 +233,8 @@ def main():
                           **({"scale_remedy": "matches"} if a.scale_remedy == "matches" else {}),
                           **({"frame_stats": "fused"} if a.frame_stats == "fused" else {}), **({"edge_mask": "fused"} if a.edge_mask == "fused" else {}),
                           **({"dynamic_masks": "detections"} if a.dynamic_masks == "detections" else {}),
-                          **({"seeding": "fused"} if a.seeding == "fused" else {}), **({"map_edit": "fused"} if a.map_edit == "fused" else {}))
+                          **({"seeding": "fused"} if a.seeding == "fused" else {}), **({"map_edit": "fused"} if a.map_edit == "fused" else {}),
+                          **({"config_path": a.config, "dataset_path": a.dataset_path, "ingest": a.ingest} if a.config else {}))
     out.update(frame_stats=a.frame_stats, edge_mask=a.edge_mask, dynamic_masks=a.dynamic_masks, seeding=a.seeding, map_edit=a.map_edit)
     for rec in out.get("pose_init", []):
         print("  frame {frame:3d} kf {keyframe:3d} inliers {inl:>5} init error {e:.4f} ({r:.3f} deg; previous pose {p:.4f}) tracking iterations {it}".format(
