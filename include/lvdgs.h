@@ -35,6 +35,26 @@
  *  - all float tensors are float32, contiguous, row-major; matrices are 4x4 in the
  *    row-vector layout the reference's Camera produces (world_view_transform =
  *    getWorld2View2(R,T).transpose(0,1), utils/camera_utils.py:106-116).
+ *
+ * Host blocks
+ *  Seven calls enqueue their launches, do not wait, and report through a block of host memory, `host_state`: lvdgs_depth_align,
+ *  lvdgs_pnp_ransac, lvdgs_reciprocal_nn, lvdgs_match_depth_scale, lvdgs_frame_summary, lvdgs_seed_points, lvdgs_map_edit_plan.
+ *  - the block is the caller's: page-locked, mapped host memory (hipHostMalloc, a pinned PyTorch tensor) of the size its section
+ *    states, which the caller passes by its HOST address; memory that is not so is refused with LVDGS_E_HIP, "<call>: host_state is
+ *    not mapped pinned memory", before any launch;
+ *  - the call's last launch writes the block as int32 words, and its TAG word LAST.  The calls tagged with `seq` store it behind a
+ *    system-scope fence: a host that finds the tag finds every other word of the block.  The calls tagged with a status store it
+ *    last with no fence in front (the fence measurably slows them): their block is complete behind the caller's wait for the
+ *    stream, not before;
+ *  - the caller clears the tag word, makes the call, synchronises the stream ONCE and looks at the tag: a word that is not this
+ *    call's tag means that the call left no state (nothing else in the block is then to be believed);
+ *  - the tag is the `seq` of the argument block -- any value the caller's previous call did not use, 0 excepted -- for
+ *    lvdgs_frame_summary, lvdgs_seed_points and lvdgs_map_edit_plan, and the status word [0], never 0, for lvdgs_pnp_ransac,
+ *    lvdgs_reciprocal_nn and lvdgs_match_depth_scale;
+ *  - lvdgs_depth_align is the exception: its block has no tag, it is a state that every launch which changes it mirrors, that is
+ *    complete behind the caller's wait for the stream, and that lvdgs_depth_align_resume reads ON THE HOST -- the caller leaves it
+ *    alone between the two.
+ *  The sections below give each block's size and word layout only.
  */
 #ifndef LVDGS_H
 #define LVDGS_H
@@ -579,15 +599,14 @@ int lvdgs_gaussian_backward_batch(const lvdgs_args *const *views, int32_t count,
  *   else num_accurate = 0, and if count > 0 and (k < 2 or count >= min): s = mean r[acc] / mean m[acc] (UNSCALED m), num_accurate = count.
  * Fill (float32, as NumPy): ms = m * s; error = |r - ms| / (ms + 1e-8) > final_error_threshold or r == 0; final = error ? ms : r.
  * lvdgs_depth_align enqueues max_iter iteration launches and the fill (an iteration whose state is not RUNNING stands down); no host
- * wait.  The last launch to change the state copies it to host_state (LVDGS_DEPTH_ALIGN_STATE_WORDS int32 words of page-locked,
- * mapped host memory: [0] s (float bits), [1] s_prev (float bits), [2] status, [3] k of the last iteration run, [4] num_accurate,
+ * wait.  Every launch that changes the state copies it to host_state (a host block without a tag: "Host blocks" above;
+ * LVDGS_DEPTH_ALIGN_STATE_WORDS int32 words: [0] s (float bits), [1] s_prev (float bits), [2] status, [3] k of the last iteration run, [4] num_accurate,
  * [5] passing patches of the last iteration run, [6] accurate pixels of the last iteration run, [7] 1 once the fill has run).  The
  * caller synchronises the stream once and reads it.  status LVDGS_DEPTH_ALIGN_REMEDY (final_depth / error_mask not written): the
  * caller evaluates the remedy and calls lvdgs_depth_align_resume with its scale, which enqueues iteration 3 and the fill (remedy at
- * k == 2) or the fill alone (k == 3), and synchronises again.  scratch: lvdgs_depth_align_scratch_bytes(W, H, patch_size) bytes,
+ * k == 2) or the fill alone (k == 3), reading k from host_state, and synchronises again.  scratch: lvdgs_depth_align_scratch_bytes(W, H, patch_size) bytes,
  * ZERO-FILLED before its first use (every call leaves it so).  Bit-deterministic: the sums are taken in a fixed order.
- * LVDGS_E_INVALID: bad sizes, patch_size outside 1..LVDGS_DEPTH_ALIGN_MAX_PATCH, max_iter < 0, a NULL pointer, scratch too small;
- * LVDGS_E_HIP: host_state is not mapped pinned memory. */
+ * LVDGS_E_INVALID: bad sizes, patch_size outside 1..LVDGS_DEPTH_ALIGN_MAX_PATCH, max_iter < 0, a NULL pointer, scratch too small. */
 #define LVDGS_DEPTH_ALIGN_MAX_PATCH 64
 #define LVDGS_DEPTH_ALIGN_STATE_WORDS 8
 enum {
@@ -634,12 +653,11 @@ int lvdgs_depth_align_resume(const lvdgs_depth_align_args *a, float scale, void 
  *   under the final pose.  Sums over matches are taken in a fixed order: two calls give the same bits.
  * FAILED (the pose is the exact identity, the mask zero) with reason FEW_VALID (fewer than 6 valid matches), ALL_VOID, FEW_INLIERS
  *   (the winner's score < min_inliers) or SINGULAR (a refinement step fails).
- * Two launches, enqueued at once; no host wait.  host_state: LVDGS_PNP_HOST_BYTES bytes of page-locked, mapped host memory (the host
- * address): LVDGS_PNP_STATE_WORDS int32 words -- [0] status, [1] valid matches, [2] inliers under the final pose, [3] the winning
- * hypothesis (-1: none), [4] its score, [5] reason, [6] [7] zero -- then the pose as 12 doubles, row-major [R | t].  The caller
- * synchronises the stream once and reads it.  scratch: lvdgs_pnp_scratch_bytes(num_matches, hypotheses) bytes, no initialisation needed.
+ * Two launches, enqueued at once; no host wait.  host_state: a host block ("Host blocks" above) of LVDGS_PNP_HOST_BYTES bytes:
+ * LVDGS_PNP_STATE_WORDS int32 words -- [0] status, the tag, [1] valid matches, [2] inliers under the final pose, [3] the winning
+ * hypothesis (-1: none), [4] its score, [5] reason, [6] [7] zero -- then the pose as 12 doubles, row-major [R | t].  scratch: lvdgs_pnp_scratch_bytes(num_matches, hypotheses) bytes, no initialisation needed.
  * LVDGS_E_INVALID: args NULL, a NULL pointer, bad raster size, num_matches < 0, hypotheses outside 1..LVDGS_PNP_MAX_HYPOTHESES,
- * reproj_error / fx / fy not > 0, scratch too small; LVDGS_E_HIP: host_state is not mapped pinned memory. */
+ * reproj_error / fx / fy not > 0, scratch too small. */
 #define LVDGS_PNP_MAX_HYPOTHESES 4096
 #define LVDGS_PNP_STATE_WORDS 8
 #define LVDGS_PNP_HOST_BYTES 128
@@ -688,12 +706,11 @@ int lvdgs_pnp_ransac(const lvdgs_pnp_args *a, void *stream);
  * Every index written lies inside its map whatever the descriptors hold; with non-finite descriptors the result is otherwise unspecified.
  * Two calls on the same inputs give the same bytes.
  * 2 + 4 max_iter launches, enqueued at once; no host wait (the active set lives on the device; a search launch without active seeds
- * does nothing).  host_state: LVDGS_RNN_STATE_WORDS int32 words of page-locked, mapped host memory (the host address): [0] status
+ * does nothing).  host_state: a host block ("Host blocks" above) of LVDGS_RNN_STATE_WORDS int32 words: [0] status, the tag
  * (LVDGS_RNN_OK once the call has run), [1] seeds, [2] matches M, [3] unconverged seeds, [4] rounds that had an active seed, [5..7] zero.
  * scratch: lvdgs_recip_nn_scratch_bytes(...) bytes, no initialisation needed.
  * LVDGS_E_INVALID: args NULL, a NULL pointer, a size not > 0, a map of more than 2^31 - 1 floats, dim outside 1..LVDGS_RNN_MAX_DIM,
- * subsample < 1, max_iter < 1, more than LVDGS_RNN_MAX_SEEDS seeds, capacity below the seed count, scratch too small;
- * LVDGS_E_HIP: host_state is not mapped pinned memory. */
+ * subsample < 1, max_iter < 1, more than LVDGS_RNN_MAX_SEEDS seeds, capacity below the seed count, scratch too small. */
 #define LVDGS_RNN_MAX_DIM 64
 #define LVDGS_RNN_MAX_SEEDS 8192
 #define LVDGS_RNN_STATE_WORDS 8
@@ -785,11 +802,10 @@ int lvdgs_format_image(const lvdgs_format_image_args *a, void *stream);
  * A match is VALID when 0 <= x < raster_width, 0 <= y < raster_height, -1 < u < raster_width, -1 < v < raster_height (NaN: not) and both
  *   values are finite and > 0 (deviations: the reference lets +inf through, and its out-of-raster indices wrap or raise).
  * scale = float32((sum1 / n) / (sum2 / n)) over the n valid matches, the sums in float64 in a fixed order: two calls give the same bits.
- * One launch; no host wait.  host_state: LVDGS_MATCH_SCALE_HOST_BYTES bytes of page-locked, mapped host memory (the host address):
- * LVDGS_MATCH_SCALE_STATE_WORDS int32 words -- [0] status, [1] num_matches, [2] n, [3] the scale's float bits (0 when n == 0),
- * [4..7] zero -- then sum1 and sum2 as two doubles.  The caller synchronises the stream once and reads it.
- * LVDGS_E_INVALID: args NULL, a NULL pointer (the matches may be NULL when num_matches == 0), num_matches < 0, a size not > 0;
- * LVDGS_E_HIP: host_state is not mapped pinned memory. */
+ * One launch; no host wait.  host_state: a host block ("Host blocks" above) of LVDGS_MATCH_SCALE_HOST_BYTES bytes:
+ * LVDGS_MATCH_SCALE_STATE_WORDS int32 words -- [0] status, the tag, [1] num_matches, [2] n, [3] the scale's float bits (0 when n == 0),
+ * [4..7] zero -- then sum1 and sum2 as two doubles.
+ * LVDGS_E_INVALID: args NULL, a NULL pointer (the matches may be NULL when num_matches == 0), num_matches < 0, a size not > 0. */
 #define LVDGS_MATCH_SCALE_STATE_WORDS 8
 #define LVDGS_MATCH_SCALE_HOST_BYTES 64
 enum {
@@ -859,15 +875,14 @@ int lvdgs_edge_mask(const lvdgs_edge_mask_args *a, void *stream);
  * Covisibility.  cur[g] = n_touched[g] > 0 for Gaussian g of num_gaussians.  For row r of num_rows (rows[r]: num_gaussians bytes,
  *   nonzero = visible from that keyframe): intersection = #(cur & row), union = #(cur | row), own = #row.  visible = #cur.
  * mask_count = the nonzero bytes of count_mask (num_pixels bytes; NULL: 0).
- * A clear of the state and six launches, enqueued at once; no host wait.  host_state: LVDGS_FRAME_SUMMARY_HOST_BYTES bytes of
- * page-locked, mapped host memory (the host address), as int32 words: [LVDGS_FRAME_SUMMARY_SEQ] the call's `seq`, WRITTEN LAST -- a
- * caller that passes a fresh seq and, after synchronising the stream once, finds it there has the whole block --,
+ * A clear of the state and six launches, enqueued at once; no host wait.  host_state: a host block ("Host blocks" above) of
+ * LVDGS_FRAME_SUMMARY_HOST_BYTES bytes: [LVDGS_FRAME_SUMMARY_SEQ] the call's `seq`, the tag,
  * [_MEDIAN] the median's float bits, [_SELECTED] n, [_VISIBLE], [_MASK_COUNT], zeros up to LVDGS_FRAME_SUMMARY_ROWS, then three
  * words per row, LVDGS_FRAME_SUMMARY_MAX_ROWS of them: intersection, union, own (zero for the rows not passed).
  * scratch: the bytes lvdgs_frame_summary_scratch_bytes gives, no initialisation needed.  Integer sums only: two calls give the same bytes.
  * LVDGS_E_RANGE: num_rows outside 0..LVDGS_FRAME_SUMMARY_MAX_ROWS, num_gaussians < 0, num_pixels < 0; LVDGS_E_INVALID: args NULL,
  * host_state / scratch NULL, depth NULL with num_pixels > 0, n_touched or one of the rows NULL with num_gaussians > 0, scratch too
- * small -- all before any launch; LVDGS_E_HIP: host_state is not mapped pinned memory. */
+ * small -- all before any launch. */
 #define LVDGS_FRAME_SUMMARY_MAX_ROWS 16
 #define LVDGS_FRAME_SUMMARY_HOST_BYTES 256
 enum {
@@ -1000,14 +1015,13 @@ int lvdgs_dynamic_mask(const lvdgs_dynamic_mask_args *a, void *stream);
  * gain, offset: one float each ON THE DEVICE (NULL: 1 and 0); the caller's exp(exposure_a) and exposure_b.
  * want_median: the (P - 1) / 2-th smallest of all P = width*height depth values, the bits of torch.median (a NaN depth is outside
  * that contract, as for lvdgs_frame_summary).
- * A clear of the state and eight launches (twelve with the median), enqueued at once; no host wait.  host_state:
- * LVDGS_SEED_HOST_BYTES bytes of page-locked, mapped host memory (the host address), as int32 words: [LVDGS_SEED_SEQ] the call's
- * `seq`, WRITTEN LAST; [_N_VALID]; [_N_KEEP], the rows written; [_MEDIAN] the float bits, or the quiet NaN 0x7fc00000 when not asked
+ * A clear of the state and eight launches (twelve with the median), enqueued at once; no host wait.  host_state: a host block
+ * ("Host blocks" above) of LVDGS_SEED_HOST_BYTES bytes: [LVDGS_SEED_SEQ] the call's `seq`, the tag; [_N_VALID]; [_N_KEEP], the rows written; [_MEDIAN] the float bits, or the quiet NaN 0x7fc00000 when not asked
  * for; [_THRESHOLD] the key t, for diagnosis; zeros after it.  scratch: the bytes lvdgs_seed_scratch_bytes gives (0: the size is
  * refused), no initialisation needed.  No atomic decides an output position: two calls give the same bytes.
  * Before any launch -- LVDGS_E_RANGE: width or height below 1, more than 2^31 - 1 pixels, inv_downsample NaN or outside (0, 1],
  * capacity < (int64)((double)(width*height) * inv_downsample) (the host-side bound of n_keep); LVDGS_E_INVALID: args, depth, R, T, xyz,
- * host_state or scratch NULL, rgb or f_dc NULL with an image, scratch too small; LVDGS_E_HIP: host_state is not mapped pinned memory. */
+ * host_state or scratch NULL, rgb or f_dc NULL with an image, scratch too small. */
 #define LVDGS_SEED_HOST_BYTES 64
 enum {
     LVDGS_SEED_SEQ = 0,
@@ -1041,8 +1055,8 @@ int lvdgs_seed_points(const lvdgs_seed_args *a, void *stream);
  * index_select / cat launches) ----
  * lvdgs_map_edit_plan decides, counts and lays out; it moves no row.  For N = num_gaussians source rows it writes, per OUTPUT row r,
  *   src[r] (the source row), kind[r] (LVDGS_EDIT_KEEP / _CLONE / _SPLIT0 / _SPLIT1) and noise_row[r] (-1 unless a split child),
- * and into host_state -- page-locked, mapped host memory of host_bytes >= 4 (LVDGS_EDIT_HOST_SRC + 2 N) bytes, as int32 words --
- *   [LVDGS_EDIT_SEQ] the call's `seq`, WRITTEN LAST; [_N_OUT] output rows; [_N_KEEP] those of kind KEEP; [_N_CLONE] those of kind
+ * and into host_state -- a host block ("Host blocks" above) of host_bytes >= 4 (LVDGS_EDIT_HOST_SRC + 2 N) bytes --
+ *   [LVDGS_EDIT_SEQ] the call's `seq`, the tag; [_N_OUT] output rows; [_N_KEEP] those of kind KEEP; [_N_CLONE] those of kind
  *   CLONE; [_N_SPLIT_SEL] the split SOURCES, pruned or not (the noise tensor has 2 n_split_sel rows); [_N_PRUNED_FINAL] the rows the
  *   final prune took (prune mode: N - n_out); zeros up to [LVDGS_EDIT_HOST_SRC]; then src[0 .. n_out), and in prune mode with rule (b)
  *   n_obs[src[r]] for r in [0, n_out) behind it.
@@ -1073,8 +1087,7 @@ int lvdgs_seed_points(const lvdgs_seed_args *a, void *stream);
  * lvdgs_map_edit_scratch_bytes(N) gives (0: N < 0), no initialisation needed.
  * Before any launch -- LVDGS_E_INVALID: args, src, kind, noise_row, host_state or scratch NULL; a mode's inputs NULL (prune (b):
  * kf_id, n_obs, a vis row; densify: grad_accum, denom, scaling, opacity); scratch too small; LVDGS_E_RANGE: N < 0, an unknown mode,
- * num_vis_rows outside [0, LVDGS_EDIT_MAX_VIS_ROWS], a vis_stride other than 0, 1, 4, 8, scale_dims not 1 or 3, capacity or host_bytes too small; LVDGS_E_HIP: host_state
- * is not mapped pinned memory.
+ * num_vis_rows outside [0, LVDGS_EDIT_MAX_VIS_ROWS], a vis_stride other than 0, 1, 4, 8, scale_dims not 1 or 3, capacity or host_bytes too small.
  *
  * lvdgs_map_edit_apply moves the rows of up to LVDGS_EDIT_MAX_COLUMNS columns in one launch and does not wait: for every column and
  * every r < n_out, out row r (row_bytes bytes, any value >= 1) is

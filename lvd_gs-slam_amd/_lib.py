@@ -6,6 +6,7 @@ from here raises -- there is no CPU or PyTorch fallback.
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -503,6 +504,85 @@ class on_device:
         if self.prev is not None:
             torch.cuda.set_device(self.prev)
         return False
+
+
+class DeviceScratch:
+    """A library call's scratch, one buffer per device: kept while large enough, replaced by a larger one on demand
+    (``device_bytes``).  ``zeroed``: a new buffer is zero-filled once; ``headroom``: a new buffer gets half as much again."""
+
+    def __init__(self, *, zeroed=False, headroom=False):
+        self.zeroed, self.headroom, self.buffers = zeroed, headroom, {}
+
+    def get(self, device, nbytes):
+        nbytes = int(nbytes)
+        buf = self.buffers.get(device.index)
+        if buf is None or buf.numel() < nbytes:
+            buf = self.buffers[device.index] = device_bytes(nbytes + (nbytes // 2 if self.headroom else 0), device)
+            if self.zeroed:
+                buf.zero_()
+        return buf
+
+
+def next_seq(seq):
+    """The sequence number that follows ``seq``: 1 .. 0x7FFFFFFF round and round, never 0 -- what a cleared tag word holds."""
+    return (int(seq) % 0x7FFFFFFF) + 1
+
+
+def host_block_verdict(words, name, tag, seq=None, statuses=()):
+    """The tag word of a host block after the call's one wait: returned when it is the call's sequence number or one of the statuses
+    the call can end in; anything else -- the cleared word above all -- means the call wrote no state."""
+    found = int(words[tag])
+    if (seq is not None and found == seq) or found in statuses:
+        return found
+    expected = f"sequence number {seq}" if seq is not None else "status " + " or ".join(str(s) for s in statuses)
+    raise LvdgsError(f"{name} left no state (word [{tag}] of its host block holds {found}, expected {expected})")
+
+
+class HostCall:
+    """One entry point of the library that reports through a block of pinned host memory (include/lvdgs.h, "Host blocks"): its
+    per-device block, scratch and sequence counter, and the call with its one wait.
+
+    ``name``: the library function.  ``statuses``: what its tag word -- ``[tag]`` of the block -- may hold after the call; None: the
+    call is tagged with the ``seq`` of its argument block, which ``run`` fills in.  ``tag=None``: no tag (``lvdgs_depth_align``,
+    whose block is a state that its resume call reads: ``run`` neither clears nor judges it)."""
+
+    def __init__(self, name, *, statuses=None, tag=0, zeroed=False, headroom=False):
+        self.name, self.statuses, self.tag, self.headroom = name, statuses, tag, headroom
+        self.scratch = DeviceScratch(zeroed=zeroed, headroom=headroom)
+        self.blocks, self.words, self.seq = {}, {}, {}      # device index -> pinned block; -> its int32 words; -> last sequence number
+        self.fn = None
+
+    def resources(self, device, block_bytes, scratch_bytes=None):
+        """(the device's pinned block of at least ``block_bytes`` bytes -- the one of the call before while large enough --, its scratch
+        of at least ``scratch_bytes``; None: the call takes no scratch)."""
+        block_bytes = int(block_bytes)
+        block = self.blocks.get(device.index)
+        if block is None or block.numel() < block_bytes:
+            block = self.blocks[device.index] = torch.zeros(block_bytes + (block_bytes // 2 if self.headroom else 0), dtype=torch.uint8).pin_memory()
+            self.words[device.index] = block.numpy().view(np.int32)
+        return block, None if scratch_bytes is None else self.scratch.get(device, scratch_bytes)
+
+    def wait(self, device):
+        """The one wait of the call: until everything enqueued on the device's current stream has run."""
+        torch.cuda.current_stream(device).synchronize()
+
+    def run(self, device, args, fn=None):
+        """``fn(byref(args), stream)`` (default: the library function) on ``device``, whose block ``args.host_state`` is, and the
+        wait -> the block as int32 words (a view: copy what is to outlive the next call)."""
+        words = self.words[device.index]
+        if fn is None:
+            fn = self.fn = self.fn or getattr(lib(), self.name)
+        seq = None
+        if self.tag is not None:
+            words[self.tag] = 0      # whatever the call before left: only this call's own tag counts
+            if self.statuses is None:
+                seq = args.seq = self.seq[device.index] = next_seq(self.seq.get(device.index, 0))
+        with on_device(device):
+            check(fn(C.byref(args), raw_stream(device)), self.name)
+            self.wait(device)
+        if self.tag is not None:
+            host_block_verdict(words, self.name, self.tag, seq, self.statuses or ())
+        return words
 
 
 _gc_policy = None      # "scoped" | "process" | "off"; None: not decided yet (LVDGS_GC_FREEZE / set_gc_policy / first loop entry)

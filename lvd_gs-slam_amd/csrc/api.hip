@@ -32,6 +32,14 @@ int check_hip(hipError_t e, const char *what) {
     return LVDGS_E_HIP;
 }
 
+int host_block_address(void *host_state, const char *name, int32_t **dev) {
+    void *d = nullptr;
+    const hipError_t e = hipHostGetDevicePointer(&d, host_state, 0);
+    if (e != hipSuccess) { set_error("%s: host_state is not mapped pinned memory: %s", name, hipGetErrorString(e)); return LVDGS_E_HIP; }
+    *dev = reinterpret_cast<int32_t *>(d);
+    return LVDGS_OK;
+}
+
 // ---------------------------------------------------------------- profiling
 namespace {
 struct ProfSlot {

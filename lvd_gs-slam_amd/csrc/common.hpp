@@ -51,6 +51,9 @@ inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 // ---- error plumbing ----
 void set_error(const char *fmt, ...);
 int check_hip(hipError_t e, const char *what);
+// *dev = the address under which the device sees a caller's host block (include/lvdgs.h, "Host blocks"); "<name>: host_state is not
+// mapped pinned memory" when it is not one
+int host_block_address(void *host_state, const char *name, int32_t **dev);
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per device and kernel (the attribute is per device; one process
 // per GPU is the intended use, but a process may still touch several devices)

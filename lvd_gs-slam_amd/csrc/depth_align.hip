@@ -70,6 +70,8 @@ __host__ __device__ inline bool top_stop(float s, float s_prev, float eps) {
     return d < eps && s != 1.0f;
 }
 
+// The one host block that is not sealed (seal_host_block): a state without a tag, mirrored by every launch that changes it -- several
+// times per call -- and read by the host only behind its wait for the stream, where the last mirror is complete.
 __device__ __forceinline__ void mirror_state(const AlignParams &P, const DepthAlignState &st) {
     P.hdr->st = st;
     if (P.host_state) {
@@ -288,9 +290,7 @@ int align_params(const lvdgs_depth_align_args *a, AlignParams &P) {
     P.hdr = reinterpret_cast<DepthAlignHeader *>(a->scratch);
     P.slab = reinterpret_cast<PatchPartial *>(reinterpret_cast<char *>(a->scratch) + align256(sizeof(DepthAlignHeader)));
     P.final_depth = a->final_depth; P.error_mask = a->error_mask;
-    void *dev = nullptr;
-    if (int e = check_hip(hipHostGetDevicePointer(&dev, a->host_state, 0), "depth align: host_state is not mapped pinned memory")) return e;
-    P.host_state = reinterpret_cast<int32_t *>(dev);
+    if (int e = host_block_address(a->host_state, "depth align", &P.host_state)) return e;
     return LVDGS_OK;
 }
 

@@ -190,4 +190,13 @@ __device__ __forceinline__ int write_lane(int v, int x, int lane) { return lvdgs
 
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 
+// last step of a call that reports through a pinned host block: the host sees everything stored before the tag before it sees the tag
+// (the payload goes through the same volatile pointer, by the one thread that seals).  The publish kernels of the calls tagged with a
+// sequence number end in it; the three tagged with a status (pnp.hip, recip_nn.hip, matcher_io.hip) say why they do not.
+__device__ __forceinline__ void seal_host_block(volatile int32_t *w, int index, int32_t tag) {
+    __threadfence_system();
+    w[index] = tag;
+    __threadfence_system();
+}
+
 }  // namespace lvdgs

@@ -207,9 +207,7 @@ __global__ void summary_publish_kernel(SummaryParams S) {
     for (int j = LVDGS_FRAME_SUMMARY_MASK_COUNT + 1; j < LVDGS_FRAME_SUMMARY_ROWS; j++) w[j] = 0;
     for (int r = 0; r < LVDGS_FRAME_SUMMARY_MAX_ROWS; r++)
         for (int j = 0; j < 3; j++) w[LVDGS_FRAME_SUMMARY_ROWS + 3 * r + j] = r < S.R ? (int32_t)S.cnt->rows[r][j] : 0;
-    __threadfence_system();
-    w[LVDGS_FRAME_SUMMARY_SEQ] = (int32_t)S.seq;   // last: a host that sees it sees the rest
-    __threadfence_system();
+    seal_host_block(w, LVDGS_FRAME_SUMMARY_SEQ, (int32_t)S.seq);
 }
 
 size_t summary_state_bytes() { return align256(sizeof(SelectState)) + align256(sizeof(SummaryCounters)); }
@@ -304,9 +302,7 @@ int lvdgs_frame_summary(const lvdgs_frame_summary_args *a, void *stream) {
     for (int r = 0; r < S.R; r++) S.rows[r] = a->rows[r];
     S.st = reinterpret_cast<SelectState *>(a->scratch);
     S.cnt = reinterpret_cast<SummaryCounters *>(reinterpret_cast<char *>(a->scratch) + align256(sizeof(SelectState)));
-    void *dev = nullptr;
-    if (int e = check_hip(hipHostGetDevicePointer(&dev, a->host_state, 0), "frame summary: host_state is not mapped pinned memory")) return e;
-    S.host = reinterpret_cast<int32_t *>(dev);
+    if (int e = host_block_address(a->host_state, "frame summary", &S.host)) return e;
     if (int e = check_hip(hipMemsetAsync(a->scratch, 0, summary_state_bytes(), s), "frame summary: clearing the state")) return e;
     if (int e = launch_select(DepthSource{S.depth, S.opacity, S.mask, S.bar}, S.P, S.st, -1, "summary_median", s)) return e;
     {

@@ -172,9 +172,7 @@ __global__ void edit_publish_kernel(PlanParams P) {
     w[LVDGS_EDIT_N_SPLIT_SEL] = (int32_t)n_sel;
     w[LVDGS_EDIT_N_PRUNED_FINAL] = (int32_t)(before - n_out);
     for (int j = LVDGS_EDIT_N_PRUNED_FINAL + 1; j < LVDGS_EDIT_HOST_SRC; j++) w[j] = 0;
-    __threadfence_system();
-    w[LVDGS_EDIT_SEQ] = (int32_t)P.seq;   // last: a host that sees it sees the rest
-    __threadfence_system();
+    seal_host_block(w, LVDGS_EDIT_SEQ, (int32_t)P.seq);
 }
 
 struct ApplyParams {
@@ -265,9 +263,7 @@ int lvdgs_map_edit_plan(const lvdgs_map_edit_plan_args *a, void *stream) {
     P.code = reinterpret_cast<uint8_t *>(base + L.code);
     P.counts = reinterpret_cast<uint32_t *>(base + L.counts);
     P.totals = reinterpret_cast<uint32_t *>(base + L.totals);
-    void *dev = nullptr;
-    if (int e = check_hip(hipHostGetDevicePointer(&dev, a->host_state, 0), "map edit plan: host_state is not mapped pinned memory")) return e;
-    P.host = reinterpret_cast<int32_t *>(dev);
+    if (int e = host_block_address(a->host_state, "map edit plan", &P.host)) return e;
     P.host_words = (int64_t)(a->host_bytes / sizeof(int32_t));
     if (P.blocks) {
         ProfScope ps("edit_count", s);

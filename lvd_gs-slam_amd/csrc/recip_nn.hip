@@ -270,6 +270,8 @@ __global__ void __launch_bounds__(RNN_ONE) rnn_final_kernel(RnnParams P, int n2)
         }
     }
     if (tid == 0) {
+        // NOT sealed (device_utils.hpp: seal_host_block), like pnp.hip's write_state: the host's wait for the stream is what makes the block complete.
+        // Measured on the MI355X: volatile payload stores and the seal cost 10-14 us per call, outside its run-to-run spread.
         int32_t *w = P.host_state;
         w[1] = P.seeds; w[2] = M; w[3] = P.seeds - retired; w[4] = (int32_t)P.hdr->rounds; w[5] = 0; w[6] = 0; w[7] = 0;
         w[0] = LVDGS_RNN_OK;
@@ -326,9 +328,7 @@ int lvdgs_reciprocal_nn(const lvdgs_recip_nn_args *a, void *stream) {
     P.old2 = reinterpret_cast<int32_t *>(base + 3 * col); P.retired = reinterpret_cast<int32_t *>(base + 4 * col);
     P.act[0] = reinterpret_cast<uint32_t *>(base + 5 * col); P.act[1] = reinterpret_cast<uint32_t *>(base + 6 * col);
     P.keys = reinterpret_cast<u64 *>(base + 7 * col);
-    void *dev = nullptr;
-    if (int e = check_hip(hipHostGetDevicePointer(&dev, a->host_state, 0), "recip_nn: host_state is not mapped pinned memory")) return e;
-    P.host_state = reinterpret_cast<int32_t *>(dev);
+    if (int e = host_block_address(a->host_state, "recip_nn", &P.host_state)) return e;
     int n2 = 2 * RNN_ONE;
     while (n2 < P.seeds) n2 *= 2;
     if (int e = allow_dynamic_lds(reinterpret_cast<const void *>(&rnn_final_kernel), LVDGS_RNN_MAX_SEEDS * (int)sizeof(u64), lds_done)) return e;

@@ -153,9 +153,7 @@ __global__ void seed_publish_kernel(SeedParams S) {
     w[LVDGS_SEED_MEDIAN] = (int32_t)(S.want_median ? select_result_bits(S.st_median->n, S.st_median->prefix) : SEL_QUIET_NAN);
     w[LVDGS_SEED_THRESHOLD] = (int32_t)S.st_key->prefix;
     for (int j = LVDGS_SEED_THRESHOLD + 1; j < (int)(LVDGS_SEED_HOST_BYTES / sizeof(int32_t)); j++) w[j] = 0;
-    __threadfence_system();
-    w[LVDGS_SEED_SEQ] = (int32_t)S.seq;   // last: a host that sees it sees the rest
-    __threadfence_system();
+    seal_host_block(w, LVDGS_SEED_SEQ, (int32_t)S.seq);
 }
 
 size_t seed_state_bytes() { return 2 * align256(sizeof(SelectState)) + align256(SEED_MAX_BLOCKS * sizeof(uint32_t)); }
@@ -204,9 +202,7 @@ int lvdgs_seed_points(const lvdgs_seed_args *a, void *stream) {
     S.st_key = reinterpret_cast<SelectState *>(base);
     S.st_median = reinterpret_cast<SelectState *>(base + align256(sizeof(SelectState)));
     S.counts = reinterpret_cast<uint32_t *>(base + 2 * align256(sizeof(SelectState)));
-    void *dev = nullptr;
-    if (int e = check_hip(hipHostGetDevicePointer(&dev, a->host_state, 0), "seed points: host_state is not mapped pinned memory")) return e;
-    S.host = reinterpret_cast<int32_t *>(dev);
+    if (int e = host_block_address(a->host_state, "seed points", &S.host)) return e;
     const int blocks = select_blocks(P);   // <= SEED_MAX_BLOCKS spans
     S.span = ((P + blocks - 1) / blocks + SEED_THREADS - 1) / SEED_THREADS * SEED_THREADS;
     if (int e = check_hip(hipMemsetAsync(a->scratch, 0, seed_state_bytes(), s), "seed points: clearing the state")) return e;

@@ -14,7 +14,6 @@ the matcher's raster, a ratio of means at the matches); here it is ``find_scale`
 behind the matcher is out of scope.  Without a remedy (or when it returns None), the current scale is kept (the documented
 stand-in).  Whether the remedy branch was reached, and what it did, is recorded in ``last_call`` (and logged at INFO level).
 """
-import ctypes as C
 import logging
 from types import SimpleNamespace
 
@@ -34,23 +33,14 @@ last_call = SimpleNamespace(patch_num=0, status=None, iteration=None, remedies=[
 # sum1 / sum2 (the float64 sums of the two maps' samples over the valid matches).
 last_scale = SimpleNamespace(status=None, matches=0, valid=0, scale=None, sum1=0.0, sum2=0.0)
 
-_resources = {}   # device index -> (pinned state words, scratch tensor)
-_scale_blocks = {}   # device index -> pinned host block of lvdgs_match_depth_scale
+# lvdgs_depth_align's block is a state that lvdgs_depth_align_resume reads on the host: no tag, never cleared; its scratch is zero-filled
+# once and every call leaves it so
+_align = _lib.HostCall("lvdgs_depth_align", tag=None, zeroed=True)
+_scale = _lib.HostCall("lvdgs_match_depth_scale", statuses=(_lib.MATCH_SCALE_OK, _lib.MATCH_SCALE_NO_VALID))
 
 
-def _state_and_scratch(device, nbytes):
-    key = device.index
-    hs, scratch = _resources.get(key, (None, None))
-    if hs is None:
-        hs = torch.zeros(_lib.DEPTH_ALIGN_STATE_WORDS, dtype=torch.int32).pin_memory()
-    if scratch is None or scratch.numel() < nbytes:
-        scratch = torch.zeros(max(int(nbytes), 256), dtype=torch.uint8, device=device)   # zero-filled once; every call leaves it so
-    _resources[key] = (hs, scratch)
-    return hs, scratch
-
-
-def _read_state(hs):
-    w = hs.numpy().copy()
+def _read_state(words):
+    w = words.copy()
     return SimpleNamespace(s=w[0:1].view(np.float32)[0], s_prev=w[1:2].view(np.float32)[0], status=int(w[2]), k=int(w[3]),
                            num_accurate=int(w[4]), patch_num=int(w[5]), count=int(w[6]), filled=int(w[7]))
 
@@ -90,7 +80,7 @@ def process_depth(render_depth, mono_depth, last_depth=None, im1=None, im2=None,
     final = torch.empty((H, W), dtype=torch.float32, device=device)
     mask = torch.empty((H, W), dtype=torch.uint8, device=device)
     need = L.lvdgs_depth_align_scratch_bytes(W, H, max(int(patch_size), 1))
-    hs, scratch = _state_and_scratch(device, need)
+    hs, scratch = _align.resources(device, 4 * _lib.DEPTH_ALIGN_STATE_WORDS, need)
     a = _lib.DepthAlignArgs(width=W, height=H, patch_size=int(patch_size), max_iter=int(max_iter), mean_threshold=float(mean_threshold),
                             std_threshold=float(std_threshold), error_threshold=float(error_threshold),
                             final_error_threshold=float(final_error_threshold), epsilon=float(epsilon),
@@ -98,10 +88,7 @@ def process_depth(render_depth, mono_depth, last_depth=None, im1=None, im2=None,
                             render_depth=r.data_ptr(), mono_depth=m.data_ptr(), final_depth=final.data_ptr(), error_mask=mask.data_ptr(),
                             host_state=hs.data_ptr(), scratch=scratch.data_ptr(), scratch_bytes=scratch.numel())
     with _lib.on_device(device):
-        stream = _lib.raw_stream(device)
-        _lib.check(L.lvdgs_depth_align(C.byref(a), stream), "lvdgs_depth_align")
-        torch.cuda.current_stream(device).synchronize()      # the one wait of a call without the remedy
-        st = _read_state(hs)
+        st = _read_state(_align.run(device, a))      # the one wait of a call without the remedy
         remedies = []     # (k, scale given by the remedy or None)
         while st.status == _lib.DEPTH_ALIGN_REMEDY and len(remedies) < 2:
             given = None if scale_remedy is None else scale_remedy(im1, im2, last_depth, mono_depth, model)
@@ -113,9 +100,7 @@ def process_depth(render_depth, mono_depth, last_depth=None, im1=None, im2=None,
             remedies.append((st.k, given))
             log.info("process_depth: %d accurate pixels at iteration %d (< %d): scale remedy %s", st.count, st.k,
                      int(min_accurate_pixels_ratio * H * W), "applied" if given is not None else "absent, scale kept")
-            _lib.check(L.lvdgs_depth_align_resume(C.byref(a), float(scale), stream), "lvdgs_depth_align_resume")
-            torch.cuda.current_stream(device).synchronize()
-            st = _read_state(hs)
+            st = _read_state(_align.run(device, a, lambda args, stream: L.lvdgs_depth_align_resume(args, float(scale), stream)))
         if not st.filled:
             raise _lib.LvdgsError(f"lvdgs_depth_align ended without its fill (status {st.status})")
     last_call.patch_num, last_call.status, last_call.iteration = st.patch_num, st.status, (st.k if max_iter > 0 else None)
@@ -157,23 +142,14 @@ def scale_from_matches(matches_im1, matches_im2, depth1, depth2, raster):
     m2 = m2.to(device=device, dtype=torch.float32).contiguous()
     d1, d2 = _device_map(depth1, device, "depth1"), _device_map(depth2, device, "depth2")
     W1, H1 = int(raster[0]), int(raster[1])
-    block = _scale_blocks.get(device.index)
-    if block is None:
-        block = _scale_blocks[device.index] = torch.zeros(_lib.MATCH_SCALE_HOST_BYTES, dtype=torch.uint8).pin_memory()
-    block.zero_()
+    block, _ = _scale.resources(device, _lib.MATCH_SCALE_HOST_BYTES)
     M = int(m1.shape[0])
     a = _lib.MatchScaleArgs(num_matches=M, raster_width=W1, raster_height=H1, width1=d1.shape[1], height1=d1.shape[0], width2=d2.shape[1],
                             height2=d2.shape[0], matches_im1=m1.data_ptr() if M else None, matches_im2=m2.data_ptr() if M else None,
                             depth1=d1.data_ptr(), depth2=d2.data_ptr(), host_state=block.data_ptr())
-    with _lib.on_device(device):
-        _lib.check(_lib.lib().lvdgs_match_depth_scale(C.byref(a), _lib.raw_stream(device)), "lvdgs_match_depth_scale")
-        torch.cuda.current_stream(device).synchronize()      # the one wait of the call
-    raw = block.numpy()
-    w = raw[:4 * _lib.MATCH_SCALE_STATE_WORDS].view(np.int32).copy()
-    sums = raw[4 * _lib.MATCH_SCALE_STATE_WORDS:4 * _lib.MATCH_SCALE_STATE_WORDS + 16].view(np.float64).copy()
+    w = _scale.run(device, a).copy()      # the one wait of the call
+    sums = w[_lib.MATCH_SCALE_STATE_WORDS:_lib.MATCH_SCALE_STATE_WORDS + 4].view(np.float64)
     status = int(w[0])
-    if status not in (_lib.MATCH_SCALE_OK, _lib.MATCH_SCALE_NO_VALID):
-        raise _lib.LvdgsError(f"lvdgs_match_depth_scale left no state (status word {status})")
     scale = float(w[3:4].view(np.float32)[0]) if status == _lib.MATCH_SCALE_OK else None
     last_scale.status, last_scale.matches, last_scale.valid, last_scale.scale = status, int(w[1]), int(w[2]), scale
     last_scale.sum1, last_scale.sum2 = float(sums[0]), float(sums[1])

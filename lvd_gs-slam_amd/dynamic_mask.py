@@ -24,7 +24,7 @@ VEHICLE_KEYWORDS = ("car", "truck", "bus", "vehicle", "van", "suv", "motorcycle"
 BOX_FORMATS = {"xyxy": _lib.DYNAMIC_MASK_BOXES_XYXY, "cxcywh": _lib.DYNAMIC_MASK_BOXES_CXCYWH}
 OUTPUTS = ("static_mask", "dynamic_mask", "expanded_dynamic_mask", "expanded_static_mask", "valid_rgb")
 
-_scratch = {}      # device index -> scratch tensor
+_scratch = _lib.DeviceScratch()
 
 
 def is_vehicle(label):
@@ -113,10 +113,7 @@ def assemble(width, height, boxes, vehicle=None, sam_masks=None, *, first_frame,
     else:
         image = depth = None
     L = _lib.lib()
-    nbytes = int(L.lvdgs_dynamic_mask_scratch_bytes(W, H))
-    scratch = _scratch.get(device.index)
-    if scratch is None or scratch.numel() < nbytes:
-        scratch = _scratch[device.index] = _lib.device_bytes(nbytes, device)
+    scratch = _scratch.get(device, L.lvdgs_dynamic_mask_scratch_bytes(W, H))
     out = DynamicMasks()
     keyframe_only = OUTPUTS[2:]
     for name in outputs:

@@ -15,8 +15,8 @@ import torch
 
 from . import _lib
 
-_edge_scratch = {}      # device index -> scratch tensor
-_summary_state = {}     # device index -> [pinned host block, scratch tensor, last sequence number]
+_edge_scratch = _lib.DeviceScratch()
+_summary = _lib.HostCall("lvdgs_frame_summary", tag=_lib.FRAME_SUMMARY_SEQ)
 
 
 class EdgeMask:
@@ -32,10 +32,7 @@ def edge_mask_call(image, edge_threshold, dataset_type=None, *, loss_mask=False,
     _, H, W = image.shape
     blocks = dataset_type == "replica"
     L = _lib.lib()
-    nbytes = int(L.lvdgs_edge_mask_scratch_bytes(W, H))
-    scratch = _edge_scratch.get(device.index)
-    if scratch is None or scratch.numel() < nbytes:
-        scratch = _edge_scratch[device.index] = _lib.device_bytes(nbytes, device)
+    scratch = _edge_scratch.get(device, L.lvdgs_edge_mask_scratch_bytes(W, H))
     out = EdgeMask()
     out.mask = torch.empty((1, H, W), dtype=torch.float32 if blocks else torch.bool, device=device)
     out.loss_mask = torch.empty(H * W, dtype=torch.uint8, device=device) if loss_mask else None
@@ -122,32 +119,20 @@ def frame_summary(render_pkg, visibility_rows, mask=None, count_mask=None, opaci
     mask_b, count_b = pixel_masks
 
     L = _lib.lib()
-    state = _summary_state.get(device.index)
-    if state is None:
-        state = _summary_state[device.index] = [torch.zeros(_lib.FRAME_SUMMARY_HOST_BYTES, dtype=torch.uint8).pin_memory(),
-                                                _lib.device_bytes(L.lvdgs_frame_summary_scratch_bytes(), device), 0]
-    block, scratch, _ = state
-    words = block.numpy().view(np.int32)
+    block, scratch = _summary.resources(device, _lib.FRAME_SUMMARY_HOST_BYTES, L.lvdgs_frame_summary_scratch_bytes())
     out = FrameSummary()
     out.covis = {}
     R = _lib.FRAME_SUMMARY_MAX_ROWS
     chunks = [on_device[i:i + R] for i in range(0, len(on_device), R)] or [[]]
-    stream = torch.cuda.current_stream(device)
     for chunk in chunks:
-        state[2] = seq = (state[2] % 0x7FFFFFFF) + 1
-        a = _lib.FrameSummaryArgs(num_pixels=P, num_gaussians=N, num_rows=len(chunk), seq=seq, opacity_bar=float(opacity_bar),
+        a = _lib.FrameSummaryArgs(num_pixels=P, num_gaussians=N, num_rows=len(chunk), opacity_bar=float(opacity_bar),
                                   depth=depth.data_ptr(), opacity=None if opacity is None else opacity.data_ptr(),
                                   mask=None if mask_b is None else mask_b.data_ptr(), n_touched=n_touched.data_ptr(),
                                   count_mask=None if count_b is None else count_b.data_ptr(), host_state=block.data_ptr(),
                                   scratch=scratch.data_ptr(), scratch_bytes=scratch.numel())
         for r, (_, b) in enumerate(chunk):
             a.rows[r] = b.data_ptr()
-        with _lib.on_device(device):
-            _lib.check(L.lvdgs_frame_summary(C.byref(a), _lib.raw_stream(device)), "lvdgs_frame_summary")
-            stream.synchronize()      # the one wait of the call
-        w = words.copy()
-        if int(w[_lib.FRAME_SUMMARY_SEQ]) != seq:
-            raise _lib.LvdgsError(f"lvdgs_frame_summary left no state (sequence word {int(w[_lib.FRAME_SUMMARY_SEQ])}, expected {seq})")
+        w = _summary.run(device, a).copy()      # the one wait of the call
         out.median_bits = int(w[_lib.FRAME_SUMMARY_MEDIAN]) & 0xFFFFFFFF
         out.median_depth = float(w[_lib.FRAME_SUMMARY_MEDIAN:_lib.FRAME_SUMMARY_MEDIAN + 1].view(np.float32)[0])
         out.selected, out.visible = int(w[_lib.FRAME_SUMMARY_SELECTED]), int(w[_lib.FRAME_SUMMARY_VISIBLE])

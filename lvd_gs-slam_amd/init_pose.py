@@ -36,10 +36,10 @@ last_call = SimpleNamespace(status=None, reason=None, valid_matches=0, inliers=0
 # and converged flag when the call asked for it, else None).
 last_match = SimpleNamespace(seeds=0, matches=0, unconverged=0, rounds=0, seed_state=None)
 
-_resources = {}   # device index -> (pinned host block, its words as int32, its pose as float64, scratch tensor)
-_match_resources = {}   # device index -> (pinned state words, scratch tensor)
+_pnp = _lib.HostCall("lvdgs_pnp_ransac", statuses=(_lib.PNP_OK, _lib.PNP_FAILED))
+_match = _lib.HostCall("lvdgs_reciprocal_nn", statuses=(_lib.RNN_OK,))
 _format_tables = {}     # (device index, W, H, size) -> (plan, table_x, table_y device tensors): made once per image size and device
-_format_scratch = {}    # device index -> scratch tensor
+_format_scratch = _lib.DeviceScratch()
 
 
 def matcher_raster(W, H, size=512):
@@ -52,17 +52,6 @@ def matcher_raster(W, H, size=512):
     if w == h:
         halfh = 3 * halfw // 4
     return 2 * halfw, 2 * halfh
-
-
-def _host_block(device, nbytes):
-    key = device.index
-    block, scratch = _resources.get(key, (None, None))
-    if block is None:
-        block = torch.zeros(_lib.PNP_HOST_BYTES, dtype=torch.uint8).pin_memory()
-    if scratch is None or scratch.numel() < nbytes:
-        scratch = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
-    _resources[key] = (block, scratch)
-    return block, scratch
 
 
 def pnp_ransac(depth, matches_im1, matches_im2, K, dist_coeffs=None, hypotheses=128, reproj_error=5.0, seed=0, min_inliers=6):
@@ -88,25 +77,19 @@ def pnp_ransac(depth, matches_im1, matches_im2, K, dist_coeffs=None, hypotheses=
         raise ValueError("pnp_ransac: dist_coeffs must be the five coefficients k1 k2 p1 p2 k3")
     L = _lib.lib()
     mask = torch.empty(max(M, 1), dtype=torch.uint8, device=device)
-    block, scratch = _host_block(device, L.lvdgs_pnp_scratch_bytes(M, max(int(hypotheses), 0)))
+    block, scratch = _pnp.resources(device, _lib.PNP_HOST_BYTES, L.lvdgs_pnp_scratch_bytes(M, max(int(hypotheses), 0)))
     a = _lib.PnpArgs(width=W1, height=H1, num_matches=M, hypotheses=int(hypotheses), min_inliers=int(min_inliers), seed=int(seed) & 0xFFFFFFFF,
                      fx=float(K[0]), fy=float(K[1]), cx=float(K[2]), cy=float(K[3]), dist=(C.c_double * 5)(*dist.tolist()),
                      reproj_error=float(reproj_error), depth=d.data_ptr(), matches_im1=m1.data_ptr(), matches_im2=m2.data_ptr(),
                      inlier_mask=mask.data_ptr(), host_state=block.data_ptr(), scratch=scratch.data_ptr(), scratch_bytes=scratch.numel())
-    with _lib.on_device(device):
-        _lib.check(L.lvdgs_pnp_ransac(C.byref(a), _lib.raw_stream(device)), "lvdgs_pnp_ransac")
-        torch.cuda.current_stream(device).synchronize()      # the one wait of the call
-    raw = block.numpy()
-    w = raw[:4 * _lib.PNP_STATE_WORDS].view(np.int32).copy()
-    rt = raw[4 * _lib.PNP_STATE_WORDS:].view(np.float64).copy().reshape(3, 4)
+    w = _pnp.run(device, a).copy()      # the one wait of the call
+    rt = w[_lib.PNP_STATE_WORDS:_lib.PNP_STATE_WORDS + 24].view(np.float64).reshape(3, 4)
     last_call.status, last_call.valid_matches, last_call.inliers, last_call.hypothesis = int(w[0]), int(w[1]), int(w[2]), int(w[3])
     last_call.winner_count, last_call.reason, last_call.matches = int(w[4]), int(w[5]), M
     last_call.inlier_mask = mask[:M].bool()
     pose = np.eye(4)
     if last_call.status == _lib.PNP_OK:
         pose[:3, :] = rt
-    elif last_call.status != _lib.PNP_FAILED:
-        raise _lib.LvdgsError(f"lvdgs_pnp_ransac left no state (status word {last_call.status})")
     return pose, last_call.inlier_mask
 
 
@@ -135,27 +118,16 @@ def reciprocal_matches(desc1, desc2, subsample=8, max_iter=10, seed_state=False)
     seeds = len(range(S // 2, H1, S)) * len(range(S // 2, W1, S)) if S >= 1 else 0
     L = _lib.lib()
     need = L.lvdgs_recip_nn_scratch_bytes(W1, H1, S) if S >= 1 else 0
-    block, scratch = _match_resources.get(device.index, (None, None))
-    if block is None:
-        block = torch.zeros(_lib.RNN_STATE_WORDS, dtype=torch.int32).pin_memory()
-    if scratch is None or scratch.numel() < need:
-        scratch = torch.empty(max(int(need), 256), dtype=torch.uint8, device=device)
-    _match_resources[device.index] = (block, scratch)
+    block, scratch = _match.resources(device, 4 * _lib.RNN_STATE_WORDS, need)
     cap = max(seeds, 1)
     m1 = torch.empty((cap, 2), dtype=torch.int32, device=device)
     m2 = torch.empty((cap, 2), dtype=torch.float32, device=device)
     state = torch.empty((cap, 3), dtype=torch.int32, device=device) if seed_state else None
-    block.zero_()
     a = _lib.RecipNnArgs(width1=W1, height1=H1, width2=W2, height2=H2, dim=D, subsample=S, max_iter=int(max_iter), capacity=cap,
                          desc1=d1.data_ptr(), desc2=d2.data_ptr(), matches_im1=m1.data_ptr(), matches_im2=m2.data_ptr(),
                          seed_state=None if state is None else state.data_ptr(), host_state=block.data_ptr(), scratch=scratch.data_ptr(),
                          scratch_bytes=scratch.numel())
-    with _lib.on_device(device):
-        _lib.check(L.lvdgs_reciprocal_nn(C.byref(a), _lib.raw_stream(device)), "lvdgs_reciprocal_nn")
-        torch.cuda.current_stream(device).synchronize()      # the one wait of the call
-    w = block.numpy().copy()
-    if int(w[0]) != _lib.RNN_OK:
-        raise _lib.LvdgsError(f"lvdgs_reciprocal_nn left no state (status word {int(w[0])})")
+    w = _match.run(device, a).copy()      # the one wait of the call
     last_match.seeds, last_match.matches, last_match.unconverged, last_match.rounds = int(w[1]), int(w[2]), int(w[3]), int(w[4])
     last_match.seed_state = None if state is None else state[:last_match.seeds]
     return m1[:last_match.matches], m2[:last_match.matches]
@@ -193,10 +165,7 @@ def format_image(img, size=512, *, quantised=False):
     H, W = int(x.shape[1]), int(x.shape[2])
     p, table_x, table_y = _format_plan(device, W, H, int(size))
     L = _lib.lib()
-    need = L.lvdgs_format_scratch_bytes(W, H, int(size))
-    scratch = _format_scratch.get(device.index)
-    if scratch is None or scratch.numel() < need:
-        scratch = _format_scratch[device.index] = torch.empty(max(int(need), 256), dtype=torch.uint8, device=device)
+    scratch = _format_scratch.get(device, L.lvdgs_format_scratch_bytes(W, H, int(size)))
     out = torch.empty((1, 3, p.out_height, p.out_width), dtype=torch.float32, device=device)
     q = torch.empty((p.out_height, p.out_width, 3), dtype=torch.uint8, device=device) if quantised else None
     a = _lib.FormatImageArgs(width=W, height=H, size=int(size), image=x.data_ptr(), table_x=table_x.data_ptr(), table_y=table_y.data_ptr(),

@@ -6,11 +6,11 @@
 ``apply``         moves the rows of every per-Gaussian array a caller names -- parameters, Adam moments, statistics, visibility rows --
                   in one launch, and computes the split children's positions and scales.
 
-A plan is one library call and ONE wait (``_wait``) on a block of pinned host memory that then holds the counts and the source row of
-every output row; ``apply`` does not wait.  The noise of the split children is the caller's: it is drawn between plan and apply, with
+A plan is one library call and ONE wait (``_plan``, a ``_lib.HostCall``) on a block of pinned host memory that then holds the counts and
+the source row of every output row; ``apply`` does not wait.  The noise of the split children is the caller's: it is drawn between plan and apply, with
 the shape the plan reports, so a model that edits its map this way consumes its generator as the host statements do.
 
-A ``Plan``'s device arrays belong to the per-device state and are valid until the next plan on that device.
+A ``Plan``'s device arrays belong to the per-device outputs and are valid until the next plan on that device.
 """
 import ctypes as C
 
@@ -19,7 +19,8 @@ import torch
 
 from . import _lib
 
-_state = {}     # device index -> {"block": pinned host block, "scratch", "src", "kind", "noise_row": device buffers, "seq": last sequence number}
+_plan = _lib.HostCall("lvdgs_map_edit_plan", tag=_lib.EDIT_SEQ, headroom=True)     # the block grows with the map: half as much again when it does
+_outputs = {}     # device index -> {"src", "kind", "noise_row": the plan's device buffers; "block", "scratch": what _plan lends the plan being made}
 INT32_MIN = -2 ** 31
 COPY, ZERO, XYZ, SCALE = _lib.EDIT_COPY, _lib.EDIT_ZERO, _lib.EDIT_XYZ, _lib.EDIT_SCALE
 
@@ -32,23 +33,10 @@ class Plan:
                  "src", "kind", "noise_row", "src_cpu", "n_obs", "n_obs_cpu")
 
 
-def _wait(device):
-    """The one wait of a plan: until everything enqueued on the device's current stream has run."""
-    torch.cuda.current_stream(device).synchronize()
-
-
 def _device_state(device, n, rows):
     """The per-device buffers, grown on demand: the pinned block for 2 ``n`` rows, scratch for ``n``, plan outputs for ``rows``."""
-    L = _lib.lib()
-    st = _state.get(device.index)
-    if st is None:
-        st = _state[device.index] = {"block": None, "scratch": None, "src": None, "kind": None, "noise_row": None, "seq": 0}
-    words = _lib.EDIT_HOST_SRC + 2 * n
-    if st["block"] is None or st["block"].numel() < 4 * words:
-        st["block"] = torch.zeros(4 * max(words + words // 2, 4096), dtype=torch.uint8).pin_memory()
-    need = L.lvdgs_map_edit_scratch_bytes(n)
-    if st["scratch"] is None or st["scratch"].numel() < need:
-        st["scratch"] = _lib.device_bytes(need + need // 2, device)
+    st = _outputs.setdefault(device.index, {"src": None})
+    st["block"], st["scratch"] = _plan.resources(device, 4 * max(_lib.EDIT_HOST_SRC + 2 * n, 4096), _lib.lib().lvdgs_map_edit_scratch_bytes(n))
     if st["src"] is None or st["src"].numel() < rows:
         cap = max(rows + rows // 2, 1024)
         st["src"] = torch.empty(cap, dtype=torch.int32, device=device)
@@ -64,20 +52,13 @@ def _device_of(t):
 
 
 def _run_plan(a, st, device, n, rule):
-    L = _lib.lib()
-    st["seq"] = seq = (st["seq"] % 0x7FFFFFFF) + 1
     block = st["block"]
-    a.num_gaussians, a.seq = n, seq
+    a.num_gaussians = n
     a.src, a.kind, a.noise_row = st["src"].data_ptr(), st["kind"].data_ptr(), st["noise_row"].data_ptr()
     a.capacity = st["src"].numel()
     a.host_state, a.host_bytes = block.data_ptr(), block.numel()
     a.scratch, a.scratch_bytes = st["scratch"].data_ptr(), st["scratch"].numel()
-    with _lib.on_device(device):
-        _lib.check(L.lvdgs_map_edit_plan(C.byref(a), _lib.raw_stream(device)), "lvdgs_map_edit_plan")
-        _wait(device)      # the one wait of the plan
-    words = block.numpy().view(np.int32)
-    if int(words[_lib.EDIT_SEQ]) != seq:
-        raise _lib.LvdgsError(f"lvdgs_map_edit_plan left no state (sequence word {int(words[_lib.EDIT_SEQ])}, expected {seq})")
+    words = _plan.run(device, a)      # the one wait of the plan; a view of the block: what leaves here is copied out of it below
     p = Plan()
     p.mode, p.device, p.n_in, p.scale_dims = a.mode, device, n, a.scale_dims
     p.n_out, p.n_keep, p.n_clone = int(words[_lib.EDIT_N_OUT]), int(words[_lib.EDIT_N_KEEP]), int(words[_lib.EDIT_N_CLONE])

@@ -11,13 +11,12 @@ The subsample is a pure function of (seed, pixel index, validity): the pixels wh
 selects the same pixels.  It is NOT the subset ``numpy.random.Generator.choice`` draws, hence ``GaussianModel.seeding = "fused"`` is
 opt-in.
 """
-import ctypes as C
 import numpy as np
 import torch
 
 from . import _lib
 
-_state = {}     # device index -> [pinned host block, scratch tensor, last sequence number]
+_call = _lib.HostCall("lvdgs_seed_points", tag=_lib.SEED_SEQ)
 _MASK64 = (1 << 64) - 1
 
 
@@ -71,31 +70,20 @@ def seed_points(image, depth, intrinsics, R, T, downsample, seed, *, gain=None, 
     capacity = max(int(H * W * inv), 0)
 
     L = _lib.lib()
-    state = _state.get(device.index)
-    if state is None:
-        state = _state[device.index] = [torch.zeros(_lib.SEED_HOST_BYTES, dtype=torch.uint8).pin_memory(),
-                                        _lib.device_bytes(L.lvdgs_seed_scratch_bytes(W, H), device), 0]
-    block, scratch, _ = state
-    words = block.numpy().view(np.int32)
+    block, scratch = _call.resources(device, _lib.SEED_HOST_BYTES, L.lvdgs_seed_scratch_bytes(W, H))
     out = SeedPoints()
     rows = max(capacity, 1)
     xyz = torch.empty((rows, 3), dtype=torch.float32, device=device)
     rgb = torch.empty((rows, 3), dtype=torch.float32, device=device) if image is not None else None
     f_dc = torch.empty((rows, 3), dtype=torch.float32, device=device) if image is not None else None
     pixel = torch.empty(rows, dtype=torch.int32, device=device)
-    state[2] = seq = (state[2] % 0x7FFFFFFF) + 1
     a = _lib.SeedArgs(width=W, height=H, fx=fx, fy=fy, cx=cx, cy=cy, depth_trunc=float(depth_trunc), want_median=int(bool(want_median)),
-                      inv_downsample=inv, seed=int(seed) & _MASK64, seq=seq, capacity=capacity,
+                      inv_downsample=inv, seed=int(seed) & _MASK64, capacity=capacity,
                       image=None if image is None else image.data_ptr(), gain=None if gain is None else gain.data_ptr(),
                       offset=None if offset is None else offset.data_ptr(), depth=depth.data_ptr(), R=R.data_ptr(), T=T.data_ptr(),
                       xyz=xyz.data_ptr(), rgb=None if rgb is None else rgb.data_ptr(), f_dc=None if f_dc is None else f_dc.data_ptr(),
                       pixel=pixel.data_ptr(), host_state=block.data_ptr(), scratch=scratch.data_ptr(), scratch_bytes=scratch.numel())
-    with _lib.on_device(device):
-        _lib.check(L.lvdgs_seed_points(C.byref(a), _lib.raw_stream(device)), "lvdgs_seed_points")
-        torch.cuda.current_stream(device).synchronize()      # the one wait of the call
-    w = words.copy()
-    if int(w[_lib.SEED_SEQ]) != seq:
-        raise _lib.LvdgsError(f"lvdgs_seed_points left no state (sequence word {int(w[_lib.SEED_SEQ])}, expected {seq})")
+    w = _call.run(device, a).copy()      # the one wait of the call
     out.n_valid, out.n = int(w[_lib.SEED_N_VALID]), int(w[_lib.SEED_N_KEEP])
     out.median_bits = int(w[_lib.SEED_MEDIAN]) & 0xFFFFFFFF
     out.median_depth = float(w[_lib.SEED_MEDIAN:_lib.SEED_MEDIAN + 1].view(np.float32)[0])

@@ -30,7 +30,7 @@ def summarise(depth, opacity, touched=None, rows=(), mask=None, count_mask=None)
     touched = np.zeros(0, np.int32) if touched is None else touched
     pkg = dict(depth=up(depth), opacity=up(opacity), n_touched=up(touched.astype(np.int32)))
     fs = frame_stats.frame_summary(pkg, [up(r) for r in rows], mask=up(mask), count_mask=up(count_mask))
-    block = frame_stats._summary_state[torch.device(DEV, torch.cuda.current_device()).index][0].numpy().copy()
+    block = frame_stats._summary.blocks[torch.device(DEV, torch.cuda.current_device()).index].numpy().copy()
     return fs, block, pkg
 
 

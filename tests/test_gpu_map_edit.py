@@ -340,12 +340,12 @@ def test_pruning_pass(prune_mode, initialized):
 # ---------------------------------------------------------------- 6. one wait, the same bytes twice
 def _count_waits(fn):
     from lvdgs import map_edit
-    calls, real = [], map_edit._wait
-    map_edit._wait = lambda device: (calls.append(device), real(device))[1]
+    calls, real = [], map_edit._plan.wait
+    map_edit._plan.wait = lambda device: (calls.append(device), real(device))[1]
     try:
         fn()
     finally:
-        map_edit._wait = real
+        del map_edit._plan.wait
     return len(calls)
 
 
