@@ -1217,6 +1217,67 @@ int lvdgs_undistort_map(int32_t width, int32_t height, double fx, double fy, dou
                         int32_t *sx, int32_t *sy, void *stream);
 int lvdgs_ingest_frame(const lvdgs_ingest_args *a, void *stream);
 
+/* ---- Frame evaluation: the per-frame block of eval_rendering (reference utils/eval_utils_0806.py:216-312: two boolean masks, four
+ * boolean gathers, two PSNRs, two SSIMs, and a copy of both images and the depth to the host for the 8-bit images it saves) ----
+ * One call per rendered frame, enqueued on the caller's stream: no host wait, no copy.  render, gt_image: 3*height*width float32
+ * (render unclamped, gt_image in [0, 1]); static_mask: height*width bytes (non-0 = static) or NULL; bg: 3 floats or NULL (= 0); depth:
+ * height*width float32 or NULL.  Element by element, for channel c and pixel p, all float32 unless said otherwise, no contraction:
+ *   a = min(max(render, 0), 1);   basic = gt > 0 (per channel element);   keep = basic & (static_mask[p] != 0)
+ *   sum_sq_full = sum over basic of (a - gt) * (a - gt);  n_basic = |basic|;   sum_sq_static, n_keep: the same over keep.
+ *     Each difference and square is float32; the sums are float64, taken per 32x32 tile of a plane by its workgroup (its waves'
+ *     butterfly sums, the waves from 0 up) and then over the workgroups by one finishing workgroup (thread t takes partials t, t + 512,
+ *     ...): a fixed order, no float atomics; the counts are integers.  PSNR is the caller's 10 log10(n / sum).
+ *   ssim_full = mean over the 3*height*width elements of m(a, gt): SSIM as lvdgs_ssim_l1 states it -- 11 taps, sigma 1.5, the float32
+ *     window g[k] = exp(-(k - 5)^2 / 4.5) divided by (float)(the float64 sum of the eleven g[k]) = 3.75923276, which is torch's g.sum(), zero padding, A = w*x, B = w*y, S = w*(x^2 + y^2), Z = w*(xy) by fmaf chains,
+ *     m = ((2AB + C1)(2(Z - AB) + C2)) * (rcp(A^2 + B^2 + C1) * rcp(S - (A^2 + B^2) + C2)), C1 = 0.01^2, C2 = 0.03^2 -- each m float32,
+ *     their sum float64 in the order above, divided by the count in float64.
+ *   ssim_static = the same mean of m(a', gt') with a'[c][p] = keep[c][p] ? a[c][p] : bg[c], gt'[c][p] = keep[c][p] ? gt[c][p] : bg[c]:
+ *     the mask is per channel element, which the single-plane keep_mask of lvdgs_ssim_l1 cannot express.
+ *   static_mask NULL: keep = basic; the static quantities are not computed and the row reports them equal to the full ones.
+ *   depth_min, depth_max: over the frame (fminf / fmaxf; non-finite depth is the caller's precondition and is not handled).
+ * The row (64 bytes, written by the finishing launch to the DEVICE address out_row; the caller owns a table of them and reads it
+ * when it likes):
+ *   double sum_sq_full, sum_sq_static; uint64 n_basic, n_keep; double ssim_full, ssim_static; float depth_min, depth_max (0 without
+ *   depth); uint32 flags (LVDGS_FRAME_EVAL_HAS_MASK, _HAS_DEPTH, _DEPTH_CONSTANT); uint32 reserved (0).
+ * Optional byte outputs (each pointer may be NULL), what the reference hands to Image.fromarray:
+ *   pred8, gt8, residual8: height*width*3 interleaved;  pred8 = (uint8)(a * 255.0f), gt8 = (uint8)(gt * 255.0f), a float32 product
+ *     truncated;  residual8 = |pred8 - gt8|.
+ *   depth8: height*width;  (uint8)(((d - depth_min) / (depth_max - depth_min)) * 255.0f), float32 in that order with an IEEE-rounded
+ *     division.  A third launch of the same call reads the extrema from the row on the device.
+ *   A constant depth map: the reference divides by zero and casts NaN to uint8, which is undefined.  BY DEFINITION the library writes
+ *     depth8 = 0 everywhere and sets LVDGS_FRAME_EVAL_DEPTH_CONSTANT in the row.
+ * Launches: one over 32x32 tiles x 3 planes (sums, counts, both SSIM sums, extrema, colour bytes), the finishing one, and depth8's
+ * when asked for.  scratch: the bytes lvdgs_frame_eval_scratch_bytes gives (0: a size not > 0), no initialisation needed.
+ * out_row and scratch hold doubles: both must be 8-byte aligned.
+ * LVDGS_E_INVALID, before anything is enqueued: args NULL, width or height not > 0, render / gt_image / out_row / scratch NULL, depth8
+ * without depth, scratch too small, out_row or scratch not 8-byte aligned.  LVDGS_E_RANGE: more than 65535 tile rows, or more than
+ * 2^31 - 1 workgroups (tiles x 3). */
+enum { LVDGS_FRAME_EVAL_HAS_MASK = 1, LVDGS_FRAME_EVAL_HAS_DEPTH = 2, LVDGS_FRAME_EVAL_DEPTH_CONSTANT = 4 };
+typedef struct lvdgs_frame_eval_row {
+    double sum_sq_full, sum_sq_static;
+    uint64_t n_basic, n_keep;
+    double ssim_full, ssim_static;
+    float depth_min, depth_max;
+    uint32_t flags;
+    uint32_t reserved;
+} lvdgs_frame_eval_row;
+typedef struct lvdgs_frame_eval_args {
+    int32_t width, height;
+    const float *render;          /* 3*height*width, unclamped                      */
+    const float *gt_image;        /* 3*height*width in [0, 1]                       */
+    const uint8_t *static_mask;   /* height*width, non-0 = static, or NULL          */
+    const float *bg;              /* 3, or NULL: 0                                  */
+    const float *depth;           /* height*width, or NULL                          */
+    void *out_row;                /* device: one lvdgs_frame_eval_row               */
+    uint8_t *pred8;               /* out height*width*3, or NULL                    */
+    uint8_t *gt8;                 /* out height*width*3, or NULL                    */
+    uint8_t *residual8;           /* out height*width*3, or NULL                    */
+    uint8_t *depth8;              /* out height*width, or NULL; needs depth         */
+    void *scratch; size_t scratch_bytes;
+} lvdgs_frame_eval_args;
+size_t lvdgs_frame_eval_scratch_bytes(int32_t width, int32_t height);
+int lvdgs_frame_eval(const lvdgs_frame_eval_args *a, void *stream);
+
 /* ---- diagnostics ---- */
 const char *lvdgs_last_error(void);
 const char *lvdgs_version(void);

@@ -295,6 +295,33 @@ class IngestArgs(C.Structure):
     ]
 
 
+class FrameEvalArgs(C.Structure):
+    """struct lvdgs_frame_eval_args (include/lvdgs.h)."""
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32),
+        ("render", _fp), ("gt_image", _fp), ("static_mask", _fp), ("bg", _fp), ("depth", _fp), ("out_row", _fp),
+        ("pred8", _fp), ("gt8", _fp), ("residual8", _fp), ("depth8", _fp),
+        ("scratch", _fp), ("scratch_bytes", C.c_size_t),
+    ]
+
+
+class FrameEvalRow(C.Structure):
+    """struct lvdgs_frame_eval_row (include/lvdgs.h): what one call leaves at ``out_row``."""
+    _fields_ = [
+        ("sum_sq_full", C.c_double), ("sum_sq_static", C.c_double), ("n_basic", C.c_uint64), ("n_keep", C.c_uint64),
+        ("ssim_full", C.c_double), ("ssim_static", C.c_double), ("depth_min", C.c_float), ("depth_max", C.c_float),
+        ("flags", C.c_uint32), ("reserved", C.c_uint32),
+    ]
+
+
+FRAME_EVAL_ROW_BYTES = 64
+FRAME_EVAL_HAS_MASK, FRAME_EVAL_HAS_DEPTH, FRAME_EVAL_DEPTH_CONSTANT = 1, 2, 4
+# the row as a NumPy record (same offsets as FrameEvalRow)
+FRAME_EVAL_ROW_DTYPE = np.dtype([("sum_sq_full", "<f8"), ("sum_sq_static", "<f8"), ("n_basic", "<u8"), ("n_keep", "<u8"),
+                                 ("ssim_full", "<f8"), ("ssim_static", "<f8"), ("depth_min", "<f4"), ("depth_max", "<f4"),
+                                 ("flags", "<u4"), ("reserved", "<u4")])
+
+
 MAP_OUTSIDE = -2 ** 31     # INT32_MIN in an undistortion map: the destination pixel's source lies outside
 
 
@@ -326,6 +353,7 @@ EXPORTS = (
     "lvdgs_seed_scratch_bytes", "lvdgs_seed_points",
     "lvdgs_map_edit_scratch_bytes", "lvdgs_map_edit_plan", "lvdgs_map_edit_apply",
     "lvdgs_undistort_map", "lvdgs_ingest_frame",
+    "lvdgs_frame_eval_scratch_bytes", "lvdgs_frame_eval",
     "lvdgs_last_error", "lvdgs_version", "lvdgs_profile_enable",
     "lvdgs_profile_reset", "lvdgs_profile_read",
 )
@@ -448,6 +476,9 @@ def lib():
         L.lvdgs_undistort_map.argtypes = [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double),
                                           _fp, _fp, C.c_void_p]
         L.lvdgs_ingest_frame.argtypes = [C.POINTER(IngestArgs), C.c_void_p]
+        L.lvdgs_frame_eval_scratch_bytes.restype = C.c_size_t
+        L.lvdgs_frame_eval_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
+        L.lvdgs_frame_eval.argtypes = [C.POINTER(FrameEvalArgs), C.c_void_p]
         L.lvdgs_profile_enable.argtypes = [C.c_int]
         L.lvdgs_profile_read.argtypes = [C.POINTER(KernelTime), C.c_int]
         _lib = L

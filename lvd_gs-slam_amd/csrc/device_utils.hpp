@@ -65,6 +65,9 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// Minimum over the 64 lanes, valid in every lane: the maximum of the negated values (exact; -inf / +inf seeds keep their meaning).
+__device__ __forceinline__ float wave_min(float v) { return -wave_max(-v); }
+
 // Inclusive prefix sum over the wave's lanes, in every lane (lane 63: the wave's total); lane shifts by 1, 2, ... 32.
 // T: uint32_t, int.  Reached by all 64 lanes.  No LDS, no barrier.
 template <typename T>

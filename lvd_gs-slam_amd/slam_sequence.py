@@ -577,13 +577,14 @@ class SlamSequence:
             out[i] = float((c(cam.R, cam.T) - c(cam.R_gt, cam.T_gt)).norm())
         return out
 
-    def eval_rendering(self, metrics_fn=None):
+    def eval_rendering(self, metrics_fn=None, *, fused=False):
         """``eval_rendering``'s numbers (utils/eval_utils_0806.py:172-306): every NON-keyframe frame rendered from its tracked pose
         against the dataset's image; means of PSNR (and of whatever else ``metrics_fn`` returns: default ``eval_utils.frame_metrics``,
-        which needs the GPU for SSIM)."""
+        which needs the GPU for SSIM).  ``fused``: one ``eval_utils.FrameEvaluator`` over the loop -- one library call per frame, no
+        wait -- and one read of its table at the end (``metrics_fn`` is then not used)."""
         if metrics_fn is None:
             from .eval_utils import frame_metrics as metrics_fn
-        rows = []
+        rows, evaluator = [], None
         for idx in range(0, len(self.cameras) - 1):      # (`end_idx = len(frames) - 1`, :184)
             if idx in self.kf_indices:
                 continue
@@ -594,7 +595,15 @@ class SlamSequence:
             static = getattr(frame, "expanded_static_mask", None)
             if static is None:
                 static = getattr(frame, "static_mask", None)
+            if fused:
+                if evaluator is None:
+                    from .eval_utils import FrameEvaluator
+                    evaluator = FrameEvaluator(pkg["render"].shape[-2], pkg["render"].shape[-1], pkg["render"].device, len(self.cameras))
+                evaluator.add(pkg["render"], gt_image.to(pkg["render"].device), static, self.background)
+                continue
             rows.append(metrics_fn(pkg["render"], gt_image.to(pkg["render"].device), static, self.background))
+        if evaluator is not None:
+            rows = [{k: v for k, v in r.items() if k not in ("depth_min", "depth_max")} for r in evaluator.results()]
         if not rows:
             return {}
         return {k: float(np.mean([r[k] for r in rows if r.get(k) is not None])) for k in rows[0] if any(r.get(k) is not None for r in rows)}

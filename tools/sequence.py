@@ -127,7 +127,7 @@ def directory_sequence(dev, config_path, dataset_path=None, ingest="host", caden
 
 def run_sequence(dev, frames=60, scale=1.0, cadence="reference", fused="auto", idle=10, refine=500, masks=True, seed=0, training=None,
                  window_size=None, on_event=None, geometry="kitti07", pcd_downsample=None, mono_scale_drift=0.0, trajectory=None,
-                 config_path=None, dataset_path=None, ingest="host", **sequence_kwargs):
+                 config_path=None, dataset_path=None, ingest="host", eval_mode="host", **sequence_kwargs):
     torch.manual_seed(seed)
     random.seed(seed)
     if config_path is not None:      # frames from a directory: at most ``frames`` of them
@@ -153,12 +153,17 @@ def run_sequence(dev, frames=60, scale=1.0, cadence="reference", fused="auto", i
     seq.run()
     out = seq.summary()
     out["ate_rmse"] = seq.eval_ate()
-    before = seq.eval_rendering()
+    eval_fused = eval_mode == "fused"      # one FrameEvaluator over the evaluation loop, one read at its end
+    t_eval = time.perf_counter()
+    before = seq.eval_rendering(fused=eval_fused)
+    out["eval_rendering_seconds"] = round(time.perf_counter() - t_eval, 4)
     out["psnr_before_refinement"], out["ssim_before_refinement"] = before.get("psnr"), before.get("ssim")
     out["psnr_static_before_refinement"] = before.get("psnr_static")
     if refine:
         seq.refine(refine)
-        after = seq.eval_rendering()
+        t_eval = time.perf_counter()
+        after = seq.eval_rendering(fused=eval_fused)
+        out["eval_rendering_seconds_after_refinement"] = round(time.perf_counter() - t_eval, 4)
         out["psnr"], out["ssim"], out["psnr_static"] = after.get("psnr"), after.get("ssim"), after.get("psnr_static")
         s = seq.seconds["refinement"]
         out["refinement_ms_per_iteration"] = round(1e3 * s / refine, 4)
@@ -214,6 +219,9 @@ def main():
     ap.add_argument("--map-edit", choices=["host", "fused"], default="host",
                     help="prune_points, densify_and_prune and the pruning pass: GaussianModel's PyTorch statements (default), or one map_edit plan, "
                          "one wait and one launch each (lvdgs_map_edit_plan / lvdgs_map_edit_apply)")
+    ap.add_argument("--eval", choices=["host", "fused"], default="host", dest="eval_mode",
+                    help="eval_rendering's per-frame block: frame_metrics' PyTorch statements with their host waits (default), or one "
+                         "lvdgs_frame_eval call per frame and one read of the table at the end (eval_utils.FrameEvaluator)")
     ap.add_argument("--config", default=None, metavar="YAML",
                     help="run on the dataset this settings file names (lvdgs.config_utils.load_config + lvdgs.dataset.load_dataset) instead of the "
                          "synthetic drive; --frames caps the frames read, --cadence short lays the short schedule over the file's Training block")
@@ -228,14 +236,14 @@ def main():
     ev = (lambda e, s: print(f"  frame {s.counts['frames']:3d} {e:16s} N = {s._n()}", file=sys.stderr)) if a.verbose else None
     out, _ = run_sequence(dev, a.frames, a.scale, a.cadence, False if a.no_fused else "auto", a.idle, a.refine, not a.no_masks, seed=a.seed,
                           window_size=a.window_size, on_event=ev, geometry=a.geometry, pcd_downsample=a.pcd_downsample,
-                          mono_scale_drift=a.mono_scale_drift, **({"keyframe_depth": "patch_align"} if a.keyframe_depth == "patch_align" else {}),
+                          mono_scale_drift=a.mono_scale_drift, eval_mode=a.eval_mode, **({"keyframe_depth": "patch_align"} if a.keyframe_depth == "patch_align" else {}),
                           **({"pose_init": a.pose_init} if a.pose_init else {}), **({"matcher": "descriptors"} if a.matcher == "descriptors" else {}),
                           **({"scale_remedy": "matches"} if a.scale_remedy == "matches" else {}),
                           **({"frame_stats": "fused"} if a.frame_stats == "fused" else {}), **({"edge_mask": "fused"} if a.edge_mask == "fused" else {}),
                           **({"dynamic_masks": "detections"} if a.dynamic_masks == "detections" else {}),
                           **({"seeding": "fused"} if a.seeding == "fused" else {}), **({"map_edit": "fused"} if a.map_edit == "fused" else {}),
                           **({"config_path": a.config, "dataset_path": a.dataset_path, "ingest": a.ingest} if a.config else {}))
-    out.update(frame_stats=a.frame_stats, edge_mask=a.edge_mask, dynamic_masks=a.dynamic_masks, seeding=a.seeding, map_edit=a.map_edit)
+    out.update(frame_stats=a.frame_stats, edge_mask=a.edge_mask, dynamic_masks=a.dynamic_masks, seeding=a.seeding, map_edit=a.map_edit, eval=a.eval_mode)
     for rec in out.get("pose_init", []):
         print("  frame {frame:3d} kf {keyframe:3d} inliers {inl:>5} init error {e:.4f} ({r:.3f} deg; previous pose {p:.4f}) tracking iterations {it}".format(
             frame=rec["frame"], keyframe=rec["keyframe"], inl=rec.get("inliers", "-"), e=rec["init_translation_error"], r=rec["init_rotation_error_deg"],
