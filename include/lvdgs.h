@@ -1217,6 +1217,30 @@ int lvdgs_undistort_map(int32_t width, int32_t height, double fx, double fy, dou
                         int32_t *sx, int32_t *sy, void *stream);
 int lvdgs_ingest_frame(const lvdgs_ingest_args *a, void *stream);
 
+/* ---- a depth file's samples to the float32 plane (reference utils/dataset.py :331-335: the first channel of the depth and mono-depth
+ * files divided by depth_scale and depth_scale * 5 as float64 arrays on the host; every consumer then casts to float32 and uploads) ----
+ * out[v][u] = (float)((double)sample / divisor): the float64 division followed by the cast, as lvdgs.dataset.convert_depth_host
+ * states it on the host.  The sample of pixel (u, v) lies at src + v * src_row_bytes + u * pixel_stride: an unsigned byte
+ * (LVDGS_DEPTH_SAMPLE_BYTE) or an unsigned 16-bit word in the machine's byte order (LVDGS_DEPTH_SAMPLE_WORD).  pixel_stride is in
+ * bytes: 1 for a byte plane, 3 for the first channel of a frame's colour bytes already on the device (a dataset whose depth path is
+ * its colour path), 2 for a 16-bit plane; any stride not below the sample's size is taken.  The call reads no byte outside the
+ * height rows of width * pixel_stride bytes each, and writes height*width floats without a row gap.  One launch, no host wait, no
+ * copy; out needs float alignment only (16-byte stores are used where it has 16).  Two calls give the same bytes.
+ * LVDGS_E_INVALID, before anything is enqueued: args / src / out NULL, width or height not > 0, a divisor that is zero or not
+ * finite, an unknown sample_type, pixel_stride below the sample's size, src_row_bytes < width * pixel_stride, and for 16-bit samples
+ * an odd src, an odd src_row_bytes or an odd pixel_stride.  LVDGS_E_RANGE: a raster beyond 2^31 workgroups. */
+enum { LVDGS_DEPTH_SAMPLE_BYTE = 1, LVDGS_DEPTH_SAMPLE_WORD = 2 };
+typedef struct lvdgs_ingest_depth_args {
+    int32_t width, height;
+    const void *src;              /* device: height rows of src_row_bytes           */
+    int32_t sample_type;          /* LVDGS_DEPTH_SAMPLE_*                           */
+    int32_t pixel_stride;         /* bytes from one pixel's sample to the next      */
+    int64_t src_row_bytes;
+    double divisor;
+    float *out;                   /* out height*width                               */
+} lvdgs_ingest_depth_args;
+int lvdgs_ingest_depth(const lvdgs_ingest_depth_args *a, void *stream);
+
 /* ---- Frame evaluation: the per-frame block of eval_rendering (reference utils/eval_utils_0806.py:216-312: two boolean masks, four
  * boolean gathers, two PSNRs, two SSIMs, and a copy of both images and the depth to the host for the 8-bit images it saves) ----
  * One call per rendered frame, enqueued on the caller's stream: no host wait, no copy.  render, gt_image: 3*height*width float32

@@ -295,6 +295,14 @@ class IngestArgs(C.Structure):
     ]
 
 
+class IngestDepthArgs(C.Structure):
+    """struct lvdgs_ingest_depth_args (include/lvdgs.h)."""
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32), ("src", _fp), ("sample_type", C.c_int32), ("pixel_stride", C.c_int32),
+        ("src_row_bytes", C.c_int64), ("divisor", C.c_double), ("out", _fp),
+    ]
+
+
 class FrameEvalArgs(C.Structure):
     """struct lvdgs_frame_eval_args (include/lvdgs.h)."""
     _fields_ = [
@@ -322,6 +330,7 @@ FRAME_EVAL_ROW_DTYPE = np.dtype([("sum_sq_full", "<f8"), ("sum_sq_static", "<f8"
                                  ("flags", "<u4"), ("reserved", "<u4")])
 
 
+DEPTH_SAMPLE_BYTE, DEPTH_SAMPLE_WORD = 1, 2     # lvdgs_ingest_depth_args.sample_type
 MAP_OUTSIDE = -2 ** 31     # INT32_MIN in an undistortion map: the destination pixel's source lies outside
 
 
@@ -352,7 +361,7 @@ EXPORTS = (
     "lvdgs_dynamic_mask_state_bytes", "lvdgs_dynamic_mask_scratch_bytes", "lvdgs_dynamic_mask",
     "lvdgs_seed_scratch_bytes", "lvdgs_seed_points",
     "lvdgs_map_edit_scratch_bytes", "lvdgs_map_edit_plan", "lvdgs_map_edit_apply",
-    "lvdgs_undistort_map", "lvdgs_ingest_frame",
+    "lvdgs_undistort_map", "lvdgs_ingest_frame", "lvdgs_ingest_depth",
     "lvdgs_frame_eval_scratch_bytes", "lvdgs_frame_eval",
     "lvdgs_last_error", "lvdgs_version", "lvdgs_profile_enable",
     "lvdgs_profile_reset", "lvdgs_profile_read",
@@ -476,6 +485,7 @@ def lib():
         L.lvdgs_undistort_map.argtypes = [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double),
                                           _fp, _fp, C.c_void_p]
         L.lvdgs_ingest_frame.argtypes = [C.POINTER(IngestArgs), C.c_void_p]
+        L.lvdgs_ingest_depth.argtypes = [C.POINTER(IngestDepthArgs), C.c_void_p]
         L.lvdgs_frame_eval_scratch_bytes.restype = C.c_size_t
         L.lvdgs_frame_eval_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
         L.lvdgs_frame_eval.argtypes = [C.POINTER(FrameEvalArgs), C.c_void_p]

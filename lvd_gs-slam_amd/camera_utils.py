@@ -29,6 +29,7 @@ class Camera(nn.Module):
         self.T = torch.zeros(3, device=device)
         self.R_gt, self.T_gt = gt_T[:3, :3], gt_T[:3, 3]
         self.original_image, self.depth, self.mono_depth = color, depth, mono_depth
+        self.depth32 = None      # `depth` as a float32 plane on the device, when the dataset made one (init_from_dataset)
         self.grad_mask = None
         self.fx, self.fy, self.cx, self.cy = fx, fy, cx, cy
         self.FoVx, self.FoVy = fovx, fovy
@@ -44,10 +45,17 @@ class Camera(nn.Module):
     # ---- constructors the front end uses --------------------------------------------------------
     @staticmethod
     def init_from_dataset(dataset, idx, projection_matrix):
-        color, depth, pose, mono_depth = dataset[idx]
-        return Camera(idx, color, depth, mono_depth, pose, projection_matrix, dataset.fx, dataset.fy,
-                      dataset.cx, dataset.cy, dataset.fovx, dataset.fovy, dataset.height,
-                      dataset.width, device=dataset.device)
+        # a dataset with `frame` (lvdgs.dataset) hands out the record: the same 4-tuple and, with planes="device", the float32 planes
+        # beside it -- depth32 for the seeding, mono_depth32 as the cached device copy slam_utils._mono_depth would upload
+        record = dataset.frame(idx) if hasattr(dataset, "frame") else None
+        color, depth, pose, mono_depth = dataset[idx] if record is None else record.frame
+        cam = Camera(idx, color, depth, mono_depth, pose, projection_matrix, dataset.fx, dataset.fy,
+                     dataset.cx, dataset.cy, dataset.fovx, dataset.fovy, dataset.height,
+                     dataset.width, device=dataset.device)
+        if record is not None and record.mono_depth32 is not None:
+            cam.depth32 = record.depth32
+            cam._lvdgs_mono_depth = (mono_depth, record.mono_depth32[None])
+        return cam
 
     @staticmethod
     def init_from_gui(uid, T, FoVx, FoVy, fx, fy, cx, cy, H, W, device="cuda:0"):
@@ -117,5 +125,5 @@ class Camera(nn.Module):
         self.grad_mask = mag
 
     def clean(self):
-        for name in ("original_image", "depth", "grad_mask") + _POSE_PARAMS + _EXPOSURE_PARAMS:
+        for name in ("original_image", "depth", "depth32", "grad_mask") + _POSE_PARAMS + _EXPOSURE_PARAMS:
             setattr(self, name, None)

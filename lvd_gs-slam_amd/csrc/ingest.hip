@@ -3,6 +3,9 @@
 //   lvdgs_undistort_map : the fixed-point undistortion map of a calibration, once per dataset (cv2.initUndistortRectifyMap's model)
 //   lvdgs_ingest_frame  : H x W x 3 bytes -> the bilinear remap through that map (optional) -> 3 x H x W float32 = byte / 255, and the
 //                         remapped bytes when asked for.  One launch each, no host wait, no copy.
+//   lvdgs_ingest_depth  : a depth file's 8- or 16-bit samples (a plane of their own, or the first channel of the colour bytes already
+//                         on the device) -> the H x W float32 plane = (float)((double)sample / divisor).  One launch; 1..3 B read and
+//                         4 B written per pixel, the same flat groups of four.
 // Semantics: include/lvdgs.h, DESIGN.md section 4k.  Parity of the remap with the real cv2.remap is UNPINNED (OpenCV is not installed
 // where this was written): the rule is the one the header states, in integers.
 //
@@ -157,6 +160,64 @@ __global__ void __launch_bounds__(ING_THREADS) ingest_kernel(IngestParams P) {
     }
 }
 
+struct DepthParams {
+    int W;
+    int64_t P;                 // W * H
+    const uint8_t *src;
+    int64_t pitch;             // src_row_bytes
+    int stride;                // bytes between the samples of neighbouring pixels
+    double divisor;
+    float *out;
+    int src_vec;               // the samples of a full group are one aligned load: a dword (bytes) or two (16-bit words)
+    int src_dwords;            // stride 3, rows without a gap, dword-aligned base: three dword loads per full group
+    int out_vec;               // 16-byte stores for full groups
+};
+
+__device__ __forceinline__ float depth_value(uint32_t sample, double divisor) { return (float)((double)sample / divisor); }
+
+// grid: one thread per ING_PIXELS consecutive pixels of the flat raster; WORD: 16-bit samples, else bytes
+template <bool WORD>
+__global__ void __launch_bounds__(ING_THREADS) ingest_depth_kernel(DepthParams P) {
+    const int64_t p0 = ((int64_t)blockIdx.x * ING_THREADS + threadIdx.x) * ING_PIXELS;
+    if (p0 >= P.P) return;
+    const int n = P.P - p0 < ING_PIXELS ? (int)(P.P - p0) : ING_PIXELS;
+    const bool full = n == ING_PIXELS;
+    uint32_t s[ING_PIXELS] = {0u, 0u, 0u, 0u};
+    if (full && P.src_vec) {                       // rows without a gap, stride == the sample's size: the group is contiguous
+        if constexpr (WORD) {
+            const uint2 w = *reinterpret_cast<const uint2 *>(P.src + 2 * p0);
+            s[0] = w.x & 0xffffu; s[1] = w.x >> 16; s[2] = w.y & 0xffffu; s[3] = w.y >> 16;
+        } else {
+            const uint32_t w = *reinterpret_cast<const uint32_t *>(P.src + p0);
+            s[0] = w & 255u; s[1] = (w >> 8) & 255u; s[2] = (w >> 16) & 255u; s[3] = w >> 24;
+        }
+    } else if (!WORD && full && P.src_dwords) {    // the first of every three bytes: bytes 0, 3, 6, 9 of twelve
+        const uint32_t *q = reinterpret_cast<const uint32_t *>(P.src + 3 * p0);
+        const uint32_t w0 = q[0], w1 = q[1], w2 = q[2];
+        s[0] = w0 & 255u; s[1] = w0 >> 24; s[2] = (w1 >> 16) & 255u; s[3] = (w2 >> 8) & 255u;
+    } else {
+        int64_t v = p0 / P.W;
+        int u = (int)(p0 - v * P.W);
+#pragma unroll
+        for (int k = 0; k < ING_PIXELS; k++) {
+            if (k < n) {
+                const uint8_t *q = P.src + v * P.pitch + (int64_t)u * P.stride;
+                s[k] = WORD ? (uint32_t)*reinterpret_cast<const uint16_t *>(q) : (uint32_t)*q;
+                if (++u == P.W) { u = 0; v++; }
+            }
+        }
+    }
+    float *dst = P.out + p0;
+    if (full && P.out_vec) {
+        *reinterpret_cast<float4 *>(dst) = make_float4(depth_value(s[0], P.divisor), depth_value(s[1], P.divisor),
+                                                       depth_value(s[2], P.divisor), depth_value(s[3], P.divisor));
+    } else {
+#pragma unroll
+        for (int k = 0; k < ING_PIXELS; k++)
+            if (k < n) dst[k] = depth_value(s[k], P.divisor);
+    }
+}
+
 inline bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 }  // namespace
@@ -208,6 +269,41 @@ int lvdgs_ingest_frame(const lvdgs_ingest_args *a, void *stream) {
     if (a->map_sx) hipLaunchKernelGGL(ingest_kernel<true>, dim3(cdiv(groups, ING_THREADS)), dim3(ING_THREADS), 0, s, P);
     else hipLaunchKernelGGL(ingest_kernel<false>, dim3(cdiv(groups, ING_THREADS)), dim3(ING_THREADS), 0, s, P);
     LVDGS_LAUNCH_CHECK("ingest_frame", 0, s);
+    return LVDGS_OK;
+}
+
+int lvdgs_ingest_depth(const lvdgs_ingest_depth_args *a, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!a) { set_error("ingest_depth: args is NULL"); return LVDGS_E_INVALID; }
+    if (a->width <= 0 || a->height <= 0) { set_error("ingest_depth: bad image size %dx%d", a->width, a->height); return LVDGS_E_INVALID; }
+    if (!a->src || !a->out) { set_error("ingest_depth: src / out is NULL"); return LVDGS_E_INVALID; }
+    if (!(a->divisor != 0.0) || !isfinite(a->divisor)) { set_error("ingest_depth: the divisor must be finite and not zero"); return LVDGS_E_INVALID; }
+    if (a->sample_type != LVDGS_DEPTH_SAMPLE_BYTE && a->sample_type != LVDGS_DEPTH_SAMPLE_WORD) {
+        set_error("ingest_depth: unknown sample_type %d", a->sample_type); return LVDGS_E_INVALID;
+    }
+    const bool word = a->sample_type == LVDGS_DEPTH_SAMPLE_WORD;
+    const int size = word ? 2 : 1;
+    if (a->pixel_stride < size) { set_error("ingest_depth: pixel_stride %d below the sample's %d bytes", a->pixel_stride, size); return LVDGS_E_INVALID; }
+    if (a->src_row_bytes < (int64_t)a->width * a->pixel_stride) {
+        set_error("ingest_depth: src_row_bytes %lld below width * pixel_stride = %lld", (long long)a->src_row_bytes, (long long)a->width * a->pixel_stride);
+        return LVDGS_E_INVALID;
+    }
+    if (word && (!aligned(a->src, 2) || a->src_row_bytes % 2 != 0 || a->pixel_stride % 2 != 0)) {
+        set_error("ingest_depth: 16-bit samples need an even src, src_row_bytes and pixel_stride"); return LVDGS_E_INVALID;
+    }
+    DepthParams P{};
+    P.W = a->width; P.P = (int64_t)a->width * a->height;
+    const int64_t groups = (P.P + ING_PIXELS - 1) / ING_PIXELS;
+    if (groups > (int64_t)INT32_MAX * ING_THREADS) { set_error("ingest_depth: %dx%d is too large a raster", a->width, a->height); return LVDGS_E_RANGE; }
+    P.src = static_cast<const uint8_t *>(a->src); P.pitch = a->src_row_bytes; P.stride = a->pixel_stride; P.divisor = a->divisor; P.out = a->out;
+    const bool gapless = a->src_row_bytes == (int64_t)a->width * a->pixel_stride;
+    P.src_vec = gapless && a->pixel_stride == size && aligned(a->src, 4 * size);
+    P.src_dwords = !word && gapless && a->pixel_stride == 3 && aligned(a->src, 4);
+    P.out_vec = aligned(a->out, 16);
+    ProfScope ps("ingest_depth", s);
+    if (word) hipLaunchKernelGGL(ingest_depth_kernel<true>, dim3(cdiv(groups, ING_THREADS)), dim3(ING_THREADS), 0, s, P);
+    else hipLaunchKernelGGL(ingest_depth_kernel<false>, dim3(cdiv(groups, ING_THREADS)), dim3(ING_THREADS), 0, s, P);
+    LVDGS_LAUNCH_CHECK("ingest_depth", 0, s);
     return LVDGS_OK;
 }
 

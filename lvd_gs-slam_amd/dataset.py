@@ -16,6 +16,10 @@ over the bus for a 1920 x 1280 frame, no float64 frame on the host.  Both give t
 include/lvdgs.h.  Parity of the undistortion with the real ``cv2.remap`` is UNPINNED (OpenCV is not installed
 where this was written).
 
+``__getitem__`` is ``assemble(read(idx))``, a host half and a device half, so that ``FramePrefetcher`` can run the host half of the next
+frames on worker threads while the loops work (the reference's loader is serial); ``planes="device"`` also makes the float32 depth
+planes on the device (``lvdgs_ingest_depth``) and hands them to the loops beside the host arrays.  Both are opt-in.
+
 Deviations from the reference: ``device`` is a keyword (default ``"cuda:0"``), not hard-coded; a calibration without ``depth_scale``
 raises ``ValueError`` at construction (the reference hits an unbound name in ``__getitem__``); a colour file that does not decode to
 three 8-bit channels is refused; the RealSense live class is out of scope."""
@@ -23,6 +27,8 @@ import ctypes as C
 import glob
 import json
 import os
+import queue
+import threading
 
 import numpy as np
 import torch
@@ -77,6 +83,15 @@ def convert_host(image):
     return np.ascontiguousarray((image.astype(np.float64) / 255.0).astype(np.float32).transpose(2, 0, 1))
 
 
+def convert_depth_host(samples, divisor):
+    """uint8 / uint16 samples -> float32: (float)((double)sample / divisor), the arithmetic of ``lvdgs_ingest_depth`` (include/lvdgs.h).
+    It is the reference's float64 division followed by the cast to float32 every consumer of a depth plane applies."""
+    samples = np.asarray(samples)
+    if samples.dtype not in (np.uint8, np.uint16):
+        raise ValueError(f"convert_depth_host: samples must be uint8 or uint16, got {samples.dtype}")
+    return (samples.astype(np.float64) / float(divisor)).astype(np.float32)
+
+
 # ---- the device entry points ----
 def _gpu(device, what):
     device = torch.device(device)
@@ -122,6 +137,31 @@ def ingest_frame(src, sx=None, sy=None, *, want_u8=False):
     with _lib.on_device(device):
         _lib.check(_lib.lib().lvdgs_ingest_frame(C.byref(a), _lib.raw_stream(device)), "lvdgs_ingest_frame")
     return (image, u8) if want_u8 else image
+
+
+_WORD_DTYPES = tuple(d for d in (torch.int16, getattr(torch, "uint16", None)) if d is not None)
+
+
+def ingest_depth(src, divisor):
+    """One ``lvdgs_ingest_depth`` call: ``src`` (H, W) on a GPU, uint8 or 16-bit (int16 is read as unsigned: the bits of a uint16 file) --
+    a view with a pixel and a row stride is taken as it is, e.g. ``frame[:, :, 0]`` of a frame's colour bytes -- and the divisor -> the
+    (H, W) float32 plane ``(float)((double)sample / divisor)``.  No host wait, no copy."""
+    if not torch.is_tensor(src) or not src.is_cuda or (src.dtype is not torch.uint8 and src.dtype not in _WORD_DTYPES):
+        raise _lib.LvdgsError("ingest_depth: src must be a uint8 or 16-bit integer tensor on a GPU (there is no CPU path)")
+    if src.ndim != 2 or src.shape[0] < 1 or src.shape[1] < 1:
+        raise ValueError(f"ingest_depth: src must be (H, W) with H, W > 0, got {tuple(src.shape)}")
+    H, W = int(src.shape[0]), int(src.shape[1])
+    size = src.element_size()
+    if (W > 1 and src.stride(1) < 1) or (H > 1 and src.stride(0) < W * max(src.stride(1), 1)):
+        src = src.contiguous()
+    stride = size * int(src.stride(1)) if W > 1 else size
+    pitch = size * int(src.stride(0)) if H > 1 else W * stride
+    out = torch.empty((H, W), dtype=torch.float32, device=src.device)
+    a = _lib.IngestDepthArgs(width=W, height=H, src=src.data_ptr(), sample_type=_lib.DEPTH_SAMPLE_BYTE if size == 1 else _lib.DEPTH_SAMPLE_WORD,
+                             pixel_stride=stride, src_row_bytes=pitch, divisor=float(divisor), out=out.data_ptr())
+    with _lib.on_device(src.device):
+        _lib.check(_lib.lib().lvdgs_ingest_depth(C.byref(a), _lib.raw_stream(src.device)), "lvdgs_ingest_depth")
+    return out
 
 
 # ---- parsers: which files make a sequence, and the world-to-camera pose of each frame ----
@@ -288,14 +328,43 @@ def _first_channel(array):
     return array[:, :, 0] if array.ndim == 3 else array
 
 
-class MonocularDataset(BaseDataset):
-    """Calibration, the undistortion map and ``__getitem__`` (utils/dataset.py:263-344); the subclasses say which files."""
+class FrameRecord:
+    """One frame between ``MonocularDataset.read`` and ``assemble``.  ``read`` fills the host half: ``raw`` (H, W, 3) uint8, ``depth`` and
+    ``mono_depth`` (the float64 arrays of the 4-tuple), ``pose`` (the float64 matrix, a host array) and, for ``planes="device"``, the
+    files' own samples (``depth_samples`` / ``mono_samples``: None where the path is the colour path; the same array where both paths
+    are one file).  ``assemble`` adds ``frame`` (the 4-tuple ``dataset[idx]`` returns) and the (H, W) float32 device planes ``depth32``
+    / ``mono_depth32`` (None with ``planes="host"``)."""
+    __slots__ = ("idx", "raw", "depth", "mono_depth", "pose", "depth_samples", "mono_samples", "frame", "depth32", "mono_depth32", "ready")
 
-    def __init__(self, args, path, config, *, device="cuda:0", ingest="host"):
+    def __init__(self, idx, raw, depth, mono_depth, pose, depth_samples=None, mono_samples=None):
+        self.idx, self.raw, self.depth, self.mono_depth, self.pose = idx, raw, depth, mono_depth, pose
+        self.depth_samples, self.mono_samples = depth_samples, mono_samples
+        self.frame = self.depth32 = self.mono_depth32 = None
+        self.ready = None       # FramePrefetcher: the event after this frame's work on its side stream
+
+
+def _upload(array, device):
+    return torch.from_numpy(array).to(device)
+
+
+class MonocularDataset(BaseDataset):
+    """Calibration, the undistortion map and ``__getitem__`` (utils/dataset.py:263-344); the subclasses say which files.
+
+    ``__getitem__`` is ``assemble(read(idx))``: ``read`` is the host half (decodes, the two float64 divisions; callable from any thread,
+    it writes nothing shared), ``assemble`` the device half (the upload, ``ingest_image``, the pose tensor).  ``planes="device"``
+    (needs ``ingest="fused"``): ``assemble`` also makes the float32 planes ``depth32`` / ``mono_depth32`` on the device by
+    ``lvdgs_ingest_depth`` -- from the colour bytes already there for a placeholder path, else from the file's 8- or 16-bit samples,
+    uploaded once -- and ``frame(idx)`` returns the record that carries them beside the unchanged 4-tuple."""
+
+    def __init__(self, args, path, config, *, device="cuda:0", ingest="host", planes="host"):
         super().__init__(args, path, config, device=device)
         if ingest not in ("host", "fused"):
             raise ValueError(f"ingest: 'host' or 'fused', got {ingest!r}")
-        self.ingest = ingest
+        if planes not in ("host", "device"):
+            raise ValueError(f"planes: 'host' or 'device', got {planes!r}")
+        if planes == "device" and ingest != "fused":
+            raise ValueError("planes='device' needs ingest='fused': the planes are made from bytes that mode puts on the device")
+        self.ingest, self.planes = ingest, planes
         cal = config["Dataset"]["Calibration"]
         self.fx, self.fy, self.cx, self.cy = cal["fx"], cal["fy"], cal["cx"], cal["cy"]
         self.width, self.height = cal["width"], cal["height"]
@@ -336,17 +405,21 @@ class MonocularDataset(BaseDataset):
         """First channel of a depth file."""
         return _first_channel(np.array(Image.open(path)))
 
-    def ingest_image(self, raw, want_u8=False):
+    def ingest_image(self, raw, want_u8=False, *, src=None):
         """(H, W, 3) uint8 on the host -> the frame's (3, H, W) float32 tensor on ``device`` (with ``want_u8``: and the bytes after the
-        undistortion, on ``device``), by this dataset's mode."""
+        undistortion, on ``device``), by this dataset's mode.  ``src``: fused mode, ``raw`` already on the device."""
         sx, sy = self.undistort_map() if self.disorted else (None, None)
         if self.ingest == "fused":
-            return ingest_frame(torch.from_numpy(raw).to(_gpu(self.device, "ingest='fused'")), sx, sy, want_u8=want_u8)
+            if src is None:
+                src = _upload(raw, _gpu(self.device, "ingest='fused'"))
+            return ingest_frame(src, sx, sy, want_u8=want_u8)
         u8 = remap_host(raw, sx, sy) if self.disorted else raw
         image = torch.from_numpy(convert_host(u8)).to(device=self.device, dtype=self.dtype)
         return (image, torch.from_numpy(u8).to(self.device)) if want_u8 else image
 
-    def __getitem__(self, idx):
+    def read(self, idx):
+        """The host half of a frame -> a ``FrameRecord``: every file decoded once, the two float64 divisions.  No device call, nothing
+        shared is written: any thread may call it."""
         color_path = self.color_paths[idx]
         raw = self.decode_color(color_path)
         depth_path, mono_path = self.depth_paths[idx], self.mono_depth_paths[idx]
@@ -354,9 +427,47 @@ class MonocularDataset(BaseDataset):
         mono_src = raw[:, :, 0] if mono_path == color_path else (depth_src if mono_path == depth_path else self.load_image(mono_path))
         depth = depth_src / self.depth_scale
         mono_depth = mono_src / (self.depth_scale * 5)
-        image = self.ingest_image(raw)
-        pose = torch.from_numpy(self.poses[idx]).to(device=self.device)
-        return image, depth, pose, mono_depth
+        rec = FrameRecord(idx, raw, depth, mono_depth, self.poses[idx])
+        if self.planes == "device":
+            for src in (depth_src, mono_src):
+                if src.dtype not in (np.uint8, np.uint16):
+                    raise ValueError(f"frame {idx}: planes='device' takes 8- or 16-bit depth files, this one decodes to {src.dtype}")
+            if depth_path != color_path:
+                rec.depth_samples = np.ascontiguousarray(depth_src)
+            if mono_path != color_path:
+                rec.mono_samples = rec.depth_samples if mono_path == depth_path else np.ascontiguousarray(mono_src)
+        return rec
+
+    def assemble(self, rec, upload=None):
+        """The device half of a frame: ``read``'s record -> the 4-tuple (also kept as ``rec.frame``).  ``upload(host array) -> device
+        tensor`` replaces the plain copy of fused mode (``FramePrefetcher``: its pinned ring)."""
+        if self.planes == "device" or (self.ingest == "fused" and upload is not None):
+            dev = _gpu(self.device, "ingest='fused'")
+            put = upload if upload is not None else (lambda a: _upload(a, dev))
+            src = put(rec.raw)
+            image = self.ingest_image(rec.raw, src=src)
+            if self.planes == "device":
+                # a 16-bit plane travels as int16: the same bits, a dtype every torch copy takes
+                words = lambda a: a.view(np.int16) if a.dtype == np.uint16 else a
+                ds = src[:, :, 0] if rec.depth_samples is None else put(words(rec.depth_samples))
+                ms = src[:, :, 0] if rec.mono_samples is None else (ds if rec.mono_samples is rec.depth_samples else put(words(rec.mono_samples)))
+                rec.depth32 = ingest_depth(ds, self.depth_scale)
+                rec.mono_depth32 = ingest_depth(ms, self.depth_scale * 5)
+        else:
+            image = self.ingest_image(rec.raw)
+        # (through `upload` the pose goes the frame's way: a plain copy from pageable memory would wait for the stream)
+        pose = torch.from_numpy(rec.pose).to(device=self.device) if upload is None else upload(np.ascontiguousarray(rec.pose))
+        rec.frame = (image, rec.depth, pose, rec.mono_depth)
+        return rec.frame
+
+    def frame(self, idx):
+        """``dataset[idx]`` as a record: ``frame(idx).frame`` is that 4-tuple, ``depth32`` / ``mono_depth32`` the device planes."""
+        rec = self.read(idx)
+        self.assemble(rec)
+        return rec
+
+    def __getitem__(self, idx):
+        return self.assemble(self.read(idx))
 
 
 class dl3dvDataset(MonocularDataset):
@@ -392,9 +503,202 @@ class ReplicaDataset(MonocularDataset):
 _TYPES = {"tum": TUMDataset, "replica": ReplicaDataset, "waymo": WaymoDataset, "KITTI": KITTIDataset, "dl3dv": dl3dvDataset}
 
 
-def load_dataset(args, path, config, *, device="cuda:0", ingest="host"):
+def load_dataset(args, path, config, *, device="cuda:0", ingest="host", planes="host"):
     """The dataset of ``config["Dataset"]["type"]`` (utils/dataset.py:404-416)."""
     kind = config["Dataset"]["type"]
     if kind not in _TYPES:
         raise ValueError(f"Unknown dataset type {kind!r}: one of {sorted(_TYPES)}")
-    return _TYPES[kind](args, path, config, device=device, ingest=ingest)
+    return _TYPES[kind](args, path, config, device=device, ingest=ingest, planes=planes)
+
+
+# ---- frames read ahead of the loops ----
+PREFETCH_WORKERS = 4         # the default: PIL's decoders release the interpreter lock and four threads read about three times the frames
+                             # of one (profiles/ingest_prefetch.json); a constant, never taken from the machine's CPU count
+PREFETCH_MAX_WORKERS = 16
+
+
+class _Pending:
+    """One frame on its way through a worker: ``done`` is set once ``record`` or ``error`` is."""
+    __slots__ = ("done", "record", "error")
+
+    def __init__(self):
+        self.done, self.record, self.error = threading.Event(), None, None
+
+
+class FramePrefetcher:
+    """Reads the frames of ``dataset`` ahead of the loop that consumes them.  ``order`` is the sequence of indices the consumer will
+    ask for; ``workers`` daemon threads run ``dataset.read`` (host only: decode and the float64 divisions) for at most ``depth`` frames
+    beyond the one last taken; ``take(idx)`` returns what ``dataset[idx]`` returns (``frame(idx)``: the record, with the device planes).
+    It stands where a dataset stands: ``len()``, ``[idx]``, and every other attribute is the dataset's.
+
+    Threads and the device.  A worker makes no HIP and no torch-device call; every upload and launch is made by the thread that calls
+    ``take``.  With ``ingest="fused"`` on a GPU that thread, while it hands out frame i, also enqueues the upload and ingest of frames
+    whose decode has finished on ONE side stream, from a small ring of pinned buffers (a slot is reused only once the event after its
+    copy has completed; with no slot free the frame waits for its own turn and takes the plain copy of ``dataset[idx]``).  The
+    consumer's stream takes the frame over with ``wait_event`` and every tensor handed out is marked ``record_stream`` for it.
+    ``take`` never synchronises.  In host mode ``assemble`` runs at the frame's turn, as ``dataset[idx]`` does.
+
+    A worker's exception is raised by ``take`` at that frame's turn, as it was raised; the frames after it stay available.  A ``take``
+    out of ``order`` is a direct ``dataset`` read.  A wait for a worker ends after ``timeout`` seconds with ``TimeoutError``.
+    ``close()`` (or leaving the ``with`` block) stops and joins the workers."""
+
+    def __init__(self, dataset, order, depth=3, workers=PREFETCH_WORKERS, timeout=120.0):
+        if int(depth) < 1:
+            raise ValueError(f"FramePrefetcher: depth must be at least 1, got {depth}")
+        if int(workers) < 1:
+            raise ValueError(f"FramePrefetcher: workers must be at least 1, got {workers}")
+        workers = min(int(workers), PREFETCH_MAX_WORKERS)            # capped: more decode threads than this only contend
+        if not all(callable(getattr(dataset, name, None)) for name in ("read", "assemble", "frame")):
+            raise TypeError("FramePrefetcher: the dataset must split a frame into read / assemble (lvdgs.dataset.MonocularDataset)")
+        self.dataset, self.order, self.depth, self.timeout = dataset, list(order), int(depth), float(timeout)
+        self._cursor = 0              # position in `order` of the next frame in turn
+        self._submitted = 0           # positions below this have been given to the workers
+        self._pending = {}            # position -> _Pending
+        self._todo = queue.Queue()
+        self._stop = threading.Event()
+        self._closed = False
+        self._side = self._consumer_device = None
+        self._ring, self._ring_slots = [], 4 * (self.depth + 1)      # colour, two planes and the pose of every frame in flight
+        if getattr(dataset, "disorted", False):
+            dataset.undistort_map()                                  # made here, before the first worker starts
+        if getattr(dataset, "ingest", "host") == "fused" and torch.device(dataset.device).type == "cuda" and torch.cuda.is_available():
+            self._consumer_device = _gpu(dataset.device, "FramePrefetcher")
+            self._side = torch.cuda.Stream(self._consumer_device)
+            self._side.wait_stream(torch.cuda.current_stream(self._consumer_device))     # the undistortion map was made there
+        self._threads = [threading.Thread(target=self._work, name=f"lvdgs-prefetch-{k}", daemon=True) for k in range(int(workers))]
+        for t in self._threads:
+            t.start()
+        self._refill()
+
+    # -- the workers: host only --
+    def _work(self):
+        while not self._stop.is_set():
+            try:
+                job = self._todo.get(timeout=0.5)
+            except queue.Empty:
+                continue
+            if job is None:
+                return
+            idx, pending = job
+            try:
+                pending.record = self.dataset.read(idx)
+            except BaseException as e:       # handed to take(), which raises it at the frame's turn
+                pending.error = e
+            pending.done.set()
+
+    def _refill(self):
+        """Give the workers every position up to ``depth`` beyond the one last taken (``_cursor - 1``)."""
+        limit = min(len(self.order), self._cursor + self.depth)
+        while self._submitted < limit:
+            p = self._pending[self._submitted] = _Pending()
+            self._todo.put((self.order[self._submitted], p))
+            self._submitted += 1
+
+    # -- the consumer's thread --
+    def _slot(self, nbytes):
+        """A free pinned buffer of at least ``nbytes``: [buffer, event of its last copy], or None when every slot is in flight."""
+        for slot in self._ring:
+            if slot[1] is None or slot[1].query():
+                if slot[0].numel() < nbytes:
+                    slot[0] = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+                slot[1] = None
+                return slot
+        if len(self._ring) < self._ring_slots:
+            self._ring.append([torch.empty(nbytes, dtype=torch.uint8, pin_memory=True), None])
+            return self._ring[-1]
+        return None
+
+    def _ring_free(self, count):
+        return self._ring_slots - len(self._ring) + sum(1 for s in self._ring if s[1] is None or s[1].query()) >= count
+
+    def _upload(self, array):
+        """A host array -> a device tensor of its dtype and shape, copied from a pinned slot on the current (side) stream."""
+        array = np.ascontiguousarray(array)
+        flat = array.reshape(-1).view(np.uint8)
+        slot = self._slot(flat.size)
+        if slot is None:
+            return _upload(array, self._consumer_device)
+        staged = slot[0][:flat.size]
+        np.copyto(staged.numpy(), flat)
+        out = torch.empty(flat.size, dtype=torch.uint8, device=self._consumer_device)
+        out.copy_(staged, non_blocking=True)
+        slot[1] = torch.cuda.Event()
+        slot[1].record(torch.cuda.current_stream(self._consumer_device))
+        return out.view(torch.from_numpy(array).dtype).view(array.shape)
+
+    def _stage(self, rec):
+        """Enqueue ``rec``'s device half on the side stream."""
+        with torch.cuda.stream(self._side):
+            self.dataset.assemble(rec, upload=self._upload)
+            rec.ready = torch.cuda.Event()
+            rec.ready.record(self._side)
+
+    def _stage_ahead(self):
+        """Frames after the cursor whose decode has finished, in order, while the ring has room for a whole frame."""
+        for pos in range(self._cursor, self._submitted):
+            p = self._pending[pos]
+            if not p.done.is_set() or p.error is not None:
+                break
+            if p.record.frame is None:
+                if not self._ring_free(4):
+                    break
+                self._stage(p.record)
+
+    def frame(self, idx):
+        """``take(idx)`` as the record (``dataset.frame(idx)``)."""
+        if self._closed:
+            raise RuntimeError("FramePrefetcher: take() after close()")
+        if self._cursor >= len(self.order) or self.order[self._cursor] != idx:
+            return self.dataset.frame(idx)                            # out of order: a direct read, nothing waits
+        p = self._pending.pop(self._cursor)
+        self._cursor += 1
+        self._refill()
+        if not p.done.wait(self.timeout):
+            raise TimeoutError(f"FramePrefetcher: frame {idx} was not read within {self.timeout:g} s")
+        if p.error is not None:
+            raise p.error
+        rec = p.record
+        if self._side is None:
+            self.dataset.assemble(rec)
+            return rec
+        if rec.frame is None:
+            self._stage(rec)
+        current = torch.cuda.current_stream(self._consumer_device)
+        current.wait_event(rec.ready)
+        for t in (rec.frame[0], rec.frame[2], rec.depth32, rec.mono_depth32):
+            if t is not None:
+                t.record_stream(current)
+        self._stage_ahead()
+        return rec
+
+    def take(self, idx):
+        return self.frame(idx).frame
+
+    def __getitem__(self, idx):
+        return self.take(idx)
+
+    def __len__(self):
+        return len(self.dataset)
+
+    def __getattr__(self, name):          # (only what this object lacks: the dataset's intrinsics, paths, static_mask, ...)
+        if name.startswith("_") or name == "dataset":
+            raise AttributeError(name)
+        return getattr(self.dataset, name)
+
+    def close(self):
+        if self._closed:
+            return
+        self._closed = True
+        self._stop.set()
+        for _ in self._threads:
+            self._todo.put(None)
+        for t in self._threads:
+            t.join(self.timeout)
+        self._pending.clear()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False

@@ -308,7 +308,7 @@ def _frame_static_mask(frame):
 
 
 def eval_rendering(frames, gaussians, dataset, save_dir, pipe, background, datatype, kf_indices, iteration="final", *, render_fn=None,
-                   fused=True, save_images=False, lpips_fn=None, metrics_fn=None):
+                   fused=True, save_images=False, lpips_fn=None, metrics_fn=None, prefetch=0):
     """The reference's ``eval_rendering`` (utils/eval_utils_0806.py:172-437): every non-keyframe frame in ``range(len(frames) - 1)``
     rendered and scored -> the ``mean_*`` dict, also written to ``<save_dir>/psnr/<iteration>/final_result.json``.
 
@@ -316,7 +316,9 @@ def eval_rendering(frames, gaussians, dataset, save_dir, pipe, background, datat
     ``(rendering, gt_image, static_mask, background) -> frame_metrics's dict`` replaces either.  ``save_images``: also
     ``render_rgb/{idx}_pred.png``, ``render_depth/{idx}_pred.png`` and ``render_depth_npy/{idx}_pred.npy`` (the fused path writes the
     device bytes).  ``lpips_fn(image, gt) -> 0-dim tensor``: adds the ``mean_lpips*`` keys; its values stay on the device until the
-    end.  ``datatype`` is accepted and unused, as in the reference."""
+    end.  ``prefetch``: that many frames read ahead on ``dataset.FramePrefetcher``'s threads, in the order they are scored
+    (``dataset`` is then a ``lvdgs.dataset`` one); the numbers and files are the same.  ``datatype`` is accepted and unused, as in the
+    reference."""
     from .image_utils import mkdir_p
     if render_fn is None:
         from .gaussian_renderer import render as render_fn
@@ -326,52 +328,59 @@ def eval_rendering(frames, gaussians, dataset, save_dir, pipe, background, datat
         for sub in ("render_rgb", "render_depth", "render_depth_npy"):
             mkdir_p(os.path.join(save_dir, sub))
     evaluator, rows, lpips_full, lpips_static = None, [], [], []
-    for idx in range(0, end_idx):
-        if idx in kf_indices:
-            continue
-        frame = frames[idx]
-        gt_image = dataset[idx][0]
-        with torch.no_grad():
-            pkg = render_fn(frame, gaussians, pipe, background)
-        rendering, depth = pkg["render"].detach(), pkg.get("depth")
-        gt_image = gt_image.to(rendering.device)
-        static = _frame_static_mask(frame)
-        use_fused = fused and metrics_fn is None
-        if use_fused:
-            if evaluator is None:
-                evaluator = FrameEvaluator(rendering.shape[-2], rendering.shape[-1], rendering.device, max(end_idx, 1), want_images=save_images)
-            # the reference moves the mask to the device itself (:247-250), as frame_metrics does; the evaluator takes device tensors only
-            dev_static = None if static is None else static.to(rendering.device)
-            dev_bg = background.to(rendering.device) if torch.is_tensor(background) else background
-            row = evaluator.add(rendering, gt_image, dev_static, dev_bg, depth if save_images else None)
-        else:
-            rows.append((metrics_fn or frame_metrics)(rendering, gt_image, static, background))
-        if lpips_fn is not None:
-            image = torch.clamp(rendering, 0.0, 1.0)
-            lpips_full.append(lpips_fn(image, gt_image).detach().reshape(()))
-            m = static
-            if m is not None:
-                if m.dim() == 3:
-                    m = m.squeeze(-1) if m.shape[-1] == 1 else m.squeeze(0)
-                keep = (gt_image > 0) & m.to(device=image.device, dtype=torch.bool)
-                bg = torch.zeros(3, device=image.device) if background is None else background.to(image.device)
-                fill = bg.view(3, 1, 1).expand_as(image)
-                masked = lpips_fn(torch.where(keep, image, fill), torch.where(keep, gt_image, fill)).detach().reshape(())
-                # (:273, :302-306: a mask that keeps nothing scores the full frame) -- chosen on the device, no wait
-                lpips_static.append(torch.where(keep.any(), masked, lpips_full[-1]))
-            else:
-                lpips_static.append(lpips_full[-1])
-        if save_images:
+    scored = [idx for idx in range(0, end_idx) if idx not in kf_indices]
+    source = dataset
+    if prefetch > 0 and scored:
+        from .dataset import FramePrefetcher
+        source = FramePrefetcher(dataset, scored, depth=prefetch)
+    try:
+        for idx in scored:
+            frame = frames[idx]
+            gt_image = source[idx][0]
+            with torch.no_grad():
+                pkg = render_fn(frame, gaussians, pipe, background)
+            rendering, depth = pkg["render"].detach(), pkg.get("depth")
+            gt_image = gt_image.to(rendering.device)
+            static = _frame_static_mask(frame)
+            use_fused = fused and metrics_fn is None
             if use_fused:
-                q = {k: v.cpu().numpy() for k, v in evaluator.images(row).items()}
-                if depth is not None:
-                    q["depth"] = depth.detach().squeeze().cpu().numpy()
+                if evaluator is None:
+                    evaluator = FrameEvaluator(rendering.shape[-2], rendering.shape[-1], rendering.device, max(end_idx, 1), want_images=save_images)
+                # the reference moves the mask to the device itself (:247-250), as frame_metrics does; the evaluator takes device tensors only
+                dev_static = None if static is None else static.to(rendering.device)
+                dev_bg = background.to(rendering.device) if torch.is_tensor(background) else background
+                row = evaluator.add(rendering, gt_image, dev_static, dev_bg, depth if save_images else None)
             else:
-                q = quantised_images(torch.clamp(rendering, 0.0, 1.0), gt_image, depth)
-            if "depth8" in q:
-                Image.fromarray(q["depth8"]).save(os.path.join(save_dir, "render_depth", f"{idx}_pred.png"), dpi=(300, 300))
-                np.save(os.path.join(save_dir, "render_depth_npy", f"{idx}_pred.npy"), q["depth"])
-            Image.fromarray(q["pred8"]).save(os.path.join(save_dir, "render_rgb", f"{idx}_pred.png"), dpi=(300, 300))
+                rows.append((metrics_fn or frame_metrics)(rendering, gt_image, static, background))
+            if lpips_fn is not None:
+                image = torch.clamp(rendering, 0.0, 1.0)
+                lpips_full.append(lpips_fn(image, gt_image).detach().reshape(()))
+                m = static
+                if m is not None:
+                    if m.dim() == 3:
+                        m = m.squeeze(-1) if m.shape[-1] == 1 else m.squeeze(0)
+                    keep = (gt_image > 0) & m.to(device=image.device, dtype=torch.bool)
+                    bg = torch.zeros(3, device=image.device) if background is None else background.to(image.device)
+                    fill = bg.view(3, 1, 1).expand_as(image)
+                    masked = lpips_fn(torch.where(keep, image, fill), torch.where(keep, gt_image, fill)).detach().reshape(())
+                    # (:273, :302-306: a mask that keeps nothing scores the full frame) -- chosen on the device, no wait
+                    lpips_static.append(torch.where(keep.any(), masked, lpips_full[-1]))
+                else:
+                    lpips_static.append(lpips_full[-1])
+            if save_images:
+                if use_fused:
+                    q = {k: v.cpu().numpy() for k, v in evaluator.images(row).items()}
+                    if depth is not None:
+                        q["depth"] = depth.detach().squeeze().cpu().numpy()
+                else:
+                    q = quantised_images(torch.clamp(rendering, 0.0, 1.0), gt_image, depth)
+                if "depth8" in q:
+                    Image.fromarray(q["depth8"]).save(os.path.join(save_dir, "render_depth", f"{idx}_pred.png"), dpi=(300, 300))
+                    np.save(os.path.join(save_dir, "render_depth_npy", f"{idx}_pred.npy"), q["depth"])
+                Image.fromarray(q["pred8"]).save(os.path.join(save_dir, "render_rgb", f"{idx}_pred.png"), dpi=(300, 300))
+    finally:
+        if source is not dataset:
+            source.close()
     if evaluator is not None:
         rows = evaluator.results()
     output = dict()

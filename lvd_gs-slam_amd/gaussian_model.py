@@ -416,7 +416,11 @@ class GaussianModel:
         if depthmap is not None:
             depth = torch.as_tensor(np.asarray(depthmap) if not torch.is_tensor(depthmap) else depthmap, dtype=torch.float32, device=dev)
         else:
-            depth = None if getattr(cam, "depth", None) is None else torch.as_tensor(cam.depth, dtype=torch.float32, device=dev)
+            depth32 = getattr(cam, "depth32", None)      # the dataset's device plane (planes="device"): cam.depth cast, without the upload
+            if depth32 is not None and getattr(cam, "depth", None) is not None:
+                depth = depth32.to(dev)
+            else:
+                depth = None if getattr(cam, "depth", None) is None else torch.as_tensor(cam.depth, dtype=torch.float32, device=dev)
             if self._cfg("Dataset", "sensor_type", "monocular") == "monocular" or depth is None:
                 noise = torch.from_numpy(self.rng.standard_normal((H, W)).astype(np.float32)).to(dev)
                 depth = (1.0 + (noise - 0.5) * 0.05) * scale  # a fronto-parallel slab at `scale` until depth is learnt

@@ -118,7 +118,7 @@ class SlamSequence:
                  refine_loss_fn=None, keyframe_depth=None, idle_map_iters=0, camera_cls=None, cameras_extent=6.0, on_event=None,
                  group=None, aux_group=None, bands_ok=None, depth_align_fn=None, scale_remedy=None, depth_align_params=None,
                  pose_init=None, matcher=None, pose_init_params=None, frame_stats="torch", edge_mask="torch", dynamic_masks="dataset",
-                 masker=None, seeding="host", map_edit="host"):
+                 masker=None, seeding="host", map_edit="host", prefetch=0):
         from .backend_map import map_window
         if camera_cls is None:
             from .camera_utils import Camera as camera_cls
@@ -181,6 +181,11 @@ class SlamSequence:
         if map_edit not in ("host", "fused"):
             raise ValueError(f"map_edit: 'host' or 'fused', not {map_edit!r}")
         self.map_edit = map_edit
+        # prefetch: 0 (the default: every frame read by `dataset[idx]` at its turn) or the number of frames dataset.FramePrefetcher reads
+        # ahead of `run` on its worker threads -- the same frames, so the same poses and the same map
+        if int(prefetch) < 0:
+            raise ValueError(f"prefetch: a number of frames >= 0, not {prefetch!r}")
+        self.prefetch, self._frames = int(prefetch), None
         # dynamic_masks: "dataset" (the default: dataset.static_mask's finished masks) or "detections" (`masker`, a
         # dynamic_mask.DynamicMasker: the masks, add_new_keyframe's dilation and valid_rgb come from its calls)
         if dynamic_masks not in ("dataset", "detections"):
@@ -274,7 +279,7 @@ class SlamSequence:
     # ------------------------------------------------------------------ front end
     def new_viewpoint(self, idx):
         """``Camera.init_from_dataset`` + ``compute_grad_mask`` (utils/slam_frontend.py:1794-1798)."""
-        vp = self.camera_cls.init_from_dataset(self.dataset, idx, self.projection_matrix)
+        vp = self.camera_cls.init_from_dataset(self.dataset if self._frames is None else self._frames, idx, self.projection_matrix)
         if self.edge_mask == "fused" and torch.is_tensor(vp.original_image) and vp.original_image.is_cuda:
             vp.compute_grad_mask(self.config, fused=True)
         else:
@@ -546,9 +551,17 @@ class SlamSequence:
     def run(self, n_frames=None):
         t0 = time.perf_counter()
         n = len(self.dataset) if n_frames is None else min(n_frames, len(self.dataset))
-        with _lib.quiet_gc():
-            for idx in range(n):
-                self.step(idx)
+        if self.prefetch > 0:
+            from .dataset import FramePrefetcher
+            self._frames = FramePrefetcher(self.dataset, range(n), depth=self.prefetch)
+        try:
+            with _lib.quiet_gc():
+                for idx in range(n):
+                    self.step(idx)
+        finally:
+            if self._frames is not None:      # at the end of the run and on an exception: no worker thread outlives it
+                self._frames.close()
+                self._frames = None
         self._sync()
         self.seconds["wall"] = time.perf_counter() - t0
         return self

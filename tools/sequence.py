@@ -6,7 +6,7 @@ the end ATE (Umeyama), PSNR before / after a colour refinement (lvdgs.slam_seque
 utils/slam_backend.py:485-609, utils/eval_utils_0806.py:33-306).
 
     python tools/sequence.py [--frames 60] [--scale 1.0] [--cadence reference|short] [--no-fused] [--idle 10] [--refine 500] [--no-masks] [--pose-init previous|pnp] [--scale-remedy keep|matches]
-    python tools/sequence.py --config YAML [--dataset-path DIR] [--ingest host|fused]     # the frames of a directory instead (lvdgs.dataset.load_dataset)
+    python tools/sequence.py --config YAML [--dataset-path DIR] [--ingest host|fused] [--prefetch N] [--planes host|device]     # the frames of a directory instead (lvdgs.dataset.load_dataset)
 
 Prints one JSON object (bench.py's config.side.sequence_kitti07_geom is the same record).  `--cadence reference`: the iteration
 counts and densification schedule of configs/mono/KITTI/base_config.yaml as they are; `short`: every burst a fifth of it (the GPU
@@ -102,7 +102,7 @@ def kitti_sequence(dev, frames=60, scale=1.0, cadence="reference", masks=True, n
     return cfg, ds, truth
 
 
-def directory_sequence(dev, config_path, dataset_path=None, ingest="host", cadence="reference", training=None, window_size=None):
+def directory_sequence(dev, config_path, dataset_path=None, ingest="host", cadence="reference", training=None, window_size=None, planes="host"):
     """(config, dataset): the settings of ``config_path`` (lvdgs.config_utils.load_config) and the dataset they name
     (lvdgs.dataset.load_dataset: KITTI, waymo, dl3dv, replica or tum files on disk; ``dataset_path`` replaces the YAML's).  ``cadence``
     "reference" leaves the Training block as the file has it, "short" lays ``SHORT`` over it; ``training`` / ``window_size`` as in
@@ -122,16 +122,16 @@ def directory_sequence(dev, config_path, dataset_path=None, ingest="host", caden
     cfg.setdefault("Results", {}).update(save_results=False, use_gui=False)
     if dataset_path is not None:
         cfg["Dataset"]["dataset_path"] = dataset_path
-    return cfg, load_dataset(None, None, cfg, device=dev, ingest=ingest)
+    return cfg, load_dataset(None, None, cfg, device=dev, ingest=ingest, planes=planes)
 
 
 def run_sequence(dev, frames=60, scale=1.0, cadence="reference", fused="auto", idle=10, refine=500, masks=True, seed=0, training=None,
                  window_size=None, on_event=None, geometry="kitti07", pcd_downsample=None, mono_scale_drift=0.0, trajectory=None,
-                 config_path=None, dataset_path=None, ingest="host", eval_mode="host", **sequence_kwargs):
+                 config_path=None, dataset_path=None, ingest="host", eval_mode="host", planes="host", **sequence_kwargs):
     torch.manual_seed(seed)
     random.seed(seed)
     if config_path is not None:      # frames from a directory: at most ``frames`` of them
-        cfg, ds = directory_sequence(dev, config_path, dataset_path, ingest, cadence, training, window_size)
+        cfg, ds = directory_sequence(dev, config_path, dataset_path, ingest, cadence, training, window_size, planes)
         masks, geometry = False, cfg["Dataset"]["type"]
         ds.num_imgs = min(len(ds), frames)
     else:
@@ -176,6 +176,8 @@ def run_sequence(dev, frames=60, scale=1.0, cadence="reference", fused="auto", i
     out.update(geometry=geometry, width=ds.width, height=ds.height, cadence=cadence, fused=fused, idle_map_iters=idle, keyframes_carry_static_mask=masks)
     if config_path is not None:
         out.update(config=config_path, ingest=ingest)
+        if planes != "host" or sequence_kwargs.get("prefetch"):
+            out.update(planes=planes, prefetch=int(sequence_kwargs.get("prefetch") or 0))
     if mono_scale_drift or sequence_kwargs.get("keyframe_depth") is not None:
         out.update(mono_scale_drift=mono_scale_drift, keyframe_depth=sequence_kwargs.get("keyframe_depth") or "mono")
     return out, seq
@@ -229,6 +231,11 @@ def main():
     ap.add_argument("--ingest", choices=["host", "fused"], default="host",
                     help="with --config: undistort and convert a decoded frame in NumPy and upload float32 (default), or upload its bytes and make "
                          "one lvdgs_ingest_frame call (the same bits)")
+    ap.add_argument("--prefetch", type=int, default=0, metavar="N",
+                    help="with --config: read N frames ahead of the loops on worker threads (lvdgs.dataset.FramePrefetcher); the same frames")
+    ap.add_argument("--planes", choices=["host", "device"], default="host",
+                    help="with --config --ingest fused: device makes the float32 depth planes on the GPU (lvdgs_ingest_depth) and the loops "
+                         "take them without another upload")
     ap.add_argument("--verbose", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -242,7 +249,8 @@ def main():
                           **({"frame_stats": "fused"} if a.frame_stats == "fused" else {}), **({"edge_mask": "fused"} if a.edge_mask == "fused" else {}),
                           **({"dynamic_masks": "detections"} if a.dynamic_masks == "detections" else {}),
                           **({"seeding": "fused"} if a.seeding == "fused" else {}), **({"map_edit": "fused"} if a.map_edit == "fused" else {}),
-                          **({"config_path": a.config, "dataset_path": a.dataset_path, "ingest": a.ingest} if a.config else {}))
+                          **({"config_path": a.config, "dataset_path": a.dataset_path, "ingest": a.ingest, "planes": a.planes} if a.config else {}),
+                          **({"prefetch": a.prefetch} if a.config and a.prefetch else {}))
     out.update(frame_stats=a.frame_stats, edge_mask=a.edge_mask, dynamic_masks=a.dynamic_masks, seeding=a.seeding, map_edit=a.map_edit, eval=a.eval_mode)
     for rec in out.get("pose_init", []):
         print("  frame {frame:3d} kf {keyframe:3d} inliers {inl:>5} init error {e:.4f} ({r:.3f} deg; previous pose {p:.4f}) tracking iterations {it}".format(
