@@ -37,8 +37,9 @@
  *    getWorld2View2(R,T).transpose(0,1), utils/camera_utils.py:106-116).
  *
  * Host blocks
- *  Seven calls enqueue their launches, do not wait, and report through a block of host memory, `host_state`: lvdgs_depth_align,
- *  lvdgs_pnp_ransac, lvdgs_reciprocal_nn, lvdgs_match_depth_scale, lvdgs_frame_summary, lvdgs_seed_points, lvdgs_map_edit_plan.
+ *  Eight calls enqueue their launches, do not wait, and report through a block of host memory, `host_state`: lvdgs_depth_align,
+ *  lvdgs_pnp_ransac, lvdgs_reciprocal_nn, lvdgs_match_depth_scale, lvdgs_frame_summary, lvdgs_seed_points, lvdgs_map_edit_plan,
+ *  lvdgs_tsdf_mesh.
  *  - the block is the caller's: page-locked, mapped host memory (hipHostMalloc, a pinned PyTorch tensor) of the size its section
  *    states, which the caller passes by its HOST address; memory that is not so is refused with LVDGS_E_HIP, "<call>: host_state is
  *    not mapped pinned memory", before any launch;
@@ -49,7 +50,7 @@
  *  - the caller clears the tag word, makes the call, synchronises the stream ONCE and looks at the tag: a word that is not this
  *    call's tag means that the call left no state (nothing else in the block is then to be believed);
  *  - the tag is the `seq` of the argument block -- any value the caller's previous call did not use, 0 excepted -- for
- *    lvdgs_frame_summary, lvdgs_seed_points and lvdgs_map_edit_plan, and the status word [0], never 0, for lvdgs_pnp_ransac,
+ *    lvdgs_frame_summary, lvdgs_seed_points, lvdgs_map_edit_plan and lvdgs_tsdf_mesh, and the status word [0], never 0, for lvdgs_pnp_ransac,
  *    lvdgs_reciprocal_nn and lvdgs_match_depth_scale;
  *  - lvdgs_depth_align is the exception: its block has no tag, it is a state that every launch which changes it mirrors, that is
  *    complete behind the caller's wait for the stream, and that lvdgs_depth_align_resume reads ON THE HOST -- the caller leaves it
@@ -1301,6 +1302,99 @@ typedef struct lvdgs_frame_eval_args {
 } lvdgs_frame_eval_args;
 size_t lvdgs_frame_eval_scratch_bytes(int32_t width, int32_t height);
 int lvdgs_frame_eval(const lvdgs_frame_eval_args *a, void *stream);
+
+/* ---- TSDF fusion of depth maps and a mesh by surface nets (what an Open3D-style ScalableTSDFVolume.integrate /
+ * extract_triangle_mesh does on the host, after a copy of every depth map and image) ----
+ * THE VOLUME: nx*ny*nz samples at the lattice points p[a] = origin[a] + voxel_size * (float)i_a (one float32 product, one float32
+ * sum), linear index s = i + nx * (j + ny * k) in int64, in caller-owned planes: tsdf and weight, float32, and optionally r, g, b,
+ * float32 running means (all three or none).  A zeroed block is an empty volume; there is no clear call.
+ *
+ * lvdgs_tsdf_integrate applies, to every voxel, views[0 .. count-1] in list order (count 0: nothing to do; at most
+ * LVDGS_TSDF_MAX_VIEWS).  A view: width, height; fx, fy, cx, cy; R (9, row-major) and T (3) ON THE DEVICE, p_c = R p_w + T as for
+ * lvdgs_seed_points; depth, height*width float32; image, 3*height*width planar float32, or NULL; mask, height*width bytes, non-0 =
+ * use, or NULL; depth_min, depth_trunc (may be +inf).  Per voxel and view, all float32, evaluated as written, no contraction:
+ *   1. x = ((R[0]*px + R[1]*py) + R[2]*pz) + T[0],  y and z alike with rows 1 and 2.  Skip unless z > depth_min.
+ *   2. u = fx * (x / z) + cx,  v = fy * (y / z) + cy;  uf = floorf(u + 0.5f), vf alike.  Skip unless 0 <= uf < width and
+ *      0 <= vf < height (float comparisons: a NaN or a value beyond int32 skips);  ui = (int)uf, vi = (int)vf.
+ *   3. d = depth[vi*width + ui].  Skip unless d > 0 && d <= depth_trunc (NaN fails), and unless mask is NULL or mask[vi*width+ui] != 0.
+ *   4. sdf = d - z.  Skip if sdf < -trunc.  t = fminf(1.0f, sdf / trunc).
+ *   5. w1 = w + 1.0f;  tsdf = (tsdf * w + t) / w1;  with an image, per colour plane c = (c * w + image[ch][vi][ui]) / w1 (the colour
+ *      as it is, not clamped; a view without an image leaves the colour planes alone);  w = fminf(w1, max_weight).
+ * One thread owns four voxels along x and keeps them in registers across the views: the planes are read and written once per call
+ * (16 bytes per lane when nx is a multiple of 4 and the planes are 16-byte aligned, element by element otherwise; rows that no
+ * view changes are not written back).  A workgroup owns a brick of 64 x 4 x 4 voxels and first decides, per view, from the
+ * brick's eight corner voxels alone whether the view can touch it: not when every z is at or below depth_min, when every z lies
+ * beyond depth_trunc + trunc, or -- for a brick wholly in front of the camera -- when all of it projects left of, right of, above
+ * or below the image; each test carries a margin above the rounding of steps 1 and 2, so only voxels the rule skips are skipped,
+ * and a brick no view can touch is not read.  No atomics: two calls give the same bytes.  One launch, no host wait, no copy.
+ * Before the launch -- LVDGS_E_INVALID: vol, its tsdf or weight NULL, r, g, b neither all set nor all NULL, views NULL with count >
+ * 0, a view, its R, T or depth NULL, count outside 0 .. LVDGS_TSDF_MAX_VIEWS, an image on a volume without colour planes;
+ * LVDGS_E_RANGE: a dimension below 1, more than 2^31 - 1 samples, ny or nz beyond 262140 (65535 bricks), voxel_size, trunc or
+ * max_weight not finite and > 0, a view's width or height below 1 or more than 2^31 - 1 pixels.
+ *
+ * lvdgs_tsdf_mesh: surface nets over the same planes.  A sample is OBSERVED when weight > 0 and INSIDE when tsdf < 0.  Cell (i, j, k),
+ * i < nx-1, j < ny-1, k < nz-1, with the samples (i+dx, j+dy, k+dz) as corners, is ACTIVE when all eight are observed and they are
+ * not all on one side.
+ *   Vertex of an active cell: over its 12 edges in the order x edges (dy,dz) = (0,0) (1,0) (0,1) (1,1), y edges (dx,dz) = (0,0) (1,0)
+ *   (0,1) (1,1), z edges (dx,dy) = (0,0) (1,0) (0,1) (1,1), each from its low end f0 to its high end f1: where the ends differ in
+ *   side, q = f0 / (f0 - f1), the crossing is the low corner's offset with q added along the edge's axis, and its colour is
+ *   c0 + q * (c1 - c0) per plane.  The three coordinates and three colours are summed in that order starting from 0.0f and divided
+ *   by (float)(the number of crossings);  position[a] = origin[a] + voxel_size * ((float)cell_a + mean[a]).  Vertices are numbered in
+ *   the order of their cells' low-corner sample index s.
+ *   Faces: for the lattice edge from sample (i, j, k) to its neighbour along axis a, (a, b, c) a cyclic permutation of (x, y, z),
+ *   whose ends differ in side and whose four surrounding cells -- the sample's coordinates with (b, c) offset by c0 = (-1,-1),
+ *   c1 = (0,-1), c2 = (0,0), c3 = (-1,0) -- exist and are active: the low end inside gives (c0,c1,c2), (c0,c2,c3), otherwise
+ *   (c0,c2,c1), (c0,c3,c2), as vertex numbers (int32); normals point from inside to outside.  Faces are ordered by s, within a
+ *   sample by axis x, y, z, the two triangles as written.
+ * Launches, enqueued at once: classify (a byte per sample: active, inside, observed; vertices per span of samples), the edges (a
+ * byte per sample; faces per span), one workgroup's scan of both counts, the vertices with the cell-to-vertex numbers in scratch,
+ * the faces, and the publish.  No atomic decides a position: two calls give the same bytes.  vertices, colors: vertex_capacity*3
+ * float32 (colors NULL: none; it needs the volume's colour planes); faces: face_capacity*3 int32.  Rows beyond a capacity are
+ * not written -- nothing behind capacity*3 elements is touched -- and the counts reported are the exact ones, so one retry sized
+ * by them succeeds.  host_state: a host block ("Host blocks" above) of LVDGS_TSDF_HOST_BYTES bytes: [LVDGS_TSDF_SEQ] the call's
+ * `seq`, the tag; [_N_VERTICES]; [_N_FACES], saturated at 2^31 - 1; [_OVERFLOW] bit 0: more vertices than vertex_capacity, bit 1:
+ * more faces than face_capacity, bit 2: more than 2^31 - 1 faces (no retry can hold them); zeros after it.  scratch: the bytes
+ * lvdgs_tsdf_mesh_scratch_bytes gives (0: the size is refused), no initialisation needed.
+ * Before any launch -- LVDGS_E_INVALID: args, tsdf, weight, vertices, faces, host_state or scratch NULL, r, g, b neither all set nor
+ * all NULL, colors without colour planes, scratch too small; LVDGS_E_RANGE: a dimension below 2, more than 2^31 - 1 samples,
+ * voxel_size not finite and > 0, a negative capacity. */
+#define LVDGS_TSDF_MAX_VIEWS 16
+#define LVDGS_TSDF_HOST_BYTES 64
+enum {
+    LVDGS_TSDF_SEQ = 0,
+    LVDGS_TSDF_N_VERTICES = 1,
+    LVDGS_TSDF_N_FACES = 2,
+    LVDGS_TSDF_OVERFLOW = 3
+};
+typedef struct lvdgs_tsdf_volume {
+    int32_t nx, ny, nz;
+    float origin[3];
+    float voxel_size, trunc, max_weight;   /* lvdgs_tsdf_mesh reads voxel_size only  */
+    float *tsdf, *weight;         /* nx*ny*nz each                                  */
+    float *r, *g, *b;             /* nx*ny*nz each, or all NULL: no colour          */
+} lvdgs_tsdf_volume;
+typedef struct lvdgs_tsdf_view {
+    int32_t width, height;
+    float fx, fy, cx, cy;
+    float depth_min, depth_trunc;
+    const float *R, *T;           /* 9 row-major and 3, on the device               */
+    const float *depth;           /* height*width                                   */
+    const float *image;           /* 3*height*width planar, or NULL                 */
+    const uint8_t *mask;          /* height*width, non-0 = use, or NULL             */
+} lvdgs_tsdf_view;
+typedef struct lvdgs_tsdf_mesh_args {
+    lvdgs_tsdf_volume vol;
+    uint32_t seq;
+    int32_t vertex_capacity, face_capacity;   /* rows the outputs hold               */
+    float *vertices;              /* out vertex_capacity*3                          */
+    float *colors;                /* out vertex_capacity*3, or NULL                 */
+    int32_t *faces;               /* out face_capacity*3                            */
+    int32_t *host_state;          /* LVDGS_TSDF_HOST_BYTES, pinned host (the host address) */
+    void *scratch; size_t scratch_bytes;
+} lvdgs_tsdf_mesh_args;
+int lvdgs_tsdf_integrate(const lvdgs_tsdf_volume *vol, const lvdgs_tsdf_view *const *views, int32_t count, void *stream);
+size_t lvdgs_tsdf_mesh_scratch_bytes(int32_t nx, int32_t ny, int32_t nz);
+int lvdgs_tsdf_mesh(const lvdgs_tsdf_mesh_args *a, void *stream);
 
 /* ---- diagnostics ---- */
 const char *lvdgs_last_error(void);

@@ -330,6 +330,38 @@ FRAME_EVAL_ROW_DTYPE = np.dtype([("sum_sq_full", "<f8"), ("sum_sq_static", "<f8"
                                  ("flags", "<u4"), ("reserved", "<u4")])
 
 
+class TsdfVolumeArgs(C.Structure):
+    """struct lvdgs_tsdf_volume (include/lvdgs.h)."""
+    _fields_ = [
+        ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("origin", C.c_float * 3),
+        ("voxel_size", C.c_float), ("trunc", C.c_float), ("max_weight", C.c_float),
+        ("tsdf", _fp), ("weight", _fp), ("r", _fp), ("g", _fp), ("b", _fp),
+    ]
+
+
+class TsdfViewArgs(C.Structure):
+    """struct lvdgs_tsdf_view (include/lvdgs.h)."""
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+        ("depth_min", C.c_float), ("depth_trunc", C.c_float),
+        ("R", _fp), ("T", _fp), ("depth", _fp), ("image", _fp), ("mask", _fp),
+    ]
+
+
+class TsdfMeshArgs(C.Structure):
+    """struct lvdgs_tsdf_mesh_args (include/lvdgs.h)."""
+    _fields_ = [
+        ("vol", TsdfVolumeArgs), ("seq", C.c_uint32), ("vertex_capacity", C.c_int32), ("face_capacity", C.c_int32),
+        ("vertices", _fp), ("colors", _fp), ("faces", _fp), ("host_state", _fp),
+        ("scratch", _fp), ("scratch_bytes", C.c_size_t),
+    ]
+
+
+TSDF_MAX_VIEWS, TSDF_HOST_BYTES = 16, 64
+TSDF_SEQ, TSDF_N_VERTICES, TSDF_N_FACES, TSDF_OVERFLOW = 0, 1, 2, 3
+TSDF_OVERFLOW_VERTICES, TSDF_OVERFLOW_FACES, TSDF_OVERFLOW_INT32 = 1, 2, 4     # bits of the [TSDF_OVERFLOW] word
+
+
 DEPTH_SAMPLE_BYTE, DEPTH_SAMPLE_WORD = 1, 2     # lvdgs_ingest_depth_args.sample_type
 MAP_OUTSIDE = -2 ** 31     # INT32_MIN in an undistortion map: the destination pixel's source lies outside
 
@@ -363,6 +395,7 @@ EXPORTS = (
     "lvdgs_map_edit_scratch_bytes", "lvdgs_map_edit_plan", "lvdgs_map_edit_apply",
     "lvdgs_undistort_map", "lvdgs_ingest_frame", "lvdgs_ingest_depth",
     "lvdgs_frame_eval_scratch_bytes", "lvdgs_frame_eval",
+    "lvdgs_tsdf_integrate", "lvdgs_tsdf_mesh_scratch_bytes", "lvdgs_tsdf_mesh",
     "lvdgs_last_error", "lvdgs_version", "lvdgs_profile_enable",
     "lvdgs_profile_reset", "lvdgs_profile_read",
 )
@@ -489,6 +522,10 @@ def lib():
         L.lvdgs_frame_eval_scratch_bytes.restype = C.c_size_t
         L.lvdgs_frame_eval_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
         L.lvdgs_frame_eval.argtypes = [C.POINTER(FrameEvalArgs), C.c_void_p]
+        L.lvdgs_tsdf_integrate.argtypes = [C.POINTER(TsdfVolumeArgs), C.POINTER(C.POINTER(TsdfViewArgs)), C.c_int32, C.c_void_p]
+        L.lvdgs_tsdf_mesh_scratch_bytes.restype = C.c_size_t
+        L.lvdgs_tsdf_mesh_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+        L.lvdgs_tsdf_mesh.argtypes = [C.POINTER(TsdfMeshArgs), C.c_void_p]
         L.lvdgs_profile_enable.argtypes = [C.c_int]
         L.lvdgs_profile_read.argtypes = [C.POINTER(KernelTime), C.c_int]
         _lib = L

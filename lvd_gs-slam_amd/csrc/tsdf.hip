@@ -1,0 +1,578 @@
+// TSDF fusion of depth maps into a dense volume and a mesh of it by surface nets (rules, arithmetic and the host block:
+// include/lvdgs.h, "TSDF fusion").
+//
+// lvdgs_tsdf_integrate: one launch.  A workgroup of 256 threads owns a brick of 64 x 4 x 4 voxels; a thread owns four voxels along x
+// (16 lanes span a row of 64: 256 contiguous bytes of a plane), keeps them in registers across the up to 16 views and writes a row
+// back only when a view changed it.  Before anything is read, lanes 0 .. count-1 of every wave test one view each against the brick's
+// eight corner voxels (brick_may_touch) and a ballot makes the wave-uniform mask of the views the brick is walked for; a brick with an
+// empty mask returns without touching memory.
+//
+// lvdgs_tsdf_mesh: six launches.  Every workgroup owns one contiguous span of samples; positions come from counts per span, one
+// workgroup's scan of them, and a second walk with one workgroup scan per 256 samples (seeding.hip's ordered compaction): integer
+// decisions only, no atomics, two calls give the same bytes.
+//
+// Built like every file here with -ffp-contract=off and without fast-math: the float32 expressions of the header are evaluated as
+// written, the divisions IEEE-rounded, and a NumPy float32 restatement gives the same bits.
+#include <cmath>
+
+#include "common.hpp"
+#include "device_utils.hpp"
+
+namespace lvdgs {
+namespace {
+
+constexpr int TSDF_THREADS = 256;
+constexpr int BRICK_X = 64, BRICK_Y = 4, BRICK_Z = 4;   // 16 lanes x 4 voxels, 4 rows per wave, 4 waves
+constexpr int TSDF_MAX_BLOCKS = 2048;                   // spans of the mesh passes (a multiple of TSDF_THREADS: whole scan rounds)
+
+struct TsdfView {
+    int W, H;
+    float fx, fy, cx, cy, dmin, dtrunc;
+    const float *R, *T, *depth, *image;
+    const uint8_t *mask;
+};
+
+struct IntegrateParams {
+    int nx, ny, nz, count;
+    float ox, oy, oz, vs, trunc, maxw;
+    float *tsdf, *weight, *r, *g, *b;
+    TsdfView v[LVDGS_TSDF_MAX_VIEWS];
+};
+
+// Can view V change a voxel of the brick whose corner voxels are (i0|i1, j0|j1, k0|k1)?  false only when the per-voxel rule skips
+// every voxel of it.  The lattice positions are monotone in the index and x, y, z of step 1 are affine in them, so each quantity below
+// is bounded over the brick by its values at the corners, up to the rounding of step 1: at most 4 * 2^-24 of M = |R0 px| + |R1 py| +
+// |R2 pz| + |T| for a voxel and as much for a corner -- ez = 1e-6 M covers both twice over.
+//  * behind:  every z <= depth_min.
+//  * far:     d <= depth_trunc, so sdf <= depth_trunc - z (rounding is monotone); below -trunc for every z.
+//  * frustum, for a brick with z >= M / 64 > 0 only: u + 0.5 < 0 is fx x + (cx + 0.5) z < 0, affine again, and u + 0.5 >= W likewise.
+//    The computed u is off by at most fx (ex + |x / z| ez) / z + a few ulps of |u| + |cx|; times z, with 1 / z <= 64 / Mz, that is under
+//    2e-5 (fx Mx + (|cx| + W + 1) Mz): the margin taken is 1e-4 of it.
+__device__ __forceinline__ bool brick_may_touch(const IntegrateParams &p, const TsdfView &V, int i0, int i1, int j0, int j1, int k0, int k1) {
+    float R[9], T[3];
+#pragma unroll
+    for (int q = 0; q < 9; q++) R[q] = V.R[q];
+#pragma unroll
+    for (int q = 0; q < 3; q++) T[q] = V.T[q];
+    const float inf = __builtin_inff();
+    const float cl = V.cx + 0.5f, cr = cl - (float)V.W, ct = V.cy + 0.5f, cb = ct - (float)V.H;
+    float zmin = inf, zmax = -inf, Mx = 0.f, My = 0.f, Mz = 0.f;
+    float gl = -inf, gr = inf, gt = -inf, gb = inf;
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+        const float px = p.ox + p.vs * (float)((c & 1) ? i1 : i0);
+        const float py = p.oy + p.vs * (float)((c & 2) ? j1 : j0);
+        const float pz = p.oz + p.vs * (float)((c & 4) ? k1 : k0);
+        const float x = ((R[0] * px + R[1] * py) + R[2] * pz) + T[0];
+        const float y = ((R[3] * px + R[4] * py) + R[5] * pz) + T[1];
+        const float z = ((R[6] * px + R[7] * py) + R[8] * pz) + T[2];
+        Mx = fmaxf(Mx, fabsf(R[0] * px) + fabsf(R[1] * py) + fabsf(R[2] * pz) + fabsf(T[0]));
+        My = fmaxf(My, fabsf(R[3] * px) + fabsf(R[4] * py) + fabsf(R[5] * pz) + fabsf(T[1]));
+        Mz = fmaxf(Mz, fabsf(R[6] * px) + fabsf(R[7] * py) + fabsf(R[8] * pz) + fabsf(T[2]));
+        zmin = fminf(zmin, z); zmax = fmaxf(zmax, z);
+        gl = fmaxf(gl, V.fx * x + cl * z); gr = fminf(gr, V.fx * x + cr * z);
+        gt = fmaxf(gt, V.fy * y + ct * z); gb = fminf(gb, V.fy * y + cb * z);
+    }
+    if (!(Mx + My + Mz < inf)) return true;   // a NaN or an overflow somewhere: let the voxels decide
+    const float ez = 1e-6f * Mz;
+    if (zmax + ez <= V.dmin) return false;
+    const float zlo = zmin - 2.f * ez;
+    if (V.dtrunc - zlo < -p.trunc) return false;
+    if (zlo > 0.f && zlo >= 0.015625f * Mz && V.fx > 0.f && V.fy > 0.f) {
+        const float mx = 1e-4f * (V.fx * Mx + (fabsf(V.cx) + (float)V.W + 1.f) * Mz);
+        const float my = 1e-4f * (V.fy * My + (fabsf(V.cy) + (float)V.H + 1.f) * Mz);
+        if (gl + mx < 0.f || gr - mx > 0.f || gt + my < 0.f || gb - my > 0.f) return false;
+    }
+    return true;
+}
+
+// COLOR: the volume has colour planes.  VEC: nx % 4 == 0 and every plane 16-byte aligned -- a thread's four voxels are one float4.
+template <bool COLOR, bool VEC>
+__global__ void __launch_bounds__(TSDF_THREADS) tsdf_integrate_kernel(IntegrateParams p) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int bi = blockIdx.x * BRICK_X, bj = blockIdx.y * BRICK_Y, bk = blockIdx.z * BRICK_Z;
+    bool touch = false;
+    if (lane < p.count)
+        touch = brick_may_touch(p, p.v[lane], bi, min(bi + BRICK_X, p.nx) - 1, bj, min(bj + BRICK_Y, p.ny) - 1, bk, min(bk + BRICK_Z, p.nz) - 1);
+    const uint32_t live = (uint32_t)__ballot(touch);   // the same in all four waves
+    if (live == 0u) return;
+
+    const int i0 = bi + (lane & 15) * 4, j = bj + (lane >> 4), k = bk + wave;
+    if (i0 >= p.nx || j >= p.ny || k >= p.nz) return;
+    const int nv = min(4, p.nx - i0);   // (VEC: always 4)
+    const int64_t base = (int64_t)i0 + (int64_t)p.nx * ((int64_t)j + (int64_t)p.ny * (int64_t)k);
+    float f[4], w[4], cr[4], cg[4], cb[4];
+    auto load4 = [&](const float *plane, float (&dst)[4]) {
+        if constexpr (VEC) {
+            const float4 q = *reinterpret_cast<const float4 *>(plane + base);
+            dst[0] = q.x; dst[1] = q.y; dst[2] = q.z; dst[3] = q.w;
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; q++) dst[q] = q < nv ? plane[base + q] : 0.f;
+        }
+    };
+    auto store4 = [&](float *plane, const float (&src)[4]) {
+        if constexpr (VEC) {
+            *reinterpret_cast<float4 *>(plane + base) = make_float4(src[0], src[1], src[2], src[3]);
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; q++)
+                if (q < nv) plane[base + q] = src[q];
+        }
+    };
+    load4(p.tsdf, f);
+    load4(p.weight, w);
+    if constexpr (COLOR) { load4(p.r, cr); load4(p.g, cg); load4(p.b, cb); }
+
+    const float py = p.oy + p.vs * (float)j, pz = p.oz + p.vs * (float)k;
+    float px[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) px[q] = p.ox + p.vs * (float)(i0 + q);
+    bool changed = false, recoloured = false;
+    for (int v = 0; v < p.count; v++) {
+        if (!((live >> v) & 1u)) continue;   // (wave-uniform)
+        const TsdfView &V = p.v[v];
+        float R[9], T[3];
+#pragma unroll
+        for (int q = 0; q < 9; q++) R[q] = V.R[q];
+#pragma unroll
+        for (int q = 0; q < 3; q++) T[q] = V.T[q];
+        const int64_t P = (int64_t)V.W * V.H;
+        const bool coloured = COLOR && V.image != nullptr;
+        // in stages over the thread's four voxels, so that their gathers are in flight together: the pixel (pixel 0 stands in where
+        // there is none: every gather below has a valid address and needs no branch), depth and mask, the colours, the update
+        float z[4];
+        int pix[4];
+        bool ok[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const float x = ((R[0] * px[q] + R[1] * py) + R[2] * pz) + T[0];
+            const float y = ((R[3] * px[q] + R[4] * py) + R[5] * pz) + T[1];
+            z[q] = ((R[6] * px[q] + R[7] * py) + R[8] * pz) + T[2];
+            const float u = V.fx * (x / z[q]) + V.cx, vv = V.fy * (y / z[q]) + V.cy;
+            const float uf = floorf(u + 0.5f), vf = floorf(vv + 0.5f);
+            ok[q] = q < nv && z[q] > V.dmin && uf >= 0.f && uf < (float)V.W && vf >= 0.f && vf < (float)V.H;
+            pix[q] = ok[q] ? (int)vf * V.W + (int)uf : 0;
+        }
+        if (!__any(ok[0] || ok[1] || ok[2] || ok[3])) continue;   // (a wave's rows outside this view)
+        float d[4];
+        uint8_t m[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) d[q] = V.depth[pix[q]];
+#pragma unroll
+        for (int q = 0; q < 4; q++) m[q] = V.mask ? V.mask[pix[q]] : (uint8_t)1;
+        float sdf[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            sdf[q] = d[q] - z[q];
+            ok[q] = ok[q] && d[q] > 0.f && d[q] <= V.dtrunc && m[q] != 0 && !(sdf[q] < -p.trunc);
+        }
+        float c0[4], c1[4], c2[4];
+        if (coloured) {
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const int at = ok[q] ? pix[q] : 0;
+                c0[q] = V.image[at]; c1[q] = V.image[P + at]; c2[q] = V.image[2 * P + at];
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            if (!ok[q]) continue;
+            const float t = fminf(1.0f, sdf[q] / p.trunc);
+            const float w0 = w[q], w1 = w0 + 1.0f;
+            f[q] = (f[q] * w0 + t) / w1;
+            if (coloured) {
+                cr[q] = (cr[q] * w0 + c0[q]) / w1;
+                cg[q] = (cg[q] * w0 + c1[q]) / w1;
+                cb[q] = (cb[q] * w0 + c2[q]) / w1;
+                recoloured = true;
+            }
+            w[q] = fminf(w1, p.maxw);
+            changed = true;
+        }
+    }
+    if (changed) { store4(p.tsdf, f); store4(p.weight, w); }
+    if constexpr (COLOR) {
+        if (recoloured) { store4(p.r, cr); store4(p.g, cg); store4(p.b, cb); }
+    }
+}
+
+// ---------------------------------------------------------------- the mesh ----
+
+enum : uint8_t { CELL_ACTIVE = 1, SAMPLE_INSIDE = 2, SAMPLE_OBSERVED = 4 };   // the classify pass's byte
+enum : uint8_t { EDGE_LOW_INSIDE = 8 };                                        // the edge pass's byte: bits 0-2 the axes whose edge gives faces
+
+struct MeshParams {
+    int nx, ny, nz;
+    uint32_t n, span;      // samples; samples per workgroup, a multiple of TSDF_THREADS
+    float ox, oy, oz, vs;
+    const float *tsdf, *weight, *r, *g, *b;
+    int vcap, fcap;
+    uint32_t seq;
+    float *vertices, *colors;
+    int32_t *faces;
+    uint8_t *flags, *edges;            // n each
+    int32_t *cellvert;                 // n: an active cell's vertex number, at its low corner's sample
+    uint32_t *vcount, *fcount;         // TSDF_MAX_BLOCKS each: per span; vcount becomes the vertices in front of the span
+    unsigned long long *fbase;         // TSDF_MAX_BLOCKS: the faces in front of the span
+    unsigned long long *totals;        // [0] vertices, [1] faces
+    int32_t *host;
+};
+
+struct Sample { int i, j, k; };
+__device__ __forceinline__ Sample sample_of(const MeshParams &M, uint32_t s) {
+    const uint32_t row = s / (uint32_t)M.nx;
+    Sample c;
+    c.i = (int)(s - row * (uint32_t)M.nx);
+    c.k = (int)(row / (uint32_t)M.ny);
+    c.j = (int)(row - (uint32_t)c.k * (uint32_t)M.ny);
+    return c;
+}
+
+__global__ void __launch_bounds__(TSDF_THREADS) tsdf_classify_kernel(MeshParams M) {
+    __shared__ uint32_t sh[SCAN_WORDS];
+    const uint32_t begin = blockIdx.x * M.span;
+    const uint32_t end = M.n - begin < M.span ? M.n : begin + M.span;
+    const uint32_t sx = 1u, sy = (uint32_t)M.nx, sz = (uint32_t)M.nx * (uint32_t)M.ny;
+    uint32_t mine = 0;
+    for (uint32_t s = begin + threadIdx.x; s < end; s += TSDF_THREADS) {
+        const Sample c = sample_of(M, s);
+        const bool obs = M.weight[s] > 0.f, in = M.tsdf[s] < 0.f;
+        bool active = false;
+        if (c.i < M.nx - 1 && c.j < M.ny - 1 && c.k < M.nz - 1) {
+            bool all = true;
+            int n_in = 0;
+#pragma unroll
+            for (int q = 0; q < 8; q++) {
+                const uint32_t o = s + ((q & 1) ? sx : 0u) + ((q & 2) ? sy : 0u) + ((q & 4) ? sz : 0u);
+                all = all && M.weight[o] > 0.f;
+                n_in += M.tsdf[o] < 0.f ? 1 : 0;
+            }
+            active = all && n_in > 0 && n_in < 8;
+        }
+        M.flags[s] = (uint8_t)((active ? CELL_ACTIVE : 0) | (in ? SAMPLE_INSIDE : 0) | (obs ? SAMPLE_OBSERVED : 0));
+        mine += active ? 1u : 0u;
+    }
+    uint32_t total = 0;
+    scan_workgroup<TSDF_THREADS>(mine, sh, &total);
+    if (threadIdx.x == 0) M.vcount[blockIdx.x] = total;
+}
+
+__global__ void __launch_bounds__(TSDF_THREADS) tsdf_edges_kernel(MeshParams M) {
+    __shared__ uint32_t sh[SCAN_WORDS];
+    const uint32_t begin = blockIdx.x * M.span;
+    const uint32_t end = M.n - begin < M.span ? M.n : begin + M.span;
+    const uint32_t sy = (uint32_t)M.nx, sz = (uint32_t)M.nx * (uint32_t)M.ny;
+    uint32_t mine = 0;
+    for (uint32_t s = begin + threadIdx.x; s < end; s += TSDF_THREADS) {
+        const Sample c = sample_of(M, s);
+        const uint8_t fl = M.flags[s];
+        const bool in0 = fl & SAMPLE_INSIDE;
+        uint32_t e = 0;
+        if (fl & CELL_ACTIVE) {   // c2 = the sample's own cell, for every axis; it being a cell puts i, j, k below n - 1
+            auto act = [&](uint32_t o) { return (M.flags[o] & CELL_ACTIVE) != 0; };
+            auto differs = [&](uint32_t o) { return ((M.flags[o] & SAMPLE_INSIDE) != 0) != in0; };
+            const bool bi = c.i >= 1, bj = c.j >= 1, bk = c.k >= 1;
+            if (bj && bk && differs(s + 1u) && act(s - sy - sz) && act(s - sz) && act(s - sy)) e |= 1u;    // x: (b, c) = (y, z)
+            if (bk && bi && differs(s + sy) && act(s - sz - 1u) && act(s - 1u) && act(s - sz)) e |= 2u;    // y: (b, c) = (z, x)
+            if (bi && bj && differs(s + sz) && act(s - 1u - sy) && act(s - sy) && act(s - 1u)) e |= 4u;    // z: (b, c) = (x, y)
+        }
+        M.edges[s] = (uint8_t)(e | (in0 ? EDGE_LOW_INSIDE : 0));
+        mine += 2u * (uint32_t)__popc(e);
+    }
+    uint32_t total = 0;
+    scan_workgroup<TSDF_THREADS>(mine, sh, &total);
+    if (threadIdx.x == 0) M.fcount[blockIdx.x] = total;
+}
+
+// One workgroup: the counts of the `blocks` <= TSDF_MAX_BLOCKS spans become the rows in front of each.  A round's sum fits 32 bits
+// (256 spans of at most 2^20 samples, six faces each); the carry over the rounds is 64 bits for the faces.
+__global__ void __launch_bounds__(TSDF_THREADS) tsdf_scan_kernel(MeshParams M, int blocks) {
+    __shared__ uint32_t sh[SCAN_WORDS];
+    static_assert(TSDF_MAX_BLOCKS % TSDF_THREADS == 0, "whole rounds");
+    uint32_t vcarry = 0;
+    unsigned long long fcarry = 0;
+    for (int base = 0; base < blocks; base += TSDF_THREADS) {   // (uniform)
+        const int b = base + threadIdx.x;
+        const uint32_t cv = b < blocks ? M.vcount[b] : 0u, cf = b < blocks ? M.fcount[b] : 0u;
+        uint32_t tv = 0, tf = 0;
+        const uint32_t ev = scan_workgroup<TSDF_THREADS>(cv, sh, &tv);
+        const uint32_t ef = scan_workgroup<TSDF_THREADS>(cf, sh, &tf);
+        if (b < blocks) { M.vcount[b] = vcarry + ev; M.fbase[b] = fcarry + ef; }
+        vcarry += tv;
+        fcarry += tf;
+    }
+    if (threadIdx.x == 0) { M.totals[0] = vcarry; M.totals[1] = fcarry; }
+}
+
+template <bool COLOR>
+__global__ void __launch_bounds__(TSDF_THREADS) tsdf_vertices_kernel(MeshParams M) {
+    __shared__ uint32_t sh[SCAN_WORDS];
+    const uint32_t begin = blockIdx.x * M.span;
+    const uint32_t end = M.n - begin < M.span ? M.n : begin + M.span;
+    const uint32_t sy = (uint32_t)M.nx, sz = (uint32_t)M.nx * (uint32_t)M.ny;
+    uint32_t row0 = M.vcount[blockIdx.x];
+    for (uint32_t tile = begin; tile < end; tile += TSDF_THREADS) {   // (uniform: every thread reaches the scan)
+        const uint32_t s = tile + threadIdx.x;
+        const bool act = s < end && (M.flags[s] & CELL_ACTIVE);
+        uint32_t total = 0;
+        const uint32_t excl = scan_workgroup<TSDF_THREADS>(act ? 1u : 0u, sh, &total);
+        const uint32_t row = row0 + excl;
+        row0 += total;
+        if (!act) continue;
+        M.cellvert[s] = (int32_t)row;
+        if (row >= (uint32_t)M.vcap) continue;
+        uint32_t o[8];
+        float f[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            o[q] = s + ((q & 1) ? 1u : 0u) + ((q & 2) ? sy : 0u) + ((q & 4) ? sz : 0u);
+            f[q] = M.tsdf[o[q]];
+        }
+        float sum[3] = {0.f, 0.f, 0.f}, col[3] = {0.f, 0.f, 0.f};
+        int crossings = 0;
+        // the 12 edges: axis, then the two other offsets in (x before y before z) order, low bit first
+#pragma unroll
+        for (int e = 0; e < 12; e++) {
+            const int axis = e >> 2, lo_bit = e & 1, hi_bit = (e >> 1) & 1;
+            // corner number (dx | dy << 1 | dz << 2) of the edge's low end
+            const int c0 = axis == 0 ? (lo_bit << 1 | hi_bit << 2) : axis == 1 ? (lo_bit | hi_bit << 2) : (lo_bit | hi_bit << 1);
+            const int c1 = c0 | (1 << axis);
+            const float f0 = f[c0], f1 = f[c1];
+            if ((f0 < 0.f) == (f1 < 0.f)) continue;
+            const float q = f0 / (f0 - f1);
+#pragma unroll
+            for (int a = 0; a < 3; a++) sum[a] += a == axis ? q : (float)((c0 >> a) & 1);
+            if constexpr (COLOR) {
+                const float r0 = M.r[o[c0]], r1 = M.r[o[c1]], g0 = M.g[o[c0]], g1 = M.g[o[c1]], b0 = M.b[o[c0]], b1 = M.b[o[c1]];
+                col[0] += r0 + q * (r1 - r0);
+                col[1] += g0 + q * (g1 - g0);
+                col[2] += b0 + q * (b1 - b0);
+            }
+            crossings++;
+        }
+        const float cnt = (float)crossings;
+        const Sample c = sample_of(M, s);
+        const size_t out = (size_t)row * 3;
+        M.vertices[out + 0] = M.ox + M.vs * ((float)c.i + sum[0] / cnt);
+        M.vertices[out + 1] = M.oy + M.vs * ((float)c.j + sum[1] / cnt);
+        M.vertices[out + 2] = M.oz + M.vs * ((float)c.k + sum[2] / cnt);
+        if constexpr (COLOR) {
+            if (M.colors) {
+                M.colors[out + 0] = col[0] / cnt;
+                M.colors[out + 1] = col[1] / cnt;
+                M.colors[out + 2] = col[2] / cnt;
+            }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(TSDF_THREADS) tsdf_faces_kernel(MeshParams M) {
+    __shared__ uint32_t sh[SCAN_WORDS];
+    const uint32_t begin = blockIdx.x * M.span;
+    const uint32_t end = M.n - begin < M.span ? M.n : begin + M.span;
+    const uint32_t sy = (uint32_t)M.nx, sz = (uint32_t)M.nx * (uint32_t)M.ny;
+    unsigned long long row0 = M.fbase[blockIdx.x];
+    const unsigned long long cap = (unsigned long long)M.fcap;
+    for (uint32_t tile = begin; tile < end; tile += TSDF_THREADS) {   // (uniform)
+        const uint32_t s = tile + threadIdx.x;
+        const uint32_t e = s < end ? M.edges[s] : 0u;
+        uint32_t total = 0;
+        const uint32_t excl = scan_workgroup<TSDF_THREADS>(2u * (uint32_t)__popc(e & 7u), sh, &total);
+        unsigned long long row = row0 + excl;
+        row0 += total;
+        if (!(e & 7u) || row >= cap) continue;
+        const bool low_in = e & EDGE_LOW_INSIDE;
+        const int32_t own = M.cellvert[s];
+#pragma unroll
+        for (int axis = 0; axis < 3; axis++) {
+            if (!((e >> axis) & 1u)) continue;
+            const uint32_t sb = axis == 0 ? sy : axis == 1 ? sz : 1u, sc = axis == 0 ? sz : axis == 1 ? 1u : sy;   // strides of b and c
+            const int32_t v0 = M.cellvert[s - sb - sc], v1 = M.cellvert[s - sc], v2 = own, v3 = M.cellvert[s - sb];
+            const int32_t tri[2][3] = {{v0, low_in ? v1 : v2, low_in ? v2 : v1}, {v0, low_in ? v2 : v3, low_in ? v3 : v2}};
+#pragma unroll
+            for (int t = 0; t < 2; t++, row++) {
+                if (row >= cap) continue;
+                int32_t *dst = M.faces + (size_t)row * 3;
+                dst[0] = tri[t][0]; dst[1] = tri[t][1]; dst[2] = tri[t][2];
+            }
+        }
+    }
+}
+
+__global__ void tsdf_publish_kernel(MeshParams M) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    volatile int32_t *w = M.host;
+    const unsigned long long nv = M.totals[0], nf = M.totals[1];
+    const bool too_many = nf > (unsigned long long)INT32_MAX;
+    w[LVDGS_TSDF_N_VERTICES] = (int32_t)nv;
+    w[LVDGS_TSDF_N_FACES] = too_many ? INT32_MAX : (int32_t)nf;
+    w[LVDGS_TSDF_OVERFLOW] = (nv > (unsigned long long)M.vcap ? 1 : 0) | (nf > (unsigned long long)M.fcap ? 2 : 0) | (too_many ? 4 : 0);
+    for (int j = LVDGS_TSDF_OVERFLOW + 1; j < (int)(LVDGS_TSDF_HOST_BYTES / sizeof(int32_t)); j++) w[j] = 0;
+    seal_host_block(w, LVDGS_TSDF_SEQ, (int32_t)M.seq);
+}
+
+// the scratch: flags, edges (n bytes each), cellvert (n words), vcount, fcount (words), fbase (doublewords), totals
+struct MeshLayout { size_t flags, edges, cellvert, vcount, fcount, fbase, totals, bytes; };
+MeshLayout mesh_layout(size_t n) {
+    MeshLayout L{};
+    size_t at = 0;
+    L.flags = at; at += align256(n);
+    L.edges = at; at += align256(n);
+    L.cellvert = at; at += align256(n * sizeof(int32_t));
+    L.vcount = at; at += align256(TSDF_MAX_BLOCKS * sizeof(uint32_t));
+    L.fcount = at; at += align256(TSDF_MAX_BLOCKS * sizeof(uint32_t));
+    L.fbase = at; at += align256(TSDF_MAX_BLOCKS * sizeof(unsigned long long));
+    L.totals = at; at += 256;
+    L.bytes = at;
+    return L;
+}
+
+bool positive_finite(float v) { return v > 0.f && std::isfinite(v); }
+
+// dims >= least each and at most 2^31 - 1 samples
+int check_dims(const char *name, const lvdgs_tsdf_volume &v, int least) {
+    if (v.nx < least || v.ny < least || v.nz < least) {
+        set_error("%s: volume %dx%dx%d, every dimension must be at least %d", name, v.nx, v.ny, v.nz, least); return LVDGS_E_RANGE;
+    }
+    if ((int64_t)v.nx * v.ny > INT32_MAX || (int64_t)v.nx * v.ny * v.nz > INT32_MAX) {
+        set_error("%s: volume %dx%dx%d has more than 2^31 - 1 cells", name, v.nx, v.ny, v.nz); return LVDGS_E_RANGE;
+    }
+    return LVDGS_OK;
+}
+
+int check_planes(const char *name, const lvdgs_tsdf_volume &v) {
+    if (!v.tsdf || !v.weight) { set_error("%s: tsdf / weight plane is NULL", name); return LVDGS_E_INVALID; }
+    const int colours = (v.r ? 1 : 0) + (v.g ? 1 : 0) + (v.b ? 1 : 0);
+    if (colours != 0 && colours != 3) { set_error("%s: colour planes r, g, b must be all set or all NULL", name); return LVDGS_E_INVALID; }
+    return LVDGS_OK;
+}
+
+}  // namespace
+}  // namespace lvdgs
+
+using namespace lvdgs;
+
+extern "C" {
+
+int lvdgs_tsdf_integrate(const lvdgs_tsdf_volume *vol, const lvdgs_tsdf_view *const *views, int32_t count, void *stream) {
+    const char *name = "tsdf integrate";
+    if (!vol) { set_error("%s: volume is NULL", name); return LVDGS_E_INVALID; }
+    if (count < 0 || count > LVDGS_TSDF_MAX_VIEWS) { set_error("%s: count %d is outside 0 .. %d", name, count, LVDGS_TSDF_MAX_VIEWS); return LVDGS_E_INVALID; }
+    if (int e = check_planes(name, *vol)) return e;
+    if (int e = check_dims(name, *vol, 1)) return e;
+    if (!positive_finite(vol->voxel_size) || !positive_finite(vol->trunc) || !positive_finite(vol->max_weight)) {
+        set_error("%s: voxel_size %g, trunc %g and max_weight %g must be finite and positive", name, vol->voxel_size, vol->trunc, vol->max_weight);
+        return LVDGS_E_RANGE;
+    }
+    const dim3 grid(cdiv(vol->nx, BRICK_X), cdiv(vol->ny, BRICK_Y), cdiv(vol->nz, BRICK_Z));
+    if (grid.y > 65535u || grid.z > 65535u) { set_error("%s: ny or nz beyond 262140 (65535 bricks)", name); return LVDGS_E_RANGE; }
+    if (count > 0 && !views) { set_error("%s: view list is NULL", name); return LVDGS_E_INVALID; }
+    IntegrateParams p{};
+    for (int v = 0; v < count; v++) {
+        const lvdgs_tsdf_view *a = views[v];
+        if (!a) { set_error("%s: view %d is NULL", name, v); return LVDGS_E_INVALID; }
+        if (a->width < 1 || a->height < 1 || (int64_t)a->width * a->height > INT32_MAX) {
+            set_error("%s: view %d: image size %dx%d", name, v, a->width, a->height); return LVDGS_E_RANGE;
+        }
+        if (!a->R || !a->T || !a->depth) { set_error("%s: view %d: R / T / depth is NULL", name, v); return LVDGS_E_INVALID; }
+        if (a->image && !vol->r) { set_error("%s: view %d has an image, the volume no colour planes", name, v); return LVDGS_E_INVALID; }
+        p.v[v] = TsdfView{a->width, a->height, a->fx, a->fy, a->cx, a->cy, a->depth_min, a->depth_trunc, a->R, a->T, a->depth, a->image, a->mask};
+    }
+    if (count == 0) return LVDGS_OK;
+    p.nx = vol->nx; p.ny = vol->ny; p.nz = vol->nz; p.count = count;
+    p.ox = vol->origin[0]; p.oy = vol->origin[1]; p.oz = vol->origin[2];
+    p.vs = vol->voxel_size; p.trunc = vol->trunc; p.maxw = vol->max_weight;
+    p.tsdf = vol->tsdf; p.weight = vol->weight; p.r = vol->r; p.g = vol->g; p.b = vol->b;
+    const bool color = vol->r != nullptr;
+    const uintptr_t bits = (uintptr_t)vol->tsdf | (uintptr_t)vol->weight | (uintptr_t)vol->r | (uintptr_t)vol->g | (uintptr_t)vol->b;
+    const bool vec = vol->nx % 4 == 0 && (bits & 15u) == 0;
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps("tsdf_integrate", s);
+    const dim3 block(TSDF_THREADS);
+    if (color && vec) hipLaunchKernelGGL((tsdf_integrate_kernel<true, true>), grid, block, 0, s, p);
+    else if (color) hipLaunchKernelGGL((tsdf_integrate_kernel<true, false>), grid, block, 0, s, p);
+    else if (vec) hipLaunchKernelGGL((tsdf_integrate_kernel<false, true>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((tsdf_integrate_kernel<false, false>), grid, block, 0, s, p);
+    LVDGS_LAUNCH_CHECK("tsdf_integrate", 0, s);
+    return LVDGS_OK;
+}
+
+size_t lvdgs_tsdf_mesh_scratch_bytes(int32_t nx, int32_t ny, int32_t nz) {
+    if (nx < 2 || ny < 2 || nz < 2 || (int64_t)nx * ny > INT32_MAX || (int64_t)nx * ny * nz > INT32_MAX) return 0;
+    return mesh_layout((size_t)nx * ny * nz).bytes;
+}
+
+int lvdgs_tsdf_mesh(const lvdgs_tsdf_mesh_args *a, void *stream) {
+    const char *name = "tsdf mesh";
+    if (!a) { set_error("%s: args is NULL", name); return LVDGS_E_INVALID; }
+    const lvdgs_tsdf_volume &vol = a->vol;
+    if (int e = check_planes(name, vol)) return e;
+    if (int e = check_dims(name, vol, 2)) return e;
+    if (!positive_finite(vol.voxel_size)) { set_error("%s: voxel_size %g must be finite and positive", name, vol.voxel_size); return LVDGS_E_RANGE; }
+    if (a->vertex_capacity < 0 || a->face_capacity < 0) {
+        set_error("%s: negative capacity (%d vertices, %d faces)", name, a->vertex_capacity, a->face_capacity); return LVDGS_E_RANGE;
+    }
+    if (!a->vertices || !a->faces || !a->host_state || !a->scratch) {
+        set_error("%s: vertices / faces / host_state / scratch is NULL", name); return LVDGS_E_INVALID;
+    }
+    if (a->colors && !vol.r) { set_error("%s: colors asked for, the volume has no colour planes", name); return LVDGS_E_INVALID; }
+    const size_t n = (size_t)vol.nx * vol.ny * vol.nz;
+    const MeshLayout L = mesh_layout(n);
+    if (a->scratch_bytes < L.bytes) { set_error("%s: scratch too small", name); return LVDGS_E_INVALID; }
+    if ((uintptr_t)a->scratch & 7u) { set_error("%s: scratch must be 8-byte aligned", name); return LVDGS_E_INVALID; }
+    MeshParams M{};
+    M.nx = vol.nx; M.ny = vol.ny; M.nz = vol.nz; M.n = (uint32_t)n;
+    M.ox = vol.origin[0]; M.oy = vol.origin[1]; M.oz = vol.origin[2]; M.vs = vol.voxel_size;
+    M.tsdf = vol.tsdf; M.weight = vol.weight; M.r = vol.r; M.g = vol.g; M.b = vol.b;
+    M.vcap = a->vertex_capacity; M.fcap = a->face_capacity; M.seq = a->seq;
+    M.vertices = a->vertices; M.colors = a->colors; M.faces = a->faces;
+    char *base = reinterpret_cast<char *>(a->scratch);
+    M.flags = reinterpret_cast<uint8_t *>(base + L.flags);
+    M.edges = reinterpret_cast<uint8_t *>(base + L.edges);
+    M.cellvert = reinterpret_cast<int32_t *>(base + L.cellvert);
+    M.vcount = reinterpret_cast<uint32_t *>(base + L.vcount);
+    M.fcount = reinterpret_cast<uint32_t *>(base + L.fcount);
+    M.fbase = reinterpret_cast<unsigned long long *>(base + L.fbase);
+    M.totals = reinterpret_cast<unsigned long long *>(base + L.totals);
+    if (int e = host_block_address(a->host_state, name, &M.host)) return e;
+    // spans: as many as there are rounds of TSDF_THREADS samples, at most TSDF_MAX_BLOCKS; the last span may be short, none is empty
+    const size_t rounds = (n + TSDF_THREADS - 1) / TSDF_THREADS;
+    const size_t want = rounds < (size_t)TSDF_MAX_BLOCKS ? rounds : (size_t)TSDF_MAX_BLOCKS;
+    M.span = (uint32_t)((rounds + want - 1) / want * TSDF_THREADS);
+    const int blocks = (int)((n + M.span - 1) / M.span);
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(blocks), block(TSDF_THREADS);
+    {
+        ProfScope ps("tsdf_classify", s);
+        hipLaunchKernelGGL(tsdf_classify_kernel, grid, block, 0, s, M);
+        LVDGS_LAUNCH_CHECK("tsdf_classify", 0, s);
+    }
+    {
+        ProfScope ps("tsdf_edges", s);
+        hipLaunchKernelGGL(tsdf_edges_kernel, grid, block, 0, s, M);
+        LVDGS_LAUNCH_CHECK("tsdf_edges", 0, s);
+    }
+    {
+        ProfScope ps("tsdf_scan", s);
+        hipLaunchKernelGGL(tsdf_scan_kernel, dim3(1), block, 0, s, M, blocks);
+        LVDGS_LAUNCH_CHECK("tsdf_scan", 0, s);
+    }
+    {
+        ProfScope ps("tsdf_vertices", s);
+        if (vol.r) hipLaunchKernelGGL(tsdf_vertices_kernel<true>, grid, block, 0, s, M);
+        else hipLaunchKernelGGL(tsdf_vertices_kernel<false>, grid, block, 0, s, M);
+        LVDGS_LAUNCH_CHECK("tsdf_vertices", 0, s);
+    }
+    {
+        ProfScope ps("tsdf_faces", s);
+        hipLaunchKernelGGL(tsdf_faces_kernel, grid, block, 0, s, M);
+        LVDGS_LAUNCH_CHECK("tsdf_faces", 0, s);
+    }
+    ProfScope ps("tsdf_publish", s);
+    hipLaunchKernelGGL(tsdf_publish_kernel, dim3(1), dim3(WAVE), 0, s, M);
+    LVDGS_LAUNCH_CHECK("tsdf_publish", 0, s);
+    return LVDGS_OK;
+}
+
+}  // extern "C"

@@ -621,6 +621,60 @@ class SlamSequence:
             return {}
         return {k: float(np.mean([r[k] for r in rows if r.get(k) is not None])) for k in rows[0] if any(r.get(k) is not None for r in rows)}
 
+    def fuse_mesh(self, voxel_size, bounds=None, frames="keyframes", mask="static", depth_trunc=None, max_voxels=1 << 26):
+        """A surface of the finished map: the chosen frames rendered at their estimated poses with the run's ``render_fn``, their depth,
+        colour and -- ``mask="static"``, where a frame has one -- static mask fused into a TSDF volume (``tsdf.TsdfVolume``, 16 views per
+        library call, no wait), and the volume's surface-nets mesh (one wait).  What the reference's evaluation does with Open3D on the
+        host after copying every rendered depth map and image.
+
+        ``bounds``: (lo, hi) of the volume; default: the extent of the Gaussians with opacity at least 0.5 (all of them when none has),
+        padded by the truncation distance ``4 * voxel_size``.  ``frames``: "keyframes", "all" or frame indices.  ``mask``: "static" or None.
+        ``depth_trunc``: rendered depth beyond it is not fused (None: no limit).  ``max_voxels``: a volume that would hold more samples gets
+        a larger voxel size (``TsdfVolume.from_bounds``; the record says so).  -> (``tsdf.Mesh`` on the device, a record: dims, the
+        voxel size used and asked for, frames fused, vertex and face counts)."""
+        from .tsdf import TsdfVolume
+        gaussians = self.frontend_gaussians
+        if frames == "keyframes":
+            chosen = list(self.kf_indices)
+        elif frames == "all":
+            chosen = sorted(self.cameras)
+        else:
+            chosen = [int(i) for i in frames]
+        if mask not in ("static", None):
+            raise ValueError(f"fuse_mesh: mask 'static' or None, not {mask!r}")
+        with torch.no_grad():
+            xyz = gaussians.get_xyz.detach()
+            if bounds is None:
+                opaque = gaussians.get_opacity.detach().reshape(-1) >= 0.5
+                points = xyz[opaque] if bool(opaque.any()) else xyz
+                pad = 4.0 * float(voxel_size)
+                bounds = ((points.min(0).values - pad).tolist(), (points.max(0).values + pad).tolist())
+            volume = TsdfVolume.from_bounds(bounds[0], bounds[1], voxel_size, max_voxels=max_voxels, device=xyz.device)
+            views = []
+            for idx in chosen:
+                frame = self.cameras[idx]
+                pkg = self.render_fn(frame, gaussians, self.pipeline_params, self.background)
+                static = None
+                if mask == "static":
+                    static = getattr(frame, "expanded_static_mask", None)
+                    if static is None:
+                        static = getattr(frame, "static_mask", None)
+                    if static is not None:
+                        static = static.to(xyz.device)
+                depth = pkg["depth"].detach()
+                views.append(dict(depth=depth.reshape(depth.shape[-2], depth.shape[-1]).contiguous(), R=frame.R, T=frame.T,
+                                  intrinsics=(frame.fx, frame.fy, frame.cx, frame.cy), image=pkg["render"].detach().contiguous(), mask=static,
+                                  depth_trunc=float("inf") if depth_trunc is None else float(depth_trunc)))
+                if len(views) == 16:
+                    volume.integrate_views(views)
+                    views = []
+            if views:
+                volume.integrate_views(views)
+        mesh = volume.extract_mesh()
+        record = dict(dims=list(volume.dims), voxel_size=volume.voxel_size, voxel_size_requested=volume.voxel_size_requested,
+                      frames=len(chosen), vertices=int(mesh.vertices.shape[0]), faces=int(mesh.faces.shape[0]))
+        return mesh, record
+
     def summary(self):
         c, s = dict(self.counts), dict(self.seconds)
         ns = [n for _, n in self.gaussian_counts]

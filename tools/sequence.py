@@ -236,12 +236,17 @@ def main():
     ap.add_argument("--planes", choices=["host", "device"], default="host",
                     help="with --config --ingest fused: device makes the float32 depth planes on the GPU (lvdgs_ingest_depth) and the loops "
                          "take them without another upload")
+    ap.add_argument("--mesh", default=None, metavar="PATH",
+                    help="after the run: fuse the keyframes' rendered depth into a TSDF volume on the device (SlamSequence.fuse_mesh, "
+                         "lvdgs_tsdf_integrate / lvdgs_tsdf_mesh) and write the mesh as a binary PLY")
+    ap.add_argument("--mesh-voxel", type=float, default=None, metavar="SIZE",
+                    help="with --mesh: the voxel size (default: 1/192 of the longest side of the opaque Gaussians' extent)")
     ap.add_argument("--verbose", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     t0 = time.perf_counter()
     ev = (lambda e, s: print(f"  frame {s.counts['frames']:3d} {e:16s} N = {s._n()}", file=sys.stderr)) if a.verbose else None
-    out, _ = run_sequence(dev, a.frames, a.scale, a.cadence, False if a.no_fused else "auto", a.idle, a.refine, not a.no_masks, seed=a.seed,
+    out, seq = run_sequence(dev, a.frames, a.scale, a.cadence, False if a.no_fused else "auto", a.idle, a.refine, not a.no_masks, seed=a.seed,
                           window_size=a.window_size, on_event=ev, geometry=a.geometry, pcd_downsample=a.pcd_downsample,
                           mono_scale_drift=a.mono_scale_drift, eval_mode=a.eval_mode, **({"keyframe_depth": "patch_align"} if a.keyframe_depth == "patch_align" else {}),
                           **({"pose_init": a.pose_init} if a.pose_init else {}), **({"matcher": "descriptors"} if a.matcher == "descriptors" else {}),
@@ -256,6 +261,20 @@ def main():
         print("  frame {frame:3d} kf {keyframe:3d} inliers {inl:>5} init error {e:.4f} ({r:.3f} deg; previous pose {p:.4f}) tracking iterations {it}".format(
             frame=rec["frame"], keyframe=rec["keyframe"], inl=rec.get("inliers", "-"), e=rec["init_translation_error"], r=rec["init_rotation_error_deg"],
             p=rec["previous_translation_error"], it=rec["tracking_iterations"]), file=sys.stderr)
+    if a.mesh:
+        from lvdgs.tsdf import save_mesh_ply
+        voxel = a.mesh_voxel
+        if voxel is None:
+            g = seq.frontend_gaussians
+            xyz = g.get_xyz.detach()
+            opaque = g.get_opacity.detach().reshape(-1) >= 0.5
+            points = xyz[opaque] if bool(opaque.any()) else xyz
+            voxel = float((points.max(0).values - points.min(0).values).max()) / 192.0
+        t_mesh = time.perf_counter()
+        mesh, record = seq.fuse_mesh(voxel)
+        record["fuse_mesh_seconds"] = round(time.perf_counter() - t_mesh, 4)
+        save_mesh_ply(a.mesh, mesh)
+        out["mesh"] = dict(record, path=a.mesh, file_bytes=os.path.getsize(a.mesh))
     out["seed"] = a.seed
     out["tool_seconds"] = round(time.perf_counter() - t0, 2)
     print(json.dumps(out))
