@@ -14,7 +14,7 @@ from torch import nn
 from . import _lib
 
 
-_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}  # LVDGS_F32 / LVDGS_F16 / LVDGS_BF16
+_DTYPES = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
 
 
 def rope_2d(tokens: torch.Tensor, positions: torch.Tensor, base: float, fwd: float) -> None:

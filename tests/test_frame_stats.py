@@ -4,7 +4,6 @@ validation without a GPU.  The kernels themselves: tests/test_gpu_frame_stats.py
 import ctypes as C
 import os
 import re
-import subprocess
 from types import SimpleNamespace
 
 import numpy as np
@@ -97,30 +96,7 @@ def test_header_declares_and_library_exports_the_new_symbols():
     L = _lib.lib()
     for name in NEW_SYMBOLS:
         assert name in declared and name in _lib.EXPORTS and hasattr(L, name), name
-    text = open(HEADER).read()
-    enums = {k: int(v) for k, v in re.findall(r"\b(LVDGS_[A-Z_]+)\s*=\s*(\d+)", text)}
-    defines = {k: int(v) for k, v in re.findall(r"#define\s+(LVDGS_[A-Z_]+)\s+(\d+)", text)}
-    assert (enums["LVDGS_EDGE_MASK_MEDIAN"], enums["LVDGS_EDGE_MASK_BLOCKS"]) == (_lib.EDGE_MASK_MEDIAN, _lib.EDGE_MASK_BLOCKS)
-    assert (defines["LVDGS_FRAME_SUMMARY_MAX_ROWS"], defines["LVDGS_FRAME_SUMMARY_HOST_BYTES"]) == (_lib.FRAME_SUMMARY_MAX_ROWS, _lib.FRAME_SUMMARY_HOST_BYTES)
-    for k in ("SEQ", "MEDIAN", "SELECTED", "VISIBLE", "MASK_COUNT", "ROWS"):
-        assert enums["LVDGS_FRAME_SUMMARY_" + k] == getattr(_lib, "FRAME_SUMMARY_" + k), k
     assert 4 * (_lib.FRAME_SUMMARY_ROWS + 3 * _lib.FRAME_SUMMARY_MAX_ROWS) <= _lib.FRAME_SUMMARY_HOST_BYTES
-
-
-@pytest.mark.parametrize("ctype,cname", [("EdgeMaskArgs", "lvdgs_edge_mask_args"), ("FrameSummaryArgs", "lvdgs_frame_summary_args")])
-def test_ctypes_structs_match_the_c_layout(tmp_path, ctype, cname):
-    cls = getattr(_lib, ctype)
-    fields = [f for f, _ in cls._fields_]
-    lines = "\n".join(f'    printf("{f} %zu\\n", offsetof({cname}, {f}));' for f in fields)
-    src = tmp_path / "probe.c"
-    src.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "{HEADER}"\nint main(void) {{\n'
-                   f'    printf("sizeof %zu\\n", sizeof({cname}));\n{lines}\n    return 0;\n}}\n')
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-std=c11", "-o", str(exe), str(src)])
-    out = dict(line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())
-    assert int(out["sizeof"]) == C.sizeof(cls), ctype
-    for f in fields:
-        assert int(out[f]) == getattr(cls, f).offset, (ctype, f)
 
 
 def _refused(status, want):

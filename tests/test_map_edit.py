@@ -1,7 +1,5 @@
-"""Map edit without a GPU: the provenance oracle against the project's own host path, the argument blocks' layouts, the refusals."""
+"""Map edit without a GPU: the provenance oracle against the project's own host path, the refusals (the argument blocks' layouts: tests/test_abi.py)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,8 +10,6 @@ import map_edit_oracle as orc
 from lvdgs import _lib
 from lvdgs.gaussian_model import build_rotation
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "lvdgs.h")
 CPU_SIZES = (0, 1, 65, 1025)      # (the oracle and the host path are size-blind: the large sizes are the GPU tests')
 CASES = [(k, n, S, d) for k in cases.KINDS for n in CPU_SIZES for S, d in ((3, 3), (1, 0))] + [("mixed", 1023, 3, 0)]
 
@@ -94,36 +90,6 @@ def test_cases_cover_what_the_issue_names():
     assert all((o["kind"] == k).sum() > 10 for k in range(4)) and o["n_pruned_final"] > 10
     ties = np.nonzero((g == np.float32(case["max_grad"]))[:, 0])[0]
     assert np.isin(ties, o["src"][o["kind"] != orc.KEEP]).any()        # a tie is selected: >= at equality
-
-
-def _probe(tmp_path, cname, fields):
-    lines = "\n".join(f'    printf("{f} %zu\\n", offsetof({cname}, {c}));' for f, c in fields)
-    src = tmp_path / "probe.c"
-    src.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "{HEADER}"\nint main(void) {{\n'
-                   f'    printf("sizeof %zu\\n", sizeof({cname}));\n{lines}\n    return 0;\n}}\n')
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-std=c11", "-o", str(exe), str(src)])
-    return dict(line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())
-
-
-@pytest.mark.parametrize("ctype,cname", [("MapEditPlanArgs", "lvdgs_map_edit_plan_args"), ("MapEditApplyArgs", "lvdgs_map_edit_apply_args"),
-                                         ("MapEditColumn", "lvdgs_map_edit_column")])
-def test_argument_blocks_match_their_c_layout(tmp_path, ctype, cname):
-    cls = getattr(_lib, ctype)
-    fields = [(f, f.rstrip("_")) for f, _ in cls._fields_]       # (`in` is a Python keyword: the mirror calls it in_)
-    out = _probe(tmp_path, cname, fields)
-    assert int(out["sizeof"]) == C.sizeof(cls)
-    for f, _ in fields:
-        assert int(out[f]) == getattr(cls, f).offset, f
-
-
-def test_constants_match_the_header():
-    text = open(HEADER).read()
-    import re
-    val = lambda name: int(re.search(r"\b" + name + r"\s*=?\s+(\d+)", text).group(1))
-    for name in ("MAX_COLUMNS", "MAX_VIS_ROWS", "PRUNE", "DENSIFY", "KEEP", "CLONE", "SPLIT0", "SPLIT1", "COPY", "ZERO", "XYZ", "SCALE", "SEQ", "N_OUT",
-                 "N_KEEP", "N_CLONE", "N_SPLIT_SEL", "N_PRUNED_FINAL", "HOST_SRC"):
-        assert val("LVDGS_EDIT_" + name) == getattr(_lib, "EDIT_" + name), name
 
 
 def _plan_args():

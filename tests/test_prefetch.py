@@ -3,7 +3,6 @@ golden 48 x 32 trees, the host statement of the depth conversion and the refusal
 import ctypes as C
 import json
 import os
-import subprocess
 import threading
 
 import numpy as np
@@ -11,7 +10,7 @@ import pytest
 import torch
 
 from lvdgs import _lib, dataset as D
-from test_dataset import GOLDEN, HEADER, rebuild_tree, same_bits
+from test_dataset import GOLDEN, rebuild_tree, same_bits
 
 DIVISORS = (256.0, 5000.0, 6553.5, 5 * 6553.5)
 
@@ -186,22 +185,6 @@ def test_the_planes_of_a_tree_are_the_conversion_of_its_samples(golden, tmp_path
     assert samples.dtype == np.uint16
     assert same_bits(D.convert_depth_host(samples, ds.depth_scale), rec.depth.astype(np.float32))
     assert same_bits(D.convert_depth_host(ds.load_image(ds.mono_depth_paths[1]), ds.depth_scale * 5), rec.mono_depth.astype(np.float32))
-
-
-def test_ingest_depth_args_mirror_matches_the_c_layout(tmp_path):
-    fields = [f for f, _ in _lib.IngestDepthArgs._fields_]
-    lines = "\n".join(f'    printf("{f} %zu\\n", offsetof(lvdgs_ingest_depth_args, {f}));' for f in fields)
-    src = tmp_path / "probe.c"
-    src.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "{HEADER}"\nint main(void) {{\n'
-                   f'    printf("sizeof %zu\\n", sizeof(lvdgs_ingest_depth_args));\n{lines}\n'
-                   f'    printf("byte %d\\nword %d\\n", LVDGS_DEPTH_SAMPLE_BYTE, LVDGS_DEPTH_SAMPLE_WORD);\n    return 0;\n}}\n')
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-std=c11", "-o", str(exe), str(src)])
-    out = dict(line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())
-    assert int(out["sizeof"]) == C.sizeof(_lib.IngestDepthArgs)
-    for f in fields:
-        assert int(out[f]) == getattr(_lib.IngestDepthArgs, f).offset, f
-    assert (int(out["byte"]), int(out["word"])) == (_lib.DEPTH_SAMPLE_BYTE, _lib.DEPTH_SAMPLE_WORD)
 
 
 def valid_depth_args(**over):
