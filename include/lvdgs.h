@@ -1396,6 +1396,115 @@ int lvdgs_tsdf_integrate(const lvdgs_tsdf_volume *vol, const lvdgs_tsdf_view *co
 size_t lvdgs_tsdf_mesh_scratch_bytes(int32_t nx, int32_t ny, int32_t nz);
 int lvdgs_tsdf_mesh(const lvdgs_tsdf_mesh_args *a, void *stream);
 
+/* ---- Mesh scoring: area-weighted samples of a mesh and exact nearest neighbours between two clouds (what NICE-SLAM's eval_recon
+ * does with trimesh.sample.sample_surface and a SciPy KD-tree on the host, after copying both meshes there) ----
+ * lvdgs_mesh_sample draws num_samples points from (vertices (V,3) float32, faces (F,3) int32).  A function of (mesh, seed, sample
+ * index) alone: no generator state, the same bytes on every call.  In the order evaluated:
+ *   1. Area of face f with corners a, b, c = vertices[faces[f][0..2]], float64 from the float32 coordinates, no contraction:
+ *      e1 = b - a, e2 = c - a;  n = (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z, e1x*e2y - e1y*e2x);  A_f = 0.5 * sqrt((nx*nx + ny*ny) + nz*nz).
+ *      A face with an index outside 0 .. V-1, or whose A_f is not finite and > 0, has weight 0 (A_f := 0).
+ *   2. A_max = the maximum of the A_f (order-free).  q_f = (uint64) floor(A_f / A_max * 4294967296.0), float64: the largest face
+ *      gets 2^32, a weighted face may get 0 when it is 2^32 times smaller.  n_weighted = |{f: A_f > 0}|.
+ *   3. prefix[f] = q_0 + ... + q_f in uint64 (integers: exact in any order);  total = prefix[F-1] < 2^63.
+ *   4. Sample k:  k_j = key(3k + j), j = 0, 1, 2, with i = 3k + j in uint64 and seeding's fmix32:
+ *        key(i) = fmix32( fmix32((uint32)i + seed_lo) ^ (seed_hi + (uint32)(i >> 32)) ),   seed = seed_hi:seed_lo.
+ *      t = (uint64)(((k_0 << 32 | k_1) * total) >> 64) (the high half of the 128-bit product);  face = the first f with prefix[f] > t
+ *      (a face with q_f = 0 is never chosen);  u1 = k_2 >> 8,  u2 = k_1 & 0xFFFFFF (the low bits of k_1 move t by less than one
+ *      part in 2^32 of a face's interval);  if (u1 + u2 > 2^24) { u1 = 2^24 - u1; u2 = 2^24 - u2; } -- the fold, in integers, so
+ *      that no rounding of a sum decides it;  r1 = (float)u1 * 2^-24,  r2 = (float)u2 * 2^-24, both exact;
+ *      point[x] = (a[x] + r1 * (b[x] - a[x])) + r2 * (c[x] - a[x]) in float32 as written, y and z alike; colors, when vertex_colors
+ *      is given, by the same expression over the corners' colours;  face_index[k] = face.
+ * Outputs: points num_samples*3 float32; face_index num_samples int32 or NULL; colors num_samples*3 float32 or NULL (needs
+ * vertex_colors, V*3 float32).  info: the DEVICE address of one lvdgs_mesh_sample_info, 16 bytes: flags (LVDGS_MESH_SAMPLE_NO_AREA:
+ * no face has a positive weight -- nothing is sampled, points / face_index / colors are left untouched), n_weighted, total.
+ * Five launches, enqueued at once: areas with a maximum per span of faces, the weights with a sum per span, one workgroup's scan of
+ * the spans, the prefix (one workgroup scan per 256 faces, seeding's ordered compaction), the samples (a binary search each).  No
+ * atomics, no host wait, no copy.  scratch: the bytes lvdgs_mesh_sample_scratch_bytes(num_faces) gives (0: the size is refused), 8-byte
+ * aligned, no initialisation needed.  num_samples == 0: nothing to do.
+ * Before any launch -- LVDGS_E_INVALID: args, vertices, faces, points, info or scratch NULL; colors without vertex_colors; a negative
+ * count; num_vertices, num_faces or num_samples above 2^31 - 1; num_faces == 0; scratch too small or misaligned.
+ *
+ * lvdgs_cloud_distance: for each of num_queries points q_i the nearest of num_reference points r_j, EXACTLY:
+ *   d2_i = min over j of ((dx*dx + dy*dy) + dz*dz),  dx = q_i[x] - r_j[x], dy, dz alike, float32 as written, no contraction;
+ *   idx_i = the lowest j that attains it.
+ * A reference point with a non-finite coordinate never wins.  A query with a non-finite coordinate gets d2 = +inf, idx = -1 and is
+ * SKIPPED; with no usable reference point every query is skipped and LVDGS_CLOUD_DISTANCE_NO_REFERENCE is set.  Every other query
+ * is COUNTED.  The result does not depend on the grid below, on points_per_cell or on the order atomics arrive in.
+ * How it is found: the usable reference points' bounding box (a reduction), a uniform grid over it whose resolution one thread
+ * decides on the device from their number, the box, points_per_cell (<= 0: LVDGS_CLOUD_DISTANCE_POINTS_PER_CELL) and the cell
+ * budget of the scratch, at most LVDGS_CLOUD_DISTANCE_MAX_DIM cells along an axis; a counting sort of the reference points and of
+ * the queries (a query outside the box goes to the nearest cell) by cell -- integer atomic counts, workgroup scans, scatter.  A
+ * workgroup of one wave then takes one cell's queries and stages the reference points of the cell's 3 x 3 x 3 neighbourhood in LDS,
+ * 512 (8 KiB) at a time, once for up to 64 queries.  A query whose best is not below the neighbourhood's reach goes on alone: planes of
+ * cells outward from its own, rows outward within a plane, the row's run of cells that can still hold a nearer point.  A cell, row
+ * or plane is skipped only when it holds no point, or when L * 0.99999f > best, L = the float32 sum of squares of its per-axis gaps
+ * to the query, each gap taken to the cell's planes moved outward by slop[a] = h[a] / 256 + 1e-6f * (|lo[a]| + |hi[a]|): the cell
+ * index of a point, (p[a] - lo[a]) * (n[a] / extent[a]) truncated and clamped, is off by less than 1024 * 3 * 2^-24 < 1/256 of a
+ * cell, the planes lo[a] + c * h[a] by less than 3 * 2^-24 of |lo| + |hi|, and the per-point expression and L by less than 6 * 2^-24
+ * relative together -- so a skipped point's d2 is above the best, never equal to it.
+ * Outputs: d2 num_queries float32 or NULL; idx num_queries int32 or NULL; out_row: the DEVICE address of one lvdgs_cloud_distance_row,
+ * LVDGS_CLOUD_DISTANCE_ROW_BYTES bytes of the caller's table, written by the finishing launch:
+ *   sum_distance = the float64 sum of (double)sqrtf(d2) over the counted queries, sum_squared = of (double)d2, in a fixed order
+ *   (thread t of workgroup b takes queries b * chunk + t, + 256, ...; butterfly sums of the waves, the waves from 0 up, then thread
+ *   t of one finishing workgroup takes partials t, t + 256, ...): two calls give the same bits;  n_counted, n_skipped;
+ *   n_below[t] = |{counted: sqrtf(d2) < thresholds[t]}| for t < num_thresholds (0 beyond);  max_distance = the largest sqrtf(d2)
+ *   (0 when nothing is counted);  flags;  n_reference = the usable reference points;  reserved (0).
+ * num_queries == 0: nothing to do, the row is not written.  scratch: the bytes lvdgs_cloud_distance_scratch_bytes(num_queries,
+ * num_reference) gives (0: a count is refused), 16-byte aligned, no initialisation needed; out_row 8-byte aligned.  No host wait,
+ * no copy.
+ * Before any launch -- LVDGS_E_INVALID: args, queries, out_row or scratch NULL, reference NULL with num_reference > 0; a negative
+ * count or one above 2^31 - 1; num_thresholds outside 0 .. LVDGS_CLOUD_DISTANCE_MAX_THRESHOLDS; a threshold not finite and >= 0;
+ * scratch too small or misaligned. */
+#define LVDGS_MESH_SAMPLE_INFO_BYTES 16
+#define LVDGS_CLOUD_DISTANCE_ROW_BYTES 64
+#define LVDGS_CLOUD_DISTANCE_MAX_THRESHOLDS 4
+#define LVDGS_CLOUD_DISTANCE_POINTS_PER_CELL 8
+#define LVDGS_CLOUD_DISTANCE_MAX_DIM 1024
+enum { LVDGS_MESH_SAMPLE_NO_AREA = 1 };
+enum { LVDGS_CLOUD_DISTANCE_NO_REFERENCE = 1 };
+typedef struct lvdgs_mesh_sample_info {
+    uint32_t flags;
+    uint32_t n_weighted;
+    uint64_t total;
+} lvdgs_mesh_sample_info;
+typedef struct lvdgs_mesh_sample_args {
+    int64_t num_vertices, num_faces, num_samples;
+    uint64_t seed;
+    const float *vertices;        /* num_vertices*3                                 */
+    const int32_t *faces;         /* num_faces*3                                    */
+    const float *vertex_colors;   /* num_vertices*3, or NULL                        */
+    float *points;                /* out num_samples*3                              */
+    int32_t *face_index;          /* out num_samples, or NULL                       */
+    float *colors;                /* out num_samples*3, or NULL; needs vertex_colors */
+    void *info;                   /* device: one lvdgs_mesh_sample_info             */
+    void *scratch; size_t scratch_bytes;
+} lvdgs_mesh_sample_args;
+typedef struct lvdgs_cloud_distance_row {
+    double sum_distance, sum_squared;
+    uint32_t n_counted, n_skipped;
+    uint32_t n_below[LVDGS_CLOUD_DISTANCE_MAX_THRESHOLDS];
+    float max_distance;
+    uint32_t flags;
+    uint32_t n_reference;
+    uint32_t reserved[3];
+} lvdgs_cloud_distance_row;
+typedef struct lvdgs_cloud_distance_args {
+    int64_t num_queries, num_reference;
+    const float *queries;         /* num_queries*3                                  */
+    const float *reference;       /* num_reference*3                                */
+    int32_t num_thresholds;
+    int32_t points_per_cell;      /* <= 0: LVDGS_CLOUD_DISTANCE_POINTS_PER_CELL     */
+    float thresholds[LVDGS_CLOUD_DISTANCE_MAX_THRESHOLDS];
+    float *d2;                    /* out num_queries, or NULL                       */
+    int32_t *idx;                 /* out num_queries, or NULL                       */
+    void *out_row;                /* device: one lvdgs_cloud_distance_row           */
+    void *scratch; size_t scratch_bytes;
+} lvdgs_cloud_distance_args;
+size_t lvdgs_mesh_sample_scratch_bytes(int64_t num_faces);
+int lvdgs_mesh_sample(const lvdgs_mesh_sample_args *a, void *stream);
+size_t lvdgs_cloud_distance_scratch_bytes(int64_t num_queries, int64_t num_reference);
+int lvdgs_cloud_distance(const lvdgs_cloud_distance_args *a, void *stream);
+
 /* ---- diagnostics ---- */
 const char *lvdgs_last_error(void);
 const char *lvdgs_version(void);

@@ -16,6 +16,7 @@ Import as ``lvdgs`` (see ``/lvdgs.py``).  Submodules:
   gaussian_model     the Gaussian map (parameters, Adam groups, seeding, densify / prune)
   config_utils       load_config: the YAML settings with their inherit_from chain
   dataset            load_dataset: KITTI / waymo / dl3dv / replica / tum directories; a frame's undistortion and conversion (host or one HIP call)
+  mesh_eval          a mesh scored against ground-truth geometry: area-weighted samples, exact nearest neighbours, accuracy / completion / F-score
   ms_deform_attn     multi-scale deformable attention (GroundingDINO's ``groundingdino._C``); install() puts it in place
 
 Nothing here falls back to a CPU implementation: the HIP library

@@ -365,6 +365,51 @@ TSDF_SEQ, TSDF_N_VERTICES, TSDF_N_FACES, TSDF_OVERFLOW = 0, 1, 2, 3
 TSDF_OVERFLOW_VERTICES, TSDF_OVERFLOW_FACES, TSDF_OVERFLOW_INT32 = 1, 2, 4     # bits of the [TSDF_OVERFLOW] word
 
 
+class MeshSampleInfo(C.Structure):
+    _c_name_ = "lvdgs_mesh_sample_info"     # what one lvdgs_mesh_sample leaves at ``info``
+    _fields_ = [("flags", C.c_uint32), ("n_weighted", C.c_uint32), ("total", C.c_uint64)]
+
+
+class MeshSampleArgs(C.Structure):
+    _c_name_ = "lvdgs_mesh_sample_args"
+    _fields_ = [
+        ("num_vertices", C.c_int64), ("num_faces", C.c_int64), ("num_samples", C.c_int64), ("seed", C.c_uint64),
+        ("vertices", _fp), ("faces", _fp), ("vertex_colors", _fp), ("points", _fp), ("face_index", _fp), ("colors", _fp), ("info", _fp),
+        ("scratch", _fp), ("scratch_bytes", C.c_size_t),
+    ]
+
+
+MESH_SAMPLE_INFO_BYTES, MESH_SAMPLE_NO_AREA = 16, 1
+CLOUD_DISTANCE_ROW_BYTES, CLOUD_DISTANCE_MAX_THRESHOLDS, CLOUD_DISTANCE_POINTS_PER_CELL, CLOUD_DISTANCE_MAX_DIM = 64, 4, 8, 1024
+CLOUD_DISTANCE_NO_REFERENCE = 1
+MESH_SAMPLE_INFO_DTYPE = np.dtype([("flags", "<u4"), ("n_weighted", "<u4"), ("total", "<u8")])
+
+
+class CloudDistanceRow(C.Structure):
+    _c_name_ = "lvdgs_cloud_distance_row"     # what one lvdgs_cloud_distance leaves at ``out_row``
+    _fields_ = [
+        ("sum_distance", C.c_double), ("sum_squared", C.c_double), ("n_counted", C.c_uint32), ("n_skipped", C.c_uint32),
+        ("n_below", C.c_uint32 * CLOUD_DISTANCE_MAX_THRESHOLDS), ("max_distance", C.c_float), ("flags", C.c_uint32),
+        ("n_reference", C.c_uint32), ("reserved", C.c_uint32 * 3),
+    ]
+
+
+# the row as a NumPy record (same offsets as CloudDistanceRow)
+CLOUD_DISTANCE_ROW_DTYPE = np.dtype([("sum_distance", "<f8"), ("sum_squared", "<f8"), ("n_counted", "<u4"), ("n_skipped", "<u4"),
+                                     ("n_below", "<u4", (CLOUD_DISTANCE_MAX_THRESHOLDS,)), ("max_distance", "<f4"), ("flags", "<u4"),
+                                     ("n_reference", "<u4"), ("reserved", "<u4", (3,))])
+
+
+class CloudDistanceArgs(C.Structure):
+    _c_name_ = "lvdgs_cloud_distance_args"
+    _fields_ = [
+        ("num_queries", C.c_int64), ("num_reference", C.c_int64), ("queries", _fp), ("reference", _fp),
+        ("num_thresholds", C.c_int32), ("points_per_cell", C.c_int32), ("thresholds", C.c_float * CLOUD_DISTANCE_MAX_THRESHOLDS),
+        ("d2", _fp), ("idx", _fp), ("out_row", _fp),
+        ("scratch", _fp), ("scratch_bytes", C.c_size_t),
+    ]
+
+
 DEPTH_SAMPLE_BYTE, DEPTH_SAMPLE_WORD = 1, 2     # lvdgs_ingest_depth_args.sample_type
 MAP_OUTSIDE = -2 ** 31     # INT32_MIN in an undistortion map: the destination pixel's source lies outside
 
@@ -467,6 +512,10 @@ PROTOTYPES = {
     "lvdgs_tsdf_integrate": (_status, [_P(TsdfVolumeArgs), _P(_P(TsdfViewArgs)), _i32, _stream]),
     "lvdgs_tsdf_mesh_scratch_bytes": (_size, [_i32, _i32, _i32]),
     "lvdgs_tsdf_mesh": (_status, [_P(TsdfMeshArgs), _stream]),
+    "lvdgs_mesh_sample_scratch_bytes": (_size, [_i64]),
+    "lvdgs_mesh_sample": (_status, [_P(MeshSampleArgs), _stream]),
+    "lvdgs_cloud_distance_scratch_bytes": (_size, [_i64, _i64]),
+    "lvdgs_cloud_distance": (_status, [_P(CloudDistanceArgs), _stream]),
     "lvdgs_last_error": (C.c_char_p, []),
     "lvdgs_version": (C.c_char_p, []),
     "lvdgs_profile_enable": (None, [C.c_int]),

@@ -1,0 +1,265 @@
+"""A mesh scored against ground-truth geometry on the device: area-weighted samples of both surfaces and the exact nearest neighbour
+of every sample in the other cloud (HIP, ``csrc/mesh_eval.hip``; the rules: ``include/lvdgs.h``, "Mesh scoring").
+
+``sample_mesh``    ``lvdgs_mesh_sample``: ``n`` points as a function of (mesh, seed, sample index); no generator state, no wait.
+``nearest``        ``lvdgs_cloud_distance``: ``d2``, ``idx`` and one row of sums and counts in a device table; no wait, no copy.
+``score``          both samplings, both directed searches and ONE read of the table (one ``Stream.synchronize``): accuracy, completion,
+                   completion ratio, precision, recall, F-score, chamfer -- NICE-SLAM's ``eval_recon`` protocol.
+``load_mesh_ply``  what ``tsdf.save_mesh_ply`` wrote.
+
+What trimesh's ``sample_surface`` and a SciPy KD-tree do on the host after a copy of both meshes.  There is no CPU path: tensors that
+are not on a GPU raise ``LvdgsError``.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from .tsdf import Mesh
+
+_INT32_MAX = 2 ** 31 - 1
+_sample_scratch = _lib.DeviceScratch()
+_distance_scratch = _lib.DeviceScratch()
+_ROW, _INFO = _lib.CLOUD_DISTANCE_ROW_BYTES, _lib.MESH_SAMPLE_INFO_BYTES
+_score_tables = {}      # device index -> the Table of ``score``
+
+
+def _cuda_device(t, what):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise _lib.LvdgsError(f"{what} must be a tensor on a GPU (there is no CPU path)")
+    return t.device
+
+
+def _points(t, what, device=None):
+    """``t`` as a contiguous (P, 3) float32 tensor on its GPU."""
+    dev = _cuda_device(t, what)
+    if device is not None and dev != device:
+        raise _lib.LvdgsError(f"{what} is on {dev}, expected {device}")
+    if t.ndim != 2 or t.shape[1] != 3:
+        raise _lib.LvdgsError(f"{what} must have the shape (P, 3), not {tuple(t.shape)}")
+    if t.shape[0] > _INT32_MAX:
+        raise _lib.LvdgsError(f"{what}: more than 2^31 - 1 rows")
+    return _lib.f32(t, dev)
+
+
+def _mesh_parts(mesh):
+    """(vertices (V, 3) float32, faces (F, 3) int32, colours (V, 3) float32 or None) of a ``tsdf.Mesh`` or a (vertices, faces) pair."""
+    if isinstance(mesh, Mesh):
+        vertices, colors, faces = mesh
+    elif isinstance(mesh, (tuple, list)) and len(mesh) == 2:
+        (vertices, faces), colors = mesh, None
+    else:
+        raise _lib.LvdgsError("a mesh is a tsdf.Mesh or a (vertices, faces) pair")
+    vertices = _points(vertices, "mesh vertices")
+    dev = vertices.device
+    if not torch.is_tensor(faces) or faces.device != dev or faces.ndim != 2 or faces.shape[1] != 3 or faces.dtype.is_floating_point:
+        raise _lib.LvdgsError("mesh faces must be an (F, 3) integer tensor on the vertices' GPU")
+    faces = faces.detach()
+    if faces.dtype is not torch.int32 or not faces.is_contiguous():
+        faces = faces.to(torch.int32).contiguous()
+    if colors is not None:
+        colors = _points(colors, "mesh colours", dev)
+        if colors.shape[0] != vertices.shape[0]:
+            raise _lib.LvdgsError("mesh colours must have one row per vertex")
+    return vertices, faces, colors
+
+
+class Table:
+    """``rows`` cloud-distance rows followed by ``infos`` sampling info rows in ONE device buffer, and its one read."""
+
+    def __init__(self, device, rows=1, infos=0):
+        self.device, self.rows, self.infos = device, int(rows), int(infos)
+        self.buffer = torch.zeros(self.rows * _ROW + self.infos * _INFO, dtype=torch.uint8, device=device)
+        self.host = None      # pinned, made by the first read
+
+    def row_ptr(self, i):
+        assert 0 <= i < self.rows
+        return C.c_void_p(self.buffer.data_ptr() + i * _ROW)
+
+    def info_ptr(self, i):
+        assert 0 <= i < self.infos
+        return C.c_void_p(self.buffer.data_ptr() + self.rows * _ROW + i * _INFO)
+
+    def read(self):
+        """-> (the rows, the infos) as NumPy record arrays: one copy to pinned memory and THE one wait (``Stream.synchronize``)."""
+        if self.host is None:
+            self.host = torch.zeros(self.buffer.numel(), dtype=torch.uint8).pin_memory()
+        self.host.copy_(self.buffer, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        raw = self.host.numpy()
+        rows = raw[:self.rows * _ROW].view(_lib.CLOUD_DISTANCE_ROW_DTYPE).copy()
+        infos = raw[self.rows * _ROW:].view(_lib.MESH_SAMPLE_INFO_DTYPE).copy()
+        return rows, infos
+
+
+def sample_raw(vertices, faces, n, seed, points, info_ptr, vertex_colors=None, colors=None, face_index=None):
+    """One ``lvdgs_mesh_sample`` call into the caller's tensors; ``info_ptr``: a device address (``Table.info_ptr``).  No wait."""
+    dev = vertices.device
+    L = _lib.lib()
+    need = int(L.lvdgs_mesh_sample_scratch_bytes(int(faces.shape[0])))
+    scratch = _sample_scratch.get(dev, need)
+    a = _lib.MeshSampleArgs(num_vertices=int(vertices.shape[0]), num_faces=int(faces.shape[0]), num_samples=int(n),
+                            seed=int(seed) & (2 ** 64 - 1), vertices=vertices.data_ptr(), faces=faces.data_ptr(),
+                            vertex_colors=None if vertex_colors is None else vertex_colors.data_ptr(), points=points.data_ptr(),
+                            face_index=None if face_index is None else face_index.data_ptr(),
+                            colors=None if colors is None else colors.data_ptr(), info=info_ptr,
+                            scratch=scratch.data_ptr(), scratch_bytes=scratch.numel())
+    with _lib.on_device(dev):
+        _lib.check(L.lvdgs_mesh_sample(C.byref(a), _lib.raw_stream(dev)), "lvdgs_mesh_sample")
+
+
+def _sample(mesh, n, seed, info_ptr, want_colors=True):
+    vertices, faces, vcolors = _mesh_parts(mesh)
+    n = int(n)
+    if n < 0 or n > _INT32_MAX:
+        raise _lib.LvdgsError(f"sample_mesh: n = {n} is outside 0 .. 2^31 - 1")
+    if faces.shape[0] == 0:
+        raise _lib.LvdgsError("sample_mesh: the mesh has no faces")
+    dev = vertices.device
+    # NaN rows: a mesh without area leaves them, and the search skips them
+    points = torch.full((n, 3), math.nan, dtype=torch.float32, device=dev)
+    colors = torch.full((n, 3), math.nan, dtype=torch.float32, device=dev) if (vcolors is not None and want_colors) else None
+    sample_raw(vertices, faces, n, seed, points, info_ptr, vertex_colors=vcolors if colors is not None else None, colors=colors)
+    return points, colors
+
+
+def sample_mesh(mesh, n, seed=0):
+    """``n`` area-weighted samples of ``mesh`` (a ``tsdf.Mesh`` or a (vertices, faces) pair on a GPU): (n, 3) float32 points, and for a
+    mesh with vertex colours ``(points, colors)``.  The same bytes for the same (mesh, seed); no wait.  A mesh without any area
+    leaves every row NaN."""
+    vertices = mesh[0]
+    table = Table(_cuda_device(vertices, "mesh vertices"), rows=0, infos=1)
+    points, colors = _sample(mesh, n, seed, table.info_ptr(0))
+    return points if colors is None else (points, colors)
+
+
+def nearest(query, reference, thresholds=(), points_per_cell=0, want_d2=True, want_idx=True, table=None, row=0):
+    """For every row of ``query`` (M, 3) the nearest row of ``reference`` (N, 3): -> (``d2`` (M,) float32, ``idx`` (M,) int32, the
+    ``Table`` whose row ``row`` the call fills -- ``table.read()`` is the wait).  ``thresholds``: up to four distances whose counts
+    the row reports.  ``want_d2`` / ``want_idx`` False: None in their place, only the row is written."""
+    query = _points(query, "nearest: query")
+    dev = query.device
+    reference = _points(reference, "nearest: reference", dev)
+    thresholds = [float(t) for t in thresholds]
+    if len(thresholds) > _lib.CLOUD_DISTANCE_MAX_THRESHOLDS:
+        raise _lib.LvdgsError(f"nearest: at most {_lib.CLOUD_DISTANCE_MAX_THRESHOLDS} thresholds")
+    M, N = int(query.shape[0]), int(reference.shape[0])
+    L = _lib.lib()
+    scratch = _distance_scratch.get(dev, int(L.lvdgs_cloud_distance_scratch_bytes(M, N)))
+    table = Table(dev, rows=row + 1) if table is None else table
+    d2 = torch.empty(M, dtype=torch.float32, device=dev) if want_d2 else None
+    idx = torch.empty(M, dtype=torch.int32, device=dev) if want_idx else None
+    a = _lib.CloudDistanceArgs(num_queries=M, num_reference=N, queries=query.data_ptr(), reference=reference.data_ptr() if N else None,
+                               num_thresholds=len(thresholds), points_per_cell=int(points_per_cell),
+                               thresholds=(C.c_float * _lib.CLOUD_DISTANCE_MAX_THRESHOLDS)(*thresholds),
+                               d2=None if d2 is None else d2.data_ptr(), idx=None if idx is None else idx.data_ptr(),
+                               out_row=table.row_ptr(row), scratch=scratch.data_ptr(), scratch_bytes=scratch.numel())
+    with _lib.on_device(dev):
+        _lib.check(L.lvdgs_cloud_distance(C.byref(a), _lib.raw_stream(dev)), "lvdgs_cloud_distance")
+    return d2, idx, table
+
+
+def _ratio(a, b):
+    return float(a) / float(b) if b else math.nan
+
+
+def score_from_rows(est_to_gt, gt_to_est, threshold=None):
+    """The score's numbers from the two rows (records of ``CLOUD_DISTANCE_ROW_DTYPE``; ``n_below[0]`` counts the threshold).  A
+    direction in which nothing was counted gives NaN, not an exception."""
+    ne, ng = int(est_to_gt["n_counted"]), int(gt_to_est["n_counted"])
+    accuracy = _ratio(est_to_gt["sum_distance"], ne)
+    completion = _ratio(gt_to_est["sum_distance"], ng)
+    precision = _ratio(int(est_to_gt["n_below"][0]), ne)
+    recall = _ratio(int(gt_to_est["n_below"][0]), ng)
+    both = precision + recall
+    fscore = 2.0 * precision * recall / both if both > 0 else (math.nan if math.isnan(both) else 0.0)
+    return dict(accuracy=accuracy, completion=completion, completion_ratio=recall, precision=precision, recall=recall, fscore=fscore,
+                chamfer=0.5 * (accuracy + completion), n_est=ne, n_gt=ng,
+                skipped_est=int(est_to_gt["n_skipped"]), skipped_gt=int(gt_to_est["n_skipped"]),
+                flags_est=int(est_to_gt["flags"]), flags_gt=int(gt_to_est["flags"]),
+                max_est=float(est_to_gt["max_distance"]), max_gt=float(gt_to_est["max_distance"]),
+                threshold=None if threshold is None else float(threshold))
+
+
+MeshScore = dict      # what ``score`` returns: the keys of ``score_from_rows``
+
+
+def _is_cloud(x):
+    return torch.is_tensor(x)
+
+
+def score(est, gt, n_samples=200_000, threshold=0.05, seed=0, seed_gt=None, points_per_cell=0) -> MeshScore:
+    """``est`` against ``gt``, each a mesh (sampled: ``n_samples`` points, seeds ``seed`` and ``seed_gt``, default ``seed + 1``) or a
+    (P, 3) cloud (used as given).  accuracy: mean distance est -> gt; completion: gt -> est; completion_ratio = recall: the share of
+    gt samples nearer than ``threshold``; precision: the share of est samples; fscore; chamfer: the mean of the two means.  One
+    ``Stream.synchronize``, at the end, and no other wait."""
+    first = est if _is_cloud(est) else est[0]
+    dev = _cuda_device(first, "score: est")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    table = _score_tables.get(dev.index)
+    if table is None:
+        table = _score_tables[dev.index] = Table(dev, rows=2, infos=2)
+    table.buffer.zero_()      # a cloud given as such leaves its info row alone
+    seeds = (int(seed), int(seed) + 1 if seed_gt is None else int(seed_gt))
+    clouds = []
+    for slot, (what, seed_) in enumerate(zip((est, gt), seeds)):
+        if _is_cloud(what):
+            clouds.append(_points(what, "score: a cloud", dev))
+        else:
+            clouds.append(_sample(what, n_samples, seed_, table.info_ptr(slot), want_colors=False)[0])
+        if clouds[-1].shape[0] == 0:
+            raise _lib.LvdgsError("score: a cloud without points")
+    nearest(clouds[0], clouds[1], (threshold,), points_per_cell, want_d2=False, want_idx=False, table=table, row=0)
+    nearest(clouds[1], clouds[0], (threshold,), points_per_cell, want_d2=False, want_idx=False, table=table, row=1)
+    rows, infos = table.read()
+    for slot, name in enumerate(("est", "gt")):
+        if int(infos[slot]["flags"]) & _lib.MESH_SAMPLE_NO_AREA:
+            raise _lib.LvdgsError(f"score: the {name} mesh has no face with a positive area")
+    return score_from_rows(rows[0], rows[1], threshold)
+
+
+def load_mesh_ply(path, device="cuda") -> Mesh:
+    """The binary little-endian PLY that ``tsdf.save_mesh_ply`` writes, as a ``tsdf.Mesh`` on ``device``: vertices float32, colours (the
+    file's bytes / 255) or None, faces int32."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.find(b"end_header\n")
+    if not data.startswith(b"ply\n") or end < 0:
+        raise _lib.LvdgsError(f"{path}: not a PLY file")
+    header = data[:end].decode("ascii").split("\n")
+    body = data[end + len(b"end_header\n"):]
+    if "format binary_little_endian 1.0" not in header:
+        raise _lib.LvdgsError(f"{path}: only binary little-endian PLY is read")
+    counts, props, element = {}, {}, None
+    for line in header:
+        w = line.split()
+        if w[:1] == ["element"]:
+            element = w[1]
+            counts[element], props[element] = int(w[2]), []
+        elif w[:1] == ["property"] and element is not None:
+            props[element].append(w[1:])
+    kinds = {"float": "<f4", "uchar": "u1", "int": "<i4"}
+    try:
+        vdt = np.dtype([(p[-1], kinds[p[0]]) for p in props["vertex"]])
+        face_ok = props["face"] == [["list", "uchar", "int", "vertex_indices"]]
+    except KeyError as e:
+        raise _lib.LvdgsError(f"{path}: an element or property type save_mesh_ply does not write ({e})") from None
+    if not face_ok or not {"x", "y", "z"} <= set(vdt.names):
+        raise _lib.LvdgsError(f"{path}: not the layout save_mesh_ply writes")
+    nv, nf = counts["vertex"], counts["face"]
+    fdt = np.dtype([("n", "u1"), ("i", "<i4", (3,))])
+    if len(body) < nv * vdt.itemsize + nf * fdt.itemsize:
+        raise _lib.LvdgsError(f"{path}: the file is shorter than its header says")
+    v = np.frombuffer(body, dtype=vdt, count=nv)
+    f = np.frombuffer(body, dtype=fdt, count=nf, offset=nv * vdt.itemsize)
+    if nf and not (f["n"] == 3).all():
+        raise _lib.LvdgsError(f"{path}: a face that is no triangle")
+    vertices = np.stack([v["x"], v["y"], v["z"]], axis=1).astype(np.float32)
+    colors = None
+    if {"red", "green", "blue"} <= set(vdt.names):
+        colors = np.stack([v["red"], v["green"], v["blue"]], axis=1).astype(np.float32) / np.float32(255)
+    to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    return Mesh(to(vertices), None if colors is None else to(colors), to(f["i"].astype(np.int32).reshape(-1, 3)))

@@ -675,6 +675,89 @@ class SlamSequence:
                       frames=len(chosen), vertices=int(mesh.vertices.shape[0]), faces=int(mesh.faces.shape[0]))
         return mesh, record
 
+    def _chosen_frames(self, frames):
+        if frames == "keyframes":
+            return list(self.kf_indices)
+        return sorted(self.cameras) if frames == "all" else [int(i) for i in frames]
+
+    def _fuse_dataset_depth(self, volume, chosen, poses, depth_trunc):
+        """The chosen frames' dataset depth (``Camera.depth32``, or ``Camera.depth`` / the dataset's plane uploaded once) fused into ``volume`` at the
+        ground-truth poses (``poses="gt"``) or the estimated ones; a frame without depth is left out.  -> the frames fused."""
+        dev, views, fused = volume.device, [], 0
+        for idx in chosen:
+            frame = self.cameras[idx]
+            depth = getattr(frame, "depth32", None)
+            if depth is None:
+                depth = getattr(frame, "depth", None)
+            if depth is None:      # a finished frame has given its planes back (Camera.clean): the dataset still has them
+                record = self.dataset.frame(idx) if hasattr(self.dataset, "frame") else None
+                depth = None if record is None else record.depth32
+                if depth is None:
+                    depth = (self.dataset[idx] if record is None else record.frame)[1]
+            if depth is None:
+                continue
+            depth = torch.as_tensor(np.asarray(depth) if not torch.is_tensor(depth) else depth, dtype=torch.float32, device=dev)
+            depth = depth.detach().to(dev).reshape(int(frame.image_height), int(frame.image_width)).contiguous()
+            R, T = (frame.R_gt, frame.T_gt) if poses == "gt" else (frame.R, frame.T)
+            views.append(dict(depth=depth, R=R.detach().to(dev), T=T.detach().to(dev), intrinsics=(frame.fx, frame.fy, frame.cx, frame.cy),
+                              depth_trunc=float("inf") if depth_trunc is None else float(depth_trunc)))
+            fused += 1
+            if len(views) == 16:
+                volume.integrate_views(views)
+                views = []
+        if views:
+            volume.integrate_views(views)
+        return fused
+
+    def eval_mesh(self, voxel_size, bounds=None, frames="keyframes", n_samples=200_000, threshold=None, seed=0, seed_gt=None, mask="static",
+                  depth_trunc=None, max_voxels=1 << 26, est_depth="render"):
+        """The finished map's surface scored against ground-truth geometry (``mesh_eval.score``: accuracy, completion, completion ratio,
+        precision, recall, F-score, chamfer -- NICE-SLAM's ``eval_recon`` protocol), everything on the device.
+
+        The estimate is ``fuse_mesh``'s mesh as it stands (``est_depth="dataset"``: the dataset's depth fused at the ESTIMATED poses
+        instead of the rendered depth -- what the trajectory alone costs the surface).  The ground truth is a second volume of the same
+        bounds and voxel size, fused from the same frames' dataset depth at ``R_gt``, ``T_gt``.  ``threshold``: default twice the voxel
+        size actually used.  A dataset without metric depth (all-zero planes: the KITTI / dl3dv placeholders) gives an empty
+        ground-truth mesh, which raises ``LvdgsError``.  Three waits: one per mesh, one for the score.
+        -> (the score's dict, a record: both meshes' counts, the voxel size, the threshold, the samples and seeds)."""
+        from . import mesh_eval
+        from .tsdf import TsdfVolume
+        if est_depth not in ("render", "dataset"):
+            raise ValueError(f"eval_mesh: est_depth 'render' or 'dataset', not {est_depth!r}")
+        chosen = self._chosen_frames(frames)
+        gaussians = self.frontend_gaussians
+        with torch.no_grad():
+            xyz = gaussians.get_xyz.detach()
+            if bounds is None:      # fuse_mesh's default, taken here so that both volumes share it
+                opaque = gaussians.get_opacity.detach().reshape(-1) >= 0.5
+                points = xyz[opaque] if bool(opaque.any()) else xyz
+                pad = 4.0 * float(voxel_size)
+                bounds = ((points.min(0).values - pad).tolist(), (points.max(0).values + pad).tolist())
+            if est_depth == "render":
+                est, est_record = self.fuse_mesh(voxel_size, bounds=bounds, frames=chosen, mask=mask, depth_trunc=depth_trunc, max_voxels=max_voxels)
+            else:
+                volume = TsdfVolume.from_bounds(bounds[0], bounds[1], voxel_size, max_voxels=max_voxels, color=False, device=xyz.device)
+                fused = self._fuse_dataset_depth(volume, chosen, "estimated", depth_trunc)
+                est = volume.extract_mesh()
+                est_record = dict(dims=list(volume.dims), voxel_size=volume.voxel_size, voxel_size_requested=volume.voxel_size_requested,
+                                  frames=fused, vertices=int(est.vertices.shape[0]), faces=int(est.faces.shape[0]))
+            truth = TsdfVolume.from_bounds(bounds[0], bounds[1], voxel_size, max_voxels=max_voxels, color=False, device=xyz.device)
+            fused = self._fuse_dataset_depth(truth, chosen, "gt", depth_trunc)
+            gt = truth.extract_mesh()
+        gt_record = dict(dims=list(truth.dims), voxel_size=truth.voxel_size, frames=fused, vertices=int(gt.vertices.shape[0]), faces=int(gt.faces.shape[0]))
+        if gt_record["faces"] == 0:
+            raise _lib.LvdgsError(f"eval_mesh: the ground-truth mesh is empty ({fused} of {len(chosen)} frames have a depth plane and none of it "
+                                  "lies in the volume): a dataset without metric depth cannot score a mesh")
+        if est_record["faces"] == 0:
+            raise _lib.LvdgsError("eval_mesh: the estimated mesh is empty")
+        used = float(truth.voxel_size)
+        threshold = 2.0 * used if threshold is None else float(threshold)
+        result = mesh_eval.score(est, gt, n_samples=n_samples, threshold=threshold, seed=seed, seed_gt=seed_gt)
+        self.last_eval_meshes = (est, gt)
+        record = dict(est=est_record, gt=gt_record, est_depth=est_depth, voxel_size=used, threshold=threshold, n_samples=int(n_samples),
+                      seed=int(seed), seed_gt=int(seed) + 1 if seed_gt is None else int(seed_gt))
+        return result, record
+
     def summary(self):
         c, s = dict(self.counts), dict(self.seconds)
         ns = [n for _, n in self.gaussian_counts]

@@ -213,7 +213,8 @@ class SequenceDataset:
 
 
 def make_sequence(truth, render_fn, pipe, W, H, n_frames, device, fx=None, fy=None, cx=None, cy=None, seed=0, depth_noise=0.02,
-                  image_noise=0.0, dynamic_objects=False, step=0.02, sway=0.15, yaw=0.03, period=40.0, camera_cls=None, mono_scale_drift=0.0):
+                  image_noise=0.0, dynamic_objects=False, step=0.02, sway=0.15, yaw=0.03, period=40.0, camera_cls=None, mono_scale_drift=0.0,
+                  metric_depth=False):
     """``n_frames`` frames of ``vehicle_trajectory`` through the map ``truth`` (a GaussianModel), rendered ONCE by ``render_fn``
     (the product's ``render`` on the GPU, the dense float64 renderer in the CPU tests): image = clamped render (+ seeded pixel
     noise), mono depth = expected depth of the opaque pixels x (1 + ``depth_noise`` N(0,1)) -- a metric depth predictor's output,
@@ -222,7 +223,9 @@ def make_sequence(truth, render_fn, pipe, W, H, n_frames, device, fx=None, fy=No
     and marked dynamic in ``static_mask(idx)``.  ``mono_scale_drift``: frame i's mono depth is further multiplied by
     ``mono_scale_factor(i, mono_scale_drift)`` -- a monocular predictor's per-frame scale inconsistency, what the keyframe depth
     alignment (LVD-GS Algorithm 1) exists for; deterministic, no random draws (at 0 the dataset is bit-identical to one made without
-    it).  The factors are kept as ``dataset.mono_scales``."""
+    it).  The factors are kept as ``dataset.mono_scales``.  ``metric_depth``: the frames also carry the expected depth itself, without
+    noise or drift and 0 where the map is not opaque, as ``dataset[idx][1]`` -- a ground-truth depth sensor, what ``SlamSequence.eval_mesh``
+    fuses its ground-truth surface from (a monocular run reads no depth plane; no random draw is added or moved)."""
     if camera_cls is None:
         from .camera_utils import Camera as camera_cls
     fx = float(W) if fx is None else fx
@@ -232,7 +235,7 @@ def make_sequence(truth, render_fn, pipe, W, H, n_frames, device, fx=None, fy=No
     proj = getProjectionMatrix2(znear=0.01, zfar=100.0, fx=fx, fy=fy, cx=cx, cy=cy, W=W, H=H).transpose(0, 1)
     bg = torch.zeros(3, device=device)
     gen = torch.Generator().manual_seed(9000 + seed)
-    images, monos, masks = [], [], []
+    images, monos, masks, truths = [], [], [], []
     poses = vehicle_trajectory(n_frames, step, sway, yaw, period)
     for i, w2c in enumerate(poses):
         cam = camera_cls(i, torch.zeros(3, H, W, device=device), None, None, torch.eye(4), proj.to(device), fx, fy, cx, cy,
@@ -246,6 +249,8 @@ def make_sequence(truth, render_fn, pipe, W, H, n_frames, device, fx=None, fy=No
         img = img.clamp(0.0, 1.0)
         opac = pkg["opacity"][0].detach().float()
         depth = torch.where(opac > 0.5, pkg["depth"][0].detach().float() / opac.clamp(min=1e-3), torch.zeros_like(opac))
+        if metric_depth:
+            truths.append(depth.cpu().numpy().astype("float32"))
         depth = depth * (1.0 + depth_noise * torch.randn(H, W, generator=gen).to(depth.device))
         if mono_scale_drift:
             depth = depth * mono_scale_factor(i, mono_scale_drift)
@@ -256,7 +261,8 @@ def make_sequence(truth, render_fn, pipe, W, H, n_frames, device, fx=None, fy=No
             masks.append(m.to(device))
         images.append(img.contiguous().to(device))
         monos.append(depth.cpu().numpy().astype("float32"))
-    ds = SequenceDataset(images, monos, poses, W, H, fx, fy, cx, cy, device, static_masks=masks if dynamic_objects else None)
+    ds = SequenceDataset(images, monos, poses, W, H, fx, fy, cx, cy, device, depths=truths if metric_depth else None,
+                         static_masks=masks if dynamic_objects else None)
     ds.mono_scales = [mono_scale_factor(i, mono_scale_drift) if mono_scale_drift else 1.0 for i in range(len(poses))]
     if dynamic_objects:
         ds.dynamic_seeds = [100 * seed + i for i in range(len(poses))]      # dynamic_object_rectangles' seeds (RectangleDetector)

@@ -73,7 +73,7 @@ GEOMETRY = {"kitti07": dict(W=1226, H=370, fx=707.0912, cx=601.8873, cy=183.1104
 
 
 def kitti_sequence(dev, frames=60, scale=1.0, cadence="reference", masks=True, n_true=None, seed=0, training=None, window_size=None, geometry="kitti07",
-                   pcd_downsample=None, mono_scale_drift=0.0, trajectory=None):
+                   pcd_downsample=None, mono_scale_drift=0.0, trajectory=None, metric_depth=False):
     """(config, dataset, true map): a frame geometry of ``GEOMETRY`` (x ``scale``), the merged KITTI-07 config with the chosen cadence.
     ``trajectory``: ``synthetic.vehicle_trajectory``'s parameters (step, sway, yaw, period) laid over the default drive's."""
     geo = GEOMETRY[geometry]
@@ -97,7 +97,7 @@ def kitti_sequence(dev, frames=60, scale=1.0, cadence="reference", masks=True, n
     # of view is wider than the generator's (fx < W) and the camera moves
     truth = truth_model(W, H, n_true, 1.5 * scale, 16.0 * scale, 0.9, dev, seed=11 + seed)
     ds = synthetic.make_sequence(truth, render, PIPE, W, H, frames, dev, fx=fx, fy=fy, cx=cx, cy=cy, seed=seed, depth_noise=0.02,
-                                 image_noise=0.01, dynamic_objects=masks, mono_scale_drift=mono_scale_drift,
+                                 image_noise=0.01, dynamic_objects=masks, mono_scale_drift=mono_scale_drift, metric_depth=metric_depth,
                                  **{**dict(step=0.02, sway=0.15, yaw=0.03, period=40.0), **(trajectory or {})})
     return cfg, ds, truth
 
@@ -127,7 +127,7 @@ def directory_sequence(dev, config_path, dataset_path=None, ingest="host", caden
 
 def run_sequence(dev, frames=60, scale=1.0, cadence="reference", fused="auto", idle=10, refine=500, masks=True, seed=0, training=None,
                  window_size=None, on_event=None, geometry="kitti07", pcd_downsample=None, mono_scale_drift=0.0, trajectory=None,
-                 config_path=None, dataset_path=None, ingest="host", eval_mode="host", planes="host", **sequence_kwargs):
+                 config_path=None, dataset_path=None, ingest="host", eval_mode="host", planes="host", metric_depth=False, **sequence_kwargs):
     torch.manual_seed(seed)
     random.seed(seed)
     if config_path is not None:      # frames from a directory: at most ``frames`` of them
@@ -136,7 +136,8 @@ def run_sequence(dev, frames=60, scale=1.0, cadence="reference", fused="auto", i
         ds.num_imgs = min(len(ds), frames)
     else:
         cfg, ds, truth = kitti_sequence(dev, frames, scale, cadence, masks, seed=seed, training=training, window_size=window_size, geometry=geometry,
-                                        pcd_downsample=pcd_downsample, mono_scale_drift=mono_scale_drift, trajectory=trajectory)
+                                        pcd_downsample=pcd_downsample, mono_scale_drift=mono_scale_drift, trajectory=trajectory,
+                                        metric_depth=metric_depth)
         del truth
     m = empty_map(cfg, dev)
     if sequence_kwargs.get("matcher") == "descriptors":      # descriptor maps matched on the device (the network's stand-in: synthetic.WorldDescriptors)
@@ -240,7 +241,11 @@ def main():
                     help="after the run: fuse the keyframes' rendered depth into a TSDF volume on the device (SlamSequence.fuse_mesh, "
                          "lvdgs_tsdf_integrate / lvdgs_tsdf_mesh) and write the mesh as a binary PLY")
     ap.add_argument("--mesh-voxel", type=float, default=None, metavar="SIZE",
-                    help="with --mesh: the voxel size (default: 1/192 of the longest side of the opaque Gaussians' extent)")
+                    help="with --mesh / --mesh-eval: the voxel size (default: 1/192 of the longest side of the opaque Gaussians' extent)")
+    ap.add_argument("--mesh-eval", action="store_true",
+                    help="after the run: the fused mesh scored against a mesh fused from the dataset's depth at the ground-truth poses "
+                         "(SlamSequence.eval_mesh, lvdgs_mesh_sample / lvdgs_cloud_distance): accuracy, completion, F-score; needs no --mesh PATH")
+    ap.add_argument("--mesh-samples", type=int, default=200_000, metavar="N", help="with --mesh-eval: samples per mesh")
     ap.add_argument("--verbose", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -248,7 +253,7 @@ def main():
     ev = (lambda e, s: print(f"  frame {s.counts['frames']:3d} {e:16s} N = {s._n()}", file=sys.stderr)) if a.verbose else None
     out, seq = run_sequence(dev, a.frames, a.scale, a.cadence, False if a.no_fused else "auto", a.idle, a.refine, not a.no_masks, seed=a.seed,
                           window_size=a.window_size, on_event=ev, geometry=a.geometry, pcd_downsample=a.pcd_downsample,
-                          mono_scale_drift=a.mono_scale_drift, eval_mode=a.eval_mode, **({"keyframe_depth": "patch_align"} if a.keyframe_depth == "patch_align" else {}),
+                          mono_scale_drift=a.mono_scale_drift, eval_mode=a.eval_mode, metric_depth=a.mesh_eval, **({"keyframe_depth": "patch_align"} if a.keyframe_depth == "patch_align" else {}),
                           **({"pose_init": a.pose_init} if a.pose_init else {}), **({"matcher": "descriptors"} if a.matcher == "descriptors" else {}),
                           **({"scale_remedy": "matches"} if a.scale_remedy == "matches" else {}),
                           **({"frame_stats": "fused"} if a.frame_stats == "fused" else {}), **({"edge_mask": "fused"} if a.edge_mask == "fused" else {}),
@@ -261,20 +266,24 @@ def main():
         print("  frame {frame:3d} kf {keyframe:3d} inliers {inl:>5} init error {e:.4f} ({r:.3f} deg; previous pose {p:.4f}) tracking iterations {it}".format(
             frame=rec["frame"], keyframe=rec["keyframe"], inl=rec.get("inliers", "-"), e=rec["init_translation_error"], r=rec["init_rotation_error_deg"],
             p=rec["previous_translation_error"], it=rec["tracking_iterations"]), file=sys.stderr)
+    voxel = a.mesh_voxel
+    if (a.mesh or a.mesh_eval) and voxel is None:
+        g = seq.frontend_gaussians
+        xyz = g.get_xyz.detach()
+        opaque = g.get_opacity.detach().reshape(-1) >= 0.5
+        points = xyz[opaque] if bool(opaque.any()) else xyz
+        voxel = float((points.max(0).values - points.min(0).values).max()) / 192.0
     if a.mesh:
         from lvdgs.tsdf import save_mesh_ply
-        voxel = a.mesh_voxel
-        if voxel is None:
-            g = seq.frontend_gaussians
-            xyz = g.get_xyz.detach()
-            opaque = g.get_opacity.detach().reshape(-1) >= 0.5
-            points = xyz[opaque] if bool(opaque.any()) else xyz
-            voxel = float((points.max(0).values - points.min(0).values).max()) / 192.0
         t_mesh = time.perf_counter()
         mesh, record = seq.fuse_mesh(voxel)
         record["fuse_mesh_seconds"] = round(time.perf_counter() - t_mesh, 4)
         save_mesh_ply(a.mesh, mesh)
         out["mesh"] = dict(record, path=a.mesh, file_bytes=os.path.getsize(a.mesh))
+    if a.mesh_eval:
+        t_eval = time.perf_counter()
+        score, record = seq.eval_mesh(voxel, n_samples=a.mesh_samples)
+        out["mesh_eval"] = dict(score, record=record, eval_mesh_seconds=round(time.perf_counter() - t_eval, 4))
     out["seed"] = a.seed
     out["tool_seconds"] = round(time.perf_counter() - t0, 2)
     print(json.dumps(out))
