@@ -47,6 +47,11 @@ inline void tile_row_band(const lvdgs_args &a, int *row0, int *row1) {
     *row1 = a.tile_row_end < *row0 ? *row0 : (a.tile_row_end > gy ? gy : a.tile_row_end);
 }
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+// MurmurHash3's 32-bit finalizer, a bijection of uint32: what the keys of seeding.hip and mesh_eval.hip are built from
+__host__ __device__ inline uint32_t fmix32(uint32_t h) {
+    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+    return h;
+}
 
 // ---- error plumbing ----
 void set_error(const char *fmt, ...);

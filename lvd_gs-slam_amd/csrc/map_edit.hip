@@ -3,10 +3,9 @@
 // (semantics, the host block and the arithmetic order: include/lvdgs.h, DESIGN.md section "Map edit").
 //
 // The plan is an ordered compaction into four consecutive segments -- KEEP rows, CLONE rows, SPLIT0 rows, SPLIT1 rows, each ascending
-// by source -- and has seeding.hip's shape: every workgroup owns one contiguous span of source rows, classifies them once into one
-// code byte per row and counts its rows per segment; one workgroup scans the counts; the write pass walks each span again in tiles of
-// EDIT_THREADS rows with workgroup scans (device_utils.hpp) per tile and reads the code bytes, so the two passes cannot disagree.  No
-// atomic decides a position.  Launches, all enqueued at once: edit_count_kernel, edit_scan_kernel, edit_write_kernel (which also fills
+// by source -- as a span scan (spans.hpp) with five counters a span: the count pass classifies every source row once into one code
+// byte and counts the span's rows per segment; the write pass reads the code bytes, so the two passes cannot disagree, and runs one
+// tile walk per segment.  Launches, all enqueued at once: edit_count_kernel, edit_scan_kernel, edit_write_kernel (which also fills
 // the host block's src copy), edit_publish_kernel (the counts, the sequence word last).  With no rows: the scan and the publish only.
 //
 // Apply is a bandwidth kernel: blockIdx.y is the column, the lanes run over consecutive dwords (bytes, for rows or addresses that are
@@ -14,6 +13,7 @@
 #include "common.hpp"
 #include "device_utils.hpp"
 #include "map_edit_host.hpp"
+#include "spans.hpp"
 
 namespace lvdgs {
 namespace {
@@ -86,10 +86,9 @@ __device__ __forceinline__ uint8_t classify(const PlanParams &P, int64_t i) {
 
 __global__ void __launch_bounds__(EDIT_THREADS) edit_count_kernel(PlanParams P) {
     __shared__ uint32_t sh[SCAN_WORDS];
-    const int64_t begin = (int64_t)blockIdx.x * P.span;
-    const int64_t end = begin + P.span < P.N ? begin + P.span : P.N;
+    const SpanRange<int64_t> r = span_range((int64_t)P.N, P.span, blockIdx.x);
     uint32_t mine[EDIT_COUNTERS] = {0, 0, 0, 0, 0};
-    for (int64_t i = begin + threadIdx.x; i < end; i += EDIT_THREADS) {
+    for (int64_t i = r.begin + threadIdx.x; i < r.end; i += EDIT_THREADS) {
         const uint8_t c = classify(P, i);
         P.code[i] = c;
 #pragma unroll
@@ -107,16 +106,8 @@ __global__ void __launch_bounds__(EDIT_THREADS) edit_count_kernel(PlanParams P) 
 __global__ void __launch_bounds__(EDIT_THREADS) edit_scan_kernel(PlanParams P) {
     __shared__ uint32_t sh[SCAN_WORDS];
     for (int q = 0; q < EDIT_COUNTERS; q++) {
-        uint32_t carry = 0;
-        for (int base = 0; base < P.blocks; base += EDIT_THREADS) {   // (uniform)
-            const int j = base + threadIdx.x;
-            const uint32_t c = j < P.blocks ? P.counts[j * EDIT_COUNTERS + q] : 0u;
-            uint32_t total = 0;
-            const uint32_t excl = scan_workgroup<EDIT_THREADS>(c, sh, &total);
-            if (j < P.blocks) P.counts[j * EDIT_COUNTERS + q] = carry + excl;
-            carry += total;
-        }
-        if (threadIdx.x == 0) P.totals[q] = carry;
+        const uint32_t total = scan_span_counts<EDIT_THREADS>(P.counts + q, P.counts + q, P.blocks, EDIT_COUNTERS, sh);
+        if (threadIdx.x == 0) P.totals[q] = total;
     }
 }
 
@@ -132,24 +123,19 @@ __device__ __forceinline__ void put_row(const PlanParams &P, int64_t row, int64_
 
 __global__ void __launch_bounds__(EDIT_THREADS) edit_write_kernel(PlanParams P) {
     __shared__ uint32_t sh[SCAN_WORDS];
-    const int64_t begin = (int64_t)blockIdx.x * P.span;
-    const int64_t end = begin + P.span < P.N ? begin + P.span : P.N;
+    const SpanRange<int64_t> r = span_range((int64_t)P.N, P.span, blockIdx.x);
     const int64_t n_keep = P.totals[0], n_clone = P.totals[1], n_child = P.totals[2], n_sel = P.totals[3];
     const int64_t n_out = n_keep + n_clone + 2 * n_child;
     // first row of this span in each segment (the children's two segments share one count), and its first split rank
-    int64_t row[EDIT_SEGMENTS] = {(int64_t)P.counts[blockIdx.x * EDIT_COUNTERS + 0], n_keep + P.counts[blockIdx.x * EDIT_COUNTERS + 1],
-                                  n_keep + n_clone + P.counts[blockIdx.x * EDIT_COUNTERS + 2], (int64_t)P.counts[blockIdx.x * EDIT_COUNTERS + 3]};
-    for (int64_t base = begin; base < end; base += EDIT_THREADS) {   // (uniform: every thread reaches the scans)
+    const uint32_t *front = P.counts + blockIdx.x * EDIT_COUNTERS;
+    TileWalk<EDIT_THREADS, uint32_t, int64_t> walk[EDIT_SEGMENTS] = {{(int64_t)front[0]}, {n_keep + front[1]}, {n_keep + n_clone + front[2]},
+                                                                     {(int64_t)front[3]}};
+    for (int64_t base = r.begin; base < r.end; base += EDIT_THREADS) {   // (uniform)
         const int64_t i = base + threadIdx.x;
-        const uint8_t c = i < end ? P.code[i] : 0;
+        const uint8_t c = i < r.end ? P.code[i] : 0;
         int64_t at[EDIT_SEGMENTS];
 #pragma unroll
-        for (int q = 0; q < EDIT_SEGMENTS; q++) {
-            uint32_t total = 0;
-            const uint32_t excl = scan_workgroup<EDIT_THREADS>((uint32_t)((c >> q) & 1u), sh, &total);
-            at[q] = row[q] + excl;
-            row[q] += total;
-        }
+        for (int q = 0; q < EDIT_SEGMENTS; q++) at[q] = walk[q].place((uint32_t)((c >> q) & 1u), sh);
         if (c & CODE_KEEP) put_row(P, at[0], n_out, i, LVDGS_EDIT_KEEP, -1);
         if (c & CODE_CLONE) put_row(P, at[1], n_out, i, LVDGS_EDIT_CLONE, -1);
         if (c & CODE_CHILDREN) {
@@ -249,7 +235,8 @@ int lvdgs_map_edit_plan(const lvdgs_map_edit_plan_args *a, void *stream) {
     if (int e = edit_check_plan(a)) return e;
     PlanParams P{};
     P.mode = a->mode; P.N = a->num_gaussians; P.S = a->scale_dims; P.capacity = a->capacity; P.seq = a->seq;
-    edit_spans(P.N, &P.blocks, &P.span);
+    const Spans spans = edit_spans(P.N);
+    P.blocks = spans.blocks; P.span = spans.span;
     P.remove = a->mode == LVDGS_EDIT_PRUNE ? a->remove : nullptr;
     P.num_vis = a->num_vis_rows; P.vis_stride = a->vis_stride ? a->vis_stride : 1; P.prune_num = a->prune_num; P.min_kf_id = a->min_kf_id;
     for (int k = 0; k < LVDGS_EDIT_MAX_VIS_ROWS; k++) P.vis[k] = a->vis_rows[k];

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/lvdgs.h"
+#include "spans.hpp"
 
 namespace lvdgs {
 
@@ -27,14 +28,8 @@ inline EditLayout edit_layout(int32_t N) {
     return L;
 }
 
-// the spans of a plan over N > 0 rows: `blocks` workgroups of `span` rows each (a multiple of EDIT_THREADS); N == 0: none
-inline void edit_spans(int32_t N, int *blocks, int64_t *span) {
-    if (N <= 0) { *blocks = 0; *span = EDIT_THREADS; return; }
-    int64_t b = ((int64_t)N + EDIT_THREADS - 1) / EDIT_THREADS;
-    if (b > EDIT_MAX_BLOCKS) b = EDIT_MAX_BLOCKS;
-    *blocks = (int)b;
-    *span = (((int64_t)N + b - 1) / b + EDIT_THREADS - 1) / EDIT_THREADS * EDIT_THREADS;
-}
+// the spans of a plan over N rows (spans.hpp)
+inline Spans edit_spans(int32_t N) { return make_spans(N, EDIT_THREADS, EDIT_MAX_BLOCKS, EDIT_THREADS); }
 
 inline int edit_check_plan(const lvdgs_map_edit_plan_args *a) {
     if (!a) { set_error("map edit plan: args is NULL"); return LVDGS_E_INVALID; }

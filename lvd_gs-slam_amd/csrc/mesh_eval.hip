@@ -1,13 +1,12 @@
 // Mesh scoring: area-weighted samples of a triangle mesh and exact nearest neighbours between two point clouds (rules, arithmetic and
 // the rows: include/lvdgs.h, "Mesh scoring").
 //
-// lvdgs_mesh_sample: five launches.  Every workgroup owns one contiguous span of faces (tsdf.hip's spans): float64 areas and the
-// span's maximum; the integer weights q and the span's sum; one workgroup's scan of the span sums; the inclusive prefix, one
-// workgroup scan per 256 faces, written over the weights; one thread per sample (three keys, a binary search, one triangle).
-// Integer decisions only, no atomics: two calls give the same bytes.
+// lvdgs_mesh_sample: five launches.  Float64 areas and the maximum per span of faces; then a span scan (spans.hpp) of the integer
+// weights q, in 64 bits, whose write pass leaves the inclusive prefix over the weights; one thread per sample (three keys, a binary
+// search, one triangle).  Integer decisions only, no atomics: two calls give the same bytes.
 //
 // lvdgs_cloud_distance: the reference points' box (two launches), a grid decided by one thread, a counting sort of both clouds by
-// cell (zero, count, three scan launches over the cells, scatter), the search -- a workgroup of ONE wave per cell of queries, the
+// cell (zero, count, a span scan over the cells, scatter), the search -- a workgroup of ONE wave per cell of queries, the
 // cell's neighbourhood staged in LDS 512 points at a time --, and the row (two launches).  The cells are numbered
 // x fastest, so the points of a run of cells along x lie side by side in the sorted array and start[] of the run's ends says how
 // many there are: a row's or a plane's emptiness costs two loads.  The order of the points inside a cell depends on how the
@@ -19,20 +18,17 @@
 
 #include "common.hpp"
 #include "device_utils.hpp"
+#include "spans.hpp"
 
 namespace lvdgs {
 namespace {
 
 constexpr int ME_THREADS = 256;
-constexpr int ME_MAX_BLOCKS = 2048;   // spans of the sampling passes (a multiple of ME_THREADS: whole scan rounds)
+constexpr int ME_MAX_BLOCKS = 2048;   // spans of the sampling passes
 typedef unsigned long long u64;
 
 // ---------------------------------------------------------------- sampling ----
 
-__device__ __forceinline__ uint32_t fmix32(uint32_t h) {   // seeding.hip's
-    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-    return h;
-}
 __device__ __forceinline__ uint32_t sample_key(u64 i, uint32_t seed_lo, uint32_t seed_hi) {
     return fmix32(fmix32((uint32_t)i + seed_lo) ^ (seed_hi + (uint32_t)(i >> 32)));
 }
@@ -54,10 +50,9 @@ struct SampleParams {
 
 __global__ void __launch_bounds__(ME_THREADS) sample_area_kernel(SampleParams P) {
     __shared__ double s_max[ME_THREADS / 64];
-    const uint32_t begin = blockIdx.x * P.span;
-    const uint32_t end = P.F - begin < P.span ? P.F : begin + P.span;
+    const SpanRange<uint32_t> r = span_range(P.F, P.span, blockIdx.x);
     double mine = 0.0;
-    for (uint32_t f = begin + threadIdx.x; f < end; f += ME_THREADS) {
+    for (uint32_t f = r.begin + threadIdx.x; f < r.end; f += ME_THREADS) {
         const int32_t ia = P.faces[3 * (size_t)f], ib = P.faces[3 * (size_t)f + 1], ic = P.faces[3 * (size_t)f + 2];
         double A = 0.0;
         if ((uint32_t)ia < P.V && (uint32_t)ib < P.V && (uint32_t)ic < P.V) {
@@ -96,12 +91,11 @@ __global__ void __launch_bounds__(ME_THREADS) sample_weight_kernel(SampleParams 
     amax = s_max[0];
     for (int w = 1; w < ME_THREADS / 64; w++) amax = fmax(amax, s_max[w]);
 
-    const uint32_t begin = blockIdx.x * P.span;
-    const uint32_t end = P.F - begin < P.span ? P.F : begin + P.span;
+    const SpanRange<uint32_t> r = span_range(P.F, P.span, blockIdx.x);
     u64 mine = 0;
     uint32_t weighted = 0;
     u64 *q = reinterpret_cast<u64 *>(P.area);
-    for (uint32_t f = begin + threadIdx.x; f < end; f += ME_THREADS) {
+    for (uint32_t f = r.begin + threadIdx.x; f < r.end; f += ME_THREADS) {
         const double A = P.area[f];
         const u64 w = A > 0.0 ? (u64)floor(A / amax * 4294967296.0) : 0ull;   // (amax >= A > 0)
         q[f] = w;
@@ -119,21 +113,8 @@ __global__ void __launch_bounds__(ME_THREADS) sample_weight_kernel(SampleParams 
 __global__ void __launch_bounds__(ME_THREADS) sample_scan_kernel(SampleParams P, int blocks) {
     __shared__ u64 sh[SCAN_WORDS];
     __shared__ uint32_t sh32[SCAN_WORDS];
-    static_assert(ME_MAX_BLOCKS % ME_THREADS == 0, "whole rounds");
-    u64 carry = 0;
-    uint32_t weighted = 0;
-    for (int base = 0; base < blocks; base += ME_THREADS) {   // (uniform)
-        const int b = base + threadIdx.x;
-        const u64 s = b < blocks ? P.bsum[b] : 0ull;
-        const uint32_t c = b < blocks ? P.bcount[b] : 0u;
-        u64 ts = 0;
-        uint32_t tc = 0;
-        const u64 es = scan_workgroup<ME_THREADS>(s, sh, &ts);
-        scan_workgroup<ME_THREADS>(c, sh32, &tc);
-        if (b < blocks) P.bsum[b] = carry + es;
-        carry += ts;
-        weighted += tc;
-    }
+    const u64 carry = scan_span_counts<ME_THREADS>(P.bsum, P.bsum, blocks, 1, sh);
+    const uint32_t weighted = scan_span_counts<ME_THREADS>(P.bcount, P.bcount, blocks, 1, sh32);   // (for its total alone)
     if (threadIdx.x == 0) {
         P.totals[0] = carry;
         P.info->flags = carry == 0ull ? LVDGS_MESH_SAMPLE_NO_AREA : 0u;
@@ -144,17 +125,14 @@ __global__ void __launch_bounds__(ME_THREADS) sample_scan_kernel(SampleParams P,
 
 __global__ void __launch_bounds__(ME_THREADS) sample_prefix_kernel(SampleParams P) {
     __shared__ u64 sh[SCAN_WORDS];
-    const uint32_t begin = blockIdx.x * P.span;
-    const uint32_t end = P.F - begin < P.span ? P.F : begin + P.span;
+    const SpanRange<uint32_t> r = span_range(P.F, P.span, blockIdx.x);
     u64 *q = reinterpret_cast<u64 *>(P.area);
-    u64 row0 = P.bsum[blockIdx.x];
-    for (uint32_t tile = begin; tile < end; tile += ME_THREADS) {   // (uniform: every thread reaches the scan)
+    TileWalk<ME_THREADS, u64> walk{P.bsum[blockIdx.x]};
+    for (uint32_t tile = r.begin; tile < r.end; tile += ME_THREADS) {   // (uniform)
         const uint32_t f = tile + threadIdx.x;
-        const u64 w = f < end ? q[f] : 0ull;
-        u64 total = 0;
-        const u64 excl = scan_workgroup<ME_THREADS>(w, sh, &total);
-        if (f < end) q[f] = row0 + excl + w;
-        row0 += total;
+        const u64 w = f < r.end ? q[f] : 0ull;
+        const u64 before = walk.place(w, sh);
+        if (f < r.end) q[f] = before + w;
     }
 }
 
@@ -247,67 +225,51 @@ __device__ __forceinline__ bool finite3(float x, float y, float z) {
     return fabsf(x) < inf && fabsf(y) < inf && fabsf(z) < inf;   // (NaN fails)
 }
 
+// The fold of one partial box per thread over the workgroup, valid in thread 0: wave minima, maxima and sums, then the waves from 0
+// up (all exact: any order gives the same box).  s_box: one per wave.
+__device__ __forceinline__ BoxPartial empty_box() {
+    const float inf = __builtin_inff();
+    return BoxPartial{{inf, inf, inf}, {-inf, -inf, -inf}, 0u, 0u};
+}
+__device__ __forceinline__ void box_join(BoxPartial &b, const BoxPartial &q) {
+#pragma unroll
+    for (int a = 0; a < 3; a++) { b.lo[a] = fminf(b.lo[a], q.lo[a]); b.hi[a] = fmaxf(b.hi[a], q.hi[a]); }
+    b.count += q.count;
+}
+__device__ __forceinline__ BoxPartial workgroup_box(BoxPartial b, BoxPartial *s_box) {
+#pragma unroll
+    for (int a = 0; a < 3; a++) { b.lo[a] = wave_min(b.lo[a]); b.hi[a] = wave_max(b.hi[a]); }
+    b.count = wave_sum(b.count);
+    if ((threadIdx.x & 63) == 0) s_box[threadIdx.x >> 6] = b;
+    __syncthreads();
+    if (threadIdx.x != 0) return b;
+    BoxPartial out = s_box[0];
+    for (int w = 1; w < ME_THREADS / 64; w++) box_join(out, s_box[w]);
+    return out;
+}
+
 __global__ void __launch_bounds__(ME_THREADS) cloud_box_kernel(CloudParams P) {
     __shared__ BoxPartial s_box[ME_THREADS / 64];
-    const float inf = __builtin_inff();
-    float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
-    uint32_t count = 0;
+    BoxPartial mine = empty_box();
     for (uint32_t j = blockIdx.x * ME_THREADS + threadIdx.x; j < P.N; j += gridDim.x * ME_THREADS) {
         const float x = P.reference[3 * (size_t)j], y = P.reference[3 * (size_t)j + 1], z = P.reference[3 * (size_t)j + 2];
-        if (!finite3(x, y, z)) continue;
-        lo[0] = fminf(lo[0], x); lo[1] = fminf(lo[1], y); lo[2] = fminf(lo[2], z);
-        hi[0] = fmaxf(hi[0], x); hi[1] = fmaxf(hi[1], y); hi[2] = fmaxf(hi[2], z);
-        count++;
+        if (finite3(x, y, z)) box_join(mine, BoxPartial{{x, y, z}, {x, y, z}, 1u, 0u});
     }
-#pragma unroll
-    for (int a = 0; a < 3; a++) { lo[a] = wave_min(lo[a]); hi[a] = wave_max(hi[a]); }
-    count = wave_sum(count);
-    if ((threadIdx.x & 63) == 0) {
-        BoxPartial &b = s_box[threadIdx.x >> 6];
-#pragma unroll
-        for (int a = 0; a < 3; a++) { b.lo[a] = lo[a]; b.hi[a] = hi[a]; }
-        b.count = count; b.pad = 0;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        BoxPartial out = s_box[0];
-        for (int w = 1; w < ME_THREADS / 64; w++) {
-            for (int a = 0; a < 3; a++) { out.lo[a] = fminf(out.lo[a], s_box[w].lo[a]); out.hi[a] = fmaxf(out.hi[a], s_box[w].hi[a]); }
-            out.count += s_box[w].count;
-        }
-        P.box[blockIdx.x] = out;
-    }
+    const BoxPartial out = workgroup_box(mine, s_box);
+    if (threadIdx.x == 0) P.box[blockIdx.x] = out;
 }
 
 // One workgroup: the box of the `blocks` partial boxes, then thread 0 decides the grid.
 __global__ void __launch_bounds__(ME_THREADS) cloud_grid_kernel(CloudParams P, int blocks) {
     __shared__ BoxPartial s_box[ME_THREADS / 64];
     const float inf = __builtin_inff();
-    float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
-    uint32_t count = 0;
-    for (int b = threadIdx.x; b < blocks; b += ME_THREADS) {
-        const BoxPartial q = P.box[b];
-#pragma unroll
-        for (int a = 0; a < 3; a++) { lo[a] = fminf(lo[a], q.lo[a]); hi[a] = fmaxf(hi[a], q.hi[a]); }
-        count += q.count;
-    }
-#pragma unroll
-    for (int a = 0; a < 3; a++) { lo[a] = wave_min(lo[a]); hi[a] = wave_max(hi[a]); }
-    count = wave_sum(count);
-    if ((threadIdx.x & 63) == 0) {
-        BoxPartial &b = s_box[threadIdx.x >> 6];
-#pragma unroll
-        for (int a = 0; a < 3; a++) { b.lo[a] = lo[a]; b.hi[a] = hi[a]; }
-        b.count = count; b.pad = 0;
-    }
-    __syncthreads();
+    BoxPartial mine = empty_box();
+    for (int b = threadIdx.x; b < blocks; b += ME_THREADS) box_join(mine, P.box[b]);
+    const BoxPartial all = workgroup_box(mine, s_box);
     if (threadIdx.x != 0) return;
     Grid G{};
-    for (int a = 0; a < 3; a++) { G.lo[a] = inf; G.hi[a] = -inf; }
-    for (int w = 0; w < ME_THREADS / 64; w++) {
-        for (int a = 0; a < 3; a++) { G.lo[a] = fminf(G.lo[a], s_box[w].lo[a]); G.hi[a] = fmaxf(G.hi[a], s_box[w].hi[a]); }
-        G.n_ref += s_box[w].count;
-    }
+    for (int a = 0; a < 3; a++) { G.lo[a] = all.lo[a]; G.hi[a] = all.hi[a]; }
+    G.n_ref = all.count;
     G.flags = G.n_ref == 0u ? LVDGS_CLOUD_DISTANCE_NO_REFERENCE : 0u;
     if (G.n_ref == 0u) { for (int a = 0; a < 3; a++) G.lo[a] = G.hi[a] = 0.f; }
     // axes with a finite positive extent share the cells; the others get one
@@ -387,53 +349,40 @@ __global__ void __launch_bounds__(ME_THREADS) cloud_count_kernel(CloudParams P) 
     }
 }
 
-// the scan over the cells, for both clouds (blockIdx.y): sums per span, one workgroup's scan of them, the starts
-__device__ __forceinline__ uint32_t cell_span(int ncells) {
-    const uint32_t rounds = ((uint32_t)ncells + ME_THREADS - 1) / ME_THREADS;
-    return (rounds + CD_SCAN_BLOCKS - 1) / CD_SCAN_BLOCKS * ME_THREADS;
-}
+// the span scan over the cells, for both clouds (blockIdx.y).  The host does not know the cell count: always CD_SCAN_BLOCKS spans, the
+// trailing ones empty, of a length decided here
+__device__ __forceinline__ uint32_t cell_span(uint32_t ncells) { return span_length(ncells, CD_SCAN_BLOCKS, ME_THREADS); }
 __global__ void __launch_bounds__(ME_THREADS) cloud_span_sum_kernel(CloudParams P) {
     __shared__ uint32_t sh[SCAN_WORDS];
-    const uint32_t ncells = (uint32_t)P.grid->ncells, span = cell_span((int)ncells);
-    const uint64_t begin64 = (uint64_t)blockIdx.x * span;
-    const uint32_t begin = begin64 < ncells ? (uint32_t)begin64 : ncells;
-    const uint32_t end = ncells - begin < span ? ncells : begin + span;
+    const uint32_t ncells = (uint32_t)P.grid->ncells;
+    const SpanRange<uint32_t> r = span_range(ncells, cell_span(ncells), blockIdx.x);
     const uint32_t *cnt = P.cnt[blockIdx.y];
     uint32_t mine = 0;
-    for (uint32_t c = begin + threadIdx.x; c < end; c += ME_THREADS) mine += cnt[c];
+    for (uint32_t c = r.begin + threadIdx.x; c < r.end; c += ME_THREADS) mine += cnt[c];
     uint32_t total = 0;
     scan_workgroup<ME_THREADS>(mine, sh, &total);
     if (threadIdx.x == 0) P.spansum[blockIdx.y * CD_SCAN_BLOCKS + blockIdx.x] = total;
 }
 __global__ void __launch_bounds__(ME_THREADS) cloud_span_scan_kernel(CloudParams P) {
     __shared__ uint32_t sh[SCAN_WORDS];
-    static_assert(CD_SCAN_BLOCKS == ME_THREADS, "one round");
     const uint32_t ncells = (uint32_t)P.grid->ncells;
     for (int which = 0; which < 2; which++) {
         uint32_t *s = P.spansum + which * CD_SCAN_BLOCKS;
-        const uint32_t v = s[threadIdx.x];
-        uint32_t total = 0;
-        const uint32_t excl = scan_workgroup<ME_THREADS>(v, sh, &total);
-        s[threadIdx.x] = excl;
+        const uint32_t total = scan_span_counts<ME_THREADS>(s, s, CD_SCAN_BLOCKS, 1, sh);
         if (threadIdx.x == 0) P.start[which][ncells] = total;
     }
 }
 __global__ void __launch_bounds__(ME_THREADS) cloud_span_write_kernel(CloudParams P) {
     __shared__ uint32_t sh[SCAN_WORDS];
-    const uint32_t ncells = (uint32_t)P.grid->ncells, span = cell_span((int)ncells);
-    const uint64_t begin64 = (uint64_t)blockIdx.x * span;
-    const uint32_t begin = begin64 < ncells ? (uint32_t)begin64 : ncells;
-    const uint32_t end = ncells - begin < span ? ncells : begin + span;
+    const uint32_t ncells = (uint32_t)P.grid->ncells;
+    const SpanRange<uint32_t> r = span_range(ncells, cell_span(ncells), blockIdx.x);
     const uint32_t *cnt = P.cnt[blockIdx.y];
     uint32_t *start = P.start[blockIdx.y];
-    uint32_t row0 = P.spansum[blockIdx.y * CD_SCAN_BLOCKS + blockIdx.x];
-    for (uint32_t tile = begin; tile < end; tile += ME_THREADS) {   // (uniform)
+    TileWalk<ME_THREADS, uint32_t> walk{P.spansum[blockIdx.y * CD_SCAN_BLOCKS + blockIdx.x]};
+    for (uint32_t tile = r.begin; tile < r.end; tile += ME_THREADS) {   // (uniform)
         const uint32_t c = tile + threadIdx.x;
-        const uint32_t v = c < end ? cnt[c] : 0u;
-        uint32_t total = 0;
-        const uint32_t excl = scan_workgroup<ME_THREADS>(v, sh, &total);
-        if (c < end) start[c] = row0 + excl;
-        row0 += total;
+        const uint32_t at = walk.place(c < r.end ? cnt[c] : 0u, sh);
+        if (c < r.end) start[c] = at;
     }
 }
 
@@ -571,75 +520,52 @@ __global__ void __launch_bounds__(CD_SEARCH_THREADS) cloud_search_kernel(CloudPa
     }
 }
 
-__global__ void __launch_bounds__(ME_THREADS) cloud_sum_kernel(CloudParams P, uint32_t chunk) {
-    __shared__ SumPartial s_part[ME_THREADS / 64];
-    const uint64_t begin64 = (uint64_t)blockIdx.x * chunk;
-    const uint32_t begin = begin64 < P.M ? (uint32_t)begin64 : P.M;
-    const uint32_t end = P.M - begin < chunk ? P.M : begin + chunk;
-    double s1 = 0.0, s2 = 0.0;
-    uint32_t counted = 0, skipped = 0, below[LVDGS_CLOUD_DISTANCE_MAX_THRESHOLDS] = {0u, 0u, 0u, 0u};
-    float maxd = 0.f;
-    for (uint32_t i = begin + threadIdx.x; i < end; i += ME_THREADS) {
-        if (P.idx[i] < 0) { skipped++; continue; }
-        const float v = P.d2[i], d = sqrtf(v);
-        s1 += (double)d; s2 += (double)v;
-        counted++;
+// The sum of one partial row per thread over the workgroup, valid in thread 0.  The order of the double additions is part of the
+// row's bits: the xor-butterfly wave_sum, then thread 0 adds the waves from 0 up.  s_part: one per wave.
+__device__ __forceinline__ void sum_join(SumPartial &o, const SumPartial &q) {
+    o.s1 += q.s1; o.s2 += q.s2; o.counted += q.counted; o.skipped += q.skipped;
 #pragma unroll
-        for (int t = 0; t < LVDGS_CLOUD_DISTANCE_MAX_THRESHOLDS; t++) below[t] += (t < P.nthr && d < P.thr[t]) ? 1u : 0u;
-        maxd = fmaxf(maxd, d);
-    }
-    s1 = wave_sum(s1); s2 = wave_sum(s2);
-    counted = wave_sum(counted); skipped = wave_sum(skipped);
+    for (int t = 0; t < LVDGS_CLOUD_DISTANCE_MAX_THRESHOLDS; t++) o.below[t] += q.below[t];
+    o.maxd = fmaxf(o.maxd, q.maxd);
+}
+__device__ __forceinline__ SumPartial workgroup_sum(SumPartial v, SumPartial *s_part) {
+    v.s1 = wave_sum(v.s1); v.s2 = wave_sum(v.s2);
+    v.counted = wave_sum(v.counted); v.skipped = wave_sum(v.skipped);
 #pragma unroll
-    for (int t = 0; t < LVDGS_CLOUD_DISTANCE_MAX_THRESHOLDS; t++) below[t] = wave_sum(below[t]);
-    maxd = wave_max(maxd);
-    if ((threadIdx.x & 63) == 0) {
-        SumPartial &o = s_part[threadIdx.x >> 6];
-        o.s1 = s1; o.s2 = s2; o.counted = counted; o.skipped = skipped; o.maxd = maxd; o.pad = 0;
-        for (int t = 0; t < LVDGS_CLOUD_DISTANCE_MAX_THRESHOLDS; t++) o.below[t] = below[t];
-    }
+    for (int t = 0; t < LVDGS_CLOUD_DISTANCE_MAX_THRESHOLDS; t++) v.below[t] = wave_sum(v.below[t]);
+    v.maxd = wave_max(v.maxd);
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        SumPartial o = s_part[0];
-        for (int w = 1; w < ME_THREADS / 64; w++) {
-            o.s1 += s_part[w].s1; o.s2 += s_part[w].s2; o.counted += s_part[w].counted; o.skipped += s_part[w].skipped;
-            for (int t = 0; t < LVDGS_CLOUD_DISTANCE_MAX_THRESHOLDS; t++) o.below[t] += s_part[w].below[t];
-            o.maxd = fmaxf(o.maxd, s_part[w].maxd);
-        }
-        P.sum[blockIdx.x] = o;
-    }
+    if (threadIdx.x != 0) return v;
+    SumPartial o = s_part[0];
+    for (int w = 1; w < ME_THREADS / 64; w++) sum_join(o, s_part[w]);
+    return o;
 }
 
-// One workgroup: the partial rows in a fixed order (thread t takes t, t + 256, ...; wave sums; the waves from 0 up) and the row.
+__global__ void __launch_bounds__(ME_THREADS) cloud_sum_kernel(CloudParams P, uint32_t chunk) {
+    __shared__ SumPartial s_part[ME_THREADS / 64];
+    const SpanRange<uint32_t> r = span_range(P.M, chunk, blockIdx.x);
+    SumPartial mine{};
+    for (uint32_t i = r.begin + threadIdx.x; i < r.end; i += ME_THREADS) {
+        if (P.idx[i] < 0) { mine.skipped++; continue; }
+        const float v = P.d2[i], d = sqrtf(v);
+        mine.s1 += (double)d; mine.s2 += (double)v;
+        mine.counted++;
+#pragma unroll
+        for (int t = 0; t < LVDGS_CLOUD_DISTANCE_MAX_THRESHOLDS; t++) mine.below[t] += (t < P.nthr && d < P.thr[t]) ? 1u : 0u;
+        mine.maxd = fmaxf(mine.maxd, d);
+    }
+    const SumPartial o = workgroup_sum(mine, s_part);
+    if (threadIdx.x == 0) P.sum[blockIdx.x] = o;
+}
+
+// One workgroup: the partial rows in a fixed order (thread t takes t, t + 256, ...; then workgroup_sum's) and the row.
 __global__ void __launch_bounds__(ME_THREADS) cloud_finish_kernel(CloudParams P, int blocks) {
     __shared__ SumPartial s_part[ME_THREADS / 64];
-    double s1 = 0.0, s2 = 0.0;
-    uint32_t counted = 0, skipped = 0, below[LVDGS_CLOUD_DISTANCE_MAX_THRESHOLDS] = {0u, 0u, 0u, 0u};
-    float maxd = 0.f;
-    for (int b = threadIdx.x; b < blocks; b += ME_THREADS) {
-        const SumPartial q = P.sum[b];
-        s1 += q.s1; s2 += q.s2; counted += q.counted; skipped += q.skipped;
-        for (int t = 0; t < LVDGS_CLOUD_DISTANCE_MAX_THRESHOLDS; t++) below[t] += q.below[t];
-        maxd = fmaxf(maxd, q.maxd);
-    }
-    s1 = wave_sum(s1); s2 = wave_sum(s2);
-    counted = wave_sum(counted); skipped = wave_sum(skipped);
-#pragma unroll
-    for (int t = 0; t < LVDGS_CLOUD_DISTANCE_MAX_THRESHOLDS; t++) below[t] = wave_sum(below[t]);
-    maxd = wave_max(maxd);
-    if ((threadIdx.x & 63) == 0) {
-        SumPartial &o = s_part[threadIdx.x >> 6];
-        o.s1 = s1; o.s2 = s2; o.counted = counted; o.skipped = skipped; o.maxd = maxd; o.pad = 0;
-        for (int t = 0; t < LVDGS_CLOUD_DISTANCE_MAX_THRESHOLDS; t++) o.below[t] = below[t];
-    }
-    __syncthreads();
+    SumPartial mine{};
+    for (int b = threadIdx.x; b < blocks; b += ME_THREADS) sum_join(mine, P.sum[b]);
+    const SumPartial o = workgroup_sum(mine, s_part);
     if (threadIdx.x != 0) return;
-    SumPartial o = s_part[0];
-    for (int w = 1; w < ME_THREADS / 64; w++) {
-        o.s1 += s_part[w].s1; o.s2 += s_part[w].s2; o.counted += s_part[w].counted; o.skipped += s_part[w].skipped;
-        for (int t = 0; t < LVDGS_CLOUD_DISTANCE_MAX_THRESHOLDS; t++) o.below[t] += s_part[w].below[t];
-        o.maxd = fmaxf(o.maxd, s_part[w].maxd);
-    }
     lvdgs_cloud_distance_row *row = P.row;
     row->sum_distance = o.s1; row->sum_squared = o.s2;
     row->n_counted = o.counted; row->n_skipped = o.skipped;
@@ -719,11 +645,9 @@ int lvdgs_mesh_sample(const lvdgs_mesh_sample_args *a, void *stream) {
     P.bsum = reinterpret_cast<u64 *>(base + L.bsum);
     P.bcount = reinterpret_cast<uint32_t *>(base + L.bcount);
     P.totals = reinterpret_cast<u64 *>(base + L.totals);
-    // spans: as many as there are rounds of ME_THREADS faces, at most ME_MAX_BLOCKS; the last span may be short, none is empty
-    const size_t rounds = ((size_t)P.F + ME_THREADS - 1) / ME_THREADS;
-    const size_t want = rounds < (size_t)ME_MAX_BLOCKS ? rounds : (size_t)ME_MAX_BLOCKS;
-    P.span = (uint32_t)((rounds + want - 1) / want * ME_THREADS);
-    const int blocks = (int)(((size_t)P.F + P.span - 1) / P.span);
+    const Spans spans = make_spans(a->num_faces, ME_THREADS, ME_MAX_BLOCKS, ME_THREADS);
+    const int blocks = spans.blocks;
+    P.span = spans.span;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(blocks), block(ME_THREADS);
     {

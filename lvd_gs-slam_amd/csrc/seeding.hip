@@ -14,25 +14,22 @@
 //
 // t is an order statistic of the valid keys: select.hpp's four passes with a source that yields keys and a rank that is a function of
 // the count pass 0 finds.  The optional median of ALL depth values is the same four passes as they stand.
-// The ordered compaction has no atomic that decides a position: every workgroup owns one contiguous span of pixels, counts its
-// selected pixels, one workgroup scans the counts, and the write pass walks each span again in tiles of SEED_THREADS pixels with one
-// workgroup scan per tile.  Integer decisions and the float expressions of the header only: two calls give the same bytes.
+// The ordered compaction of the selected pixels is a span scan (spans.hpp).  Integer decisions and the float expressions of the header
+// only: two calls give the same bytes.
 //
 // Launches, all enqueued at once: a clear of the state, then EIGHT -- four select passes over the keys, seed_count_kernel,
 // seed_scan_kernel, seed_write_kernel, seed_publish_kernel (the host block, its sequence word last) -- and four more select passes
 // in front of them when the median is asked for: TWELVE.  The number depends on nothing else.
 #include "select.hpp"
+#include "spans.hpp"
 
 namespace lvdgs {
 namespace {
 
 constexpr int SEED_THREADS = 256;
 constexpr int SEED_MAX_BLOCKS = SEL_MAX_BLOCKS;   // spans, = words of the count array
+constexpr uint32_t SEED_MIN_SPAN = SEL_THREADS * SEL_ITEMS_PER_THREAD;   // a span is sized like a workgroup of the select passes
 
-__host__ __device__ inline uint32_t fmix32(uint32_t h) {
-    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-    return h;
-}
 __host__ __device__ inline uint32_t pixel_key(uint32_t i, uint32_t seed_lo, uint32_t seed_hi) { return fmix32(fmix32(i + seed_lo) ^ seed_hi); }
 
 struct SeedParams {
@@ -79,10 +76,9 @@ __global__ void __launch_bounds__(SEED_THREADS) seed_count_kernel(SeedParams S) 
     __shared__ uint32_t sh[SCAN_WORDS];
     const uint32_t t = S.st_key->prefix;
     const bool keep = keep_of(S.st_key->n, S.inv_downsample) > 0;
-    const int64_t begin = (int64_t)blockIdx.x * S.span;
-    const int64_t end = begin + S.span < S.P ? begin + S.span : S.P;
+    const SpanRange<int64_t> r = span_range(S.P, S.span, blockIdx.x);
     uint32_t mine = 0;
-    for (int64_t i = begin + threadIdx.x; i < end; i += SEED_THREADS) mine += selected(S, i, t, keep);
+    for (int64_t i = r.begin + threadIdx.x; i < r.end; i += SEED_THREADS) mine += selected(S, i, t, keep);
     uint32_t total = 0;
     scan_workgroup<SEED_THREADS>(mine, sh, &total);
     if (threadIdx.x == 0) S.counts[blockIdx.x] = total;
@@ -91,38 +87,25 @@ __global__ void __launch_bounds__(SEED_THREADS) seed_count_kernel(SeedParams S) 
 // One workgroup: the counts of the `blocks` <= SEED_MAX_BLOCKS spans become the number of rows in front of each.
 __global__ void __launch_bounds__(SEED_THREADS) seed_scan_kernel(SeedParams S, int blocks) {
     __shared__ uint32_t sh[SCAN_WORDS];
-    static_assert(SEED_MAX_BLOCKS % SEED_THREADS == 0, "whole rounds");
-    uint32_t carry = 0;
-    for (int base = 0; base < blocks; base += SEED_THREADS) {   // (uniform)
-        const int j = base + threadIdx.x;
-        const uint32_t c = j < blocks ? S.counts[j] : 0u;
-        uint32_t total = 0;
-        const uint32_t excl = scan_workgroup<SEED_THREADS>(c, sh, &total);
-        if (j < blocks) S.counts[j] = carry + excl;
-        carry += total;
-    }
+    scan_span_counts<SEED_THREADS>(S.counts, S.counts, blocks, 1, sh);
 }
 
 __global__ void __launch_bounds__(SEED_THREADS) seed_write_kernel(SeedParams S) {
     __shared__ uint32_t sh[SCAN_WORDS];
     const uint32_t t = S.st_key->prefix;
     const bool keep = keep_of(S.st_key->n, S.inv_downsample) > 0;
-    const int64_t begin = (int64_t)blockIdx.x * S.span;
-    const int64_t end = begin + S.span < S.P ? begin + S.span : S.P;
+    const SpanRange<int64_t> r = span_range(S.P, S.span, blockIdx.x);
     const float gain = S.gain ? *S.gain : 1.0f, offset = S.offset ? *S.offset : 0.0f;
     float R[9], T[3];
 #pragma unroll
     for (int j = 0; j < 9; j++) R[j] = S.R[j];
 #pragma unroll
     for (int j = 0; j < 3; j++) T[j] = S.T[j];
-    uint32_t row0 = S.counts[blockIdx.x];
-    for (int64_t base = begin; base < end; base += SEED_THREADS) {   // (uniform: every thread reaches the scan)
+    TileWalk<SEED_THREADS, uint32_t> walk{S.counts[blockIdx.x]};
+    for (int64_t base = r.begin; base < r.end; base += SEED_THREADS) {   // (uniform)
         const int64_t i = base + threadIdx.x;
-        const bool sel = i < end && selected(S, i, t, keep);
-        uint32_t total = 0;
-        const uint32_t excl = scan_workgroup<SEED_THREADS>(sel ? 1u : 0u, sh, &total);
-        const int64_t row = (int64_t)row0 + excl;
-        row0 += total;
+        const bool sel = i < r.end && selected(S, i, t, keep);
+        const int64_t row = walk.place(sel ? 1u : 0u, sh);
         if (!sel || row >= S.capacity) continue;   // (the host-side bound of n_keep keeps every row inside the capacity)
         const int v = (int)(i / S.W), u = (int)(i - (int64_t)v * S.W);
         const float z = S.depth[i];
@@ -203,8 +186,9 @@ int lvdgs_seed_points(const lvdgs_seed_args *a, void *stream) {
     S.st_median = reinterpret_cast<SelectState *>(base + align256(sizeof(SelectState)));
     S.counts = reinterpret_cast<uint32_t *>(base + 2 * align256(sizeof(SelectState)));
     if (int e = host_block_address(a->host_state, "seed points", &S.host)) return e;
-    const int blocks = select_blocks(P);   // <= SEED_MAX_BLOCKS spans
-    S.span = ((P + blocks - 1) / blocks + SEED_THREADS - 1) / SEED_THREADS * SEED_THREADS;
+    const Spans spans = make_spans(P, SEED_THREADS, SEED_MAX_BLOCKS, SEED_MIN_SPAN);
+    const int blocks = spans.blocks;
+    S.span = spans.span;
     if (int e = check_hip(hipMemsetAsync(a->scratch, 0, seed_state_bytes(), s), "seed points: clearing the state")) return e;
     if (S.want_median)
         if (int e = launch_select(AllDepthSource{S.depth}, P, S.st_median, select_rank(-1), "seed_median", s)) return e;

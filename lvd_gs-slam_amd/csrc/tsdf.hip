@@ -7,9 +7,8 @@
 // eight corner voxels (brick_may_touch) and a ballot makes the wave-uniform mask of the views the brick is walked for; a brick with an
 // empty mask returns without touching memory.
 //
-// lvdgs_tsdf_mesh: six launches.  Every workgroup owns one contiguous span of samples; positions come from counts per span, one
-// workgroup's scan of them, and a second walk with one workgroup scan per 256 samples (seeding.hip's ordered compaction): integer
-// decisions only, no atomics, two calls give the same bytes.
+// lvdgs_tsdf_mesh: six launches.  Vertices and faces are two span scans (spans.hpp) over the samples that share one scan launch:
+// integer decisions only, no atomics, two calls give the same bytes.
 //
 // Built like every file here with -ffp-contract=off and without fast-math: the float32 expressions of the header are evaluated as
 // written, the divisions IEEE-rounded, and a NumPy float32 restatement gives the same bits.
@@ -17,13 +16,14 @@
 
 #include "common.hpp"
 #include "device_utils.hpp"
+#include "spans.hpp"
 
 namespace lvdgs {
 namespace {
 
 constexpr int TSDF_THREADS = 256;
 constexpr int BRICK_X = 64, BRICK_Y = 4, BRICK_Z = 4;   // 16 lanes x 4 voxels, 4 rows per wave, 4 waves
-constexpr int TSDF_MAX_BLOCKS = 2048;                   // spans of the mesh passes (a multiple of TSDF_THREADS: whole scan rounds)
+constexpr int TSDF_MAX_BLOCKS = 2048;                   // spans of the mesh passes
 
 struct TsdfView {
     int W, H;
@@ -231,11 +231,10 @@ __device__ __forceinline__ Sample sample_of(const MeshParams &M, uint32_t s) {
 
 __global__ void __launch_bounds__(TSDF_THREADS) tsdf_classify_kernel(MeshParams M) {
     __shared__ uint32_t sh[SCAN_WORDS];
-    const uint32_t begin = blockIdx.x * M.span;
-    const uint32_t end = M.n - begin < M.span ? M.n : begin + M.span;
+    const SpanRange<uint32_t> r = span_range(M.n, M.span, blockIdx.x);
     const uint32_t sx = 1u, sy = (uint32_t)M.nx, sz = (uint32_t)M.nx * (uint32_t)M.ny;
     uint32_t mine = 0;
-    for (uint32_t s = begin + threadIdx.x; s < end; s += TSDF_THREADS) {
+    for (uint32_t s = r.begin + threadIdx.x; s < r.end; s += TSDF_THREADS) {
         const Sample c = sample_of(M, s);
         const bool obs = M.weight[s] > 0.f, in = M.tsdf[s] < 0.f;
         bool active = false;
@@ -260,11 +259,10 @@ __global__ void __launch_bounds__(TSDF_THREADS) tsdf_classify_kernel(MeshParams 
 
 __global__ void __launch_bounds__(TSDF_THREADS) tsdf_edges_kernel(MeshParams M) {
     __shared__ uint32_t sh[SCAN_WORDS];
-    const uint32_t begin = blockIdx.x * M.span;
-    const uint32_t end = M.n - begin < M.span ? M.n : begin + M.span;
+    const SpanRange<uint32_t> r = span_range(M.n, M.span, blockIdx.x);
     const uint32_t sy = (uint32_t)M.nx, sz = (uint32_t)M.nx * (uint32_t)M.ny;
     uint32_t mine = 0;
-    for (uint32_t s = begin + threadIdx.x; s < end; s += TSDF_THREADS) {
+    for (uint32_t s = r.begin + threadIdx.x; s < r.end; s += TSDF_THREADS) {
         const Sample c = sample_of(M, s);
         const uint8_t fl = M.flags[s];
         const bool in0 = fl & SAMPLE_INSIDE;
@@ -289,36 +287,21 @@ __global__ void __launch_bounds__(TSDF_THREADS) tsdf_edges_kernel(MeshParams M) 
 // (256 spans of at most 2^20 samples, six faces each); the carry over the rounds is 64 bits for the faces.
 __global__ void __launch_bounds__(TSDF_THREADS) tsdf_scan_kernel(MeshParams M, int blocks) {
     __shared__ uint32_t sh[SCAN_WORDS];
-    static_assert(TSDF_MAX_BLOCKS % TSDF_THREADS == 0, "whole rounds");
-    uint32_t vcarry = 0;
-    unsigned long long fcarry = 0;
-    for (int base = 0; base < blocks; base += TSDF_THREADS) {   // (uniform)
-        const int b = base + threadIdx.x;
-        const uint32_t cv = b < blocks ? M.vcount[b] : 0u, cf = b < blocks ? M.fcount[b] : 0u;
-        uint32_t tv = 0, tf = 0;
-        const uint32_t ev = scan_workgroup<TSDF_THREADS>(cv, sh, &tv);
-        const uint32_t ef = scan_workgroup<TSDF_THREADS>(cf, sh, &tf);
-        if (b < blocks) { M.vcount[b] = vcarry + ev; M.fbase[b] = fcarry + ef; }
-        vcarry += tv;
-        fcarry += tf;
-    }
-    if (threadIdx.x == 0) { M.totals[0] = vcarry; M.totals[1] = fcarry; }
+    const uint32_t nv = scan_span_counts<TSDF_THREADS>(M.vcount, M.vcount, blocks, 1, sh);
+    const unsigned long long nf = scan_span_counts<TSDF_THREADS>(M.fcount, M.fbase, blocks, 1, sh);
+    if (threadIdx.x == 0) { M.totals[0] = nv; M.totals[1] = nf; }
 }
 
 template <bool COLOR>
 __global__ void __launch_bounds__(TSDF_THREADS) tsdf_vertices_kernel(MeshParams M) {
     __shared__ uint32_t sh[SCAN_WORDS];
-    const uint32_t begin = blockIdx.x * M.span;
-    const uint32_t end = M.n - begin < M.span ? M.n : begin + M.span;
+    const SpanRange<uint32_t> r = span_range(M.n, M.span, blockIdx.x);
     const uint32_t sy = (uint32_t)M.nx, sz = (uint32_t)M.nx * (uint32_t)M.ny;
-    uint32_t row0 = M.vcount[blockIdx.x];
-    for (uint32_t tile = begin; tile < end; tile += TSDF_THREADS) {   // (uniform: every thread reaches the scan)
+    TileWalk<TSDF_THREADS, uint32_t> walk{M.vcount[blockIdx.x]};
+    for (uint32_t tile = r.begin; tile < r.end; tile += TSDF_THREADS) {   // (uniform)
         const uint32_t s = tile + threadIdx.x;
-        const bool act = s < end && (M.flags[s] & CELL_ACTIVE);
-        uint32_t total = 0;
-        const uint32_t excl = scan_workgroup<TSDF_THREADS>(act ? 1u : 0u, sh, &total);
-        const uint32_t row = row0 + excl;
-        row0 += total;
+        const bool act = s < r.end && (M.flags[s] & CELL_ACTIVE);
+        const uint32_t row = walk.place(act ? 1u : 0u, sh);
         if (!act) continue;
         M.cellvert[s] = (int32_t)row;
         if (row >= (uint32_t)M.vcap) continue;
@@ -369,18 +352,14 @@ __global__ void __launch_bounds__(TSDF_THREADS) tsdf_vertices_kernel(MeshParams 
 
 __global__ void __launch_bounds__(TSDF_THREADS) tsdf_faces_kernel(MeshParams M) {
     __shared__ uint32_t sh[SCAN_WORDS];
-    const uint32_t begin = blockIdx.x * M.span;
-    const uint32_t end = M.n - begin < M.span ? M.n : begin + M.span;
+    const SpanRange<uint32_t> r = span_range(M.n, M.span, blockIdx.x);
     const uint32_t sy = (uint32_t)M.nx, sz = (uint32_t)M.nx * (uint32_t)M.ny;
-    unsigned long long row0 = M.fbase[blockIdx.x];
+    TileWalk<TSDF_THREADS, uint32_t, unsigned long long> walk{M.fbase[blockIdx.x]};
     const unsigned long long cap = (unsigned long long)M.fcap;
-    for (uint32_t tile = begin; tile < end; tile += TSDF_THREADS) {   // (uniform)
+    for (uint32_t tile = r.begin; tile < r.end; tile += TSDF_THREADS) {   // (uniform)
         const uint32_t s = tile + threadIdx.x;
-        const uint32_t e = s < end ? M.edges[s] : 0u;
-        uint32_t total = 0;
-        const uint32_t excl = scan_workgroup<TSDF_THREADS>(2u * (uint32_t)__popc(e & 7u), sh, &total);
-        unsigned long long row = row0 + excl;
-        row0 += total;
+        const uint32_t e = s < r.end ? M.edges[s] : 0u;
+        unsigned long long row = walk.place(2u * (uint32_t)__popc(e & 7u), sh);
         if (!(e & 7u) || row >= cap) continue;
         const bool low_in = e & EDGE_LOW_INSIDE;
         const int32_t own = M.cellvert[s];
@@ -536,11 +515,9 @@ int lvdgs_tsdf_mesh(const lvdgs_tsdf_mesh_args *a, void *stream) {
     M.fbase = reinterpret_cast<unsigned long long *>(base + L.fbase);
     M.totals = reinterpret_cast<unsigned long long *>(base + L.totals);
     if (int e = host_block_address(a->host_state, name, &M.host)) return e;
-    // spans: as many as there are rounds of TSDF_THREADS samples, at most TSDF_MAX_BLOCKS; the last span may be short, none is empty
-    const size_t rounds = (n + TSDF_THREADS - 1) / TSDF_THREADS;
-    const size_t want = rounds < (size_t)TSDF_MAX_BLOCKS ? rounds : (size_t)TSDF_MAX_BLOCKS;
-    M.span = (uint32_t)((rounds + want - 1) / want * TSDF_THREADS);
-    const int blocks = (int)((n + M.span - 1) / M.span);
+    const Spans spans = make_spans((int64_t)n, TSDF_THREADS, TSDF_MAX_BLOCKS, TSDF_THREADS);
+    const int blocks = spans.blocks;
+    M.span = spans.span;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(blocks), block(TSDF_THREADS);
     {

@@ -11,6 +11,9 @@ condition on the inputs, so ``expf`` on the device, NumPy's and PyTorch's expone
 import numpy as np
 
 SIZES = (0, 1, 63, 64, 65, 1023, 1025, 70_001)
+# above 1024 x 256 rows, the most spans of a plan times a tile: a span is two tiles long and the write pass carries its rows across them
+# (for kind "mixed" only -- the span scan is blind to what the rows are steered to)
+LONG_SPANS = 262_401
 # kind -> what the rows are steered to
 KINDS = ("mixed", "mixed_no_screen", "none", "all_clone", "all_split", "all_pruned", "children_pruned")
 EXTENT, PERCENT_DENSE, MAX_GRAD, MIN_OPACITY, MAX_SCREEN = 6.0, 0.01, 0.0002, 0.05, 20.0

@@ -47,14 +47,13 @@ def _check_plan(p, o):
 
 
 # ---------------------------------------------------------------- 1. the plan
-@pytest.mark.parametrize("S", (3, 1))
-@pytest.mark.parametrize("n", cases.SIZES)
-@pytest.mark.parametrize("kind", cases.KINDS)
+@pytest.mark.parametrize("kind,n,S", [(k, n, S) for k in cases.KINDS for n in cases.SIZES for S in (3, 1)] +
+                         [("mixed", cases.LONG_SPANS, 3), ("mixed", cases.LONG_SPANS, 1)])
 def test_densify_plan_is_the_oracles(kind, n, S):
     _check_plan(_plan_densify(_case(kind, n, S)), _oracle(kind, n, S))
 
 
-@pytest.mark.parametrize("n", cases.SIZES)
+@pytest.mark.parametrize("n", cases.SIZES + (cases.LONG_SPANS,))
 def test_prune_plans_are_the_oracles(n):
     from lvdgs import map_edit
     rng = np.random.default_rng(n)

@@ -85,11 +85,13 @@ def test_sampling_skips_faces_without_weight():
     assert want["n_weighted"] == len(f) - len(bad) and not bad & set(fi.tolist()) and np.isfinite(p).all()
 
 
-@pytest.mark.parametrize("faces", [257, 70_000])
+@pytest.mark.parametrize("faces", [257, 70_000, 525_312])
 def test_sampling_a_prefix_over_several_workgroups(faces):
-    """257 faces: two rounds of a workgroup's scan; 70 000: 274 spans, two rounds of the scan over the spans."""
-    v, f, c = orc.wavy_wall(176, 201, seed=7)
-    assert len(f) == 70_000
+    """257 faces: two rounds of a workgroup's scan; 70 000: 274 spans, two rounds of the scan over the spans; 525 312: above 2048 x 256,
+    so a span is two tiles of 256 faces long and the prefix pass carries its sum from the first tile into the second."""
+    nx, ny = (514, 513) if faces == 525_312 else (176, 201)
+    v, f, c = orc.wavy_wall(nx, ny, seed=7)
+    assert len(f) == max(faces, 70_000)
     _check_sampling(v, f[:faces], 2000, seed=11, c=c if faces == 257 else None)
 
 
@@ -232,6 +234,17 @@ def test_search_a_cell_with_more_points_than_the_tile():
     _check_search("tile-one-cell", q, dense, ppc=10 ** 9)
     r = np.concatenate([dense, _cloud(21, 200, lo=(0, 0, 0), size=(1, 1, 1))])
     _check_search("tile-among-cells", q, r, ppc=8)
+
+
+def test_search_a_grid_of_more_cells_than_one_tile_a_span():
+    """The scan over the cells has 256 spans of 256-cell tiles, so it takes more than 65 536 cells for a span to be two tiles long.
+    The grid cannot be read back; by the header's rule 120 000 points uniform in a cube at one point per cell give: target = 120 000
+    cells = the budget, h = extent / 49.3, 50 cells an axis = 125 000 > budget, h * 1.1 = extent / 44.8, 45 cells an axis = 91 125
+    cells <= budget.  Above 65 536: spans of 512 cells, 178 of them with cells."""
+    r = _cloud(22, 120_000, lo=(0, 0, 0), size=(1, 1, 1))
+    q = _cloud(23, 1500, lo=(-0.05, -0.05, -0.05), size=(1.1, 1.1, 1.1))
+    assert math.floor(1 / ((1 / 120_000) ** (1 / 3) * 1.1)) + 1 == 45 and 50 ** 3 > 120_000 >= 45 ** 3 > 65_536
+    _check_search("many-cells", q, r, thresholds=(0.01,), ppc=1)
 
 
 def test_search_coplanar_and_collinear_reference_points():

@@ -180,7 +180,7 @@ def _extraction(name):
     return _EXTRACTION[name]
 
 
-@pytest.mark.parametrize("name", ["sphere", "slanted", "blobs", "holes"])
+@pytest.mark.parametrize("name", ["sphere", "slanted", "blobs", "holes", "rounds", "tiles"])
 def test_extraction_against_the_mirror(name):
     vol, (v, c, f) = _extraction(name)
     tv = _device_volume(vol)

@@ -142,8 +142,21 @@ def analytic_volume(dims, sdf, voxel_size=0.1, origin=(0.0, 0.0, 0.0), color=Tru
     return vol
 
 
+def two_spheres(dims, seed):
+    """Two overlapping spheres across the middle of the volume, 1 % of the samples unobserved: a surface that crosses many spans."""
+    extent = 0.1 * np.asarray(dims, np.float64)
+    r = 0.3 * extent.min()
+    a, b = extent * np.array([0.38, 0.45, 0.5]), extent * np.array([0.64, 0.55, 0.48])
+    return analytic_volume(dims, lambda p: np.minimum(np.linalg.norm(p - a, axis=1) - r, np.linalg.norm(p - b, axis=1) - 0.9 * r),
+                           holes=0.01, seed=seed)
+
+
 def extraction_cases():
-    """name -> volume: the fused sphere, a slanted plane, two blobs that touch the boundary, and a volume with unobserved holes."""
+    """name -> volume: the fused sphere, a slanted plane, two blobs that touch the boundary, a volume with unobserved holes, and two
+    volumes sized for the span scan of the extraction (256 samples to a tile, 256 spans to a round of the scan, at most 2048 spans):
+    ``rounds`` has 69 120 samples = 270 spans of one tile, so the scan of the span counts carries into a second round; ``tiles`` has
+    540 000 samples = 2110 tiles, above 2048, so a span is two tiles long (1055 spans, five rounds) and the write passes carry their
+    row from the first tile into the second."""
     s = sphere_case()
     fused = orc.copy_volume(s["vol"])
     orc.integrate_f32(fused, s["views"])
@@ -153,4 +166,4 @@ def extraction_cases():
     blobs = analytic_volume((19, 12, 10), lambda p: np.minimum(np.linalg.norm(p - np.array([0.55, 0.5, 0.45]), axis=1) - 0.33,
                                                                np.linalg.norm(p - np.array([1.5, 0.7, 0.2]), axis=1) - 0.41))
     holes = analytic_volume((17, 15, 9), lambda p: np.linalg.norm(p - np.array([0.8, 0.7, 0.4]), axis=1) - 0.55, holes=0.03, seed=3)
-    return dict(sphere=fused, slanted=slanted, blobs=blobs, holes=holes)
+    return dict(sphere=fused, slanted=slanted, blobs=blobs, holes=holes, rounds=two_spheres((48, 40, 36), 7), tiles=two_spheres((90, 80, 75), 8))

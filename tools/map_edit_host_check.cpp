@@ -11,14 +11,20 @@ using namespace lvdgs;
 int main() {
     int fails = 0;
 #define EXPECT(cond) do { if (!(cond)) { printf("FAIL line %d: %s (%s)\n", __LINE__, #cond, last); fails++; } } while (0)
-    for (int32_t N : {0, 1, 255, 256, 257, 70001, 262144, 262145, 2000000, INT32_MAX}) {
+    for (int32_t N : {0, 1, 255, 256, 257, 70001, 262144, 262145, 262400, 262401, 2000000, INT32_MAX}) {
         EditLayout L = edit_layout(N);
         EXPECT(L.counts >= (size_t)N && L.counts % 256 == 0 && L.totals % 256 == 0 && L.bytes > L.totals);
         EXPECT(L.totals - L.counts >= (size_t)EDIT_MAX_BLOCKS * EDIT_COUNTERS * 4);
-        int blocks; int64_t span; edit_spans(N, &blocks, &span);
-        EXPECT(blocks >= 0 && blocks <= EDIT_MAX_BLOCKS && span % EDIT_THREADS == 0 && (int64_t)blocks * span >= N);
-        if (N > 0) EXPECT((int64_t)(blocks - 1) * span < N || blocks == EDIT_MAX_BLOCKS);
+        const Spans s = edit_spans(N);
+        const int blocks = s.blocks; const int64_t span = s.span;
+        EXPECT(blocks >= 0 && blocks <= EDIT_MAX_BLOCKS && span >= EDIT_THREADS && span % EDIT_THREADS == 0 && (int64_t)blocks * span >= N);
+        if (N > 0) EXPECT((int64_t)(blocks - 1) * span < N);   // no span is empty
+        else EXPECT(blocks == 0);
     }
+    // the shared geometry with a smallest span above the workgroup (seeding's): 1100 x 960 pixels in 459 spans of 2304, not 512
+    { const Spans s = make_spans(1100 * 960, 256, 512, 2048); EXPECT(s.blocks == 459 && s.span == 2304); }
+    { const Spans s = make_spans(3000, 256, 512, 2048); EXPECT(s.blocks == 2 && s.span == 2048); }
+    EXPECT(span_length(0, 256, 256) == 256 && span_length(65536, 256, 256) == 256 && span_length(65537, 256, 256) == 512);
     std::vector<char> mem(4096);
     lvdgs_map_edit_plan_args a; memset(&a, 0, sizeof a);
     EXPECT(edit_check_plan(nullptr) == LVDGS_E_INVALID);
