@@ -1396,6 +1396,119 @@ int lvdgs_tsdf_integrate(const lvdgs_tsdf_volume *vol, const lvdgs_tsdf_view *co
 size_t lvdgs_tsdf_mesh_scratch_bytes(int32_t nx, int32_t ny, int32_t nz);
 int lvdgs_tsdf_mesh(const lvdgs_tsdf_mesh_args *a, void *stream);
 
+/* ---- Block-sparse TSDF volume: the fusion rule and the surface nets of "TSDF fusion" on an unbounded lattice of which only the
+ * blocks near a surface are stored (what an Open3D-style ScalableTSDFVolume keeps in a host hash map) ----
+ * THE LATTICE: samples at p[a] = origin[a] + voxel_size * (float)g_a, g a SIGNED global index (one float32 product, one float32 sum,
+ * as for the dense volume).  A BLOCK is 8 x 8 x 8 samples: block coordinate b_a = floor(g_a / 8), each in [-2^20, 2^20), local
+ * index l = i + 8 * (j + 8 * k) with g_a = 8 * b_a + (i, j, k)_a.  THE KEY of a block, never 0:
+ *   key = 1 << 63 | (uint64)(bz + 2^20) << 42 | (uint64)(by + 2^20) << 21 | (uint64)(bx + 2^20)      -- ascending key = ascending (bz, by, bx).
+ * STORAGE, all caller-owned, on the device, and an empty volume when zeroed (there is no clear call): a pool of pool_blocks blocks
+ * in planes tsdf, weight and optionally r, g, b (all three or none), pool_blocks * 512 float32 each, block p at [512 p, 512 p + 512);
+ * block_key, pool_blocks int64 (the key of pool block p, 0: unused; a key is negative as an int64, so a signed ascending sort puts
+ * the unused entries last); an open-addressing table of table_slots (a power of two, >= 2 * pool_blocks) 64-bit keys and int32
+ * values (key 0: empty slot; value: the pool index, or -1 for a key that found the pool exhausted -- ABSENT to every reader), probed
+ * linearly from (mix(key) & (table_slots - 1)), mix = MurmurHash3's 64-bit finalizer; and a header of LVDGS_TSDF_BLOCKS_HEADER_WORDS
+ * int32: [_HEADER_USED] blocks in use, [_HEADER_DROPPED] keys entered with -1, [_HEADER_OUT_OF_RANGE] samples skipped for their
+ * coordinate (wraps at 2^32), [_HEADER_FLAGS] bit 0 (LVDGS_TSDF_BLOCKS_TABLE_FULL): a key found no slot.  Every kernel brings what it
+ * reads from the header, from `order` and from the table into range before it indexes with it.
+ *
+ * lvdgs_tsdf_blocks_integrate(vol, views, count): views as for lvdgs_tsdf_integrate.  Three launches, no host wait, no copy.
+ * ALLOCATION, for every view and every pixel (ui, vi), a thread each; all float32 as written, no contraction:
+ *   1. d = depth[vi*width + ui].  Skip unless d > 0 && d <= depth_trunc, and unless mask is NULL or mask[vi*width + ui] != 0.
+ *   2. The host computes, in float32, n_steps = 2 * (int)ceilf((trunc + voxel_size) / (0.5f * voxel_size)) + 1 (refused above
+ *      LVDGS_TSDF_BLOCKS_MAX_STEPS) and step = 0.5f * voxel_size.
+ *   3. For s = 0 .. n_steps-1:  zs = (d - (float)(n_steps / 2) * step) + (float)s * step;  skip the sample unless zs > depth_min;
+ *      xc = ((float)ui - cx) / fx * zs,  yc = ((float)vi - cy) / fy * zs;  q = (xc - T[0], yc - T[1], zs - T[2]);
+ *      p[a] = ((R[0*3+a] * q[0] + R[1*3+a] * q[1]) + R[2*3+a] * q[2])  (R^T q);  c[a] = floorf((p[a] - origin[a]) / (8.0f * voxel_size)).
+ *      Unless -1048576.0f <= c[a] < 1048576.0f for every a (a NaN fails) the sample is skipped and counted in [_HEADER_OUT_OF_RANGE].
+ *      Otherwise b = (int)c and the block is inserted if it is absent (a lane does not probe for the key of its previous sample).
+ *   A key is entered by a 64-bit atomicCAS on the slot's key -- the only atomic that decides anything; the winner takes the next
+ *   pool index from a counter and then writes the slot's value and block_key[index], or -1 and one count of [_HEADER_DROPPED] when
+ *   the pool is exhausted: exact while the table has room; a key that finds every slot taken sets TABLE_FULL.  The values are read
+ *   by later launches only.  Which pool index a block gets is not part of the contract; the SET of blocks is, while none is dropped.
+ * INTEGRATION: every sample of every block in use -- those of earlier calls and those of this call -- gets steps 1-5 of "TSDF
+ * fusion", views in list order: the dense rule on the global lattice restricted to the allocated blocks, the free-space updates
+ * inside them included.  A block allocated by a later call starts from zero at that call.  One workgroup of 256 threads per block,
+ * a thread owns the samples l and l + 256 and keeps them in registers across the views; per view the block's eight corner samples
+ * decide (brick_may_touch, the dense kernel's test, one lane per view and a ballot) whether the view is walked; planes are read
+ * once and written once, when a view changed them.  No atomics on plane data.
+ * Before any launch -- LVDGS_E_INVALID: vol, tsdf, weight, block_key, table_keys, table_values or header NULL, r, g, b neither all
+ * set nor all NULL, views NULL with count > 0, a view, its R, T or depth NULL, count outside 0 .. LVDGS_TSDF_MAX_VIEWS, an image on a
+ * volume without colour planes; LVDGS_E_RANGE: pool_blocks outside 1 .. LVDGS_TSDF_BLOCKS_MAX_POOL, table_slots not a power of two,
+ * below 2 * pool_blocks or above 2^30, voxel_size, trunc or max_weight not finite and > 0, more than LVDGS_TSDF_BLOCKS_MAX_STEPS
+ * steps, a view's width or height below 1 or more than 2^31 - 1 pixels.
+ *
+ * lvdgs_tsdf_blocks_mesh: surface nets with the definitions of lvdgs_tsdf_mesh -- observed, inside, active cell, vertex, colour,
+ * faces, winding -- on the global lattice; a sample of a block that is not in use is UNOBSERVED, so cells and faces cross block
+ * borders through the neighbours' samples.  position[a] = origin[a] + voxel_size * ((float)g_a + mean[a]), g the cell's low corner.
+ * Only cells with cell_lo[a] <= g_a < cell_hi[a] for every a can be active (INT32_MIN and INT32_MAX: all of them): with cell_lo = 0
+ * and cell_hi = n - 1 the mesh is that of a dense volume of n samples per axis on the same lattice.
+ * `order`: pool_blocks int32 on the device, the pool indices sorted by ascending key, the blocks in use first (plumbing: a sort of
+ * block_key).  Vertices are ordered by (block in `order`, l of the cell's low corner), faces by (block in `order`, l, axis x, y, z),
+ * the two triangles as written.  No atomic decides a position: two calls give the same bytes.  Launches, enqueued at once: the rank
+ * of every pool block; the 27 neighbours of every block by table lookup; classify per block (the block and its +1 shell, 9^3
+ * samples, in LDS: a 512-bit mask of active cells and their count); the edges (a byte per sample, the face count per block); one
+ * workgroup's scan of both counts over the blocks; the vertices (a cell's vertex number = its block's base + the active cells of
+ * the mask below l); the faces; the publish.  Capacities, rows beyond them and the retry: as for lvdgs_tsdf_mesh.  host_state: a
+ * host block of LVDGS_TSDF_BLOCKS_HOST_BYTES bytes: [LVDGS_TSDF_BLOCKS_SEQ] the call's `seq`, the tag; [_N_VERTICES]; [_N_FACES],
+ * saturated at 2^31 - 1; [_OVERFLOW], the bits of [LVDGS_TSDF_OVERFLOW]; [_USED], [_DROPPED], [_OUT_OF_RANGE], [_FLAGS]: the header;
+ * zeros after it.  scratch: the bytes lvdgs_tsdf_blocks_mesh_scratch_bytes(pool_blocks) gives (0: refused), 8-byte aligned, no
+ * initialisation needed.
+ * Before any launch -- as for the integration, and LVDGS_E_INVALID: args, order, vertices, faces, host_state or scratch NULL, colors
+ * without colour planes, scratch too small or misaligned; LVDGS_E_RANGE: a negative capacity.
+ *
+ * lvdgs_tsdf_blocks_rehash(vol): enters block_key[0 .. used-1] with their indices into vol's table, which the caller has zeroed (a
+ * larger one, after the planes and keys were copied into a larger pool); keys that were dropped are forgotten: [_HEADER_DROPPED]
+ * and [_HEADER_FLAGS] are reset.  One launch, no wait.  Refusals: those of the integration that concern vol. */
+#define LVDGS_TSDF_BLOCKS_HEADER_WORDS 8
+#define LVDGS_TSDF_BLOCKS_HOST_BYTES 64
+#define LVDGS_TSDF_BLOCKS_MAX_POOL 4194304
+#define LVDGS_TSDF_BLOCKS_MAX_STEPS 1025
+enum {
+    LVDGS_TSDF_BLOCKS_HEADER_USED = 0,
+    LVDGS_TSDF_BLOCKS_HEADER_DROPPED = 1,
+    LVDGS_TSDF_BLOCKS_HEADER_OUT_OF_RANGE = 2,
+    LVDGS_TSDF_BLOCKS_HEADER_FLAGS = 3
+};
+enum { LVDGS_TSDF_BLOCKS_TABLE_FULL = 1 };
+enum {
+    LVDGS_TSDF_BLOCKS_SEQ = 0,
+    LVDGS_TSDF_BLOCKS_N_VERTICES = 1,
+    LVDGS_TSDF_BLOCKS_N_FACES = 2,
+    LVDGS_TSDF_BLOCKS_OVERFLOW = 3,
+    LVDGS_TSDF_BLOCKS_USED = 4,
+    LVDGS_TSDF_BLOCKS_DROPPED = 5,
+    LVDGS_TSDF_BLOCKS_OUT_OF_RANGE = 6,
+    LVDGS_TSDF_BLOCKS_FLAGS = 7
+};
+typedef struct lvdgs_tsdf_blocks {
+    int32_t pool_blocks, table_slots;
+    float origin[3];
+    float voxel_size, trunc, max_weight;
+    float *tsdf, *weight;         /* pool_blocks*512 each                           */
+    float *r, *g, *b;             /* pool_blocks*512 each, or all NULL: no colour   */
+    int64_t *block_key;           /* pool_blocks                                    */
+    uint64_t *table_keys;         /* table_slots                                    */
+    int32_t *table_values;        /* table_slots                                    */
+    int32_t *header;              /* LVDGS_TSDF_BLOCKS_HEADER_WORDS, on the device  */
+} lvdgs_tsdf_blocks;
+typedef struct lvdgs_tsdf_blocks_mesh_args {
+    lvdgs_tsdf_blocks vol;
+    uint32_t seq;
+    int32_t vertex_capacity, face_capacity;   /* rows the outputs hold               */
+    int32_t cell_lo[3], cell_hi[3];           /* cells with cell_lo <= g < cell_hi   */
+    const int32_t *order;         /* pool_blocks: pool indices by ascending key     */
+    float *vertices;              /* out vertex_capacity*3                          */
+    float *colors;                /* out vertex_capacity*3, or NULL                 */
+    int32_t *faces;               /* out face_capacity*3                            */
+    int32_t *host_state;          /* LVDGS_TSDF_BLOCKS_HOST_BYTES, pinned host (the host address) */
+    void *scratch; size_t scratch_bytes;
+} lvdgs_tsdf_blocks_mesh_args;
+int lvdgs_tsdf_blocks_integrate(const lvdgs_tsdf_blocks *vol, const lvdgs_tsdf_view *const *views, int32_t count, void *stream);
+size_t lvdgs_tsdf_blocks_mesh_scratch_bytes(int32_t pool_blocks);
+int lvdgs_tsdf_blocks_mesh(const lvdgs_tsdf_blocks_mesh_args *a, void *stream);
+int lvdgs_tsdf_blocks_rehash(const lvdgs_tsdf_blocks *vol, void *stream);
+
 /* ---- Mesh scoring: area-weighted samples of a mesh and exact nearest neighbours between two clouds (what NICE-SLAM's eval_recon
  * does with trimesh.sample.sample_surface and a SciPy KD-tree on the host, after copying both meshes there) ----
  * lvdgs_mesh_sample draws num_samples points from (vertices (V,3) float32, faces (F,3) int32).  A function of (mesh, seed, sample

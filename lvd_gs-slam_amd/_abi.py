@@ -365,6 +365,32 @@ TSDF_SEQ, TSDF_N_VERTICES, TSDF_N_FACES, TSDF_OVERFLOW = 0, 1, 2, 3
 TSDF_OVERFLOW_VERTICES, TSDF_OVERFLOW_FACES, TSDF_OVERFLOW_INT32 = 1, 2, 4     # bits of the [TSDF_OVERFLOW] word
 
 
+class TsdfBlocksArgs(C.Structure):
+    _c_name_ = "lvdgs_tsdf_blocks"
+    _fields_ = [
+        ("pool_blocks", C.c_int32), ("table_slots", C.c_int32), ("origin", C.c_float * 3),
+        ("voxel_size", C.c_float), ("trunc", C.c_float), ("max_weight", C.c_float),
+        ("tsdf", _fp), ("weight", _fp), ("r", _fp), ("g", _fp), ("b", _fp),
+        ("block_key", _fp), ("table_keys", _fp), ("table_values", _fp), ("header", _fp),
+    ]
+
+
+class TsdfBlocksMeshArgs(C.Structure):
+    _c_name_ = "lvdgs_tsdf_blocks_mesh_args"
+    _fields_ = [
+        ("vol", TsdfBlocksArgs), ("seq", C.c_uint32), ("vertex_capacity", C.c_int32), ("face_capacity", C.c_int32),
+        ("cell_lo", C.c_int32 * 3), ("cell_hi", C.c_int32 * 3), ("order", _fp), ("vertices", _fp), ("colors", _fp), ("faces", _fp), ("host_state", _fp),
+        ("scratch", _fp), ("scratch_bytes", C.c_size_t),
+    ]
+
+
+TSDF_BLOCKS_HEADER_WORDS, TSDF_BLOCKS_HOST_BYTES, TSDF_BLOCKS_MAX_POOL, TSDF_BLOCKS_MAX_STEPS = 8, 64, 4194304, 1025
+TSDF_BLOCKS_HEADER_USED, TSDF_BLOCKS_HEADER_DROPPED, TSDF_BLOCKS_HEADER_OUT_OF_RANGE, TSDF_BLOCKS_HEADER_FLAGS = 0, 1, 2, 3
+TSDF_BLOCKS_TABLE_FULL = 1
+(TSDF_BLOCKS_SEQ, TSDF_BLOCKS_N_VERTICES, TSDF_BLOCKS_N_FACES, TSDF_BLOCKS_OVERFLOW, TSDF_BLOCKS_USED, TSDF_BLOCKS_DROPPED,
+ TSDF_BLOCKS_OUT_OF_RANGE, TSDF_BLOCKS_FLAGS) = range(8)
+
+
 class MeshSampleInfo(C.Structure):
     _c_name_ = "lvdgs_mesh_sample_info"     # what one lvdgs_mesh_sample leaves at ``info``
     _fields_ = [("flags", C.c_uint32), ("n_weighted", C.c_uint32), ("total", C.c_uint64)]
@@ -512,6 +538,10 @@ PROTOTYPES = {
     "lvdgs_tsdf_integrate": (_status, [_P(TsdfVolumeArgs), _P(_P(TsdfViewArgs)), _i32, _stream]),
     "lvdgs_tsdf_mesh_scratch_bytes": (_size, [_i32, _i32, _i32]),
     "lvdgs_tsdf_mesh": (_status, [_P(TsdfMeshArgs), _stream]),
+    "lvdgs_tsdf_blocks_integrate": (_status, [_P(TsdfBlocksArgs), _P(_P(TsdfViewArgs)), _i32, _stream]),
+    "lvdgs_tsdf_blocks_mesh_scratch_bytes": (_size, [_i32]),
+    "lvdgs_tsdf_blocks_mesh": (_status, [_P(TsdfBlocksMeshArgs), _stream]),
+    "lvdgs_tsdf_blocks_rehash": (_status, [_P(TsdfBlocksArgs), _stream]),
     "lvdgs_mesh_sample_scratch_bytes": (_size, [_i64]),
     "lvdgs_mesh_sample": (_status, [_P(MeshSampleArgs), _stream]),
     "lvdgs_cloud_distance_scratch_bytes": (_size, [_i64, _i64]),

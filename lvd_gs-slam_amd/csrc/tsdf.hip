@@ -1,6 +1,8 @@
 // TSDF fusion of depth maps into a dense volume and a mesh of it by surface nets (rules, arithmetic and the host block:
 // include/lvdgs.h, "TSDF fusion").
 //
+// The per-voxel rule, the corner test of a brick and the vertex of a cell are tsdf_rule.hpp's, shared with tsdf_blocks.hip.
+//
 // lvdgs_tsdf_integrate: one launch.  A workgroup of 256 threads owns a brick of 64 x 4 x 4 voxels; a thread owns four voxels along x
 // (16 lanes span a row of 64: 256 contiguous bytes of a plane), keeps them in registers across the up to 16 views and writes a row
 // back only when a view changed it.  Before anything is read, lanes 0 .. count-1 of every wave test one view each against the brick's
@@ -17,6 +19,7 @@
 #include "common.hpp"
 #include "device_utils.hpp"
 #include "spans.hpp"
+#include "tsdf_rule.hpp"
 
 namespace lvdgs {
 namespace {
@@ -25,66 +28,12 @@ constexpr int TSDF_THREADS = 256;
 constexpr int BRICK_X = 64, BRICK_Y = 4, BRICK_Z = 4;   // 16 lanes x 4 voxels, 4 rows per wave, 4 waves
 constexpr int TSDF_MAX_BLOCKS = 2048;                   // spans of the mesh passes
 
-struct TsdfView {
-    int W, H;
-    float fx, fy, cx, cy, dmin, dtrunc;
-    const float *R, *T, *depth, *image;
-    const uint8_t *mask;
-};
-
 struct IntegrateParams {
     int nx, ny, nz, count;
-    float ox, oy, oz, vs, trunc, maxw;
+    TsdfLattice lat;
     float *tsdf, *weight, *r, *g, *b;
     TsdfView v[LVDGS_TSDF_MAX_VIEWS];
 };
-
-// Can view V change a voxel of the brick whose corner voxels are (i0|i1, j0|j1, k0|k1)?  false only when the per-voxel rule skips
-// every voxel of it.  The lattice positions are monotone in the index and x, y, z of step 1 are affine in them, so each quantity below
-// is bounded over the brick by its values at the corners, up to the rounding of step 1: at most 4 * 2^-24 of M = |R0 px| + |R1 py| +
-// |R2 pz| + |T| for a voxel and as much for a corner -- ez = 1e-6 M covers both twice over.
-//  * behind:  every z <= depth_min.
-//  * far:     d <= depth_trunc, so sdf <= depth_trunc - z (rounding is monotone); below -trunc for every z.
-//  * frustum, for a brick with z >= M / 64 > 0 only: u + 0.5 < 0 is fx x + (cx + 0.5) z < 0, affine again, and u + 0.5 >= W likewise.
-//    The computed u is off by at most fx (ex + |x / z| ez) / z + a few ulps of |u| + |cx|; times z, with 1 / z <= 64 / Mz, that is under
-//    2e-5 (fx Mx + (|cx| + W + 1) Mz): the margin taken is 1e-4 of it.
-__device__ __forceinline__ bool brick_may_touch(const IntegrateParams &p, const TsdfView &V, int i0, int i1, int j0, int j1, int k0, int k1) {
-    float R[9], T[3];
-#pragma unroll
-    for (int q = 0; q < 9; q++) R[q] = V.R[q];
-#pragma unroll
-    for (int q = 0; q < 3; q++) T[q] = V.T[q];
-    const float inf = __builtin_inff();
-    const float cl = V.cx + 0.5f, cr = cl - (float)V.W, ct = V.cy + 0.5f, cb = ct - (float)V.H;
-    float zmin = inf, zmax = -inf, Mx = 0.f, My = 0.f, Mz = 0.f;
-    float gl = -inf, gr = inf, gt = -inf, gb = inf;
-#pragma unroll
-    for (int c = 0; c < 8; c++) {
-        const float px = p.ox + p.vs * (float)((c & 1) ? i1 : i0);
-        const float py = p.oy + p.vs * (float)((c & 2) ? j1 : j0);
-        const float pz = p.oz + p.vs * (float)((c & 4) ? k1 : k0);
-        const float x = ((R[0] * px + R[1] * py) + R[2] * pz) + T[0];
-        const float y = ((R[3] * px + R[4] * py) + R[5] * pz) + T[1];
-        const float z = ((R[6] * px + R[7] * py) + R[8] * pz) + T[2];
-        Mx = fmaxf(Mx, fabsf(R[0] * px) + fabsf(R[1] * py) + fabsf(R[2] * pz) + fabsf(T[0]));
-        My = fmaxf(My, fabsf(R[3] * px) + fabsf(R[4] * py) + fabsf(R[5] * pz) + fabsf(T[1]));
-        Mz = fmaxf(Mz, fabsf(R[6] * px) + fabsf(R[7] * py) + fabsf(R[8] * pz) + fabsf(T[2]));
-        zmin = fminf(zmin, z); zmax = fmaxf(zmax, z);
-        gl = fmaxf(gl, V.fx * x + cl * z); gr = fminf(gr, V.fx * x + cr * z);
-        gt = fmaxf(gt, V.fy * y + ct * z); gb = fminf(gb, V.fy * y + cb * z);
-    }
-    if (!(Mx + My + Mz < inf)) return true;   // a NaN or an overflow somewhere: let the voxels decide
-    const float ez = 1e-6f * Mz;
-    if (zmax + ez <= V.dmin) return false;
-    const float zlo = zmin - 2.f * ez;
-    if (V.dtrunc - zlo < -p.trunc) return false;
-    if (zlo > 0.f && zlo >= 0.015625f * Mz && V.fx > 0.f && V.fy > 0.f) {
-        const float mx = 1e-4f * (V.fx * Mx + (fabsf(V.cx) + (float)V.W + 1.f) * Mz);
-        const float my = 1e-4f * (V.fy * My + (fabsf(V.cy) + (float)V.H + 1.f) * Mz);
-        if (gl + mx < 0.f || gr - mx > 0.f || gt + my < 0.f || gb - my > 0.f) return false;
-    }
-    return true;
-}
 
 // COLOR: the volume has colour planes.  VEC: nx % 4 == 0 and every plane 16-byte aligned -- a thread's four voxels are one float4.
 template <bool COLOR, bool VEC>
@@ -93,7 +42,7 @@ __global__ void __launch_bounds__(TSDF_THREADS) tsdf_integrate_kernel(IntegrateP
     const int bi = blockIdx.x * BRICK_X, bj = blockIdx.y * BRICK_Y, bk = blockIdx.z * BRICK_Z;
     bool touch = false;
     if (lane < p.count)
-        touch = brick_may_touch(p, p.v[lane], bi, min(bi + BRICK_X, p.nx) - 1, bj, min(bj + BRICK_Y, p.ny) - 1, bk, min(bk + BRICK_Z, p.nz) - 1);
+        touch = brick_may_touch(p.lat, p.v[lane], bi, min(bi + BRICK_X, p.nx) - 1, bj, min(bj + BRICK_Y, p.ny) - 1, bk, min(bk + BRICK_Z, p.nz) - 1);
     const uint32_t live = (uint32_t)__ballot(touch);   // the same in all four waves
     if (live == 0u) return;
 
@@ -124,10 +73,10 @@ __global__ void __launch_bounds__(TSDF_THREADS) tsdf_integrate_kernel(IntegrateP
     load4(p.weight, w);
     if constexpr (COLOR) { load4(p.r, cr); load4(p.g, cg); load4(p.b, cb); }
 
-    const float py = p.oy + p.vs * (float)j, pz = p.oz + p.vs * (float)k;
+    const float py = p.lat.oy + p.lat.vs * (float)j, pz = p.lat.oz + p.lat.vs * (float)k;
     float px[4];
 #pragma unroll
-    for (int q = 0; q < 4; q++) px[q] = p.ox + p.vs * (float)(i0 + q);
+    for (int q = 0; q < 4; q++) px[q] = p.lat.ox + p.lat.vs * (float)(i0 + q);
     bool changed = false, recoloured = false;
     for (int v = 0; v < p.count; v++) {
         if (!((live >> v) & 1u)) continue;   // (wave-uniform)
@@ -146,13 +95,10 @@ __global__ void __launch_bounds__(TSDF_THREADS) tsdf_integrate_kernel(IntegrateP
         bool ok[4];
 #pragma unroll
         for (int q = 0; q < 4; q++) {
-            const float x = ((R[0] * px[q] + R[1] * py) + R[2] * pz) + T[0];
-            const float y = ((R[3] * px[q] + R[4] * py) + R[5] * pz) + T[1];
-            z[q] = ((R[6] * px[q] + R[7] * py) + R[8] * pz) + T[2];
-            const float u = V.fx * (x / z[q]) + V.cx, vv = V.fy * (y / z[q]) + V.cy;
-            const float uf = floorf(u + 0.5f), vf = floorf(vv + 0.5f);
-            ok[q] = q < nv && z[q] > V.dmin && uf >= 0.f && uf < (float)V.W && vf >= 0.f && vf < (float)V.H;
-            pix[q] = ok[q] ? (int)vf * V.W + (int)uf : 0;
+            const TsdfPixel at = tsdf_pixel(V, R, T, px[q], py, pz);
+            z[q] = at.z;
+            ok[q] = q < nv && at.ok;
+            pix[q] = ok[q] ? at.pix : 0;
         }
         if (!__any(ok[0] || ok[1] || ok[2] || ok[3])) continue;   // (a wave's rows outside this view)
         float d[4];
@@ -164,8 +110,8 @@ __global__ void __launch_bounds__(TSDF_THREADS) tsdf_integrate_kernel(IntegrateP
         float sdf[4];
 #pragma unroll
         for (int q = 0; q < 4; q++) {
-            sdf[q] = d[q] - z[q];
-            ok[q] = ok[q] && d[q] > 0.f && d[q] <= V.dtrunc && m[q] != 0 && !(sdf[q] < -p.trunc);
+            const bool seen = tsdf_seen(V, p.lat.trunc, d[q], m[q], z[q], &sdf[q]);
+            ok[q] = ok[q] && seen;
         }
         float c0[4], c1[4], c2[4];
         if (coloured) {
@@ -178,16 +124,8 @@ __global__ void __launch_bounds__(TSDF_THREADS) tsdf_integrate_kernel(IntegrateP
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             if (!ok[q]) continue;
-            const float t = fminf(1.0f, sdf[q] / p.trunc);
-            const float w0 = w[q], w1 = w0 + 1.0f;
-            f[q] = (f[q] * w0 + t) / w1;
-            if (coloured) {
-                cr[q] = (cr[q] * w0 + c0[q]) / w1;
-                cg[q] = (cg[q] * w0 + c1[q]) / w1;
-                cb[q] = (cb[q] * w0 + c2[q]) / w1;
-                recoloured = true;
-            }
-            w[q] = fminf(w1, p.maxw);
+            tsdf_blend(p.lat, sdf[q], coloured, c0[q], c1[q], c2[q], f[q], w[q], cr[q], cg[q], cb[q]);
+            recoloured = recoloured || coloured;
             changed = true;
         }
     }
@@ -312,39 +250,18 @@ __global__ void __launch_bounds__(TSDF_THREADS) tsdf_vertices_kernel(MeshParams 
             o[q] = s + ((q & 1) ? 1u : 0u) + ((q & 2) ? sy : 0u) + ((q & 4) ? sz : 0u);
             f[q] = M.tsdf[o[q]];
         }
-        float sum[3] = {0.f, 0.f, 0.f}, col[3] = {0.f, 0.f, 0.f};
-        int crossings = 0;
-        // the 12 edges: axis, then the two other offsets in (x before y before z) order, low bit first
-#pragma unroll
-        for (int e = 0; e < 12; e++) {
-            const int axis = e >> 2, lo_bit = e & 1, hi_bit = (e >> 1) & 1;
-            // corner number (dx | dy << 1 | dz << 2) of the edge's low end
-            const int c0 = axis == 0 ? (lo_bit << 1 | hi_bit << 2) : axis == 1 ? (lo_bit | hi_bit << 2) : (lo_bit | hi_bit << 1);
-            const int c1 = c0 | (1 << axis);
-            const float f0 = f[c0], f1 = f[c1];
-            if ((f0 < 0.f) == (f1 < 0.f)) continue;
-            const float q = f0 / (f0 - f1);
-#pragma unroll
-            for (int a = 0; a < 3; a++) sum[a] += a == axis ? q : (float)((c0 >> a) & 1);
-            if constexpr (COLOR) {
-                const float r0 = M.r[o[c0]], r1 = M.r[o[c1]], g0 = M.g[o[c0]], g1 = M.g[o[c1]], b0 = M.b[o[c0]], b1 = M.b[o[c1]];
-                col[0] += r0 + q * (r1 - r0);
-                col[1] += g0 + q * (g1 - g0);
-                col[2] += b0 + q * (b1 - b0);
-            }
-            crossings++;
-        }
-        const float cnt = (float)crossings;
+        float mean[3], col[3];
+        tsdf_cell_vertex<COLOR>(f, [&](int q, int ch) { return (ch == 0 ? M.r : ch == 1 ? M.g : M.b)[o[q]]; }, mean, col);
         const Sample c = sample_of(M, s);
         const size_t out = (size_t)row * 3;
-        M.vertices[out + 0] = M.ox + M.vs * ((float)c.i + sum[0] / cnt);
-        M.vertices[out + 1] = M.oy + M.vs * ((float)c.j + sum[1] / cnt);
-        M.vertices[out + 2] = M.oz + M.vs * ((float)c.k + sum[2] / cnt);
+        M.vertices[out + 0] = M.ox + M.vs * ((float)c.i + mean[0]);
+        M.vertices[out + 1] = M.oy + M.vs * ((float)c.j + mean[1]);
+        M.vertices[out + 2] = M.oz + M.vs * ((float)c.k + mean[2]);
         if constexpr (COLOR) {
             if (M.colors) {
-                M.colors[out + 0] = col[0] / cnt;
-                M.colors[out + 1] = col[1] / cnt;
-                M.colors[out + 2] = col[2] / cnt;
+                M.colors[out + 0] = col[0];
+                M.colors[out + 1] = col[1];
+                M.colors[out + 2] = col[2];
             }
         }
     }
@@ -460,8 +377,7 @@ int lvdgs_tsdf_integrate(const lvdgs_tsdf_volume *vol, const lvdgs_tsdf_view *co
     }
     if (count == 0) return LVDGS_OK;
     p.nx = vol->nx; p.ny = vol->ny; p.nz = vol->nz; p.count = count;
-    p.ox = vol->origin[0]; p.oy = vol->origin[1]; p.oz = vol->origin[2];
-    p.vs = vol->voxel_size; p.trunc = vol->trunc; p.maxw = vol->max_weight;
+    p.lat = TsdfLattice{vol->origin[0], vol->origin[1], vol->origin[2], vol->voxel_size, vol->trunc, vol->max_weight};
     p.tsdf = vol->tsdf; p.weight = vol->weight; p.r = vol->r; p.g = vol->g; p.b = vol->b;
     const bool color = vol->r != nullptr;
     const uintptr_t bits = (uintptr_t)vol->tsdf | (uintptr_t)vol->weight | (uintptr_t)vol->r | (uintptr_t)vol->g | (uintptr_t)vol->b;

@@ -44,6 +44,7 @@ Stand-ins for what is out of scope, all injectable:
 ``render_fn`` / ``view_loss_fn`` / ``refine_loss_fn`` / ``knn_fn`` default to the HIP paths; the CPU tests pass the dense float64
 renderer and the loss oracle so that the same harness runs at toy size without a GPU.
 """
+import math
 import time
 from types import SimpleNamespace
 
@@ -621,7 +622,8 @@ class SlamSequence:
             return {}
         return {k: float(np.mean([r[k] for r in rows if r.get(k) is not None])) for k in rows[0] if any(r.get(k) is not None for r in rows)}
 
-    def fuse_mesh(self, voxel_size, bounds=None, frames="keyframes", mask="static", depth_trunc=None, max_voxels=1 << 26):
+    def fuse_mesh(self, voxel_size, bounds=None, frames="keyframes", mask="static", depth_trunc=None, max_voxels=1 << 26, volume="dense",
+                  pool_blocks=None):
         """A surface of the finished map: the chosen frames rendered at their estimated poses with the run's ``render_fn``, their depth,
         colour and -- ``mask="static"``, where a frame has one -- static mask fused into a TSDF volume (``tsdf.TsdfVolume``, 16 views per
         library call, no wait), and the volume's surface-nets mesh (one wait).  What the reference's evaluation does with Open3D on the
@@ -631,8 +633,16 @@ class SlamSequence:
         padded by the truncation distance ``4 * voxel_size``.  ``frames``: "keyframes", "all" or frame indices.  ``mask``: "static" or None.
         ``depth_trunc``: rendered depth beyond it is not fused (None: no limit).  ``max_voxels``: a volume that would hold more samples gets
         a larger voxel size (``TsdfVolume.from_bounds``; the record says so).  -> (``tsdf.Mesh`` on the device, a record: dims, the
-        voxel size used and asked for, frames fused, vertex and face counts)."""
+        voxel size used and asked for, frames fused, vertex and face counts).
+
+        ``volume="blocks"``: a ``tsdf_blocks.TsdfBlockVolume`` with its origin at the low corner of ``bounds`` instead -- only the blocks
+        the rendered surfaces cross are stored, the voxel size asked for is always the one used and ``max_voxels`` is not consulted.
+        ``pool_blocks``: the pool to start with (default 4096); when the fusion had to drop blocks the pool is doubled once and the
+        frames are fused again.  The record then carries blocks, dropped and pool_blocks in place of dims (one more wait: the stats)."""
         from .tsdf import TsdfVolume
+        from .tsdf_blocks import TsdfBlockVolume
+        if volume not in ("dense", "blocks"):
+            raise ValueError(f"fuse_mesh: volume 'dense' or 'blocks', not {volume!r}")
         gaussians = self.frontend_gaussians
         if frames == "keyframes":
             chosen = list(self.kf_indices)
@@ -649,30 +659,49 @@ class SlamSequence:
                 points = xyz[opaque] if bool(opaque.any()) else xyz
                 pad = 4.0 * float(voxel_size)
                 bounds = ((points.min(0).values - pad).tolist(), (points.max(0).values + pad).tolist())
-            volume = TsdfVolume.from_bounds(bounds[0], bounds[1], voxel_size, max_voxels=max_voxels, device=xyz.device)
-            views = []
-            for idx in chosen:
-                frame = self.cameras[idx]
-                pkg = self.render_fn(frame, gaussians, self.pipeline_params, self.background)
-                static = None
-                if mask == "static":
-                    static = getattr(frame, "expanded_static_mask", None)
-                    if static is None:
-                        static = getattr(frame, "static_mask", None)
-                    if static is not None:
-                        static = static.to(xyz.device)
-                depth = pkg["depth"].detach()
-                views.append(dict(depth=depth.reshape(depth.shape[-2], depth.shape[-1]).contiguous(), R=frame.R, T=frame.T,
-                                  intrinsics=(frame.fx, frame.fy, frame.cx, frame.cy), image=pkg["render"].detach().contiguous(), mask=static,
-                                  depth_trunc=float("inf") if depth_trunc is None else float(depth_trunc)))
-                if len(views) == 16:
-                    volume.integrate_views(views)
-                    views = []
-            if views:
-                volume.integrate_views(views)
-        mesh = volume.extract_mesh()
-        record = dict(dims=list(volume.dims), voxel_size=volume.voxel_size, voxel_size_requested=volume.voxel_size_requested,
+            if volume == "blocks":
+                vol = TsdfBlockVolume(bounds[0], voxel_size, 4096 if pool_blocks is None else int(pool_blocks), device=xyz.device)
+            else:
+                vol = TsdfVolume.from_bounds(bounds[0], bounds[1], voxel_size, max_voxels=max_voxels, device=xyz.device)
+
+            def fuse():
+                views = []
+                for idx in chosen:
+                    frame = self.cameras[idx]
+                    pkg = self.render_fn(frame, gaussians, self.pipeline_params, self.background)
+                    static = None
+                    if mask == "static":
+                        static = getattr(frame, "expanded_static_mask", None)
+                        if static is None:
+                            static = getattr(frame, "static_mask", None)
+                        if static is not None:
+                            static = static.to(xyz.device)
+                    depth = pkg["depth"].detach()
+                    views.append(dict(depth=depth.reshape(depth.shape[-2], depth.shape[-1]).contiguous(), R=frame.R, T=frame.T,
+                                      intrinsics=(frame.fx, frame.fy, frame.cx, frame.cy), image=pkg["render"].detach().contiguous(), mask=static,
+                                      depth_trunc=float("inf") if depth_trunc is None else float(depth_trunc)))
+                    if len(views) == 16:
+                        vol.integrate_views(views)
+                        views = []
+                if views:
+                    vol.integrate_views(views)
+
+            fuse()
+            if volume == "blocks" and vol.stats()["dropped"]:
+                vol.grow(2 * vol.pool_blocks)
+                vol.reset()
+                fuse()
+        if volume == "blocks":      # the cells of the dense volume over ``bounds`` at this voxel size: nothing outside the box is meshed
+            cells = [max(int(math.ceil((b - a) / float(voxel_size))) + 1, 2) - 1 for a, b in zip(bounds[0], bounds[1])]
+            mesh = vol.extract_mesh(cell_range=((0, 0, 0), cells))
+        else:
+            mesh = vol.extract_mesh()
+        record = dict(voxel_size=vol.voxel_size, voxel_size_requested=vol.voxel_size_requested,
                       frames=len(chosen), vertices=int(mesh.vertices.shape[0]), faces=int(mesh.faces.shape[0]))
+        if volume == "blocks":
+            record.update(volume="blocks", blocks=vol.last_stats["blocks"], dropped=vol.last_stats["dropped"], pool_blocks=vol.pool_blocks)
+        else:
+            record.update(dims=list(vol.dims))
         return mesh, record
 
     def _chosen_frames(self, frames):
@@ -710,7 +739,7 @@ class SlamSequence:
         return fused
 
     def eval_mesh(self, voxel_size, bounds=None, frames="keyframes", n_samples=200_000, threshold=None, seed=0, seed_gt=None, mask="static",
-                  depth_trunc=None, max_voxels=1 << 26, est_depth="render"):
+                  depth_trunc=None, max_voxels=1 << 26, est_depth="render", volume="dense", pool_blocks=None):
         """The finished map's surface scored against ground-truth geometry (``mesh_eval.score``: accuracy, completion, completion ratio,
         precision, recall, F-score, chamfer -- NICE-SLAM's ``eval_recon`` protocol), everything on the device.
 
@@ -719,6 +748,8 @@ class SlamSequence:
         bounds and voxel size, fused from the same frames' dataset depth at ``R_gt``, ``T_gt``.  ``threshold``: default twice the voxel
         size actually used.  A dataset without metric depth (all-zero planes: the KITTI / dl3dv placeholders) gives an empty
         ground-truth mesh, which raises ``LvdgsError``.  Three waits: one per mesh, one for the score.
+        ``volume="blocks"``, ``pool_blocks``: the estimate's rendered depth goes into a block-sparse volume (``fuse_mesh``); the ground
+        truth and ``est_depth="dataset"`` stay dense.
         -> (the score's dict, a record: both meshes' counts, the voxel size, the threshold, the samples and seeds)."""
         from . import mesh_eval
         from .tsdf import TsdfVolume
@@ -734,7 +765,8 @@ class SlamSequence:
                 pad = 4.0 * float(voxel_size)
                 bounds = ((points.min(0).values - pad).tolist(), (points.max(0).values + pad).tolist())
             if est_depth == "render":
-                est, est_record = self.fuse_mesh(voxel_size, bounds=bounds, frames=chosen, mask=mask, depth_trunc=depth_trunc, max_voxels=max_voxels)
+                est, est_record = self.fuse_mesh(voxel_size, bounds=bounds, frames=chosen, mask=mask, depth_trunc=depth_trunc, max_voxels=max_voxels,
+                                                 volume=volume, pool_blocks=pool_blocks)
             else:
                 volume = TsdfVolume.from_bounds(bounds[0], bounds[1], voxel_size, max_voxels=max_voxels, color=False, device=xyz.device)
                 fused = self._fuse_dataset_depth(volume, chosen, "estimated", depth_trunc)

@@ -242,6 +242,9 @@ def main():
                          "lvdgs_tsdf_integrate / lvdgs_tsdf_mesh) and write the mesh as a binary PLY")
     ap.add_argument("--mesh-voxel", type=float, default=None, metavar="SIZE",
                     help="with --mesh / --mesh-eval: the voxel size (default: 1/192 of the longest side of the opaque Gaussians' extent)")
+    ap.add_argument("--mesh-volume", choices=("dense", "blocks"), default="dense",
+                    help="with --mesh / --mesh-eval: 'blocks' fuses the rendered depth into a block-sparse volume (tsdf_blocks.TsdfBlockVolume): only "
+                         "the blocks near a surface are stored and the voxel size asked for is the one used")
     ap.add_argument("--mesh-eval", action="store_true",
                     help="after the run: the fused mesh scored against a mesh fused from the dataset's depth at the ground-truth poses "
                          "(SlamSequence.eval_mesh, lvdgs_mesh_sample / lvdgs_cloud_distance): accuracy, completion, F-score; needs no --mesh PATH")
@@ -276,13 +279,13 @@ def main():
     if a.mesh:
         from lvdgs.tsdf import save_mesh_ply
         t_mesh = time.perf_counter()
-        mesh, record = seq.fuse_mesh(voxel)
+        mesh, record = seq.fuse_mesh(voxel, volume=a.mesh_volume)
         record["fuse_mesh_seconds"] = round(time.perf_counter() - t_mesh, 4)
         save_mesh_ply(a.mesh, mesh)
         out["mesh"] = dict(record, path=a.mesh, file_bytes=os.path.getsize(a.mesh))
     if a.mesh_eval:
         t_eval = time.perf_counter()
-        score, record = seq.eval_mesh(voxel, n_samples=a.mesh_samples)
+        score, record = seq.eval_mesh(voxel, n_samples=a.mesh_samples, volume=a.mesh_volume)
         out["mesh_eval"] = dict(score, record=record, eval_mesh_seconds=round(time.perf_counter() - t_eval, 4))
     out["seed"] = a.seed
     out["tool_seconds"] = round(time.perf_counter() - t0, 2)
