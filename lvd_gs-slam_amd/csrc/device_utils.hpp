@@ -69,7 +69,8 @@ __device__ __forceinline__ float wave_max(float v) {
 __device__ __forceinline__ float wave_min(float v) { return -wave_max(-v); }
 
 // Inclusive prefix sum over the wave's lanes, in every lane (lane 63: the wave's total); lane shifts by 1, 2, ... 32.
-// T: uint32_t, int.  Reached by all 64 lanes.  No LDS, no barrier.
+// T: uint32_t, int, unsigned long long (the 64-bit form moves both halves; tested through scan_workgroup).  Reached by all 64 lanes.
+// No LDS, no barrier.
 template <typename T>
 __device__ __forceinline__ T wave_inclusive_scan(T v) {
     const int lane = threadIdx.x & 63;
@@ -82,11 +83,13 @@ __device__ __forceinline__ T wave_inclusive_scan(T v) {
 }
 
 // Exclusive prefix sum of one value per thread over a workgroup of THREADS threads (up to 16 whole waves, all of which reach it);
-// *total = the workgroup's sum, in every thread.  T: uint32_t, int.  s_scan: SCAN_WORDS words of LDS; two barriers (wave scans,
-// then the wave totals by wave 0), both passed by every thread, so they also publish what the caller wrote to LDS before the call.
+// *total = the workgroup's sum, in every thread.  T: uint32_t, int, unsigned long long (sums wrap modulo the type).  s_scan: SCAN_WORDS
+// words of T in LDS; two barriers (wave scans, then the wave totals by wave 0), both passed by every thread, so they also publish what
+// the caller wrote to LDS before the call.
 // Words 0-15 are written before the first barrier and read between the two, words 16-31 written between them and read behind the
 // second: a second call on the same s_scan needs NO barrier in front (its first barrier orders its writes of 16-31 behind this
-// call's reads), and the first call needs none either when nothing else has s_scan in use.
+// call's reads), and the first call needs none either when nothing else has s_scan in use.  Every instantiation in use, and these
+// three promises, are pinned by tests/test_gpu_primitives.py through the probe library (tests/probe/primitives_probe.hip).
 constexpr int SCAN_WORDS = 32;
 template <int THREADS, typename T>
 __device__ __forceinline__ T scan_workgroup(T v, T *s_scan, T *total) {

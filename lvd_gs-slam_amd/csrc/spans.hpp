@@ -55,6 +55,7 @@ __device__ __forceinline__ SpanRange<I> span_range(I n, I span, uint32_t block) 
 // front of span j to before[j * stride] (in place when before == counts) and returns the total, in every thread.  Rounds of THREADS
 // spans, the last one padded with zeros, with a carry of type C across the rounds.  T is the type a round is scanned in: the sum of
 // the THREADS counts of one round must fit T; the total need only fit C.  sh: SCAN_WORDS of LDS; calls may follow each other on it.
+// (T, C) in use and tested: (uint32_t, uint32_t), (uint32_t, unsigned long long), (unsigned long long, unsigned long long).
 template <int THREADS, typename T, typename C>
 __device__ __forceinline__ C scan_span_counts(const T *counts, C *before, int blocks, int stride, T *sh) {
     C carry = 0;
@@ -78,7 +79,8 @@ __device__ __forceinline__ C scan_span_counts(const T *counts, C *before, int bl
 // Step 3: the running position of a workgroup that walks its span in tiles of THREADS elements.  `row` starts as what lies in front of
 // the span (step 2's word for it).  place(v) is called once a tile by EVERY thread of the workgroup -- the tile loop's condition must
 // be uniform, a thread past the span's end passes 0 -- and returns the position of this thread's element, then moves `row` past the
-// tile.  T, C and sh as for scan_span_counts: a tile's sum must fit T.
+// tile.  T, C and sh as for scan_span_counts: a tile's sum must fit T.  (T, C) in use and tested: those of scan_span_counts and
+// (uint32_t, int64_t).
 template <int THREADS, typename T, typename C = T>
 struct TileWalk {
     C row;

@@ -26,6 +26,21 @@ def depth_map(W, H, valid_share=0.6, seed=0, specials=True):
     return d
 
 
+def marked_depth_map(W, H, seed=5):
+    """(H, W) float32 as a mono depth carries it: -1 markers on three pixels in ten, other negatives on a quarter (so the lower median
+    of ALL values, what depth.median() is, is a negative value that is no marker), both zeros, a few +inf, the rest in (0, 100].  No NaN."""
+    rng = np.random.default_rng(seed)
+    d = (0.5 + 60.0 * rng.random((H, W))).astype(np.float32)
+    kind = rng.random((H, W))
+    d[kind < 0.55] = (-0.1 - 5.0 * rng.random((H, W))).astype(np.float32)[kind < 0.55]
+    d[kind < 0.30] = -1.0
+    d[kind > 0.97] = np.inf
+    flat = d.reshape(-1)
+    flat[::97] = 0.0
+    flat[5::97] = -0.0
+    return d
+
+
 def image(W, H, seed=1):
     """(3, H, W) float32 with values below 0, exactly 0 and 1, and above 1."""
     rng = np.random.default_rng(seed)

@@ -75,6 +75,20 @@ def test_bits_against_the_oracle(W, H, ds):
     same_as_oracle(with_median, oracle.seed_points(None, clean, cases.INTRINSICS, R, T, 1.0 / ds, seed))
 
 
+@pytest.mark.parametrize("W,H,ds", [(W, H, ds) for (W, H), ds in zip(cases.SIZES, (4, 8, 32))])
+def test_median_of_negative_markers_and_infinities(W, H, ds):
+    """Every depth takes part in depth.median(): -1 markers, other negatives, both zeros and +inf go through the select's negative branch and
+    across the sign in its bucket choice; here the median itself is negative."""
+    depth = cases.marked_depth_map(W, H)
+    got = fused(None, depth, ds, 80, want_median=True)
+    want = oracle.lower_median(depth)
+    assert want < 0 and want != -1.0 and np.isinf(depth).any() and (depth == -1.0).any()
+    assert got.median_bits == int(bits(want.reshape(1))[0]) == int(bits(torch.from_numpy(depth).cuda().median().reshape(1))[0])
+    R, T = cases.pose()
+    same_as_oracle(got, oracle.seed_points(None, depth, cases.INTRINSICS, R, T, 1.0 / ds, 80))
+    assert got.n > 0
+
+
 def _sparse(W, H, n_valid, seed=4):
     d = np.zeros((H, W), np.float32)
     at = np.random.default_rng(seed).choice(W * H, size=n_valid, replace=False)

@@ -77,6 +77,16 @@ def test_selection_is_uniform_over_pixels_and_neighbours():
     assert np.abs(zp).max() <= 5
 
 
+@pytest.mark.parametrize("W,H", cases.SIZES[:2])
+def test_marked_depth_map_has_a_negative_median_that_torch_agrees_on(W, H):
+    d = cases.marked_depth_map(W, H)
+    want = oracle.lower_median(d)
+    assert not np.isnan(d).any() and np.isinf(d).any() and (d == -1.0).any() and np.signbit(d[d == 0]).any() and not np.signbit(d[d == 0]).all()
+    assert want < 0 and want != -1.0 and 0.5 < (d < 0).mean() < 0.6
+    assert float(torch.from_numpy(d).median()) == float(want)
+    assert 0.2 < oracle.valid_mask(d).mean() < 0.5      # and there is something to seed
+
+
 def test_call_seed_is_a_splitmix64_step():
     from lvdgs.seeding import call_seed
     # SplitMix64's first output for the seeds 0 and 1234567, and its second for the seed 0 (the state after one step is the increment)
