@@ -996,6 +996,113 @@ size_t lvdgs_dynamic_mask_state_bytes(int32_t width, int32_t height, int32_t his
 size_t lvdgs_dynamic_mask_scratch_bytes(int32_t width, int32_t height);
 int lvdgs_dynamic_mask(const lvdgs_dynamic_mask_args *a, void *stream);
 
+/* ---- dense Farneback optical flow and the motion mask of the masker's fallback branch (reference utils/slam_frontend.py
+ * _fallback_detection :651-672: cv2.cvtColor, cv2.calcOpticalFlowFarneback(prev, cur, None, pyr_scale=0.5, levels=3, winsize=15,
+ * iterations=3, poly_n=5, poly_sigma=1.2, flags=0), magnitude > motion_threshold, a 7 x 7 cv2.dilate) ----
+ * THE TEXT BELOW IS THE DEFINITION.  It restates OpenCV's Farneback with the box window (flags = 0, no initial flow); parity with
+ * the real cv2 -- calcOpticalFlowFarneback, the grey conversion, dilate -- is UNPINNED: OpenCV is not installed where this is built.
+ * (h, w) is a level's size, (H, W) = (height, width) the frame's.  float = float32; every float expression is evaluated as written,
+ * without contraction; a sum over taps adds one product at a time, taps ascending.  "On the host in double" values reach the device
+ * rounded to float32.  The flow of a second frame that is the first one shifted by +d is +d.
+ * GREY (lvdgs_motion_mask).  image is (3, H, W) float32.  Per channel q = (uint8)min(max(c * 255.0f, 0), 255), truncated (the
+ *   reference's (img * 255).astype(np.uint8); NaN is outside the contract); grey = (4899 R + 9617 G + 1868 B + 8192) >> 14 in integers.
+ * PYRAMID.  k = 0, s = 1; while k < levels: s *= pyr_scale; stop when W s < 32 or H s < 32; else k++.  Levels k .. 0 are processed,
+ *   coarse to fine.  Level k: scale = the product of k factors pyr_scale, sigma = (1 / scale - 1) / 2, ksize = max(rint(5 sigma) | 1, 3),
+ *   w = rint(W scale), h = rint(H scale), rint rounding half to even (261 x 259: 130 x 130, 65 x 65, 33 x 32).  Each of the two grey
+ *   images is converted to float, blurred at FULL resolution -- along the rows, then along the columns, border reflect-101 -- by ksize
+ *   taps ([1/4, 1/2, 1/4] when sigma == 0, else exp(-x^2 / (2 sigma^2)) normalised to sum 1, on the host in double), and resized to
+ *   w x h bilinearly: source coordinate s = (i + 0.5) * (n_in / n_out) - 0.5 in double, i0 = floor(s), f = (float)(s - i0), the indices
+ *   i0 and i0 + 1 clamped to the image, value (a (1 - fx) + b fx) (1 - fy) + (c (1 - fx) + d fx) fy with a, b the upper pair.  The
+ *   flow of the coarser level is resized the same way, component by component, and multiplied by (float)(1 / pyr_scale); the coarsest
+ *   level starts from zero.
+ * POLYNOMIAL EXPANSION (n = poly_n, taps -n .. n), on the host in double: g[x] = exp(-x^2 / (2 poly_sigma^2)) rounded to float32, then
+ *   divided by its sum; xg = x g, xxg = x^2 g; the 6 x 6 moment matrix G with G00 = sum g[y] g[x], G11 = sum g g x^2, G33 = sum g g x^4,
+ *   G55 = sum g g x^2 y^2 over the (2n + 1)^2 window, G22 = G03 = G04 = G30 = G40 = G11, G44 = G33, G34 = G43 = G55, the rest 0;
+ *   ig11 = inv(G)[1][1], ig03 = inv(G)[0][3], ig33 = inv(G)[3][3], ig55 = inv(G)[5][5].  Correlations of the level image along the
+ *   columns with g, xg, xxg give v0, v1, v2; along the rows then b1 = v0*g, b2 = v0*xg, b4 = v0*xxg, b3 = v1*g, b5 = v1*xg, b6 = v2*g;
+ *   both passes replicate the edge.  R = [b3 ig11, b2 ig11, b1 ig03 + b6 ig33, b1 ig03 + b4 ig33, b5 ig55]: (y, x, yy, xx, xy).
+ * MATRICES at pixel (x, y) with flow (dx, dy): fx = (float)x + dx, fy = (float)y + dy, x1 = floor(fx), y1 = floor(fy).  If 0 <= x1 <
+ *   w - 1 and 0 <= y1 < h - 1: with fx -= x1, fy -= y1 the five channels of R1 are interpolated into r2 .. r6 as a00 R1[y1][x1] +
+ *   a01 R1[y1][x1+1] + a10 R1[y1+1][x1] + a11 R1[y1+1][x1+1], a00 = (1-fx)(1-fy), a01 = fx (1-fy), a10 = (1-fx) fy, a11 = fx fy; then
+ *   r4 = (R0[2] + r4) 0.5, r5 = (R0[3] + r5) 0.5, r6 = (R0[4] + r6) 0.25, r2 = (R0[0] - r2) 0.5 + (r4 dy + r6 dx),
+ *   r3 = (R0[1] - r3) 0.5 + (r6 dy + r5 dx).  Otherwise r2 = r3 = 0, r4 = R0[2], r5 = R0[3], r6 = R0[4] 0.5.  All five are multiplied by
+ *   bx by, where bx = B[min(x, 5)] B[min(w - 1 - x, 5)] (by likewise with y, h), B = {0.14, 0.14, 0.4472, 0.4472, 0.4472, 1}.
+ *   M = [r4 r4 + r6 r6, (r4 + r5) r6, r5 r5 + r6 r6, r4 r2 + r6 r3, r6 r2 + r5 r3].
+ * UPDATE.  S = the sum of M over the winsize x winsize window -- along the rows, then along the columns, both replicating the edge --
+ *   times (float)(1 / winsize^2).  With [g11, g12, g22, h1, h2] = S: idet = 1 / (g11 g22 - g12 g12 + 1e-3f),
+ *   flow_x = (g11 h2 - g12 h1) idet, flow_y = (g22 h1 - g12 h2) idet.  A level runs `iterations` updates; M is recomputed from the
+ *   new flow after every update but the last.
+ * lvdgs_farneback_flow: prev, next: H*W grey bytes each on the device; flow: (H, W, 2) float32, x then y.  scratch:
+ *   lvdgs_farneback_scratch_bytes bytes, no initialisation needed (0 for sizes the call refuses).  Per level one launch that blurs and
+ *   resizes both images, one that expands both, one that resizes the flow and forms M, and one per update (it sums M, solves and forms
+ *   the next M): 3 + iterations launches a level, enqueued at once, their number a function of the sizes and parameters only.
+ * LVDGS_E_INVALID: args, prev, next, flow or scratch NULL; winsize even or outside 3..31; poly_n neither 5 nor 7; scratch too small.
+ * LVDGS_E_RANGE: width or height outside 1..16384; pyr_scale not inside (0, 1); levels outside 0..8; iterations outside 1..10;
+ * poly_sigma not above 0; a pyramid level whose blur has more than LVDGS_FARNEBACK_MAX_BLUR_TAPS taps.  All before any launch.
+ *
+ * lvdgs_motion_mask: the fallback's statements around the flow, stateful.  state: lvdgs_motion_mask_state_bytes bytes, caller-owned: a
+ *   header and the stored grey plane; a zeroed block -- and a block left by another frame size -- holds no previous frame.  mode:
+ *   LVDGS_MOTION_OBSERVE alone: the grey plane of image becomes the stored frame, nothing else is written (one launch).
+ *   LVDGS_MOTION_MASK: the flow from the stored frame to the grey plane of image; moving = sqrtf(fx fx + fy fy) > (float)motion_threshold;
+ *     mask = moving dilated by dilate_kernel (odd, 1..15) by the DILATION rule of lvdgs_dynamic_mask's step 5 (the same bit-plane code),
+ *     written as H*W bytes of 0 / 1.  With no stored frame the mask is all zero.  The stored frame is unchanged, unless
+ *   LVDGS_MOTION_ADVANCE is set as well: then the grey plane of image is the stored frame after the call.
+ *   info: LVDGS_MOTION_INFO_WORDS int32 on the device (required by MASK; nobody has to read them): [_HAS_PREV] a frame was stored, [_LEVELS]
+ *   the pyramid's levels, [_MOVING_PIXELS] set pixels before the dilation, [_MASK_PIXELS] after it; the rest 0 (OBSERVE writes none).
+ *   flow: optional output as above (undefined content when no frame was stored).  scratch: lvdgs_motion_mask_scratch_bytes bytes.
+ *   A clear of info, the grey launch, the flow's launches, one launch for the threshold and one for the dilation: enqueued at once,
+ *   their number a function of the sizes and parameters only -- never of whether a frame is stored.  No host wait, no copy, no float
+ *   atomics: equal inputs and equal state give equal bytes.
+ * LVDGS_E_INVALID, beyond the flow's: image or state NULL; mask, info or scratch NULL in a MASK call; a mode other than OBSERVE,
+ * MASK or MASK | ADVANCE; a dilate_kernel that is even or outside 1..15; state -- in a MASK call: or scratch -- too small.  LVDGS_E_RANGE: the flow's.  All
+ * before any launch. */
+#define LVDGS_FARNEBACK_MAX_BLUR_TAPS 127
+enum {
+    LVDGS_MOTION_OBSERVE = 1,
+    LVDGS_MOTION_MASK = 2,
+    LVDGS_MOTION_ADVANCE = 4
+};
+#define LVDGS_MOTION_INFO_WORDS 8
+enum {
+    LVDGS_MOTION_INFO_HAS_PREV = 0,
+    LVDGS_MOTION_INFO_LEVELS = 1,
+    LVDGS_MOTION_INFO_MOVING_PIXELS = 2,
+    LVDGS_MOTION_INFO_MASK_PIXELS = 3
+};
+typedef struct lvdgs_farneback_params {
+    double pyr_scale;             /* (0, 1); the reference's 0.5                    */
+    int32_t levels;               /* 0..8; 3                                        */
+    int32_t winsize;              /* odd, 3..31; 15                                 */
+    int32_t iterations;           /* 1..10; 3                                       */
+    int32_t poly_n;               /* 5 or 7; 5                                      */
+    double poly_sigma;            /* > 0; 1.2                                       */
+} lvdgs_farneback_params;
+typedef struct lvdgs_farneback_args {
+    int32_t width, height;
+    lvdgs_farneback_params params;
+    const uint8_t *prev, *next;   /* H*W grey bytes each                            */
+    float *flow;                  /* out H*W*2                                      */
+    void *scratch; size_t scratch_bytes;
+} lvdgs_farneback_args;
+typedef struct lvdgs_motion_mask_args {
+    int32_t width, height;
+    int32_t mode;                 /* LVDGS_MOTION_*                                 */
+    int32_t dilate_kernel;        /* odd, 1..15; the reference's 7                  */
+    lvdgs_farneback_params params;
+    double motion_threshold;      /* the reference's 3.0; rounded to float32        */
+    const float *image;           /* 3*H*W                                          */
+    uint8_t *mask;                /* out H*W bytes (MASK)                           */
+    float *flow;                  /* out H*W*2, or NULL                             */
+    int32_t *info;                /* out LVDGS_MOTION_INFO_WORDS                    */
+    void *state; size_t state_bytes;
+    void *scratch; size_t scratch_bytes;
+} lvdgs_motion_mask_args;
+size_t lvdgs_farneback_scratch_bytes(int32_t width, int32_t height);
+int lvdgs_farneback_flow(const lvdgs_farneback_args *a, void *stream);
+size_t lvdgs_motion_mask_state_bytes(int32_t width, int32_t height);
+size_t lvdgs_motion_mask_scratch_bytes(int32_t width, int32_t height);
+int lvdgs_motion_mask(const lvdgs_motion_mask_args *a, void *stream);
+
 /* ---- seeding a keyframe's Gaussians (GaussianModel.create_pcd_from_image_and_depth: a full sort for the median, nonzero, a host
  * draw, an upload and about fifteen gathers, with two host waits) ----
  * Pixel i = v*width + u is VALID when depth[i] > 0 && depth[i] <= depth_trunc (NaN fails).  n_valid = the number of valid pixels;

@@ -237,6 +237,36 @@ DYNAMIC_MASK_INFO = ("boxes", "vehicle_detected", "use_sam_result", "filtered", 
                      "static_pixels", "expanded_pixels", "valid_pixels", "depth_pixels")   # the words' names, in LVDGS_DYNAMIC_MASK_INFO_* order
 
 
+class FarnebackParams(C.Structure):
+    _c_name_ = "lvdgs_farneback_params"
+    _fields_ = [("pyr_scale", C.c_double), ("levels", C.c_int32), ("winsize", C.c_int32), ("iterations", C.c_int32), ("poly_n", C.c_int32),
+                ("poly_sigma", C.c_double)]
+
+
+class FarnebackArgs(C.Structure):
+    _c_name_ = "lvdgs_farneback_args"
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32), ("params", FarnebackParams),
+        ("prev", _fp), ("next", _fp), ("flow", _fp), ("scratch", _fp), ("scratch_bytes", C.c_size_t),
+    ]
+
+
+class MotionMaskArgs(C.Structure):
+    _c_name_ = "lvdgs_motion_mask_args"
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32), ("mode", C.c_int32), ("dilate_kernel", C.c_int32), ("params", FarnebackParams),
+        ("motion_threshold", C.c_double), ("image", _fp), ("mask", _fp), ("flow", _fp), ("info", _fp),
+        ("state", _fp), ("state_bytes", C.c_size_t), ("scratch", _fp), ("scratch_bytes", C.c_size_t),
+    ]
+
+
+FARNEBACK_MAX_BLUR_TAPS = 127
+MOTION_OBSERVE, MOTION_MASK, MOTION_ADVANCE = 1, 2, 4
+MOTION_INFO_WORDS = 8
+MOTION_INFO_HAS_PREV, MOTION_INFO_LEVELS, MOTION_INFO_MOVING_PIXELS, MOTION_INFO_MASK_PIXELS = range(4)
+MOTION_INFO = ("has_prev", "levels", "moving_pixels", "mask_pixels")   # the words' names, in LVDGS_MOTION_INFO_* order
+
+
 class SeedArgs(C.Structure):
     _c_name_ = "lvdgs_seed_args"
     _fields_ = [
@@ -525,6 +555,11 @@ PROTOTYPES = {
     "lvdgs_dynamic_mask_state_bytes": (_size, [_i32, _i32, _i32]),
     "lvdgs_dynamic_mask_scratch_bytes": (_size, [_i32, _i32]),
     "lvdgs_dynamic_mask": (_status, [_P(DynamicMaskArgs), _stream]),
+    "lvdgs_farneback_scratch_bytes": (_size, [_i32, _i32]),
+    "lvdgs_farneback_flow": (_status, [_P(FarnebackArgs), _stream]),
+    "lvdgs_motion_mask_state_bytes": (_size, [_i32, _i32]),
+    "lvdgs_motion_mask_scratch_bytes": (_size, [_i32, _i32]),
+    "lvdgs_motion_mask": (_status, [_P(MotionMaskArgs), _stream]),
     "lvdgs_seed_scratch_bytes": (_size, [_i32, _i32]),
     "lvdgs_seed_points": (_status, [_P(SeedArgs), _stream]),
     "lvdgs_map_edit_scratch_bytes": (_size, [_i32]),

@@ -19,7 +19,7 @@
 //   dm_vehicle_kernel  a wave per word: the vehicle dilation when vehicle_detected; dynamic_mask / static_mask bytes and counts; one
 //                      thread moves the history's header on (every reader of it ran in the launch before)
 //   dm_expand_kernel   (expand_kernel != 0) a wave per word: the keyframe's dilation; expanded_* / valid_rgb bytes, the masked depth, counts
-#include "common.hpp"
+#include "bitplane.hpp"
 
 namespace lvdgs {
 namespace {
@@ -27,7 +27,7 @@ namespace {
 constexpr int DM_THREADS = 256;
 constexpr int DM_WAVES = DM_THREADS / WAVE;
 constexpr int DM_MAX_BLOCKS = 1024;      // of the wave-per-word kernels: a wave walks the words with the grid's stride, its counts leave once
-constexpr int DM_MAX_KERNEL = 15;        // dilation windows: odd, up to this (one lane per row of the window, 16 lanes to OR over)
+constexpr int DM_MAX_KERNEL = BITPLANE_MAX_KERNEL;   // dilation windows: odd, up to this (bitplane.hpp)
 constexpr int DM_MAX_HISTORY = 8;        // a 4-bit count per pixel
 constexpr size_t DM_HEADER_BYTES = 256;
 
@@ -51,13 +51,7 @@ struct DmParams {
     uint64_t *plane0, *plane1;           // scratch: boxes, then final (in place) | the union, then dynamic
 };
 
-__device__ __forceinline__ uint64_t low_bits(int n) { return n >= 64 ? ~0ull : ((1ull << n) - 1ull); }   // n in 0..64
-__device__ __forceinline__ uint64_t valid_bits(const DmParams &P, int wx) { return low_bits(min(64, P.W - wx * 64)); }
-
-__device__ __forceinline__ uint64_t wave_or(uint64_t v, int lanes) {   // OR over the first `lanes` (a power of two) lanes, in all of them
-    for (int off = lanes >> 1; off > 0; off >>= 1) v |= (uint64_t)__shfl_xor((unsigned long long)v, off);
-    return v;
-}
+__device__ __forceinline__ uint64_t valid_bits(const DmParams &P, int wx) { return row_valid_bits(P.W, wx); }
 
 // A box as the reference's statements leave it: x1, y1 inclusive, x2, y2 exclusive; false when it is dropped.
 __device__ __forceinline__ bool box_rect(const DmParams &P, int b, int &x1, int &y1, int &x2, int &y2, bool &veh) {
@@ -88,21 +82,7 @@ __device__ __forceinline__ bool box_rect(const DmParams &P, int b, int &x1, int 
     return true;
 }
 
-// Block-wide sums into info: every wave's lane 0 adds what the wave gathered over its words into LDS, then one atomic per counter and
-// block (at most DM_MAX_BLOCKS of them meet on a word of info).  Integer sums: the order of arrival does not show.  Called by every
-// thread of the block.
-template <int N>
-__device__ __forceinline__ void add_counts(int32_t *info, const int (&slot)[N], const uint32_t (&v)[N], bool lane0) {
-    __shared__ uint32_t acc[N];
-    if ((int)threadIdx.x < N) acc[threadIdx.x] = 0;
-    __syncthreads();
-    if (lane0)
-        for (int j = 0; j < N; j++)
-            if (v[j]) atomicAdd(&acc[j], v[j]);
-    __syncthreads();
-    if ((int)threadIdx.x < N && acc[threadIdx.x]) atomicAdd(&info[slot[threadIdx.x]], (int32_t)acc[threadIdx.x]);
-}
-
+// (the block-wide sums into info: add_counts of bitplane.hpp; at most DM_MAX_BLOCKS blocks meet on a word of info)
 __global__ void __launch_bounds__(DM_THREADS) dm_build_kernel(DmParams P) {
     const int lane = threadIdx.x % WAVE;
     const int64_t n = (int64_t)P.W * P.H;
@@ -206,20 +186,9 @@ __global__ void __launch_bounds__(DM_THREADS) dm_select_kernel(DmParams P) {
     P.plane0[word] = final_word;
 }
 
-// Word (y, wx) of `plane` dilated by a k x k window of ones, the border contributing nothing.  Wave-cooperative: lane j < k takes
-// row y - k / 2 + j -- its word widened by shifts across its two neighbours --, the rows are OR-ed over 16 lanes.  All lanes return the word.
+// Word (y, wx) of `plane` dilated by a k x k window of ones (bitplane.hpp).  All lanes return the word.
 __device__ __forceinline__ uint64_t dilate_word(const DmParams &P, const uint64_t *plane, int y, int wx, int k, int lane) {
-    const int r = k >> 1;
-    uint64_t h = 0;
-    const int yy = y - r + lane;
-    if (lane < k && yy >= 0 && yy < P.H) {
-        const uint64_t *row = plane + (int64_t)yy * P.wpr;
-        const uint64_t cur = row[wx], prev = wx > 0 ? row[wx - 1] : 0ull, next = wx + 1 < P.wpr ? row[wx + 1] : 0ull;
-        h = cur;
-        for (int s = 1; s <= r; s++) h |= (cur << s) | (prev >> (64 - s)) | (cur >> s) | (next << (64 - s));
-    }
-    h = wave_or(h, 16);
-    return (uint64_t)__shfl((unsigned long long)h, 0) & valid_bits(P, wx);
+    return lvdgs::dilate_word(plane, P.W, P.H, P.wpr, y, wx, k, lane);
 }
 
 __global__ void __launch_bounds__(DM_THREADS) dm_vehicle_kernel(DmParams P) {
@@ -281,10 +250,6 @@ __global__ void __launch_bounds__(DM_THREADS) dm_expand_kernel(DmParams P) {
     const int slot[3] = {LVDGS_DYNAMIC_MASK_INFO_EXPANDED_PIXELS, LVDGS_DYNAMIC_MASK_INFO_VALID_PIXELS, LVDGS_DYNAMIC_MASK_INFO_DEPTH_PIXELS};
     add_counts<3>(P.info, slot, v, lane == 0);
 }
-
-int words_per_row(int width) { return (width + 63) / 64; }
-size_t plane_bytes(int width, int height) { return (size_t)height * words_per_row(width) * sizeof(uint64_t); }
-bool odd_kernel(int k) { return k >= 1 && k <= DM_MAX_KERNEL && (k & 1); }
 
 }  // namespace
 }  // namespace lvdgs

@@ -224,7 +224,9 @@ class DynamicMasker:
     normalised "cxcywh"), ``labels`` K host strings -- the vehicle keyword test is done here.
     ``segment(image, boxes) -> (K', H, W)`` bool masks on the device: the SAM seat (None: no SAM).
     ``fallback(image, frame_idx) -> (H, W) bool mask or None``: the reference's ``_fallback_detection`` for a frame without boxes; None
-    (the seat or its result) is its last resort, the empty mask.  Such a frame leaves the history untouched.
+    (the seat or its result) is its last resort, the empty mask.  Such a frame leaves the history untouched.  A seat with an
+    ``observe(image)`` method -- ``optical_flow.MotionFallback``, the reference's dense-flow fallback -- is shown every frame WITH
+    boxes that is not a first frame: where the reference sets its ``prev_frame``.
     ``fused=True``: ``assemble`` (HIP; the frames must be on a GPU).  ``fused=False``: ``assemble_torch`` on the image's device."""
 
     def __init__(self, detect, segment=None, fallback=None, history_length=5, fused=True, box_format="xyxy", vehicle_kernels=(7, 5)):
@@ -244,6 +246,8 @@ class DynamicMasker:
         self.mask_history = []
         if self._history is not None:
             self._history.reset()
+        if hasattr(self.fallback, "reset"):      # a seat with state of its own (MotionFallback's stored frame)
+            self.fallback.reset()
 
     def _device_history(self, W, H, device):
         h = self._history
@@ -265,6 +269,8 @@ class DynamicMasker:
             vehicle = [is_vehicle(s) for s in labels]
             sam = None if self.segment is None else self.segment(image, boxes)
             first_flag = first
+            if not first and hasattr(self.fallback, "observe"):      # where the reference sets prev_frame (_refine_with_motion, :1109, :1139)
+                self.fallback.observe(image)
         kw = dict(first_frame=first_flag, box_format=self.box_format, vehicle_kernels=self.vehicle_kernels, expand_kernel=expand_kernel,
                   image=image, rgb_boundary_threshold=rgb_boundary_threshold, depth=depth)
         if self.fused:
