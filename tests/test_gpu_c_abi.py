@@ -141,6 +141,7 @@ def test_forward_batch_equals_forward_view_by_view_state_and_images():
     """lvdgs_forward_batch (every stage of several views of one map in one launch) against lvdgs_forward per view: pair counts, the
     whole geometry / binning / image state and every output image, bit for bit -- with and without LVDGS_FLAG_NO_BLEND, with a view
     whose pair capacity is too small (LVDGS_E_CAPACITY for that view alone, the others complete), and the argument checks."""
+    import c_abi_views
     from lvdgs import _lib, synthetic
     L = _lib.lib()
     dev = torch.device("cuda")
@@ -153,24 +154,8 @@ def test_forward_batch_equals_forward_view_by_view_state_and_images():
     keep = []
 
     def view(k, cap):
-        cam = synthetic.make_camera(W, H, pose_seed=20 + k)
-        mats = {n: getattr(cam, n).to(dev).contiguous() for n in ("world_view_transform", "full_proj_transform", "projection_matrix", "camera_center")}
-        a = _lib.Args()
-        a.image_height, a.image_width, a.tanfovx, a.tanfovy = H, W, cam.tanfovx, cam.tanfovy
-        a.scale_modifier, a.sh_degree = 1.0, 0
-        a.bg, a.viewmatrix, a.projmatrix = _p(bgd), _p(mats["world_view_transform"]), _p(mats["full_proj_transform"])
-        a.projmatrix_raw, a.campos = _p(mats["projection_matrix"]), _p(mats["camera_center"])
-        a.num_gaussians, a.sh_coeffs = N, 0
-        a.means3D, a.opacities, a.scales, a.rotations, a.colors_precomp = _p(t["means3D"]), _p(t["opacities"]), _p(t["scales"]), _p(t["rotations"]), _p(t["colors"])
-        st = dict(radii=torch.zeros(N, dtype=torch.int32, device=dev), n_touched=torch.zeros(N, dtype=torch.int32, device=dev),
-                  color=torch.zeros(3, H, W, device=dev), depth=torch.zeros(1, H, W, device=dev), opacity=torch.zeros(1, H, W, device=dev),
-                  geom=buf(L.lvdgs_geom_bytes(N)), image=buf(L.lvdgs_image_bytes(W, H)), binning=buf(L.lvdgs_binning_bytes(cap)),
-                  scratch=buf(max(L.lvdgs_prepare_scratch_bytes(N), L.lvdgs_render_scratch_bytes(N, cap, W, H))))
-        a.radii, a.n_touched, a.out_color, a.out_depth, a.out_opacity = _p(st["radii"]), _p(st["n_touched"]), _p(st["color"]), _p(st["depth"]), _p(st["opacity"])
-        a.geom_state, a.geom_bytes, a.image_state, a.image_bytes = _p(st["geom"]), st["geom"].numel(), _p(st["image"]), st["image"].numel()
-        a.binning_state, a.binning_bytes, a.scratch, a.scratch_bytes = _p(st["binning"]), st["binning"].numel(), _p(st["scratch"]), st["scratch"].numel()
-        a.pair_capacity = cap
-        keep.append((mats, st))
+        a, st = c_abi_views.forward_view(L, t, synthetic.make_camera(W, H, pose_seed=20 + k), W, H, bgd, cap)
+        keep.append(st)
         return a, st
 
     cap = 400_000

@@ -40,7 +40,9 @@ def test_two_million_gaussians_1920x1280():
 
 @pytest.mark.parametrize("N,longest", [(60_000, 10_000), (140_000, 16_384)])
 def test_very_long_tile_lists(N, longest):
-    """Segments of more than 2048 entries sort on LDS with 1024 threads, beyond 16384 in place on global memory."""
+    """Segments of more than 2048 entries sort on LDS with 1024 threads, beyond 16384 in place on global memory.  (Which launch takes
+    them depends on what the thread's earlier frames queued; tests/test_gpu_tile_sort.py has the exact boundaries -- 1024/1025,
+    2048/2049, 16384/16385 -- in every such state.)"""
     import hip_runner
     from lvdgs import synthetic
     W, H = 64, 64
