@@ -1,7 +1,9 @@
 // TSDF fusion of depth maps into a dense volume and a mesh of it by surface nets (rules, arithmetic and the host block:
 // include/lvdgs.h, "TSDF fusion").
 //
-// The per-voxel rule, the corner test of a brick and the vertex of a cell are tsdf_rule.hpp's, shared with tsdf_blocks.hip.
+// The rules are tsdf_rule.hpp's, shared with tsdf_blocks.hip: the corner test of a brick, the walk of a thread's samples through the
+// views, when a cell is active, which edges give faces, a cell's vertex, a quad's winding, the counts of the host block, and the host's
+// checks of planes, constants and views.  This file is the dense storage around them: bricks, rows, strides and spans.
 //
 // lvdgs_tsdf_integrate: one launch.  A workgroup of 256 threads owns a brick of 64 x 4 x 4 voxels; a thread owns four voxels along x
 // (16 lanes span a row of 64: 256 contiguous bytes of a plane), keeps them in registers across the up to 16 views and writes a row
@@ -14,8 +16,6 @@
 //
 // Built like every file here with -ffp-contract=off and without fast-math: the float32 expressions of the header are evaluated as
 // written, the divisions IEEE-rounded, and a NumPy float32 restatement gives the same bits.
-#include <cmath>
-
 #include "common.hpp"
 #include "device_utils.hpp"
 #include "spans.hpp"
@@ -73,62 +73,15 @@ __global__ void __launch_bounds__(TSDF_THREADS) tsdf_integrate_kernel(IntegrateP
     load4(p.weight, w);
     if constexpr (COLOR) { load4(p.r, cr); load4(p.g, cg); load4(p.b, cb); }
 
-    const float py = p.lat.oy + p.lat.vs * (float)j, pz = p.lat.oz + p.lat.vs * (float)k;
-    float px[4];
+    float px[4], py[4], pz[4];
+    bool valid[4];
 #pragma unroll
-    for (int q = 0; q < 4; q++) px[q] = p.lat.ox + p.lat.vs * (float)(i0 + q);
-    bool changed = false, recoloured = false;
-    for (int v = 0; v < p.count; v++) {
-        if (!((live >> v) & 1u)) continue;   // (wave-uniform)
-        const TsdfView &V = p.v[v];
-        float R[9], T[3];
-#pragma unroll
-        for (int q = 0; q < 9; q++) R[q] = V.R[q];
-#pragma unroll
-        for (int q = 0; q < 3; q++) T[q] = V.T[q];
-        const int64_t P = (int64_t)V.W * V.H;
-        const bool coloured = COLOR && V.image != nullptr;
-        // in stages over the thread's four voxels, so that their gathers are in flight together: the pixel (pixel 0 stands in where
-        // there is none: every gather below has a valid address and needs no branch), depth and mask, the colours, the update
-        float z[4];
-        int pix[4];
-        bool ok[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const TsdfPixel at = tsdf_pixel(V, R, T, px[q], py, pz);
-            z[q] = at.z;
-            ok[q] = q < nv && at.ok;
-            pix[q] = ok[q] ? at.pix : 0;
-        }
-        if (!__any(ok[0] || ok[1] || ok[2] || ok[3])) continue;   // (a wave's rows outside this view)
-        float d[4];
-        uint8_t m[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) d[q] = V.depth[pix[q]];
-#pragma unroll
-        for (int q = 0; q < 4; q++) m[q] = V.mask ? V.mask[pix[q]] : (uint8_t)1;
-        float sdf[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const bool seen = tsdf_seen(V, p.lat.trunc, d[q], m[q], z[q], &sdf[q]);
-            ok[q] = ok[q] && seen;
-        }
-        float c0[4], c1[4], c2[4];
-        if (coloured) {
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const int at = ok[q] ? pix[q] : 0;
-                c0[q] = V.image[at]; c1[q] = V.image[P + at]; c2[q] = V.image[2 * P + at];
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            if (!ok[q]) continue;
-            tsdf_blend(p.lat, sdf[q], coloured, c0[q], c1[q], c2[q], f[q], w[q], cr[q], cg[q], cb[q]);
-            recoloured = recoloured || coloured;
-            changed = true;
-        }
+    for (int q = 0; q < 4; q++) {
+        px[q] = p.lat.ox + p.lat.vs * (float)(i0 + q); py[q] = p.lat.oy + p.lat.vs * (float)j; pz[q] = p.lat.oz + p.lat.vs * (float)k;
+        valid[q] = q < nv;
     }
+    bool changed = false, recoloured = false;
+    tsdf_fuse_views<4, COLOR>(p.lat, p.v, p.count, live, px, py, pz, valid, f, w, cr, cg, cb, changed, recoloured);
     if (changed) { store4(p.tsdf, f); store4(p.weight, w); }
     if constexpr (COLOR) {
         if (recoloured) { store4(p.r, cr); store4(p.g, cg); store4(p.b, cb); }
@@ -136,9 +89,6 @@ __global__ void __launch_bounds__(TSDF_THREADS) tsdf_integrate_kernel(IntegrateP
 }
 
 // ---------------------------------------------------------------- the mesh ----
-
-enum : uint8_t { CELL_ACTIVE = 1, SAMPLE_INSIDE = 2, SAMPLE_OBSERVED = 4 };   // the classify pass's byte
-enum : uint8_t { EDGE_LOW_INSIDE = 8 };                                        // the edge pass's byte: bits 0-2 the axes whose edge gives faces
 
 struct MeshParams {
     int nx, ny, nz;
@@ -177,15 +127,10 @@ __global__ void __launch_bounds__(TSDF_THREADS) tsdf_classify_kernel(MeshParams 
         const bool obs = M.weight[s] > 0.f, in = M.tsdf[s] < 0.f;
         bool active = false;
         if (c.i < M.nx - 1 && c.j < M.ny - 1 && c.k < M.nz - 1) {
-            bool all = true;
-            int n_in = 0;
-#pragma unroll
-            for (int q = 0; q < 8; q++) {
+            active = tsdf_cell_active([&](int q) {
                 const uint32_t o = s + ((q & 1) ? sx : 0u) + ((q & 2) ? sy : 0u) + ((q & 4) ? sz : 0u);
-                all = all && M.weight[o] > 0.f;
-                n_in += M.tsdf[o] < 0.f ? 1 : 0;
-            }
-            active = all && n_in > 0 && n_in < 8;
+                return (uint8_t)((M.weight[o] > 0.f ? SAMPLE_OBSERVED : 0) | (M.tsdf[o] < 0.f ? SAMPLE_INSIDE : 0));
+            });
         }
         M.flags[s] = (uint8_t)((active ? CELL_ACTIVE : 0) | (in ? SAMPLE_INSIDE : 0) | (obs ? SAMPLE_OBSERVED : 0));
         mine += active ? 1u : 0u;
@@ -206,12 +151,13 @@ __global__ void __launch_bounds__(TSDF_THREADS) tsdf_edges_kernel(MeshParams M) 
         const bool in0 = fl & SAMPLE_INSIDE;
         uint32_t e = 0;
         if (fl & CELL_ACTIVE) {   // c2 = the sample's own cell, for every axis; it being a cell puts i, j, k below n - 1
-            auto act = [&](uint32_t o) { return (M.flags[o] & CELL_ACTIVE) != 0; };
-            auto differs = [&](uint32_t o) { return ((M.flags[o] & SAMPLE_INSIDE) != 0) != in0; };
-            const bool bi = c.i >= 1, bj = c.j >= 1, bk = c.k >= 1;
-            if (bj && bk && differs(s + 1u) && act(s - sy - sz) && act(s - sz) && act(s - sy)) e |= 1u;    // x: (b, c) = (y, z)
-            if (bk && bi && differs(s + sy) && act(s - sz - 1u) && act(s - 1u) && act(s - sz)) e |= 2u;    // y: (b, c) = (z, x)
-            if (bi && bj && differs(s + sz) && act(s - 1u - sy) && act(s - sy) && act(s - 1u)) e |= 4u;    // z: (b, c) = (x, y)
+            // an offset of -1 along an axis needs the sample's index there to be at least 1
+            auto at = [&](int dx, int dy, int dz) { return s + (uint32_t)dx + (uint32_t)dy * sy + (uint32_t)dz * sz; };
+            auto differs = [&](int dx, int dy, int dz) { return ((M.flags[at(dx, dy, dz)] & SAMPLE_INSIDE) != 0) != in0; };
+            auto act = [&](int dx, int dy, int dz) {
+                return c.i + dx >= 0 && c.j + dy >= 0 && c.k + dz >= 0 && (M.flags[at(dx, dy, dz)] & CELL_ACTIVE) != 0;
+            };
+            e = tsdf_edge_axes(differs, act);
         }
         M.edges[s] = (uint8_t)(e | (in0 ? EDGE_LOW_INSIDE : 0));
         mine += 2u * (uint32_t)__popc(e);
@@ -283,15 +229,10 @@ __global__ void __launch_bounds__(TSDF_THREADS) tsdf_faces_kernel(MeshParams M) 
 #pragma unroll
         for (int axis = 0; axis < 3; axis++) {
             if (!((e >> axis) & 1u)) continue;
-            const uint32_t sb = axis == 0 ? sy : axis == 1 ? sz : 1u, sc = axis == 0 ? sz : axis == 1 ? 1u : sy;   // strides of b and c
-            const int32_t v0 = M.cellvert[s - sb - sc], v1 = M.cellvert[s - sc], v2 = own, v3 = M.cellvert[s - sb];
-            const int32_t tri[2][3] = {{v0, low_in ? v1 : v2, low_in ? v2 : v1}, {v0, low_in ? v2 : v3, low_in ? v3 : v2}};
-#pragma unroll
-            for (int t = 0; t < 2; t++, row++) {
-                if (row >= cap) continue;
-                int32_t *dst = M.faces + (size_t)row * 3;
-                dst[0] = tri[t][0]; dst[1] = tri[t][1]; dst[2] = tri[t][2];
-            }
+            const TsdfStep b = tsdf_axis_step(axis + 1), c = tsdf_axis_step(axis + 2);
+            const uint32_t sb = (uint32_t)b.x + (uint32_t)b.y * sy + (uint32_t)b.z * sz, sc = (uint32_t)c.x + (uint32_t)c.y * sy + (uint32_t)c.z * sz;
+            tsdf_write_quad(M.faces, row, cap, low_in, M.cellvert[s - sb - sc], M.cellvert[s - sc], own, M.cellvert[s - sb]);
+            row += 2;
         }
     }
 }
@@ -299,11 +240,7 @@ __global__ void __launch_bounds__(TSDF_THREADS) tsdf_faces_kernel(MeshParams M) 
 __global__ void tsdf_publish_kernel(MeshParams M) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     volatile int32_t *w = M.host;
-    const unsigned long long nv = M.totals[0], nf = M.totals[1];
-    const bool too_many = nf > (unsigned long long)INT32_MAX;
-    w[LVDGS_TSDF_N_VERTICES] = (int32_t)nv;
-    w[LVDGS_TSDF_N_FACES] = too_many ? INT32_MAX : (int32_t)nf;
-    w[LVDGS_TSDF_OVERFLOW] = (nv > (unsigned long long)M.vcap ? 1 : 0) | (nf > (unsigned long long)M.fcap ? 2 : 0) | (too_many ? 4 : 0);
+    tsdf_publish_counts(w, M.totals, M.vcap, M.fcap);
     for (int j = LVDGS_TSDF_OVERFLOW + 1; j < (int)(LVDGS_TSDF_HOST_BYTES / sizeof(int32_t)); j++) w[j] = 0;
     seal_host_block(w, LVDGS_TSDF_SEQ, (int32_t)M.seq);
 }
@@ -324,8 +261,6 @@ MeshLayout mesh_layout(size_t n) {
     return L;
 }
 
-bool positive_finite(float v) { return v > 0.f && std::isfinite(v); }
-
 // dims >= least each and at most 2^31 - 1 samples
 int check_dims(const char *name, const lvdgs_tsdf_volume &v, int least) {
     if (v.nx < least || v.ny < least || v.nz < least) {
@@ -334,13 +269,6 @@ int check_dims(const char *name, const lvdgs_tsdf_volume &v, int least) {
     if ((int64_t)v.nx * v.ny > INT32_MAX || (int64_t)v.nx * v.ny * v.nz > INT32_MAX) {
         set_error("%s: volume %dx%dx%d has more than 2^31 - 1 cells", name, v.nx, v.ny, v.nz); return LVDGS_E_RANGE;
     }
-    return LVDGS_OK;
-}
-
-int check_planes(const char *name, const lvdgs_tsdf_volume &v) {
-    if (!v.tsdf || !v.weight) { set_error("%s: tsdf / weight plane is NULL", name); return LVDGS_E_INVALID; }
-    const int colours = (v.r ? 1 : 0) + (v.g ? 1 : 0) + (v.b ? 1 : 0);
-    if (colours != 0 && colours != 3) { set_error("%s: colour planes r, g, b must be all set or all NULL", name); return LVDGS_E_INVALID; }
     return LVDGS_OK;
 }
 
@@ -354,27 +282,14 @@ extern "C" {
 int lvdgs_tsdf_integrate(const lvdgs_tsdf_volume *vol, const lvdgs_tsdf_view *const *views, int32_t count, void *stream) {
     const char *name = "tsdf integrate";
     if (!vol) { set_error("%s: volume is NULL", name); return LVDGS_E_INVALID; }
-    if (count < 0 || count > LVDGS_TSDF_MAX_VIEWS) { set_error("%s: count %d is outside 0 .. %d", name, count, LVDGS_TSDF_MAX_VIEWS); return LVDGS_E_INVALID; }
-    if (int e = check_planes(name, *vol)) return e;
+    if (int e = tsdf_check_count(name, count)) return e;
+    if (int e = tsdf_check_planes(name, *vol)) return e;
     if (int e = check_dims(name, *vol, 1)) return e;
-    if (!positive_finite(vol->voxel_size) || !positive_finite(vol->trunc) || !positive_finite(vol->max_weight)) {
-        set_error("%s: voxel_size %g, trunc %g and max_weight %g must be finite and positive", name, vol->voxel_size, vol->trunc, vol->max_weight);
-        return LVDGS_E_RANGE;
-    }
+    if (int e = tsdf_check_constants(name, *vol)) return e;
     const dim3 grid(cdiv(vol->nx, BRICK_X), cdiv(vol->ny, BRICK_Y), cdiv(vol->nz, BRICK_Z));
     if (grid.y > 65535u || grid.z > 65535u) { set_error("%s: ny or nz beyond 262140 (65535 bricks)", name); return LVDGS_E_RANGE; }
-    if (count > 0 && !views) { set_error("%s: view list is NULL", name); return LVDGS_E_INVALID; }
     IntegrateParams p{};
-    for (int v = 0; v < count; v++) {
-        const lvdgs_tsdf_view *a = views[v];
-        if (!a) { set_error("%s: view %d is NULL", name, v); return LVDGS_E_INVALID; }
-        if (a->width < 1 || a->height < 1 || (int64_t)a->width * a->height > INT32_MAX) {
-            set_error("%s: view %d: image size %dx%d", name, v, a->width, a->height); return LVDGS_E_RANGE;
-        }
-        if (!a->R || !a->T || !a->depth) { set_error("%s: view %d: R / T / depth is NULL", name, v); return LVDGS_E_INVALID; }
-        if (a->image && !vol->r) { set_error("%s: view %d has an image, the volume no colour planes", name, v); return LVDGS_E_INVALID; }
-        p.v[v] = TsdfView{a->width, a->height, a->fx, a->fy, a->cx, a->cy, a->depth_min, a->depth_trunc, a->R, a->T, a->depth, a->image, a->mask};
-    }
+    if (int e = tsdf_pack_views(name, views, count, vol->r != nullptr, p.v)) return e;
     if (count == 0) return LVDGS_OK;
     p.nx = vol->nx; p.ny = vol->ny; p.nz = vol->nz; p.count = count;
     p.lat = TsdfLattice{vol->origin[0], vol->origin[1], vol->origin[2], vol->voxel_size, vol->trunc, vol->max_weight};
@@ -402,7 +317,7 @@ int lvdgs_tsdf_mesh(const lvdgs_tsdf_mesh_args *a, void *stream) {
     const char *name = "tsdf mesh";
     if (!a) { set_error("%s: args is NULL", name); return LVDGS_E_INVALID; }
     const lvdgs_tsdf_volume &vol = a->vol;
-    if (int e = check_planes(name, vol)) return e;
+    if (int e = tsdf_check_planes(name, vol)) return e;
     if (int e = check_dims(name, vol, 2)) return e;
     if (!positive_finite(vol.voxel_size)) { set_error("%s: voxel_size %g must be finite and positive", name, vol.voxel_size); return LVDGS_E_RANGE; }
     if (a->vertex_capacity < 0 || a->face_capacity < 0) {

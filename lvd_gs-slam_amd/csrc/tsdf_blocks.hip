@@ -1,6 +1,7 @@
 // The block-sparse TSDF volume: blocks of 8 x 8 x 8 samples in a pool, found through an open-addressing table of 64-bit keys
-// (storage, rules and the host block: include/lvdgs.h, "Block-sparse TSDF volume").  The per-voxel rule, the
-// corner test and the vertex of a cell are tsdf_rule.hpp's, shared with the dense volume (tsdf.hip).
+// (storage, rules and the host block: include/lvdgs.h, "Block-sparse TSDF volume").  The fusion rule with its walk over
+// the views, the surface-nets decisions and the host's checks of planes, constants and views are tsdf_rule.hpp's, shared with the dense
+// volume (tsdf.hip); this file is the blocks' storage around them: keys, table, pool, the 9^3 tile and the neighbours of a block.
 //
 // lvdgs_tsdf_blocks_integrate: three launches.  Allocation -- a thread per pixel walks its ray's band in half-voxel steps and enters
 // the blocks it meets (one 64-bit atomicCAS per new key decides who enters it; the winner draws the pool index); one thread brings
@@ -9,9 +10,6 @@
 // lvdgs_tsdf_blocks_mesh: eight launches over the blocks in key order (`order`).  Everything a launch reads from the header, from
 // `order`, from the table or from an earlier launch's scratch is brought into range before it indexes: garbage gives a wrong mesh,
 // never an access outside the caller's arrays.  Integer decisions only, no atomics: two calls give the same bytes.
-#include <algorithm>
-#include <cmath>
-
 #include "common.hpp"
 #include "device_utils.hpp"
 #include "spans.hpp"
@@ -187,52 +185,11 @@ __global__ void __launch_bounds__(TB_THREADS) tsdf_blocks_integrate_kernel(Block
             w[q] = p.vol.weight[base + 256 * q];
             if constexpr (COLOR) { cr[q] = p.vol.r[base + 256 * q]; cg[q] = p.vol.g[base + 256 * q]; cb[q] = p.vol.b[base + 256 * q]; }
         }
-        const float px = lat.ox + lat.vs * (float)(gx + i), py = lat.oy + lat.vs * (float)(gy + j);
-        const float pz[2] = {lat.oz + lat.vs * (float)(gz + k), lat.oz + lat.vs * (float)(gz + k + 4)};
+        const float x = lat.ox + lat.vs * (float)(gx + i), y = lat.oy + lat.vs * (float)(gy + j);
+        const float px[2] = {x, x}, py[2] = {y, y}, pz[2] = {lat.oz + lat.vs * (float)(gz + k), lat.oz + lat.vs * (float)(gz + k + 4)};
+        const bool valid[2] = {true, true};
         bool changed = false, recoloured = false;
-        for (int v = 0; v < p.count; v++) {
-            if (!((live >> v) & 1u)) continue;   // (wave-uniform)
-            const TsdfView &V = p.v[v];
-            float R[9], T[3];
-#pragma unroll
-            for (int q = 0; q < 9; q++) R[q] = V.R[q];
-#pragma unroll
-            for (int q = 0; q < 3; q++) T[q] = V.T[q];
-            const int64_t P = (int64_t)V.W * V.H;
-            const bool coloured = COLOR && V.image != nullptr;
-            // in stages over the two samples, as the dense kernel does over its four: the pixels, depth and mask, the colours, the update
-            TsdfPixel at[2];
-#pragma unroll
-            for (int q = 0; q < 2; q++) at[q] = tsdf_pixel(V, R, T, px, py, pz[q]);
-            if (!__any(at[0].ok || at[1].ok)) continue;
-            float d[2], sdf[2];
-            uint8_t m[2];
-            bool ok[2];
-#pragma unroll
-            for (int q = 0; q < 2; q++) d[q] = V.depth[at[q].pix];
-#pragma unroll
-            for (int q = 0; q < 2; q++) m[q] = V.mask ? V.mask[at[q].pix] : (uint8_t)1;
-#pragma unroll
-            for (int q = 0; q < 2; q++) {
-                const bool seen = tsdf_seen(V, lat.trunc, d[q], m[q], at[q].z, &sdf[q]);
-                ok[q] = at[q].ok && seen;
-            }
-            float c0[2] = {0.f, 0.f}, c1[2] = {0.f, 0.f}, c2[2] = {0.f, 0.f};
-            if (coloured) {
-#pragma unroll
-                for (int q = 0; q < 2; q++) {
-                    const int pix = ok[q] ? at[q].pix : 0;
-                    c0[q] = V.image[pix]; c1[q] = V.image[P + pix]; c2[q] = V.image[2 * P + pix];
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 2; q++) {
-                if (!ok[q]) continue;
-                tsdf_blend(lat, sdf[q], coloured, c0[q], c1[q], c2[q], f[q], w[q], cr[q], cg[q], cb[q]);
-                recoloured = recoloured || coloured;
-                changed = true;
-            }
-        }
+        tsdf_fuse_views<2, COLOR>(lat, p.v, p.count, live, px, py, pz, valid, f, w, cr, cg, cb, changed, recoloured);
         if (changed) {
 #pragma unroll
             for (int q = 0; q < 2; q++) { p.vol.tsdf[base + 256 * q] = f[q]; p.vol.weight[base + 256 * q] = w[q]; }
@@ -250,8 +207,6 @@ __global__ void __launch_bounds__(TB_THREADS) tsdf_blocks_integrate_kernel(Block
 // Blocks are addressed by RANK, their place in `order`.  A sample or cell near a block is named by local coordinates in -1 .. 8 per
 // axis; neighbour n = (dx + 1) + 3 * (dy + 1) + 9 * (dz + 1) of the 27 holds the block that owns it.
 
-enum : uint8_t { SAMPLE_INSIDE = 2, SAMPLE_OBSERVED = 4 };   // the staged byte of a sample
-enum : uint8_t { EDGE_LOW_INSIDE = 8 };                       // the edge pass's byte: bits 0-2 the axes whose edge gives faces
 constexpr int TILE_EDGE = 9, TILE_SAMPLES = 9 * 9 * 9;
 
 struct BlocksMeshParams {
@@ -352,15 +307,9 @@ __global__ void __launch_bounds__(TB_THREADS) tsdf_blocks_classify_kernel(Blocks
         for (int half = 0; half < 2; half++) {
             const int l = threadIdx.x + 256 * half, i = l & 7, j = (l >> 3) & 7, k = l >> 6;
             const int gx = bx * 8 + i, gy = by * 8 + j, gz = bz * 8 + k;
-            bool all = gx >= M.cell_lo[0] && gx < M.cell_hi[0] && gy >= M.cell_lo[1] && gy < M.cell_hi[1] && gz >= M.cell_lo[2] && gz < M.cell_hi[2];
-            int n_in = 0;
-#pragma unroll
-            for (int q = 0; q < 8; q++) {
-                const uint8_t fl = tile[(i + (q & 1)) + TILE_EDGE * ((j + ((q >> 1) & 1)) + TILE_EDGE * (k + (q >> 2)))];
-                all = all && (fl & SAMPLE_OBSERVED);
-                n_in += (fl & SAMPLE_INSIDE) ? 1 : 0;
-            }
-            const unsigned long long bits = __ballot(all && n_in > 0 && n_in < 8);   // cells 64 * (wave + 4 * half) .. + 63
+            const bool in_range = gx >= M.cell_lo[0] && gx < M.cell_hi[0] && gy >= M.cell_lo[1] && gy < M.cell_hi[1] && gz >= M.cell_lo[2] && gz < M.cell_hi[2];
+            const bool active = tsdf_cell_active([&](int q) { return tile[(i + (q & 1)) + TILE_EDGE * ((j + ((q >> 1) & 1)) + TILE_EDGE * (k + (q >> 2)))]; });
+            const unsigned long long bits = __ballot(in_range && active);   // cells 64 * (wave + 4 * half) .. + 63
             if (lane == 0) {
                 uint32_t *dst = M.mask + (size_t)r * 16 + 2 * (wave + 4 * half);
                 dst[0] = (uint32_t)bits; dst[1] = (uint32_t)(bits >> 32);
@@ -405,11 +354,9 @@ __global__ void __launch_bounds__(TB_THREADS) tsdf_blocks_edges_kernel(BlocksMes
             const bool in0 = tile[i + TILE_EDGE * (j + TILE_EDGE * k)] & SAMPLE_INSIDE;
             uint32_t e = 0;
             if ((M.mask[(size_t)r * 16 + (l >> 5)] >> (l & 31)) & 1u) {   // c2 = the sample's own cell, for every axis
-                auto differs = [&](int x, int y, int z) { return ((tile[x + TILE_EDGE * (y + TILE_EDGE * z)] & SAMPLE_INSIDE) != 0) != in0; };
-                auto act = [&](int x, int y, int z) { return cell_active(M, r, used, x, y, z); };
-                if (differs(i + 1, j, k) && act(i, j - 1, k - 1) && act(i, j, k - 1) && act(i, j - 1, k)) e |= 1u;    // x: (b, c) = (y, z)
-                if (differs(i, j + 1, k) && act(i - 1, j, k - 1) && act(i - 1, j, k) && act(i, j, k - 1)) e |= 2u;    // y: (b, c) = (z, x)
-                if (differs(i, j, k + 1) && act(i - 1, j - 1, k) && act(i, j - 1, k) && act(i - 1, j, k)) e |= 4u;    // z: (b, c) = (x, y)
+                auto differs = [&](int dx, int dy, int dz) { return ((tile[(i + dx) + TILE_EDGE * ((j + dy) + TILE_EDGE * (k + dz))] & SAMPLE_INSIDE) != 0) != in0; };
+                auto act = [&](int dx, int dy, int dz) { return cell_active(M, r, used, i + dx, j + dy, k + dz); };
+                e = tsdf_edge_axes(differs, act);
             }
             M.edges[(size_t)r * BLOCK_SAMPLES + l] = (uint8_t)(e | (in0 ? EDGE_LOW_INSIDE : 0));
             mine += 2u * (uint32_t)__popc(e);
@@ -484,18 +431,10 @@ __global__ void __launch_bounds__(TB_THREADS) tsdf_blocks_faces_kernel(BlocksMes
 #pragma unroll
             for (int axis = 0; axis < 3; axis++) {
                 if (!((e >> axis) & 1u)) continue;
-                // the unit steps of b and c, (a, b, c) cyclic
-                const int bxs = axis == 2, bys = axis == 0, bzs = axis == 1, cxs = axis == 1, cys = axis == 2, czs = axis == 0;
-                const int32_t v0 = cell_vertex(M, r, used, i - bxs - cxs, j - bys - cys, k - bzs - czs);
-                const int32_t v1 = cell_vertex(M, r, used, i - cxs, j - cys, k - czs), v2 = own;
-                const int32_t v3 = cell_vertex(M, r, used, i - bxs, j - bys, k - bzs);
-                const int32_t tri[2][3] = {{v0, low_in ? v1 : v2, low_in ? v2 : v1}, {v0, low_in ? v2 : v3, low_in ? v3 : v2}};
-#pragma unroll
-                for (int t = 0; t < 2; t++, row++) {
-                    if (row >= cap) continue;
-                    int32_t *dst = M.faces + (size_t)row * 3;
-                    dst[0] = tri[t][0]; dst[1] = tri[t][1]; dst[2] = tri[t][2];
-                }
+                const TsdfStep b = tsdf_axis_step(axis + 1), c = tsdf_axis_step(axis + 2);
+                tsdf_write_quad(M.faces, row, cap, low_in, cell_vertex(M, r, used, i - b.x - c.x, j - b.y - c.y, k - b.z - c.z),
+                                cell_vertex(M, r, used, i - c.x, j - c.y, k - c.z), own, cell_vertex(M, r, used, i - b.x, j - b.y, k - b.z));
+                row += 2;
             }
         }
     }
@@ -504,11 +443,7 @@ __global__ void __launch_bounds__(TB_THREADS) tsdf_blocks_faces_kernel(BlocksMes
 __global__ void tsdf_blocks_publish_kernel(BlocksMeshParams M) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     volatile int32_t *w = M.host;
-    const unsigned long long nv = M.totals[0], nf = M.totals[1];
-    const bool too_many = nf > (unsigned long long)INT32_MAX;
-    w[LVDGS_TSDF_BLOCKS_N_VERTICES] = (int32_t)nv;
-    w[LVDGS_TSDF_BLOCKS_N_FACES] = too_many ? INT32_MAX : (int32_t)nf;
-    w[LVDGS_TSDF_BLOCKS_OVERFLOW] = (nv > (unsigned long long)M.vcap ? 1 : 0) | (nf > (unsigned long long)M.fcap ? 2 : 0) | (too_many ? 4 : 0);
+    tsdf_publish_counts(w, M.totals, M.vcap, M.fcap);
     w[LVDGS_TSDF_BLOCKS_USED] = used_blocks(M.vol);
     w[LVDGS_TSDF_BLOCKS_DROPPED] = M.vol.header[LVDGS_TSDF_BLOCKS_HEADER_DROPPED];
     w[LVDGS_TSDF_BLOCKS_OUT_OF_RANGE] = M.vol.header[LVDGS_TSDF_BLOCKS_HEADER_OUT_OF_RANGE];
@@ -550,14 +485,10 @@ BlocksMeshLayout blocks_mesh_layout(size_t pool) {
     return L;
 }
 
-bool positive_finite(float v) { return v > 0.f && std::isfinite(v); }
-
 // everything the three calls refuse about the volume itself
 int check_volume(const char *name, const lvdgs_tsdf_blocks *vol, BlockVolume *out) {
     if (!vol) { set_error("%s: volume is NULL", name); return LVDGS_E_INVALID; }
-    if (!vol->tsdf || !vol->weight) { set_error("%s: tsdf / weight plane is NULL", name); return LVDGS_E_INVALID; }
-    const int colours = (vol->r ? 1 : 0) + (vol->g ? 1 : 0) + (vol->b ? 1 : 0);
-    if (colours != 0 && colours != 3) { set_error("%s: colour planes r, g, b must be all set or all NULL", name); return LVDGS_E_INVALID; }
+    if (int e = tsdf_check_planes(name, *vol)) return e;
     if (!vol->block_key || !vol->table_keys || !vol->table_values || !vol->header) {
         set_error("%s: block_key / table_keys / table_values / header is NULL", name); return LVDGS_E_INVALID;
     }
@@ -569,10 +500,7 @@ int check_volume(const char *name, const lvdgs_tsdf_blocks *vol, BlockVolume *ou
         set_error("%s: table_slots %d must be a power of two, at least 2 * pool_blocks (%d) and at most 2^30", name, vol->table_slots, vol->pool_blocks);
         return LVDGS_E_RANGE;
     }
-    if (!positive_finite(vol->voxel_size) || !positive_finite(vol->trunc) || !positive_finite(vol->max_weight)) {
-        set_error("%s: voxel_size %g, trunc %g and max_weight %g must be finite and positive", name, vol->voxel_size, vol->trunc, vol->max_weight);
-        return LVDGS_E_RANGE;
-    }
+    if (int e = tsdf_check_constants(name, *vol)) return e;
     out->pool = vol->pool_blocks; out->slots = vol->table_slots;
     out->lat = TsdfLattice{vol->origin[0], vol->origin[1], vol->origin[2], vol->voxel_size, vol->trunc, vol->max_weight};
     out->tsdf = vol->tsdf; out->weight = vol->weight; out->r = vol->r; out->g = vol->g; out->b = vol->b;
@@ -594,26 +522,15 @@ extern "C" {
 int lvdgs_tsdf_blocks_integrate(const lvdgs_tsdf_blocks *vol, const lvdgs_tsdf_view *const *views, int32_t count, void *stream) {
     const char *name = "tsdf blocks integrate";
     BlocksIntegrateParams p{};
-    if (count < 0 || count > LVDGS_TSDF_MAX_VIEWS) { set_error("%s: count %d is outside 0 .. %d", name, count, LVDGS_TSDF_MAX_VIEWS); return LVDGS_E_INVALID; }
+    if (int e = tsdf_check_count(name, count)) return e;
     if (int e = check_volume(name, vol, &p.vol)) return e;
     const float steps = ceilf((vol->trunc + vol->voxel_size) / (0.5f * vol->voxel_size));
     if (!(steps <= (float)((LVDGS_TSDF_BLOCKS_MAX_STEPS - 1) / 2))) {
         set_error("%s: trunc %g over voxel_size %g needs more than %d steps along a ray", name, vol->trunc, vol->voxel_size, LVDGS_TSDF_BLOCKS_MAX_STEPS);
         return LVDGS_E_RANGE;
     }
-    if (count > 0 && !views) { set_error("%s: view list is NULL", name); return LVDGS_E_INVALID; }
-    int64_t most_pixels = 0;
-    for (int v = 0; v < count; v++) {
-        const lvdgs_tsdf_view *a = views[v];
-        if (!a) { set_error("%s: view %d is NULL", name, v); return LVDGS_E_INVALID; }
-        if (a->width < 1 || a->height < 1 || (int64_t)a->width * a->height > INT32_MAX) {
-            set_error("%s: view %d: image size %dx%d", name, v, a->width, a->height); return LVDGS_E_RANGE;
-        }
-        if (!a->R || !a->T || !a->depth) { set_error("%s: view %d: R / T / depth is NULL", name, v); return LVDGS_E_INVALID; }
-        if (a->image && !vol->r) { set_error("%s: view %d has an image, the volume no colour planes", name, v); return LVDGS_E_INVALID; }
-        p.v[v] = TsdfView{a->width, a->height, a->fx, a->fy, a->cx, a->cy, a->depth_min, a->depth_trunc, a->R, a->T, a->depth, a->image, a->mask};
-        most_pixels = std::max(most_pixels, (int64_t)a->width * a->height);
-    }
+    int64_t most_pixels;
+    if (int e = tsdf_pack_views(name, views, count, vol->r != nullptr, p.v, &most_pixels)) return e;
     if (count == 0) return LVDGS_OK;
     p.count = count;
     AllocParams ap{};

@@ -12,12 +12,11 @@ A volume holds what its pool holds: ``stats()["dropped"]`` > 0 says that surface
 There is no CPU path: tensors that are not on a GPU raise ``LvdgsError``.
 """
 import ctypes as C
-import math
 
 import torch
 
 from . import _lib
-from .tsdf import Mesh, TsdfVolume
+from .tsdf import Mesh, TsdfVolume, _TsdfBase
 
 _mesh_call = _lib.HostCall("lvdgs_tsdf_blocks_mesh", tag=_lib.TSDF_BLOCKS_SEQ)
 _INT32_MAX = 2 ** 31 - 1
@@ -43,26 +42,17 @@ def table_slots_for(pool_blocks):
     return 1 << max(1, (2 * int(pool_blocks) - 1).bit_length())
 
 
-class TsdfBlockVolume:
+class TsdfBlockVolume(_TsdfBase):
     """Samples at ``origin + voxel_size * g`` for signed global indices ``g``; block ``b = floor(g / 8)`` per axis, stored when a view's
     depth band crossed it.  ``pool_blocks`` blocks of 512 samples per plane (``tsdf``, ``weight`` and, with ``color``, ``r``, ``g``,
-    ``b``), ``block_key`` (pool_blocks int64), the table (``table_slots`` keys and values) and the header."""
+    ``b``), ``block_key`` (pool_blocks int64), the table (``table_slots`` keys and values) and the header.  Fusion (``integrate*``) is
+    the dense volume's, into ``lvdgs_tsdf_blocks_integrate``."""
+    _integrate = "lvdgs_tsdf_blocks_integrate"
 
     def __init__(self, origin, voxel_size, pool_blocks, trunc=None, max_weight=64.0, color=True, device="cuda", table_slots=None):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.LvdgsError("TsdfBlockVolume: the volume lives on a GPU (there is no CPU path)")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.origin = tuple(float(v) for v in origin)
-        self.voxel_size = self.voxel_size_requested = float(voxel_size)
-        self.trunc = 4.0 * self.voxel_size if trunc is None else float(trunc)
-        self.max_weight = float(max_weight)
-        self.color = bool(color)
+        super().__init__(origin, voxel_size, trunc, max_weight, color, device)
         if len(self.origin) != 3:
             raise _lib.LvdgsError("TsdfBlockVolume: origin has three entries")
-        self.frames = 0
-        self._capacity = None
         self._allocate(pool_blocks, table_slots)
 
     def _allocate(self, pool_blocks, table_slots=None):
@@ -94,31 +84,6 @@ class TsdfBlockVolume:
         for t in (self.planes, self.block_key, self.table_keys, self.table_values, self.header):
             t.zero_()
         self.frames = 0
-
-    # ---- fusion ----------------------------------------------------------------------------------
-    _view = TsdfVolume._view      # one view's argument block and the tensors it points into (reads self.device and self.color)
-
-    def integrate_views(self, views):
-        """``views``: dicts of ``integrate``'s arguments, fused in list order, 16 per library call.  No wait."""
-        blocks = [self._view(**v) for v in views]
-        L = _lib.lib()
-        stream = _lib.raw_stream(self.device)
-        with _lib.on_device(self.device):
-            for first in range(0, len(blocks), _lib.TSDF_MAX_VIEWS):
-                chunk = blocks[first:first + _lib.TSDF_MAX_VIEWS]
-                ptrs = (C.POINTER(_lib.TsdfViewArgs) * len(chunk))(*[C.pointer(a) for a, _ in chunk])
-                _lib.check(L.lvdgs_tsdf_blocks_integrate(C.byref(self._vol), ptrs, len(chunk), stream), "lvdgs_tsdf_blocks_integrate")
-        self.frames += len(blocks)
-
-    def integrate(self, depth, R, T, intrinsics, image=None, mask=None, depth_min=0.0, depth_trunc=math.inf):
-        """Fuse one view: the arguments of ``TsdfVolume.integrate``."""
-        self.integrate_views([dict(depth=depth, R=R, T=T, intrinsics=intrinsics, image=image, mask=mask, depth_min=depth_min,
-                                   depth_trunc=depth_trunc)])
-
-    def integrate_camera(self, viewpoint, depth, image=None, mask=None, depth_min=0.0, depth_trunc=math.inf):
-        """``integrate`` with ``R``, ``T`` and the intrinsics of a ``camera_utils.Camera``."""
-        self.integrate(depth, viewpoint.R, viewpoint.T, (viewpoint.fx, viewpoint.fy, viewpoint.cx, viewpoint.cy), image=image, mask=mask,
-                       depth_min=depth_min, depth_trunc=depth_trunc)
 
     # ---- what the volume holds -------------------------------------------------------------------
     def stats(self):
@@ -189,9 +154,7 @@ class TsdfBlockVolume:
         L = _lib.lib()
         block, scratch = _mesh_call.resources(dev, _lib.TSDF_BLOCKS_HOST_BYTES, L.lvdgs_tsdf_blocks_mesh_scratch_bytes(self.pool_blocks))
         order = self._order().to(torch.int32)
-        vertices = torch.empty((max(vcap, 1), 3), dtype=torch.float32, device=dev)
-        colors = torch.empty((max(vcap, 1), 3), dtype=torch.float32, device=dev) if self.color else None
-        faces = torch.empty((max(fcap, 1), 3), dtype=torch.int32, device=dev)
+        vertices, colors, faces = out = self._mesh_buffers(vcap, fcap)
         a = _lib.TsdfBlocksMeshArgs(vol=self._vol, vertex_capacity=vcap, face_capacity=fcap, cell_lo=(C.c_int32 * 3)(*[int(v) for v in lo]),
                                     cell_hi=(C.c_int32 * 3)(*[int(v) for v in hi]), order=order.data_ptr(), vertices=vertices.data_ptr(),
                                     colors=None if colors is None else colors.data_ptr(), faces=faces.data_ptr(), host_state=block.data_ptr(),
@@ -200,7 +163,7 @@ class TsdfBlockVolume:
         self.last_stats = dict(blocks=int(w[_lib.TSDF_BLOCKS_USED]), dropped=int(w[_lib.TSDF_BLOCKS_DROPPED]),
                                out_of_range=int(w[_lib.TSDF_BLOCKS_OUT_OF_RANGE]) & 0xFFFFFFFF,
                                table_full=bool(int(w[_lib.TSDF_BLOCKS_FLAGS]) & _lib.TSDF_BLOCKS_TABLE_FULL))
-        return (vertices, colors, faces), int(w[_lib.TSDF_BLOCKS_N_VERTICES]), int(w[_lib.TSDF_BLOCKS_N_FACES]), int(w[_lib.TSDF_BLOCKS_OVERFLOW])
+        return out, int(w[_lib.TSDF_BLOCKS_N_VERTICES]), int(w[_lib.TSDF_BLOCKS_N_FACES]), int(w[_lib.TSDF_BLOCKS_OVERFLOW])
 
     def extract_mesh(self, vertex_capacity=None, face_capacity=None, cell_range=None) -> Mesh:
         """The surface-nets mesh of the volume as it stands, vertices in (key, l) order.  The capacities default to the last
@@ -208,17 +171,4 @@ class TsdfBlockVolume:
         repeated once with the exact counts.  ``last_stats`` holds the header as the call saw it.  ``cell_range`` = (lo, hi): only cells
         whose low corner's global index lies in lo <= g < hi per axis -- ((0, 0, 0), (nx - 1, ny - 1, nz - 1)) gives the mesh of a dense
         volume of (nx, ny, nz) samples on this lattice."""
-        guess = self._capacity or (min(self.pool_blocks * 96, _INT32_MAX // 4),) * 2
-        vcap = guess[0] if vertex_capacity is None else int(vertex_capacity)
-        fcap = min(_INT32_MAX, 2 * guess[1]) if face_capacity is None else int(face_capacity)
-        out, nv, nf, overflow = self._mesh_once(vcap, fcap, cell_range)
-        if overflow & _lib.TSDF_OVERFLOW_INT32:
-            raise _lib.LvdgsError("TsdfBlockVolume.extract_mesh: more than 2^31 - 1 faces")
-        if overflow:
-            out, nv, nf, overflow = self._mesh_once(nv, nf, cell_range)
-            if overflow:
-                raise _lib.LvdgsError(f"TsdfBlockVolume.extract_mesh: the retry with the exact counts overflowed ({overflow})")
-        self._capacity = (nv + nv // 4 + 64, nf // 2 + nf // 8 + 64)
-        self.last_counts = (nv, nf)
-        vertices, colors, faces = out
-        return Mesh(vertices[:nv], None if colors is None else colors[:nv], faces[:nf])
+        return self._extract(min(self.pool_blocks * 96, _INT32_MAX // 4), self.pool_blocks * BLOCK_SAMPLES, vertex_capacity, face_capacity, cell_range)
