@@ -37,9 +37,9 @@
  *    getWorld2View2(R,T).transpose(0,1), utils/camera_utils.py:106-116).
  *
  * Host blocks
- *  Eight calls enqueue their launches, do not wait, and report through a block of host memory, `host_state`: lvdgs_depth_align,
+ *  Nine calls enqueue their launches, do not wait, and report through a block of host memory, `host_state`: lvdgs_depth_align,
  *  lvdgs_pnp_ransac, lvdgs_reciprocal_nn, lvdgs_match_depth_scale, lvdgs_frame_summary, lvdgs_seed_points, lvdgs_map_edit_plan,
- *  lvdgs_tsdf_mesh.
+ *  lvdgs_tsdf_mesh, lvdgs_mesh_cull.
  *  - the block is the caller's: page-locked, mapped host memory (hipHostMalloc, a pinned PyTorch tensor) of the size its section
  *    states, which the caller passes by its HOST address; memory that is not so is refused with LVDGS_E_HIP, "<call>: host_state is
  *    not mapped pinned memory", before any launch;
@@ -50,7 +50,7 @@
  *  - the caller clears the tag word, makes the call, synchronises the stream ONCE and looks at the tag: a word that is not this
  *    call's tag means that the call left no state (nothing else in the block is then to be believed);
  *  - the tag is the `seq` of the argument block -- any value the caller's previous call did not use, 0 excepted -- for
- *    lvdgs_frame_summary, lvdgs_seed_points, lvdgs_map_edit_plan and lvdgs_tsdf_mesh, and the status word [0], never 0, for lvdgs_pnp_ransac,
+ *    lvdgs_frame_summary, lvdgs_seed_points, lvdgs_map_edit_plan, lvdgs_tsdf_mesh and lvdgs_mesh_cull, and the status word [0], never 0, for lvdgs_pnp_ransac,
  *    lvdgs_reciprocal_nn and lvdgs_match_depth_scale;
  *  - lvdgs_depth_align is the exception: its block has no tag, it is a state that every launch which changes it mirrors, that is
  *    complete behind the caller's wait for the stream, and that lvdgs_depth_align_resume reads ON THE HOST -- the caller leaves it
@@ -1724,6 +1724,94 @@ size_t lvdgs_mesh_sample_scratch_bytes(int64_t num_faces);
 int lvdgs_mesh_sample(const lvdgs_mesh_sample_args *a, void *stream);
 size_t lvdgs_cloud_distance_scratch_bytes(int64_t num_queries, int64_t num_reference);
 int lvdgs_cloud_distance(const lvdgs_cloud_distance_args *a, void *stream);
+
+/* Culling a mesh to what the evaluated frames observed, before it is scored (what NICE-SLAM-style evaluations do on the host with
+ * trimesh and a Python loop over the frames, after copying the meshes and every depth map there).
+ *
+ * lvdgs_mesh_visibility marks the vertices that some view sees: seen, num_vertices bytes, IN AND OUT -- a byte that is non-0 on entry
+ * is left as it is, a byte that is 0 becomes 1 when a view of this call sees the vertex (seen[v] |= ...): any number of frames goes
+ * through in calls of up to LVDGS_TSDF_MAX_VIEWS views and the caller zeroes the plane once.  views: the lvdgs_tsdf_view of "TSDF
+ * fusion" (R, T, depth, mask on the device; image is ignored), count 0 .. LVDGS_TSDF_MAX_VIEWS.  Per vertex p = (px, py, pz) and view,
+ * all float32, evaluated as written, no contraction:
+ *   - steps 1 and 2 of "TSDF fusion" as they stand: x, y, z, skip unless z > depth_min; u, v, uf, vf, skip unless the half-up pixel
+ *     (ui, vi) lies inside the image;
+ *   - a view with depth == NULL is FRUSTUM ONLY: the vertex is seen when z <= depth_trunc;
+ *   - with a depth plane, d = depth[vi*width + ui] and the vertex is seen when the tests of steps 3 and 4 hold with occlusion_eps in
+ *     the place of trunc: d > 0 && d <= depth_trunc, mask NULL or mask[vi*width + ui] != 0, and !(d - z < -occlusion_eps) -- the
+ *     condition under which a fusion with the truncation distance occlusion_eps would have updated a voxel at p.
+ * A vertex with a non-finite coordinate is never seen: a NaN makes z a NaN, an infinity makes x, y and z each infinite or NaN, and
+ * then either z > depth_min fails or x / z is a NaN and the float comparisons of step 2 fail.
+ * One thread per vertex; the views are walked with their pose and intrinsics in scalar registers, a view is skipped by a whole wave
+ * none of whose vertices passes steps 1 and 2, and a wave whose vertices are all seen stops.  One launch, no scratch, no atomics, no
+ * host wait.  num_vertices == 0 or count == 0: nothing to do.
+ * Before the launch -- LVDGS_E_INVALID: args NULL; a negative num_vertices or one above 2^31 - 1; count outside 0 ..
+ * LVDGS_TSDF_MAX_VIEWS; vertices or seen NULL with num_vertices > 0; views NULL with count > 0; a view, its R or its T NULL;
+ * LVDGS_E_RANGE: occlusion_eps not finite or negative; a view's width or height below 1 or more than 2^31 - 1 pixels.
+ * THE FLOAT32 RULE AGAINST EXACT ARITHMETIC, u = 2^-24: x, y, z of step 1 are each within 4u * M of their exact values, M = |R0 px| +
+ * |R1 py| + |R2 pz| + |T| of the row (three products and three sums, every partial sum at most M).  So the decision of a view can
+ * differ from the one exact arithmetic takes only for a vertex that lies
+ *   - within 4u Mz of z = depth_min, or (frustum only) of z = depth_trunc;
+ *   - within 5u (Mz + |d|) of d - z = -occlusion_eps (z as above, and the difference rounds by u |d - z| <= u (|d| + Mz); d, the mask
+ *     and occlusion_eps are float32 values that both read alike, so d > 0 and d <= depth_trunc never differ);
+ *   - with u + 0.5 (v + 0.5) within  fx (4u Mx + |x / z| 4u Mz) / |z|  +  4u (|u| + |cx| + 1)  of an integer 0 .. width (height), a
+ *     pixel edge: the quotient x / z inherits the errors of x and z and rounds once, the product with fx, the sum with cx and the sum
+ *     with 0.5 round once each.
+ * tests/test_mesh_cull.py excludes exactly those vertices, with the factors doubled, and requires equality on the rest.
+ *
+ * lvdgs_mesh_cull writes the kept part of a mesh (vertices (V,3) float32, vertex_colors (V,3) float32 or NULL, faces (F,3) int32) in
+ * the original order.  seen: V bytes, non-0 = seen (lvdgs_mesh_visibility's plane, or any other).  A face is KEPT when all three of
+ * its indices lie in 0 .. V-1 and, face_rule LVDGS_MESH_CULL_ALL: all three vertices are seen, LVDGS_MESH_CULL_ANY: at least one is.
+ * A vertex is KEPT exactly when a kept face references it (under ANY that includes unseen vertices; a seen vertex that no kept face
+ * references goes).  Kept vertices keep their relative order and so do kept faces; kept faces are rewritten through the old-to-new
+ * vertex numbers.  Outputs, of the inputs' capacity, so that nothing can overflow: out_vertices V*3; out_colors V*3 or NULL (needs
+ * vertex_colors); out_faces F*3; vertex_origin V int32 or NULL: the old index of each kept vertex; face_origin F int32 or NULL:
+ * likewise.  Rows beyond the counts are not touched.  Coordinates and colours are copied bit for bit.
+ * Launches, enqueued at once: a clear of the used-vertex plane; the face flags, the kept faces per span of faces and a plain store
+ * of 1 per referenced vertex; the used vertices per span of vertices; one workgroup's scan of both counts; the vertices and colours,
+ * with the old-to-new numbers in scratch; the faces; the publish.  No atomic decides a position: two calls give the same bytes.
+ * host_state: a host block ("Host blocks" above) of LVDGS_MESH_CULL_HOST_BYTES bytes: [LVDGS_MESH_CULL_SEQ] the call's `seq`, the
+ * tag; [_N_VERTICES]; [_N_FACES]; zeros after it.  scratch: the bytes lvdgs_mesh_cull_scratch_bytes(num_vertices, num_faces) gives
+ * (0: a count is refused), no initialisation needed.  One wait, at the caller.
+ * Before any launch -- LVDGS_E_INVALID: args NULL; a negative count or one above 2^31 - 1; a face_rule that is neither; vertices, seen
+ * or out_vertices NULL with V > 0; faces or out_faces NULL with F > 0; host_state or scratch NULL; out_colors without vertex_colors;
+ * scratch too small or not 4-byte aligned; an output that overlaps an input, the scratch or another output. */
+#define LVDGS_MESH_CULL_HOST_BYTES 64
+enum {
+    LVDGS_MESH_CULL_SEQ = 0,
+    LVDGS_MESH_CULL_N_VERTICES = 1,
+    LVDGS_MESH_CULL_N_FACES = 2
+};
+enum {
+    LVDGS_MESH_CULL_ALL = 0,
+    LVDGS_MESH_CULL_ANY = 1
+};
+typedef struct lvdgs_mesh_visibility_args {
+    int64_t num_vertices;
+    const float *vertices;        /* num_vertices*3                                 */
+    const lvdgs_tsdf_view *const *views;   /* count views; image ignored, depth may be NULL: frustum only */
+    int32_t count;
+    float occlusion_eps;          /* finite, >= 0                                   */
+    uint8_t *seen;                /* in/out num_vertices                            */
+} lvdgs_mesh_visibility_args;
+typedef struct lvdgs_mesh_cull_args {
+    int64_t num_vertices, num_faces;
+    const float *vertices;        /* num_vertices*3                                 */
+    const float *vertex_colors;   /* num_vertices*3, or NULL                        */
+    const int32_t *faces;         /* num_faces*3                                    */
+    const uint8_t *seen;          /* num_vertices, non-0 = seen                     */
+    int32_t face_rule;            /* LVDGS_MESH_CULL_ALL or _ANY                    */
+    uint32_t seq;
+    float *out_vertices;          /* out num_vertices*3                             */
+    float *out_colors;            /* out num_vertices*3, or NULL; needs vertex_colors */
+    int32_t *out_faces;           /* out num_faces*3                                */
+    int32_t *vertex_origin;       /* out num_vertices, or NULL                      */
+    int32_t *face_origin;         /* out num_faces, or NULL                         */
+    int32_t *host_state;          /* LVDGS_MESH_CULL_HOST_BYTES, pinned host (the host address) */
+    void *scratch; size_t scratch_bytes;
+} lvdgs_mesh_cull_args;
+int lvdgs_mesh_visibility(const lvdgs_mesh_visibility_args *a, void *stream);
+size_t lvdgs_mesh_cull_scratch_bytes(int64_t num_vertices, int64_t num_faces);
+int lvdgs_mesh_cull(const lvdgs_mesh_cull_args *a, void *stream);
 
 /* ---- diagnostics ---- */
 const char *lvdgs_last_error(void);

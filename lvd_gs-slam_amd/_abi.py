@@ -466,6 +466,27 @@ class CloudDistanceArgs(C.Structure):
     ]
 
 
+class MeshVisibilityArgs(C.Structure):
+    _c_name_ = "lvdgs_mesh_visibility_args"
+    _fields_ = [
+        ("num_vertices", C.c_int64), ("vertices", _fp), ("views", _fp), ("count", C.c_int32), ("occlusion_eps", C.c_float), ("seen", _fp),
+    ]
+
+
+class MeshCullArgs(C.Structure):
+    _c_name_ = "lvdgs_mesh_cull_args"
+    _fields_ = [
+        ("num_vertices", C.c_int64), ("num_faces", C.c_int64), ("vertices", _fp), ("vertex_colors", _fp), ("faces", _fp), ("seen", _fp),
+        ("face_rule", C.c_int32), ("seq", C.c_uint32),
+        ("out_vertices", _fp), ("out_colors", _fp), ("out_faces", _fp), ("vertex_origin", _fp), ("face_origin", _fp), ("host_state", _fp),
+        ("scratch", _fp), ("scratch_bytes", C.c_size_t),
+    ]
+
+
+MESH_CULL_HOST_BYTES = 64
+MESH_CULL_SEQ, MESH_CULL_N_VERTICES, MESH_CULL_N_FACES = 0, 1, 2
+MESH_CULL_ALL, MESH_CULL_ANY = 0, 1     # lvdgs_mesh_cull_args.face_rule
+
 DEPTH_SAMPLE_BYTE, DEPTH_SAMPLE_WORD = 1, 2     # lvdgs_ingest_depth_args.sample_type
 MAP_OUTSIDE = -2 ** 31     # INT32_MIN in an undistortion map: the destination pixel's source lies outside
 
@@ -581,6 +602,9 @@ PROTOTYPES = {
     "lvdgs_mesh_sample": (_status, [_P(MeshSampleArgs), _stream]),
     "lvdgs_cloud_distance_scratch_bytes": (_size, [_i64, _i64]),
     "lvdgs_cloud_distance": (_status, [_P(CloudDistanceArgs), _stream]),
+    "lvdgs_mesh_visibility": (_status, [_P(MeshVisibilityArgs), _stream]),
+    "lvdgs_mesh_cull_scratch_bytes": (_size, [_i64, _i64]),
+    "lvdgs_mesh_cull": (_status, [_P(MeshCullArgs), _stream]),
     "lvdgs_last_error": (C.c_char_p, []),
     "lvdgs_version": (C.c_char_p, []),
     "lvdgs_profile_enable": (None, [C.c_int]),

@@ -6,6 +6,10 @@ of every sample in the other cloud (HIP, ``csrc/mesh_eval.hip``; the rules: ``in
 ``score``          both samplings, both directed searches and ONE read of the table (one ``Stream.synchronize``): accuracy, completion,
                    completion ratio, precision, recall, F-score, chamfer -- NICE-SLAM's ``eval_recon`` protocol.
 ``load_mesh_ply``  what ``tsdf.save_mesh_ply`` wrote.
+``visibility``     ``lvdgs_mesh_visibility``: the vertices that some view sees -- inside a frustum and, where the view has a depth plane, not
+                   behind what it shows --, 16 views per call into one byte plane; no wait.
+``cull_mesh``      ``lvdgs_mesh_cull``: the part of a mesh whose faces' vertices were seen, in the original order (HIP,
+                   ``csrc/mesh_cull.hip``); ONE wait, for the two counts.
 
 What trimesh's ``sample_surface`` and a SciPy KD-tree do on the host after a copy of both meshes.  There is no CPU path: tensors that
 are not on a GPU raise ``LvdgsError``.
@@ -17,13 +21,15 @@ import numpy as np
 import torch
 
 from . import _lib
-from .tsdf import Mesh
+from .tsdf import Mesh, view_block
 
 _INT32_MAX = 2 ** 31 - 1
 _sample_scratch = _lib.DeviceScratch()
 _distance_scratch = _lib.DeviceScratch()
 _ROW, _INFO = _lib.CLOUD_DISTANCE_ROW_BYTES, _lib.MESH_SAMPLE_INFO_BYTES
 _score_tables = {}      # device index -> the Table of ``score``
+_cull_call = _lib.HostCall("lvdgs_mesh_cull", tag=_lib.MESH_CULL_SEQ)
+FACE_RULES = {"all": _lib.MESH_CULL_ALL, "any": _lib.MESH_CULL_ANY}
 
 
 def _cuda_device(t, what):
@@ -219,6 +225,85 @@ def score(est, gt, n_samples=200_000, threshold=0.05, seed=0, seed_gt=None, poin
         if int(infos[slot]["flags"]) & _lib.MESH_SAMPLE_NO_AREA:
             raise _lib.LvdgsError(f"score: the {name} mesh has no face with a positive area")
     return score_from_rows(rows[0], rows[1], threshold)
+
+
+def visibility(vertices, views, occlusion_eps=0.0, seen=None):
+    """Which of ``vertices`` (V, 3) some view sees -> ``seen``, (V,) uint8 on the vertices' GPU.  ``views``: the dicts that
+    ``TsdfVolume.integrate_views`` takes -- ``depth`` (H, W), ``R``, ``T``, ``intrinsics``, ``mask``, ``depth_min``, ``depth_trunc``; an
+    ``image`` is ignored.  A view with ``depth=None`` carries ``size=(H, W)`` and is frustum only: a vertex in front of ``depth_min``,
+    inside the image and not beyond ``depth_trunc`` is seen.  With a depth plane the vertex must also not lie more than ``occlusion_eps``
+    behind the pixel's depth, which must be positive, not beyond ``depth_trunc`` and unmasked.  ``seen``: a plane to accumulate into (it
+    is written in place; bytes that are set stay set); default: a zeroed one.  16 views per library call, no wait."""
+    vertices = _points(vertices, "visibility: vertices")
+    dev = vertices.device
+    V = int(vertices.shape[0])
+    if seen is None:
+        seen = torch.zeros(V, dtype=torch.uint8, device=dev)
+    elif not torch.is_tensor(seen) or seen.device != dev or seen.dtype is not torch.uint8 or tuple(seen.shape) != (V,) or not seen.is_contiguous():
+        raise _lib.LvdgsError("visibility: seen must be a contiguous (V,) uint8 tensor on the vertices' GPU")
+    blocks = []
+    for v in views:
+        v = {k: x for k, x in v.items() if k != "image"}
+        depth, size = v.pop("depth", None), v.pop("size", None)
+        if depth is None and size is None:
+            raise _lib.LvdgsError("visibility: a view without a depth plane needs size=(H, W)")
+        blocks.append(view_block("visibility", dev, False, depth, size=size, **v))
+    L = _lib.lib()
+    stream = _lib.raw_stream(dev)
+    with _lib.on_device(dev):
+        for first in range(0, len(blocks), _lib.TSDF_MAX_VIEWS):
+            chunk = blocks[first:first + _lib.TSDF_MAX_VIEWS]
+            ptrs = (C.POINTER(_lib.TsdfViewArgs) * len(chunk))(*[C.pointer(a) for a, _ in chunk])
+            a = _lib.MeshVisibilityArgs(num_vertices=V, vertices=vertices.data_ptr(), views=C.cast(ptrs, C.c_void_p), count=len(chunk),
+                                        occlusion_eps=float(occlusion_eps), seen=seen.data_ptr())
+            _lib.check(L.lvdgs_mesh_visibility(C.byref(a), stream), "lvdgs_mesh_visibility")
+    return seen
+
+
+def cull_raw(vertices, faces, seen, face_rule, out_vertices, out_faces, vertex_colors=None, out_colors=None, vertex_origin=None, face_origin=None):
+    """One ``lvdgs_mesh_cull`` call into the caller's tensors and its one wait -> (kept vertices, kept faces).  Rows beyond the counts
+    are not touched."""
+    dev = vertices.device
+    V, F = int(vertices.shape[0]), int(faces.shape[0])
+    L = _lib.lib()
+    block, scratch = _cull_call.resources(dev, _lib.MESH_CULL_HOST_BYTES, L.lvdgs_mesh_cull_scratch_bytes(V, F))
+    a = _lib.MeshCullArgs(num_vertices=V, num_faces=F, vertices=_lib.ptr(vertices), vertex_colors=_lib.ptr(vertex_colors), faces=_lib.ptr(faces),
+                          seen=_lib.ptr(seen), face_rule=int(face_rule), out_vertices=_lib.ptr(out_vertices), out_colors=_lib.ptr(out_colors),
+                          out_faces=_lib.ptr(out_faces), vertex_origin=_lib.ptr(vertex_origin), face_origin=_lib.ptr(face_origin),
+                          host_state=block.data_ptr(), scratch=scratch.data_ptr(), scratch_bytes=scratch.numel())
+    w = _cull_call.run(dev, a)      # the one wait of the call
+    return int(w[_lib.MESH_CULL_N_VERTICES]), int(w[_lib.MESH_CULL_N_FACES])
+
+
+def cull_mesh(mesh, views=None, seen=None, occlusion_eps=0.0, face_rule="all", want_origin=False):
+    """``mesh`` (a ``tsdf.Mesh`` or a (vertices, faces) pair on a GPU) without the faces that were not seen -> (a ``tsdf.Mesh`` on the
+    device, a record).  ``views``: what ``visibility`` takes, with ``occlusion_eps``; ``seen``: a (V,) uint8 plane to start from, or
+    the whole decision when there are no views.  ``face_rule``: "all" -- a face stays when its three vertices are seen -- or "any".  A
+    vertex stays exactly when a kept face references it; vertices and faces keep their order.  An empty result is a mesh with zero
+    faces.  The record: vertices_before, faces_before, vertices, faces, and with ``want_origin`` vertex_origin and face_origin, the
+    old index of each kept row (int32, on the device).  ONE wait."""
+    vertices, faces, colors = _mesh_parts(mesh)
+    if face_rule not in FACE_RULES:
+        raise _lib.LvdgsError(f"cull_mesh: face_rule 'all' or 'any', not {face_rule!r}")
+    if views is None and seen is None:
+        raise _lib.LvdgsError("cull_mesh: give the views, a seen plane, or both")
+    dev = vertices.device
+    V, F = int(vertices.shape[0]), int(faces.shape[0])
+    if views is not None:
+        seen = visibility(vertices, views, occlusion_eps, seen=seen)
+    elif not torch.is_tensor(seen) or seen.device != dev or seen.dtype is not torch.uint8 or tuple(seen.shape) != (V,) or not seen.is_contiguous():
+        raise _lib.LvdgsError("cull_mesh: seen must be a contiguous (V,) uint8 tensor on the mesh's GPU")
+    out_vertices = torch.empty((max(V, 1), 3), dtype=torch.float32, device=dev)
+    out_colors = None if colors is None else torch.empty((max(V, 1), 3), dtype=torch.float32, device=dev)
+    out_faces = torch.empty((max(F, 1), 3), dtype=torch.int32, device=dev)
+    vertex_origin = torch.empty(max(V, 1), dtype=torch.int32, device=dev) if want_origin else None
+    face_origin = torch.empty(max(F, 1), dtype=torch.int32, device=dev) if want_origin else None
+    nv, nf = cull_raw(vertices, faces, seen, FACE_RULES[face_rule], out_vertices, out_faces, vertex_colors=colors, out_colors=out_colors,
+                      vertex_origin=vertex_origin, face_origin=face_origin)
+    record = dict(vertices_before=V, faces_before=F, vertices=nv, faces=nf)
+    if want_origin:
+        record.update(vertex_origin=vertex_origin[:nv], face_origin=face_origin[:nf])
+    return Mesh(out_vertices[:nv], None if out_colors is None else out_colors[:nv], out_faces[:nf]), record
 
 
 def load_mesh_ply(path, device="cuda") -> Mesh:

@@ -45,6 +45,7 @@ Stand-ins for what is out of scope, all injectable:
 renderer and the loss oracle so that the same harness runs at toy size without a GPU.
 """
 import math
+import os
 import time
 from types import SimpleNamespace
 
@@ -709,37 +710,54 @@ class SlamSequence:
             return list(self.kf_indices)
         return sorted(self.cameras) if frames == "all" else [int(i) for i in frames]
 
-    def _fuse_dataset_depth(self, volume, chosen, poses, depth_trunc):
-        """The chosen frames' dataset depth (``Camera.depth32``, or ``Camera.depth`` / the dataset's plane uploaded once) fused into ``volume`` at the
-        ground-truth poses (``poses="gt"``) or the estimated ones; a frame without depth is left out.  -> the frames fused."""
-        dev, views, fused = volume.device, [], 0
+    def _dataset_depth_plane(self, idx, dev):
+        """Frame ``idx``'s dataset depth (``Camera.depth32``, or ``Camera.depth`` / the dataset's plane uploaded once) as an (H, W) float32 tensor
+        on ``dev``; None for a frame without one."""
+        frame = self.cameras[idx]
+        depth = getattr(frame, "depth32", None)
+        if depth is None:
+            depth = getattr(frame, "depth", None)
+        if depth is None:      # a finished frame has given its planes back (Camera.clean): the dataset still has them
+            record = self.dataset.frame(idx) if hasattr(self.dataset, "frame") else None
+            depth = None if record is None else record.depth32
+            if depth is None:
+                depth = (self.dataset[idx] if record is None else record.frame)[1]
+        if depth is None:
+            return None
+        depth = torch.as_tensor(np.asarray(depth) if not torch.is_tensor(depth) else depth, dtype=torch.float32, device=dev)
+        return depth.detach().to(dev).reshape(int(frame.image_height), int(frame.image_width)).contiguous()
+
+    def _frame_views(self, chosen, poses, depth_trunc, dev, depth="dataset"):
+        """The chosen frames as the view dicts of ``TsdfVolume.integrate_views`` / ``mesh_eval.visibility``, at the ground-truth poses
+        (``poses="gt"``) or the estimated ones.  ``depth="dataset"``: with the frame's dataset depth plane, a frame without one left out;
+        ``depth=None``: every frame, frustum only (``size`` in the plane's place)."""
+        views = []
         for idx in chosen:
             frame = self.cameras[idx]
-            depth = getattr(frame, "depth32", None)
-            if depth is None:
-                depth = getattr(frame, "depth", None)
-            if depth is None:      # a finished frame has given its planes back (Camera.clean): the dataset still has them
-                record = self.dataset.frame(idx) if hasattr(self.dataset, "frame") else None
-                depth = None if record is None else record.depth32
-                if depth is None:
-                    depth = (self.dataset[idx] if record is None else record.frame)[1]
-            if depth is None:
-                continue
-            depth = torch.as_tensor(np.asarray(depth) if not torch.is_tensor(depth) else depth, dtype=torch.float32, device=dev)
-            depth = depth.detach().to(dev).reshape(int(frame.image_height), int(frame.image_width)).contiguous()
             R, T = (frame.R_gt, frame.T_gt) if poses == "gt" else (frame.R, frame.T)
-            views.append(dict(depth=depth, R=R.detach().to(dev), T=T.detach().to(dev), intrinsics=(frame.fx, frame.fy, frame.cx, frame.cy),
-                              depth_trunc=float("inf") if depth_trunc is None else float(depth_trunc)))
-            fused += 1
-            if len(views) == 16:
-                volume.integrate_views(views)
-                views = []
-        if views:
-            volume.integrate_views(views)
-        return fused
+            view = dict(R=R.detach().to(dev), T=T.detach().to(dev), intrinsics=(frame.fx, frame.fy, frame.cx, frame.cy),
+                        depth_trunc=float("inf") if depth_trunc is None else float(depth_trunc))
+            if depth == "dataset":
+                plane = self._dataset_depth_plane(idx, dev)
+                if plane is None:
+                    continue
+                view["depth"] = plane
+            else:
+                view.update(depth=None, size=(int(frame.image_height), int(frame.image_width)))
+            views.append(view)
+        return views
+
+    def _fuse_dataset_depth(self, volume, chosen, poses, depth_trunc):
+        """The chosen frames' dataset depth fused into ``volume`` at the ground-truth poses (``poses="gt"``) or the estimated ones; a frame
+        without depth is left out.  -> the frames fused."""
+        views = self._frame_views(chosen, poses, depth_trunc, volume.device)
+        for first in range(0, len(views), 16):
+            volume.integrate_views(views[first:first + 16])
+        return len(views)
 
     def eval_mesh(self, voxel_size, bounds=None, frames="keyframes", n_samples=200_000, threshold=None, seed=0, seed_gt=None, mask="static",
-                  depth_trunc=None, max_voxels=1 << 26, est_depth="render", volume="dense", pool_blocks=None):
+                  depth_trunc=None, max_voxels=1 << 26, est_depth="render", volume="dense", pool_blocks=None, gt_mesh=None, cull=None,
+                  cull_eps=None, face_rule="all"):
         """The finished map's surface scored against ground-truth geometry (``mesh_eval.score``: accuracy, completion, completion ratio,
         precision, recall, F-score, chamfer -- NICE-SLAM's ``eval_recon`` protocol), everything on the device.
 
@@ -750,11 +768,27 @@ class SlamSequence:
         ground-truth mesh, which raises ``LvdgsError``.  Three waits: one per mesh, one for the score.
         ``volume="blocks"``, ``pool_blocks``: the estimate's rendered depth goes into a block-sparse volume (``fuse_mesh``); the ground
         truth and ``est_depth="dataset"`` stay dense.
-        -> (the score's dict, a record: both meshes' counts, the voxel size, the threshold, the samples and seeds)."""
+
+        ``gt_mesh``: a ``tsdf.Mesh`` on the device or the path of a PLY (``mesh_eval.load_mesh_ply``) in the ground-truth poses' world
+        frame -- a dataset's own scene mesh --, used as the ground truth in place of the second volume (one wait fewer); the dataset then
+        needs metric depth only for ``cull="visible"``.
+        ``cull``: None, or both meshes culled to what the chosen frames observed before they are scored (``mesh_eval.cull_mesh``, one more
+        wait per mesh): "frustum" -- the estimate by the frames at their estimated ``R``, ``T``, the ground truth by the same frames at
+        ``R_gt``, ``T_gt``, a vertex seen when it lies inside some frame's image and not beyond ``depth_trunc`` --; "visible" -- the ground
+        truth is also tested against the frames' dataset depth planes (``_fuse_dataset_depth``'s), a vertex more than ``cull_eps`` behind
+        its pixel's depth is not seen; the estimate stays frustum-culled, its surface being what those frames rendered.  ``cull_eps``:
+        default the truncation distance ``4 * voxel_size`` actually used -- a fused surface lies within that band of the depth that
+        produced it.  ``face_rule``: "all" or "any" of a face's vertices seen.
+        -> (the score's dict, a record: both meshes' counts, the voxel size, the threshold, the samples and seeds; with ``cull`` per mesh
+        also vertices_before, faces_before, cull and cull_eps)."""
         from . import mesh_eval
-        from .tsdf import TsdfVolume
+        from .tsdf import Mesh, TsdfVolume
         if est_depth not in ("render", "dataset"):
             raise ValueError(f"eval_mesh: est_depth 'render' or 'dataset', not {est_depth!r}")
+        if cull not in (None, "frustum", "visible"):
+            raise ValueError(f"eval_mesh: cull None, 'frustum' or 'visible', not {cull!r}")
+        if face_rule not in mesh_eval.FACE_RULES:
+            raise ValueError(f"eval_mesh: face_rule 'all' or 'any', not {face_rule!r}")
         chosen = self._chosen_frames(frames)
         gaussians = self.frontend_gaussians
         with torch.no_grad():
@@ -773,16 +807,41 @@ class SlamSequence:
                 est = volume.extract_mesh()
                 est_record = dict(dims=list(volume.dims), voxel_size=volume.voxel_size, voxel_size_requested=volume.voxel_size_requested,
                                   frames=fused, vertices=int(est.vertices.shape[0]), faces=int(est.faces.shape[0]))
-            truth = TsdfVolume.from_bounds(bounds[0], bounds[1], voxel_size, max_voxels=max_voxels, color=False, device=xyz.device)
-            fused = self._fuse_dataset_depth(truth, chosen, "gt", depth_trunc)
-            gt = truth.extract_mesh()
-        gt_record = dict(dims=list(truth.dims), voxel_size=truth.voxel_size, frames=fused, vertices=int(gt.vertices.shape[0]), faces=int(gt.faces.shape[0]))
+            if gt_mesh is None:
+                truth = TsdfVolume.from_bounds(bounds[0], bounds[1], voxel_size, max_voxels=max_voxels, color=False, device=xyz.device)
+                fused = self._fuse_dataset_depth(truth, chosen, "gt", depth_trunc)
+                gt = truth.extract_mesh()
+                gt_record = dict(dims=list(truth.dims), voxel_size=truth.voxel_size, frames=fused, vertices=int(gt.vertices.shape[0]),
+                                 faces=int(gt.faces.shape[0]))
+                used = float(truth.voxel_size)
+            else:
+                gt = gt_mesh if isinstance(gt_mesh, Mesh) else mesh_eval.load_mesh_ply(os.fspath(gt_mesh), device=xyz.device)
+                gt_record = dict(source="mesh" if isinstance(gt_mesh, Mesh) else os.fspath(gt_mesh), vertices=int(gt.vertices.shape[0]),
+                                 faces=int(gt.faces.shape[0]))
+                used = float(est_record["voxel_size"])
         if gt_record["faces"] == 0:
+            if gt_mesh is not None:
+                raise _lib.LvdgsError("eval_mesh: the ground-truth mesh has no faces")
             raise _lib.LvdgsError(f"eval_mesh: the ground-truth mesh is empty ({fused} of {len(chosen)} frames have a depth plane and none of it "
                                   "lies in the volume): a dataset without metric depth cannot score a mesh")
         if est_record["faces"] == 0:
             raise _lib.LvdgsError("eval_mesh: the estimated mesh is empty")
-        used = float(truth.voxel_size)
+        if cull is not None:
+            eps = 4.0 * used if cull_eps is None else float(cull_eps)
+            dev = xyz.device
+            gt_views = self._frame_views(chosen, "gt", depth_trunc, dev, depth="dataset" if cull == "visible" else None)
+            if not gt_views:
+                raise _lib.LvdgsError(f"eval_mesh: cull='visible' needs the frames' dataset depth and none of the {len(chosen)} frames has a plane")
+            for name, mesh, record, views, how in (("estimated", est, est_record, self._frame_views(chosen, "estimated", depth_trunc, dev, depth=None), "frustum"),
+                                                   ("ground-truth", gt, gt_record, gt_views, cull)):
+                kept, counts = mesh_eval.cull_mesh(mesh, views=views, occlusion_eps=eps, face_rule=face_rule)
+                record.update(counts, cull=how, cull_eps=eps)
+                if counts["faces"] == 0:
+                    raise _lib.LvdgsError(f"eval_mesh: the {name} mesh has no face that the {len(views)} frames saw (cull={how!r})")
+                if name == "estimated":
+                    est = kept
+                else:
+                    gt = kept
         threshold = 2.0 * used if threshold is None else float(threshold)
         result = mesh_eval.score(est, gt, n_samples=n_samples, threshold=threshold, seed=seed, seed_gt=seed_gt)
         self.last_eval_meshes = (est, gt)

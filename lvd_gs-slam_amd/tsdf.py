@@ -23,6 +23,46 @@ _mesh_call = _lib.HostCall("lvdgs_tsdf_mesh", tag=_lib.TSDF_SEQ)
 _INT32_MAX = 2 ** 31 - 1
 
 
+def view_block(name, dev, color, depth, R, T, intrinsics, image=None, mask=None, depth_min=0.0, depth_trunc=math.inf, size=None):
+    """One view's argument block (``lvdgs_tsdf_view``) and the tensors it points into, for the call ``name`` on the GPU ``dev``.
+    ``color``: an image is acceptable.  ``size``: None -- a depth plane is required --, or the (height, width) of a view that may come
+    without one (``depth=None``: the view is frustum only, ``mesh_eval.visibility``)."""
+    if torch.is_tensor(depth) and depth.ndim == 3 and depth.shape[0] == 1:
+        depth = depth[0]
+    if depth is None and size is not None:
+        H, W = (int(v) for v in size)
+    else:
+        if not _lib.is_f32(depth, dev) or depth.ndim != 2:
+            raise _lib.LvdgsError(f"{name}: depth must be a contiguous (H, W) float32 tensor on the volume's GPU (there is no CPU path)")
+        H, W = depth.shape
+        if size is not None and (int(size[0]), int(size[1])) != (H, W):
+            raise _lib.LvdgsError(f"{name}: the view's size {tuple(size)} is not its depth plane's {(H, W)}")
+    if image is not None:
+        if not color:
+            raise _lib.LvdgsError(f"{name}: an image on a volume made with color=False")
+        if not _lib.is_f32(image, dev) or tuple(image.shape) != (3, H, W):
+            raise _lib.LvdgsError(f"{name}: image must be a contiguous (3, H, W) float32 tensor of the depth's size on its device")
+    if mask is not None:
+        if not torch.is_tensor(mask) or mask.device != dev:
+            raise _lib.LvdgsError(f"{name}: mask must be a tensor on the volume's GPU")
+        mask = mask.reshape(-1) if mask.numel() == H * W else mask
+        if mask.numel() != H * W:
+            raise _lib.LvdgsError(f"{name}: mask must have the depth's H * W elements")
+        mask = (mask if mask.dtype in (torch.uint8, torch.bool) else mask != 0).contiguous()
+        mask = mask.view(torch.uint8) if mask.dtype is torch.bool else mask
+    for what, t in (("R", R), ("T", T)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise _lib.LvdgsError(f"{name}: {what} must be a tensor on the volume's GPU")
+    R, T = _lib.f32(R, dev), _lib.f32(T, dev)
+    if R.numel() != 9 or T.numel() != 3:
+        raise _lib.LvdgsError(f"{name}: R must be (3, 3) and T (3,)")
+    fx, fy, cx, cy = (float(v) for v in intrinsics)
+    a = _lib.TsdfViewArgs(width=W, height=H, fx=fx, fy=fy, cx=cx, cy=cy, depth_min=float(depth_min), depth_trunc=float(depth_trunc),
+                          R=R.data_ptr(), T=T.data_ptr(), depth=None if depth is None else depth.data_ptr(),
+                          image=None if image is None else image.data_ptr(), mask=None if mask is None else mask.data_ptr())
+    return a, (depth, R, T, image, mask)
+
+
 class _TsdfBase:
     """What the dense and the block-sparse volume share: the lattice and the constants of the rule, a view's argument block, the fusion
     calls, and the capacities of a mesh call with their one retry.  A volume supplies ``_vol`` (its argument struct), ``_integrate``
@@ -47,36 +87,8 @@ class _TsdfBase:
     # ---- fusion ----------------------------------------------------------------------------------
     def _view(self, depth, R, T, intrinsics, image=None, mask=None, depth_min=0.0, depth_trunc=math.inf):
         """One view's argument block and the tensors it points into."""
-        dev = self.device
-        if torch.is_tensor(depth) and depth.ndim == 3 and depth.shape[0] == 1:
-            depth = depth[0]
-        if not _lib.is_f32(depth, dev) or depth.ndim != 2:
-            raise _lib.LvdgsError(f"{self._name}.integrate: depth must be a contiguous (H, W) float32 tensor on the volume's GPU (there is no CPU path)")
-        H, W = depth.shape
-        if image is not None:
-            if not self.color:
-                raise _lib.LvdgsError(f"{self._name}.integrate: an image on a volume made with color=False")
-            if not _lib.is_f32(image, dev) or tuple(image.shape) != (3, H, W):
-                raise _lib.LvdgsError(f"{self._name}.integrate: image must be a contiguous (3, H, W) float32 tensor of the depth's size on its device")
-        if mask is not None:
-            if not torch.is_tensor(mask) or mask.device != dev:
-                raise _lib.LvdgsError(f"{self._name}.integrate: mask must be a tensor on the volume's GPU")
-            mask = mask.reshape(-1) if mask.numel() == H * W else mask
-            if mask.numel() != H * W:
-                raise _lib.LvdgsError(f"{self._name}.integrate: mask must have the depth's H * W elements")
-            mask = (mask if mask.dtype in (torch.uint8, torch.bool) else mask != 0).contiguous()
-            mask = mask.view(torch.uint8) if mask.dtype is torch.bool else mask
-        for name, t in (("R", R), ("T", T)):
-            if not torch.is_tensor(t) or not t.is_cuda:
-                raise _lib.LvdgsError(f"{self._name}.integrate: {name} must be a tensor on the volume's GPU")
-        R, T = _lib.f32(R, dev), _lib.f32(T, dev)
-        if R.numel() != 9 or T.numel() != 3:
-            raise _lib.LvdgsError(f"{self._name}.integrate: R must be (3, 3) and T (3,)")
-        fx, fy, cx, cy = (float(v) for v in intrinsics)
-        a = _lib.TsdfViewArgs(width=W, height=H, fx=fx, fy=fy, cx=cx, cy=cy, depth_min=float(depth_min), depth_trunc=float(depth_trunc),
-                              R=R.data_ptr(), T=T.data_ptr(), depth=depth.data_ptr(), image=None if image is None else image.data_ptr(),
-                              mask=None if mask is None else mask.data_ptr())
-        return a, (depth, R, T, image, mask)
+        return view_block(f"{self._name}.integrate", self.device, self.color, depth, R, T, intrinsics, image=image, mask=mask,
+                          depth_min=depth_min, depth_trunc=depth_trunc)
 
     def integrate_views(self, views):
         """``views``: dicts of ``integrate``'s arguments, fused in list order, 16 per library call.  No wait."""

@@ -249,6 +249,13 @@ def main():
                     help="after the run: the fused mesh scored against a mesh fused from the dataset's depth at the ground-truth poses "
                          "(SlamSequence.eval_mesh, lvdgs_mesh_sample / lvdgs_cloud_distance): accuracy, completion, F-score; needs no --mesh PATH")
     ap.add_argument("--mesh-samples", type=int, default=200_000, metavar="N", help="with --mesh-eval: samples per mesh")
+    ap.add_argument("--mesh-gt", default=None, metavar="PATH",
+                    help="with --mesh-eval: a ground-truth mesh (a binary PLY in the ground-truth poses' world frame, mesh_eval.load_mesh_ply) in "
+                         "place of the one fused from the dataset's depth")
+    ap.add_argument("--mesh-cull", choices=("frustum", "visible"), default=None,
+                    help="with --mesh-eval: cull both meshes to what the evaluated frames observed before scoring (mesh_eval.cull_mesh, "
+                         "lvdgs_mesh_visibility / lvdgs_mesh_cull): 'frustum' -- inside some frame's image --, 'visible' -- the ground truth also "
+                         "not behind the frames' dataset depth")
     ap.add_argument("--verbose", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -285,8 +292,11 @@ def main():
         out["mesh"] = dict(record, path=a.mesh, file_bytes=os.path.getsize(a.mesh))
     if a.mesh_eval:
         t_eval = time.perf_counter()
-        score, record = seq.eval_mesh(voxel, n_samples=a.mesh_samples, volume=a.mesh_volume)
+        score, record = seq.eval_mesh(voxel, n_samples=a.mesh_samples, volume=a.mesh_volume, gt_mesh=a.mesh_gt, cull=a.mesh_cull)
         out["mesh_eval"] = dict(score, record=record, eval_mesh_seconds=round(time.perf_counter() - t_eval, 4))
+        if a.mesh_cull:      # the same meshes scored whole, beside the culled score
+            whole, _ = seq.eval_mesh(voxel, n_samples=a.mesh_samples, volume=a.mesh_volume, gt_mesh=a.mesh_gt)
+            out["mesh_eval"]["without_cull"] = {k: whole[k] for k in ("accuracy", "completion", "completion_ratio", "precision", "recall", "fscore")}
     out["seed"] = a.seed
     out["tool_seconds"] = round(time.perf_counter() - t0, 2)
     print(json.dumps(out))
