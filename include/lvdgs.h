@@ -1813,6 +1813,82 @@ int lvdgs_mesh_visibility(const lvdgs_mesh_visibility_args *a, void *stream);
 size_t lvdgs_mesh_cull_scratch_bytes(int64_t num_vertices, int64_t num_faces);
 int lvdgs_mesh_cull(const lvdgs_mesh_cull_args *a, void *stream);
 
+/* Depth and face indices rendered from a mesh: a triangle rasteriser with a depth buffer (what NICE-SLAM-style evaluations do on the
+ * host with pyrender, after copying the mesh there, to cull a mesh against itself and to report a depth L1).
+ *
+ * lvdgs_mesh_depth renders views[0 .. count-1] (count 0 .. LVDGS_TSDF_MAX_VIEWS) of (vertices (V,3) float32, faces (F,3) int32).  A view
+ * is the lvdgs_tsdf_view of "TSDF fusion": R and T on the device; depth, image and mask are ignored and may be NULL.  Per view v it
+ * writes depth[v], height*width float32: the camera z of the nearest covering face, or 0.0f where no face covers (the "no depth"
+ * every consumer of a depth plane here understands: d > 0), and, when face_index is not NULL, face_index[v], height*width int32: the
+ * index of that face, or -1.  depth and face_index are HOST arrays of count device addresses; face_index NULL: no face planes,
+ * otherwise every one of its entries is set.  All float32, evaluated as written, no contraction:
+ *   VERTICES.  x, y, z of step 1 of "TSDF fusion"; u = fx * (x / z) + cx, v = fy * (y / z) + cy, the expressions of step 2, continuous
+ *     and not rounded.  Pixel (i, j) has its centre at u = i, v = j (the half-up pixel of step 2 is the one whose centre is nearest).
+ *     dm = fmaxf(depth_min, 0.0f) stands for depth_min throughout: the planes hold positive depths only.
+ *   WHICH FACES TAKE PART.  Face f = (a0, a1, a2) takes part in a view when all three indices lie in 0 .. V-1; all three z > dm -- a
+ *     face that crosses the near plane is dropped WHOLE, there is no clipping --; fabsf(u) < +inf and fabsf(v) < +inf for all three (u and v
+ *     finite: a NaN fails); and its area is not 0:  ar = (u1 - u0) * (v2 - v0) - (v1 - v0) * (u2 - u0),  ar > 0 || ar < 0.  A vertex with a
+ *     non-finite coordinate drops its faces by these comparisons failing, as in the visibility rule.
+ *   PIXEL BOX.  lo = ceilf(fminf(fminf(u0, u1), u2)), hi = floorf(fmaxf(fmaxf(u0, u1), u2)); no pixel unless lo < (float)width && hi >=
+ *     0.0f && lo <= hi (float comparisons first, as in step 2); then i runs from (lo > 0.0f ? (int)lo : 0) to (hi < (float)width ?
+ *     (int)hi : width - 1), which is max(0, lo) .. min(width - 1, hi).  j alike from v and height.
+ *   EDGE VALUES, watertight by construction.  The edge of a face between its vertices a and b: order the two by VERTEX INDEX, lo the
+ *     smaller one (equal indices: either, the value is 0 both ways), and
+ *         s = (u_hi - u_lo) * ((float)j - v_lo) - (v_hi - v_lo) * ((float)i - u_lo).
+ *     The edge value is s when the face lists the edge as lo -> hi and -s otherwise (negation is exact).  E_k is the value of the
+ *     edge opposite vertex k, listed as a1 -> a2, a2 -> a0, a0 -> a1 for k = 0, 1, 2.  The pixel is COVERED when all three E_k >= 0 or
+ *     all three <= 0: both windings count and edges are inclusive (scene meshes have no reliable winding, and an occluder occludes
+ *     from both sides).  Two faces that share an edge compute the same s for it, so at every pixel at least one of them passes
+ *     that edge: a welded surface has no pinholes from rounding, and double coverage is harmless under a minimum.
+ *   DEPTH of a covered pixel, perspective-correct (linear in 1/z):  A = (E0 + E1) + E2;  w_k = E_k / A;
+ *         inv = (w0 * (1.0f / z0) + w1 * (1.0f / z1)) + w2 * (1.0f / z2);  zp = 1.0f / inv.
+ *     The candidate is skipped unless zp > dm && zp <= depth_trunc (a NaN -- A == 0 gives one -- fails).
+ *   WINNER.  The smallest zp; among equal zp the smallest face index.  One 64-bit key per pixel, (uint64)float_bits(zp) << 32 |
+ *     (uint32)f -- the bits of positive floats order as unsigned integers --, reduced by an unsigned 64-bit atomic minimum in a
+ *     scratch plane.  A minimum does not depend on arrival order: two calls give the same bytes.  It is the only atomic of the call
+ *     and decides a value, never a position.
+ * Launches, enqueued at once, no host wait, no copy: the fill of the scratch keys with all ones; the raster launch -- one lane owns
+ * one face and loads its three vertices once per call; the views are walked with their pose and intrinsics in scalar registers, and
+ * a view in which no face of a wave has a pixel box is skipped by the wave; a lane walks its own box while the box holds at most 16
+ * pixels, a larger box is handed to the whole wave, one face at a time, whose 64 lanes walk it in tiles of 8 x 8 pixels (the result
+ * does not depend on that threshold: it is a minimum); a plain load of the key in front of the atomic could skip a candidate that is not smaller (a stale
+ * value is only ever larger, so the skip would be safe), but measured it costs more than it saves and is compiled out --; the resolve launch, which turns each key into the depth float and the face index, 0.0f and
+ * -1 for an untouched key, and writes height*width elements per plane, nothing behind them.  num_faces == 0 or num_vertices == 0
+ * still writes the empty planes.  scratch: the bytes lvdgs_mesh_depth_scratch_bytes(total_pixels) gives for the sum of height*width
+ * over the views of the call -- 8 bytes per pixel, rounded up to a multiple of 256, of which the call needs the 8 per pixel -- (0: the size is refused: negative, or more than 2^31 - 1 pixels a view times
+ * LVDGS_TSDF_MAX_VIEWS), 8-byte aligned, no initialisation needed.
+ * Before any launch -- LVDGS_E_INVALID: args NULL; a negative count or one above 2^31 - 1; vertices NULL with V > 0, faces NULL with
+ * F > 0; count outside 0 .. LVDGS_TSDF_MAX_VIEWS; views or depth NULL with count > 0; a view, its R, its T or its depth output
+ * NULL; a face_index list with a NULL entry; scratch NULL, too small or not 8-byte aligned (count > 0); an output that overlaps an
+ * input (vertices, faces, a view's R or T), the scratch or another output;  LVDGS_E_RANGE: a view's width or height below 1 or more
+ * than 2^31 - 1 pixels.
+ * THE FLOAT32 RULE AGAINST EXACT ARITHMETIC, u = 2^-24, with the float32 u, v, z of the vertices as the operands (both read them
+ * alike; the box follows from them without rounding):
+ *   - an edge value: the two differences of each product round once each, the product once, the final difference once, so s is
+ *     within  4u (|u_hi - u_lo| |j - v_lo| + |v_hi - v_lo| |i - u_lo|)  of its exact value (first order in u; (float)i and (float)j
+ *     are exact for images below 2^24 pixels a side).  Coverage can differ from exact arithmetic only at a pixel where an edge
+ *     value of a face lies within that bound of 0.
+ *   - zp of a covered pixel: the E_k have one sign, so A, the w_k and inv are sums and quotients of like-signed terms without
+ *     cancellation -- two sums, a quotient, the reciprocal of z_k, a product, two sums and the last reciprocal: 8u relative --, and an
+ *     error e_k of E_k moves inv by at most e_k / |A| times the spread of the 1 / z_k.  zp is within
+ *         (8u + ((e_0 + e_1 + e_2) / |A|) * (z_max / z_min - 1)) * zp
+ *     of its exact value, e_k the edge bound above, z_max and z_min over the face's three vertices.
+ * tests/test_mesh_depth.py takes both bounds doubled: pixels where an edge value lies within the first of 0, or two candidate depths
+ * (or a candidate and dm or depth_trunc) within the second of each other, are set aside, at most 1 % of the covered ones, and the rest
+ * must agree. */
+typedef struct lvdgs_mesh_depth_args {
+    int64_t num_vertices, num_faces;
+    const float *vertices;        /* num_vertices*3                                 */
+    const int32_t *faces;         /* num_faces*3                                    */
+    const lvdgs_tsdf_view *const *views;   /* count views; depth, image and mask ignored */
+    int32_t count;
+    float *const *depth;          /* host: count device addresses, out height*width each */
+    int32_t *const *face_index;   /* host: count device addresses, out height*width each, or NULL */
+    void *scratch; size_t scratch_bytes;
+} lvdgs_mesh_depth_args;
+size_t lvdgs_mesh_depth_scratch_bytes(int64_t total_pixels);
+int lvdgs_mesh_depth(const lvdgs_mesh_depth_args *a, void *stream);
+
 /* ---- diagnostics ---- */
 const char *lvdgs_last_error(void);
 const char *lvdgs_version(void);

@@ -487,6 +487,15 @@ MESH_CULL_HOST_BYTES = 64
 MESH_CULL_SEQ, MESH_CULL_N_VERTICES, MESH_CULL_N_FACES = 0, 1, 2
 MESH_CULL_ALL, MESH_CULL_ANY = 0, 1     # lvdgs_mesh_cull_args.face_rule
 
+
+class MeshDepthArgs(C.Structure):
+    _c_name_ = "lvdgs_mesh_depth_args"
+    _fields_ = [
+        ("num_vertices", C.c_int64), ("num_faces", C.c_int64), ("vertices", _fp), ("faces", _fp), ("views", _fp), ("count", C.c_int32),
+        ("depth", _fp), ("face_index", _fp), ("scratch", _fp), ("scratch_bytes", C.c_size_t),
+    ]
+
+
 DEPTH_SAMPLE_BYTE, DEPTH_SAMPLE_WORD = 1, 2     # lvdgs_ingest_depth_args.sample_type
 MAP_OUTSIDE = -2 ** 31     # INT32_MIN in an undistortion map: the destination pixel's source lies outside
 
@@ -605,6 +614,8 @@ PROTOTYPES = {
     "lvdgs_mesh_visibility": (_status, [_P(MeshVisibilityArgs), _stream]),
     "lvdgs_mesh_cull_scratch_bytes": (_size, [_i64, _i64]),
     "lvdgs_mesh_cull": (_status, [_P(MeshCullArgs), _stream]),
+    "lvdgs_mesh_depth_scratch_bytes": (_size, [_i64]),
+    "lvdgs_mesh_depth": (_status, [_P(MeshDepthArgs), _stream]),
     "lvdgs_last_error": (C.c_char_p, []),
     "lvdgs_version": (C.c_char_p, []),
     "lvdgs_profile_enable": (None, [C.c_int]),

@@ -75,12 +75,20 @@ __device__ __forceinline__ bool brick_may_touch(const TsdfLattice &p, const Tsdf
 
 // Steps 1 and 2 for the voxel at (px, py, pz): its camera depth z, whether it lies in front of depth_min and inside the image, and
 // its pixel (pixel 0 stands in where there is none: a gather from it has a valid address and needs no branch).
-struct TsdfPixel { float z; int pix; bool ok; };
-__device__ __forceinline__ TsdfPixel tsdf_pixel(const TsdfView &V, const float (&R)[9], const float (&T)[3], float px, float py, float pz) {
+// Step 1 and the two expressions of step 2 that stay continuous: the camera depth z and the image position (u, v) of (px, py, pz).
+struct TsdfProjected { float z, u, v; };
+__device__ __forceinline__ TsdfProjected tsdf_project(float fx, float fy, float cx, float cy, const float (&R)[9], const float (&T)[3],
+                                                      float px, float py, float pz) {
     const float x = ((R[0] * px + R[1] * py) + R[2] * pz) + T[0];
     const float y = ((R[3] * px + R[4] * py) + R[5] * pz) + T[1];
     const float z = ((R[6] * px + R[7] * py) + R[8] * pz) + T[2];
-    const float u = V.fx * (x / z) + V.cx, vv = V.fy * (y / z) + V.cy;
+    return TsdfProjected{z, fx * (x / z) + cx, fy * (y / z) + cy};
+}
+
+struct TsdfPixel { float z; int pix; bool ok; };
+__device__ __forceinline__ TsdfPixel tsdf_pixel(const TsdfView &V, const float (&R)[9], const float (&T)[3], float px, float py, float pz) {
+    const TsdfProjected at = tsdf_project(V.fx, V.fy, V.cx, V.cy, R, T, px, py, pz);
+    const float z = at.z, u = at.u, vv = at.v;
     const float uf = floorf(u + 0.5f), vf = floorf(vv + 0.5f);
     TsdfPixel P;
     P.z = z;

@@ -9,7 +9,11 @@ of every sample in the other cloud (HIP, ``csrc/mesh_eval.hip``; the rules: ``in
 ``visibility``     ``lvdgs_mesh_visibility``: the vertices that some view sees -- inside a frustum and, where the view has a depth plane, not
                    behind what it shows --, 16 views per call into one byte plane; no wait.
 ``cull_mesh``      ``lvdgs_mesh_cull``: the part of a mesh whose faces' vertices were seen, in the original order (HIP,
-                   ``csrc/mesh_cull.hip``); ONE wait, for the two counts.
+                   ``csrc/mesh_cull.hip``); ONE wait, for the two counts.  ``occlusion="self"``: the views' depth
+                   planes are first rendered from the mesh itself.
+``render_depth``   ``lvdgs_mesh_depth``: per view the depth plane -- and the face-index plane -- a rasteriser with a depth buffer gives of a
+                   mesh (HIP, ``csrc/mesh_depth.hip``), 16 views per call; no wait.
+``depth_l1_terms`` the sum and the count of one frame's "Depth L1" between two rendered planes, as torch statements.
 
 What trimesh's ``sample_surface`` and a SciPy KD-tree do on the host after a copy of both meshes.  There is no CPU path: tensors that
 are not on a GPU raise ``LvdgsError``.
@@ -29,6 +33,7 @@ _distance_scratch = _lib.DeviceScratch()
 _ROW, _INFO = _lib.CLOUD_DISTANCE_ROW_BYTES, _lib.MESH_SAMPLE_INFO_BYTES
 _score_tables = {}      # device index -> the Table of ``score``
 _cull_call = _lib.HostCall("lvdgs_mesh_cull", tag=_lib.MESH_CULL_SEQ)
+_depth_scratch = _lib.DeviceScratch()
 FACE_RULES = {"all": _lib.MESH_CULL_ALL, "any": _lib.MESH_CULL_ANY}
 
 
@@ -275,20 +280,86 @@ def cull_raw(vertices, faces, seen, face_rule, out_vertices, out_faces, vertex_c
     return int(w[_lib.MESH_CULL_N_VERTICES]), int(w[_lib.MESH_CULL_N_FACES])
 
 
-def cull_mesh(mesh, views=None, seen=None, occlusion_eps=0.0, face_rule="all", want_origin=False):
+def _size_of_view(v, what):
+    size, depth = v.get("size"), v.get("depth")
+    if size is None and torch.is_tensor(depth) and depth.ndim >= 2:
+        size = depth.shape[-2:]
+    if size is None:
+        raise _lib.LvdgsError(f"{what}: a view needs size=(H, W)")
+    return int(size[0]), int(size[1])
+
+
+def render_depth(mesh, views, want_faces=False):
+    """``mesh`` (a ``tsdf.Mesh`` or a (vertices, faces) pair on a GPU) seen from ``views`` -> a list of (H, W) float32 depth planes on the
+    mesh's GPU: per pixel the camera z of the nearest face that covers the pixel's centre, 0 where none does.  ``want_faces``: ->
+    (the depth planes, the (H, W) int32 planes of the winning faces' indices, -1 where none).  ``views``: the dicts ``visibility`` takes
+    -- ``R``, ``T``, ``intrinsics``, ``depth_min``, ``depth_trunc`` and ``size=(H, W)``, which is required unless the view carries a depth
+    plane of that size; ``depth``, ``image`` and ``mask`` are ignored.  Both windings of a face cover, edges are inclusive, a face with a
+    vertex at or in front of ``depth_min`` is dropped whole (include/lvdgs.h, "Mesh scoring").  16 views per library call, no wait."""
+    vertices, faces, _ = _mesh_parts(mesh)
+    dev = vertices.device
+    blocks, sizes = [], []
+    for v in views:
+        size = _size_of_view(v, "render_depth")
+        v = {k: x for k, x in v.items() if k not in ("image", "depth", "mask", "size")}
+        blocks.append(view_block("render_depth", dev, False, None, size=size, **v))
+        sizes.append(size)
+    depth = [torch.empty(size, dtype=torch.float32, device=dev) for size in sizes]
+    index = [torch.empty(size, dtype=torch.int32, device=dev) for size in sizes] if want_faces else None
+    L = _lib.lib()
+    stream = _lib.raw_stream(dev)
+    V, F = int(vertices.shape[0]), int(faces.shape[0])
+    with _lib.on_device(dev):
+        for first in range(0, len(blocks), _lib.TSDF_MAX_VIEWS):
+            chunk = blocks[first:first + _lib.TSDF_MAX_VIEWS]
+            n = len(chunk)
+            ptrs = (C.POINTER(_lib.TsdfViewArgs) * n)(*[C.pointer(a) for a, _ in chunk])
+            planes = (C.c_void_p * n)(*[d.data_ptr() for d in depth[first:first + n]])
+            indices = (C.c_void_p * n)(*[d.data_ptr() for d in index[first:first + n]]) if want_faces else None
+            scratch = _depth_scratch.get(dev, L.lvdgs_mesh_depth_scratch_bytes(sum(h * w for h, w in sizes[first:first + n])))
+            a = _lib.MeshDepthArgs(num_vertices=V, num_faces=F, vertices=vertices.data_ptr() if V else None, faces=faces.data_ptr() if F else None,
+                                   views=C.cast(ptrs, C.c_void_p), count=n, depth=C.cast(planes, C.c_void_p),
+                                   face_index=None if indices is None else C.cast(indices, C.c_void_p),
+                                   scratch=scratch.data_ptr(), scratch_bytes=scratch.numel())
+            _lib.check(L.lvdgs_mesh_depth(C.byref(a), stream), "lvdgs_mesh_depth")
+    return (depth, index) if want_faces else depth
+
+
+def depth_l1_terms(d_est, d_gt, depth_trunc=None):
+    """One frame's terms of the "Depth L1" between two depth planes of one size, as torch statements on the planes' device -> (the sum of
+    ``|d_est - d_gt|`` in float64, the number of pixels, int64) over the pixels where both are ``> 0`` and, with ``depth_trunc``, not beyond
+    it.  No wait."""
+    both = (d_est > 0) & (d_gt > 0)
+    if depth_trunc is not None:
+        both = both & (d_est <= float(depth_trunc)) & (d_gt <= float(depth_trunc))
+    diff = (d_est.to(torch.float64) - d_gt.to(torch.float64)).abs()
+    return torch.where(both, diff, torch.zeros_like(diff)).sum(), both.sum()
+
+
+def cull_mesh(mesh, views=None, seen=None, occlusion_eps=0.0, face_rule="all", want_origin=False, occlusion=None):
     """``mesh`` (a ``tsdf.Mesh`` or a (vertices, faces) pair on a GPU) without the faces that were not seen -> (a ``tsdf.Mesh`` on the
     device, a record).  ``views``: what ``visibility`` takes, with ``occlusion_eps``; ``seen``: a (V,) uint8 plane to start from, or
     the whole decision when there are no views.  ``face_rule``: "all" -- a face stays when its three vertices are seen -- or "any".  A
     vertex stays exactly when a kept face references it; vertices and faces keep their order.  An empty result is a mesh with zero
     faces.  The record: vertices_before, faces_before, vertices, faces, and with ``want_origin`` vertex_origin and face_origin, the
-    old index of each kept row (int32, on the device).  ONE wait."""
+    old index of each kept row (int32, on the device).  ``occlusion="self"``: every view's depth plane is replaced by the depth rendered
+    from the mesh itself (``render_depth``; a view needs no plane of its own, ``size`` is enough), so a vertex more than ``occlusion_eps``
+    behind the mesh's first surface in a view is not seen by it.  ONE wait."""
     vertices, faces, colors = _mesh_parts(mesh)
     if face_rule not in FACE_RULES:
         raise _lib.LvdgsError(f"cull_mesh: face_rule 'all' or 'any', not {face_rule!r}")
+    if occlusion not in (None, "self"):
+        raise _lib.LvdgsError(f"cull_mesh: occlusion None or 'self', not {occlusion!r}")
     if views is None and seen is None:
         raise _lib.LvdgsError("cull_mesh: give the views, a seen plane, or both")
+    if occlusion is not None and views is None:
+        raise _lib.LvdgsError("cull_mesh: occlusion='self' needs the views")
     dev = vertices.device
     V, F = int(vertices.shape[0]), int(faces.shape[0])
+    if occlusion is not None:
+        views = list(views)
+        planes = render_depth((vertices, faces), views)
+        views = [dict({k: x for k, x in v.items() if k not in ("size", "image")}, depth=plane) for v, plane in zip(views, planes)]
     if views is not None:
         seen = visibility(vertices, views, occlusion_eps, seen=seen)
     elif not torch.is_tensor(seen) or seen.device != dev or seen.dtype is not torch.uint8 or tuple(seen.shape) != (V,) or not seen.is_contiguous():

@@ -757,7 +757,7 @@ class SlamSequence:
 
     def eval_mesh(self, voxel_size, bounds=None, frames="keyframes", n_samples=200_000, threshold=None, seed=0, seed_gt=None, mask="static",
                   depth_trunc=None, max_voxels=1 << 26, est_depth="render", volume="dense", pool_blocks=None, gt_mesh=None, cull=None,
-                  cull_eps=None, face_rule="all"):
+                  cull_eps=None, face_rule="all", depth_l1=False):
         """The finished map's surface scored against ground-truth geometry (``mesh_eval.score``: accuracy, completion, completion ratio,
         precision, recall, F-score, chamfer -- NICE-SLAM's ``eval_recon`` protocol), everything on the device.
 
@@ -779,14 +779,22 @@ class SlamSequence:
         its pixel's depth is not seen; the estimate stays frustum-culled, its surface being what those frames rendered.  ``cull_eps``:
         default the truncation distance ``4 * voxel_size`` actually used -- a fused surface lies within that band of the depth that
         produced it.  ``face_rule``: "all" or "any" of a face's vertices seen.
+        "occlusion" -- each mesh is culled against the depth rendered from ITSELF (``mesh_eval.render_depth``) at the chosen frames, the
+        estimate at the estimated ``R``, ``T``, the ground truth at ``R_gt``, ``T_gt``, both with ``cull_eps``: a second wall, or the inside of
+        a fused shell, goes from either mesh.  No dataset depth is read, so with ``gt_mesh`` a dataset without metric depth can be scored
+        this way.
+        ``depth_l1``: both final meshes are rendered at the chosen frames (each at its own poses, as above) and the record gains
+        ``depth_l1`` -- the mean over the frames of the frame's mean ``|d_est - d_gt|`` over the pixels where both depths are ``> 0`` and, with
+        ``depth_trunc``, not beyond it (``mesh_eval.depth_l1_terms``; a frame without such a pixel is left out, NaN when there is none) --
+        and ``depth_l1_pixels``, the pixels counted; ``last_eval_depths`` keeps the planes.  One more wait, taken at the end.
         -> (the score's dict, a record: both meshes' counts, the voxel size, the threshold, the samples and seeds; with ``cull`` per mesh
         also vertices_before, faces_before, cull and cull_eps)."""
         from . import mesh_eval
         from .tsdf import Mesh, TsdfVolume
         if est_depth not in ("render", "dataset"):
             raise ValueError(f"eval_mesh: est_depth 'render' or 'dataset', not {est_depth!r}")
-        if cull not in (None, "frustum", "visible"):
-            raise ValueError(f"eval_mesh: cull None, 'frustum' or 'visible', not {cull!r}")
+        if cull not in (None, "frustum", "visible", "occlusion"):
+            raise ValueError(f"eval_mesh: cull None, 'frustum', 'visible' or 'occlusion', not {cull!r}")
         if face_rule not in mesh_eval.FACE_RULES:
             raise ValueError(f"eval_mesh: face_rule 'all' or 'any', not {face_rule!r}")
         chosen = self._chosen_frames(frames)
@@ -832,9 +840,11 @@ class SlamSequence:
             gt_views = self._frame_views(chosen, "gt", depth_trunc, dev, depth="dataset" if cull == "visible" else None)
             if not gt_views:
                 raise _lib.LvdgsError(f"eval_mesh: cull='visible' needs the frames' dataset depth and none of the {len(chosen)} frames has a plane")
-            for name, mesh, record, views, how in (("estimated", est, est_record, self._frame_views(chosen, "estimated", depth_trunc, dev, depth=None), "frustum"),
+            occlusion = "self" if cull == "occlusion" else None
+            for name, mesh, record, views, how in (("estimated", est, est_record, self._frame_views(chosen, "estimated", depth_trunc, dev, depth=None),
+                                                    "occlusion" if occlusion else "frustum"),
                                                    ("ground-truth", gt, gt_record, gt_views, cull)):
-                kept, counts = mesh_eval.cull_mesh(mesh, views=views, occlusion_eps=eps, face_rule=face_rule)
+                kept, counts = mesh_eval.cull_mesh(mesh, views=views, occlusion_eps=eps, face_rule=face_rule, occlusion=occlusion)
                 record.update(counts, cull=how, cull_eps=eps)
                 if counts["faces"] == 0:
                     raise _lib.LvdgsError(f"eval_mesh: the {name} mesh has no face that the {len(views)} frames saw (cull={how!r})")
@@ -847,6 +857,21 @@ class SlamSequence:
         self.last_eval_meshes = (est, gt)
         record = dict(est=est_record, gt=gt_record, est_depth=est_depth, voxel_size=used, threshold=threshold, n_samples=int(n_samples),
                       seed=int(seed), seed_gt=int(seed) + 1 if seed_gt is None else int(seed_gt))
+        if depth_l1:
+            dev = xyz.device
+            planes = [mesh_eval.render_depth(mesh, self._frame_views(chosen, poses, depth_trunc, dev, depth=None))
+                      for mesh, poses in ((est, "estimated"), (gt, "gt"))]
+            terms = [torch.stack([total, pixels.to(torch.float64)])      # per frame: (sum, pixels)
+                     for total, pixels in (mesh_eval.depth_l1_terms(a, b, depth_trunc) for a, b in zip(*planes))]
+            table = torch.stack(terms) if terms else torch.zeros((0, 2), dtype=torch.float64, device=dev)
+            host = torch.empty(table.shape, dtype=torch.float64).pin_memory()
+            host.copy_(table, non_blocking=True)
+            torch.cuda.current_stream(dev).synchronize()      # the one wait of the depth L1
+            sums, pixels = host.numpy()[:, 0], host.numpy()[:, 1]
+            counted = pixels > 0
+            record.update(depth_l1=float((sums[counted] / pixels[counted]).mean()) if counted.any() else math.nan,
+                          depth_l1_pixels=int(pixels.sum()))
+            self.last_eval_depths = tuple(planes)
         return result, record
 
     def summary(self):

@@ -184,6 +184,39 @@ def run_sequence(dev, frames=60, scale=1.0, cadence="reference", fused="auto", i
     return out, seq
 
 
+def png16(plane):
+    """An (H, W) uint16 array as the bytes of a 16-bit grey PNG."""
+    import struct
+    import zlib
+
+    import numpy as np
+    h, w = plane.shape
+    rows = np.concatenate([np.zeros((h, 1), np.uint8), plane.astype(">u2").view(np.uint8).reshape(h, 2 * w)], axis=1)      # filter 0 per row
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 16, 0, 0, 0, 0)) + chunk(b"IDAT", zlib.compress(rows.tobytes(), 6))
+            + chunk(b"IEND", b""))
+
+
+def write_depth_planes(directory, planes, fmt):
+    """``SlamSequence.last_eval_depths`` -- (the estimate's planes, the ground truth's), one per evaluated frame -- into ``directory``."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    written = 0
+    for name, group in zip(("est", "gt"), planes):
+        for k, plane in enumerate(group):
+            d = plane.detach().cpu().numpy()
+            path = os.path.join(directory, f"{name}_{k:04d}.{fmt}")
+            if fmt == "npy":
+                np.save(path, d)
+            else:
+                with open(path, "wb") as fh:
+                    fh.write(png16(np.clip(np.rint(d.astype(np.float64) * 1000.0), 0, 65535).astype(np.uint16)))
+            written += 1
+    return dict(directory=directory, format=fmt, files=written)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=60)
@@ -252,10 +285,19 @@ def main():
     ap.add_argument("--mesh-gt", default=None, metavar="PATH",
                     help="with --mesh-eval: a ground-truth mesh (a binary PLY in the ground-truth poses' world frame, mesh_eval.load_mesh_ply) in "
                          "place of the one fused from the dataset's depth")
-    ap.add_argument("--mesh-cull", choices=("frustum", "visible"), default=None,
+    ap.add_argument("--mesh-cull", choices=("frustum", "visible", "occlusion"), default=None,
                     help="with --mesh-eval: cull both meshes to what the evaluated frames observed before scoring (mesh_eval.cull_mesh, "
                          "lvdgs_mesh_visibility / lvdgs_mesh_cull): 'frustum' -- inside some frame's image --, 'visible' -- the ground truth also "
-                         "not behind the frames' dataset depth")
+                         "not behind the frames' dataset depth --, 'occlusion' -- each mesh against the depth rendered from itself "
+                         "(lvdgs_mesh_depth), which needs no dataset depth")
+    ap.add_argument("--mesh-depth-l1", action="store_true",
+                    help="with --mesh-eval: both final meshes rendered at the evaluated frames (mesh_eval.render_depth) and the mean absolute "
+                         "difference of the two depths over the pixels both cover: the protocol's 'Depth L1'")
+    ap.add_argument("--mesh-depth-out", default=None, metavar="DIR",
+                    help="with --mesh-eval: the depth planes rendered from both final meshes at the evaluated frames, written to DIR as "
+                         "est_NNNN / gt_NNNN in --mesh-depth-format")
+    ap.add_argument("--mesh-depth-format", choices=("png", "npy"), default="png",
+                    help="with --mesh-depth-out: 'png' -- 16-bit grey, millimetres, saturated at 65535 --, 'npy' -- the float32 plane as it is")
     ap.add_argument("--verbose", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -292,8 +334,17 @@ def main():
         out["mesh"] = dict(record, path=a.mesh, file_bytes=os.path.getsize(a.mesh))
     if a.mesh_eval:
         t_eval = time.perf_counter()
-        score, record = seq.eval_mesh(voxel, n_samples=a.mesh_samples, volume=a.mesh_volume, gt_mesh=a.mesh_gt, cull=a.mesh_cull)
+        want_depth = a.mesh_depth_l1 or a.mesh_depth_out is not None
+        score, record = seq.eval_mesh(voxel, n_samples=a.mesh_samples, volume=a.mesh_volume, gt_mesh=a.mesh_gt, cull=a.mesh_cull, depth_l1=want_depth)
         out["mesh_eval"] = dict(score, record=record, eval_mesh_seconds=round(time.perf_counter() - t_eval, 4))
+        if a.mesh_cull:
+            print("  mesh cull {how}: estimate {eb} -> {ea} faces, ground truth {gb} -> {ga} faces".format(
+                how=a.mesh_cull, eb=record["est"]["faces_before"], ea=record["est"]["faces"], gb=record["gt"]["faces_before"], ga=record["gt"]["faces"]),
+                file=sys.stderr)
+        if want_depth:
+            print(f"  depth L1 {record['depth_l1']:.5f} over {record['depth_l1_pixels']} pixels", file=sys.stderr)
+        if a.mesh_depth_out is not None:
+            out["mesh_eval"]["depth_planes"] = write_depth_planes(a.mesh_depth_out, seq.last_eval_depths, a.mesh_depth_format)
         if a.mesh_cull:      # the same meshes scored whole, beside the culled score
             whole, _ = seq.eval_mesh(voxel, n_samples=a.mesh_samples, volume=a.mesh_volume, gt_mesh=a.mesh_gt)
             out["mesh_eval"]["without_cull"] = {k: whole[k] for k in ("accuracy", "completion", "completion_ratio", "precision", "recall", "fscore")}
