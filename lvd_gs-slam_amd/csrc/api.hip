@@ -138,20 +138,7 @@ bool tile_order_in_use(int num_tiles) {
 }
 
 // ---------------------------------------------------------------- layouts
-// Carves the arrays of a state view out of a buffer, every one aligned to 256 bytes (no view: into one of its own; no buffer: sizes only).
-template <typename V>
-struct Carver {
-    V own, &v;
-    char *base;
-    size_t off = 0;
-    Carver(V *view, void *buffer) : v(view ? *view : own), base((char *)buffer) {}
-    template <typename T>
-    void operator()(T *&ptr, size_t count) {
-        ptr = base ? reinterpret_cast<T *>(base + off) : nullptr;
-        off += align256(count * sizeof(T));
-    }
-};
-
+// (carve.hpp: one function per buffer gives its size and binds its arrays)
 size_t geom_layout(int N, GeomView *v, void *base) {
     Carver<GeomView> c(v, base);
     const size_t n = (size_t)(N > 0 ? N : 1);

@@ -30,20 +30,13 @@ struct KnnScratch {
 };
 
 size_t knn_layout(int P, KnnScratch *v, void *base) {
-    KnnScratch tmp;
-    if (!v) v = &tmp;
-    size_t off = 0;
-    char *b = (char *)base;
-    auto carve = [&](auto *&ptr, size_t count) {
-        using T = std::remove_reference_t<decltype(*ptr)>;
-        ptr = b ? reinterpret_cast<T *>(b + off) : nullptr;
-        off += align256(count * sizeof(T));
-    };
+    Carver<KnnScratch> c(v, base);
+    KnnScratch &k = c.v;
     const size_t n = (size_t)(P > 0 ? P : 1), nbox = (n + KNN_BOX_SMALL - 1) / KNN_BOX_SMALL;
-    carve(v->keys[0], n); carve(v->keys[1], n); carve(v->vals[0], n); carve(v->vals[1], n);
-    carve(v->hist, radix_hist_entries(P)); carve(v->totals, (size_t)1 << SORT_MAX_BITS);
-    carve(v->bounds, KNN_BOUNDS_BLOCKS * 6); carve(v->box_lo, nbox * 3); carve(v->box_hi, nbox * 3);
-    return off;
+    c(k.keys[0], n); c(k.keys[1], n); c(k.vals[0], n); c(k.vals[1], n);
+    c(k.hist, radix_hist_entries(P)); c(k.totals, (size_t)1 << SORT_MAX_BITS);
+    c(k.bounds, KNN_BOUNDS_BLOCKS * 6); c(k.box_lo, nbox * 3); c(k.box_hi, nbox * 3);
+    return c.off;
 }
 
 // per-workgroup bounding boxes of a grid-stride share of the points: partial[block][6] (min xyz, max xyz)

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/lvdgs.h"
+#include "carve.hpp"
 
 namespace lvdgs {
 
@@ -38,7 +39,6 @@ constexpr int SORT_CHUNK = SORT_THREADS * SORT_IPT; // elements per workgroup
 constexpr int SORT_MAX_BITS = 8;                   // digit width limit: <= 256 bins keeps same-digit runs long enough
                                                    // for the scatter's stores to coalesce
 
-inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 // the tile rows a call renders (lvdgs_args.tile_row_begin / _end; both 0 = all of them)
 inline void tile_row_band(const lvdgs_args &a, int *row0, int *row1) {
     const int gy = (a.image_height + TILE - 1) / TILE;

@@ -263,6 +263,13 @@ int iter_blocks(int W, int H, int p) {
     return (int)((npatch + DA_PATCHES_PER_BLOCK - 1) / DA_PATCHES_PER_BLOCK);
 }
 
+// the scratch: the header, a partial per workgroup of the iteration (a size the call refuses: the header alone)
+size_t align_layout(int W, int H, int p, AlignParams *P, void *base) {
+    Carver<AlignParams> c(P, base);
+    c(c.v.hdr, 1); c(c.v.slab, W <= 0 || H <= 0 || p < 1 ? 0 : (size_t)iter_blocks(W, H, p));
+    return c.off;
+}
+
 int align_params(const lvdgs_depth_align_args *a, AlignParams &P) {
     if (!a) { set_error("depth align: args is NULL"); return LVDGS_E_INVALID; }
     if (a->width <= 0 || a->height <= 0 || (int64_t)a->width * a->height > INT32_MAX) {
@@ -275,10 +282,10 @@ int align_params(const lvdgs_depth_align_args *a, AlignParams &P) {
     if (!a->render_depth || !a->mono_depth || !a->final_depth || !a->error_mask || !a->host_state || !a->scratch) {
         set_error("depth align: render_depth / mono_depth / final_depth / error_mask / host_state / scratch is NULL"); return LVDGS_E_INVALID;
     }
-    if (a->scratch_bytes < lvdgs_depth_align_scratch_bytes(a->width, a->height, a->patch_size)) {
+    P = AlignParams{};
+    if (a->scratch_bytes < align_layout(a->width, a->height, a->patch_size, &P, a->scratch)) {
         set_error("depth align: scratch too small"); return LVDGS_E_INVALID;
     }
-    P = AlignParams{};
     P.W = a->width; P.H = a->height; P.p = a->patch_size;
     P.npx = cdiv(a->width, a->patch_size);
     P.npatch = cdiv(a->height, a->patch_size) * P.npx;
@@ -287,8 +294,6 @@ int align_params(const lvdgs_depth_align_args *a, AlignParams &P) {
     P.eps = (float)a->epsilon; P.final_thr = (float)a->final_error_threshold;
     P.min_accurate = (int64_t)(a->min_accurate_pixels_ratio * (double)((int64_t)a->width * a->height));   // Python's int(ratio * H * W)
     P.r = a->render_depth; P.m = a->mono_depth;
-    P.hdr = reinterpret_cast<DepthAlignHeader *>(a->scratch);
-    P.slab = reinterpret_cast<PatchPartial *>(reinterpret_cast<char *>(a->scratch) + align256(sizeof(DepthAlignHeader)));
     P.final_depth = a->final_depth; P.error_mask = a->error_mask;
     if (int e = host_block_address(a->host_state, "depth align", &P.host_state)) return e;
     return LVDGS_OK;
@@ -313,8 +318,7 @@ int launch_fill(const AlignParams &P, int force, float s_in, int force_status, h
 extern "C" {
 
 size_t lvdgs_depth_align_scratch_bytes(int32_t width, int32_t height, int32_t patch_size) {
-    if (width <= 0 || height <= 0 || patch_size < 1) return align256(sizeof(DepthAlignHeader));
-    return align256(sizeof(DepthAlignHeader)) + align256((size_t)iter_blocks(width, height, patch_size) * sizeof(PatchPartial));
+    return align_layout(width, height, patch_size, nullptr, nullptr);
 }
 
 int lvdgs_depth_align(const lvdgs_depth_align_args *a, void *stream) {

@@ -251,6 +251,20 @@ __global__ void __launch_bounds__(DM_THREADS) dm_expand_kernel(DmParams P) {
     add_counts<3>(P.info, slot, v, lane == 0);
 }
 
+// the state: the header, the ring of the last history_length dynamic masks
+size_t dm_state_layout(int W, int H, int history_length, DmParams *P, void *base) {
+    Carver<DmParams> c(P, base);
+    c.bytes(c.v.header, DM_HEADER_BYTES); c.bytes(c.v.ring, (size_t)history_length * plane_bytes(W, H));
+    return c.off;
+}
+
+// the scratch: two bit planes
+size_t dm_scratch_layout(int W, int H, DmParams *P, void *base) {
+    Carver<DmParams> c(P, base);
+    c.bytes(c.v.plane0, plane_bytes(W, H)); c.bytes(c.v.plane1, plane_bytes(W, H));
+    return c.off;
+}
+
 }  // namespace
 }  // namespace lvdgs
 
@@ -260,12 +274,12 @@ extern "C" {
 
 size_t lvdgs_dynamic_mask_state_bytes(int32_t width, int32_t height, int32_t history_length) {
     if (width < 1 || height < 1 || (int64_t)width * height > INT32_MAX || history_length < 1 || history_length > DM_MAX_HISTORY) return 0;
-    return DM_HEADER_BYTES + align256((size_t)history_length * plane_bytes(width, height));
+    return dm_state_layout(width, height, history_length, nullptr, nullptr);
 }
 
 size_t lvdgs_dynamic_mask_scratch_bytes(int32_t width, int32_t height) {
     if (width < 1 || height < 1 || (int64_t)width * height > INT32_MAX) return 0;
-    return 2 * align256(plane_bytes(width, height));
+    return dm_scratch_layout(width, height, nullptr, nullptr);
 }
 
 int lvdgs_dynamic_mask(const lvdgs_dynamic_mask_args *a, void *stream) {
@@ -296,11 +310,11 @@ int lvdgs_dynamic_mask(const lvdgs_dynamic_mask_args *a, void *stream) {
     if (a->num_sam_masks > 0 && !a->sam_masks) { set_error("dynamic mask: sam_masks is NULL"); return LVDGS_E_INVALID; }
     if (a->expand_kernel != 0 && !a->image) { set_error("dynamic mask: image is NULL (expand_kernel %d)", a->expand_kernel); return LVDGS_E_INVALID; }
     if (a->depth_out && !a->depth_in) { set_error("dynamic mask: depth_out without depth_in"); return LVDGS_E_INVALID; }
-    if (a->state_bytes < lvdgs_dynamic_mask_state_bytes(a->width, a->height, a->history_length)) {
+    DmParams P{};
+    if (a->state_bytes < dm_state_layout(a->width, a->height, a->history_length, &P, a->state)) {
         set_error("dynamic mask: state too small"); return LVDGS_E_INVALID;
     }
-    if (a->scratch_bytes < lvdgs_dynamic_mask_scratch_bytes(a->width, a->height)) { set_error("dynamic mask: scratch too small"); return LVDGS_E_INVALID; }
-    DmParams P{};
+    if (a->scratch_bytes < dm_scratch_layout(a->width, a->height, &P, a->scratch)) { set_error("dynamic mask: scratch too small"); return LVDGS_E_INVALID; }
     P.W = a->width; P.H = a->height; P.wpr = words_per_row(P.W);
     P.words = (int64_t)P.H * P.wpr;
     P.first = a->first_frame != 0; P.box_format = a->box_format;
@@ -313,10 +327,6 @@ int lvdgs_dynamic_mask(const lvdgs_dynamic_mask_args *a, void *stream) {
     P.static_mask = a->static_mask; P.dynamic_mask = a->dynamic_mask;
     P.expanded_dynamic = a->expanded_dynamic; P.expanded_static = a->expanded_static; P.valid_rgb = a->valid_rgb;
     P.info = a->info;
-    P.header = reinterpret_cast<DmHeader *>(a->state);
-    P.ring = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(a->state) + DM_HEADER_BYTES);
-    P.plane0 = reinterpret_cast<uint64_t *>(a->scratch);
-    P.plane1 = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(a->scratch) + align256(plane_bytes(P.W, P.H)));
     const int wave_blocks = (int)min((int64_t)cdiv(P.words, DM_WAVES), (int64_t)DM_MAX_BLOCKS), thread_blocks = cdiv(P.words, DM_THREADS);
     if (int e = check_hip(hipMemsetAsync(a->info, 0, LVDGS_DYNAMIC_MASK_INFO_WORDS * sizeof(int32_t), s), "dynamic mask: clearing info")) return e;
     {

@@ -210,7 +210,19 @@ __global__ void summary_publish_kernel(SummaryParams S) {
     seal_host_block(w, LVDGS_FRAME_SUMMARY_SEQ, (int32_t)S.seq);
 }
 
-size_t summary_state_bytes() { return align256(sizeof(SelectState)) + align256(sizeof(SummaryCounters)); }
+// the edge mask's scratch: the selection's state, the gradient magnitudes (LVDGS_EDGE_MASK_BLOCKS keeps them in the caller's mask plane)
+size_t edge_layout(int W, int H, EdgeParams *P, void *base) {
+    Carver<EdgeParams> c(P, base);
+    c(c.v.st, 1); c(c.v.mag, (size_t)W * H);
+    return c.off;
+}
+
+// the summary's: the selection's state, the counters
+size_t summary_layout(SummaryParams *S, void *base) {
+    Carver<SummaryParams> c(S, base);
+    c(c.v.st, 1); c(c.v.cnt, 1);
+    return c.off;
+}
 
 }  // namespace
 }  // namespace lvdgs
@@ -221,7 +233,7 @@ extern "C" {
 
 size_t lvdgs_edge_mask_scratch_bytes(int32_t width, int32_t height) {
     if (width < 2 || height < 2) return 0;
-    return align256(sizeof(SelectState)) + align256((size_t)width * height * sizeof(float));
+    return edge_layout(width, height, nullptr, nullptr);
 }
 
 int lvdgs_edge_mask(const lvdgs_edge_mask_args *a, void *stream) {
@@ -237,12 +249,11 @@ int lvdgs_edge_mask(const lvdgs_edge_mask_args *a, void *stream) {
         set_error("edge mask: image size %dx%d has no %d x %d grid of blocks", a->width, a->height, EDGE_GRID, EDGE_GRID); return LVDGS_E_RANGE;
     }
     if (!a->image || !a->mask || !a->scratch) { set_error("edge mask: image / mask / scratch is NULL"); return LVDGS_E_INVALID; }
-    if (a->scratch_bytes < lvdgs_edge_mask_scratch_bytes(a->width, a->height)) { set_error("edge mask: scratch too small"); return LVDGS_E_INVALID; }
     EdgeParams P{};
+    if (a->scratch_bytes < edge_layout(a->width, a->height, &P, a->scratch)) { set_error("edge mask: scratch too small"); return LVDGS_E_INVALID; }
     P.W = a->width; P.H = a->height; P.mode = a->mode;
     P.thr = (float)a->edge_threshold;
     P.image = a->image;
-    P.st = reinterpret_cast<SelectState *>(a->scratch);
     P.loss_mask = a->loss_mask; P.stats = a->stats;
     const int64_t n = (int64_t)P.W * P.H;
     const int pixel_blocks = (int)((n + FS_THREADS - 1) / FS_THREADS);
@@ -259,7 +270,6 @@ int lvdgs_edge_mask(const lvdgs_edge_mask_args *a, void *stream) {
         LVDGS_LAUNCH_CHECK("edge_blocks", 0, s);
         return LVDGS_OK;
     }
-    P.mag = reinterpret_cast<float *>(reinterpret_cast<char *>(a->scratch) + align256(sizeof(SelectState)));
     P.mag_copy = a->magnitude;
     P.mask = reinterpret_cast<uint8_t *>(a->mask);
     if (int e = check_hip(hipMemsetAsync(P.st, 0, sizeof(SelectState), s), "edge mask: clearing the selection state")) return e;
@@ -275,7 +285,7 @@ int lvdgs_edge_mask(const lvdgs_edge_mask_args *a, void *stream) {
     return LVDGS_OK;
 }
 
-size_t lvdgs_frame_summary_scratch_bytes(void) { return summary_state_bytes(); }
+size_t lvdgs_frame_summary_scratch_bytes(void) { return summary_layout(nullptr, nullptr); }
 
 int lvdgs_frame_summary(const lvdgs_frame_summary_args *a, void *stream) {
     hipStream_t s = (hipStream_t)stream;
@@ -293,17 +303,16 @@ int lvdgs_frame_summary(const lvdgs_frame_summary_args *a, void *stream) {
         for (int r = 0; r < a->num_rows; r++)
             if (!a->rows[r]) { set_error("frame summary: visibility row %d is NULL", r); return LVDGS_E_INVALID; }
     }
-    if (a->scratch_bytes < summary_state_bytes()) { set_error("frame summary: scratch too small"); return LVDGS_E_INVALID; }
     SummaryParams S{};
+    const size_t state_bytes = summary_layout(&S, a->scratch);
+    if (a->scratch_bytes < state_bytes) { set_error("frame summary: scratch too small"); return LVDGS_E_INVALID; }
     S.P = a->num_pixels; S.N = a->num_gaussians; S.R = a->num_rows;
     S.seq = a->seq; S.bar = a->opacity_bar;
     S.depth = a->depth; S.opacity = a->opacity; S.mask = a->mask; S.count_mask = a->count_mask;
     S.n_touched = a->n_touched;
     for (int r = 0; r < S.R; r++) S.rows[r] = a->rows[r];
-    S.st = reinterpret_cast<SelectState *>(a->scratch);
-    S.cnt = reinterpret_cast<SummaryCounters *>(reinterpret_cast<char *>(a->scratch) + align256(sizeof(SelectState)));
     if (int e = host_block_address(a->host_state, "frame summary", &S.host)) return e;
-    if (int e = check_hip(hipMemsetAsync(a->scratch, 0, summary_state_bytes(), s), "frame summary: clearing the state")) return e;
+    if (int e = check_hip(hipMemsetAsync(a->scratch, 0, state_bytes, s), "frame summary: clearing the state")) return e;
     if (int e = launch_select(DepthSource{S.depth, S.opacity, S.mask, S.bar}, S.P, S.st, -1, "summary_median", s)) return e;
     {
         ProfScope ps("summary_counts", s);

@@ -227,7 +227,7 @@ extern "C" {
 
 size_t lvdgs_map_edit_scratch_bytes(int32_t num_gaussians) {
     if (num_gaussians < 0) return 0;
-    return edit_layout(num_gaussians).bytes;
+    return edit_layout(num_gaussians, nullptr, nullptr);
 }
 
 int lvdgs_map_edit_plan(const lvdgs_map_edit_plan_args *a, void *stream) {
@@ -245,11 +245,9 @@ int lvdgs_map_edit_plan(const lvdgs_map_edit_plan_args *a, void *stream) {
     P.thr = a->grad_threshold; P.dense_extent = a->dense_extent; P.min_opacity = a->min_opacity;
     P.max_screen = a->max_screen_size; P.world_extent = a->world_extent;
     P.src = a->src; P.kind = a->kind; P.noise_row = a->noise_row;
-    const EditLayout L = edit_layout(P.N);
-    char *base = reinterpret_cast<char *>(a->scratch);
-    P.code = reinterpret_cast<uint8_t *>(base + L.code);
-    P.counts = reinterpret_cast<uint32_t *>(base + L.counts);
-    P.totals = reinterpret_cast<uint32_t *>(base + L.totals);
+    EditScratch w;
+    edit_layout(P.N, &w, a->scratch);
+    P.code = w.code; P.counts = w.counts; P.totals = w.totals;
     if (int e = host_block_address(a->host_state, "map edit plan", &P.host)) return e;
     P.host_words = (int64_t)(a->host_bytes / sizeof(int32_t));
     if (P.blocks) {

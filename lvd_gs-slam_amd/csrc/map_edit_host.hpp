@@ -1,10 +1,11 @@
-// The pure-host half of the map edit (map_edit.hip): argument validation, the column-table checks and the scratch layout arithmetic.
+// The pure-host half of the map edit (map_edit.hip): argument validation, the column-table checks and the scratch layout.
 // No HIP call and no device code in here, so a stand-alone host program can compile and run it (with a set_error of its own).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/lvdgs.h"
+#include "carve.hpp"
 #include "spans.hpp"
 
 namespace lvdgs {
@@ -17,15 +18,13 @@ constexpr int EDIT_COUNTERS = 5;        // per span: KEEP rows, CLONE rows, surv
 constexpr int EDIT_SEGMENTS = 4;        // the first four place rows (the write pass scans them); the fifth is only counted
 
 // scratch: [code: one byte per source row][counts: EDIT_MAX_BLOCKS x EDIT_COUNTERS words][totals: 8 words]
-struct EditLayout { size_t code, counts, totals, bytes; };
-inline size_t edit_align256(size_t x) { return (x + 255) & ~size_t(255); }
-inline EditLayout edit_layout(int32_t N) {
-    EditLayout L;
-    L.code = 0;
-    L.counts = edit_align256((size_t)(N > 0 ? N : 0));
-    L.totals = L.counts + edit_align256((size_t)EDIT_MAX_BLOCKS * EDIT_COUNTERS * sizeof(uint32_t));
-    L.bytes = L.totals + 256;
-    return L;
+struct EditScratch { uint8_t *code; uint32_t *counts, *totals; };
+inline size_t edit_layout(int32_t N, EditScratch *v, void *base) {
+    Carver<EditScratch> c(v, base);
+    c(c.v.code, (size_t)(N > 0 ? N : 0));
+    c(c.v.counts, (size_t)EDIT_MAX_BLOCKS * EDIT_COUNTERS);
+    c.bytes(c.v.totals, 256);
+    return c.off;
 }
 
 // the spans of a plan over N rows (spans.hpp)
@@ -63,7 +62,7 @@ inline int edit_check_plan(const lvdgs_map_edit_plan_args *a) {
             set_error("map edit plan: grad_accum / denom / scaling / opacity is NULL"); return LVDGS_E_INVALID;
         }
     }
-    if (a->scratch_bytes < edit_layout(N).bytes) { set_error("map edit plan: scratch too small"); return LVDGS_E_INVALID; }
+    if (a->scratch_bytes < edit_layout(N, nullptr, nullptr)) { set_error("map edit plan: scratch too small"); return LVDGS_E_INVALID; }
     return LVDGS_OK;
 }
 

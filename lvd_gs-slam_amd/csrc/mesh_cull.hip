@@ -174,28 +174,15 @@ __global__ void cull_publish_kernel(CullParams P) {
     seal_host_block(w, LVDGS_MESH_CULL_SEQ, (int32_t)P.seq);
 }
 
-// the scratch: used (V bytes), keep (F bytes), newindex (V words), vcount, fcount (words), totals
-struct CullLayout { size_t used, keep, newindex, vcount, fcount, totals, bytes; };
-CullLayout cull_layout(size_t V, size_t F) {
-    CullLayout L{};
-    size_t at = 0;
-    L.used = at; at += align256(V ? V : 1);
-    L.keep = at; at += align256(F ? F : 1);
-    L.newindex = at; at += align256((V ? V : 1) * sizeof(int32_t));
-    L.vcount = at; at += align256(MC_MAX_BLOCKS * sizeof(uint32_t));
-    L.fcount = at; at += align256(MC_MAX_BLOCKS * sizeof(uint32_t));
-    L.totals = at; at += 256;
-    L.bytes = at;
-    return L;
-}
-
-bool count_ok(int64_t n) { return n >= 0 && n <= (int64_t)INT32_MAX; }
-
-struct ByteRange { const char *name; const void *p; size_t bytes; };
-bool overlap(const ByteRange &a, const ByteRange &b) {
-    if (!a.p || !b.p || !a.bytes || !b.bytes) return false;
-    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
-    return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
+size_t cull_layout(size_t V, size_t F, CullParams *P, void *base) {
+    Carver<CullParams> c(P, base);
+    c(c.v.used, V ? V : 1);
+    c(c.v.keep, F ? F : 1);
+    c(c.v.newindex, V ? V : 1);
+    c(c.v.vcount, MC_MAX_BLOCKS);
+    c(c.v.fcount, MC_MAX_BLOCKS);
+    c.bytes(c.v.totals, 256);
+    return c.off;
 }
 
 }  // namespace
@@ -217,13 +204,9 @@ int lvdgs_mesh_visibility(const lvdgs_mesh_visibility_args *a, void *stream) {
     if (a->num_vertices > 0 && (!a->vertices || !a->seen)) { set_error("%s: vertices / seen is NULL", name); return LVDGS_E_INVALID; }
     if (a->count > 0 && !a->views) { set_error("%s: view list is NULL", name); return LVDGS_E_INVALID; }
     VisParams P{};
-    for (int v = 0; v < a->count; v++) {   // (tsdf_pack_views refuses a view without depth: the checks are this call's own)
+    for (int v = 0; v < a->count; v++) {   // (tsdf_pack_views refuses a view without depth: not this call)
         const lvdgs_tsdf_view *w = a->views[v];
-        if (!w) { set_error("%s: view %d is NULL", name, v); return LVDGS_E_INVALID; }
-        if (w->width < 1 || w->height < 1 || (int64_t)w->width * w->height > INT32_MAX) {
-            set_error("%s: view %d: image size %dx%d", name, v, w->width, w->height); return LVDGS_E_RANGE;
-        }
-        if (!w->R || !w->T) { set_error("%s: view %d: R / T is NULL", name, v); return LVDGS_E_INVALID; }
+        if (int e = check_view(name, v, w, false)) return e;
         P.v[v] = TsdfView{w->width, w->height, w->fx, w->fy, w->cx, w->cy, w->depth_min, w->depth_trunc, w->R, w->T, w->depth, nullptr,
                           w->depth ? w->mask : nullptr};
     }
@@ -239,7 +222,7 @@ int lvdgs_mesh_visibility(const lvdgs_mesh_visibility_args *a, void *stream) {
 
 size_t lvdgs_mesh_cull_scratch_bytes(int64_t num_vertices, int64_t num_faces) {
     if (!count_ok(num_vertices) || !count_ok(num_faces)) return 0;
-    return cull_layout((size_t)num_vertices, (size_t)num_faces).bytes;
+    return cull_layout((size_t)num_vertices, (size_t)num_faces, nullptr, nullptr);
 }
 
 int lvdgs_mesh_cull(const lvdgs_mesh_cull_args *a, void *stream) {
@@ -260,31 +243,19 @@ int lvdgs_mesh_cull(const lvdgs_mesh_cull_args *a, void *stream) {
     if (F > 0 && (!a->faces || !a->out_faces)) { set_error("%s: faces / out_faces is NULL", name); return LVDGS_E_INVALID; }
     if (!a->host_state || !a->scratch) { set_error("%s: host_state / scratch is NULL", name); return LVDGS_E_INVALID; }
     if (a->out_colors && !a->vertex_colors) { set_error("%s: out_colors asked for without vertex_colors", name); return LVDGS_E_INVALID; }
-    const CullLayout L = cull_layout(V, F);
-    if (a->scratch_bytes < L.bytes) { set_error("%s: scratch too small", name); return LVDGS_E_INVALID; }
+    CullParams P{};
+    const size_t need = cull_layout(V, F, &P, a->scratch);
+    if (a->scratch_bytes < need) { set_error("%s: scratch too small", name); return LVDGS_E_INVALID; }
     if ((uintptr_t)a->scratch & 3u) { set_error("%s: scratch must be 4-byte aligned", name); return LVDGS_E_INVALID; }
     const ByteRange in[] = {{"vertices", a->vertices, V * 12}, {"vertex_colors", a->vertex_colors, V * 12}, {"faces", a->faces, F * 12},
-                            {"seen", a->seen, V}, {"scratch", a->scratch, L.bytes}};
+                            {"seen", a->seen, V}, {"scratch", a->scratch, need}};
     const ByteRange out[] = {{"out_vertices", a->out_vertices, V * 12}, {"out_colors", a->out_colors, V * 12}, {"out_faces", a->out_faces, F * 12},
                              {"vertex_origin", a->vertex_origin, V * 4}, {"face_origin", a->face_origin, F * 4}};
-    for (size_t o = 0; o < sizeof(out) / sizeof(out[0]); o++) {
-        for (const ByteRange &i : in)
-            if (overlap(out[o], i)) { set_error("%s: %s overlaps %s", name, out[o].name, i.name); return LVDGS_E_INVALID; }
-        for (size_t q = 0; q < o; q++)
-            if (overlap(out[o], out[q])) { set_error("%s: %s overlaps %s", name, out[o].name, out[q].name); return LVDGS_E_INVALID; }
-    }
-    CullParams P{};
+    if (int e = check_no_overlap(name, in, sizeof(in) / sizeof(in[0]), out, sizeof(out) / sizeof(out[0]))) return e;
     P.V = (uint32_t)V; P.F = (uint32_t)F; P.any = a->face_rule == LVDGS_MESH_CULL_ANY; P.seq = a->seq;
     P.vertices = a->vertices; P.vcolors = a->vertex_colors; P.faces = a->faces; P.seen = a->seen;
     P.out_vertices = a->out_vertices; P.out_colors = a->out_colors; P.out_faces = a->out_faces;
     P.vertex_origin = a->vertex_origin; P.face_origin = a->face_origin;
-    char *base = reinterpret_cast<char *>(a->scratch);
-    P.used = reinterpret_cast<uint8_t *>(base + L.used);
-    P.keep = reinterpret_cast<uint8_t *>(base + L.keep);
-    P.newindex = reinterpret_cast<int32_t *>(base + L.newindex);
-    P.vcount = reinterpret_cast<uint32_t *>(base + L.vcount);
-    P.fcount = reinterpret_cast<uint32_t *>(base + L.fcount);
-    P.totals = reinterpret_cast<uint32_t *>(base + L.totals);
     if (int e = host_block_address(a->host_state, name, &P.host)) return e;
     const Spans vs = make_spans(a->num_vertices, MC_THREADS, MC_MAX_BLOCKS, MC_THREADS), fs = make_spans(a->num_faces, MC_THREADS, MC_MAX_BLOCKS, MC_THREADS);
     P.vspan = vs.span; P.fspan = fs.span;

@@ -178,22 +178,6 @@ __global__ void __launch_bounds__(MD_THREADS) mesh_depth_resolve_kernel(MdParams
     }
 }
 
-bool md_count_ok(int64_t n) { return n >= 0 && n <= (int64_t)INT32_MAX; }
-
-struct MdRange { char name[24]; const void *p; size_t bytes; };
-bool md_overlap(const MdRange &a, const MdRange &b) {
-    if (!a.p || !b.p || !a.bytes || !b.bytes) return false;
-    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
-    return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
-}
-MdRange md_range(const char *what, int v, const void *p, size_t bytes) {
-    MdRange r{};
-    if (v < 0) snprintf(r.name, sizeof(r.name), "%s", what);
-    else snprintf(r.name, sizeof(r.name), "%s[%d]", what, v);
-    r.p = p; r.bytes = bytes;
-    return r;
-}
-
 }  // namespace
 }  // namespace lvdgs
 
@@ -212,7 +196,7 @@ int lvdgs_mesh_depth(const lvdgs_mesh_depth_args *a, void *stream) {
     if (a->num_vertices < 0 || a->num_faces < 0) {
         set_error("%s: negative count (%lld vertices, %lld faces)", name, (long long)a->num_vertices, (long long)a->num_faces); return LVDGS_E_INVALID;
     }
-    if (!md_count_ok(a->num_vertices) || !md_count_ok(a->num_faces)) {
+    if (!count_ok(a->num_vertices) || !count_ok(a->num_faces)) {
         set_error("%s: a count above 2^31 - 1 (%lld vertices, %lld faces)", name, (long long)a->num_vertices, (long long)a->num_faces);
         return LVDGS_E_INVALID;
     }
@@ -226,11 +210,7 @@ int lvdgs_mesh_depth(const lvdgs_mesh_depth_args *a, void *stream) {
     size_t total = 0;
     for (int v = 0; v < a->count; v++) {
         const lvdgs_tsdf_view *w = a->views[v];
-        if (!w) { set_error("%s: view %d is NULL", name, v); return LVDGS_E_INVALID; }
-        if (w->width < 1 || w->height < 1 || (int64_t)w->width * w->height > INT32_MAX) {
-            set_error("%s: view %d: image size %dx%d", name, v, w->width, w->height); return LVDGS_E_RANGE;
-        }
-        if (!w->R || !w->T) { set_error("%s: view %d: R / T is NULL", name, v); return LVDGS_E_INVALID; }
+        if (int e = check_view(name, v, w, false)) return e;
         if (!a->depth[v]) { set_error("%s: view %d: depth output is NULL", name, v); return LVDGS_E_INVALID; }
         if (a->face_index && !a->face_index[v]) { set_error("%s: view %d: face_index output is NULL", name, v); return LVDGS_E_INVALID; }
         P.v[v] = MdView{w->width, w->height, w->fx, w->fy, w->cx, w->cy, fmaxf(w->depth_min, 0.0f), w->depth_trunc, w->R, w->T,
@@ -243,26 +223,21 @@ int lvdgs_mesh_depth(const lvdgs_mesh_depth_args *a, void *stream) {
     if (a->scratch_bytes < need) { set_error("%s: scratch too small (%zu bytes, %zu needed)", name, a->scratch_bytes, need); return LVDGS_E_INVALID; }
     if ((uintptr_t)a->scratch & 7u) { set_error("%s: scratch must be 8-byte aligned", name); return LVDGS_E_INVALID; }
     {   // an output may overlap no input, not the scratch and no other output
-        MdRange in[3 + 2 * LVDGS_TSDF_MAX_VIEWS], out[2 * LVDGS_TSDF_MAX_VIEWS];
+        ByteRange in[3 + 2 * LVDGS_TSDF_MAX_VIEWS], out[2 * LVDGS_TSDF_MAX_VIEWS];
         int ni = 0, no = 0;
-        in[ni++] = md_range("vertices", -1, a->vertices, V * 12);
-        in[ni++] = md_range("faces", -1, a->faces, F * 12);
-        in[ni++] = md_range("scratch", -1, a->scratch, need);
+        in[ni++] = byte_range("vertices", -1, a->vertices, V * 12);
+        in[ni++] = byte_range("faces", -1, a->faces, F * 12);
+        in[ni++] = byte_range("scratch", -1, a->scratch, need);
         for (int v = 0; v < a->count; v++) {
-            in[ni++] = md_range("R", v, P.v[v].R, 36);
-            in[ni++] = md_range("T", v, P.v[v].T, 12);
+            in[ni++] = byte_range("R", v, P.v[v].R, 36);
+            in[ni++] = byte_range("T", v, P.v[v].T, 12);
         }
         for (int v = 0; v < a->count; v++) {
             const size_t bytes = (size_t)P.v[v].W * (size_t)P.v[v].H * 4;
-            out[no++] = md_range("depth", v, P.v[v].depth, bytes);
-            if (P.v[v].fidx) out[no++] = md_range("face_index", v, P.v[v].fidx, bytes);
+            out[no++] = byte_range("depth", v, P.v[v].depth, bytes);
+            if (P.v[v].fidx) out[no++] = byte_range("face_index", v, P.v[v].fidx, bytes);
         }
-        for (int o = 0; o < no; o++) {
-            for (int i = 0; i < ni; i++)
-                if (md_overlap(out[o], in[i])) { set_error("%s: %s overlaps %s", name, out[o].name, in[i].name); return LVDGS_E_INVALID; }
-            for (int q = 0; q < o; q++)
-                if (md_overlap(out[o], out[q])) { set_error("%s: %s overlaps %s", name, out[o].name, out[q].name); return LVDGS_E_INVALID; }
-        }
+        if (int e = check_no_overlap(name, in, ni, out, no)) return e;
     }
     unsigned long long *keys = reinterpret_cast<unsigned long long *>(a->scratch);
     unsigned most = 1;

@@ -18,6 +18,7 @@
 
 #include "common.hpp"
 #include "device_utils.hpp"
+#include "host_checks.hpp"
 #include "spans.hpp"
 
 namespace lvdgs {
@@ -167,17 +168,14 @@ __global__ void __launch_bounds__(ME_THREADS) sample_points_kernel(SampleParams 
     }
 }
 
-struct SampleLayout { size_t area, bmax, bsum, bcount, totals, bytes; };
-SampleLayout sample_layout(size_t F) {
-    SampleLayout L{};
-    size_t at = 0;
-    L.area = at; at += align256(F * sizeof(double));
-    L.bmax = at; at += align256(ME_MAX_BLOCKS * sizeof(double));
-    L.bsum = at; at += align256(ME_MAX_BLOCKS * sizeof(u64));
-    L.bcount = at; at += align256(ME_MAX_BLOCKS * sizeof(uint32_t));
-    L.totals = at; at += 256;
-    L.bytes = at;
-    return L;
+size_t sample_layout(size_t F, SampleParams *P, void *base) {
+    Carver<SampleParams> c(P, base);
+    c(c.v.area, F);
+    c(c.v.bmax, ME_MAX_BLOCKS);
+    c(c.v.bsum, ME_MAX_BLOCKS);
+    c(c.v.bcount, ME_MAX_BLOCKS);
+    c.bytes(c.v.totals, 256);
+    return c.off;
 }
 
 // ---------------------------------------------------------------- the search ----
@@ -578,26 +576,22 @@ __global__ void __launch_bounds__(ME_THREADS) cloud_finish_kernel(CloudParams P,
 
 int64_t cell_budget(int64_t N) { return N < 64 ? 64 : N > CD_MAX_CELLS ? CD_MAX_CELLS : N; }
 
-struct CloudLayout { size_t grid, box, cnt[2], start[2], spansum, sorted[2], d2, idx, sum, bytes; };
-CloudLayout cloud_layout(size_t M, size_t N) {
-    CloudLayout L{};
+// (d2 and idx have their place in the scratch whether or not the caller brings arrays of their own)
+size_t cloud_layout(size_t M, size_t N, CloudParams *P, void *base) {
+    Carver<CloudParams> c(P, base);
     const size_t cells = (size_t)cell_budget((int64_t)N) + 1;
-    size_t at = 0;
-    L.grid = at; at += align256(sizeof(Grid));
-    L.box = at; at += align256(CD_BOX_BLOCKS * sizeof(BoxPartial));
-    for (int w = 0; w < 2; w++) { L.cnt[w] = at; at += align256(cells * sizeof(uint32_t)); }
-    for (int w = 0; w < 2; w++) { L.start[w] = at; at += align256(cells * sizeof(uint32_t)); }
-    L.spansum = at; at += align256(2 * CD_SCAN_BLOCKS * sizeof(uint32_t));
-    L.sorted[0] = at; at += align256((N ? N : 1) * sizeof(float4));
-    L.sorted[1] = at; at += align256((M ? M : 1) * sizeof(float4));
-    L.d2 = at; at += align256((M ? M : 1) * sizeof(float));
-    L.idx = at; at += align256((M ? M : 1) * sizeof(int32_t));
-    L.sum = at; at += align256(CD_SUM_BLOCKS * sizeof(SumPartial));
-    L.bytes = at;
-    return L;
+    c(c.v.grid, 1);
+    c(c.v.box, CD_BOX_BLOCKS);
+    for (int w = 0; w < 2; w++) c(c.v.cnt[w], cells);
+    for (int w = 0; w < 2; w++) c(c.v.start[w], cells);
+    c(c.v.spansum, 2 * CD_SCAN_BLOCKS);
+    c(c.v.sorted[0], N ? N : 1);
+    c(c.v.sorted[1], M ? M : 1);
+    c(c.v.d2, M ? M : 1);
+    c(c.v.idx, M ? M : 1);
+    c(c.v.sum, CD_SUM_BLOCKS);
+    return c.off;
 }
-
-bool count_ok(int64_t n) { return n >= 0 && n <= (int64_t)INT32_MAX; }
 
 }  // namespace
 }  // namespace lvdgs
@@ -608,7 +602,7 @@ extern "C" {
 
 size_t lvdgs_mesh_sample_scratch_bytes(int64_t num_faces) {
     if (num_faces < 1 || num_faces > (int64_t)INT32_MAX) return 0;
-    return sample_layout((size_t)num_faces).bytes;
+    return sample_layout((size_t)num_faces, nullptr, nullptr);
 }
 
 int lvdgs_mesh_sample(const lvdgs_mesh_sample_args *a, void *stream) {
@@ -629,22 +623,15 @@ int lvdgs_mesh_sample(const lvdgs_mesh_sample_args *a, void *stream) {
         set_error("%s: vertices / faces / points / info / scratch is NULL", name); return LVDGS_E_INVALID;
     }
     if (a->colors && !a->vertex_colors) { set_error("%s: colors asked for without vertex_colors", name); return LVDGS_E_INVALID; }
-    const SampleLayout L = sample_layout((size_t)a->num_faces);
-    if (a->scratch_bytes < L.bytes) { set_error("%s: scratch too small", name); return LVDGS_E_INVALID; }
+    SampleParams P{};
+    if (a->scratch_bytes < sample_layout((size_t)a->num_faces, &P, a->scratch)) { set_error("%s: scratch too small", name); return LVDGS_E_INVALID; }
     if (((uintptr_t)a->scratch | (uintptr_t)a->info) & 7u) { set_error("%s: scratch and info must be 8-byte aligned", name); return LVDGS_E_INVALID; }
     if (a->num_samples == 0) return LVDGS_OK;
-    SampleParams P{};
     P.V = (uint32_t)a->num_vertices; P.F = (uint32_t)a->num_faces; P.n = (uint32_t)a->num_samples;
     P.seed_lo = (uint32_t)a->seed; P.seed_hi = (uint32_t)(a->seed >> 32);
     P.vertices = a->vertices; P.vcolors = a->vertex_colors; P.faces = a->faces;
     P.points = a->points; P.colors = a->colors; P.face_index = a->face_index;
     P.info = reinterpret_cast<lvdgs_mesh_sample_info *>(a->info);
-    char *base = reinterpret_cast<char *>(a->scratch);
-    P.area = reinterpret_cast<double *>(base + L.area);
-    P.bmax = reinterpret_cast<double *>(base + L.bmax);
-    P.bsum = reinterpret_cast<u64 *>(base + L.bsum);
-    P.bcount = reinterpret_cast<uint32_t *>(base + L.bcount);
-    P.totals = reinterpret_cast<u64 *>(base + L.totals);
     const Spans spans = make_spans(a->num_faces, ME_THREADS, ME_MAX_BLOCKS, ME_THREADS);
     const int blocks = spans.blocks;
     P.span = spans.span;
@@ -679,7 +666,7 @@ int lvdgs_mesh_sample(const lvdgs_mesh_sample_args *a, void *stream) {
 
 size_t lvdgs_cloud_distance_scratch_bytes(int64_t num_queries, int64_t num_reference) {
     if (!count_ok(num_queries) || !count_ok(num_reference)) return 0;
-    return cloud_layout((size_t)num_queries, (size_t)num_reference).bytes;
+    return cloud_layout((size_t)num_queries, (size_t)num_reference, nullptr, nullptr);
 }
 
 int lvdgs_cloud_distance(const lvdgs_cloud_distance_args *a, void *stream) {
@@ -703,31 +690,20 @@ int lvdgs_cloud_distance(const lvdgs_cloud_distance_args *a, void *stream) {
     if (!a->queries || !a->out_row || !a->scratch || (!a->reference && a->num_reference > 0)) {
         set_error("%s: queries / reference / out_row / scratch is NULL", name); return LVDGS_E_INVALID;
     }
-    const CloudLayout L = cloud_layout((size_t)a->num_queries, (size_t)a->num_reference);
-    if (a->scratch_bytes < L.bytes) { set_error("%s: scratch too small", name); return LVDGS_E_INVALID; }
+    CloudParams P{};
+    if (a->scratch_bytes < cloud_layout((size_t)a->num_queries, (size_t)a->num_reference, &P, a->scratch)) { set_error("%s: scratch too small", name); return LVDGS_E_INVALID; }
     if (((uintptr_t)a->scratch & 15u) || ((uintptr_t)a->out_row & 7u)) {
         set_error("%s: scratch must be 16-byte and out_row 8-byte aligned", name); return LVDGS_E_INVALID;
     }
     if (a->num_queries == 0) return LVDGS_OK;
-    CloudParams P{};
     P.M = (uint32_t)a->num_queries; P.N = (uint32_t)a->num_reference;
     P.queries = a->queries; P.reference = a->reference;
     P.ppc = a->points_per_cell; P.nthr = a->num_thresholds;
     P.budget = cell_budget(a->num_reference);
     for (int t = 0; t < LVDGS_CLOUD_DISTANCE_MAX_THRESHOLDS; t++) P.thr[t] = t < a->num_thresholds ? a->thresholds[t] : 0.f;
-    char *base = reinterpret_cast<char *>(a->scratch);
-    P.d2 = a->d2 ? a->d2 : reinterpret_cast<float *>(base + L.d2);
-    P.idx = a->idx ? a->idx : reinterpret_cast<int32_t *>(base + L.idx);
+    if (a->d2) P.d2 = a->d2;
+    if (a->idx) P.idx = a->idx;
     P.row = reinterpret_cast<lvdgs_cloud_distance_row *>(a->out_row);
-    P.grid = reinterpret_cast<Grid *>(base + L.grid);
-    P.box = reinterpret_cast<BoxPartial *>(base + L.box);
-    for (int w = 0; w < 2; w++) {
-        P.cnt[w] = reinterpret_cast<uint32_t *>(base + L.cnt[w]);
-        P.start[w] = reinterpret_cast<uint32_t *>(base + L.start[w]);
-        P.sorted[w] = reinterpret_cast<float4 *>(base + L.sorted[w]);
-    }
-    P.spansum = reinterpret_cast<uint32_t *>(base + L.spansum);
-    P.sum = reinterpret_cast<SumPartial *>(base + L.sum);
     hipStream_t s = (hipStream_t)stream;
     const dim3 block(ME_THREADS);
     auto blocks_for = [](uint32_t n, int most) { const int64_t b = ((int64_t)n + ME_THREADS - 1) / ME_THREADS; return (unsigned)(b < 1 ? 1 : b > most ? most : b); };

@@ -413,16 +413,32 @@ struct FlowScratch {
     float *img[2], *R[2], *M[2], *flow_odd;
 };
 size_t flow_scratch_layout(int W, int H, FlowScratch *v, void *base) {
-    char *p = reinterpret_cast<char *>(base);
-    size_t off = 0;
+    Carver<FlowScratch> c(v, base);
     const size_t px = (size_t)W * H;
-    auto take = [&](size_t floats) { float *q = reinterpret_cast<float *>(p + off); off += align256(floats * sizeof(float)); return q; };
-    float *q;
-    for (int i = 0; i < 2; i++) { q = take(px); if (v) v->img[i] = q; }
-    for (int i = 0; i < 2; i++) { q = take(5 * px); if (v) v->R[i] = q; }
-    for (int i = 0; i < 2; i++) { q = take(5 * px); if (v) v->M[i] = q; }
-    q = take(2 * px); if (v) v->flow_odd = q;
-    return off;
+    for (int i = 0; i < 2; i++) c(c.v.img[i], px);
+    for (int i = 0; i < 2; i++) c(c.v.R[i], 5 * px);
+    for (int i = 0; i < 2; i++) c(c.v.M[i], 5 * px);
+    c(c.v.flow_odd, 2 * px);
+    return c.off;
+}
+
+// the motion mask's state: the header, then the grey plane of the stored frame
+struct MmState { MmHeader *header; uint8_t *stored; };
+size_t mm_state_layout(int W, int H, MmState *v, void *base) {
+    Carver<MmState> c(v, base);
+    c.bytes(c.v.header, MM_HEADER_BYTES); c(c.v.stored, (size_t)W * H);
+    return c.off;
+}
+
+// ... and its scratch: the flow's scratch (run_flow lays it out), then a flow buffer (used when the caller wants none), the grey plane
+// of the call's image, one bit plane
+struct MmScratch { void *flow_scratch; float *flow; uint8_t *cur; uint64_t *plane; };
+size_t mm_scratch_layout(int W, int H, MmScratch *v, void *base) {
+    Carver<MmScratch> c(v, base);
+    const size_t px = (size_t)W * H;
+    c.bytes(c.v.flow_scratch, flow_scratch_layout(W, H, nullptr, nullptr));
+    c(c.v.flow, 2 * px); c(c.v.cur, px); c.bytes(c.v.plane, plane_bytes(W, H));
+    return c.off;
 }
 
 int check_flow_params(const char *who, int width, int height, const lvdgs_farneback_params &p, Level *levels, int *num_levels) {
@@ -538,8 +554,6 @@ int run_flow(int W, int H, const lvdgs_farneback_params &p, const Level *levels,
     return LVDGS_OK;
 }
 
-size_t mm_plane_offset(int W, int H) { return align256(flow_scratch_layout(W, H, nullptr, nullptr)); }
-
 }  // namespace
 }  // namespace lvdgs
 
@@ -565,14 +579,12 @@ int lvdgs_farneback_flow(const lvdgs_farneback_args *a, void *stream) {
 
 size_t lvdgs_motion_mask_state_bytes(int32_t width, int32_t height) {
     if (!size_ok(width, height)) return 0;
-    return MM_HEADER_BYTES + align256((size_t)width * height);
+    return mm_state_layout(width, height, nullptr, nullptr);
 }
 
-// the flow's scratch, then a flow buffer (used when the caller wants none), the grey plane of the call's image, one bit plane
 size_t lvdgs_motion_mask_scratch_bytes(int32_t width, int32_t height) {
     if (!size_ok(width, height)) return 0;
-    const size_t px = (size_t)width * height;
-    return mm_plane_offset(width, height) + align256(2 * px * sizeof(float)) + align256(px) + align256(plane_bytes(width, height));
+    return mm_scratch_layout(width, height, nullptr, nullptr);
 }
 
 int lvdgs_motion_mask(const lvdgs_motion_mask_args *a, void *stream) {
@@ -595,8 +607,9 @@ int lvdgs_motion_mask(const lvdgs_motion_mask_args *a, void *stream) {
     if (!observe && a->scratch_bytes < lvdgs_motion_mask_scratch_bytes(a->width, a->height)) { set_error("motion mask: scratch too small"); return LVDGS_E_INVALID; }
     const int W = a->width, H = a->height;
     const int64_t px = (int64_t)W * H;
-    MmHeader *header = reinterpret_cast<MmHeader *>(a->state);
-    uint8_t *stored = reinterpret_cast<uint8_t *>(a->state) + MM_HEADER_BYTES;
+    MmState st;
+    mm_state_layout(W, H, &st, a->state);
+    MmHeader *header = st.header; uint8_t *stored = st.stored;
     const int grey_blocks = (int)min((int64_t)cdiv(px, OF_THREADS), (int64_t)4 * MM_MAX_BLOCKS);
     if (observe) {
         ProfScope ps("of_grey", s);
@@ -604,22 +617,23 @@ int lvdgs_motion_mask(const lvdgs_motion_mask_args *a, void *stream) {
         LVDGS_LAUNCH_CHECK("of_grey", 0, s);
         return LVDGS_OK;
     }
-    char *base = reinterpret_cast<char *>(a->scratch) + mm_plane_offset(W, H);
-    float *flow = a->flow ? a->flow : reinterpret_cast<float *>(base);
-    uint8_t *cur = reinterpret_cast<uint8_t *>(base + align256(2 * (size_t)px * sizeof(float)));
+    MmScratch w;
+    mm_scratch_layout(W, H, &w, a->scratch);
+    float *flow = a->flow ? a->flow : w.flow;
+    uint8_t *cur = w.cur;
     MmParams P{};
     P.W = W; P.H = H; P.wpr = words_per_row(W); P.words = (int64_t)H * P.wpr;
     P.levels = num_levels; P.dilate_k = a->dilate_kernel; P.advance = (a->mode & LVDGS_MOTION_ADVANCE) != 0;
     P.thr = (float)a->motion_threshold;
     P.flow = flow; P.cur = cur; P.mask = a->mask; P.info = a->info; P.header = header; P.stored = stored;
-    P.plane = reinterpret_cast<uint64_t *>(cur + align256((size_t)px));
+    P.plane = w.plane;
     if (int e = check_hip(hipMemsetAsync(a->info, 0, LVDGS_MOTION_INFO_WORDS * sizeof(int32_t), s), "motion mask: clearing info")) return e;
     {
         ProfScope ps("of_grey", s);
         hipLaunchKernelGGL(of_grey_kernel, dim3(grey_blocks), dim3(OF_THREADS), 0, s, a->image, px, cur, (MmHeader *)nullptr, W, H);
         LVDGS_LAUNCH_CHECK("of_grey", 0, s);
     }
-    if (int e = run_flow(W, H, a->params, levels, num_levels, stored, cur, flow, a->scratch, s)) return e;
+    if (int e = run_flow(W, H, a->params, levels, num_levels, stored, cur, flow, w.flow_scratch, s)) return e;
     const int wave_blocks = (int)min((int64_t)cdiv(P.words, OF_ROWS), (int64_t)MM_MAX_BLOCKS);
     {
         ProfScope ps("of_moving", s);

@@ -381,6 +381,16 @@ __global__ void __launch_bounds__(PNP_THREADS) pnp_hypotheses_kernel(PnpParams P
     if (tid == 0) write_state(P, LVDGS_PNP_OK, valid, inliers, win, win_count, LVDGS_PNP_FAIL_NONE, T);
 }
 
+// the scratch: the header, five columns of a double per match, a record per hypothesis
+size_t pnp_layout(int num_matches, int hypotheses, PnpParams *P, void *base) {
+    Carver<PnpParams> c(P, base);
+    const size_t m = num_matches > 0 ? (size_t)num_matches : 0, h = hypotheses > 0 ? (size_t)hypotheses : 0;
+    c(c.v.hdr, 1);
+    c(c.v.px, m); c(c.v.py, m); c(c.v.pz, m); c(c.v.qu, m); c(c.v.qv, m);
+    c(c.v.recs, h);
+    return c.off;
+}
+
 }  // namespace
 }  // namespace lvdgs
 
@@ -388,10 +398,7 @@ using namespace lvdgs;
 
 extern "C" {
 
-size_t lvdgs_pnp_scratch_bytes(int32_t num_matches, int32_t hypotheses) {
-    const size_t m = num_matches > 0 ? (size_t)num_matches : 0, h = hypotheses > 0 ? (size_t)hypotheses : 0;
-    return align256(sizeof(PnpHeader)) + 5 * align256(m * sizeof(double)) + align256(h * sizeof(HypRec));
-}
+size_t lvdgs_pnp_scratch_bytes(int32_t num_matches, int32_t hypotheses) { return pnp_layout(num_matches, hypotheses, nullptr, nullptr); }
 
 int lvdgs_pnp_ransac(const lvdgs_pnp_args *a, void *stream) {
     hipStream_t s = (hipStream_t)stream;
@@ -407,21 +414,14 @@ int lvdgs_pnp_ransac(const lvdgs_pnp_args *a, void *stream) {
     if (!a->depth || !a->inlier_mask || !a->host_state || !a->scratch || (a->num_matches > 0 && (!a->matches_im1 || !a->matches_im2))) {
         set_error("pnp: depth / matches_im1 / matches_im2 / inlier_mask / host_state / scratch is NULL"); return LVDGS_E_INVALID;
     }
-    if (a->scratch_bytes < lvdgs_pnp_scratch_bytes(a->num_matches, a->hypotheses)) { set_error("pnp: scratch too small"); return LVDGS_E_INVALID; }
     PnpParams P{};
+    if (a->scratch_bytes < pnp_layout(a->num_matches, a->hypotheses, &P, a->scratch)) { set_error("pnp: scratch too small"); return LVDGS_E_INVALID; }
     P.W = a->width; P.H = a->height; P.M = a->num_matches; P.hyp = a->hypotheses; P.min_inliers = a->min_inliers;
     P.seed = a->seed;
     P.fx = a->fx; P.fy = a->fy; P.cx = a->cx; P.cy = a->cy;
     P.k1 = a->dist[0]; P.k2 = a->dist[1]; P.p1 = a->dist[2]; P.p2 = a->dist[3]; P.k3 = a->dist[4];
     P.thr2 = a->reproj_error * a->reproj_error;
     P.depth = a->depth; P.m1 = a->matches_im1; P.m2 = a->matches_im2; P.mask = a->inlier_mask;
-    char *base = reinterpret_cast<char *>(a->scratch);
-    P.hdr = reinterpret_cast<PnpHeader *>(base);
-    base += align256(sizeof(PnpHeader));
-    const size_t col = align256((size_t)P.M * sizeof(double));
-    P.px = reinterpret_cast<double *>(base); P.py = reinterpret_cast<double *>(base + col); P.pz = reinterpret_cast<double *>(base + 2 * col);
-    P.qu = reinterpret_cast<double *>(base + 3 * col); P.qv = reinterpret_cast<double *>(base + 4 * col);
-    P.recs = reinterpret_cast<HypRec *>(base + 5 * col);
     if (int e = host_block_address(a->host_state, "pnp", &P.host_state)) return e;
     {
         ProfScope ps("pnp_gather", s);

@@ -281,6 +281,16 @@ __global__ void __launch_bounds__(RNN_ONE) rnn_final_kernel(RnnParams P, int n2)
 
 int seeds_along(int n, int S) { return n > S / 2 ? (n - S / 2 + S - 1) / S : 0; }
 
+// the scratch: the header, seven columns of a word per seed, a key per seed
+size_t rnn_layout(size_t seeds, RnnParams *P, void *base) {
+    Carver<RnnParams> c(P, base);
+    c(c.v.hdr, 1);
+    c(c.v.xy1, seeds); c(c.v.xy2, seeds); c(c.v.old1, seeds); c(c.v.old2, seeds); c(c.v.retired, seeds);
+    c(c.v.act[0], seeds); c(c.v.act[1], seeds);
+    c(c.v.keys, seeds);
+    return c.off;
+}
+
 }  // namespace
 }  // namespace lvdgs
 
@@ -290,8 +300,7 @@ extern "C" {
 
 size_t lvdgs_recip_nn_scratch_bytes(int32_t width1, int32_t height1, int32_t subsample) {
     if (width1 <= 0 || height1 <= 0 || subsample <= 0) return 0;
-    const size_t n = (size_t)seeds_along(width1, subsample) * (size_t)seeds_along(height1, subsample);
-    return align256(sizeof(RnnHeader)) + 7 * align256(n * sizeof(int32_t)) + align256(n * sizeof(u64));
+    return rnn_layout((size_t)seeds_along(width1, subsample) * (size_t)seeds_along(height1, subsample), nullptr, nullptr);
 }
 
 int lvdgs_reciprocal_nn(const lvdgs_recip_nn_args *a, void *stream) {
@@ -315,19 +324,11 @@ int lvdgs_reciprocal_nn(const lvdgs_recip_nn_args *a, void *stream) {
     if (!a->desc1 || !a->desc2 || !a->matches_im1 || !a->matches_im2 || !a->host_state || !a->scratch) {
         set_error("recip_nn: desc1 / desc2 / matches_im1 / matches_im2 / host_state / scratch is NULL"); return LVDGS_E_INVALID;
     }
-    if (a->scratch_bytes < lvdgs_recip_nn_scratch_bytes(a->width1, a->height1, a->subsample)) { set_error("recip_nn: scratch too small"); return LVDGS_E_INVALID; }
     RnnParams P{};
+    if (a->scratch_bytes < rnn_layout((size_t)seeds, &P, a->scratch)) { set_error("recip_nn: scratch too small"); return LVDGS_E_INVALID; }
     P.W1 = a->width1; P.H1 = a->height1; P.W2 = a->width2; P.H2 = a->height2; P.D = a->dim; P.S = a->subsample;
     P.seeds = (int)seeds; P.seeds_x = sx; P.capacity = a->capacity;
     P.desc1 = a->desc1; P.desc2 = a->desc2; P.m1 = a->matches_im1; P.m2 = a->matches_im2; P.seed_state = a->seed_state;
-    char *base = reinterpret_cast<char *>(a->scratch);
-    P.hdr = reinterpret_cast<RnnHeader *>(base);
-    base += align256(sizeof(RnnHeader));
-    const size_t col = align256((size_t)seeds * sizeof(int32_t));
-    P.xy1 = reinterpret_cast<int32_t *>(base); P.xy2 = reinterpret_cast<int32_t *>(base + col); P.old1 = reinterpret_cast<int32_t *>(base + 2 * col);
-    P.old2 = reinterpret_cast<int32_t *>(base + 3 * col); P.retired = reinterpret_cast<int32_t *>(base + 4 * col);
-    P.act[0] = reinterpret_cast<uint32_t *>(base + 5 * col); P.act[1] = reinterpret_cast<uint32_t *>(base + 6 * col);
-    P.keys = reinterpret_cast<u64 *>(base + 7 * col);
     if (int e = host_block_address(a->host_state, "recip_nn", &P.host_state)) return e;
     int n2 = 2 * RNN_ONE;
     while (n2 < P.seeds) n2 *= 2;

@@ -139,7 +139,12 @@ __global__ void seed_publish_kernel(SeedParams S) {
     seal_host_block(w, LVDGS_SEED_SEQ, (int32_t)S.seq);
 }
 
-size_t seed_state_bytes() { return 2 * align256(sizeof(SelectState)) + align256(SEED_MAX_BLOCKS * sizeof(uint32_t)); }
+// the scratch: the two selections' states, a count per span
+size_t seed_layout(SeedParams *S, void *base) {
+    Carver<SeedParams> c(S, base);
+    c(c.v.st_key, 1); c(c.v.st_median, 1); c(c.v.counts, SEED_MAX_BLOCKS);
+    return c.off;
+}
 
 }  // namespace
 }  // namespace lvdgs
@@ -150,7 +155,7 @@ extern "C" {
 
 size_t lvdgs_seed_scratch_bytes(int32_t width, int32_t height) {
     if (width < 1 || height < 1 || (int64_t)width * height > INT32_MAX) return 0;
-    return seed_state_bytes();
+    return seed_layout(nullptr, nullptr);
 }
 
 int lvdgs_seed_points(const lvdgs_seed_args *a, void *stream) {
@@ -172,8 +177,9 @@ int lvdgs_seed_points(const lvdgs_seed_args *a, void *stream) {
         set_error("seed points: depth / R / T / xyz / host_state / scratch is NULL"); return LVDGS_E_INVALID;
     }
     if (a->image && (!a->rgb || !a->f_dc)) { set_error("seed points: rgb / f_dc is NULL with an image"); return LVDGS_E_INVALID; }
-    if (a->scratch_bytes < seed_state_bytes()) { set_error("seed points: scratch too small"); return LVDGS_E_INVALID; }
     SeedParams S{};
+    const size_t state_bytes = seed_layout(&S, a->scratch);
+    if (a->scratch_bytes < state_bytes) { set_error("seed points: scratch too small"); return LVDGS_E_INVALID; }
     S.W = a->width; S.H = a->height; S.P = P;
     S.capacity = a->capacity; S.want_median = a->want_median != 0;
     S.fx = a->fx; S.fy = a->fy; S.cx = a->cx; S.cy = a->cy; S.trunc = a->depth_trunc;
@@ -181,15 +187,11 @@ int lvdgs_seed_points(const lvdgs_seed_args *a, void *stream) {
     S.seed_lo = (uint32_t)a->seed; S.seed_hi = (uint32_t)(a->seed >> 32); S.seq = a->seq;
     S.image = a->image; S.gain = a->gain; S.offset = a->offset; S.depth = a->depth; S.R = a->R; S.T = a->T;
     S.xyz = a->xyz; S.rgb = a->rgb; S.f_dc = a->f_dc; S.pixel = a->pixel;
-    char *base = reinterpret_cast<char *>(a->scratch);
-    S.st_key = reinterpret_cast<SelectState *>(base);
-    S.st_median = reinterpret_cast<SelectState *>(base + align256(sizeof(SelectState)));
-    S.counts = reinterpret_cast<uint32_t *>(base + 2 * align256(sizeof(SelectState)));
     if (int e = host_block_address(a->host_state, "seed points", &S.host)) return e;
     const Spans spans = make_spans(P, SEED_THREADS, SEED_MAX_BLOCKS, SEED_MIN_SPAN);
     const int blocks = spans.blocks;
     S.span = spans.span;
-    if (int e = check_hip(hipMemsetAsync(a->scratch, 0, seed_state_bytes(), s), "seed points: clearing the state")) return e;
+    if (int e = check_hip(hipMemsetAsync(a->scratch, 0, state_bytes, s), "seed points: clearing the state")) return e;
     if (S.want_median)
         if (int e = launch_select(AllDepthSource{S.depth}, P, S.st_median, select_rank(-1), "seed_median", s)) return e;
     if (int e = launch_select(KeySource{S.depth, S.trunc, S.seed_lo, S.seed_hi}, P, S.st_key, SelectRank{-1, S.inv_downsample}, "seed_threshold", s)) return e;

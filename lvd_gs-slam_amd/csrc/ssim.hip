@@ -415,6 +415,15 @@ void fill_window(float (&win)[SW]) {
     for (int k = 0; k < SW; k++) win[k] = g[k] / sum;
 }
 
+// the masked loss's scratch of one view: the L1 / SSIM partial sums of its 3 planes, then (sum, count) per 32x32 tile for the depth term
+size_t masked_loss_layout(int W, int H, SsimView *v, void *base) {
+    Carver<SsimView> c(v, base);
+    const size_t tiles = (size_t)cdiv(W, ST) * cdiv(H, ST);
+    c(c.v.partial, 3 * tiles * 2);
+    c(c.v.dpart, tiles * 2);
+    return c.off + 256;
+}
+
 }  // namespace
 }  // namespace lvdgs
 
@@ -460,11 +469,7 @@ int lvdgs_ssim_l1(const lvdgs_ssim_args *a, void *stream) {
     return LVDGS_OK;
 }
 
-// scratch of one view: the L1 / SSIM partial sums of its 3 planes, then (sum, count) per 32x32 tile for the depth term
-size_t lvdgs_masked_loss_scratch_bytes(int32_t width, int32_t height) {
-    const size_t tiles = (size_t)cdiv(width, ST) * cdiv(height, ST);
-    return align256(3 * tiles * 2 * sizeof(float)) + align256(tiles * 2 * sizeof(float)) + 256;
-}
+size_t lvdgs_masked_loss_scratch_bytes(int32_t width, int32_t height) { return masked_loss_layout(width, height, nullptr, nullptr); }
 
 int lvdgs_masked_loss_batch(const lvdgs_masked_loss_args *const *views, int32_t count, void *stream) {
     hipStream_t s = (hipStream_t)stream;
@@ -483,17 +488,16 @@ int lvdgs_masked_loss_batch(const lvdgs_masked_loss_args *const *views, int32_t 
             const lvdgs_masked_loss_args *a = views[first + k];
             if (!a || a->width != p.W || a->height != p.H) { set_error("masked loss: view %d is NULL or differs in image size", first + k); return LVDGS_E_INVALID; }
             if (!a->image || !a->gt_image || !a->d_image || !a->out || !a->scratch) { set_error("masked loss: image / gt_image / d_image / out / scratch is NULL"); return LVDGS_E_INVALID; }
-            if (a->scratch_bytes < lvdgs_masked_loss_scratch_bytes(p.W, p.H)) { set_error("masked loss: scratch too small"); return LVDGS_E_INVALID; }
-            if (a->gt_depth && !a->depth) { set_error("masked loss: gt_depth without the rendered depth"); return LVDGS_E_INVALID; }
             SsimView &v = p.v[k];
+            if (a->scratch_bytes < masked_loss_layout(p.W, p.H, &v, a->scratch)) { set_error("masked loss: scratch too small"); return LVDGS_E_INVALID; }
+            if (a->gt_depth && !a->depth) { set_error("masked loss: gt_depth without the rendered depth"); return LVDGS_E_INVALID; }
             v.x = a->image; v.y = a->gt_image; v.keep = a->static_mask; v.bg = a->static_mask ? a->bg : nullptr;
             // d loss / d a = (1 - lambda) d mean|a - b| - lambda d mean SSIM
             v.w_l1 = (float)((1.0 - (double)a->lambda_dssim) / n);
             v.w_ssim = (float)(-(double)a->lambda_dssim / n);
-            v.partial = (float *)a->scratch;
             v.d_x = a->d_image;
             v.depth = a->gt_depth ? a->depth : nullptr; v.gt_depth = a->gt_depth;
-            v.dpart = a->gt_depth ? (float *)((char *)a->scratch + align256(3 * tiles * 2 * sizeof(float))) : nullptr;
+            if (!a->gt_depth) v.dpart = nullptr;
             f.v[k] = MaskedFinishView{(const float2 *)v.partial, (const float2 *)v.dpart, a->out, a->lambda_dssim, a->gt_depth ? a->depth_lambda : 0.f};
         }
         f.nwg = (int)(3 * tiles); f.ntiles = (int)tiles; f.inv_count = (float)(1.0 / n);

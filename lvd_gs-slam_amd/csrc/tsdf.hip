@@ -245,20 +245,16 @@ __global__ void tsdf_publish_kernel(MeshParams M) {
     seal_host_block(w, LVDGS_TSDF_SEQ, (int32_t)M.seq);
 }
 
-// the scratch: flags, edges (n bytes each), cellvert (n words), vcount, fcount (words), fbase (doublewords), totals
-struct MeshLayout { size_t flags, edges, cellvert, vcount, fcount, fbase, totals, bytes; };
-MeshLayout mesh_layout(size_t n) {
-    MeshLayout L{};
-    size_t at = 0;
-    L.flags = at; at += align256(n);
-    L.edges = at; at += align256(n);
-    L.cellvert = at; at += align256(n * sizeof(int32_t));
-    L.vcount = at; at += align256(TSDF_MAX_BLOCKS * sizeof(uint32_t));
-    L.fcount = at; at += align256(TSDF_MAX_BLOCKS * sizeof(uint32_t));
-    L.fbase = at; at += align256(TSDF_MAX_BLOCKS * sizeof(unsigned long long));
-    L.totals = at; at += 256;
-    L.bytes = at;
-    return L;
+size_t mesh_layout(size_t n, MeshParams *M, void *base) {
+    Carver<MeshParams> c(M, base);
+    c(c.v.flags, n);
+    c(c.v.edges, n);
+    c(c.v.cellvert, n);
+    c(c.v.vcount, TSDF_MAX_BLOCKS);
+    c(c.v.fcount, TSDF_MAX_BLOCKS);
+    c(c.v.fbase, TSDF_MAX_BLOCKS);
+    c.bytes(c.v.totals, 256);
+    return c.off;
 }
 
 // dims >= least each and at most 2^31 - 1 samples
@@ -310,7 +306,7 @@ int lvdgs_tsdf_integrate(const lvdgs_tsdf_volume *vol, const lvdgs_tsdf_view *co
 
 size_t lvdgs_tsdf_mesh_scratch_bytes(int32_t nx, int32_t ny, int32_t nz) {
     if (nx < 2 || ny < 2 || nz < 2 || (int64_t)nx * ny > INT32_MAX || (int64_t)nx * ny * nz > INT32_MAX) return 0;
-    return mesh_layout((size_t)nx * ny * nz).bytes;
+    return mesh_layout((size_t)nx * ny * nz, nullptr, nullptr);
 }
 
 int lvdgs_tsdf_mesh(const lvdgs_tsdf_mesh_args *a, void *stream) {
@@ -328,23 +324,14 @@ int lvdgs_tsdf_mesh(const lvdgs_tsdf_mesh_args *a, void *stream) {
     }
     if (a->colors && !vol.r) { set_error("%s: colors asked for, the volume has no colour planes", name); return LVDGS_E_INVALID; }
     const size_t n = (size_t)vol.nx * vol.ny * vol.nz;
-    const MeshLayout L = mesh_layout(n);
-    if (a->scratch_bytes < L.bytes) { set_error("%s: scratch too small", name); return LVDGS_E_INVALID; }
-    if ((uintptr_t)a->scratch & 7u) { set_error("%s: scratch must be 8-byte aligned", name); return LVDGS_E_INVALID; }
     MeshParams M{};
+    if (a->scratch_bytes < mesh_layout(n, &M, a->scratch)) { set_error("%s: scratch too small", name); return LVDGS_E_INVALID; }
+    if ((uintptr_t)a->scratch & 7u) { set_error("%s: scratch must be 8-byte aligned", name); return LVDGS_E_INVALID; }
     M.nx = vol.nx; M.ny = vol.ny; M.nz = vol.nz; M.n = (uint32_t)n;
     M.ox = vol.origin[0]; M.oy = vol.origin[1]; M.oz = vol.origin[2]; M.vs = vol.voxel_size;
     M.tsdf = vol.tsdf; M.weight = vol.weight; M.r = vol.r; M.g = vol.g; M.b = vol.b;
     M.vcap = a->vertex_capacity; M.fcap = a->face_capacity; M.seq = a->seq;
     M.vertices = a->vertices; M.colors = a->colors; M.faces = a->faces;
-    char *base = reinterpret_cast<char *>(a->scratch);
-    M.flags = reinterpret_cast<uint8_t *>(base + L.flags);
-    M.edges = reinterpret_cast<uint8_t *>(base + L.edges);
-    M.cellvert = reinterpret_cast<int32_t *>(base + L.cellvert);
-    M.vcount = reinterpret_cast<uint32_t *>(base + L.vcount);
-    M.fcount = reinterpret_cast<uint32_t *>(base + L.fcount);
-    M.fbase = reinterpret_cast<unsigned long long *>(base + L.fbase);
-    M.totals = reinterpret_cast<unsigned long long *>(base + L.totals);
     if (int e = host_block_address(a->host_state, name, &M.host)) return e;
     const Spans spans = make_spans((int64_t)n, TSDF_THREADS, TSDF_MAX_BLOCKS, TSDF_THREADS);
     const int blocks = spans.blocks;

@@ -468,21 +468,18 @@ __global__ void __launch_bounds__(TB_THREADS) tsdf_blocks_rehash_kernel(BlockVol
 
 // ---------------------------------------------------------------- the host side ----
 
-// the scratch of the mesh call, by rank: rank, nbr, mask, edges, vcount, fcount, fbase, totals
-struct BlocksMeshLayout { size_t rank, nbr, mask, edges, vcount, fcount, fbase, totals, bytes; };
-BlocksMeshLayout blocks_mesh_layout(size_t pool) {
-    BlocksMeshLayout L{};
-    size_t at = 0;
-    L.rank = at; at += align256(pool * sizeof(int32_t));
-    L.nbr = at; at += align256(pool * 27 * sizeof(int32_t));
-    L.mask = at; at += align256(pool * 16 * sizeof(uint32_t));
-    L.edges = at; at += align256(pool * BLOCK_SAMPLES);
-    L.vcount = at; at += align256(pool * sizeof(uint32_t));
-    L.fcount = at; at += align256(pool * sizeof(uint32_t));
-    L.fbase = at; at += align256(pool * sizeof(unsigned long long));
-    L.totals = at; at += 256;
-    L.bytes = at;
-    return L;
+// the scratch of the mesh call (the arrays behind rank: by rank)
+size_t blocks_mesh_layout(size_t pool, BlocksMeshParams *M, void *base) {
+    Carver<BlocksMeshParams> c(M, base);
+    c(c.v.rank, pool);
+    c(c.v.nbr, pool * 27);
+    c(c.v.mask, pool * 16);
+    c(c.v.edges, pool * BLOCK_SAMPLES);
+    c(c.v.vcount, pool);
+    c(c.v.fcount, pool);
+    c(c.v.fbase, pool);
+    c.bytes(c.v.totals, 256);
+    return c.off;
 }
 
 // everything the three calls refuse about the volume itself
@@ -559,7 +556,7 @@ int lvdgs_tsdf_blocks_integrate(const lvdgs_tsdf_blocks *vol, const lvdgs_tsdf_v
 
 size_t lvdgs_tsdf_blocks_mesh_scratch_bytes(int32_t pool_blocks) {
     if (pool_blocks < 1 || pool_blocks > LVDGS_TSDF_BLOCKS_MAX_POOL) return 0;
-    return blocks_mesh_layout((size_t)pool_blocks).bytes;
+    return blocks_mesh_layout((size_t)pool_blocks, nullptr, nullptr);
 }
 
 int lvdgs_tsdf_blocks_mesh(const lvdgs_tsdf_blocks_mesh_args *a, void *stream) {
@@ -575,22 +572,12 @@ int lvdgs_tsdf_blocks_mesh(const lvdgs_tsdf_blocks_mesh_args *a, void *stream) {
     }
     if (a->colors && !a->vol.r) { set_error("%s: colors asked for, the volume has no colour planes", name); return LVDGS_E_INVALID; }
     const size_t pool = (size_t)M.vol.pool;
-    const BlocksMeshLayout L = blocks_mesh_layout(pool);
-    if (a->scratch_bytes < L.bytes) { set_error("%s: scratch too small", name); return LVDGS_E_INVALID; }
+    if (a->scratch_bytes < blocks_mesh_layout(pool, &M, a->scratch)) { set_error("%s: scratch too small", name); return LVDGS_E_INVALID; }
     if ((uintptr_t)a->scratch & 7u) { set_error("%s: scratch must be 8-byte aligned", name); return LVDGS_E_INVALID; }
     M.order = a->order;
     M.vcap = a->vertex_capacity; M.fcap = a->face_capacity; M.seq = a->seq;
     for (int q = 0; q < 3; q++) { M.cell_lo[q] = a->cell_lo[q]; M.cell_hi[q] = a->cell_hi[q]; }
     M.vertices = a->vertices; M.colors = a->colors; M.faces = a->faces;
-    char *base = reinterpret_cast<char *>(a->scratch);
-    M.rank = reinterpret_cast<int32_t *>(base + L.rank);
-    M.nbr = reinterpret_cast<int32_t *>(base + L.nbr);
-    M.mask = reinterpret_cast<uint32_t *>(base + L.mask);
-    M.edges = reinterpret_cast<uint8_t *>(base + L.edges);
-    M.vcount = reinterpret_cast<uint32_t *>(base + L.vcount);
-    M.fcount = reinterpret_cast<uint32_t *>(base + L.fcount);
-    M.fbase = reinterpret_cast<unsigned long long *>(base + L.fbase);
-    M.totals = reinterpret_cast<unsigned long long *>(base + L.totals);
     if (int e = host_block_address(a->host_state, name, &M.host)) return e;
     hipStream_t s = (hipStream_t)stream;
     const dim3 per_block(block_grid(M.vol.pool)), block(TB_THREADS);

@@ -13,6 +13,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "host_checks.hpp"
 
 namespace lvdgs {
 
@@ -319,11 +320,7 @@ inline int tsdf_pack_views(const char *name, const lvdgs_tsdf_view *const *views
     int64_t most = 0;
     for (int v = 0; v < count; v++) {
         const lvdgs_tsdf_view *a = views[v];
-        if (!a) { set_error("%s: view %d is NULL", name, v); return LVDGS_E_INVALID; }
-        if (a->width < 1 || a->height < 1 || (int64_t)a->width * a->height > INT32_MAX) {
-            set_error("%s: view %d: image size %dx%d", name, v, a->width, a->height); return LVDGS_E_RANGE;
-        }
-        if (!a->R || !a->T || !a->depth) { set_error("%s: view %d: R / T / depth is NULL", name, v); return LVDGS_E_INVALID; }
+        if (int e = check_view(name, v, a, true)) return e;
         if (a->image && !coloured) { set_error("%s: view %d has an image, the volume no colour planes", name, v); return LVDGS_E_INVALID; }
         out[v] = TsdfView{a->width, a->height, a->fx, a->fy, a->cx, a->cy, a->depth_min, a->depth_trunc, a->R, a->T, a->depth, a->image, a->mask};
         most = std::max(most, (int64_t)a->width * a->height);

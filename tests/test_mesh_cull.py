@@ -14,6 +14,7 @@ import pytest
 
 import mesh_cull_oracle as orc
 import mesh_eval_oracle as meo
+import refusal_recording
 from lvdgs import _lib
 
 P256, P4096 = C.c_void_p(256), C.c_void_p(4096)      # never dereferenced: every call that gets them is refused before a launch
@@ -55,11 +56,12 @@ def _visibility_args(blocks=(), **kw):
     ([_view(height=-3)], {}, "E_RANGE", b"image size"),
     ([_view(width=65536, height=32768)], {}, "E_RANGE", b"image size"),
 ])
-def test_mesh_visibility_refusals(views, change, status, words):
+def test_mesh_visibility_refusals(views, change, status, words, request):
     L = _lib.lib()
     a, keep = _visibility_args(views, **change)
     assert L.lvdgs_mesh_visibility(C.byref(a), None) == getattr(_lib, status)
     assert b"mesh visibility" in L.lvdgs_last_error() and words in L.lvdgs_last_error(), L.lvdgs_last_error()
+    refusal_recording.check(request.node.module.__name__ + "::" + request.node.name, getattr(_lib, status), L.lvdgs_last_error())
 
 
 def test_mesh_visibility_refuses_null_and_accepts_nothing_to_do():
@@ -105,10 +107,11 @@ def _cull_args(**kw):
     (dict(out_colors=_at(0x14000 + 60)), b"out_colors overlaps out_vertices"),
     (dict(out_faces=_at(0x100000 + 512)), b"out_faces overlaps scratch"),
 ])
-def test_mesh_cull_refusals(change, words):
+def test_mesh_cull_refusals(change, words, request):
     L = _lib.lib()
     assert L.lvdgs_mesh_cull(C.byref(_cull_args(**change)), None) == _lib.E_INVALID
     assert b"mesh cull" in L.lvdgs_last_error() and words in L.lvdgs_last_error(), L.lvdgs_last_error()
+    refusal_recording.check(request.node.module.__name__ + "::" + request.node.name, _lib.E_INVALID, L.lvdgs_last_error())
 
 
 def test_mesh_cull_refuses_null_and_neighbours_are_no_overlap():

@@ -16,6 +16,7 @@ import pytest
 import mesh_cull_oracle as mco
 import mesh_depth_oracle as orc
 import mesh_eval_oracle as meo
+import refusal_recording
 from lvdgs import _lib
 
 F32 = np.float32
@@ -83,7 +84,7 @@ def _args(views=None, depth=None, faces=None, **kw):
     (dict(face_list=[0x80000, 0x80000 - PLANE + 1]), "E_INVALID", b"face_index[1] overlaps face_index[0]"),
     (dict(depth_list=[0x100000 + 2 * 64 * 48 * 8 - 1, 0x34000]), "E_INVALID", b"depth[0] overlaps scratch"),
 ])
-def test_mesh_depth_refusals(build, status, words):
+def test_mesh_depth_refusals(build, status, words, request):
     L = _lib.lib()
     build = dict(build)
     a, keep = _args(views=build.pop("view_list", None), depth=build.pop("depth_list", None), faces=build.pop("face_list", None))
@@ -91,6 +92,7 @@ def test_mesh_depth_refusals(build, status, words):
         setattr(a, "faces" if k == "faces_ptr" else k, x)
     assert L.lvdgs_mesh_depth(C.byref(a), None) == getattr(_lib, status)
     assert b"mesh depth" in L.lvdgs_last_error() and words in L.lvdgs_last_error(), L.lvdgs_last_error()
+    refusal_recording.check(request.node.module.__name__ + "::" + request.node.name, getattr(_lib, status), L.lvdgs_last_error())
 
 
 def test_mesh_depth_refuses_null_accepts_nothing_to_do_and_neighbours_are_no_overlap():

@@ -19,6 +19,7 @@ import pytest
 import torch
 
 import mesh_eval_oracle as orc
+import refusal_recording
 from lvdgs import _abi, _lib
 
 U = 2.0 ** -24
@@ -66,10 +67,11 @@ def _distance_args(**kw):
     (dict(num_faces=0), b"no faces"), (dict(scratch_bytes=1000), b"scratch too small"), (dict(scratch=C.c_void_p(260)), b"aligned"),
     (dict(info=C.c_void_p(260)), b"aligned"),
 ])
-def test_mesh_sample_refusals(change, words):
+def test_mesh_sample_refusals(change, words, request):
     L = _lib.lib()
     assert L.lvdgs_mesh_sample(C.byref(_sample_args(**change)), None) == _lib.E_INVALID
     assert b"mesh sample" in L.lvdgs_last_error() and words in L.lvdgs_last_error(), L.lvdgs_last_error()
+    refusal_recording.check(request.node.module.__name__ + "::" + request.node.name, _lib.E_INVALID, L.lvdgs_last_error())
 
 
 def test_mesh_sample_refuses_null_and_accepts_nothing_to_do():
@@ -85,10 +87,11 @@ def test_mesh_sample_refuses_null_and_accepts_nothing_to_do():
     (dict(num_thresholds=5), b"5 thresholds, at most 4"), (dict(num_thresholds=-1), b"thresholds, at most 4"),
     (dict(scratch_bytes=1000), b"scratch too small"), (dict(scratch=C.c_void_p(264)), b"aligned"), (dict(out_row=C.c_void_p(260)), b"aligned"),
 ])
-def test_cloud_distance_refusals(change, words):
+def test_cloud_distance_refusals(change, words, request):
     L = _lib.lib()
     assert L.lvdgs_cloud_distance(C.byref(_distance_args(**change)), None) == _lib.E_INVALID
     assert b"cloud distance" in L.lvdgs_last_error() and words in L.lvdgs_last_error(), L.lvdgs_last_error()
+    refusal_recording.check(request.node.module.__name__ + "::" + request.node.name, _lib.E_INVALID, L.lvdgs_last_error())
 
 
 @pytest.mark.parametrize("bad", [-0.5, math.nan, math.inf, -math.inf])

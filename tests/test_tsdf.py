@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 import torch
 
+import refusal_recording
 import tsdf_cases as cases
 import tsdf_oracle as orc
 from lvdgs import _lib
@@ -34,6 +35,7 @@ def test_the_module_and_the_exports_exist():
 
 
 FAKE = 4096      # a non-NULL pointer value; every call below is refused before a launch, so it is never dereferenced
+_recorded = None      # of the refusal test that is running: files what _integrate and _mesh see (refusal_recording.Numbered)
 
 
 def _volume(color=False, **kw):
@@ -56,10 +58,13 @@ def _integrate(vol, views, count=None):
     L = _lib.lib()
     ptrs = (C.POINTER(_lib.TsdfViewArgs) * max(len(views), 1))(*[C.pointer(v) if v is not None else None for v in views])
     status = L.lvdgs_tsdf_integrate(C.byref(vol) if vol is not None else None, ptrs, len(views) if count is None else count, None)
+    _recorded(status, L.lvdgs_last_error())
     return status, L.lvdgs_last_error().decode()
 
 
 def test_integrate_refusals_without_gpu():
+    global _recorded
+    _recorded = refusal_recording.Numbered("test_tsdf::integrate")
     L = _lib.lib()
     inf, nan = float("inf"), float("nan")
     ok = _view()
@@ -107,10 +112,14 @@ def _mesh_args(vol=None, **kw):
 
 def _mesh(a):
     L = _lib.lib()
-    return L.lvdgs_tsdf_mesh(C.byref(a) if a is not None else None, None), L.lvdgs_last_error().decode()
+    status = L.lvdgs_tsdf_mesh(C.byref(a) if a is not None else None, None)
+    _recorded(status, L.lvdgs_last_error())
+    return status, L.lvdgs_last_error().decode()
 
 
 def test_mesh_refusals_without_gpu():
+    global _recorded
+    _recorded = refusal_recording.Numbered("test_tsdf::mesh")
     L = _lib.lib()
     assert _mesh(None) == (_lib.E_INVALID, "tsdf mesh: args is NULL")
     for plane in ("tsdf", "weight"):

@@ -14,6 +14,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import refusal_recording
 import tsdf_blocks_oracle as borc
 import tsdf_cases as cases
 import tsdf_oracle as orc
@@ -21,6 +22,7 @@ from lvdgs import _lib, tsdf_blocks
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAKE = 4096      # a non-NULL pointer value; every call below is refused before a launch, so it is never dereferenced
+_recorded = None      # of the refusal test that is running: files what _integrate and _mesh see (refusal_recording.Numbered)
 
 
 # ---------------------------------------------------------------- the ABI ----
@@ -61,6 +63,7 @@ def _integrate(vol, views, count=None):
     L = _lib.lib()
     ptrs = (C.POINTER(_lib.TsdfViewArgs) * max(len(views), 1))(*[C.pointer(v) if v is not None else None for v in views])
     status = L.lvdgs_tsdf_blocks_integrate(None if vol is None else C.byref(vol), ptrs, len(views) if count is None else count, None)
+    _recorded(status, L.lvdgs_last_error())
     return status, L.lvdgs_last_error().decode()
 
 
@@ -82,6 +85,8 @@ VOLUME_REFUSALS = [
 
 
 def test_integrate_refusals_without_gpu():
+    global _recorded
+    _recorded = refusal_recording.Numbered("test_tsdf_blocks::integrate")
     L = _lib.lib()
     ok = _view()
     assert _integrate(None, [ok]) == (_lib.E_INVALID, "tsdf blocks integrate: volume is NULL")
@@ -117,16 +122,20 @@ def _mesh_args(vol=None, **kw):
 def _mesh(a):
     L = _lib.lib()
     status = L.lvdgs_tsdf_blocks_mesh(None if a is None else C.byref(a), None)
+    _recorded(status, L.lvdgs_last_error())
     return status, L.lvdgs_last_error().decode()
 
 
 def test_mesh_and_rehash_refusals_without_gpu():
+    global _recorded
+    _recorded = refusal_recording.Numbered("test_tsdf_blocks::mesh")
     L = _lib.lib()
     assert _mesh(None) == (_lib.E_INVALID, "tsdf blocks mesh: args is NULL")
     for kw, want, words in VOLUME_REFUSALS:
         status, msg = _mesh(_mesh_args(vol=_volume(**kw)))
         assert status == want and words in msg, (kw, status, msg)
         assert L.lvdgs_tsdf_blocks_rehash(C.byref(_volume(**kw)), None) == want and words.encode() in L.lvdgs_last_error()
+        _recorded(want, L.lvdgs_last_error())
     assert L.lvdgs_tsdf_blocks_rehash(None, None) == _lib.E_INVALID
     for kw in (dict(vertex_capacity=-1), dict(face_capacity=-1)):
         status, msg = _mesh(_mesh_args(**kw))

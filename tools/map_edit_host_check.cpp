@@ -1,5 +1,5 @@
 // Stand-alone host program: the pure-host half of the map edit (csrc/map_edit_host.hpp: argument validation, the column-table checks,
-// the scratch layout arithmetic) for a run under AddressSanitizer and UBSan on the CPU:
+// the scratch layout) for a run under AddressSanitizer and UBSan on the CPU:
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Ilvd_gs-slam_amd/csrc tools/map_edit_host_check.cpp -o tools/map_edit_host_check && tools/map_edit_host_check
 #include <cstdarg>
 #include <cstdio>
@@ -12,9 +12,12 @@ int main() {
     int fails = 0;
 #define EXPECT(cond) do { if (!(cond)) { printf("FAIL line %d: %s (%s)\n", __LINE__, #cond, last); fails++; } } while (0)
     for (int32_t N : {0, 1, 255, 256, 257, 70001, 262144, 262145, 262400, 262401, 2000000, INT32_MAX}) {
-        EditLayout L = edit_layout(N);
-        EXPECT(L.counts >= (size_t)N && L.counts % 256 == 0 && L.totals % 256 == 0 && L.bytes > L.totals);
-        EXPECT(L.totals - L.counts >= (size_t)EDIT_MAX_BLOCKS * EDIT_COUNTERS * 4);
+        char *const base = (char *)4096;   // offsets: carved from a fake base, never dereferenced
+        EditScratch w;
+        const size_t bytes = edit_layout(N, &w, base), counts = (char *)w.counts - base, totals = (char *)w.totals - base;
+        EXPECT((char *)w.code == base && bytes == edit_layout(N, nullptr, nullptr));
+        EXPECT(counts >= (size_t)N && counts % 256 == 0 && totals % 256 == 0 && bytes > totals);
+        EXPECT(totals - counts >= (size_t)EDIT_MAX_BLOCKS * EDIT_COUNTERS * 4);
         const Spans s = edit_spans(N);
         const int blocks = s.blocks; const int64_t span = s.span;
         EXPECT(blocks >= 0 && blocks <= EDIT_MAX_BLOCKS && span >= EDIT_THREADS && span % EDIT_THREADS == 0 && (int64_t)blocks * span >= N);
@@ -30,7 +33,7 @@ int main() {
     EXPECT(edit_check_plan(nullptr) == LVDGS_E_INVALID);
     a.mode = LVDGS_EDIT_PRUNE; a.num_gaussians = 100; a.capacity = 100;
     a.src = (int32_t *)mem.data(); a.kind = (uint8_t *)mem.data(); a.noise_row = (int32_t *)mem.data(); a.host_state = (int32_t *)mem.data();
-    a.scratch = mem.data(); a.remove = (uint8_t *)mem.data(); a.host_bytes = 4 * (LVDGS_EDIT_HOST_SRC + 200); a.scratch_bytes = edit_layout(100).bytes;
+    a.scratch = mem.data(); a.remove = (uint8_t *)mem.data(); a.host_bytes = 4 * (LVDGS_EDIT_HOST_SRC + 200); a.scratch_bytes = edit_layout(100, nullptr, nullptr);
     EXPECT(edit_check_plan(&a) == LVDGS_OK);
     a.scratch_bytes--; EXPECT(edit_check_plan(&a) == LVDGS_E_INVALID); a.scratch_bytes++;
     a.host_bytes -= 4; EXPECT(edit_check_plan(&a) == LVDGS_E_RANGE); a.host_bytes += 4;
