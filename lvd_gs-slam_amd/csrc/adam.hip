@@ -84,9 +84,7 @@ extern "C" int lvdgs_adam_step(const lvdgs_adam_tensor *tensors, int32_t count, 
         if (t.numel > longest) longest = t.numel;
     }
     if (n == 0) return LVDGS_OK;
-    ProfScope ps("adam_step", s);
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((longest + 1023) / 1024), (unsigned)n), dim3(256), 0, s, P);
-    LVDGS_LAUNCH_CHECK("adam_step", 0, s);
+    if (int e = launch("adam_step", 0, s, adam_kernel, dim3((unsigned)((longest + 1023) / 1024), (unsigned)n), dim3(256), 0, P)) return e;
     return LVDGS_OK;
 }
 
@@ -179,8 +177,8 @@ extern "C" int lvdgs_isotropic_reg(int32_t N, const float *raw_scales, float *gr
     if (scratch_bytes < lvdgs_isotropic_scratch_bytes(N)) { set_error("isotropic reg: scratch too small"); return LVDGS_E_INVALID; }
     const int nblk = cdiv(N, 256);
     const float scale = weight / (3.f * (float)N);
-    { ProfScope ps("isotropic_reg", s); hipLaunchKernelGGL(isotropic_kernel, dim3(nblk), dim3(256), 0, s, N, raw_scales, grad_raw_scales, scale, (float *)scratch); LVDGS_LAUNCH_CHECK("isotropic_reg", 0, s); }
-    { ProfScope ps("isotropic_finish", s); hipLaunchKernelGGL(isotropic_finish_kernel, dim3(1), dim3(256), 0, s, nblk, (const float *)scratch, scale, loss); LVDGS_LAUNCH_CHECK("isotropic_finish", 0, s); }
+    if (int e = launch("isotropic_reg", 0, s, isotropic_kernel, dim3(nblk), dim3(256), 0, N, raw_scales, grad_raw_scales, scale, (float *)scratch)) return e;
+    if (int e = launch("isotropic_finish", 0, s, isotropic_finish_kernel, dim3(1), dim3(256), 0, nblk, (const float *)scratch, scale, loss)) return e;
     return LVDGS_OK;
 }
 
@@ -191,9 +189,8 @@ extern "C" int lvdgs_view_stats(int32_t N, const int32_t *radii, const int32_t *
         set_error("view stats: a required pointer is NULL"); return LVDGS_E_INVALID;
     }
     if (N == 0) return LVDGS_OK;
-    ProfScope ps("view_stats", s);
-    hipLaunchKernelGGL(view_stats_kernel, dim3(cdiv(N, 256)), dim3(256), 0, s, ViewStats{N, radii, n_touched, viewspace_grad, radii_max, norm_sum, vis_count, touched_row, split_xy});
-    LVDGS_LAUNCH_CHECK("view_stats", 0, s);
+    const ViewStats v{N, radii, n_touched, viewspace_grad, radii_max, norm_sum, vis_count, touched_row, split_xy};
+    if (int e = launch("view_stats", 0, s, view_stats_kernel, dim3(cdiv(N, 256)), dim3(256), 0, v)) return e;
     return LVDGS_OK;
 }
 
@@ -204,9 +201,7 @@ extern "C" int lvdgs_map_stats_apply(int32_t N, const int32_t *radii_max, const 
         set_error("map stats apply: a required pointer is NULL"); return LVDGS_E_INVALID;
     }
     if (N == 0) return LVDGS_OK;
-    ProfScope ps("map_stats_apply", s);
-    hipLaunchKernelGGL(map_stats_apply_kernel, dim3(cdiv(N, 256)), dim3(256), 0, s, N, radii_max, norm_sum, vis_count, split_xy, n_split, max_radii2D,
-                       xyz_gradient_accum, denom);
-    LVDGS_LAUNCH_CHECK("map_stats_apply", 0, s);
+    if (int e = launch("map_stats_apply", 0, s, map_stats_apply_kernel, dim3(cdiv(N, 256)), dim3(256), 0, N, radii_max, norm_sum, vis_count, split_xy, n_split,
+            max_radii2D, xyz_gradient_accum, denom)) return e;
     return LVDGS_OK;
 }

@@ -310,12 +310,9 @@ int launch_rope2d(void *tokens, const int64_t *positions, int B, int N, int H, i
     const int Q = D / 4;
     // 4-wide accesses need every (token, head, half, i) address aligned to 4 elements
     const bool wide = (Q % 4 == 0) && (sb % 4 == 0) && (sn % 4 == 0) && (sh % 4 == 0) && ((uintptr_t)tokens % (4 * sizeof(T)) == 0);
-    ProfScope ps("rope2d", s);
     const dim3 grid((unsigned)((int64_t)B * N)), block(256);
     const size_t lds = (size_t)D * 2 * sizeof(float);
-    if (wide) hipLaunchKernelGGL((rope2d_kernel<T, 4>), grid, block, lds, s, (T *)tokens, positions, N, H, D, sb, sn, sh, base, fwd);
-    else hipLaunchKernelGGL((rope2d_kernel<T, 1>), grid, block, lds, s, (T *)tokens, positions, N, H, D, sb, sn, sh, base, fwd);
-    LVDGS_LAUNCH_CHECK("rope2d", 0, s);
+    if (int e = launch("rope2d", 0, s, wide ? rope2d_kernel<T, 4> : rope2d_kernel<T, 1>, grid, block, lds, (T *)tokens, positions, N, H, D, sb, sn, sh, base, fwd)) return e;
     return LVDGS_OK;
 }
 
@@ -336,23 +333,16 @@ int lvdgs_dist2_knn3(int32_t P, const float *points, float *mean_dist2, void *sc
     KnnScratch w;
     knn_layout(P, &w, scratch);
     const int box = knn_box_size(P), nbox = cdiv(P, box);
-    { ProfScope ps("knn_bounds", s); hipLaunchKernelGGL(knn_bounds_kernel, dim3(KNN_BOUNDS_BLOCKS), dim3(256), 0, s, P, points, w.bounds); LVDGS_LAUNCH_CHECK("knn_bounds", 0, s); }
-    { ProfScope ps("knn_morton", s); hipLaunchKernelGGL(knn_morton_kernel, dim3(cdiv(P, 256)), dim3(256), 0, s, P, points, w.bounds, KNN_BOUNDS_BLOCKS, w.keys[0], w.vals[0]); LVDGS_LAUNCH_CHECK("knn_morton", 0, s); }
+    if (int e = launch("knn_bounds", 0, s, knn_bounds_kernel, dim3(KNN_BOUNDS_BLOCKS), dim3(256), 0, P, points, w.bounds)) return e;
+    if (int e = launch("knn_morton", 0, s, knn_morton_kernel, dim3(cdiv(P, 256)), dim3(256), 0, P, points, w.bounds, KNN_BOUNDS_BLOCKS, w.keys[0], w.vals[0])) return e;
     bool in_a = true;
     if (int e = radix_sort_pairs(w.keys[0], w.vals[0], w.keys[1], w.vals[1], P, 30, w.hist, w.totals, &in_a, 0, s)) return e;
     const uint32_t *order = in_a ? w.vals[0] : w.vals[1];
-    {
-        ProfScope ps("knn_boxes", s);
-        if (box == KNN_BOX_SMALL) hipLaunchKernelGGL(knn_boxes_kernel<KNN_BOX_SMALL>, dim3(nbox), dim3(KNN_BOX_SMALL), 0, s, P, points, order, w.box_lo, w.box_hi);
-        else hipLaunchKernelGGL(knn_boxes_kernel<KNN_BOX_LARGE>, dim3(nbox), dim3(KNN_BOX_LARGE), 0, s, P, points, order, w.box_lo, w.box_hi);
-        LVDGS_LAUNCH_CHECK("knn_boxes", 0, s);
-    }
-    {
-        ProfScope ps("knn_search", s);
-        if (box == KNN_BOX_SMALL) hipLaunchKernelGGL(knn_search_kernel<KNN_BOX_SMALL>, dim3(nbox), dim3(KNN_BOX_SMALL), 0, s, P, nbox, points, order, w.box_lo, w.box_hi, mean_dist2);
-        else hipLaunchKernelGGL(knn_search_kernel<KNN_BOX_LARGE>, dim3(nbox), dim3(KNN_BOX_LARGE), 0, s, P, nbox, points, order, w.box_lo, w.box_hi, mean_dist2);
-        LVDGS_LAUNCH_CHECK("knn_search", 0, s);
-    }
+    const bool small = box == KNN_BOX_SMALL;
+    const dim3 block(small ? KNN_BOX_SMALL : KNN_BOX_LARGE);   // the size the chosen instantiation is built for
+    if (int e = launch("knn_boxes", 0, s, small ? knn_boxes_kernel<KNN_BOX_SMALL> : knn_boxes_kernel<KNN_BOX_LARGE>, dim3(nbox), block, 0, P, points, order, w.box_lo, w.box_hi)) return e;
+    if (int e = launch("knn_search", 0, s, small ? knn_search_kernel<KNN_BOX_SMALL> : knn_search_kernel<KNN_BOX_LARGE>, dim3(nbox), block, 0, P, nbox, points, order, w.box_lo,
+            w.box_hi, mean_dist2)) return e;
     return LVDGS_OK;
 }
 

@@ -642,15 +642,12 @@ int launch_group_count(const lvdgs_args &a, const GeomView &g, const ImageView &
     const size_t lds = (size_t)t.T * sizeof(uint32_t);
     static unsigned char done[GROUP_SHAPES][16];
     ProfScope ps("group_count", s);
-    if (int e = group_dispatch(group_shape_for(N), [&](auto threads_, auto owners_, auto per_, int d) {
-            constexpr int THREADS = decltype(threads_)::value, OWNERS = decltype(owners_)::value, PER = decltype(per_)::value;
-            if (int e = allow_dynamic_lds(reinterpret_cast<const void *>(&count_pairs_kernel<THREADS, OWNERS, PER>), GROUP_MAX_TILES * 4, done[d])) return e;
-            hipLaunchKernelGGL((count_pairs_kernel<THREADS, OWNERS, PER>), dim3(nchunks), dim3(THREADS), lds, s, N, t.gx, t.T, (const uint4 *)g.rect, w.group_hist,
-                               a.n_touched, im.long_count);
-            return (int)LVDGS_OK;
-        })) return e;
-    LVDGS_LAUNCH_CHECK("group_count", a.debug, s);
-    return LVDGS_OK;
+    return group_dispatch(group_shape_for(N), [&](auto threads_, auto owners_, auto per_, int d) {
+        constexpr int THREADS = decltype(threads_)::value, OWNERS = decltype(owners_)::value, PER = decltype(per_)::value;
+        if (int e = allow_dynamic_lds(reinterpret_cast<const void *>(&count_pairs_kernel<THREADS, OWNERS, PER>), GROUP_MAX_TILES * 4, done[d])) return e;
+        return launch_checked("group_count", a.debug, s, count_pairs_kernel<THREADS, OWNERS, PER>, dim3(nchunks), dim3(THREADS), lds, N, t.gx, t.T, (const uint4 *)g.rect,
+                              w.group_hist, a.n_touched, im.long_count);
+    });
 }
 
 // colscan + tilescan: tile ranges, the pair count (total_out, may be null), the tile sort's queue, the tile order
@@ -662,13 +659,13 @@ static bool scan_rides_in_scatter(const lvdgs_args &a, int N, int T) {
     return LVDGS_SCAN_IN_SCATTER != 0 && (threads == 512 || threads == 1024) && cdiv(T, threads) <= SCAN_IN_SCATTER_RUN;
 }
 
-// launch(R): the column scan's build for nchunks matrix rows -- as many waves per workgroup as leave every wave at most 16 (then 32) rows to hold in registers
+// f(R): the column scan's build for nchunks matrix rows -- as many waves per workgroup as leave every wave at most 16 (then 32) rows to hold in registers
 template <typename F>
-static void colscan_dispatch(int nchunks, F &&launch) {
-    if (nchunks <= 8 * 16) launch(template_int<8>{});
-    else if (nchunks <= 16 * 16) launch(template_int<16>{});
-    else if (nchunks <= 32 * 16) launch(template_int<32>{});
-    else launch(template_int<0>{});
+static int colscan_dispatch(int nchunks, F &&f) {
+    if (nchunks <= 8 * 16) return f(template_int<8>{});
+    if (nchunks <= 16 * 16) return f(template_int<16>{});
+    if (nchunks <= 32 * 16) return f(template_int<32>{});
+    return f(template_int<0>{});
 }
 
 // The tile scan's arguments for a call's tile grid (the rows of its band) and for its super-tile grid
@@ -697,24 +694,23 @@ int launch_group_scan(const lvdgs_args &a, const ImageView &im, const RenderScra
     if (super_tiles_in_use(a)) {
         // two-level grouping: the super-tile grid's count matrix (launch_super_count has run) is scanned in the same two launches
         const SuperView &sv = w.super;
-        colscan_dispatch(nchunks, [&](auto R) {
-            hipLaunchKernelGGL(group_colscan_pair_kernel<decltype(R)::value>, dim3(wg_tiles, 2), dim3(1024), 0, s, t.T, t.Ts, nchunks, w.group_hist, w.group_totals, sv.hist, sv.totals);
-        });
+        if (int e = colscan_dispatch(nchunks, [&](auto R) {
+                return launch_checked("group_scan (two-level)", a.debug, s, group_colscan_pair_kernel<decltype(R)::value>, dim3(wg_tiles, 2), dim3(1024), 0, t.T, t.Ts, nchunks,
+                                      w.group_hist, w.group_totals, sv.hist, sv.totals);
+            })) return e;
         // (the super grid's pair count and hints -- longest queued list, queue length -- go to the pinned block of the call's super lists;
         // the later of the two workgroups writes the sequence number the host waits for: the host's verdict takes both pair counts)
         const TileScanArgs ss = super_grid_scan(t, sv, total_out ? total_out + SUPER_TOTAL_WORD : sv.total, report.words ? report.words + PROBE_CALL_SUPER : nullptr);
-        hipLaunchKernelGGL(group_tilescan_pair_kernel, dim3(2), dim3(1024), 0, s, pair_view(t.T, w.group_totals, ts), pair_view(t.Ts, sv.totals, ss), (uint32_t)capacity,
-                           ts.long_limit, sv.long_count + SUPER_ARRIVE_WORD);
-        LVDGS_LAUNCH_CHECK("group_scan (two-level)", a.debug, s);
+        if (int e = launch_checked("group_scan (two-level)", a.debug, s, group_tilescan_pair_kernel, dim3(2), dim3(1024), 0, pair_view(t.T, w.group_totals, ts),
+                pair_view(t.Ts, sv.totals, ss), (uint32_t)capacity, ts.long_limit, sv.long_count + SUPER_ARRIVE_WORD)) return e;
         return LVDGS_OK;
     }
-    colscan_dispatch(nchunks, [&](auto R) {
-        hipLaunchKernelGGL(group_colscan_kernel<decltype(R)::value>, dim3(wg_tiles), dim3(1024), 0, s, t.T, nchunks, w.group_hist, w.group_totals);
-    });
+    if (int e = colscan_dispatch(nchunks, [&](auto R) {
+            return launch_checked("group_scan", a.debug, s, group_colscan_kernel<decltype(R)::value>, dim3(wg_tiles), dim3(1024), 0, t.T, nchunks, w.group_hist, w.group_totals);
+        })) return e;
     if (!scan_rides_in_scatter(a, N, t.T))   // (else: launch_group_scatter's last workgroup)
-        hipLaunchKernelGGL(group_tilescan_kernel, dim3(1), dim3(1024), 0, s, t.T, (const uint32_t *)w.group_totals, (uint32_t)capacity, ts.ranges, ts.total_out, ts.long_limit,
-                           ts.queue_count, ts.queue, ts.tile_order, ts.t_lo, ts.t_hi, ts.order_valid, ts.host_out, ts.host_seq);
-    LVDGS_LAUNCH_CHECK("group_scan", a.debug, s);
+        if (int e = launch_checked("group_scan", a.debug, s, group_tilescan_kernel, dim3(1), dim3(1024), 0, t.T, (const uint32_t *)w.group_totals, (uint32_t)capacity,
+                ts.ranges, ts.total_out, ts.long_limit, ts.queue_count, ts.queue, ts.tile_order, ts.t_lo, ts.t_hi, ts.order_valid, ts.host_out, ts.host_seq)) return e;
     return LVDGS_OK;
 }
 
@@ -733,22 +729,19 @@ int launch_group_scatter(const lvdgs_args &a, const GeomView &g, const ImageView
     TileScanArgs ts{};
     if (scan_rides_in_scatter(a, N, t.T))   // the tile scan as this launch's last workgroup (launch_group_scan has made the tile totals)
         ts = tile_grid_scan(a, t, im, total_out, report.words ? report.words + PROBE_CALL : nullptr, report.seq);
-    auto launch = [&](auto kernel, int d, int threads) {
+    auto scatter = [&](auto kernel, int d, int threads) {
         if (int e = allow_dynamic_lds(reinterpret_cast<const void *>(kernel), GROUP_MAX_TILES * 4, done[d])) return e;
-        hipLaunchKernelGGL(kernel, dim3(nchunks + (ts.ranges ? 1 : 0)), dim3(threads), lds, s, N, gx, T, (const uint4 *)(super ? sv.rect : g.rect),
-                           (const uint32_t *)(super ? sv.hist : w.group_hist), (const uint2 *)(super ? sv.ranges : im.ranges),
-                           ts.ranges ? (const uint32_t *)w.group_totals : nullptr, (uint32_t)capacity, (const uint32_t *)g.depth_bits, keys64,
-                           (const uint32_t *)g.tiles_touched, (const uint32_t *)w.chunk_sums, g.slot_base, pair_valid, ts);
-        return (int)LVDGS_OK;
+        return launch_checked(super ? "super_scatter" : "group_scatter", a.debug, s, kernel, dim3(nchunks + (ts.ranges ? 1 : 0)), dim3(threads), lds, N, gx, T,
+                              (const uint4 *)(super ? sv.rect : g.rect), (const uint32_t *)(super ? sv.hist : w.group_hist), (const uint2 *)(super ? sv.ranges : im.ranges),
+                              ts.ranges ? (const uint32_t *)w.group_totals : nullptr, (uint32_t)capacity, (const uint32_t *)g.depth_bits, keys64,
+                              (const uint32_t *)g.tiles_touched, (const uint32_t *)w.chunk_sums, g.slot_base, pair_valid, ts);
     };
-    if (int e = group_dispatch(group_shape_for(N), [&](auto threads_, auto owners_, auto per_, int d) {
-            constexpr int THREADS = decltype(threads_)::value, OWNERS = decltype(owners_)::value, PER = decltype(per_)::value;
-            if (ts.ranges)   // (scan_rides_in_scatter: every shape launches 512 or 1024 threads there)
-                return slot_scan ? launch(&scatter_pairs_kernel<THREADS, OWNERS, PER, true, true>, 4 * d, THREADS) : launch(&scatter_pairs_kernel<THREADS, OWNERS, PER, false, true>, 4 * d + 1, THREADS);
-            return slot_scan ? launch(&scatter_pairs_kernel<THREADS, OWNERS, PER, true, false>, 4 * d + 2, THREADS) : launch(&scatter_pairs_kernel<THREADS, OWNERS, PER, false, false>, 4 * d + 3, THREADS);
-        })) return e;
-    LVDGS_LAUNCH_CHECK(super ? "super_scatter" : "group_scatter", a.debug, s);
-    return LVDGS_OK;
+    return group_dispatch(group_shape_for(N), [&](auto threads_, auto owners_, auto per_, int d) {
+        constexpr int THREADS = decltype(threads_)::value, OWNERS = decltype(owners_)::value, PER = decltype(per_)::value;
+        if (ts.ranges)   // (scan_rides_in_scatter: every shape launches 512 or 1024 threads there)
+            return slot_scan ? scatter(&scatter_pairs_kernel<THREADS, OWNERS, PER, true, true>, 4 * d, THREADS) : scatter(&scatter_pairs_kernel<THREADS, OWNERS, PER, false, true>, 4 * d + 1, THREADS);
+        return slot_scan ? scatter(&scatter_pairs_kernel<THREADS, OWNERS, PER, true, false>, 4 * d + 2, THREADS) : scatter(&scatter_pairs_kernel<THREADS, OWNERS, PER, false, false>, 4 * d + 3, THREADS);
+    });
 }
 
 // ---- two-level grouping: count_super -> launch_group_scan and _scatter, which take the super grid (the tile sort and the expansion: api.hip calls them) ----
@@ -768,25 +761,20 @@ int launch_super_count(const lvdgs_args &a, const GeomView &g, const SuperView &
     const size_t lds = (size_t)t.Ts * sizeof(uint32_t);
     static unsigned char done[GROUP_SHAPES][16];
     ProfScope ps("super_count", s);
-    if (int e = group_dispatch(group_shape_for(N), [&](auto threads_, auto owners_, auto per_, int d) {
-            constexpr int THREADS = decltype(threads_)::value, OWNERS = decltype(owners_)::value, PER = decltype(per_)::value;
-            if (int e = allow_dynamic_lds(reinterpret_cast<const void *>(&count_super_kernel<THREADS, OWNERS, PER>), GROUP_MAX_TILES * 4, done[d])) return e;
-            hipLaunchKernelGGL((count_super_kernel<THREADS, OWNERS, PER>), dim3(nchunks), dim3(THREADS), lds, s, N, t.gxs, t.Ts, (const uint4 *)g.rect, sv.rect, sv.hist,
-                               sv.long_count);
-            return (int)LVDGS_OK;
-        })) return e;
-    LVDGS_LAUNCH_CHECK("super_count", a.debug, s);
-    return LVDGS_OK;
+    return group_dispatch(group_shape_for(N), [&](auto threads_, auto owners_, auto per_, int d) {
+        constexpr int THREADS = decltype(threads_)::value, OWNERS = decltype(owners_)::value, PER = decltype(per_)::value;
+        if (int e = allow_dynamic_lds(reinterpret_cast<const void *>(&count_super_kernel<THREADS, OWNERS, PER>), GROUP_MAX_TILES * 4, done[d])) return e;
+        return launch_checked("super_count", a.debug, s, count_super_kernel<THREADS, OWNERS, PER>, dim3(nchunks), dim3(THREADS), lds, N, t.gxs, t.Ts, (const uint4 *)g.rect,
+                              sv.rect, sv.hist, sv.long_count);
+    });
 }
 
 int launch_super_expand(const lvdgs_args &a, const GeomView &g, const SuperView &sv, const ImageView &im, const uint32_t *super_list, uint32_t *point_list,
                         hipStream_t s) {
     const TileGrid t(a);
     if (a.num_gaussians == 0 || t.Ts == 0) return LVDGS_OK;
-    ProfScope ps("super_expand", s);
-    hipLaunchKernelGGL(expand_super_kernel, dim3(t.Ts), dim3(64 * SUPER * SUPER), 0, s, t.gx, t.gy, t.gxs, (const uint2 *)sv.ranges, super_list, (const uint4 *)g.rect,
-                       (const uint2 *)im.ranges, point_list);
-    LVDGS_LAUNCH_CHECK("super_expand", a.debug, s);
+    if (int e = launch("super_expand", a.debug, s, expand_super_kernel, dim3(t.Ts), dim3(64 * SUPER * SUPER), 0, t.gx, t.gy, t.gxs, (const uint2 *)sv.ranges, super_list,
+            (const uint4 *)g.rect, (const uint2 *)im.ranges, point_list)) return e;
     return LVDGS_OK;
 }
 
@@ -823,12 +811,12 @@ int launch_group_scan_batch(const lvdgs_args *const *a, const GeomView *g, const
             tpb.v[2 * k] = tile_grid_scan_view(t, g[k], im[k], w[k], caps[k], sv.long_count + SUPER_ARRIVE_WORD);
             tpb.v[2 * k + 1] = super_grid_scan_view(t, g[k], sv, caps[k]);
         }
-        colscan_dispatch(nchunks, [&](auto R) {
-            hipLaunchKernelGGL(group_colscan_pair_batch_kernel<decltype(R)::value>, dim3(cdiv(t.T, COLSCAN_TILES), 2 * n), dim3(1024), 0, s, t.T, t.Ts, nchunks, cpb);
-        });
-        hipLaunchKernelGGL(group_tilescan_pair_batch_kernel, dim3(2 * n), dim3(1024), 0, s, t.T, t.Ts, tpb, long_limit, row0 * t.gx, row1 * t.gx, host_words, report.seq,
-                           report.words ? report.words + PROBE_BATCH_SUPER : nullptr);
-        LVDGS_LAUNCH_CHECK("group_scan (batch, two-level)", a[0]->debug, s);
+        if (int e = colscan_dispatch(nchunks, [&](auto R) {
+                return launch_checked("group_scan (batch, two-level)", a[0]->debug, s, group_colscan_pair_batch_kernel<decltype(R)::value>, dim3(cdiv(t.T, COLSCAN_TILES), 2 * n),
+                                      dim3(1024), 0, t.T, t.Ts, nchunks, cpb);
+            })) return e;
+        if (int e = launch_checked("group_scan (batch, two-level)", a[0]->debug, s, group_tilescan_pair_batch_kernel, dim3(2 * n), dim3(1024), 0, t.T, t.Ts, tpb,
+                long_limit, row0 * t.gx, row1 * t.gx, host_words, report.seq, report.words ? report.words + PROBE_BATCH_SUPER : nullptr)) return e;
         return LVDGS_OK;
     }
     ColscanBatch cb{};
@@ -837,11 +825,11 @@ int launch_group_scan_batch(const lvdgs_args *const *a, const GeomView *g, const
         cb.hist[k] = w[k].group_hist; cb.totals[k] = w[k].group_totals;
         tb.v[k] = tile_grid_scan_view(t, g[k], im[k], w[k], caps[k], nullptr);
     }
-    colscan_dispatch(nchunks, [&](auto R) {
-        hipLaunchKernelGGL(group_colscan_batch_kernel<decltype(R)::value>, dim3(cdiv(t.T, COLSCAN_TILES), n), dim3(1024), 0, s, t.T, nchunks, cb);
-    });
-    hipLaunchKernelGGL(group_tilescan_batch_kernel, dim3(n), dim3(1024), 0, s, t.T, tb, long_limit, row0 * t.gx, row1 * t.gx, host_words, report.seq);
-    LVDGS_LAUNCH_CHECK("group_scan (batch)", a[0]->debug, s);
+    if (int e = colscan_dispatch(nchunks, [&](auto R) {
+            return launch_checked("group_scan (batch)", a[0]->debug, s, group_colscan_batch_kernel<decltype(R)::value>, dim3(cdiv(t.T, COLSCAN_TILES), n), dim3(1024), 0, t.T, nchunks, cb);
+        })) return e;
+    if (int e = launch_checked("group_scan (batch)", a[0]->debug, s, group_tilescan_batch_kernel, dim3(n), dim3(1024), 0, t.T, tb, long_limit, row0 * t.gx, row1 * t.gx,
+            host_words, report.seq)) return e;
     return LVDGS_OK;
 }
 
@@ -862,14 +850,12 @@ int launch_group_scatter_batch(const lvdgs_args *const *a, const GeomView *g, co
     }
     static unsigned char done[GROUP_SHAPES][16];
     ProfScope ps(super ? "super_scatter" : "group_scatter", s);
-    if (int e = group_dispatch(group_shape_for(N), [&](auto threads_, auto owners_, auto per_, int d) {
-            constexpr int THREADS = decltype(threads_)::value, OWNERS = decltype(owners_)::value, PER = decltype(per_)::value;
-            if (int e = allow_dynamic_lds(reinterpret_cast<const void *>(&scatter_pairs_batch_kernel<THREADS, OWNERS, PER>), GROUP_MAX_TILES * 4, done[d])) return e;
-            hipLaunchKernelGGL((scatter_pairs_batch_kernel<THREADS, OWNERS, PER>), dim3((nchunks + 7) & ~7, n), dim3(THREADS), lds, s, N, gx, T, nchunks, sb);
-            return (int)LVDGS_OK;
-        })) return e;
-    LVDGS_LAUNCH_CHECK("group_scatter (batch)", a[0]->debug, s);
-    return LVDGS_OK;
+    return group_dispatch(group_shape_for(N), [&](auto threads_, auto owners_, auto per_, int d) {
+        constexpr int THREADS = decltype(threads_)::value, OWNERS = decltype(owners_)::value, PER = decltype(per_)::value;
+        if (int e = allow_dynamic_lds(reinterpret_cast<const void *>(&scatter_pairs_batch_kernel<THREADS, OWNERS, PER>), GROUP_MAX_TILES * 4, done[d])) return e;
+        return launch_checked("group_scatter (batch)", a[0]->debug, s, scatter_pairs_batch_kernel<THREADS, OWNERS, PER>, dim3((nchunks + 7) & ~7, n), dim3(THREADS), lds, N, gx, T,
+                              nchunks, sb);
+    });
 }
 
 int launch_super_expand_batch(const lvdgs_args *const *a, const GeomView *g, const ImageView *im, const RenderScratch *w, const BinView *b, int n, hipStream_t s) {
@@ -877,19 +863,15 @@ int launch_super_expand_batch(const lvdgs_args *const *a, const GeomView *g, con
     if (a[0]->num_gaussians == 0 || t.Ts == 0 || n == 0) return LVDGS_OK;
     ExpandBatch eb{};
     for (int k = 0; k < n; k++) eb.v[k] = ExpandView{(const uint2 *)w[k].super.ranges, b[k].tile_keys, (const uint4 *)g[k].rect, (const uint2 *)im[k].ranges, b[k].point_list};
-    ProfScope ps("super_expand", s);
-    hipLaunchKernelGGL(expand_super_batch_kernel, dim3(t.Ts, n), dim3(64 * SUPER * SUPER), 0, s, t.gx, t.gy, t.gxs, eb);
-    LVDGS_LAUNCH_CHECK("super_expand (batch)", a[0]->debug, s);
+    if (int e = launch({"super_expand", "super_expand (batch)"}, a[0]->debug, s, expand_super_batch_kernel, dim3(t.Ts, n), dim3(64 * SUPER * SUPER), 0, t.gx, t.gy, t.gxs, eb)) return e;
     return LVDGS_OK;
 }
 
 int launch_emit_pairs(const lvdgs_args &a, const GeomView &g, uint32_t *tile_keys, uint32_t *ids, int64_t capacity, hipStream_t s) {
     const int N = a.num_gaussians;
     if (N == 0) return LVDGS_OK;
-    ProfScope ps("emit_pairs", s);
-    hipLaunchKernelGGL(emit_pairs_kernel, dim3(cdiv(N, 256)), dim3(256), 0, s, N, TileGrid(a).gx, g.slot_base, g.tiles_touched,
-                       (const uint4 *)g.rect, tile_keys, ids, (uint32_t)capacity);
-    LVDGS_LAUNCH_CHECK("emit_pairs", a.debug, s);
+    if (int e = launch("emit_pairs", a.debug, s, emit_pairs_kernel, dim3(cdiv(N, 256)), dim3(256), 0, N, TileGrid(a).gx, g.slot_base, g.tiles_touched,
+            (const uint4 *)g.rect, tile_keys, ids, (uint32_t)capacity)) return e;
     return LVDGS_OK;
 }
 
@@ -899,9 +881,7 @@ int launch_tile_ranges(const uint32_t *tile_keys, int64_t D, const uint32_t *D_d
     const size_t bytes = (size_t)((char *)(im.long_count + 64) - (char *)im.ranges);
     if (int e = check_hip(hipMemsetAsync(im.ranges, 0, bytes, s), "memset ranges")) return e;
     if (D == 0) return LVDGS_OK;
-    ProfScope ps("tile_ranges", s);
-    hipLaunchKernelGGL(tile_ranges_kernel, dim3(cdiv(D, 256)), dim3(256), 0, s, tile_keys, D, D_dev, im.ranges);
-    LVDGS_LAUNCH_CHECK("tile_ranges", dbg, s);
+    if (int e = launch("tile_ranges", dbg, s, tile_ranges_kernel, dim3(cdiv(D, 256)), dim3(256), 0, tile_keys, D, D_dev, im.ranges)) return e;
     return LVDGS_OK;
 }
 

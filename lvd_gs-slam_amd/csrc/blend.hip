@@ -827,23 +827,33 @@ BlendParams make_params(const lvdgs_args &a, const GeomView &g, const BinView &b
     return p;
 }
 
+// The grid of a single-view blend launch: a workgroup per tile.  Diagnostic builds (timings, not results): only the first
+// $LVDGS_DIAG_GRID workgroups (small grids: the heaviest tiles), and the grid $LVDGS_DIAG_REPEAT times over.
+int blend_grid(BlendParams &p) {
+#ifdef LVDGS_DIAG_GRID
+    if (const char *e = getenv("LVDGS_DIAG_GRID")) p.num_tiles = min(p.num_tiles, atoi(e));
+#endif
+    int grid = p.num_tiles;
+#ifdef LVDGS_DIAG_REPEAT
+    if (const char *e = getenv("LVDGS_DIAG_REPEAT")) grid *= atoi(e);
+#endif
+    return grid;
+}
+
+// The backward blend kernel of one loss mode for a call's (depth gradient, pose only)
+template <int LOSS>
+auto blend_bwd3_for(bool depth, bool pose_only) {
+    return pose_only ? (depth ? blend_bwd3_kernel<LOSS, true, true> : blend_bwd3_kernel<LOSS, false, true>)
+                     : (depth ? blend_bwd3_kernel<LOSS, true> : blend_bwd3_kernel<LOSS, false>);
+}
+
 }  // namespace
 
 int launch_blend_fwd(const lvdgs_args &a, const GeomView &g, const BinView &b, const ImageView &im, bool deep_lists, hipStream_t s) {
     BlendParams p = make_params(a, g, b, im);
     if (p.num_tiles == 0) return LVDGS_OK;
-#ifdef LVDGS_DIAG_GRID   // diagnostic build: only the first $LVDGS_DIAG_GRID workgroups (small grids: the heaviest tiles) -- timings, not results
-    if (const char *e = getenv("LVDGS_DIAG_GRID")) p.num_tiles = min(p.num_tiles, atoi(e));
-#endif
-    ProfScope ps("blend_fwd", s);
-    int grid = p.num_tiles;
-#ifdef LVDGS_DIAG_REPEAT
-    if (const char *e = getenv("LVDGS_DIAG_REPEAT")) grid *= atoi(e);
-#endif
-    if (deep_lists) hipLaunchKernelGGL(blend_fwd2_deep_kernel, dim3(grid), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(blend_fwd2_kernel, dim3(grid), dim3(256), 0, s, p);
-    LVDGS_LAUNCH_CHECK("blend_fwd", a.debug, s);
-    return LVDGS_OK;
+    const int grid = blend_grid(p);
+    return launch("blend_fwd", a.debug, s, deep_lists ? blend_fwd2_deep_kernel : blend_fwd2_kernel, dim3(grid), dim3(256), 0, p);
 }
 
 #ifndef LVDGS_BWD_DEPTH_ALWAYS
@@ -854,21 +864,9 @@ int launch_blend_bwd(const lvdgs_args &a, const GeomView &g, const BinView &b, c
     BlendParams p = make_params(a, g, b, im);
     p.pair_grads = w.pair_grads; p.pair_valid = b.pair_valid;
     if (p.num_tiles == 0) return LVDGS_OK;
-#ifdef LVDGS_DIAG_GRID
-    if (const char *e = getenv("LVDGS_DIAG_GRID")) p.num_tiles = min(p.num_tiles, atoi(e));
-#endif
-    ProfScope ps("blend_bwd", s);
-    int grid = p.num_tiles;
-#ifdef LVDGS_DIAG_REPEAT
-    if (const char *e = getenv("LVDGS_DIAG_REPEAT")) grid *= atoi(e);
-#endif
+    const int grid = blend_grid(p);
     const bool depth = LVDGS_BWD_DEPTH_ALWAYS || p.dL_ddepth, pose_only = (a.flags & LVDGS_FLAG_POSE_ONLY) != 0;
-    if (pose_only && depth) hipLaunchKernelGGL((blend_bwd3_kernel<LOSS_IMAGES, true, true>), dim3(grid), dim3(256), 0, s, p);
-    else if (pose_only) hipLaunchKernelGGL((blend_bwd3_kernel<LOSS_IMAGES, false, true>), dim3(grid), dim3(256), 0, s, p);
-    else if (depth) hipLaunchKernelGGL((blend_bwd3_kernel<LOSS_IMAGES, true>), dim3(grid), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((blend_bwd3_kernel<LOSS_IMAGES, false>), dim3(grid), dim3(256), 0, s, p);
-    LVDGS_LAUNCH_CHECK("blend_bwd", a.debug, s);
-    return LVDGS_OK;
+    return launch("blend_bwd", a.debug, s, blend_bwd3_for<LOSS_IMAGES>(depth, pose_only), dim3(grid), dim3(256), 0, p);
 }
 
 int launch_blend_bwd_fused_loss(const lvdgs_args &a, const GeomView &g, const BinView &b, const ImageView &im, const BwdScratch &w,
@@ -878,21 +876,9 @@ int launch_blend_bwd_fused_loss(const lvdgs_args &a, const GeomView &g, const Bi
     p.loss = loss;
     p.loss_propagate_opacity = propagate_opacity;
     if (p.num_tiles == 0) return LVDGS_OK;
-#ifdef LVDGS_DIAG_GRID
-    if (const char *e = getenv("LVDGS_DIAG_GRID")) p.num_tiles = min(p.num_tiles, atoi(e));
-#endif
-    ProfScope ps("blend_bwd", s);
-    int grid = p.num_tiles;
-#ifdef LVDGS_DIAG_REPEAT
-    if (const char *e = getenv("LVDGS_DIAG_REPEAT")) grid *= atoi(e);
-#endif
+    const int grid = blend_grid(p);
     const bool depth = LVDGS_BWD_DEPTH_ALWAYS || (loss.depth && loss.gt_depth && loss.w_d != 0.f), pose_only = (a.flags & LVDGS_FLAG_POSE_ONLY) != 0;
-    if (pose_only && depth) hipLaunchKernelGGL((blend_bwd3_kernel<LOSS_FUSED, true, true>), dim3(grid), dim3(256), 0, s, p);
-    else if (pose_only) hipLaunchKernelGGL((blend_bwd3_kernel<LOSS_FUSED, false, true>), dim3(grid), dim3(256), 0, s, p);
-    else if (depth) hipLaunchKernelGGL((blend_bwd3_kernel<LOSS_FUSED, true>), dim3(grid), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((blend_bwd3_kernel<LOSS_FUSED, false>), dim3(grid), dim3(256), 0, s, p);
-    LVDGS_LAUNCH_CHECK("blend_bwd", a.debug, s);
-    return LVDGS_OK;
+    return launch("blend_bwd", a.debug, s, blend_bwd3_for<LOSS_FUSED>(depth, pose_only), dim3(grid), dim3(256), 0, p);
 }
 
 // The static-mask mapping loss's fields where the kernel looks for them (BlendParams::loss_mode).
@@ -910,11 +896,10 @@ int launch_blend_bwd_masked_loss(const lvdgs_args &a, const GeomView &g, const B
     p.pair_grads = w.pair_grads; p.pair_valid = b.pair_valid;
     set_masked_loss(p, m);
     if (p.num_tiles == 0) return LVDGS_OK;
-    ProfScope ps("blend_bwd", s);
-    if (LVDGS_BWD_DEPTH_ALWAYS || m.gt_depth) hipLaunchKernelGGL((blend_bwd3_kernel<LOSS_MASKED, true>), dim3(p.num_tiles), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((blend_bwd3_kernel<LOSS_MASKED, false>), dim3(p.num_tiles), dim3(256), 0, s, p);
-    LVDGS_LAUNCH_CHECK("blend_bwd (masked loss)", a.debug, s);
-    return LVDGS_OK;
+    // (the masked loss has no pose-only form: two instantiations, not blend_bwd3_for's four)
+    const bool depth = LVDGS_BWD_DEPTH_ALWAYS || m.gt_depth;
+    return launch({"blend_bwd", "blend_bwd (masked loss)"}, a.debug, s, depth ? blend_bwd3_kernel<LOSS_MASKED, true> : blend_bwd3_kernel<LOSS_MASKED, false>,
+                  dim3(p.num_tiles), dim3(256), 0, p);
 }
 
 // One launch for both blend passes of a view (api.hip: lvdgs_forward_backward_fused_loss decides when).
@@ -927,21 +912,13 @@ int launch_blend_fwd_bwd_fused_loss(const lvdgs_args &a, const GeomView &g, cons
     p.loss = loss; p.loss_mode = LOSS_FUSED;
     p.loss_propagate_opacity = propagate_opacity;
     if (p.num_tiles == 0) return LVDGS_OK;
-    ProfScope ps("blend_fwd_bwd", s);
-    const dim3 grid(p.num_tiles), block(256);
     const bool depth = LVDGS_BWD_DEPTH_ALWAYS || (loss.depth && loss.gt_depth && loss.w_d != 0.f), pose_only = (a.flags & LVDGS_FLAG_POSE_ONLY) != 0;
-#define LVDGS_FUSED_LAUNCH(D, PO)                                                                                        \
-    do {                                                                                                                \
-        if (deep_lists) hipLaunchKernelGGL((blend_fwd_bwd_kernel<D, PO, true>), grid, block, 0, s, p);                  \
-        else hipLaunchKernelGGL((blend_fwd_bwd_kernel<D, PO, false>), grid, block, 0, s, p);                            \
-    } while (0)
-    if (pose_only && depth) LVDGS_FUSED_LAUNCH(true, true);
-    else if (pose_only) LVDGS_FUSED_LAUNCH(false, true);
-    else if (depth) LVDGS_FUSED_LAUNCH(true, false);
-    else LVDGS_FUSED_LAUNCH(false, false);
-#undef LVDGS_FUSED_LAUNCH
-    LVDGS_LAUNCH_CHECK("blend_fwd_bwd", a.debug, s);
-    return LVDGS_OK;
+    const auto deep_or_not = [&](auto deep, auto shallow) { return deep_lists ? deep : shallow; };   // (kernel pointers of one type)
+    const auto kernel = pose_only ? (depth ? deep_or_not(blend_fwd_bwd_kernel<true, true, true>, blend_fwd_bwd_kernel<true, true, false>)
+                                           : deep_or_not(blend_fwd_bwd_kernel<false, true, true>, blend_fwd_bwd_kernel<false, true, false>))
+                                  : (depth ? deep_or_not(blend_fwd_bwd_kernel<true, false, true>, blend_fwd_bwd_kernel<true, false, false>)
+                                           : deep_or_not(blend_fwd_bwd_kernel<false, false, true>, blend_fwd_bwd_kernel<false, false, false>));
+    return launch("blend_fwd_bwd", a.debug, s, kernel, dim3(p.num_tiles), dim3(256), 0, p);
 }
 
 // The blend passes of n views of one size in one launch each (api.hip: lvdgs_blend_forward_batch / lvdgs_blend_backward_fused_loss_batch).
@@ -951,10 +928,8 @@ int launch_blend_fwd_batch(const lvdgs_args *const *a, const GeomView *g, const 
         BlendBatch batch{};
         for (int k = 0; k < m; k++) batch.v[k] = make_params(*a[first + k], g[first + k], b[first + k], im[first + k]);
         if (batch.v[0].num_tiles == 0) continue;
-        ProfScope ps("blend_fwd", s);
-        if (deep_lists) hipLaunchKernelGGL(blend_fwd2_deep_batch_kernel, dim3(batch.v[0].num_tiles, m), dim3(256), 0, s, batch);
-        else hipLaunchKernelGGL(blend_fwd2_batch_kernel, dim3(batch.v[0].num_tiles, m), dim3(256), 0, s, batch);
-        LVDGS_LAUNCH_CHECK("blend_fwd (batch)", a[first]->debug, s);
+        if (int e = launch({"blend_fwd", "blend_fwd (batch)"}, a[first]->debug, s, deep_lists ? blend_fwd2_deep_batch_kernel : blend_fwd2_batch_kernel,
+                dim3(batch.v[0].num_tiles, m), dim3(256), 0, batch)) return e;
     }
     return LVDGS_OK;
 }
@@ -984,20 +959,12 @@ int launch_blend_bwd_fused_loss_batch(const lvdgs_args *const *a, const GeomView
             }
         }
         if (batch.v[0].num_tiles == 0) continue;
-        ProfScope ps("blend_bwd", s);
-        const bool pose_only = (a[first]->flags & LVDGS_FLAG_POSE_ONLY) != 0;
-        const dim3 grid(batch.v[0].num_tiles, m);
-        if (n_masked == m) {
-            if (depth) hipLaunchKernelGGL((blend_bwd3_batch_kernel<LOSS_MASKED, true, false>), grid, dim3(256), 0, s, batch);
-            else hipLaunchKernelGGL((blend_bwd3_batch_kernel<LOSS_MASKED, false, false>), grid, dim3(256), 0, s, batch);
-        } else if (n_masked) {
-            if (depth) hipLaunchKernelGGL((blend_bwd3_batch_kernel<LOSS_PER_VIEW, true, false>), grid, dim3(256), 0, s, batch);
-            else hipLaunchKernelGGL((blend_bwd3_batch_kernel<LOSS_PER_VIEW, false, false>), grid, dim3(256), 0, s, batch);
-        } else if (pose_only && depth) hipLaunchKernelGGL((blend_bwd3_batch_kernel<LOSS_FUSED, true, true>), grid, dim3(256), 0, s, batch);
-        else if (pose_only) hipLaunchKernelGGL((blend_bwd3_batch_kernel<LOSS_FUSED, false, true>), grid, dim3(256), 0, s, batch);
-        else if (depth) hipLaunchKernelGGL((blend_bwd3_batch_kernel<LOSS_FUSED, true, false>), grid, dim3(256), 0, s, batch);
-        else hipLaunchKernelGGL((blend_bwd3_batch_kernel<LOSS_FUSED, false, false>), grid, dim3(256), 0, s, batch);
-        LVDGS_LAUNCH_CHECK("blend_bwd (batch)", a[first]->debug, s);
+        const bool pose_only = (a[first]->flags & LVDGS_FLAG_POSE_ONLY) != 0;   // (only where no view has the masked loss)
+        const auto kernel = n_masked == m ? (depth ? blend_bwd3_batch_kernel<LOSS_MASKED, true, false> : blend_bwd3_batch_kernel<LOSS_MASKED, false, false>)
+                            : n_masked    ? (depth ? blend_bwd3_batch_kernel<LOSS_PER_VIEW, true, false> : blend_bwd3_batch_kernel<LOSS_PER_VIEW, false, false>)
+                            : pose_only   ? (depth ? blend_bwd3_batch_kernel<LOSS_FUSED, true, true> : blend_bwd3_batch_kernel<LOSS_FUSED, false, true>)
+                                          : (depth ? blend_bwd3_batch_kernel<LOSS_FUSED, true, false> : blend_bwd3_batch_kernel<LOSS_FUSED, false, false>);
+        if (int e = launch({"blend_bwd", "blend_bwd (batch)"}, a[first]->debug, s, kernel, dim3(batch.v[0].num_tiles, m), dim3(256), 0, batch)) return e;
     }
     return LVDGS_OK;
 }

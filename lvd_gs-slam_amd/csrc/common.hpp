@@ -72,13 +72,29 @@ struct ProfScope {
     ~ProfScope();
 };
 
-#define LVDGS_LAUNCH_CHECK(name, dbg, stream)                                   \
-    do {                                                                        \
-        if (int _e = ::lvdgs::check_hip(hipGetLastError(), name)) return _e;    \
-        if (dbg) {                                                              \
-            if (int _e = ::lvdgs::check_hip(hipStreamSynchronize(stream), name)) return _e; \
-        }                                                                       \
-    } while (0)
+// ---- the launch statement: `if (int e = launch("name", debug, s, kernel, grid, block, lds, args...)) return e;` ----
+// launch_checked launches `kernel`, reports a failed launch under `name` and, when `debug` is set, waits for the stream so
+// that a fault in the kernel is reported under `name` too.  The kernel comes as a function pointer, so its arguments convert
+// to the parameter types as in a plain call, and one instantiation of several is picked before the one launch.
+template <class... KArgs, class... Args>
+static inline int launch_checked(const char *name, int debug, hipStream_t s, void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, Args &&...args) {
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, static_cast<KArgs>(args)...);
+    if (int e = check_hip(hipGetLastError(), name)) return e;
+    return debug ? check_hip(hipStreamSynchronize(s), name) : 0;
+}
+// the profiling slot a launch is timed under and the name its errors carry: one name for both, or {scope, check}
+struct LaunchName {
+    const char *scope, *check;
+    LaunchName(const char *name) : scope(name), check(name) {}
+    LaunchName(const char *scope, const char *check) : scope(scope), check(check) {}
+};
+// launch() is launch_checked inside a ProfScope of its own: the check and the debug wait end before the scope's stop event
+// is recorded.  Launches that share one scope open the ProfScope themselves and use launch_checked for each.
+template <class... KArgs, class... Args>
+static inline int launch(LaunchName name, int debug, hipStream_t s, void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, Args &&...args) {
+    ProfScope ps(name.scope, s);
+    return launch_checked(name.check, debug, s, kernel, grid, block, lds, static_cast<Args &&>(args)...);
+}
 
 // Can a Gaussian (mean m, conic a,b,c, opacity op) reach alpha >= 1/255 anywhere in the pixel
 // rectangle [x0,x1] x [y0,y1]?  Exact minimum of q(d) = 1/2 (a dx^2 + c dy^2) + b dx dy over the

@@ -300,16 +300,12 @@ int align_params(const lvdgs_depth_align_args *a, AlignParams &P) {
 }
 
 int launch_iter(const AlignParams &P, int k, int force, float s_in, hipStream_t s) {
-    ProfScope ps("depth_align_iter", s);
-    hipLaunchKernelGGL(depth_align_iter_kernel, dim3(iter_blocks(P.W, P.H, P.p)), dim3(DA_THREADS), 0, s, P, k, force, s_in);
-    LVDGS_LAUNCH_CHECK("depth_align_iter", 0, s);
+    if (int e = launch("depth_align_iter", 0, s, depth_align_iter_kernel, dim3(iter_blocks(P.W, P.H, P.p)), dim3(DA_THREADS), 0, P, k, force, s_in)) return e;
     return LVDGS_OK;
 }
 
 int launch_fill(const AlignParams &P, int force, float s_in, int force_status, hipStream_t s) {
-    ProfScope ps("depth_align_fill", s);
-    hipLaunchKernelGGL(depth_align_fill_kernel, dim3(fill_blocks(P.W, P.H)), dim3(DA_FILL_THREADS), 0, s, P, force, s_in, force_status);
-    LVDGS_LAUNCH_CHECK("depth_align_fill", 0, s);
+    if (int e = launch("depth_align_fill", 0, s, depth_align_fill_kernel, dim3(fill_blocks(P.W, P.H)), dim3(DA_FILL_THREADS), 0, P, force, s_in, force_status)) return e;
     return LVDGS_OK;
 }
 

@@ -329,25 +329,11 @@ int lvdgs_dynamic_mask(const lvdgs_dynamic_mask_args *a, void *stream) {
     P.info = a->info;
     const int wave_blocks = (int)min((int64_t)cdiv(P.words, DM_WAVES), (int64_t)DM_MAX_BLOCKS), thread_blocks = cdiv(P.words, DM_THREADS);
     if (int e = check_hip(hipMemsetAsync(a->info, 0, LVDGS_DYNAMIC_MASK_INFO_WORDS * sizeof(int32_t), s), "dynamic mask: clearing info")) return e;
-    {
-        ProfScope ps("dm_build", s);
-        hipLaunchKernelGGL(dm_build_kernel, dim3(wave_blocks), dim3(DM_THREADS), 0, s, P);
-        LVDGS_LAUNCH_CHECK("dm_build", 0, s);
-    }
-    {
-        ProfScope ps("dm_select", s);
-        hipLaunchKernelGGL(dm_select_kernel, dim3(thread_blocks), dim3(DM_THREADS), 0, s, P);
-        LVDGS_LAUNCH_CHECK("dm_select", 0, s);
-    }
-    {
-        ProfScope ps("dm_vehicle", s);
-        hipLaunchKernelGGL(dm_vehicle_kernel, dim3(wave_blocks), dim3(DM_THREADS), 0, s, P);
-        LVDGS_LAUNCH_CHECK("dm_vehicle", 0, s);
-    }
+    if (int e = launch("dm_build", 0, s, dm_build_kernel, dim3(wave_blocks), dim3(DM_THREADS), 0, P)) return e;
+    if (int e = launch("dm_select", 0, s, dm_select_kernel, dim3(thread_blocks), dim3(DM_THREADS), 0, P)) return e;
+    if (int e = launch("dm_vehicle", 0, s, dm_vehicle_kernel, dim3(wave_blocks), dim3(DM_THREADS), 0, P)) return e;
     if (P.expand_k != 0) {
-        ProfScope ps("dm_expand", s);
-        hipLaunchKernelGGL(dm_expand_kernel, dim3(wave_blocks), dim3(DM_THREADS), 0, s, P);
-        LVDGS_LAUNCH_CHECK("dm_expand", 0, s);
+        if (int e = launch("dm_expand", 0, s, dm_expand_kernel, dim3(wave_blocks), dim3(DM_THREADS), 0, P)) return e;
     }
     return LVDGS_OK;
 }

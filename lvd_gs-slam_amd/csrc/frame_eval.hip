@@ -357,24 +357,14 @@ int lvdgs_frame_eval(const lvdgs_frame_eval_args *a, void *stream) {
     fill_eval_window(p.win);
     const int nwg = (int)(grid.x * grid.y * grid.z);
     lvdgs_frame_eval_row *row = (lvdgs_frame_eval_row *)a->out_row;
-    {
-        ProfScope ps("frame_eval", s);
-        hipLaunchKernelGGL(frame_eval_kernel, grid, dim3(EVAL_THREADS), 0, s, p);
-        LVDGS_LAUNCH_CHECK("frame_eval", 0, s);
-    }
-    {
-        ProfScope ps("frame_eval_finish", s);
-        hipLaunchKernelGGL(frame_eval_finish_kernel, dim3(1), dim3(EVAL_THREADS), 0, s, (const EvalPartial *)p.partial, nwg,
-                           (double)a->width * a->height * 3.0, a->static_mask ? 1 : 0, a->depth ? 1 : 0, row);
-        LVDGS_LAUNCH_CHECK("frame_eval_finish", 0, s);
-    }
+    if (int e = launch("frame_eval", 0, s, frame_eval_kernel, grid, dim3(EVAL_THREADS), 0, p)) return e;
+    if (int e = launch("frame_eval_finish", 0, s, frame_eval_finish_kernel, dim3(1), dim3(EVAL_THREADS), 0, (const EvalPartial *)p.partial, nwg,
+            (double)a->width * a->height * 3.0, a->static_mask ? 1 : 0, a->depth ? 1 : 0, row)) return e;
     if (a->depth8) {
         const size_t n = (size_t)a->width * a->height;
         const size_t blocks = (n + 255) / 256;
-        ProfScope ps("frame_eval_depth8", s);
-        hipLaunchKernelGGL(frame_eval_depth8_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, s, a->depth, n,
-                           (const lvdgs_frame_eval_row *)row, a->depth8);
-        LVDGS_LAUNCH_CHECK("frame_eval_depth8", 0, s);
+        if (int e = launch("frame_eval_depth8", 0, s, frame_eval_depth8_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, a->depth, n,
+                (const lvdgs_frame_eval_row *)row, a->depth8)) return e;
     }
     return LVDGS_OK;
 }

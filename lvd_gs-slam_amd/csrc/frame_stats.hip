@@ -260,28 +260,16 @@ int lvdgs_edge_mask(const lvdgs_edge_mask_args *a, void *stream) {
     if (a->mode == LVDGS_EDGE_MASK_BLOCKS) {
         P.mag = reinterpret_cast<float *>(a->mask);
         P.mag_copy = a->magnitude;
-        {
-            ProfScope ps("edge_magnitude", s);
-            hipLaunchKernelGGL(edge_magnitude_kernel, dim3(pixel_blocks), dim3(FS_THREADS), 0, s, P);
-            LVDGS_LAUNCH_CHECK("edge_magnitude", 0, s);
-        }
-        ProfScope ps("edge_blocks", s);
-        hipLaunchKernelGGL(edge_blocks_kernel, dim3(EDGE_BLOCKS), dim3(SEL_THREADS), 0, s, P);
-        LVDGS_LAUNCH_CHECK("edge_blocks", 0, s);
+        if (int e = launch("edge_magnitude", 0, s, edge_magnitude_kernel, dim3(pixel_blocks), dim3(FS_THREADS), 0, P)) return e;
+        if (int e = launch("edge_blocks", 0, s, edge_blocks_kernel, dim3(EDGE_BLOCKS), dim3(SEL_THREADS), 0, P)) return e;
         return LVDGS_OK;
     }
     P.mag_copy = a->magnitude;
     P.mask = reinterpret_cast<uint8_t *>(a->mask);
     if (int e = check_hip(hipMemsetAsync(P.st, 0, sizeof(SelectState), s), "edge mask: clearing the selection state")) return e;
-    {
-        ProfScope ps("edge_magnitude", s);
-        hipLaunchKernelGGL(edge_magnitude_kernel, dim3(pixel_blocks), dim3(FS_THREADS), 0, s, P);
-        LVDGS_LAUNCH_CHECK("edge_magnitude", 0, s);
-    }
+    if (int e = launch("edge_magnitude", 0, s, edge_magnitude_kernel, dim3(pixel_blocks), dim3(FS_THREADS), 0, P)) return e;
     if (int e = launch_select(MagSource{P.mag}, n, P.st, -1, "edge_median", s)) return e;
-    ProfScope ps("edge_threshold", s);
-    hipLaunchKernelGGL(edge_threshold_kernel, dim3(stream_blocks(n)), dim3(FS_THREADS), 0, s, P);
-    LVDGS_LAUNCH_CHECK("edge_threshold", 0, s);
+    if (int e = launch("edge_threshold", 0, s, edge_threshold_kernel, dim3(stream_blocks(n)), dim3(FS_THREADS), 0, P)) return e;
     return LVDGS_OK;
 }
 
@@ -314,15 +302,9 @@ int lvdgs_frame_summary(const lvdgs_frame_summary_args *a, void *stream) {
     if (int e = host_block_address(a->host_state, "frame summary", &S.host)) return e;
     if (int e = check_hip(hipMemsetAsync(a->scratch, 0, state_bytes, s), "frame summary: clearing the state")) return e;
     if (int e = launch_select(DepthSource{S.depth, S.opacity, S.mask, S.bar}, S.P, S.st, -1, "summary_median", s)) return e;
-    {
-        ProfScope ps("summary_counts", s);
-        const int64_t longest = S.count_mask && S.P > S.N ? S.P : S.N;
-        hipLaunchKernelGGL(summary_counts_kernel, dim3(stream_blocks(longest)), dim3(FS_THREADS), 0, s, S);
-        LVDGS_LAUNCH_CHECK("summary_counts", 0, s);
-    }
-    ProfScope ps("summary_publish", s);
-    hipLaunchKernelGGL(summary_publish_kernel, dim3(1), dim3(WAVE), 0, s, S);
-    LVDGS_LAUNCH_CHECK("summary_publish", 0, s);
+    const int64_t longest = S.count_mask && S.P > S.N ? S.P : S.N;
+    if (int e = launch("summary_counts", 0, s, summary_counts_kernel, dim3(stream_blocks(longest)), dim3(FS_THREADS), 0, S)) return e;
+    if (int e = launch("summary_publish", 0, s, summary_publish_kernel, dim3(1), dim3(WAVE), 0, S)) return e;
     return LVDGS_OK;
 }
 

@@ -241,9 +241,7 @@ int lvdgs_undistort_map(int32_t width, int32_t height, double fx, double fy, dou
     M.W = width; M.H = height; M.fx = fx; M.fy = fy; M.cx = cx; M.cy = cy;
     M.k1 = dist[0]; M.k2 = dist[1]; M.p1 = dist[2]; M.p2 = dist[3]; M.k3 = dist[4];   // OpenCV's order; read here, on the host
     M.sx = sx; M.sy = sy;
-    ProfScope ps("undistort_map", s);
-    hipLaunchKernelGGL(undistort_map_kernel, dim3(cdiv(P, ING_THREADS)), dim3(ING_THREADS), 0, s, M);
-    LVDGS_LAUNCH_CHECK("undistort_map", 0, s);
+    if (int e = launch("undistort_map", 0, s, undistort_map_kernel, dim3(cdiv(P, ING_THREADS)), dim3(ING_THREADS), 0, M)) return e;
     return LVDGS_OK;
 }
 
@@ -265,10 +263,7 @@ int lvdgs_ingest_frame(const lvdgs_ingest_args *a, void *stream) {
     P.map_vec = a->map_sx && aligned(a->map_sx, 16) && aligned(a->map_sy, 16);
     P.image_vec = aligned(a->image, 16) && P.P % 4 == 0;      // plane c starts at float c * P
     P.u8_dwords = a->image_u8 && aligned(a->image_u8, 4);
-    ProfScope ps("ingest_frame", s);
-    if (a->map_sx) hipLaunchKernelGGL(ingest_kernel<true>, dim3(cdiv(groups, ING_THREADS)), dim3(ING_THREADS), 0, s, P);
-    else hipLaunchKernelGGL(ingest_kernel<false>, dim3(cdiv(groups, ING_THREADS)), dim3(ING_THREADS), 0, s, P);
-    LVDGS_LAUNCH_CHECK("ingest_frame", 0, s);
+    if (int e = launch("ingest_frame", 0, s, a->map_sx ? ingest_kernel<true> : ingest_kernel<false>, dim3(cdiv(groups, ING_THREADS)), dim3(ING_THREADS), 0, P)) return e;
     return LVDGS_OK;
 }
 
@@ -300,10 +295,7 @@ int lvdgs_ingest_depth(const lvdgs_ingest_depth_args *a, void *stream) {
     P.src_vec = gapless && a->pixel_stride == size && aligned(a->src, 4 * size);
     P.src_dwords = !word && gapless && a->pixel_stride == 3 && aligned(a->src, 4);
     P.out_vec = aligned(a->out, 16);
-    ProfScope ps("ingest_depth", s);
-    if (word) hipLaunchKernelGGL(ingest_depth_kernel<true>, dim3(cdiv(groups, ING_THREADS)), dim3(ING_THREADS), 0, s, P);
-    else hipLaunchKernelGGL(ingest_depth_kernel<false>, dim3(cdiv(groups, ING_THREADS)), dim3(ING_THREADS), 0, s, P);
-    LVDGS_LAUNCH_CHECK("ingest_depth", 0, s);
+    if (int e = launch("ingest_depth", 0, s, word ? ingest_depth_kernel<true> : ingest_depth_kernel<false>, dim3(cdiv(groups, ING_THREADS)), dim3(ING_THREADS), 0, P)) return e;
     return LVDGS_OK;
 }
 

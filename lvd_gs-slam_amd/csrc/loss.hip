@@ -228,9 +228,8 @@ static bool loss_vec_path(const LossParams &p) {
 }
 
 template <int MODE>
-static void launch_photometric(const LossParams &p, int nblk, hipStream_t s) {
-    if (loss_vec_path(p)) hipLaunchKernelGGL((photometric_kernel<MODE, true>), dim3(nblk), dim3(LOSS_THREADS), 0, s, p);
-    else hipLaunchKernelGGL((photometric_kernel<MODE, false>), dim3(nblk), dim3(LOSS_THREADS), 0, s, p);
+static int launch_photometric(const char *name, const LossParams &p, int nblk, hipStream_t s) {
+    return launch(name, 0, s, loss_vec_path(p) ? photometric_kernel<MODE, true> : photometric_kernel<MODE, false>, dim3(nblk), dim3(LOSS_THREADS), 0, p);
 }
 
 extern "C" {
@@ -266,8 +265,8 @@ int lvdgs_photometric_loss_forward(const lvdgs_loss_args *a, void *stream) {
     if (int e = loss_common(a, p, nblk)) return e;
     if (!a->loss) { set_error("loss: output is NULL"); return LVDGS_E_INVALID; }
     p.loss = a->loss;
-    { ProfScope ps("loss_fwd", s); launch_photometric<0>(p, nblk, s); LVDGS_LAUNCH_CHECK("loss_fwd", 0, s); }
-    { ProfScope ps("loss_fwd_finish", s); hipLaunchKernelGGL(photometric_finish_kernel<0>, dim3(1), dim3(256), 0, s, p, nblk); LVDGS_LAUNCH_CHECK("loss_fwd_finish", 0, s); }
+    if (int e = launch_photometric<0>("loss_fwd", p, nblk, s)) return e;
+    if (int e = launch("loss_fwd_finish", 0, s, photometric_finish_kernel<0>, dim3(1), dim3(256), 0, p, nblk)) return e;
     return LVDGS_OK;
 }
 
@@ -278,8 +277,8 @@ int lvdgs_photometric_loss_backward(const lvdgs_loss_args *a, void *stream) {
     if (!a->grad_loss || !a->d_image) { set_error("loss backward: grad_loss / d_image is NULL"); return LVDGS_E_INVALID; }
     p.grad_out = a->grad_loss; p.d_image = a->d_image; p.d_depth = a->d_depth; p.d_opacity = a->d_opacity;
     p.d_a = a->d_exposure_a; p.d_b = a->d_exposure_b;
-    { ProfScope ps("loss_bwd", s); launch_photometric<1>(p, nblk, s); LVDGS_LAUNCH_CHECK("loss_bwd", 0, s); }
-    { ProfScope ps("loss_bwd_finish", s); hipLaunchKernelGGL(photometric_finish_kernel<1>, dim3(1), dim3(256), 0, s, p, nblk); LVDGS_LAUNCH_CHECK("loss_bwd_finish", 0, s); }
+    if (int e = launch_photometric<1>("loss_bwd", p, nblk, s)) return e;
+    if (int e = launch("loss_bwd_finish", 0, s, photometric_finish_kernel<1>, dim3(1), dim3(256), 0, p, nblk)) return e;
     return LVDGS_OK;
 }
 
@@ -292,18 +291,12 @@ static int value_and_grad_params(const lvdgs_loss_args *a, LossParams &p, int &n
     return LVDGS_OK;
 }
 
-static void launch_value_and_grad_pass(const LossParams &p, int nblk, hipStream_t s) {
-    ProfScope ps("loss_both", s);
-    launch_photometric<2>(p, nblk, s);
-}
-
 int lvdgs_photometric_loss_value_and_grad(const lvdgs_loss_args *a, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     LossParams p; int nblk;
     if (int e = value_and_grad_params(a, p, nblk, true)) return e;
-    launch_value_and_grad_pass(p, nblk, s);
-    LVDGS_LAUNCH_CHECK("loss_both", 0, s);
-    { ProfScope ps("loss_both_finish", s); hipLaunchKernelGGL(photometric_finish_kernel<2>, dim3(1), dim3(256), 0, s, p, nblk); LVDGS_LAUNCH_CHECK("loss_both_finish", 0, s); }
+    if (int e = launch_photometric<2>("loss_both", p, nblk, s)) return e;
+    if (int e = launch("loss_both_finish", 0, s, photometric_finish_kernel<2>, dim3(1), dim3(256), 0, p, nblk)) return e;
     return LVDGS_OK;
 }
 
@@ -311,8 +304,7 @@ int lvdgs_photometric_loss_partials(const lvdgs_loss_args *a, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     LossParams p; int nblk;
     if (int e = value_and_grad_params(a, p, nblk, false)) return e;
-    launch_value_and_grad_pass(p, nblk, s);
-    LVDGS_LAUNCH_CHECK("loss_both", 0, s);
+    if (int e = launch_photometric<2>("loss_both", p, nblk, s)) return e;
     return LVDGS_OK;
 }
 
@@ -358,13 +350,8 @@ int lvdgs_masked_depth_l1_forward(const lvdgs_masked_depth_args *a, void *stream
     if (!a->scratch || a->scratch_bytes < lvdgs_masked_depth_scratch_bytes(a->width, a->height)) { set_error("masked depth loss: scratch missing or too small"); return LVDGS_E_INVALID; }
     p.partial_sum = (float *)a->scratch;
     p.partial_cnt = (uint32_t *)(p.partial_sum + nblk);
-    {
-        ProfScope ps("masked_depth_fwd", s);
-        if (vec) hipLaunchKernelGGL((masked_depth_kernel<false, true>), dim3(nblk), dim3(LOSS_THREADS), 0, s, p);
-        else hipLaunchKernelGGL((masked_depth_kernel<false, false>), dim3(nblk), dim3(LOSS_THREADS), 0, s, p);
-        LVDGS_LAUNCH_CHECK("masked_depth_fwd", 0, s);
-    }
-    { ProfScope ps("masked_depth_finish", s); hipLaunchKernelGGL(masked_depth_finish_kernel, dim3(1), dim3(256), 0, s, p, nblk); LVDGS_LAUNCH_CHECK("masked_depth_finish", 0, s); }
+    if (int e = launch("masked_depth_fwd", 0, s, vec ? masked_depth_kernel<false, true> : masked_depth_kernel<false, false>, dim3(nblk), dim3(LOSS_THREADS), 0, p)) return e;
+    if (int e = launch("masked_depth_finish", 0, s, masked_depth_finish_kernel, dim3(1), dim3(256), 0, p, nblk)) return e;
     return LVDGS_OK;
 }
 
@@ -374,10 +361,7 @@ int lvdgs_masked_depth_l1_backward(const lvdgs_masked_depth_args *a, void *strea
     if (int e = masked_depth_common(a, p, nblk, vec)) return e;
     if (!a->grad_loss || !a->d_depth) { set_error("masked depth loss backward: grad_loss / d_depth is NULL"); return LVDGS_E_INVALID; }
     p.grad_out = a->grad_loss; p.d_depth = a->d_depth;
-    ProfScope ps("masked_depth_bwd", s);
-    if (vec) hipLaunchKernelGGL((masked_depth_kernel<true, true>), dim3(nblk), dim3(LOSS_THREADS), 0, s, p);
-    else hipLaunchKernelGGL((masked_depth_kernel<true, false>), dim3(nblk), dim3(LOSS_THREADS), 0, s, p);
-    LVDGS_LAUNCH_CHECK("masked_depth_bwd", 0, s);
+    if (int e = launch("masked_depth_bwd", 0, s, vec ? masked_depth_kernel<true, true> : masked_depth_kernel<true, false>, dim3(nblk), dim3(LOSS_THREADS), 0, p)) return e;
     return LVDGS_OK;
 }
 

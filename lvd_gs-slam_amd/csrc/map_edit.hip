@@ -251,23 +251,13 @@ int lvdgs_map_edit_plan(const lvdgs_map_edit_plan_args *a, void *stream) {
     if (int e = host_block_address(a->host_state, "map edit plan", &P.host)) return e;
     P.host_words = (int64_t)(a->host_bytes / sizeof(int32_t));
     if (P.blocks) {
-        ProfScope ps("edit_count", s);
-        hipLaunchKernelGGL(edit_count_kernel, dim3(P.blocks), dim3(EDIT_THREADS), 0, s, P);
-        LVDGS_LAUNCH_CHECK("edit_count", 0, s);
+        if (int e = launch("edit_count", 0, s, edit_count_kernel, dim3(P.blocks), dim3(EDIT_THREADS), 0, P)) return e;
     }
-    {
-        ProfScope ps("edit_scan", s);
-        hipLaunchKernelGGL(edit_scan_kernel, dim3(1), dim3(EDIT_THREADS), 0, s, P);
-        LVDGS_LAUNCH_CHECK("edit_scan", 0, s);
-    }
+    if (int e = launch("edit_scan", 0, s, edit_scan_kernel, dim3(1), dim3(EDIT_THREADS), 0, P)) return e;
     if (P.blocks) {
-        ProfScope ps("edit_write", s);
-        hipLaunchKernelGGL(edit_write_kernel, dim3(P.blocks), dim3(EDIT_THREADS), 0, s, P);
-        LVDGS_LAUNCH_CHECK("edit_write", 0, s);
+        if (int e = launch("edit_write", 0, s, edit_write_kernel, dim3(P.blocks), dim3(EDIT_THREADS), 0, P)) return e;
     }
-    ProfScope ps("edit_publish", s);
-    hipLaunchKernelGGL(edit_publish_kernel, dim3(1), dim3(WAVE), 0, s, P);
-    LVDGS_LAUNCH_CHECK("edit_publish", 0, s);
+    if (int e = launch("edit_publish", 0, s, edit_publish_kernel, dim3(1), dim3(WAVE), 0, P)) return e;
     return LVDGS_OK;
 }
 
@@ -287,9 +277,7 @@ int lvdgs_map_edit_apply(const lvdgs_map_edit_apply_args *a, void *stream) {
     }
     int64_t gx = (most + EDIT_THREADS - 1) / EDIT_THREADS;
     if (gx > 2048) gx = 2048;
-    ProfScope ps("edit_apply", s);
-    hipLaunchKernelGGL(edit_apply_kernel, dim3((unsigned)gx, (unsigned)a->num_columns), dim3(EDIT_THREADS), 0, s, A);
-    LVDGS_LAUNCH_CHECK("edit_apply", 0, s);
+    if (int e = launch("edit_apply", 0, s, edit_apply_kernel, dim3((unsigned)gx, (unsigned)a->num_columns), dim3(EDIT_THREADS), 0, A)) return e;
     return LVDGS_OK;
 }
 

@@ -268,16 +268,8 @@ int lvdgs_format_image(const lvdgs_format_image_args *a, void *stream) {
     P.row_first = p.row_first; P.row_count = p.row_count;
     P.image = a->image; P.table_x = a->table_x; P.table_y = a->table_y;
     P.rows = reinterpret_cast<uint8_t *>(a->scratch); P.out = a->out; P.quantised = a->quantised;
-    {
-        ProfScope ps("format_rows", s);
-        hipLaunchKernelGGL(format_rows_kernel, dim3(cdiv(P.W1, FMT_THREADS), P.row_count, 3), dim3(FMT_THREADS), 0, s, P);
-        LVDGS_LAUNCH_CHECK("format_rows", 0, s);
-    }
-    {
-        ProfScope ps("format_columns", s);
-        hipLaunchKernelGGL(format_columns_kernel, dim3(cdiv(P.W1, FMT_THREADS), P.H1, 3), dim3(FMT_THREADS), 0, s, P);
-        LVDGS_LAUNCH_CHECK("format_columns", 0, s);
-    }
+    if (int e = launch("format_rows", 0, s, format_rows_kernel, dim3(cdiv(P.W1, FMT_THREADS), P.row_count, 3), dim3(FMT_THREADS), 0, P)) return e;
+    if (int e = launch("format_columns", 0, s, format_columns_kernel, dim3(cdiv(P.W1, FMT_THREADS), P.H1, 3), dim3(FMT_THREADS), 0, P)) return e;
     return LVDGS_OK;
 }
 
@@ -296,11 +288,7 @@ int lvdgs_match_depth_scale(const lvdgs_match_scale_args *a, void *stream) {
     P.Wa = a->width1; P.Ha = a->height1; P.Wb = a->width2; P.Hb = a->height2;
     P.m1 = a->matches_im1; P.m2 = a->matches_im2; P.d1 = a->depth1; P.d2 = a->depth2;
     if (int e = host_block_address(a->host_state, "match_depth_scale", &P.host_state)) return e;
-    {
-        ProfScope ps("match_scale", s);
-        hipLaunchKernelGGL(match_scale_kernel, dim3(1), dim3(MS_THREADS), 0, s, P);
-        LVDGS_LAUNCH_CHECK("match_scale", 0, s);
-    }
+    if (int e = launch("match_scale", 0, s, match_scale_kernel, dim3(1), dim3(MS_THREADS), 0, P)) return e;
     return LVDGS_OK;
 }
 

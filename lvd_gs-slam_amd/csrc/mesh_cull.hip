@@ -214,9 +214,7 @@ int lvdgs_mesh_visibility(const lvdgs_mesh_visibility_args *a, void *stream) {
     P.V = (uint32_t)a->num_vertices; P.count = a->count; P.eps = a->occlusion_eps;
     P.vertices = a->vertices; P.seen = a->seen;
     hipStream_t s = (hipStream_t)stream;
-    ProfScope ps("mesh_visibility", s);
-    hipLaunchKernelGGL(mesh_visibility_kernel, dim3((unsigned)(((int64_t)P.V + MC_THREADS - 1) / MC_THREADS)), dim3(MC_THREADS), 0, s, P);
-    LVDGS_LAUNCH_CHECK("mesh_visibility", 0, s);
+    if (int e = launch("mesh_visibility", 0, s, mesh_visibility_kernel, dim3((unsigned)(((int64_t)P.V + MC_THREADS - 1) / MC_THREADS)), dim3(MC_THREADS), 0, P)) return e;
     return LVDGS_OK;
 }
 
@@ -266,34 +264,20 @@ int lvdgs_mesh_cull(const lvdgs_mesh_cull_args *a, void *stream) {
         if (int e = check_hip(hipMemsetAsync(P.used, 0, V, s), "mesh_cull_clear")) return e;
     }
     if (F > 0) {
-        ProfScope ps("mesh_cull_flag", s);
-        hipLaunchKernelGGL(cull_faces_flag_kernel, dim3(fs.blocks), block, 0, s, P);
-        LVDGS_LAUNCH_CHECK("mesh_cull_flag", 0, s);
+        if (int e = launch("mesh_cull_flag", 0, s, cull_faces_flag_kernel, dim3(fs.blocks), block, 0, P)) return e;
     }
     const int vblocks = F > 0 ? vs.blocks : 0;   // no face: no vertex is kept
     if (vblocks > 0) {
-        ProfScope ps("mesh_cull_count", s);
-        hipLaunchKernelGGL(cull_vertices_count_kernel, dim3(vblocks), block, 0, s, P);
-        LVDGS_LAUNCH_CHECK("mesh_cull_count", 0, s);
+        if (int e = launch("mesh_cull_count", 0, s, cull_vertices_count_kernel, dim3(vblocks), block, 0, P)) return e;
     }
-    {
-        ProfScope ps("mesh_cull_scan", s);
-        hipLaunchKernelGGL(cull_scan_kernel, dim3(1), block, 0, s, P, vblocks, fs.blocks);
-        LVDGS_LAUNCH_CHECK("mesh_cull_scan", 0, s);
-    }
+    if (int e = launch("mesh_cull_scan", 0, s, cull_scan_kernel, dim3(1), block, 0, P, vblocks, fs.blocks)) return e;
     if (vblocks > 0) {
-        ProfScope ps("mesh_cull_vertices", s);
-        hipLaunchKernelGGL(cull_vertices_kernel, dim3(vblocks), block, 0, s, P);
-        LVDGS_LAUNCH_CHECK("mesh_cull_vertices", 0, s);
+        if (int e = launch("mesh_cull_vertices", 0, s, cull_vertices_kernel, dim3(vblocks), block, 0, P)) return e;
     }
     if (F > 0) {
-        ProfScope ps("mesh_cull_faces", s);
-        hipLaunchKernelGGL(cull_faces_kernel, dim3(fs.blocks), block, 0, s, P);
-        LVDGS_LAUNCH_CHECK("mesh_cull_faces", 0, s);
+        if (int e = launch("mesh_cull_faces", 0, s, cull_faces_kernel, dim3(fs.blocks), block, 0, P)) return e;
     }
-    ProfScope ps("mesh_cull_publish", s);
-    hipLaunchKernelGGL(cull_publish_kernel, dim3(1), dim3(WAVE), 0, s, P);
-    LVDGS_LAUNCH_CHECK("mesh_cull_publish", 0, s);
+    if (int e = launch("mesh_cull_publish", 0, s, cull_publish_kernel, dim3(1), dim3(WAVE), 0, P)) return e;
     return LVDGS_OK;
 }
 

@@ -255,13 +255,9 @@ int lvdgs_mesh_depth(const lvdgs_mesh_depth_args *a, void *stream) {
         if (int e = check_hip(hipMemsetAsync(a->scratch, 0xFF, need, s), "mesh_depth_fill")) return e;
     }
     if (V > 0 && F > 0) {
-        ProfScope ps("mesh_depth_raster", s);
-        hipLaunchKernelGGL(mesh_depth_raster_kernel, dim3((unsigned)((F + MD_THREADS - 1) / MD_THREADS)), dim3(MD_THREADS), 0, s, P);
-        LVDGS_LAUNCH_CHECK("mesh_depth_raster", 0, s);
+        if (int e = launch("mesh_depth_raster", 0, s, mesh_depth_raster_kernel, dim3((unsigned)((F + MD_THREADS - 1) / MD_THREADS)), dim3(MD_THREADS), 0, P)) return e;
     }
-    ProfScope ps("mesh_depth_resolve", s);
-    hipLaunchKernelGGL(mesh_depth_resolve_kernel, dim3(most, (unsigned)a->count), dim3(MD_THREADS), 0, s, P);
-    LVDGS_LAUNCH_CHECK("mesh_depth_resolve", 0, s);
+    if (int e = launch("mesh_depth_resolve", 0, s, mesh_depth_resolve_kernel, dim3(most, (unsigned)a->count), dim3(MD_THREADS), 0, P)) return e;
     return LVDGS_OK;
 }
 

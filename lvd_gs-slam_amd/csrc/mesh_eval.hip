@@ -637,30 +637,12 @@ int lvdgs_mesh_sample(const lvdgs_mesh_sample_args *a, void *stream) {
     P.span = spans.span;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(blocks), block(ME_THREADS);
-    {
-        ProfScope ps("mesh_sample_area", s);
-        hipLaunchKernelGGL(sample_area_kernel, grid, block, 0, s, P);
-        LVDGS_LAUNCH_CHECK("mesh_sample_area", 0, s);
-    }
-    {
-        ProfScope ps("mesh_sample_weight", s);
-        hipLaunchKernelGGL(sample_weight_kernel, grid, block, 0, s, P, blocks);
-        LVDGS_LAUNCH_CHECK("mesh_sample_weight", 0, s);
-    }
-    {
-        ProfScope ps("mesh_sample_scan", s);
-        hipLaunchKernelGGL(sample_scan_kernel, dim3(1), block, 0, s, P, blocks);
-        LVDGS_LAUNCH_CHECK("mesh_sample_scan", 0, s);
-    }
-    {
-        ProfScope ps("mesh_sample_prefix", s);
-        hipLaunchKernelGGL(sample_prefix_kernel, grid, block, 0, s, P);
-        LVDGS_LAUNCH_CHECK("mesh_sample_prefix", 0, s);
-    }
+    if (int e = launch("mesh_sample_area", 0, s, sample_area_kernel, grid, block, 0, P)) return e;
+    if (int e = launch("mesh_sample_weight", 0, s, sample_weight_kernel, grid, block, 0, P, blocks)) return e;
+    if (int e = launch("mesh_sample_scan", 0, s, sample_scan_kernel, dim3(1), block, 0, P, blocks)) return e;
+    if (int e = launch("mesh_sample_prefix", 0, s, sample_prefix_kernel, grid, block, 0, P)) return e;
     const size_t sample_blocks = ((size_t)P.n + ME_THREADS - 1) / ME_THREADS;
-    ProfScope ps("mesh_sample_points", s);
-    hipLaunchKernelGGL(sample_points_kernel, dim3((unsigned)(sample_blocks < 8192 ? sample_blocks : 8192)), block, 0, s, P);
-    LVDGS_LAUNCH_CHECK("mesh_sample_points", 0, s);
+    if (int e = launch("mesh_sample_points", 0, s, sample_points_kernel, dim3((unsigned)(sample_blocks < 8192 ? sample_blocks : 8192)), block, 0, P)) return e;
     return LVDGS_OK;
 }
 
@@ -709,55 +691,24 @@ int lvdgs_cloud_distance(const lvdgs_cloud_distance_args *a, void *stream) {
     auto blocks_for = [](uint32_t n, int most) { const int64_t b = ((int64_t)n + ME_THREADS - 1) / ME_THREADS; return (unsigned)(b < 1 ? 1 : b > most ? most : b); };
     const unsigned box_blocks = P.N ? blocks_for(P.N, CD_BOX_BLOCKS) : 0u;
     if (box_blocks) {
-        ProfScope ps("cloud_box", s);
-        hipLaunchKernelGGL(cloud_box_kernel, dim3(box_blocks), block, 0, s, P);
-        LVDGS_LAUNCH_CHECK("cloud_box", 0, s);
+        if (int e = launch("cloud_box", 0, s, cloud_box_kernel, dim3(box_blocks), block, 0, P)) return e;
     }
-    {
-        ProfScope ps("cloud_grid", s);
-        hipLaunchKernelGGL(cloud_grid_kernel, dim3(1), block, 0, s, P, (int)box_blocks);
-        LVDGS_LAUNCH_CHECK("cloud_grid", 0, s);
-    }
+    if (int e = launch("cloud_grid", 0, s, cloud_grid_kernel, dim3(1), block, 0, P, (int)box_blocks)) return e;
     const unsigned both = blocks_for(P.M > P.N ? P.M : P.N, 4096);
-    {
-        ProfScope ps("cloud_zero", s);
-        hipLaunchKernelGGL(cloud_zero_kernel, dim3(blocks_for((uint32_t)P.budget + 1u, 1024)), block, 0, s, P);
-        LVDGS_LAUNCH_CHECK("cloud_zero", 0, s);
-    }
-    {
-        ProfScope ps("cloud_count", s);
-        hipLaunchKernelGGL(cloud_count_kernel, dim3(both, 2), block, 0, s, P);
-        LVDGS_LAUNCH_CHECK("cloud_count", 0, s);
-    }
+    if (int e = launch("cloud_zero", 0, s, cloud_zero_kernel, dim3(blocks_for((uint32_t)P.budget + 1u, 1024)), block, 0, P)) return e;
+    if (int e = launch("cloud_count", 0, s, cloud_count_kernel, dim3(both, 2), block, 0, P)) return e;
     {
         ProfScope ps("cloud_cell_scan", s);
-        hipLaunchKernelGGL(cloud_span_sum_kernel, dim3(CD_SCAN_BLOCKS, 2), block, 0, s, P);
-        LVDGS_LAUNCH_CHECK("cloud_span_sum", 0, s);
-        hipLaunchKernelGGL(cloud_span_scan_kernel, dim3(1), block, 0, s, P);
-        LVDGS_LAUNCH_CHECK("cloud_span_scan", 0, s);
-        hipLaunchKernelGGL(cloud_span_write_kernel, dim3(CD_SCAN_BLOCKS, 2), block, 0, s, P);
-        LVDGS_LAUNCH_CHECK("cloud_span_write", 0, s);
+        if (int e = launch_checked("cloud_span_sum", 0, s, cloud_span_sum_kernel, dim3(CD_SCAN_BLOCKS, 2), block, 0, P)) return e;
+        if (int e = launch_checked("cloud_span_scan", 0, s, cloud_span_scan_kernel, dim3(1), block, 0, P)) return e;
+        if (int e = launch_checked("cloud_span_write", 0, s, cloud_span_write_kernel, dim3(CD_SCAN_BLOCKS, 2), block, 0, P)) return e;
     }
-    {
-        ProfScope ps("cloud_scatter", s);
-        hipLaunchKernelGGL(cloud_scatter_kernel, dim3(both, 2), block, 0, s, P);
-        LVDGS_LAUNCH_CHECK("cloud_scatter", 0, s);
-    }
-    {
-        ProfScope ps("cloud_search", s);
-        hipLaunchKernelGGL(cloud_search_kernel, dim3(CD_SEARCH_BLOCKS), dim3(CD_SEARCH_THREADS), 0, s, P);
-        LVDGS_LAUNCH_CHECK("cloud_search", 0, s);
-    }
+    if (int e = launch("cloud_scatter", 0, s, cloud_scatter_kernel, dim3(both, 2), block, 0, P)) return e;
+    if (int e = launch("cloud_search", 0, s, cloud_search_kernel, dim3(CD_SEARCH_BLOCKS), dim3(CD_SEARCH_THREADS), 0, P)) return e;
     const unsigned sum_blocks = blocks_for(P.M, CD_SUM_BLOCKS);
     const uint32_t chunk = (uint32_t)(((uint64_t)P.M + sum_blocks - 1) / sum_blocks);
-    {
-        ProfScope ps("cloud_sum", s);
-        hipLaunchKernelGGL(cloud_sum_kernel, dim3(sum_blocks), block, 0, s, P, chunk);
-        LVDGS_LAUNCH_CHECK("cloud_sum", 0, s);
-    }
-    ProfScope ps("cloud_finish", s);
-    hipLaunchKernelGGL(cloud_finish_kernel, dim3(1), block, 0, s, P, (int)sum_blocks);
-    LVDGS_LAUNCH_CHECK("cloud_finish", 0, s);
+    if (int e = launch("cloud_sum", 0, s, cloud_sum_kernel, dim3(sum_blocks), block, 0, P, chunk)) return e;
+    if (int e = launch("cloud_finish", 0, s, cloud_finish_kernel, dim3(1), block, 0, P, (int)sum_blocks)) return e;
     return LVDGS_OK;
 }
 

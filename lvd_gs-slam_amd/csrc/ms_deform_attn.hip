@@ -209,11 +209,8 @@ int lvdgs_ms_deform_attn_forward(const float *value, const int64_t *spatial_shap
     const bool four = wide && P % 4 == 0 && aligned16(sampling_loc) && aligned16(attn_weight);
     const int gp_log2 = msda_group_log2(wide ? D / 4 : D);
     const dim3 grid((unsigned)(((groups << gp_log2) + 255) / 256)), block(256);
-    ProfScope ps("msda_fwd", s);
-    if (four) hipLaunchKernelGGL((msda_fwd_kernel<4, 4>), grid, block, 0, s, value, spatial_shapes, level_start, sampling_loc, attn_weight, S, H, D, Q, L, P, groups, gp_log2, out);
-    else if (wide) hipLaunchKernelGGL((msda_fwd_kernel<4, 1>), grid, block, 0, s, value, spatial_shapes, level_start, sampling_loc, attn_weight, S, H, D, Q, L, P, groups, gp_log2, out);
-    else hipLaunchKernelGGL((msda_fwd_kernel<1, 1>), grid, block, 0, s, value, spatial_shapes, level_start, sampling_loc, attn_weight, S, H, D, Q, L, P, groups, gp_log2, out);
-    LVDGS_LAUNCH_CHECK("msda_fwd", 0, s);
+    const auto kernel = wide ? (four ? msda_fwd_kernel<4, 4> : msda_fwd_kernel<4, 1>) : msda_fwd_kernel<1, 1>;   // (four implies wide)
+    if (int e = launch("msda_fwd", 0, s, kernel, grid, block, 0, value, spatial_shapes, level_start, sampling_loc, attn_weight, S, H, D, Q, L, P, groups, gp_log2, out)) return e;
     return LVDGS_OK;
 }
 
@@ -238,10 +235,8 @@ int lvdgs_ms_deform_attn_backward(const float *value, const int64_t *spatial_sha
     if (int e = check_hip(hipMemsetAsync(grad_value, 0, value_bytes, s), "ms_deform_attn_backward (memset)")) return e;
     const int gp_log2 = msda_group_log2(D);
     const dim3 grid((unsigned)(((groups << gp_log2) + 255) / 256)), block(256);
-    ProfScope ps("msda_bwd", s);
-    hipLaunchKernelGGL(msda_bwd_kernel, grid, block, 0, s, value, spatial_shapes, level_start, sampling_loc, attn_weight, grad_out, S, H, D, Q, L, P,
-                       groups, gp_log2, grad_value, grad_sampling_loc, grad_attn_weight);
-    LVDGS_LAUNCH_CHECK("msda_bwd", 0, s);
+    if (int e = launch("msda_bwd", 0, s, msda_bwd_kernel, grid, block, 0, value, spatial_shapes, level_start, sampling_loc, attn_weight, grad_out, S, H, D, Q, L, P,
+            groups, gp_log2, grad_value, grad_sampling_loc, grad_attn_weight)) return e;
     return LVDGS_OK;
 }
 

@@ -519,16 +519,12 @@ int run_flow(int W, int H, const lvdgs_farneback_params &p, const Level *levels,
                 }
                 for (int j = 0; j < lv.ksize; j++) L.taps[j] = (float)(t[j] / sum);
             }
-            ProfScope ps("of_level", s);
-            hipLaunchKernelGGL(of_level_kernel, dim3(cdiv(lv.w, OF_TX), cdiv(lv.h, OF_ROWS), 2), dim3(OF_THREADS), 0, s, L);
-            LVDGS_LAUNCH_CHECK("of_level", 0, s);
+            if (int e = launch("of_level", 0, s, of_level_kernel, dim3(cdiv(lv.w, OF_TX), cdiv(lv.h, OF_ROWS), 2), dim3(OF_THREADS), 0, L)) return e;
         }
         {
             poly.w = lv.w; poly.h = lv.h;
             poly.img[0] = fs.img[0]; poly.img[1] = fs.img[1]; poly.R[0] = fs.R[0]; poly.R[1] = fs.R[1];
-            ProfScope ps("of_polyexp", s);
-            hipLaunchKernelGGL(of_polyexp_kernel, dim3(cdiv(lv.w, OF_TX), cdiv(lv.h, OF_POLY_TY), 2), dim3(OF_THREADS), 0, s, poly);
-            LVDGS_LAUNCH_CHECK("of_polyexp", 0, s);
+            if (int e = launch("of_polyexp", 0, s, of_polyexp_kernel, dim3(cdiv(lv.w, OF_TX), cdiv(lv.h, OF_POLY_TY), 2), dim3(OF_THREADS), 0, poly)) return e;
         }
         FlowParams F{};
         F.w = lv.w; F.h = lv.h; F.pw = pw; F.ph = ph;
@@ -537,17 +533,11 @@ int run_flow(int W, int H, const lvdgs_farneback_params &p, const Level *levels,
         F.inv_area = (float)(1.0 / ((double)p.winsize * p.winsize));
         F.R0 = fs.R[0]; F.R1 = fs.R[1]; F.prev_flow = prev_flow; F.flow = cur_flow;
         F.M_out = fs.M[0];
-        {
-            ProfScope ps("of_matrices", s);
-            hipLaunchKernelGGL(of_matrices_kernel, dim3(cdiv(lv.w, OF_TX), cdiv(lv.h, OF_ROWS)), dim3(OF_THREADS), 0, s, F);
-            LVDGS_LAUNCH_CHECK("of_matrices", 0, s);
-        }
+        if (int e = launch("of_matrices", 0, s, of_matrices_kernel, dim3(cdiv(lv.w, OF_TX), cdiv(lv.h, OF_ROWS)), dim3(OF_THREADS), 0, F)) return e;
         for (int it = 0; it < p.iterations; it++) {
             F.M_in = fs.M[it & 1]; F.M_out = fs.M[(it + 1) & 1];
             F.last = it == p.iterations - 1;
-            ProfScope ps("of_update", s);
-            hipLaunchKernelGGL(of_update_kernel, dim3(cdiv(lv.w, OF_TX), cdiv(lv.h, ty)), dim3(OF_THREADS), 0, s, F);
-            LVDGS_LAUNCH_CHECK("of_update", 0, s);
+            if (int e = launch("of_update", 0, s, of_update_kernel, dim3(cdiv(lv.w, OF_TX), cdiv(lv.h, ty)), dim3(OF_THREADS), 0, F)) return e;
         }
         pw = lv.w; ph = lv.h;
     }
@@ -612,9 +602,7 @@ int lvdgs_motion_mask(const lvdgs_motion_mask_args *a, void *stream) {
     MmHeader *header = st.header; uint8_t *stored = st.stored;
     const int grey_blocks = (int)min((int64_t)cdiv(px, OF_THREADS), (int64_t)4 * MM_MAX_BLOCKS);
     if (observe) {
-        ProfScope ps("of_grey", s);
-        hipLaunchKernelGGL(of_grey_kernel, dim3(grey_blocks), dim3(OF_THREADS), 0, s, a->image, px, stored, header, W, H);
-        LVDGS_LAUNCH_CHECK("of_grey", 0, s);
+        if (int e = launch("of_grey", 0, s, of_grey_kernel, dim3(grey_blocks), dim3(OF_THREADS), 0, a->image, px, stored, header, W, H)) return e;
         return LVDGS_OK;
     }
     MmScratch w;
@@ -628,23 +616,11 @@ int lvdgs_motion_mask(const lvdgs_motion_mask_args *a, void *stream) {
     P.flow = flow; P.cur = cur; P.mask = a->mask; P.info = a->info; P.header = header; P.stored = stored;
     P.plane = w.plane;
     if (int e = check_hip(hipMemsetAsync(a->info, 0, LVDGS_MOTION_INFO_WORDS * sizeof(int32_t), s), "motion mask: clearing info")) return e;
-    {
-        ProfScope ps("of_grey", s);
-        hipLaunchKernelGGL(of_grey_kernel, dim3(grey_blocks), dim3(OF_THREADS), 0, s, a->image, px, cur, (MmHeader *)nullptr, W, H);
-        LVDGS_LAUNCH_CHECK("of_grey", 0, s);
-    }
+    if (int e = launch("of_grey", 0, s, of_grey_kernel, dim3(grey_blocks), dim3(OF_THREADS), 0, a->image, px, cur, (MmHeader *)nullptr, W, H)) return e;
     if (int e = run_flow(W, H, a->params, levels, num_levels, stored, cur, flow, w.flow_scratch, s)) return e;
     const int wave_blocks = (int)min((int64_t)cdiv(P.words, OF_ROWS), (int64_t)MM_MAX_BLOCKS);
-    {
-        ProfScope ps("of_moving", s);
-        hipLaunchKernelGGL(of_moving_kernel, dim3(wave_blocks), dim3(OF_THREADS), 0, s, P);
-        LVDGS_LAUNCH_CHECK("of_moving", 0, s);
-    }
-    {
-        ProfScope ps("of_dilate", s);
-        hipLaunchKernelGGL(of_dilate_kernel, dim3(wave_blocks), dim3(OF_THREADS), 0, s, P);
-        LVDGS_LAUNCH_CHECK("of_dilate", 0, s);
-    }
+    if (int e = launch("of_moving", 0, s, of_moving_kernel, dim3(wave_blocks), dim3(OF_THREADS), 0, P)) return e;
+    if (int e = launch("of_dilate", 0, s, of_dilate_kernel, dim3(wave_blocks), dim3(OF_THREADS), 0, P)) return e;
     return LVDGS_OK;
 }
 

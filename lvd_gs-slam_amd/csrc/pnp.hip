@@ -423,16 +423,8 @@ int lvdgs_pnp_ransac(const lvdgs_pnp_args *a, void *stream) {
     P.thr2 = a->reproj_error * a->reproj_error;
     P.depth = a->depth; P.m1 = a->matches_im1; P.m2 = a->matches_im2; P.mask = a->inlier_mask;
     if (int e = host_block_address(a->host_state, "pnp", &P.host_state)) return e;
-    {
-        ProfScope ps("pnp_gather", s);
-        hipLaunchKernelGGL(pnp_gather_kernel, dim3(cdiv(P.M > 0 ? P.M : 1, PNP_THREADS)), dim3(PNP_THREADS), 0, s, P);
-        LVDGS_LAUNCH_CHECK("pnp_gather", 0, s);
-    }
-    {
-        ProfScope ps("pnp_hypotheses", s);
-        hipLaunchKernelGGL(pnp_hypotheses_kernel, dim3(cdiv(P.hyp, PNP_WAVES)), dim3(PNP_THREADS), 0, s, P);
-        LVDGS_LAUNCH_CHECK("pnp_hypotheses", 0, s);
-    }
+    if (int e = launch("pnp_gather", 0, s, pnp_gather_kernel, dim3(cdiv(P.M > 0 ? P.M : 1, PNP_THREADS)), dim3(PNP_THREADS), 0, P)) return e;
+    if (int e = launch("pnp_hypotheses", 0, s, pnp_hypotheses_kernel, dim3(cdiv(P.hyp, PNP_WAVES)), dim3(PNP_THREADS), 0, P)) return e;
     return LVDGS_OK;
 }
 

@@ -274,9 +274,7 @@ extern "C" int lvdgs_pose_step(const lvdgs_pose_step_args *a, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     if (int e = check_pose_args(a)) return e;
     PoseStepParams pp{*a};
-    ProfScope ps("pose_step", s);
-    hipLaunchKernelGGL(pose_step_kernel, dim3(1), dim3(64), 0, s, pp);
-    LVDGS_LAUNCH_CHECK("pose_step", 0, s);
+    if (int e = launch("pose_step", 0, s, pose_step_kernel, dim3(1), dim3(64), 0, pp)) return e;
     return LVDGS_OK;
 }
 
@@ -337,10 +335,7 @@ extern "C" int lvdgs_tracking_tail(const lvdgs_loss_args *loss, const lvdgs_args
     hipStream_t s = (hipStream_t)stream;
     TailParams t;
     if (int e = make_tail_params(loss, bwd, pose, dL_dtau, partials_per_tile, t)) return e;
-    ProfScope ps("tracking_tail", s);
-    if (partials_per_tile) hipLaunchKernelGGL(tracking_tail_kernel<1024>, dim3(1), dim3(1024), 0, s, t);
-    else hipLaunchKernelGGL(tracking_tail_kernel<256>, dim3(1), dim3(256), 0, s, t);
-    LVDGS_LAUNCH_CHECK("tracking_tail", 0, s);
+    if (int e = launch("tracking_tail", 0, s, partials_per_tile ? tracking_tail_kernel<1024> : tracking_tail_kernel<256>, dim3(1), dim3(partials_per_tile ? 1024 : 256), 0, t)) return e;
     return LVDGS_OK;
 }
 
@@ -354,9 +349,7 @@ extern "C" int lvdgs_map_view_tail(const lvdgs_loss_args *loss, const lvdgs_args
         set_error("map view tail: a statistics pointer is NULL"); return LVDGS_E_INVALID;
     }
     const ViewStats v{N, bwd->radii, bwd->n_touched, bwd->dL_dmeans2D, stats->radii_max, stats->norm_sum, stats->vis_count, stats->touched_row, stats->split_xy};
-    ProfScope ps("map_view_tail", s);
-    hipLaunchKernelGGL(map_view_tail_kernel, dim3(1 + cdiv(N, 1024)), dim3(1024), 0, s, t, v);
-    LVDGS_LAUNCH_CHECK("map_view_tail", 0, s);
+    if (int e = launch("map_view_tail", 0, s, map_view_tail_kernel, dim3(1 + cdiv(N, 1024)), dim3(1024), 0, t, v)) return e;
     return LVDGS_OK;
 }
 
@@ -383,9 +376,7 @@ extern "C" int lvdgs_map_view_tail_batch(const lvdgs_loss_args *const *losses, c
                                  ViewStats{N, bwd->radii, bwd->n_touched, bwd->dL_dmeans2D, st->radii_max, st->norm_sum, st->vis_count, st->touched_row, st->split_xy}};
             max_n = N > max_n ? N : max_n;
         }
-        ProfScope ps("map_view_tail", s);
-        hipLaunchKernelGGL(map_view_tail_batch_kernel, dim3(n + cdiv(max_n, 1024)), dim3(1024), 0, s, b);
-        LVDGS_LAUNCH_CHECK("map_view_tail (batch)", 0, s);
+        if (int e = launch({"map_view_tail", "map_view_tail (batch)"}, 0, s, map_view_tail_batch_kernel, dim3(n + cdiv(max_n, 1024)), dim3(1024), 0, b)) return e;
     }
     return LVDGS_OK;
 }
@@ -400,9 +391,7 @@ extern "C" int lvdgs_pose_step_batch(const lvdgs_pose_step_args *steps, int32_t 
             if (int e = check_pose_args(steps + first + i)) return e;
             pp.a[i] = steps[first + i];
         }
-        ProfScope ps("pose_step", s);
-        hipLaunchKernelGGL(pose_step_batch_kernel, dim3(n), dim3(64), 0, s, pp);
-        LVDGS_LAUNCH_CHECK("pose_step", 0, s);
+        if (int e = launch("pose_step", 0, s, pose_step_batch_kernel, dim3(n), dim3(64), 0, pp)) return e;
     }
     return LVDGS_OK;
 }

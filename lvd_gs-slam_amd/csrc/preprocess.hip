@@ -318,9 +318,7 @@ int launch_preprocess_fwd(const lvdgs_args &a, const GeomView &g, uint32_t *bloc
     if (a.num_gaussians == 0) return LVDGS_OK;
     FwdParams p = make_fwd_params(a, g);
     p.blocksums = blocksums;
-    ProfScope ps("preprocess_fwd", s);
-    hipLaunchKernelGGL(preprocess_fwd_kernel, dim3(cdiv(p.N, 256)), dim3(256), 0, s, p);
-    LVDGS_LAUNCH_CHECK("preprocess_fwd", a.debug, s);
+    if (int e = launch("preprocess_fwd", a.debug, s, preprocess_fwd_kernel, dim3(cdiv(p.N, 256)), dim3(256), 0, p)) return e;
     return LVDGS_OK;
 }
 
@@ -332,11 +330,11 @@ static void count_super_tiles_too(FwdParams &p, const lvdgs_args &a, const Rende
 
 // A counting kernel's launch: its dynamic LDS (the tiles' counters, SUPER: the super tiles' behind them) allowed once per kernel (done).
 template <bool SUPER_COUNT, class... Params, class... Args>
-static int launch_count_kernel(void (*kernel)(Params...), unsigned char (&done)[16], dim3 grid, int threads, size_t lds, hipStream_t s, Args... args) {
+static int launch_count_kernel(const char *name, int debug, void (*kernel)(Params...), unsigned char (&done)[16], dim3 grid, int threads, size_t lds, hipStream_t s,
+                               Args... args) {
     constexpr int LDS_MAX = (SUPER_COUNT ? GROUP_MAX_TILES + GROUP_MAX_TILES / (SUPER * SUPER) + 64 : GROUP_MAX_TILES) * 4;
     if (int e = allow_dynamic_lds(reinterpret_cast<const void *>(kernel), LDS_MAX, done)) return e;
-    hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, s, args...);
-    return LVDGS_OK;
+    return launch_checked(name, debug, s, kernel, grid, dim3(threads), lds, args...);
 }
 
 int launch_preprocess_count(const lvdgs_args &a, const GeomView &g, const ImageView &im, const RenderScratch &w, hipStream_t s) {
@@ -352,12 +350,11 @@ int launch_preprocess_count(const lvdgs_args &a, const GeomView &g, const ImageV
     ProfScope ps("preprocess_fwd", s);
     if (int e = group_dispatch(group_shape_for(N), [&](auto threads_, auto owners_, auto per_, int d) {
             constexpr int THREADS = decltype(threads_)::value, OWNERS = decltype(owners_)::value, PER = decltype(per_)::value;
-            if (super) return launch_count_kernel<true>(preprocess_count_kernel<THREADS, OWNERS, PER, true>, done[GROUP_SHAPES + d], dim3(nchunks), THREADS, lds, s,
-                                                        p, T, w.group_hist, w.chunk_sums, a.n_touched, im.long_count);
-            return launch_count_kernel<false>(preprocess_count_kernel<THREADS, OWNERS, PER>, done[d], dim3(nchunks), THREADS, lds, s,
+            if (super) return launch_count_kernel<true>("preprocess_count", a.debug, preprocess_count_kernel<THREADS, OWNERS, PER, true>, done[GROUP_SHAPES + d], dim3(nchunks),
+                                                        THREADS, lds, s, p, T, w.group_hist, w.chunk_sums, a.n_touched, im.long_count);
+            return launch_count_kernel<false>("preprocess_count", a.debug, preprocess_count_kernel<THREADS, OWNERS, PER>, done[d], dim3(nchunks), THREADS, lds, s,
                                               p, T, w.group_hist, w.chunk_sums, a.n_touched, im.long_count);
         })) return e;
-    LVDGS_LAUNCH_CHECK("preprocess_count", a.debug, s);
     return LVDGS_OK;
 }
 
@@ -379,18 +376,16 @@ int launch_preprocess_count_batch(const lvdgs_args *const *a, const GeomView *g,
     ProfScope ps("preprocess_fwd", s);
     if (int e = group_dispatch(group_shape_for(N), [&](auto threads_, auto owners_, auto per_, int d) {
             constexpr int THREADS = decltype(threads_)::value, OWNERS = decltype(owners_)::value, PER = decltype(per_)::value;
-            if (super) return launch_count_kernel<true>(preprocess_count_batch_kernel<THREADS, OWNERS, PER, true>, done[GROUP_SHAPES + d], dim3(nchunks, n), THREADS, lds, s, batch, T);
-            return launch_count_kernel<false>(preprocess_count_batch_kernel<THREADS, OWNERS, PER>, done[d], dim3(nchunks, n), THREADS, lds, s, batch, T);
+            const char *name = "preprocess_count (batch)";
+            if (super) return launch_count_kernel<true>(name, a[0]->debug, preprocess_count_batch_kernel<THREADS, OWNERS, PER, true>, done[GROUP_SHAPES + d], dim3(nchunks, n), THREADS, lds, s, batch, T);
+            return launch_count_kernel<false>(name, a[0]->debug, preprocess_count_batch_kernel<THREADS, OWNERS, PER>, done[d], dim3(nchunks, n), THREADS, lds, s, batch, T);
         })) return e;
-    LVDGS_LAUNCH_CHECK("preprocess_count (batch)", a[0]->debug, s);
     return LVDGS_OK;
 }
 
 int launch_mark_visible(int N, const float *means3D, const float *view, uint8_t *present, hipStream_t s) {
     if (N == 0) return LVDGS_OK;
-    ProfScope ps("mark_visible", s);
-    hipLaunchKernelGGL(mark_visible_kernel, dim3(cdiv(N, 256)), dim3(256), 0, s, N, means3D, view, present);
-    LVDGS_LAUNCH_CHECK("mark_visible", 0, s);
+    if (int e = launch("mark_visible", 0, s, mark_visible_kernel, dim3(cdiv(N, 256)), dim3(256), 0, N, means3D, view, present)) return e;
     return LVDGS_OK;
 }
 

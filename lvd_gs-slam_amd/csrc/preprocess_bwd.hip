@@ -1019,15 +1019,11 @@ int launch_preprocess_bwd(const lvdgs_args &a, const GeomView &g, const BwdScrat
         p.rec = g.rec; p.tiles_touched = g.tiles_touched; p.slot_base = g.slot_base; p.pair_grads = b.pair_grads; p.pair_valid = pair_valid;
         p.dmeans2D = a.dL_dmeans2D; p.tau_part = b.tau_part;
         p.pair_total = pair_total; p.pair_total_super = pair_total_super; p.pair_capacity = pair_capacity;
-        ProfScope ps("preprocess_bwd", s);
         const bool helpers = (a.flags & LVDGS_FLAG_SUPER_TILES) != 0;
-        hipLaunchKernelGGL(bwd_kernel_for((a.flags & LVDGS_FLAG_POSE_ONLY) != 0, helpers), dim3(nblk), dim3(helpers ? 512 : 256), 0, s, p);
-        LVDGS_LAUNCH_CHECK("preprocess_bwd", a.debug, s);
+        if (int e = launch("preprocess_bwd", a.debug, s, bwd_kernel_for((a.flags & LVDGS_FLAG_POSE_ONLY) != 0, helpers), dim3(nblk), dim3(helpers ? 512 : 256), 0, p)) return e;
     }
     if (a.dL_dtau) {   // NULL: the partials stay in the scratch for lvdgs_tracking_tail
-        ProfScope ps("tau_reduce", s);
-        hipLaunchKernelGGL(tau_reduce_kernel, dim3(1), dim3(256), 0, s, b.tau_part, nblk, a.dL_dtau);
-        LVDGS_LAUNCH_CHECK("tau_reduce", a.debug, s);
+        if (int e = launch("tau_reduce", a.debug, s, tau_reduce_kernel, dim3(1), dim3(256), 0, b.tau_part, nblk, a.dL_dtau)) return e;
     }
     return LVDGS_OK;
 }
@@ -1049,17 +1045,14 @@ int launch_preprocess_bwd_views(const lvdgs_args *const *a, const GeomView *g, c
             const int v = first + k;
             bv.v[k] = BwdView{make_cam(*a[v]), a[v]->radii, g[v].rec, g[v].tiles_touched, g[v].slot_base, w[v].pair_grads, b[v].pair_valid, a[v]->dL_dmeans2D, w[v].tau_part};
         }
-        ProfScope ps("preprocess_bwd", s);
-        if (a0.flags & LVDGS_FLAG_SUPER_TILES) hipLaunchKernelGGL(preprocess_bwd_views_helpers_kernel, dim3(nblk), dim3(512), 0, s, bv);   // (as in launch_preprocess_bwd)
-        else hipLaunchKernelGGL(preprocess_bwd_views_kernel, dim3(nblk), dim3(256), 0, s, bv);
-        LVDGS_LAUNCH_CHECK("preprocess_bwd (views)", a0.debug, s);
+        const bool helpers = (a0.flags & LVDGS_FLAG_SUPER_TILES) != 0;   // (as in launch_preprocess_bwd)
+        if (int e = launch({"preprocess_bwd", "preprocess_bwd (views)"}, a0.debug, s, helpers ? preprocess_bwd_views_helpers_kernel : preprocess_bwd_views_kernel,
+                dim3(nblk), dim3(helpers ? 512 : 256), 0, bv)) return e;
     }
     for (int v = 0; v < n; v++)
         if (a[v]->dL_dtau) {
             if (N == 0) { if (int e = check_hip(hipMemsetAsync(a[v]->dL_dtau, 0, 6 * sizeof(float), s), "memset tau")) return e; continue; }
-            ProfScope ps("tau_reduce", s);
-            hipLaunchKernelGGL(tau_reduce_kernel, dim3(1), dim3(256), 0, s, w[v].tau_part, nblk, a[v]->dL_dtau);
-            LVDGS_LAUNCH_CHECK("tau_reduce", a[v]->debug, s);
+            if (int e = launch("tau_reduce", a[v]->debug, s, tau_reduce_kernel, dim3(1), dim3(256), 0, w[v].tau_part, nblk, a[v]->dL_dtau)) return e;
         }
     return LVDGS_OK;
 }

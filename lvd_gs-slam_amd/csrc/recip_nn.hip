@@ -333,33 +333,16 @@ int lvdgs_reciprocal_nn(const lvdgs_recip_nn_args *a, void *stream) {
     int n2 = 2 * RNN_ONE;
     while (n2 < P.seeds) n2 *= 2;
     if (int e = allow_dynamic_lds(reinterpret_cast<const void *>(&rnn_final_kernel), LVDGS_RNN_MAX_SEEDS * (int)sizeof(u64), lds_done)) return e;
-    {
-        ProfScope ps("rnn_init", s);
-        hipLaunchKernelGGL(rnn_init_kernel, dim3(cdiv(P.seeds, RNN_THREADS)), dim3(RNN_THREADS), 0, s, P);
-        LVDGS_LAUNCH_CHECK("rnn_init", 0, s);
-    }
+    if (int e = launch("rnn_init", 0, s, rnn_init_kernel, dim3(cdiv(P.seeds, RNN_THREADS)), dim3(RNN_THREADS), 0, P)) return e;
     const int groups = cdiv(P.seeds, RNN_QGROUP);
     const int ks = (P.D + 1) / 2;
     for (int half = 0; half < 2 * a->max_iter; half++) {
         const int N = (half & 1) ? P.W1 * P.H1 : P.W2 * P.H2;
         const dim3 grid(cdiv(cdiv(N, RNN_TILE), RNN_WAVES * RNN_WAVE_TILES), groups);
-        {
-            ProfScope ps("rnn_search", s);
-            if (ks == 12) hipLaunchKernelGGL(rnn_search_kernel<12>, grid, dim3(RNN_THREADS), 0, s, P, half);
-            else hipLaunchKernelGGL(rnn_search_kernel<0>, grid, dim3(RNN_THREADS), 0, s, P, half);
-            LVDGS_LAUNCH_CHECK("rnn_search", 0, s);
-        }
-        {
-            ProfScope ps("rnn_update", s);
-            hipLaunchKernelGGL(rnn_update_kernel, dim3(1), dim3(RNN_ONE), 0, s, P, half);
-            LVDGS_LAUNCH_CHECK("rnn_update", 0, s);
-        }
+        if (int e = launch("rnn_search", 0, s, ks == 12 ? rnn_search_kernel<12> : rnn_search_kernel<0>, grid, dim3(RNN_THREADS), 0, P, half)) return e;
+        if (int e = launch("rnn_update", 0, s, rnn_update_kernel, dim3(1), dim3(RNN_ONE), 0, P, half)) return e;
     }
-    {
-        ProfScope ps("rnn_final", s);
-        hipLaunchKernelGGL(rnn_final_kernel, dim3(1), dim3(RNN_ONE), (size_t)n2 * sizeof(u64), s, P, n2);
-        LVDGS_LAUNCH_CHECK("rnn_final", 0, s);
-    }
+    if (int e = launch("rnn_final", 0, s, rnn_final_kernel, dim3(1), dim3(RNN_ONE), (size_t)n2 * sizeof(u64), P, n2)) return e;
     return LVDGS_OK;
 }
 

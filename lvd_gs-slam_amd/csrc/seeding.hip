@@ -195,24 +195,10 @@ int lvdgs_seed_points(const lvdgs_seed_args *a, void *stream) {
     if (S.want_median)
         if (int e = launch_select(AllDepthSource{S.depth}, P, S.st_median, select_rank(-1), "seed_median", s)) return e;
     if (int e = launch_select(KeySource{S.depth, S.trunc, S.seed_lo, S.seed_hi}, P, S.st_key, SelectRank{-1, S.inv_downsample}, "seed_threshold", s)) return e;
-    {
-        ProfScope ps("seed_count", s);
-        hipLaunchKernelGGL(seed_count_kernel, dim3(blocks), dim3(SEED_THREADS), 0, s, S);
-        LVDGS_LAUNCH_CHECK("seed_count", 0, s);
-    }
-    {
-        ProfScope ps("seed_scan", s);
-        hipLaunchKernelGGL(seed_scan_kernel, dim3(1), dim3(SEED_THREADS), 0, s, S, blocks);
-        LVDGS_LAUNCH_CHECK("seed_scan", 0, s);
-    }
-    {
-        ProfScope ps("seed_write", s);
-        hipLaunchKernelGGL(seed_write_kernel, dim3(blocks), dim3(SEED_THREADS), 0, s, S);
-        LVDGS_LAUNCH_CHECK("seed_write", 0, s);
-    }
-    ProfScope ps("seed_publish", s);
-    hipLaunchKernelGGL(seed_publish_kernel, dim3(1), dim3(WAVE), 0, s, S);
-    LVDGS_LAUNCH_CHECK("seed_publish", 0, s);
+    if (int e = launch("seed_count", 0, s, seed_count_kernel, dim3(blocks), dim3(SEED_THREADS), 0, S)) return e;
+    if (int e = launch("seed_scan", 0, s, seed_scan_kernel, dim3(1), dim3(SEED_THREADS), 0, S, blocks)) return e;
+    if (int e = launch("seed_write", 0, s, seed_write_kernel, dim3(blocks), dim3(SEED_THREADS), 0, S)) return e;
+    if (int e = launch("seed_publish", 0, s, seed_publish_kernel, dim3(1), dim3(WAVE), 0, S)) return e;
     return LVDGS_OK;
 }
 

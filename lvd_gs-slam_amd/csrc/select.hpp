@@ -167,8 +167,7 @@ int launch_select(const Src &src, int64_t n, SelectState *st, SelectRank rank, c
     ProfScope ps(name, s);
     const int blocks = select_blocks(n);
     for (int pass = 0; pass < SEL_PASSES; pass++) {
-        hipLaunchKernelGGL(select_pass_kernel<Src>, dim3(blocks), dim3(SEL_THREADS), 0, s, src, n, st, pass, rank);
-        LVDGS_LAUNCH_CHECK(name, 0, s);
+        if (int e = launch_checked(name, 0, s, select_pass_kernel<Src>, dim3(blocks), dim3(SEL_THREADS), 0, src, n, st, pass, rank)) return e;
     }
     return LVDGS_OK;
 }

@@ -227,22 +227,9 @@ int radix_sort_pairs(uint32_t *keys_a, uint32_t *vals_a, uint32_t *keys_b, uint3
         // spread the bits evenly over the passes (13 bits -> 7 + 6)
         const int nbits = (total_bits - shift + (passes - p) - 1) / (passes - p);
         const int nbins = 1 << nbits;
-        {
-            ProfScope ps("radix_hist", s);
-            hipLaunchKernelGGL(radix_hist_kernel, dim3(nblk), dim3(SORT_THREADS), 0, s, kin, n, n_dev, shift, nbits, hist, nblk);
-            LVDGS_LAUNCH_CHECK("radix_hist", dbg, s);
-        }
-        {
-            ProfScope ps("radix_rowscan", s);
-            hipLaunchKernelGGL(radix_rowscan_kernel, dim3(cdiv(nbins, 4)), dim3(256), 0, s, hist, totals, nbins, nblk);
-            LVDGS_LAUNCH_CHECK("radix_rowscan", dbg, s);
-        }
-        {
-            ProfScope ps("radix_scatter", s);
-            hipLaunchKernelGGL(radix_scatter_kernel, dim3(nblk), dim3(SORT_THREADS), 0, s, kin, vin, kout, vout, hist, totals,
-                               n, n_dev, shift, nbits, nblk);
-            LVDGS_LAUNCH_CHECK("radix_scatter", dbg, s);
-        }
+        if (int e = launch("radix_hist", dbg, s, radix_hist_kernel, dim3(nblk), dim3(SORT_THREADS), 0, kin, n, n_dev, shift, nbits, hist, nblk)) return e;
+        if (int e = launch("radix_rowscan", dbg, s, radix_rowscan_kernel, dim3(cdiv(nbins, 4)), dim3(256), 0, hist, totals, nbins, nblk)) return e;
+        if (int e = launch("radix_scatter", dbg, s, radix_scatter_kernel, dim3(nblk), dim3(SORT_THREADS), 0, kin, vin, kout, vout, hist, totals, n, n_dev, shift, nbits, nblk)) return e;
         shift += nbits;
         uint32_t *t = kin; kin = kout; kout = t;
         t = vin; vin = vout; vout = t;
@@ -257,12 +244,7 @@ int launch_slot_scan(const uint32_t *tiles_touched, uint32_t *slot_base, uint32_
         return check_hip(hipMemsetAsync(total_dev, 0, sizeof(uint32_t), s), "memset total");
     }
     const int nblk = cdiv(N, SCAN_CHUNK);
-    {
-        ProfScope ps("scan_apply", s);
-        hipLaunchKernelGGL(scan_apply_kernel, dim3(nblk), dim3(SCAN_THREADS), 0, s, tiles_touched, N, (const uint32_t *)blocksums, slot_base,
-                           total_dev);
-        LVDGS_LAUNCH_CHECK("scan_apply", dbg, s);
-    }
+    if (int e = launch("scan_apply", dbg, s, scan_apply_kernel, dim3(nblk), dim3(SCAN_THREADS), 0, tiles_touched, N, (const uint32_t *)blocksums, slot_base, total_dev)) return e;
     return LVDGS_OK;
 }
 

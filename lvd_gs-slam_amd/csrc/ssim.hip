@@ -455,17 +455,8 @@ int lvdgs_ssim_l1(const lvdgs_ssim_args *a, void *stream) {
     fill_window(p.win);
     const dim3 grid(cdiv(a->width, ST), cdiv(a->height, ST), a->planes);
     const int nwg = (int)(grid.x * grid.y * grid.z);
-    {
-        ProfScope ps(a->d_img1 ? "ssim_l1_grad" : "ssim_l1", s);
-        if (a->d_img1) hipLaunchKernelGGL(ssim_l1_kernel<true>, grid, dim3(SSIM_THREADS), 0, s, p);
-        else hipLaunchKernelGGL(ssim_l1_kernel<false>, grid, dim3(SSIM_THREADS), 0, s, p);
-        LVDGS_LAUNCH_CHECK("ssim_l1", 0, s);
-    }
-    {
-        ProfScope ps("ssim_finish", s);
-        hipLaunchKernelGGL(ssim_finish_kernel, dim3(1), dim3(512), 0, s, (const float2 *)v.partial, nwg, (float)(1.0 / count), a->out);
-        LVDGS_LAUNCH_CHECK("ssim_finish", 0, s);
-    }
+    if (int e = launch({a->d_img1 ? "ssim_l1_grad" : "ssim_l1", "ssim_l1"}, 0, s, a->d_img1 ? ssim_l1_kernel<true> : ssim_l1_kernel<false>, grid, dim3(SSIM_THREADS), 0, p)) return e;
+    if (int e = launch("ssim_finish", 0, s, ssim_finish_kernel, dim3(1), dim3(512), 0, (const float2 *)v.partial, nwg, (float)(1.0 / count), a->out)) return e;
     return LVDGS_OK;
 }
 
@@ -502,16 +493,8 @@ int lvdgs_masked_loss_batch(const lvdgs_masked_loss_args *const *views, int32_t 
         }
         f.nwg = (int)(3 * tiles); f.ntiles = (int)tiles; f.inv_count = (float)(1.0 / n);
         const dim3 grid(cdiv(p.W, ST), cdiv(p.H, ST), 3 * m);
-        {
-            ProfScope ps("masked_loss", s);
-            hipLaunchKernelGGL(ssim_l1_kernel<true>, grid, dim3(SSIM_THREADS), 0, s, p);
-            LVDGS_LAUNCH_CHECK("masked_loss", 0, s);
-        }
-        {
-            ProfScope ps("masked_loss_finish", s);
-            hipLaunchKernelGGL(masked_loss_finish_kernel, dim3(m), dim3(512), 0, s, f);
-            LVDGS_LAUNCH_CHECK("masked_loss_finish", 0, s);
-        }
+        if (int e = launch("masked_loss", 0, s, ssim_l1_kernel<true>, grid, dim3(SSIM_THREADS), 0, p)) return e;
+        if (int e = launch("masked_loss_finish", 0, s, masked_loss_finish_kernel, dim3(m), dim3(512), 0, f)) return e;
     }
     return LVDGS_OK;
 }

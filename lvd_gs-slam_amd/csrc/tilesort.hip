@@ -350,22 +350,17 @@ int launch_tile_depth_sort(const ImageView &im, int num_tiles, int t_lo, int t_h
     const bool grouped = keys_ready && longest_expected > CLASS_W, big = !keys_ready || longest_expected > CLASS_G || longest_expected < 0;
     const int group_wgs = grouped ? min(8192, max(64, (int)((int64_t)queue_expected * 5 / 4))) : 0;
     const int solo_wgs = (LVDGS_SORT_SOLO && keys_ready && tile_order_in_use(num_tiles)) ? t_hi - t_lo : 0;
-    {
-        ProfScope ps("tile_sort", s);
-        if (keys_ready)   // counting path: the queue is there already
-            hipLaunchKernelGGL(tile_depth_sort_wave_kernel<true>, dim3(group_wgs + solo_wgs + sort_wgs + LONG_WGS), dim3(64 * SORT_WAVES), 0, s, (const uint2 *)im.ranges, t_lo, t_hi, src,
-                               point_list, im.long_count, im.long_tiles, tile_order_in_use(num_tiles) ? im.long_tiles + num_tiles : nullptr,
-                               (u64 *)keys64, group_wgs, solo_wgs, sort_wgs, grouped ? CLASS_G : CLASS_W, big ? CLASS_G : 0x7fffffff);
-        else
-            hipLaunchKernelGGL(tile_depth_sort_wave_kernel<false>, dim3(sort_wgs), dim3(64 * SORT_WAVES), 0, s, (const uint2 *)im.ranges, t_lo, t_hi, src,
-                               point_list, im.long_count, im.long_tiles, (const uint32_t *)nullptr, (u64 *)keys64, 0, 0, sort_wgs, 0, 0);
-        LVDGS_LAUNCH_CHECK("tile_sort", dbg, s);
+    if (keys_ready) {   // counting path: the queue is there already
+        if (int e = launch("tile_sort", dbg, s, tile_depth_sort_wave_kernel<true>, dim3(group_wgs + solo_wgs + sort_wgs + LONG_WGS), dim3(64 * SORT_WAVES), 0, (const uint2 *)im.ranges,
+                t_lo, t_hi, src, point_list, im.long_count, im.long_tiles, tile_order_in_use(num_tiles) ? im.long_tiles + num_tiles : nullptr,
+                (u64 *)keys64, group_wgs, solo_wgs, sort_wgs, grouped ? CLASS_G : CLASS_W, big ? CLASS_G : 0x7fffffff)) return e;
+    } else {
+        if (int e = launch("tile_sort", dbg, s, tile_depth_sort_wave_kernel<false>, dim3(sort_wgs), dim3(64 * SORT_WAVES), 0, (const uint2 *)im.ranges, t_lo, t_hi, src,
+                point_list, im.long_count, im.long_tiles, (const uint32_t *)nullptr, (u64 *)keys64, 0, 0, sort_wgs, 0, 0)) return e;
     }
     if (big) {
-        ProfScope ps("tile_sort_long", s);
-        hipLaunchKernelGGL(tile_depth_sort_long_kernel, dim3(256), dim3(1024), CLASS_B * 8, s, (const uint2 *)im.ranges, src, point_list,
-                           (const uint32_t *)im.long_count, (const uint32_t *)im.long_tiles, (unsigned long long *)keys64, keys_ready ? CLASS_G : 0);
-        LVDGS_LAUNCH_CHECK("tile_sort_long", dbg, s);
+        if (int e = launch("tile_sort_long", dbg, s, tile_depth_sort_long_kernel, dim3(256), dim3(1024), CLASS_B * 8, (const uint2 *)im.ranges, src, point_list,
+                (const uint32_t *)im.long_count, (const uint32_t *)im.long_tiles, (unsigned long long *)keys64, keys_ready ? CLASS_G : 0)) return e;
     }
     return LVDGS_OK;
 }
@@ -392,18 +387,13 @@ int launch_tile_depth_sort_batch(const lvdgs_args *const *a, const GeomView *g, 
                                           w[k].super.long_tiles, tile_order_in_use(num_tiles) ? w[k].super.long_tiles + num_tiles : nullptr, (u64 *)w[k].keys}
                            : TileSortView{(const uint2 *)im[k].ranges, KeySource{g[k].rec, b[k].point_list, (const u64 *)w[k].keys}, b[k].point_list, im[k].long_count,
                                           im[k].long_tiles, tile_order_in_use(num_tiles) ? im[k].long_tiles + num_tiles : nullptr, (u64 *)w[k].keys};
-    {
-        ProfScope ps("tile_sort", s);
-        hipLaunchKernelGGL(tile_depth_sort_wave_batch_kernel, dim3(group_wgs + solo_wgs + sort_wgs + LONG_WGS, n), dim3(64 * SORT_WAVES), 0, s, batch, t_lo, t_hi,
-                           group_wgs, solo_wgs, sort_wgs, grouped ? CLASS_G : CLASS_W, big ? CLASS_G : 0x7fffffff);
-        LVDGS_LAUNCH_CHECK("tile_sort (batch)", a[0]->debug, s);
-    }
+    if (int e = launch({"tile_sort", "tile_sort (batch)"}, a[0]->debug, s, tile_depth_sort_wave_batch_kernel, dim3(group_wgs + solo_wgs + sort_wgs + LONG_WGS, n),
+            dim3(64 * SORT_WAVES), 0, batch, t_lo, t_hi, group_wgs, solo_wgs, sort_wgs, grouped ? CLASS_G : CLASS_W, big ? CLASS_G : 0x7fffffff)) return e;
     if (big)   // segments beyond what the launch above takes (rare: a kernel per view, as in the single-view call)
         for (int k = 0; k < n; k++) {
-            ProfScope ps("tile_sort_long", s);
-            hipLaunchKernelGGL(tile_depth_sort_long_kernel, dim3(256), dim3(1024), CLASS_B * 8, s, batch.v[k].ranges, batch.v[k].src, batch.v[k].point_list,
-                               (const uint32_t *)batch.v[k].queue_count, (const uint32_t *)batch.v[k].queue, (unsigned long long *)w[k].keys, CLASS_G);
-            LVDGS_LAUNCH_CHECK("tile_sort_long", a[0]->debug, s);
+            if (int e = launch("tile_sort_long", a[0]->debug, s, tile_depth_sort_long_kernel, dim3(256), dim3(1024), CLASS_B * 8, batch.v[k].ranges, batch.v[k].src,
+                    batch.v[k].point_list, (const uint32_t *)batch.v[k].queue_count, (const uint32_t *)batch.v[k].queue, (unsigned long long *)w[k].keys,
+                    CLASS_G)) return e;
         }
     return LVDGS_OK;
 }

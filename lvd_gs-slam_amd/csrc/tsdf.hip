@@ -294,13 +294,9 @@ int lvdgs_tsdf_integrate(const lvdgs_tsdf_volume *vol, const lvdgs_tsdf_view *co
     const uintptr_t bits = (uintptr_t)vol->tsdf | (uintptr_t)vol->weight | (uintptr_t)vol->r | (uintptr_t)vol->g | (uintptr_t)vol->b;
     const bool vec = vol->nx % 4 == 0 && (bits & 15u) == 0;
     hipStream_t s = (hipStream_t)stream;
-    ProfScope ps("tsdf_integrate", s);
-    const dim3 block(TSDF_THREADS);
-    if (color && vec) hipLaunchKernelGGL((tsdf_integrate_kernel<true, true>), grid, block, 0, s, p);
-    else if (color) hipLaunchKernelGGL((tsdf_integrate_kernel<true, false>), grid, block, 0, s, p);
-    else if (vec) hipLaunchKernelGGL((tsdf_integrate_kernel<false, true>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((tsdf_integrate_kernel<false, false>), grid, block, 0, s, p);
-    LVDGS_LAUNCH_CHECK("tsdf_integrate", 0, s);
+    const auto kernel = color ? (vec ? tsdf_integrate_kernel<true, true> : tsdf_integrate_kernel<true, false>)
+                              : (vec ? tsdf_integrate_kernel<false, true> : tsdf_integrate_kernel<false, false>);
+    if (int e = launch("tsdf_integrate", 0, s, kernel, grid, dim3(TSDF_THREADS), 0, p)) return e;
     return LVDGS_OK;
 }
 
@@ -338,35 +334,12 @@ int lvdgs_tsdf_mesh(const lvdgs_tsdf_mesh_args *a, void *stream) {
     M.span = spans.span;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(blocks), block(TSDF_THREADS);
-    {
-        ProfScope ps("tsdf_classify", s);
-        hipLaunchKernelGGL(tsdf_classify_kernel, grid, block, 0, s, M);
-        LVDGS_LAUNCH_CHECK("tsdf_classify", 0, s);
-    }
-    {
-        ProfScope ps("tsdf_edges", s);
-        hipLaunchKernelGGL(tsdf_edges_kernel, grid, block, 0, s, M);
-        LVDGS_LAUNCH_CHECK("tsdf_edges", 0, s);
-    }
-    {
-        ProfScope ps("tsdf_scan", s);
-        hipLaunchKernelGGL(tsdf_scan_kernel, dim3(1), block, 0, s, M, blocks);
-        LVDGS_LAUNCH_CHECK("tsdf_scan", 0, s);
-    }
-    {
-        ProfScope ps("tsdf_vertices", s);
-        if (vol.r) hipLaunchKernelGGL(tsdf_vertices_kernel<true>, grid, block, 0, s, M);
-        else hipLaunchKernelGGL(tsdf_vertices_kernel<false>, grid, block, 0, s, M);
-        LVDGS_LAUNCH_CHECK("tsdf_vertices", 0, s);
-    }
-    {
-        ProfScope ps("tsdf_faces", s);
-        hipLaunchKernelGGL(tsdf_faces_kernel, grid, block, 0, s, M);
-        LVDGS_LAUNCH_CHECK("tsdf_faces", 0, s);
-    }
-    ProfScope ps("tsdf_publish", s);
-    hipLaunchKernelGGL(tsdf_publish_kernel, dim3(1), dim3(WAVE), 0, s, M);
-    LVDGS_LAUNCH_CHECK("tsdf_publish", 0, s);
+    if (int e = launch("tsdf_classify", 0, s, tsdf_classify_kernel, grid, block, 0, M)) return e;
+    if (int e = launch("tsdf_edges", 0, s, tsdf_edges_kernel, grid, block, 0, M)) return e;
+    if (int e = launch("tsdf_scan", 0, s, tsdf_scan_kernel, dim3(1), block, 0, M, blocks)) return e;
+    if (int e = launch("tsdf_vertices", 0, s, vol.r ? tsdf_vertices_kernel<true> : tsdf_vertices_kernel<false>, grid, block, 0, M)) return e;
+    if (int e = launch("tsdf_faces", 0, s, tsdf_faces_kernel, grid, block, 0, M)) return e;
+    if (int e = launch("tsdf_publish", 0, s, tsdf_publish_kernel, dim3(1), dim3(WAVE), 0, M)) return e;
     return LVDGS_OK;
 }
 

@@ -536,21 +536,10 @@ int lvdgs_tsdf_blocks_integrate(const lvdgs_tsdf_blocks *vol, const lvdgs_tsdf_v
     ap.step = 0.5f * vol->voxel_size;
     for (int v = 0; v < count; v++) ap.v[v] = p.v[v];
     hipStream_t s = (hipStream_t)stream;
-    {
-        ProfScope ps("tsdf_blocks_alloc", s);
-        hipLaunchKernelGGL(tsdf_blocks_alloc_kernel, dim3(cdiv(most_pixels, TB_THREADS), count), dim3(TB_THREADS), 0, s, ap);
-        LVDGS_LAUNCH_CHECK("tsdf_blocks_alloc", 0, s);
-    }
-    {
-        ProfScope ps("tsdf_blocks_settle", s);
-        hipLaunchKernelGGL(tsdf_blocks_settle_kernel, dim3(1), dim3(WAVE), 0, s, p.vol);
-        LVDGS_LAUNCH_CHECK("tsdf_blocks_settle", 0, s);
-    }
-    ProfScope ps("tsdf_blocks_integrate", s);
+    if (int e = launch("tsdf_blocks_alloc", 0, s, tsdf_blocks_alloc_kernel, dim3(cdiv(most_pixels, TB_THREADS), count), dim3(TB_THREADS), 0, ap)) return e;
+    if (int e = launch("tsdf_blocks_settle", 0, s, tsdf_blocks_settle_kernel, dim3(1), dim3(WAVE), 0, p.vol)) return e;
     const dim3 grid(block_grid(p.vol.pool)), block(TB_THREADS);
-    if (vol->r) hipLaunchKernelGGL(tsdf_blocks_integrate_kernel<true>, grid, block, 0, s, p);
-    else hipLaunchKernelGGL(tsdf_blocks_integrate_kernel<false>, grid, block, 0, s, p);
-    LVDGS_LAUNCH_CHECK("tsdf_blocks_integrate", 0, s);
+    if (int e = launch("tsdf_blocks_integrate", 0, s, vol->r ? tsdf_blocks_integrate_kernel<true> : tsdf_blocks_integrate_kernel<false>, grid, block, 0, p)) return e;
     return LVDGS_OK;
 }
 
@@ -581,45 +570,14 @@ int lvdgs_tsdf_blocks_mesh(const lvdgs_tsdf_blocks_mesh_args *a, void *stream) {
     if (int e = host_block_address(a->host_state, name, &M.host)) return e;
     hipStream_t s = (hipStream_t)stream;
     const dim3 per_block(block_grid(M.vol.pool)), block(TB_THREADS);
-    {
-        ProfScope ps("tsdf_blocks_rank", s);
-        hipLaunchKernelGGL(tsdf_blocks_rank_kernel, dim3(cdiv((int64_t)pool, TB_THREADS)), block, 0, s, M);
-        LVDGS_LAUNCH_CHECK("tsdf_blocks_rank", 0, s);
-    }
-    {
-        ProfScope ps("tsdf_blocks_neighbours", s);
-        hipLaunchKernelGGL(tsdf_blocks_neighbours_kernel, dim3(cdiv((int64_t)pool * 27, TB_THREADS)), block, 0, s, M);
-        LVDGS_LAUNCH_CHECK("tsdf_blocks_neighbours", 0, s);
-    }
-    {
-        ProfScope ps("tsdf_blocks_classify", s);
-        hipLaunchKernelGGL(tsdf_blocks_classify_kernel, per_block, block, 0, s, M);
-        LVDGS_LAUNCH_CHECK("tsdf_blocks_classify", 0, s);
-    }
-    {
-        ProfScope ps("tsdf_blocks_edges", s);
-        hipLaunchKernelGGL(tsdf_blocks_edges_kernel, per_block, block, 0, s, M);
-        LVDGS_LAUNCH_CHECK("tsdf_blocks_edges", 0, s);
-    }
-    {
-        ProfScope ps("tsdf_blocks_scan", s);
-        hipLaunchKernelGGL(tsdf_blocks_scan_kernel, dim3(1), dim3(TB_SCAN_THREADS), 0, s, M);
-        LVDGS_LAUNCH_CHECK("tsdf_blocks_scan", 0, s);
-    }
-    {
-        ProfScope ps("tsdf_blocks_vertices", s);
-        if (a->vol.r) hipLaunchKernelGGL(tsdf_blocks_vertices_kernel<true>, per_block, block, 0, s, M);
-        else hipLaunchKernelGGL(tsdf_blocks_vertices_kernel<false>, per_block, block, 0, s, M);
-        LVDGS_LAUNCH_CHECK("tsdf_blocks_vertices", 0, s);
-    }
-    {
-        ProfScope ps("tsdf_blocks_faces", s);
-        hipLaunchKernelGGL(tsdf_blocks_faces_kernel, per_block, block, 0, s, M);
-        LVDGS_LAUNCH_CHECK("tsdf_blocks_faces", 0, s);
-    }
-    ProfScope ps("tsdf_blocks_publish", s);
-    hipLaunchKernelGGL(tsdf_blocks_publish_kernel, dim3(1), dim3(WAVE), 0, s, M);
-    LVDGS_LAUNCH_CHECK("tsdf_blocks_publish", 0, s);
+    if (int e = launch("tsdf_blocks_rank", 0, s, tsdf_blocks_rank_kernel, dim3(cdiv((int64_t)pool, TB_THREADS)), block, 0, M)) return e;
+    if (int e = launch("tsdf_blocks_neighbours", 0, s, tsdf_blocks_neighbours_kernel, dim3(cdiv((int64_t)pool * 27, TB_THREADS)), block, 0, M)) return e;
+    if (int e = launch("tsdf_blocks_classify", 0, s, tsdf_blocks_classify_kernel, per_block, block, 0, M)) return e;
+    if (int e = launch("tsdf_blocks_edges", 0, s, tsdf_blocks_edges_kernel, per_block, block, 0, M)) return e;
+    if (int e = launch("tsdf_blocks_scan", 0, s, tsdf_blocks_scan_kernel, dim3(1), dim3(TB_SCAN_THREADS), 0, M)) return e;
+    if (int e = launch("tsdf_blocks_vertices", 0, s, a->vol.r ? tsdf_blocks_vertices_kernel<true> : tsdf_blocks_vertices_kernel<false>, per_block, block, 0, M)) return e;
+    if (int e = launch("tsdf_blocks_faces", 0, s, tsdf_blocks_faces_kernel, per_block, block, 0, M)) return e;
+    if (int e = launch("tsdf_blocks_publish", 0, s, tsdf_blocks_publish_kernel, dim3(1), dim3(WAVE), 0, M)) return e;
     return LVDGS_OK;
 }
 
@@ -631,9 +589,7 @@ int lvdgs_tsdf_blocks_rehash(const lvdgs_tsdf_blocks *vol, void *stream) {
     // dropped keys are forgotten with the old table: words [_HEADER_DROPPED] and [_HEADER_FLAGS] are not adjacent to a counter in use
     if (int e = check_hip(hipMemsetAsync(v.header + LVDGS_TSDF_BLOCKS_HEADER_DROPPED, 0, sizeof(int32_t), s), name)) return e;
     if (int e = check_hip(hipMemsetAsync(v.header + LVDGS_TSDF_BLOCKS_HEADER_FLAGS, 0, sizeof(int32_t), s), name)) return e;
-    ProfScope ps("tsdf_blocks_rehash", s);
-    hipLaunchKernelGGL(tsdf_blocks_rehash_kernel, dim3(cdiv(v.pool, TB_THREADS)), dim3(TB_THREADS), 0, s, v);
-    LVDGS_LAUNCH_CHECK("tsdf_blocks_rehash", 0, s);
+    if (int e = launch("tsdf_blocks_rehash", 0, s, tsdf_blocks_rehash_kernel, dim3(cdiv(v.pool, TB_THREADS)), dim3(TB_THREADS), 0, v)) return e;
     return LVDGS_OK;
 }
 

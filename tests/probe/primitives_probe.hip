@@ -76,8 +76,7 @@ template <int OP>
 int launch_wave_probe(int op, int threads, int blocks, const void *in, void *out, int a0, int a1, hipStream_t s) {
     if constexpr (OP < W_OPS) {
         if (op != OP) return launch_wave_probe<OP + 1>(op, threads, blocks, in, out, a0, a1, s);
-        hipLaunchKernelGGL(wave_probe_kernel<OP>, dim3(blocks), dim3(threads), 0, s, in, out, threads * blocks, a0, a1);
-        LVDGS_LAUNCH_CHECK("probe wave", 0, s);
+        if (int e = launch_checked("probe wave", 0, s, wave_probe_kernel<OP>, dim3(blocks), dim3(threads), 0, in, out, threads * blocks, a0, a1)) return e;
         return LVDGS_OK;
     } else {
         PROBE_REFUSE("probe wave: no op %d", op);
@@ -131,10 +130,8 @@ constexpr int CONTRACT_MAX_TRIPS = 3;
 template <int THREADS, typename T>
 int launch_scan_probe(bool contract, int blocks, const void *in, void *out, int trips, hipStream_t s) {
     const int n = THREADS * blocks;
-    if (contract) hipLaunchKernelGGL((scan_contract_kernel<THREADS, T>), dim3(blocks), dim3(THREADS), 0, s, (const T *)in, (T *)out, n, trips);
-    else hipLaunchKernelGGL((scan_basic_kernel<THREADS, T>), dim3(blocks), dim3(THREADS), 0, s, (const T *)in, (T *)out, n);
-    LVDGS_LAUNCH_CHECK("probe scan", 0, s);
-    return LVDGS_OK;
+    if (contract) return launch_checked("probe scan", 0, s, scan_contract_kernel<THREADS, T>, dim3(blocks), dim3(THREADS), 0, (const T *)in, (T *)out, n, trips);
+    return launch_checked("probe scan", 0, s, scan_basic_kernel<THREADS, T>, dim3(blocks), dim3(THREADS), 0, (const T *)in, (T *)out, n);
 }
 template <typename T>
 int launch_scan_probe_t(int threads, bool contract, int blocks, const void *in, void *out, int trips, hipStream_t s) {
@@ -155,8 +152,7 @@ __global__ void __launch_bounds__(64 * WAVES) block_sum_kernel(const T *in, T *o
 }
 template <int WAVES, typename T>
 int launch_block_sum(int blocks, const void *in, void *out, hipStream_t s) {
-    hipLaunchKernelGGL((block_sum_kernel<WAVES, T>), dim3(blocks), dim3(64 * WAVES), 0, s, (const T *)in, (T *)out, 64 * WAVES * blocks);
-    LVDGS_LAUNCH_CHECK("probe block_sum", 0, s);
+    if (int e = launch_checked("probe block_sum", 0, s, block_sum_kernel<WAVES, T>, dim3(blocks), dim3(64 * WAVES), 0, (const T *)in, (T *)out, 64 * WAVES * blocks)) return e;
     return LVDGS_OK;
 }
 
@@ -174,8 +170,7 @@ __global__ void __launch_bounds__(THREADS) span_counts_kernel(const T *counts, C
 }
 template <int THREADS, typename T, typename C>
 int launch_span_counts(const void *counts, void *before, int blocks, int stride, void *totals, hipStream_t s) {
-    hipLaunchKernelGGL((span_counts_kernel<THREADS, T, C>), dim3(1), dim3(THREADS), 0, s, (const T *)counts, (C *)before, blocks, stride, (C *)totals);
-    LVDGS_LAUNCH_CHECK("probe scan_span_counts", 0, s);
+    if (int e = launch_checked("probe scan_span_counts", 0, s, span_counts_kernel<THREADS, T, C>, dim3(1), dim3(THREADS), 0, (const T *)counts, (C *)before, blocks, stride, (C *)totals)) return e;
     return LVDGS_OK;
 }
 
@@ -220,12 +215,10 @@ template <typename T, typename C, typename B>
 int launch_compact(const uint8_t *keep, uint32_t n, int blocks, u64 row0, void *counts, void *before, uint32_t *out_index, u64 *out_row, long long capacity,
                    u64 *total_out, hipStream_t s) {
     const uint32_t span = span_length(n, (uint32_t)blocks, CP_THREADS);
-    hipLaunchKernelGGL((compact_count_kernel<T>), dim3(blocks), dim3(CP_THREADS), 0, s, keep, n, span, (T *)counts);
-    LVDGS_LAUNCH_CHECK("probe compact count", 0, s);
-    hipLaunchKernelGGL((compact_scan_kernel<T, B>), dim3(1), dim3(CP_THREADS), 0, s, (const T *)counts, (B *)before, blocks, total_out);
-    LVDGS_LAUNCH_CHECK("probe compact scan", 0, s);
-    hipLaunchKernelGGL((compact_write_kernel<T, C, B>), dim3(blocks), dim3(CP_THREADS), 0, s, keep, n, span, (const B *)before, row0, out_index, out_row, capacity);
-    LVDGS_LAUNCH_CHECK("probe compact write", 0, s);
+    if (int e = launch_checked("probe compact count", 0, s, compact_count_kernel<T>, dim3(blocks), dim3(CP_THREADS), 0, keep, n, span, (T *)counts)) return e;
+    if (int e = launch_checked("probe compact scan", 0, s, compact_scan_kernel<T, B>, dim3(1), dim3(CP_THREADS), 0, (const T *)counts, (B *)before, blocks, total_out)) return e;
+    if (int e = launch_checked("probe compact write", 0, s, compact_write_kernel<T, C, B>, dim3(blocks), dim3(CP_THREADS), 0, keep, n, span, (const B *)before, row0,
+            out_index, out_row, capacity)) return e;
     return LVDGS_OK;
 }
 
@@ -259,14 +252,11 @@ int run_select(const Src &src, int64_t n, SelectState *st, SelectRank rank, uint
     } else {   // launch_select's launches, with the ticket read between them
         const int blocks = select_blocks(n);
         for (int pass = 0; pass < SEL_PASSES; pass++) {
-            hipLaunchKernelGGL(select_pass_kernel<Src>, dim3(blocks), dim3(SEL_THREADS), 0, s, src, n, st, pass, rank);
-            LVDGS_LAUNCH_CHECK("probe select pass", 0, s);
-            hipLaunchKernelGGL(select_record_ticket_kernel, dim3(1), dim3(WAVE), 0, s, st, out, SP_TICKET_AFTER_PASS + pass);
-            LVDGS_LAUNCH_CHECK("probe select ticket", 0, s);
+            if (int e = launch_checked("probe select pass", 0, s, select_pass_kernel<Src>, dim3(blocks), dim3(SEL_THREADS), 0, src, n, st, pass, rank)) return e;
+            if (int e = launch_checked("probe select ticket", 0, s, select_record_ticket_kernel, dim3(1), dim3(WAVE), 0, st, out, SP_TICKET_AFTER_PASS + pass)) return e;
         }
     }
-    hipLaunchKernelGGL(select_finish_kernel, dim3(1), dim3(WAVE), 0, s, st, out, keys ? 1 : 0);
-    LVDGS_LAUNCH_CHECK("probe select finish", 0, s);
+    if (int e = launch_checked("probe select finish", 0, s, select_finish_kernel, dim3(1), dim3(WAVE), 0, st, out, keys ? 1 : 0)) return e;
     return LVDGS_OK;
 }
 
@@ -336,8 +326,7 @@ int lvdgs_probe_mask_bit(int set, uint64_t mask, int bit, uint64_t *out, size_t 
     if (!out || out_bytes < WAVE * sizeof(uint64_t)) PROBE_REFUSE("probe mask bit: out is NULL or holds fewer than 64 words");
     if (bit < 0 || bit > 63) PROBE_REFUSE("probe mask bit: bit %d", bit);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(mask_bit_kernel, dim3(1), dim3(WAVE), 0, s, set ? 1 : 0, (u64)mask, bit, (u64 *)out);
-    LVDGS_LAUNCH_CHECK("probe mask bit", 0, s);
+    if (int e = launch_checked("probe mask bit", 0, s, mask_bit_kernel, dim3(1), dim3(WAVE), 0, set ? 1 : 0, (u64)mask, bit, (u64 *)out)) return e;
     return LVDGS_OK;
 }
 
@@ -377,8 +366,7 @@ int lvdgs_probe_span_range(uint32_t n, uint32_t span, int blocks, uint32_t *out,
     if (!out || out_bytes < (size_t)blocks * 2 * sizeof(uint32_t)) PROBE_REFUSE("probe span_range: out is NULL or too small");
     if (n > 0x7fffffffu || span == 0 || (uint64_t)blocks * span > 0xffffffffull) PROBE_REFUSE("probe span_range: n %u, span %u outside the contract", n, span);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(span_range_kernel, dim3(blocks), dim3(WAVE), 0, s, n, span, out);
-    LVDGS_LAUNCH_CHECK("probe span_range", 0, s);
+    if (int e = launch_checked("probe span_range", 0, s, span_range_kernel, dim3(blocks), dim3(WAVE), 0, n, span, out)) return e;
     return LVDGS_OK;
 }
 
@@ -444,8 +432,7 @@ int lvdgs_probe_select_segment(const float *v, const uint8_t *take, int n, int s
     if (!v || !out) PROBE_REFUSE("probe select_segment: v / out is NULL");
     if (v_count < (size_t)n * segments || (take && take_count < (size_t)n * segments) || out_bytes < (size_t)segments * SEL_THREADS * sizeof(uint32_t)) PROBE_REFUSE("probe select_segment: a buffer is too small");
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(select_segment_kernel, dim3(segments), dim3(SEL_THREADS), 0, s, v, take, n, out);
-    LVDGS_LAUNCH_CHECK("probe select_segment", 0, s);
+    if (int e = launch_checked("probe select_segment", 0, s, select_segment_kernel, dim3(segments), dim3(SEL_THREADS), 0, v, take, n, out)) return e;
     return LVDGS_OK;
 }
 
@@ -454,8 +441,7 @@ int lvdgs_probe_hist_add(const uint8_t *ok, const uint32_t *digit, size_t lanes,
     if (!ok || !digit || !out) PROBE_REFUSE("probe hist_add: a pointer is NULL");
     if (lanes < (size_t)WAVE || out_bytes < SEL_THREADS * sizeof(uint32_t)) PROBE_REFUSE("probe hist_add: a buffer is too small");
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(hist_add_kernel, dim3(1), dim3(WAVE), 0, s, ok, digit, out);
-    LVDGS_LAUNCH_CHECK("probe hist_add", 0, s);
+    if (int e = launch_checked("probe hist_add", 0, s, hist_add_kernel, dim3(1), dim3(WAVE), 0, ok, digit, out)) return e;
     return LVDGS_OK;
 }
 
