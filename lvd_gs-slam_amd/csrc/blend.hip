@@ -25,6 +25,7 @@
 // first two-pass backward) left the library in round 3: profiles/experiments/r02_superseded_blend_kernels.hip.txt.
 // What bounds the kernels and what was tried: DESIGN.md section 2, profiles/experiments/README.md.
 #include <type_traits>
+#include <utility>
 #if defined(LVDGS_DIAG_GRID) || defined(LVDGS_DIAG_REPEAT)
 #include <cstdlib>
 #endif
@@ -33,6 +34,92 @@
 #include "device_utils.hpp"
 #include "photometric.hpp"
 
+// ------------------------------------------------------------------------------------------
+// Diagnostic builds of the backward pass (timings and counts, never results): what they record, the hooks the kernel calls and
+// the calls that read the records back.  A product build has none of the three macros: BwdDiag is then empty, its methods do nothing.
+#ifdef LVDGS_DIAG_PHASES
+#define LVDGS_IF_PHASES(...) __VA_ARGS__
+#else
+#define LVDGS_IF_PHASES(...)
+#endif
+#ifdef LVDGS_DIAG_FILL
+#define LVDGS_IF_FILL(...) __VA_ARGS__
+#else
+#define LVDGS_IF_FILL(...)
+#endif
+namespace lvdgs {
+namespace {
+// LVDGS_DIAG_PHASES: where the workgroup at the head of the order (the longest list) spends its time, in shader clock ticks of wave 0:
+// [0] prologue, [1] staging up to its barrier, [2] test + survivor batches, [3] wait for the other waves, [4] flush, [5] rounds, [6] survivors of wave 0, [7] launches
+LVDGS_IF_PHASES(__device__ unsigned long long g_phase_diag[8];)
+// ... and of EVERY workgroup of the last launch: start, end (s_memrealtime: 100 MHz, one clock for the chip), survivors of its four waves,
+// list length, HW_ID, XCC_ID
+LVDGS_IF_PHASES(__device__ unsigned long long g_wg_diag[8192][4]; __device__ unsigned g_wg_surv[8192];)
+// LVDGS_DIAG_FILL (tools/fill_diag.py): survivors, splat batches, full batches, (wave, round) pairs with survivors, summed over launches
+LVDGS_IF_FILL(__device__ unsigned long long g_fill_diag[4];)
+
+struct BwdDiag {
+    enum Phase { PROLOGUE, STAGING, BATCHES, WAIT, FLUSH };
+    LVDGS_IF_PHASES(unsigned long long wg_t0, ph_t, ph[7];)
+    LVDGS_IF_FILL(unsigned surv, batches, full, rounds;)
+    __device__ __forceinline__ BwdDiag() {
+        LVDGS_IF_PHASES(wg_t0 = __builtin_amdgcn_s_memrealtime();
+                        if (threadIdx.x == 0 && blockIdx.x < 8192) g_wg_surv[blockIdx.x] = 0u;
+                        ph_t = __builtin_amdgcn_s_memtime();
+                        for (int k = 0; k < 7; k++) ph[k] = 0;)
+        LVDGS_IF_FILL(surv = batches = full = rounds = 0;)
+    }
+    // the phase that ends here
+    __device__ __forceinline__ void mark(Phase k) { LVDGS_IF_PHASES(const unsigned long long n = __builtin_amdgcn_s_memtime(); ph[k] += n - ph_t; ph_t = n;) }
+    __device__ __forceinline__ void round_staged() { LVDGS_IF_PHASES(ph[5]++;) }
+    // the quadrant test's survivors of one (wave, round)
+    __device__ __forceinline__ void survivors(uint64_t live) {
+        LVDGS_IF_PHASES(ph[6] += (unsigned long long)__popcll(live);)
+        LVDGS_IF_FILL(surv += (unsigned)__popcll(live); rounds += live ? 1u : 0u;)
+    }
+    __device__ __forceinline__ void batch(bool is_full) { LVDGS_IF_FILL(batches++; full += is_full ? 1u : 0u;) }
+    __device__ __forceinline__ void publish(int tile, uint32_t list_length) {
+        LVDGS_IF_PHASES(
+            const int tid = threadIdx.x;
+            if (blockIdx.x == 0 && tid == 0) {
+                for (int k = 0; k < 7; k++) atomicAdd(&g_phase_diag[k], ph[k]);
+                atomicAdd(&g_phase_diag[7], 1ull);
+            }
+            if (blockIdx.x < 8192) {
+                if ((tid & 63) == 0) atomicAdd(&g_wg_surv[blockIdx.x], (unsigned)ph[6]);
+                if (tid == 0) {
+                    const unsigned hw = __builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11)), xcc = __builtin_amdgcn_s_getreg((20) | (0 << 6) | (31 << 11));
+                    g_wg_diag[blockIdx.x][0] = wg_t0; g_wg_diag[blockIdx.x][1] = __builtin_amdgcn_s_memrealtime();
+                    g_wg_diag[blockIdx.x][2] = ((unsigned long long)list_length << 32) | (unsigned)tile;
+                    g_wg_diag[blockIdx.x][3] = ((unsigned long long)xcc << 32) | hw;
+                }
+            })
+        LVDGS_IF_FILL(if ((threadIdx.x & 63) == 0) {
+            atomicAdd(&g_fill_diag[0], (unsigned long long)surv); atomicAdd(&g_fill_diag[1], (unsigned long long)batches);
+            atomicAdd(&g_fill_diag[2], (unsigned long long)full); atomicAdd(&g_fill_diag[3], (unsigned long long)rounds);
+        })
+    }
+};
+// a record of n counters to the host, zeroed afterwards on request
+template <int N, class Symbol>
+int read_diag(const Symbol &symbol, unsigned long long *out, int reset) {
+    if (out && hipMemcpyFromSymbol(out, symbol, N * sizeof(unsigned long long)) != hipSuccess) return LVDGS_E_HIP;
+    const unsigned long long z[N] = {};
+    if (reset && hipMemcpyToSymbol(symbol, z, sizeof(z)) != hipSuccess) return LVDGS_E_HIP;
+    return LVDGS_OK;
+}
+}  // namespace
+}  // namespace lvdgs
+LVDGS_IF_PHASES(
+extern "C" int lvdgs_diag_phases(unsigned long long *out8, int reset) { return lvdgs::read_diag<8>(HIP_SYMBOL(lvdgs::g_phase_diag), out8, reset); }
+extern "C" int lvdgs_diag_workgroups(unsigned long long *out_8192x4, unsigned *surv_8192) {
+    if (hipMemcpyFromSymbol(out_8192x4, HIP_SYMBOL(lvdgs::g_wg_diag), 8192 * 4 * sizeof(unsigned long long)) != hipSuccess) return LVDGS_E_HIP;
+    if (hipMemcpyFromSymbol(surv_8192, HIP_SYMBOL(lvdgs::g_wg_surv), 8192 * sizeof(unsigned)) != hipSuccess) return LVDGS_E_HIP;
+    return LVDGS_OK;
+})
+LVDGS_IF_FILL(extern "C" int lvdgs_diag_fill(unsigned long long *out4, int reset) { return lvdgs::read_diag<4>(HIP_SYMBOL(lvdgs::g_fill_diag), out4, reset); })
+
+// ------------------------------------------------------------------------------------------
 namespace lvdgs {
 
 namespace {
@@ -131,6 +218,37 @@ __device__ __forceinline__ int order_slot_of_workgroup(int b, int n) {
     return (k << 8) + (m - 1 - j);
 }
 
+// The tile this workgroup renders: its entry of the launch's tile order where the frame's grouping has written one, else its
+// place in the XCD-interleaved row-major walk.
+__device__ __forceinline__ int workgroup_of_launch(const BlendParams &p) {
+#ifdef LVDGS_DIAG_REPEAT   // diagnostic build: the grid repeated $LVDGS_DIAG_REPEAT times (what a launch over several views of this size would cost)
+    return (int)blockIdx.x % p.num_tiles;
+#else
+    return (int)blockIdx.x;
+#endif
+}
+__device__ __forceinline__ int tile_of_this_workgroup(const BlendParams &p) {
+    return (p.tile_order && *p.order_valid) ? (int)p.tile_order[order_slot_of_workgroup(workgroup_of_launch(p), p.num_tiles)]
+                                            : p.tile_base + tile_of_workgroup(workgroup_of_launch(p), p.num_tiles);
+}
+
+// What a thread of both blend passes derives from (tile, threadIdx): the tile's place in the grid, its wave's 8x8 quadrant
+// (the rectangle of its pixel centres) and its own pixel.
+struct TileGeom {
+    int tx, ty, tid, lane, wave, px, py;
+    bool inside;
+    float pxf, pyf;
+    float rx0, ry0, rx1, ry1;
+    __device__ __forceinline__ TileGeom(const BlendParams &p, int tile)
+        : tx(tile % p.gx), ty(tile / p.gx), tid(threadIdx.x), lane(tid & 63), wave(tid >> 6) {
+        const int qx0 = tx * TILE + (wave & 1) * 8, qy0 = ty * TILE + (wave >> 1) * 8;
+        px = qx0 + (lane & 7); py = qy0 + (lane >> 3);
+        inside = px < p.W && py < p.H;
+        pxf = (float)px; pyf = (float)py;
+        rx0 = (float)qx0; ry0 = (float)qy0; rx1 = (float)(qx0 + 7); ry1 = (float)(qy0 + 7);
+    }
+};
+
 // ------------------------------------------------------------------------------------------
 // One survivor of the quadrant test against the wave's 64 pixels, hand-scheduled: the hit lanes run the compositing
 // under EXEC instead of through selects (the compiler's form of the same statements is 31 vector + 17 scalar
@@ -222,21 +340,9 @@ __device__ __forceinline__ void blend_fwd2_body(const BlendParams &p, FwdShared 
     float4 *const s_q = s_recs.q;  // raw conic c, 1/a, 1/c, ln(255 opacity) resp. -inf / +inf (common.hpp: quad_prepare)
     int *const s_touch = s_recs.touch;
 
-#ifdef LVDGS_DIAG_REPEAT   // diagnostic build: the grid repeated $LVDGS_DIAG_REPEAT times (what a launch over several views of this size would cost)
-    const int diag_b = (int)blockIdx.x % p.num_tiles;
-#define blockIdx_x_ diag_b
-#else
-#define blockIdx_x_ ((int)blockIdx.x)
-#endif
-    const int tile = (p.tile_order && *p.order_valid) ? (int)p.tile_order[order_slot_of_workgroup(blockIdx_x_, p.num_tiles)] : p.tile_base + tile_of_workgroup(blockIdx_x_, p.num_tiles);
-#undef blockIdx_x_
-    const int tx = tile % p.gx, ty = tile / p.gx;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int qx0 = tx * TILE + (wave & 1) * 8, qy0 = ty * TILE + (wave >> 1) * 8;
-    const int px = qx0 + (lane & 7), py = qy0 + (lane >> 3);
-    const bool inside = px < p.W && py < p.H;
-    const float pxf = (float)px, pyf = (float)py;
-    const float rx0 = (float)qx0, ry0 = (float)qy0, rx1 = (float)(qx0 + 7), ry1 = (float)(qy0 + 7);
+    const int tile = tile_of_this_workgroup(p);
+    const TileGeom g(p, tile);
+    const int tid = g.tid, lane = g.lane;
 
     const uint2 range = p.ranges[tile];
     const int todo = (int)(range.y - range.x);
@@ -246,7 +352,7 @@ __device__ __forceinline__ void blend_fwd2_body(const BlendParams &p, FwdShared 
     // then evaluates to alpha = 0 there and fails the 1/255 test by itself, so the per-Gaussian code carries no
     // "done" mask (that mask cost five scalar instructions per Gaussian, on a scalar unit shared by four SIMDs).
     constexpr float FAR_AWAY = 1e30f;
-    float pxe = inside ? pxf : FAR_AWAY;
+    float pxe = g.inside ? g.pxf : FAR_AWAY;
     const float far_away = FAR_AWAY;
 
     for (int base = 0; base < todo; base += 256) {
@@ -279,7 +385,7 @@ __device__ __forceinline__ void blend_fwd2_body(const BlendParams &p, FwdShared 
                     const float2 M = *reinterpret_cast<const float2 *>(&s_a[jl]);
                     const float2 K = *reinterpret_cast<const float2 *>(&s_b[jl].z);
                     const float4 Q = s_q[jl];
-                    keep = reaches_rect_prepared(M.x, M.y, K.x, K.y, Q.x, Q.y, Q.z, Q.w, rx0, ry0, rx1, ry1);
+                    keep = reaches_rect_prepared(M.x, M.y, K.x, K.y, Q.x, Q.y, Q.z, Q.w, g.rx0, g.ry0, g.rx1, g.ry1);
                 }
                 uint64_t live = __ballot(keep);
                 // ---- lane -> pixel: composite the survivors in list order ----
@@ -296,7 +402,7 @@ __device__ __forceinline__ void blend_fwd2_body(const BlendParams &p, FwdShared 
                     const float4 A = s_a[jj];
                     const float2 B = *reinterpret_cast<const float2 *>(&s_b[jj]);
                     const float4 Cc = s_c[jj];
-                    const int n = composite_one<decltype(count)::value>(A, B, Cc, pxe, pyf, T, C0, C1, C2, Dp, last, (uint32_t)(base + jj + 1), far_away, full);
+                    const int n = composite_one<decltype(count)::value>(A, B, Cc, pxe, g.pyf, T, C0, C1, C2, Dp, last, (uint32_t)(base + jj + 1), far_away, full);
                     if constexpr (decltype(count)::value) vcnt = write_lane(vcnt, n, jb);  // 0 by itself once no pixel of the quadrant has transmittance above 1/2
                 };
                 // eight survivors per trip while there are that many (batches of 1 / 4 / 8: 149.7 / 147.7 / 146.5 us at config 3): the compiler is free to issue the next survivors' reads
@@ -325,8 +431,8 @@ __device__ __forceinline__ void blend_fwd2_body(const BlendParams &p, FwdShared 
             if (n) atomicAdd(&p.n_touched[my_id], n);
         }
     }
-    if (inside) {
-        const size_t pix = (size_t)py * p.W + px, P = (size_t)p.W * p.H;
+    if (g.inside) {
+        const size_t pix = (size_t)g.py * p.W + g.px, P = (size_t)p.W * p.H;
         p.final_T[pix] = T;
         p.n_contrib[pix] = last;
         p.out_color[pix] = fmaf(T, p.bg[0], C0);
@@ -384,19 +490,6 @@ __device__ __forceinline__ float fma_rotated(float g, float w, float acc) {  // 
 #ifndef LVDGS_BWD_NB
 #define LVDGS_BWD_NB 8   // survivors per batch of the backward pass: 8 or 4 (A/B builds)
 #endif
-#ifdef LVDGS_DIAG_PHASES
-// diagnostic build: where the workgroup at the head of the order (the longest list) spends its time, in shader clock ticks of wave 0:
-// [0] prologue, [1] staging up to its barrier, [2] test + survivor batches, [3] wait for the other waves, [4] flush, [5] rounds, [6] survivors of wave 0, [7] launches
-__device__ unsigned long long g_phase_diag[8];
-// ... and of EVERY workgroup of the last launch: start, end (s_memrealtime: 100 MHz, one clock for the chip), survivors of its four waves,
-// list length, HW_ID, XCC_ID
-__device__ unsigned long long g_wg_diag[8192][4];
-__device__ unsigned g_wg_surv[8192];
-#endif
-#ifdef LVDGS_DIAG_FILL
-// diagnostic build (tools/fill_diag.py): survivors, splat batches, full batches, (wave, round) pairs with survivors, summed over launches
-__device__ unsigned long long g_fill_diag[4];
-#endif
 // POSE_ONLY (LVDGS_FLAG_POSE_ONLY: the tracking loop, which consumes only dL/dtau and the exposure gradients): the sums that feed
 // nothing but the colour and opacity gradients (Su, C0..C2) are left out -- six accumulators per (wave, entry) instead of
 // ten, and without a depth gradient the (u, w) matrix holds u alone.
@@ -429,6 +522,116 @@ struct Bwd3Shared {
 #ifndef LVDGS_BWD_WGS_POSE
 #define LVDGS_BWD_WGS_POSE 7   // ... and its pose-only form (18.7 KB of LDS, 72 VGPRs; 26 880 B with a depth gradient -- all that six leave each). Same box, config 3 / KITTI geometry: 5: 240.9 / 92.0 us, 6: 240.4 / 92.1, 7: 233.7 / 92.6, 8: 233.6 / 95.8
 #endif
+// ---- staging of one round: every thread below cnt gathers one entry's record into LDS ----
+// The id a staging thread gathers its record with is requested a round AHEAD (round 5): a round's staging is two dependent trips to
+// memory -- the id, then the record -- in front of a barrier the whole workgroup waits at, and on a small grid the kernel lasts as
+// long as its longest list's chain of rounds (a KITTI frame's heaviest tile: 14 rounds), with nobody else on the CU to hide them.
+#ifndef LVDGS_BWD_ID_AHEAD
+#define LVDGS_BWD_ID_AHEAD 1   // A/B builds: 0 = the id is loaded in the round that stages it
+#endif
+// the ids of the first round staged (the last of the list)
+__device__ __forceinline__ uint32_t stage_first_ids(const BlendParams &p, const uint32_t list_start, const int tid, const int rounds, const int todo) {
+    uint32_t id_ahead = 0u;
+    if (LVDGS_BWD_ID_AHEAD && rounds > 0 && tid < min(BR, todo - (rounds - 1) * BR)) id_ahead = p.point_list[list_start + (rounds - 1) * BR + tid];
+    return id_ahead;
+}
+// the round's entries (base ... base + cnt of the list) into sh.a / b / c / craw / reach / slot, and its barrier.  (The request for the
+// ids of the round after it is one statement of the rounds loop: inside a function of its own, whichever way it was handed `r` and
+// id_ahead, the compiler put the loop's scalar tests together differently -- profiles/blend_stages/README.md.)
+template <class Shared>
+__device__ __forceinline__ void stage_round(const BlendParams &p, Shared &sh, const TileGeom &g, const uint32_t list_start, const int base, const int cnt, const uint32_t id_ahead) {
+    const int tid = g.tid;
+    if (tid < cnt) {
+        const uint32_t id = LVDGS_BWD_ID_AHEAD ? id_ahead : p.point_list[list_start + base + tid];
+        const float4 *r4 = reinterpret_cast<const float4 *>(p.rec + (size_t)id * REC_FLOATS);
+        const float4 r0 = r4[0], r1 = r4[1], r2 = r4[2];
+        sh.a[tid] = r0;
+        sh.b[tid] = make_float4(-0.5f * LOG2E * r1.x, r1.y, r2.y, -0.5f * LOG2E * r0.z);
+        sh.c[tid] = make_float4(r1.z, r1.w, r2.x, -LOG2E * r0.w);
+        sh.craw[tid] = r1.x;
+        const QuadBound qb = quad_prepare(r0.z, r0.w, r1.x, r1.y);
+        sh.reach[tid] = make_float2(qb.inv_c, qb.bound);
+        sh.slot[tid] = pair_slot(p, id, g.tx, g.ty);
+    }
+    __syncthreads();
+}
+
+// ---- quadrant test: which of the round's staged entries (lane -> entry) can touch this wave's quadrant, among those some
+// pixel of the wave composited (below wave_last) ----
+template <class Shared>
+__device__ __forceinline__ uint64_t quadrant_survivors(const Shared &sh, const TileGeom &g, const int base, const int cnt, const int wave_last) {
+    const int lane = g.lane;
+    bool keep = false;
+    if (lane < cnt && base + lane < wave_last) {
+        const float4 A = sh.a[lane];
+        const float2 Q = sh.reach[lane];
+        keep = reaches_rect_prepared(A.x, A.y, A.z, A.w, sh.craw[lane], __builtin_amdgcn_rcpf(A.z), Q.x, Q.y, g.rx0, g.ry0, g.rx1, g.ry1);
+    }
+    return __ballot(keep);
+}
+
+// ---- flush: thread -> staged entry; the fixed-order sum over the four waves' slots and the pair's record ----
+template <bool POSE_ONLY, bool DEPTH_GRAD>
+__device__ __forceinline__ void bwd_flush(const BlendParams &p, const Bwd3Shared<POSE_ONLY, DEPTH_GRAD> &sh, const int tid, const int cnt) {
+    constexpr int ACC = Bwd3Shared<POSE_ONLY, DEPTH_GRAD>::ACC;
+    if (tid < cnt) {
+        float acc[ACC];
+#pragma unroll
+        for (int k = 0; k < ACC; k++) acc[k] = 0.f;
+        const unsigned long long bit = 1ull << tid;
+#pragma unroll
+        for (int w = 0; w < 4; w++)
+            if (sh.mask[w] & bit) {
+                const float2 *o = reinterpret_cast<const float2 *>(&sh.acc[w][tid * ACC]);
+#pragma unroll
+                for (int k = 0; k < ACC / 2; k++) { const float2 t = o[k]; acc[2 * k] += t.x; acc[2 * k + 1] += t.y; }
+            }
+        // acc: Sx Sy Sxx Sxy Syy Su C0 C1 C2 CD (sums of u, not yet of h = opacity * u); POSE_ONLY: Sx Sy Sxx Sxy Syy CD
+        const float4 A = sh.a[tid];
+        const float op = sh.b[tid].y;
+        const float sx = op * acc[0], sy = op * acc[1];
+        // the pair's record: ten floats, 40 bytes (8-byte aligned: five 8-byte stores), and its "written" flag;
+        // POSE_ONLY: d/d(mean, conic, view depth) alone, six floats at the same 8-byte alignment
+        p.pair_valid[sh.slot[tid]] = 1;
+        float2 *dst = reinterpret_cast<float2 *>(p.pair_grads + (size_t)sh.slot[tid] * (POSE_ONLY ? PAIR_FLOATS_POSE : PAIR_FLOATS));
+        dst[0] = make_float2(-fmaf(A.z, sx, A.w * sy), -fmaf(sh.craw[tid], sy, A.w * sx));
+        dst[1] = make_float2(-0.5f * (op * acc[2]), -(op * acc[3]));
+        dst[2] = make_float2(-0.5f * (op * acc[4]), acc[5]);
+        if constexpr (!POSE_ONLY) {
+            dst[3] = make_float2(acc[6], acc[7]);
+            dst[4] = make_float2(acc[8], acc[9]);
+        }
+    }
+}
+
+// ---- splat pass, the steps: the ten sums a lane keeps for its slot, and what a step reads besides its (u, w) ----
+struct SplatSums { float Sx, Sy, Sxx, Sxy, Syy, Su, C0, C1, C2, CD; };
+struct SplatLane { float2 Aj; float pxf, pyf, gC0, gC1, gC2, gD; };   // the slot's mean; this lane's pixel and its gradients (the step takes its pixel's by DPP)
+// step S: the lane's slot against the pixel of lane (col - S) mod 16 of its row
+template <int S, bool POSE_ONLY, bool DEPTH_GRAD>
+__device__ __forceinline__ SplatSums splat_step(SplatSums a, const float2 uw, const SplatLane l) {
+    const float dx = sub_rotated<S>(l.Aj.x, l.pxf), dy = sub_rotated<S>(l.Aj.y, l.pyf);
+    const float t1 = uw.x * dx, t2 = uw.x * dy;
+    a.Sx += t1; a.Sy += t2;
+    a.Sxx = fmaf(t1, dx, a.Sxx); a.Sxy = fmaf(t1, dy, a.Sxy); a.Syy = fmaf(t2, dy, a.Syy);
+    if constexpr (!POSE_ONLY) {
+        a.Su += uw.x;
+        a.C0 = fma_rotated<S>(l.gC0, uw.y, a.C0); a.C1 = fma_rotated<S>(l.gC1, uw.y, a.C1);
+        a.C2 = fma_rotated<S>(l.gC2, uw.y, a.C2);
+    }
+    if constexpr (DEPTH_GRAD) a.CD = fma_rotated<S>(l.gD, uw.y, a.CD);
+    return a;
+}
+// steps 0 .. NB - 1 in order
+template <bool POSE_ONLY, bool DEPTH_GRAD, int NB, int... S>
+__device__ __forceinline__ SplatSums splat_steps(const float2 (&uw)[NB], const SplatLane l, std::integer_sequence<int, S...>) {
+    SplatSums a{};
+    ((a = splat_step<S, POSE_ONLY, DEPTH_GRAD>(a, uw[S], l)), ...);
+    return a;
+}
+
+// The backward pass of one tile: geometry, the pixel's gradient, the depth of the walk, then per round of BR entries, back to
+// front: stage / quadrant test / (pixel batch, splat batch)* / flush.
 template <int LOSS, bool DEPTH_GRAD, bool POSE_ONLY>
 __device__ __forceinline__ void blend_bwd3_body(const BlendParams &p, Bwd3Shared<POSE_ONLY, DEPTH_GRAD> &sh) {
     using Shared = Bwd3Shared<POSE_ONLY, DEPTH_GRAD>;
@@ -436,32 +639,18 @@ __device__ __forceinline__ void blend_bwd3_body(const BlendParams &p, Bwd3Shared
     constexpr bool U_ONLY = POSE_ONLY && !DEPTH_GRAD;   // the matrix holds u alone
     using MT = typename Shared::MT;
 
-#ifdef LVDGS_DIAG_REPEAT   // diagnostic build: the grid repeated $LVDGS_DIAG_REPEAT times (what a launch over several views of this size would cost)
-    const int diag_b = (int)blockIdx.x % p.num_tiles;
-#define blockIdx_x_ diag_b
-#else
-#define blockIdx_x_ ((int)blockIdx.x)
-#endif
-    const int tile = (p.tile_order && *p.order_valid) ? (int)p.tile_order[order_slot_of_workgroup(blockIdx_x_, p.num_tiles)] : p.tile_base + tile_of_workgroup(blockIdx_x_, p.num_tiles);
-#undef blockIdx_x_
-    const int tx = tile % p.gx, ty = tile / p.gx;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int qx0 = tx * TILE + (wave & 1) * 8, qy0 = ty * TILE + (wave >> 1) * 8;
-    const int px = qx0 + (lane & 7), py = qy0 + (lane >> 3);
-    const bool inside = px < p.W && py < p.H;
-    const float pxf = (float)px, pyf = (float)py;
-    const float rx0 = (float)qx0, ry0 = (float)qy0, rx1 = (float)(qx0 + 7), ry1 = (float)(qy0 + 7);
-    const size_t pix = (size_t)py * p.W + px, P = (size_t)p.W * p.H;
+    const int tile = tile_of_this_workgroup(p);
+    const TileGeom g(p, tile);
+    const int tid = g.tid, lane = g.lane, wave = g.wave;
+    const bool inside = g.inside;
+    const float pxf = g.pxf, pyf = g.pyf;
+    const size_t pix = (size_t)g.py * p.W + g.px, P = (size_t)p.W * p.H;
 
-#ifdef LVDGS_DIAG_PHASES
-    const unsigned long long wg_t0 = __builtin_amdgcn_s_memrealtime();
-    if (tid == 0 && blockIdx.x < 8192) g_wg_surv[blockIdx.x] = 0u;
-    unsigned long long ph_t = __builtin_amdgcn_s_memtime(), ph[7] = {0, 0, 0, 0, 0, 0, 0};
-    auto ph_mark = [&](int k) { const unsigned long long n = __builtin_amdgcn_s_memtime(); ph[k] += n - ph_t; ph_t = n; };
-#endif
+    BwdDiag diag;
     const uint2 range = p.ranges[tile];
     const float T_final = inside ? p.final_T[pix] : 0.f;
     const uint32_t my_last = inside ? p.n_contrib[pix] : 0u;
+    // ---- pixel gradient: dL/d(colour, depth, opacity) of this thread's pixel, by LOSS ----
     float gC0 = 0.f, gC1 = 0.f, gC2 = 0.f, gD = 0.f, gO = 0.f;
     const bool fused_loss = LOSS == LOSS_FUSED || (LOSS == LOSS_PER_VIEW && p.loss_mode == LOSS_FUSED);   // (uniform over the launch / the view)
     if (LOSS == LOSS_MASKED || (LOSS == LOSS_PER_VIEW && !fused_loss)) {
@@ -533,64 +722,25 @@ __device__ __forceinline__ void blend_bwd3_body(const BlendParams &p, Bwd3Shared
     MT *const Mmine = &sh.M[wave][0][lane];
 
     const int rounds = (todo + BR - 1) / BR;
-#ifdef LVDGS_DIAG_FILL
-    unsigned diag_surv = 0, diag_batches = 0, diag_full = 0, diag_rounds = 0;
-#endif
-#ifdef LVDGS_DIAG_PHASES
-    ph_mark(0);
-#endif
-    // The id a staging thread gathers its record with is requested a round AHEAD (round 5): a round's staging is two dependent trips to
-    // memory -- the id, then the record -- in front of a barrier the whole workgroup waits at, and on a small grid the kernel lasts as
-    // long as its longest list's chain of rounds (a KITTI frame's heaviest tile: 14 rounds), with nobody else on the CU to hide them.
-#ifndef LVDGS_BWD_ID_AHEAD
-#define LVDGS_BWD_ID_AHEAD 1   // A/B builds: 0 = the id is loaded in the round that stages it
-#endif
-    uint32_t id_ahead = 0u;
-    if (LVDGS_BWD_ID_AHEAD && rounds > 0 && tid < min(BR, todo - (rounds - 1) * BR)) id_ahead = p.point_list[range.x + (rounds - 1) * BR + tid];
+    diag.mark(BwdDiag::PROLOGUE);
+    uint32_t id_ahead = stage_first_ids(p, range.x, tid, rounds, todo);
     for (int r = rounds - 1; r >= 0; r--) {
         const int base = r * BR;
         const int cnt = min(BR, todo - base);
-        if (tid < cnt) {
-            const uint32_t id = LVDGS_BWD_ID_AHEAD ? id_ahead : p.point_list[range.x + base + tid];
-            const float4 *r4 = reinterpret_cast<const float4 *>(p.rec + (size_t)id * REC_FLOATS);
-            const float4 r0 = r4[0], r1 = r4[1], r2 = r4[2];
-            sh.a[tid] = r0;
-            sh.b[tid] = make_float4(-0.5f * LOG2E * r1.x, r1.y, r2.y, -0.5f * LOG2E * r0.z);
-            sh.c[tid] = make_float4(r1.z, r1.w, r2.x, -LOG2E * r0.w);
-            sh.craw[tid] = r1.x;
-            const QuadBound qb = quad_prepare(r0.z, r0.w, r1.x, r1.y);
-            sh.reach[tid] = make_float2(qb.inv_c, qb.bound);
-            sh.slot[tid] = pair_slot(p, id, tx, ty);
-        }
-        __syncthreads();
+        stage_round(p, sh, g, range.x, base, cnt, id_ahead);
         if (LVDGS_BWD_ID_AHEAD && r > 0 && tid < BR) id_ahead = p.point_list[range.x + base - BR + tid];   // (every round but the last listed is full)
-#ifdef LVDGS_DIAG_PHASES
-        ph_mark(1); ph[5]++;
-#endif
+        diag.mark(BwdDiag::STAGING); diag.round_staged();
         uint64_t wrote = 0ull;
         if (base < wave_last) {   // (a wave none of whose pixels got this far has nothing to test: on opaque surfaces two thirds of the (wave, round) pairs)
-            bool keep = false;
-            if (lane < cnt && base + lane < wave_last) {
-                const float4 A = sh.a[lane];
-                const float2 Q = sh.reach[lane];
-                keep = reaches_rect_prepared(A.x, A.y, A.z, A.w, sh.craw[lane], __builtin_amdgcn_rcpf(A.z), Q.x, Q.y, rx0, ry0, rx1, ry1);
-            }
-            uint64_t live = __ballot(keep);
+            uint64_t live = quadrant_survivors(sh, g, base, cnt, wave_last);
             const uint32_t rel_last = my_last > (uint32_t)base ? my_last - (uint32_t)base : 0u;  // entries below this position composited
             wrote = live;
-#ifdef LVDGS_DIAG_PHASES
-            ph[6] += (unsigned long long)__popcll(live);
-#endif
-#ifdef LVDGS_DIAG_FILL
-            diag_surv += (unsigned)__popcll(live); diag_rounds += live ? 1u : 0u;
-#endif
+            diag.survivors(live);
             while (live) {
                 // ---------------- pixel pass: the next NB survivors, back to front ----------------
                 const uint64_t before = live;
                 const int nb = min(NB, (int)__popcll(live));
-#ifdef LVDGS_DIAG_FILL
-                diag_batches++; diag_full += nb == NB ? 1u : 0u;
-#endif
+                diag.batch(nb == NB);
                 struct Rec { float4 A, B, Cc; };
                 auto next_entry = [&]() {
                     const int j = 63 - __builtin_clzll(live);
@@ -655,7 +805,6 @@ __device__ __forceinline__ void blend_bwd3_body(const BlendParams &p, Bwd3Shared
                 const bool valid = my_slot < nb;
                 const int jj = valid ? (int)sh.bj[wave][my_slot] : 0;
                 const float2 Aj = *reinterpret_cast<const float2 *>(&sh.a[jj]);
-                float Sx = 0.f, Sy = 0.f, Sxx = 0.f, Sxy = 0.f, Syy = 0.f, Su = 0.f, C0 = 0.f, C1 = 0.f, C2 = 0.f, CD = 0.f;
                 // all eight (u, w) reads go out first: their addresses are known, and at 5 waves per SIMD a read issued
                 // one step ahead is still on its way when it is needed
                 float2 uw8[NB];
@@ -664,23 +813,8 @@ __device__ __forceinline__ void blend_bwd3_body(const BlendParams &p, Bwd3Shared
                     if constexpr (U_ONLY) uw8[s8] = make_float2(Mrow[(col - s8) & 15], 0.f);
                     else uw8[s8] = Mrow[(col - s8) & 15];
                 }
-#define LVDGS_SPLAT_STEP(S)                                                                          \
-                {                                                                                    \
-                    const float2 uw = uw8[S];                                                        \
-                    const float dx = sub_rotated<S>(Aj.x, pxf), dy = sub_rotated<S>(Aj.y, pyf);      \
-                    const float t1 = uw.x * dx, t2 = uw.x * dy;                                      \
-                    Sx += t1; Sy += t2;                                                              \
-                    Sxx = fmaf(t1, dx, Sxx); Sxy = fmaf(t1, dy, Sxy); Syy = fmaf(t2, dy, Syy);       \
-                    if constexpr (!POSE_ONLY) {                                                      \
-                        Su += uw.x;                                                                  \
-                        C0 = fma_rotated<S>(gC0, uw.y, C0); C1 = fma_rotated<S>(gC1, uw.y, C1);      \
-                        C2 = fma_rotated<S>(gC2, uw.y, C2);                                          \
-                    }                                                                                \
-                    if constexpr (DEPTH_GRAD) CD = fma_rotated<S>(gD, uw.y, CD);                     \
-                }
-                LVDGS_SPLAT_STEP(0) LVDGS_SPLAT_STEP(1) LVDGS_SPLAT_STEP(2) LVDGS_SPLAT_STEP(3)
-                if constexpr (NB == 8) { LVDGS_SPLAT_STEP(NB - 4) LVDGS_SPLAT_STEP(NB - 3) LVDGS_SPLAT_STEP(NB - 2) LVDGS_SPLAT_STEP(NB - 1) }
-#undef LVDGS_SPLAT_STEP
+                const SplatSums sums = splat_steps<POSE_ONLY, DEPTH_GRAD>(uw8, SplatLane{Aj, pxf, pyf, gC0, gC1, gC2, gD}, std::make_integer_sequence<int, NB>{});
+                const float Sx = sums.Sx, Sy = sums.Sy, Sxx = sums.Sxx, Sxy = sums.Sxy, Syy = sums.Syy, Su = sums.Su, C0 = sums.C0, C1 = sums.C1, C2 = sums.C2, CD = sums.CD;
                 // fold the 8 partial sums of every slot: rows first (two pairwise folds, ten registers -> three) ...
                 float q0 = fold16(fold32(Sx, Sy), fold32(Sxx, Sxy));   // rows: Sx Sxx Sy Sxy
                 // (POSE_ONLY: Syy and CD take the places -- and so the summation trees -- they have in the full form: the
@@ -709,67 +843,14 @@ __device__ __forceinline__ void blend_bwd3_body(const BlendParams &p, Bwd3Shared
             }
         }
         if (lane == 0) sh.mask[wave] = wrote;
-#ifdef LVDGS_DIAG_PHASES
-        ph_mark(2);
-#endif
+        diag.mark(BwdDiag::BATCHES);
         __syncthreads();
-#ifdef LVDGS_DIAG_PHASES
-        ph_mark(3);
-#endif
-        if (tid < cnt) {
-            float acc[ACC];
-#pragma unroll
-            for (int k = 0; k < ACC; k++) acc[k] = 0.f;
-            const unsigned long long bit = 1ull << tid;
-#pragma unroll
-            for (int w = 0; w < 4; w++)
-                if (sh.mask[w] & bit) {
-                    const float2 *o = reinterpret_cast<const float2 *>(&sh.acc[w][tid * ACC]);
-#pragma unroll
-                    for (int k = 0; k < ACC / 2; k++) { const float2 t = o[k]; acc[2 * k] += t.x; acc[2 * k + 1] += t.y; }
-                }
-            // acc: Sx Sy Sxx Sxy Syy Su C0 C1 C2 CD (sums of u, not yet of h = opacity * u); POSE_ONLY: Sx Sy Sxx Sxy Syy CD
-            const float4 A = sh.a[tid];
-            const float op = sh.b[tid].y;
-            const float sx = op * acc[0], sy = op * acc[1];
-            // the pair's record: ten floats, 40 bytes (8-byte aligned: five 8-byte stores), and its "written" flag;
-            // POSE_ONLY: d/d(mean, conic, view depth) alone, six floats at the same 8-byte alignment
-            p.pair_valid[sh.slot[tid]] = 1;
-            float2 *dst = reinterpret_cast<float2 *>(p.pair_grads + (size_t)sh.slot[tid] * (POSE_ONLY ? PAIR_FLOATS_POSE : PAIR_FLOATS));
-            dst[0] = make_float2(-fmaf(A.z, sx, A.w * sy), -fmaf(sh.craw[tid], sy, A.w * sx));
-            dst[1] = make_float2(-0.5f * (op * acc[2]), -(op * acc[3]));
-            dst[2] = make_float2(-0.5f * (op * acc[4]), acc[5]);
-            if constexpr (!POSE_ONLY) {
-                dst[3] = make_float2(acc[6], acc[7]);
-                dst[4] = make_float2(acc[8], acc[9]);
-            }
-        }
+        diag.mark(BwdDiag::WAIT);
+        bwd_flush(p, sh, tid, cnt);
         __syncthreads();
-#ifdef LVDGS_DIAG_PHASES
-        ph_mark(4);
-#endif
+        diag.mark(BwdDiag::FLUSH);
     }
-#ifdef LVDGS_DIAG_PHASES
-    if (blockIdx.x == 0 && tid == 0) {
-        for (int k = 0; k < 7; k++) atomicAdd(&g_phase_diag[k], ph[k]);
-        atomicAdd(&g_phase_diag[7], 1ull);
-    }
-    if (blockIdx.x < 8192) {
-        if (lane == 0) atomicAdd(&g_wg_surv[blockIdx.x], (unsigned)ph[6]);
-        if (tid == 0) {
-            const unsigned hw = __builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11)), xcc = __builtin_amdgcn_s_getreg((20) | (0 << 6) | (31 << 11));
-            g_wg_diag[blockIdx.x][0] = wg_t0; g_wg_diag[blockIdx.x][1] = __builtin_amdgcn_s_memrealtime();
-            g_wg_diag[blockIdx.x][2] = ((unsigned long long)(range.y - range.x) << 32) | (unsigned)tile;
-            g_wg_diag[blockIdx.x][3] = ((unsigned long long)xcc << 32) | hw;
-        }
-    }
-#endif
-#ifdef LVDGS_DIAG_FILL
-    if (lane == 0) {
-        atomicAdd(&g_fill_diag[0], (unsigned long long)diag_surv); atomicAdd(&g_fill_diag[1], (unsigned long long)diag_batches);
-        atomicAdd(&g_fill_diag[2], (unsigned long long)diag_full); atomicAdd(&g_fill_diag[3], (unsigned long long)diag_rounds);
-    }
-#endif
+    diag.publish(tile, range.y - range.x);
 }
 
 template <int LOSS, bool DEPTH_GRAD = true, bool POSE_ONLY = false>
@@ -847,6 +928,20 @@ auto blend_bwd3_for(bool depth, bool pose_only) {
                      : (depth ? blend_bwd3_kernel<LOSS, true> : blend_bwd3_kernel<LOSS, false>);
 }
 
+// What every backward launcher adds to make_params: where the pairs' records and their "written" flags go.
+BlendParams make_bwd_params(const lvdgs_args &a, const GeomView &g, const BinView &b, const ImageView &im, const BwdScratch &w) {
+    BlendParams p = make_params(a, g, b, im);
+    p.pair_grads = w.pair_grads; p.pair_valid = b.pair_valid;
+    return p;
+}
+
+#ifndef LVDGS_BWD_DEPTH_ALWAYS
+#define LVDGS_BWD_DEPTH_ALWAYS 0   // A/B builds: 1 keeps the depth-gradient terms whatever the loss
+#endif
+// Does this fused loss have a depth term (else the DEPTH_GRAD = false kernels run)?
+bool loss_has_depth(const LossParams &loss) { return LVDGS_BWD_DEPTH_ALWAYS || (loss.depth && loss.gt_depth && loss.w_d != 0.f); }
+bool pose_only_call(const lvdgs_args &a) { return (a.flags & LVDGS_FLAG_POSE_ONLY) != 0; }
+
 }  // namespace
 
 int launch_blend_fwd(const lvdgs_args &a, const GeomView &g, const BinView &b, const ImageView &im, bool deep_lists, hipStream_t s) {
@@ -856,28 +951,23 @@ int launch_blend_fwd(const lvdgs_args &a, const GeomView &g, const BinView &b, c
     return launch("blend_fwd", a.debug, s, deep_lists ? blend_fwd2_deep_kernel : blend_fwd2_kernel, dim3(grid), dim3(256), 0, p);
 }
 
-#ifndef LVDGS_BWD_DEPTH_ALWAYS
-#define LVDGS_BWD_DEPTH_ALWAYS 0   // A/B builds: 1 keeps the depth-gradient terms whatever the loss
-#endif
 int launch_blend_bwd(const lvdgs_args &a, const GeomView &g, const BinView &b, const ImageView &im, const BwdScratch &w,
                      hipStream_t s) {
-    BlendParams p = make_params(a, g, b, im);
-    p.pair_grads = w.pair_grads; p.pair_valid = b.pair_valid;
+    BlendParams p = make_bwd_params(a, g, b, im, w);
     if (p.num_tiles == 0) return LVDGS_OK;
     const int grid = blend_grid(p);
-    const bool depth = LVDGS_BWD_DEPTH_ALWAYS || p.dL_ddepth, pose_only = (a.flags & LVDGS_FLAG_POSE_ONLY) != 0;
+    const bool depth = LVDGS_BWD_DEPTH_ALWAYS || p.dL_ddepth, pose_only = pose_only_call(a);
     return launch("blend_bwd", a.debug, s, blend_bwd3_for<LOSS_IMAGES>(depth, pose_only), dim3(grid), dim3(256), 0, p);
 }
 
 int launch_blend_bwd_fused_loss(const lvdgs_args &a, const GeomView &g, const BinView &b, const ImageView &im, const BwdScratch &w,
                                 const LossParams &loss, int propagate_opacity, hipStream_t s) {
-    BlendParams p = make_params(a, g, b, im);
-    p.pair_grads = w.pair_grads; p.pair_valid = b.pair_valid;
+    BlendParams p = make_bwd_params(a, g, b, im, w);
     p.loss = loss;
     p.loss_propagate_opacity = propagate_opacity;
     if (p.num_tiles == 0) return LVDGS_OK;
     const int grid = blend_grid(p);
-    const bool depth = LVDGS_BWD_DEPTH_ALWAYS || (loss.depth && loss.gt_depth && loss.w_d != 0.f), pose_only = (a.flags & LVDGS_FLAG_POSE_ONLY) != 0;
+    const bool depth = loss_has_depth(loss), pose_only = pose_only_call(a);
     return launch("blend_bwd", a.debug, s, blend_bwd3_for<LOSS_FUSED>(depth, pose_only), dim3(grid), dim3(256), 0, p);
 }
 
@@ -892,8 +982,7 @@ static void set_masked_loss(BlendParams &p, const MaskedLossView &m) {
 
 int launch_blend_bwd_masked_loss(const lvdgs_args &a, const GeomView &g, const BinView &b, const ImageView &im, const BwdScratch &w,
                                  const MaskedLossView &m, hipStream_t s) {
-    BlendParams p = make_params(a, g, b, im);
-    p.pair_grads = w.pair_grads; p.pair_valid = b.pair_valid;
+    BlendParams p = make_bwd_params(a, g, b, im, w);
     set_masked_loss(p, m);
     if (p.num_tiles == 0) return LVDGS_OK;
     // (the masked loss has no pose-only form: two instantiations, not blend_bwd3_for's four)
@@ -906,13 +995,12 @@ int launch_blend_bwd_masked_loss(const lvdgs_args &a, const GeomView &g, const B
 int launch_blend_fwd_bwd_fused_loss(const lvdgs_args &a, const GeomView &g, const BinView &b, const ImageView &im, const BwdScratch &w,
                                     const LossParams &loss, int propagate_opacity, bool deep_lists, const uint32_t *pair_total, uint32_t pair_capacity,
                                     const uint32_t *pair_total_super, hipStream_t s) {
-    BlendParams p = make_params(a, g, b, im);
-    p.pair_grads = w.pair_grads; p.pair_valid = b.pair_valid;
+    BlendParams p = make_bwd_params(a, g, b, im, w);
     p.pair_total = pair_total; p.pair_total_super = pair_total_super; p.pair_capacity = pair_capacity;
     p.loss = loss; p.loss_mode = LOSS_FUSED;
     p.loss_propagate_opacity = propagate_opacity;
     if (p.num_tiles == 0) return LVDGS_OK;
-    const bool depth = LVDGS_BWD_DEPTH_ALWAYS || (loss.depth && loss.gt_depth && loss.w_d != 0.f), pose_only = (a.flags & LVDGS_FLAG_POSE_ONLY) != 0;
+    const bool depth = loss_has_depth(loss), pose_only = pose_only_call(a);
     const auto deep_or_not = [&](auto deep, auto shallow) { return deep_lists ? deep : shallow; };   // (kernel pointers of one type)
     const auto kernel = pose_only ? (depth ? deep_or_not(blend_fwd_bwd_kernel<true, true, true>, blend_fwd_bwd_kernel<true, true, false>)
                                            : deep_or_not(blend_fwd_bwd_kernel<false, true, true>, blend_fwd_bwd_kernel<false, true, false>))
@@ -945,8 +1033,7 @@ int launch_blend_bwd_fused_loss_batch(const lvdgs_args *const *a, const GeomView
         for (int k = 0; k < m; k++) {
             const int v = first + k;
             BlendParams &p = batch.v[k];
-            p = make_params(*a[v], g[v], b[v], im[v]);
-            p.pair_grads = w[v].pair_grads; p.pair_valid = b[v].pair_valid;
+            p = make_bwd_params(*a[v], g[v], b[v], im[v], w[v]);
             if (masked && masked[v]) {
                 set_masked_loss(p, *masked[v]);
                 depth = depth || LVDGS_BWD_DEPTH_ALWAYS || masked[v]->gt_depth;
@@ -955,11 +1042,11 @@ int launch_blend_bwd_fused_loss_batch(const lvdgs_args *const *a, const GeomView
                 p.loss = loss[v];
                 p.loss_mode = LOSS_FUSED;
                 p.loss_propagate_opacity = propagate_opacity;
-                depth = depth || LVDGS_BWD_DEPTH_ALWAYS || (loss[v].depth && loss[v].gt_depth && loss[v].w_d != 0.f);
+                depth = depth || loss_has_depth(loss[v]);
             }
         }
         if (batch.v[0].num_tiles == 0) continue;
-        const bool pose_only = (a[first]->flags & LVDGS_FLAG_POSE_ONLY) != 0;   // (only where no view has the masked loss)
+        const bool pose_only = pose_only_call(*a[first]);   // (only where no view has the masked loss)
         const auto kernel = n_masked == m ? (depth ? blend_bwd3_batch_kernel<LOSS_MASKED, true, false> : blend_bwd3_batch_kernel<LOSS_MASKED, false, false>)
                             : n_masked    ? (depth ? blend_bwd3_batch_kernel<LOSS_PER_VIEW, true, false> : blend_bwd3_batch_kernel<LOSS_PER_VIEW, false, false>)
                             : pose_only   ? (depth ? blend_bwd3_batch_kernel<LOSS_FUSED, true, true> : blend_bwd3_batch_kernel<LOSS_FUSED, false, true>)
@@ -971,30 +1058,3 @@ int launch_blend_bwd_fused_loss_batch(const lvdgs_args *const *a, const GeomView
 
 }  // namespace lvdgs
 
-#ifdef LVDGS_DIAG_PHASES
-extern "C" int lvdgs_diag_phases(unsigned long long *out8, int reset) {
-    if (out8 && hipMemcpyFromSymbol(out8, HIP_SYMBOL(lvdgs::g_phase_diag), 8 * sizeof(unsigned long long)) != hipSuccess) return LVDGS_E_HIP;
-    if (reset) {
-        const unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(lvdgs::g_phase_diag), z, sizeof(z)) != hipSuccess) return LVDGS_E_HIP;
-    }
-    return LVDGS_OK;
-}
-#endif
-#ifdef LVDGS_DIAG_PHASES
-extern "C" int lvdgs_diag_workgroups(unsigned long long *out_8192x4, unsigned *surv_8192) {
-    if (hipMemcpyFromSymbol(out_8192x4, HIP_SYMBOL(lvdgs::g_wg_diag), 8192 * 4 * sizeof(unsigned long long)) != hipSuccess) return LVDGS_E_HIP;
-    if (hipMemcpyFromSymbol(surv_8192, HIP_SYMBOL(lvdgs::g_wg_surv), 8192 * sizeof(unsigned)) != hipSuccess) return LVDGS_E_HIP;
-    return LVDGS_OK;
-}
-#endif
-#ifdef LVDGS_DIAG_FILL
-extern "C" int lvdgs_diag_fill(unsigned long long *out4, int reset) {
-    if (out4 && hipMemcpyFromSymbol(out4, HIP_SYMBOL(lvdgs::g_fill_diag), 4 * sizeof(unsigned long long)) != hipSuccess) return LVDGS_E_HIP;
-    if (reset) {
-        const unsigned long long z[4] = {0ull, 0ull, 0ull, 0ull};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(lvdgs::g_fill_diag), z, sizeof(z)) != hipSuccess) return LVDGS_E_HIP;
-    }
-    return LVDGS_OK;
-}
-#endif

@@ -13,23 +13,10 @@ Regions:  pixel pass, straight-line  = the code between two labels that holds ei
                                        entries per execution and wave; its one reciprocal is 1/a);
           staging                    = the code with v_log_f32 (quad_prepare: once per round of 64 entries, the first wave alone);
           everything else            = prologue (fused loss), flush, loop control."""
-import os, re, subprocess, sys, collections
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "lvd_gs-slam_amd", "csrc", "blend.hip")
-asm = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-slp-vectorize",
-                      "-S", "--cuda-device-only", SRC, "-o", "-"], capture_output=True, text=True, check=True).stdout
-
-KINDS = ["valu", "valu_trans", "valu_dpp", "valu_xlane", "salu", "lds", "vmem", "branch", "wait_nop"]
-def kind(op):
-    if op.startswith(("s_waitcnt", "s_nop", "s_barrier")): return "wait_nop"
-    if op.startswith(("s_cbranch", "s_branch", "s_endpgm", "s_setpc", "s_swappc")): return "branch"
-    if op.startswith("s_"): return "salu"
-    if op.startswith("ds_"): return "lds"
-    if op.startswith(("global_", "buffer_", "flat_", "scratch_")): return "vmem"
-    if op.startswith(("v_exp", "v_rcp", "v_log", "v_sqrt", "v_rsq", "v_sin", "v_cos")): return "valu_trans"
-    if op.startswith(("v_permlane", "v_readlane", "v_writelane", "v_readfirstlane")): return "valu_xlane"
-    if op.startswith("v_"): return "valu"
-    return None
+import os, re, sys, collections
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from kernel_asm import ROOT, KINDS, compile_asm, line_kind
+asm = compile_asm("blend.hip")
 
 def kernel_text(mangled_part):
     m = re.search(r"^(_ZN5lvdgs12_GLOBAL__N_1" + mangled_part + r"\w*):[^\n]*\n(.*?)\n\s*s_endpgm", asm, re.S | re.M)
@@ -43,12 +30,7 @@ def budget(name_re, title):
         if not t or t.startswith(";"): continue
         if re.match(r"^\.LBB\d+_\d+:", t):
             segs.append(cur); cur = []; continue
-        op = t.split()[0]
-        if op.startswith("."): continue
-        k = kind(op)
-        if k is None: continue
-        dpp = "row_ror" in t or "row_shr" in t or "row_bcast" in t or "quad_perm" in t or "row_mirror" in t or "row_half_mirror" in t or "_dpp" in op
-        cur.append(("valu_dpp" if (k == "valu" and dpp) else k, op))
+        if (ko := line_kind(t)): cur.append(ko)
     segs.append(cur)
     regions = collections.OrderedDict((r, collections.Counter()) for r in ("pixel pass, straight-line batch of 8", "pixel pass, rolled (per entry)",
                                                                           "splat pass (per batch)", "quadrant test (per 64 staged entries and wave)",
